@@ -5,13 +5,15 @@ A "step" = one pass of the hot path over one batch of synthetic input already re
 encode -> z -> decode of IAN_simple at batch 64 (BASELINE.json configs[1]).  `value` = whole-job
 64x64 reconstructions per second over all ranks (replicas: the path has no data-path collective).
 
-Extra fields in the same JSON line:
+A plain run sets up, warms up, times the --steps steps and prints the headline line (value, ms_per_step, step_ms).
+--dump-outputs DIR also writes what the last timed step computed (DIR/reconstruction.npy, float32, rank 0's seeded inputs).
+--full adds every secondary measurement below to the same JSON line:
   roofline      dominant kernel (tapgemm, fp32 MFMA): algorithmic FLOP per launch / mean launch duration,
                 measured with HIP events recorded on the launch stream inside libian (ian_profile_*),
                 in a separate profiled pass of the same workload (event records perturb the timed pass);
   cpu_baseline  the torch-CPU twin of the oracle ("port": the reference's Theano path cannot run here),
                 rank 0, N=1 only, bounded sample;
-  step_ms       p50/p95 of the K timed steps (device time between consecutive steps);
+  step_ms       p50/p95 of the K timed steps (device time between consecutive steps; plain runs too);
   full_ian      the same measurement for BASELINE.json configs[2]: full IAN, batch 256 per GPU, with its own roofline;
   edit_step     p50/p95 latency of one NPE latent-brush step (BASELINE.json configs[3]): imgradRGB +
                 Z update (reference gradient descent, NPE.py:199-209) + sample_at, batch 1.
@@ -408,6 +410,21 @@ def _finalize_secondary(result):
         result["roofline"]["secondary"] = sec
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy in float32, DUMP_LIMIT_BYTES in all.  An array over its share keeps its leading
+    entries along axis 0 (the same ones at every run: the inputs are seeded)."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float32)
+        if a.nbytes > share:
+            a = a[:max(1, share // max(1, a[:1].nbytes))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -470,6 +487,11 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--arch", default="IAN_simple", choices=["IAN_simple", "IAN"])
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements: roofline (profiled pass), box probe, split-bf16 "
+                                                       "secondary, edit_step, b1_recon, cpu_baseline, full_ian, train_step (the --no-* options "
+                                                       "below drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed as "
+                                                                        "DIR/<name>.npy (float32; rank 0)")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default 64 for IAN_simple, 256 for IAN)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-edit", action="store_true")
@@ -485,6 +507,8 @@ def main(argv=None):
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / aggregation plumbing only: no GPU work, value null "
                                                            "(tests/test_comm.py runs this with 2 gloo ranks on CPU)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.train_child:
         return train_child_main(args)
@@ -520,9 +544,10 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(arch, B, steps, warmup):
-        """W warm-up + K timed reconstruction steps of `arch` at batch B (inputs resident in HBM); on rank 0 also the
-        profiled pass for the roofline.  -> (model, params, dict)"""
+    def measure(arch, B, steps, warmup, profile=True, keep_output=False):
+        """W warm-up + K timed reconstruction steps of `arch` at batch B (inputs resident in HBM); on rank 0 and with `profile`
+        also the profiled pass for the roofline; with `keep_output` the last timed step's output as host numpy ("_last").
+        -> (model, params, dict)"""
         P = O.make_params(arch, seed=1)
         model = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=P)
         h = model.handle
@@ -557,7 +582,9 @@ def main(argv=None):
         r = {"ms_per_step": dt / steps * 1e3, "value": world * B * steps / dt,
              "step_ms": {"p50": float(np.percentile(per, 50)), "p95": float(np.percentile(per, 95)), "min": float(per.min()),
                          "max": float(per.max()), "how": "HIP events on the launch stream between consecutive steps (device time)"}}
-        if rank == 0:
+        if keep_output:
+            r["_last"] = out.cpu().numpy()
+        if rank == 0 and profile:
             # --- roofline: profiled pass (HIP events around every tapgemm launch, on the launch stream) ---
             nprof = min(steps, 20)
             h.profile_enable(True)
@@ -645,12 +672,15 @@ def main(argv=None):
 
     arch = args.arch
     B = args.batch or (64 if arch == "IAN_simple" else 256)
-    model, P, main_r = measure(arch, B, args.steps, args.warmup)
+    model, P, main_r = measure(arch, B, args.steps, args.warmup, profile=args.full, keep_output=bool(args.dump_outputs) and rank == 0)
     h = model.handle
     ms_per_step, value = main_r["ms_per_step"], main_r["value"]
-    box = box_probe() if rank == 0 else None       # right after the timed region: the clocks / temperature the headline just ran at
+    box = box_probe() if (rank == 0 and args.full) else None   # right after the timed region: the clocks / temperature the headline just ran at
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"reconstruction": main_r["_last"]})
+    main_r.pop("_last", None)
     main_x, main_out = main_r.pop("_x"), main_r.pop("_out")
-    bf_sec = bf16x3_secondary(arch, B, min(args.steps, 50), 5, main_out, main_x) if (rank == 0 and not args.no_bf16x3) else {}
+    bf_sec = bf16x3_secondary(arch, B, min(args.steps, 50), 5, main_out, main_x) if (rank == 0 and args.full and not args.no_bf16x3) else {}
     if rank == 0 and box and "sustained_f32_mfma_tflops" in box and "roofline" in main_r:
         sus = box["sustained_f32_mfma_tflops"]
         main_r["roofline"]["frac_of_sustained"] = main_r["roofline"]["achieved"] / sus
@@ -658,9 +688,9 @@ def main(argv=None):
 
     result = None
     if rank == 0:
-        roofline = main_r["roofline"]
+        roofline = main_r.get("roofline")
         edit = None
-        if arch == "IAN_simple" and not args.no_edit:
+        if arch == "IAN_simple" and args.full and not args.no_edit:
             try:   # secondary measurement: never let it take the headline number down
                 z = O.make_latents(1, seed=2)
                 rgb = np.full((1, 3, 64, 64), -1.0, np.float32); rgb[:, 0] = 1.0
@@ -796,7 +826,7 @@ def main(argv=None):
                     pass
         # ---- batch-1 reconstruction latency (BASELINE.json configs[0]'s GPU twin; NPE.py:257-261 encode_images -> sample_at) ----
         b1 = None
-        if arch == "IAN_simple" and not args.no_edit:   # --no-edit (scripts/profile_round.sh): batch-64 launches only in the trace
+        if arch == "IAN_simple" and args.full and not args.no_edit:   # --no-edit (scripts/profile_round.sh): batch-64 launches only in the trace
             try:
                 x1 = torch.from_numpy(O.make_images(1, seed=5)).cuda()
                 o1 = torch.empty_like(x1)
@@ -840,7 +870,7 @@ def main(argv=None):
             host_io = {"value": 10 * B / (time.perf_counter() - t), "unit": "reconstructions/s",
                        "note": "host numpy in -> host numpy out per call (pageable memory, PCIe inclusive); never `value`"}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(arch, P, B if arch == "IAN_simple" else 32)
             except Exception as exc:
@@ -851,13 +881,14 @@ def main(argv=None):
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s encode->z->decode reconstruction, batch %d per GPU, inputs resident in HBM"
                                    % (arch, B), "parallelism": "replicas x%d (no data-path collective)" % world},
-            "step_ms": main_r["step_ms"], "roofline": roofline, "box": box, "cpu_baseline": cpu, "edit_step": edit, "b1_recon": b1,
-            "_bf16x3": bf_sec,
+            "step_ms": main_r["step_ms"],
         }
+        if args.full:
+            result.update({"roofline": roofline, "box": box, "cpu_baseline": cpu, "edit_step": edit, "b1_recon": b1, "_bf16x3": bf_sec})
         if host_io:
             result["host_io"] = host_io
     # ---- BASELINE.json configs[2]: full IAN (MDC + RGB-Beta blocks), batch 256 per GPU, same protocol --------------
-    if arch == "IAN_simple" and not args.no_full_ian:
+    if arch == "IAN_simple" and args.full and not args.no_full_ian:
         fsteps, fwarm = min(args.steps, 20), min(args.warmup, 5)
         try:
             fmodel, fP, fr = measure("IAN", 256, fsteps, fwarm)
@@ -879,9 +910,9 @@ def main(argv=None):
             result["full_ian"] = full
     # ---- train_IAN.py step (BASELINE.json configs[4]): full IAN, data parallel, RCCL gradient all-reduce ----------
     train = None
-    if not args.no_train:   # at N > 1 this is the data-parallel step: 128 images per GPU, SyncBN + MinibatchLayer all-gather ("exact")
+    if args.full and not args.no_train:   # at N > 1 this is the data-parallel step: 128 images per GPU, SyncBN + MinibatchLayer all-gather ("exact")
         train = guarded_train_leg(args, rank, world, result, backend, local)
-    if rank == 0 and result is not None:
+    if rank == 0 and result is not None and args.full:
         result["train_step"] = train
         _finalize_secondary(result)
     if world > 1:

@@ -33,6 +33,9 @@ SANITIZE = bool(os.environ.get("IAN_SANITIZE")) and not ABLATION
 NOFUSE = bool(os.environ.get("IAN_NOFUSE_BUILD")) and not ABLATION and not SANITIZE
 LIB = os.path.join(HERE, "libian_ablation.so" if ABLATION else ("libian_asan.so" if SANITIZE else ("libian_nofuse.so" if NOFUSE else "libian.so")))
 STAMP = os.path.join(HERE, ".libian_ablation.stamp" if ABLATION else (".libian_asan.stamp" if SANITIZE else (".libian_nofuse.stamp" if NOFUSE else ".libian.stamp")))
+# The ablation and no-fuse builds compile their own objects, so they take their own lock and can run beside the product build
+# (__graft_entry__.build() starts the ablation build alongside it); the sanitized build links the product build's objects and shares its lock.
+LOCK = os.path.join(HERE, ".libian_ablation.lock" if ABLATION else (".libian_nofuse.lock" if NOFUSE else ".libian.lock"))
 HOST_SOURCES = ("ian_runtime.cpp", "ian_train_abi.cpp", "ian_trainer.cpp", "ian_comm_rccl.cpp")
 # The host units contain no device code (they call the launch_* wrappers of the .hip files), so the sanitized build compiles
 # them with g++ against the HIP runtime API: GCC's ASan runtime, unlike ROCm clang's, does not intercept the HSA allocator
@@ -111,7 +114,7 @@ def build(force=False, verbose=False):
     dig = _digest()
     if not force and _fresh(dig):
         return LIB
-    lock = open(os.path.join(HERE, ".libian.lock"), "w")
+    lock = open(LOCK, "w")
     try:
         fcntl.flock(lock, fcntl.LOCK_EX)
         if not force and _fresh(dig):

@@ -23,7 +23,16 @@ Fixtures:
                        mode with two colours / sizes, 3 scroll events, Reset), the numpy / scipy lines between them restated from NPE.py
   ref_train_IAN.npz    train_IAN.make_training_functions: update_gen / update_discrim metrics, every gradient
                        (recovered from the Adam first moments), parameter values after the two updates
+  ref_configs.json     the graph IAN_simple.py (dnn=True / False) and IAN.py give under the config recorder + lowering
+                       (tests/test_host.py: config_record)
+  ref_api_surface.json API.py's class IAN: methods and positional argument names; the model methods NPE.py calls
+                       (tests/test_host.py: api_surface)
+
+    python tests/golden/make_ref_golden.py check      regenerates the masks, layers, IAN_simple, session, configs and
+                                                      surface fixtures into a temporary directory and compares them with
+                                                      the committed ones
 """
+import json
 import logging
 import os
 import sys
@@ -38,7 +47,7 @@ sys.path.insert(0, ROOT)
 
 from neural_photo_editor_amd import synthetic as S  # noqa: E402  (pure numpy generators)
 from oracle.refexec import minitheano as MT  # noqa: E402
-from oracle.refexec.install import reference_modules  # noqa: E402
+from oracle.refexec.install import REFERENCE_DIR, reference_modules  # noqa: E402
 
 PATCHES = [(26, 26, 30, 30), (0, 0, 64, 64), (0, 0, 1, 1), (63, 63, 64, 64), (10, 20, 30, 40), (60, 0, 64, 9)]
 SHIM = '''# get_model(dnn=) adapter: API.py:21 passes dnn=, IAN.get_model (IAN.py:67) only takes interp (README.md:71)
@@ -513,6 +522,57 @@ def gen_session(ref, arch, out, tmp):
     print("session %s: %d events, |Z| after infer %.3f, after the last scroll %.3f" % (arch, len(kinds), np.abs(fx["00_Z"]).max(), np.abs(fx["%02d_Z" % (len(kinds) - 2)]).max()))
 
 
+def _host_tests():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_host
+    return test_host
+
+
+def gen_configs(out):
+    """What the reference's config files give under neural_photo_editor_amd.config_loader + lowering (no Theano stand-in needed)."""
+    th = _host_tests()
+    fx = {"%s dnn=%s" % (name, dnn): th.config_record(os.path.join(REFERENCE_DIR, name), dnn)
+          for name, dnn in (("IAN_simple.py", True), ("IAN_simple.py", False), ("IAN.py", True))}
+    with open(out, "w") as f:
+        json.dump(fx, f, indent=1)
+
+
+def gen_api_surface(out):
+    th = _host_tests()
+    with open(os.path.join(REFERENCE_DIR, "API.py")) as a, open(os.path.join(REFERENCE_DIR, "NPE.py")) as n:
+        fx = th.api_surface(a.read(), n.read())
+    with open(out, "w") as f:
+        json.dump(fx, f, indent=1, sort_keys=True)
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
+
+
+def check():
+    """The committed fixtures are what the reference produces today (float64 sums may be re-associated between runs: threaded
+    torch-CPU convolutions)."""
+    logging.basicConfig(level=logging.ERROR)
+    with tempfile.TemporaryDirectory() as tmp:
+        with reference_modules() as ref:
+            gen_made_masks(ref, os.path.join(tmp, "ref_made_masks.npz"))
+            gen_layers(ref, os.path.join(tmp, "ref_layers.npz"))
+            gen_inference(ref, "IAN_simple", os.path.join(tmp, "ref_IAN_simple.npz"), tmp)
+            gen_session(ref, "IAN_simple", os.path.join(tmp, "ref_session_IAN_simple.npz"), tmp)
+        gen_configs(os.path.join(tmp, "ref_configs.json"))
+        gen_api_surface(os.path.join(tmp, "ref_api_surface.json"))
+        for name in ("ref_made_masks.npz", "ref_layers.npz", "ref_IAN_simple.npz", "ref_session_IAN_simple.npz"):
+            a, b = np.load(os.path.join(tmp, name)), np.load(os.path.join(HERE, name))
+            assert sorted(a.files) == sorted(b.files), name
+            for k in a.files:
+                assert np.array_equal(a[k], b[k]) or _rel(a[k], b[k]) < 1e-11, (name, k)
+        for name in ("ref_configs.json", "ref_api_surface.json"):
+            with open(os.path.join(tmp, name)) as a, open(os.path.join(HERE, name)) as b:
+                assert json.load(a) == json.load(b), name
+    print("fixtures regenerate from the reference")
+
+
 def main(which):
     logging.basicConfig(level=logging.ERROR)
     with reference_modules() as ref, tempfile.TemporaryDirectory() as tmp:
@@ -527,7 +587,14 @@ def main(which):
             gen_train(ref, os.path.join(HERE, "ref_train_IAN.npz"), tmp)
         if "session" in which:
             gen_session(ref, "IAN_simple", os.path.join(HERE, "ref_session_IAN_simple.npz"), tmp)
+    if "configs" in which:
+        gen_configs(os.path.join(HERE, "ref_configs.json"))
+    if "surface" in which:
+        gen_api_surface(os.path.join(HERE, "ref_api_surface.json"))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or ["masks", "layers", "IAN_simple", "IAN", "train", "session"])
+    if sys.argv[1:] == ["check"]:
+        check()
+    else:
+        main(sys.argv[1:] or ["masks", "layers", "IAN_simple", "IAN", "train", "session", "configs", "surface"])

@@ -1,6 +1,7 @@
 """CPU tests of the host side: config recorder, lowering, MADE masks (product code), checkpoint format,
 and that the C-ABI library builds, loads and exports every symbol include/ian.h declares."""
 import ctypes
+import json
 import os
 import re
 
@@ -13,7 +14,7 @@ from oracle import ian_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = os.path.join(ROOT, "neural_photo_editor_amd", "configs")
-REF = "/root/reference"
+GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 def lowered(path, dnn=True):
@@ -24,6 +25,25 @@ def lowered(path, dnn=True):
 def op_signature(low):
     return [(o.kind, o.segment, o.src, o.src2, o.src3, o.dst, o.cin, o.cout, o.in_h, o.in_w, o.act, o.has_bias,
              tuple(o.flat), tuple(o.unflat), tuple(o.scales), o.name, o.bn_name) for o in low.ops]
+
+
+def config_record(path, dnn):
+    """A config file's graph as test_reference_configs_load_unchanged compares it, in JSON form (tuples as lists, dict keys as
+    strings).  tests/golden/make_ref_golden.py records it for the reference's own config files in ref_configs.json."""
+    mod, low = lowered(path, dnn=dnn)
+    rec = {"ops": op_signature(low), "params": [(p.name, p.shape) for p in low.params], "slots": low.slots, "cfg": mod.cfg}
+    return json.loads(json.dumps(rec))
+
+
+def api_surface(api_src, npe_src):
+    """The reference's plat-style class as test_host_class_has_the_reference_surface compares it: the positional argument names of
+    every method of class IAN in API.py (read with ast: its Python 2 syntax is not executed) and the model methods NPE.py calls.
+    tests/golden/make_ref_golden.py records it in ref_api_surface.json."""
+    import ast
+    tree = ast.parse(api_src.replace("print ", "pass #"))     # py2 print statements
+    cls = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "IAN"][0]
+    return {"API.IAN": {f.name: [a.arg for a in f.args.args] for f in cls.body if isinstance(f, ast.FunctionDef)},
+            "NPE.model_calls": sorted(set(re.findall(r"model\.(\w+)\(", npe_src)))}
 
 
 def test_ian_simple_lowering():
@@ -77,17 +97,15 @@ def test_ian_lowering():
         == set(O.param_shapes("IAN"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("name,dnn", [("IAN_simple.py", True), ("IAN_simple.py", False), ("IAN.py", True)])
 def test_reference_configs_load_unchanged(name, dnn):
-    """The reference's own config files execute under the recorder and give the graph of our configs."""
-    _, ours = lowered(os.path.join(CFG, name), dnn=dnn)
-    mod, theirs = lowered(os.path.join(REF, name), dnn=dnn)
-    assert op_signature(ours) == op_signature(theirs)
-    assert [(p.name, p.shape) for p in ours.params] == [(p.name, p.shape) for p in theirs.params]
-    assert ours.slots == theirs.slots
-    ours_mod = cl.load_config(os.path.join(CFG, name))
-    assert ours_mod.cfg == mod.cfg
+    """The reference's own config files, executed under the recorder, give the graph of our configs (ref_configs.json: what
+    tests/golden/make_ref_golden.py recorded from them)."""
+    with open(os.path.join(GOLD, "ref_configs.json")) as f:
+        theirs = json.load(f)["%s dnn=%s" % (name, dnn)]
+    ours = config_record(os.path.join(CFG, name), dnn)
+    for k in ("ops", "params", "slots", "cfg"):
+        assert ours[k] == theirs[k], k
 
 
 def test_stub_environment_is_removed_afterwards():
@@ -315,24 +333,18 @@ def test_layer_creation_without_gpu_fails_loudly():
 def test_host_class_has_the_reference_surface():
     """Drop-in boundary: every public method of the reference's plat-style class (API.py:11-110) exists on
     neural_photo_editor_amd.IAN with the same positional argument names, and the constructor takes
-    (config_path, dnn).  Reads the reference source with ast (Python 2 syntax is not executed)."""
+    (config_path, dnn).  The reference's surface as ref_api_surface.json recorded it (api_surface above)."""
     import inspect
-    ref = os.path.join(REF, "API.py")
-    if not os.path.exists(ref):
-        pytest.skip("reference checkout not present")
-    import ast
-    src = open(ref).read().replace("print ", "pass #")     # py2 print statements
-    tree = ast.parse(src)
-    cls = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "IAN"][0]
-    ref_methods = {f.name: [a.arg for a in f.args.args] for f in cls.body if isinstance(f, ast.FunctionDef)}
+    with open(os.path.join(GOLD, "ref_api_surface.json")) as f:
+        fx = json.load(f)
+    ref_methods = fx["API.IAN"]
     assert set(ref_methods) == {"__init__", "imgrad", "imgradRGB", "encode_images", "get_zdim", "sample_at"}
     from neural_photo_editor_amd import IAN
     for name, args in ref_methods.items():
         ours = list(inspect.signature(getattr(IAN, name)).parameters)
         assert ours[:len(args)] == args, (name, ours, args)
     # what NPE.py calls (NPE.py:18,110,205,218,257,261,296,311,323,333,335)
-    npe = open(os.path.join(REF, "NPE.py")).read()
-    used = set(re.findall(r"model\.(\w+)\(", npe))
+    used = set(fx["NPE.model_calls"])
     assert used <= set(ref_methods) and "imgradRGB" in used and "sample_at" in used
 
 

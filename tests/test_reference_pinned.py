@@ -5,8 +5,8 @@ evaluating Theano/Lasagne stand-in of oracle/refexec/).  This is what pins the o
 the reference-owned arithmetic agree to float64 round-off.  Still [recalled]: third-party primitive conventions
 (conv / transposed conv / dilated conv / batch_norm / adam), see oracle/refexec/minilasagne.py.
 
-When /root/reference is present (build container) one test re-executes the reference and checks the committed
-fixtures are what it produces today; on the GPU box that test is skipped, the fixtures travel."""
+That the committed fixtures are what the reference produces today is checked where a reference checkout exists, outside
+the suite: `python tests/golden/make_ref_golden.py check`."""
 import os
 
 import numpy as np
@@ -247,23 +247,3 @@ def test_npe_session_replay_oracle_vs_reference_executed_session():
     tw = TorchTwin("IAN_simple", O.make_params("IAN_simple", 1), dtype=torch.float64)
     worst = compare(replay(_TwinFacade(tw), fx), fx, tol=1e-6, max_off_by_one_frac=1e-3)
     assert worst["Z"] < 1e-6
-
-
-# ---- the fixtures are what the reference produces today (build container only) -------------------------------
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout only exists in the build container")
-def test_fixtures_regenerate_from_the_reference(tmp_path):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_ref_golden", os.path.join(GOLD, "make_ref_golden.py"))
-    mk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mk)
-    from oracle.refexec.install import reference_modules
-    with reference_modules() as ref:
-        mk.gen_made_masks(ref, str(tmp_path / "m.npz"))
-        mk.gen_layers(ref, str(tmp_path / "l.npz"))
-        mk.gen_inference(ref, "IAN_simple", str(tmp_path / "s.npz"), str(tmp_path))
-        mk.gen_session(ref, "IAN_simple", str(tmp_path / "e.npz"), str(tmp_path))
-    for new, old in (("m.npz", "ref_made_masks.npz"), ("l.npz", "ref_layers.npz"), ("s.npz", "ref_IAN_simple.npz"), ("e.npz", "ref_session_IAN_simple.npz")):
-        a, b = np.load(str(tmp_path / new)), load(old)
-        assert sorted(a.files) == sorted(b.files)
-        for k in a.files:   # float64 sums may be re-associated between runs (threaded torch-CPU convolutions)
-            assert np.array_equal(a[k], b[k]) or rel(a[k], b[k]) < 1e-11, (old, k)

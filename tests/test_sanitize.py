@@ -25,7 +25,8 @@ def _sanitized_env():
     assert lib.endswith("libian_asan.so") and os.path.exists(lib) and os.path.exists(rt)
     env = dict(os.environ)
     env.pop("IAN_SANITIZE", None)
-    env.update(IAN_LIB=lib, LD_PRELOAD=rt, UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
+    # the ASan runtime goes first; a preload already in the environment stays behind it
+    env.update(IAN_LIB=lib, LD_PRELOAD=":".join(filter(None, [rt, os.environ.get("LD_PRELOAD")])), UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:protect_shadow_gap=0:detect_odr_violation=0:verify_asan_link_order=0")
     return env
 
