@@ -170,6 +170,37 @@ typedef struct ian_photo_args {
 int ian_brush_step(ian_handle* h, int32_t c1, int32_t r1, int32_t c2, int32_t r2, const float* rgb, const float* z, float coef,
                    float gscale, float* z_new, float* dz, float* x, const ian_photo_args* photo, void* stream);
 
+/* ---- several editors on one device: n independent brush events in one submission (1 <= n <= 256) ----
+   Item i is exactly one single-image call on (z[i], items[i], rgb[i]): the decoder runs per sample, rows do not couple.
+   An empty rectangle (c2 <= c1 or r2 <= r1) gives a zero gradient; a rectangle outside the image fails the whole call
+   with -7 (the message names the item) before anything is written.  items is a host array. */
+typedef struct ian_brush_item {
+  int32_t c1, r1, c2, r2;   /* API.py:66-76 rectangle, columns first as in imgrad */
+  int32_t mode;             /* 1: imgradRGB against rgb[i]; 0: imgrad (lighten / darken) */
+  float coef, gscale;       /* z_new = z + coef * (dz * gscale); ignored by ian_grad_batch */
+} ian_brush_item;
+
+/* n latents' brush gradients in one submission. rgb f32[n,3,64,64] (rows of mode-0 items are not read) or NULL when
+   no item has mode 1; z f32[n,zl]; dz f32[n,zl].  Host or device pointers, like the single-image calls. */
+int ian_grad_batch(ian_handle* h, int32_t n, const ian_brush_item* items, const float* rgb, const float* z, float* dz,
+                   void* stream);
+
+typedef struct ian_photo_batch_args {
+  const uint8_t* recon;       /* u8[n,3,64,64] */
+  const float* error;         /* f32[n,3,64,64] */
+  const double* gauss_half;   /* f64[radius+1], shared; host memory */
+  int32_t radius;             /* 0..7 */
+  uint8_t* im;                /* out u8[n,3,64,64] */
+  double* mask;               /* out f64[n,64,64] or NULL */
+} ian_photo_batch_args;
+
+/* n brush events (gradient + update + decoder [+ blend]) in one submission, one synchronisation.
+   z_new f32[n,zl] (may alias z), dz f32[n,zl] or NULL, x f32[n,3,64,64] or NULL, photo NULL or as above.
+   When z is byte for byte the z_new the previous call of this function left resident (same n, no other call in
+   between), the forward at z is skipped (IAN_NO_DEC_CACHE switches that off). */
+int ian_brush_step_batch(ian_handle* h, int32_t n, const ian_brush_item* items, const float* rgb, const float* z,
+                         float* z_new, float* dz, float* x, const ian_photo_batch_args* photo, void* stream);
+
 /* Introspection used by tests, bench.py and profiling (not part of the reference surface). */
 /* Copy the activation of tensor slot `slot` from the last call, converted to NCHW, into out (host or device). */
 int ian_read_slot(ian_handle* h, int32_t slot, int32_t n, float* out, void* stream);

@@ -22,7 +22,50 @@ import warnings
 import numpy as np
 
 from . import checkpoints, config_loader, lowering, made
-from .lib import Handle
+from .lib import BrushItem, Handle
+
+BATCH_MAX = 256     # ian_grad_batch / ian_brush_step_batch: 1 <= n <= 256
+
+
+def pack_brush_items(boxes, n_rgb=None, modes=None, weight=0.0, sign=1.0):
+    """Python arguments of the batched brush calls -> a ctypes array of ian_brush_item (include/ian.h), validated before the
+    library sees anything.  boxes (n,4) as (c1, r1, c2, r2) -- floats from Tk are truncated as imgrad's int() does; n_rgb = the
+    leading size of the RGB batch, or None when no RGB was given; modes default to 1 with RGB and 0 without; weight and sign are
+    scalars or length-n arrays: coef = float32(sign*weight) and gscale = float32(1 + (c2 - c1)), exactly as brush_step forms them."""
+    b = np.asarray(boxes)
+    if b.ndim != 2 or b.shape[1] != 4:
+        raise ValueError("boxes must have shape (n,4) as (c1,r1,c2,r2), got %s" % (b.shape,))
+    n = b.shape[0]
+    if not 1 <= n <= BATCH_MAX:
+        raise ValueError("a batch holds 1..%d brush events, got %d" % (BATCH_MAX, n))
+    if n_rgb is not None and n_rgb != n:
+        raise ValueError("RGB holds %d images for %d boxes" % (n_rgb, n))
+    if modes is None:
+        m = [1 if n_rgb is not None else 0] * n
+    else:
+        m = [int(v) for v in np.asarray(modes).reshape(-1)]
+        if len(m) != n:
+            raise ValueError("modes must have length %d, got %d" % (n, len(m)))
+        if any(v not in (0, 1) for v in m):
+            raise ValueError("modes must be 0 (imgrad) or 1 (imgradRGB)")
+        if n_rgb is None and any(m):
+            raise ValueError("item %d has mode 1 (imgradRGB) but no RGB was given" % m.index(1))
+    def per_item(v, what):
+        a = np.asarray(v, np.float64)
+        if a.ndim == 0:
+            return [float(a)] * n
+        if a.shape != (n,):
+            raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (what, n, a.shape))
+        return [float(t) for t in a]
+    w, sg = per_item(weight, "weight"), per_item(sign, "sign")
+    items = (BrushItem * n)()
+    for i in range(n):
+        c1, r1, c2, r2 = [int(v) for v in b[i]]
+        it = items[i]
+        it.c1, it.r1, it.c2, it.r2, it.mode = c1, r1, c2, r2, m[i]
+        it.coef = sg[i] * w[i]                 # rounded to float32 by ctypes, as numpy rounds the scalar
+        it.gscale = float(1 + (c2 - c1))
+    return items
 
 
 class IAN:
@@ -164,6 +207,48 @@ class IAN:
             pa = (recon, err, half, im, mask)
         coef = float(sign) * float(weight)      # rounded to float32 at the boundary, as numpy rounds the scalar
         self._h.brush_step(int(c1), int(r1), int(c2), int(r2), rgb, z[:1], coef, float(1 + (int(c2) - int(c1))), z_new, None, x, pa)
+        if photo is not None:
+            return z_new, x, pa[3], pa[4]
+        return z_new, x
+
+    # ---- several editors: n brush events in one submission (ian_grad_batch / ian_brush_step_batch) ----------------------
+    def imgrad_batch(self, boxes, z, RGB=None, modes=None):
+        """Row i = imgradRGB(*boxes[i], RGB[i:i+1], z[i:i+1]) (mode 1) or imgrad(*boxes[i], z[i:i+1]) (mode 0), for n sessions in one
+        submission.  boxes (n,4) as (c1,r1,c2,r2); modes default to 1 with RGB, 0 without.  -> dz (n, zdim)"""
+        z = self._f32(z, (self._zdim,), "z")
+        rgb = self._f32(RGB, (3, 64, 64), "RGB") if RGB is not None else None
+        items = pack_brush_items(boxes, rgb.shape[0] if rgb is not None else None, modes)
+        if z.shape[0] != len(items):
+            raise ValueError("z holds %d latents for %d boxes" % (z.shape[0], len(items)))
+        dz = np.empty((len(items), self._zdim), np.float32)
+        self._h.grad_batch(items, rgb, z, dz)
+        return dz
+
+    def brush_step_batch(self, boxes, z, RGB=None, weight=0.05, sign=-1.0, modes=None, image=True, photo=None, sigma=0.7,
+                         want_mask=False):
+        """brush_step for n edit sessions in one submission (ian_brush_step_batch): per item the gradient, z + coef*(dz*gscale) with
+        coef = float32(sign*weight) and gscale = 1 + (c2 - c1), and sample_at(z_new); weight / sign are scalars or length-n arrays.
+        -> (z_new (n,zdim), x (n,3,64,64) or None)  or, with photo=(RECON uint8 (n,3,64,64), ERROR float32 (n,3,64,64)),
+           (z_new, x or None, IM uint8 (n,3,64,64), MASK float64 (n,64,64) if want_mask else None)."""
+        z = self._f32(z, (self._zdim,), "z")
+        rgb = self._f32(RGB, (3, 64, 64), "RGB") if RGB is not None else None
+        items = pack_brush_items(boxes, rgb.shape[0] if rgb is not None else None, modes, weight, sign)
+        n = len(items)
+        if z.shape[0] != n:
+            raise ValueError("z holds %d latents for %d boxes" % (z.shape[0], n))
+        z_new = np.empty((n, self._zdim), np.float32)
+        x = np.empty((n, 3, 64, 64), np.float32) if image else None
+        pa = None
+        if photo is not None:
+            recon = np.ascontiguousarray(photo[0], dtype=np.uint8)
+            err = np.ascontiguousarray(photo[1], dtype=np.float32)
+            if recon.shape != (n, 3, 64, 64) or err.shape != (n, 3, 64, 64):
+                raise ValueError("RECON and ERROR must have shape (%d,3,64,64)" % n)
+            from . import npe_ops
+            half = npe_ops.gaussian_half_kernel(sigma, int(4.0 * float(sigma) + 0.5))
+            im, mask = np.empty((n, 3, 64, 64), np.uint8), (np.empty((n, 64, 64), np.float64) if want_mask else None)
+            pa = (recon, err, half, im, mask)
+        self._h.brush_step_batch(items, rgb, z, z_new, None, x, pa)
         if photo is not None:
             return z_new, x, pa[3], pa[4]
         return z_new, x

@@ -203,6 +203,11 @@ hipError_t launch_dense_fwd_gemv(const float* x, const float* w, int K, int nout
 // upd_z != nullptr: row j's workgroup also applies the brush update z[j] += cg[0] * (dz[j] * cg[1]) (and mirrors z, dz)
 hipError_t launch_dense_bwd_gemv(const float* g, const float* wb, int rows, int K, const float* res, float* dz, float* upd_z,
                                  const float* upd_cg, float* z_mirror, float* g_mirror, hipStream_t s);
+// n brush events (ian_grad_batch / ian_brush_step_batch): g [n][gs], dz / z [n][ds]; items = the device copy of the ian_brush_item
+// table (7 words per item), read for (coef, gscale) when upd_z != nullptr
+hipError_t launch_dense_bwd_gemv_batch(const float* g, int gs, const float* wb, int rows, int K, int n, const float* res, float* dz, int ds,
+                                       float* upd_z, const int* items, hipStream_t s);
+hipError_t launch_latent_update_batch(float* z, const float* g, int stride, const int* items, int n, int zl, hipStream_t s);
 hipError_t launch_deconv_out_px(const float* x, const float* w, const float* scale, const float* shift, float* y, float* mirror, int n,
                                 int H, int W, int Cin, int Cout, int act, hipStream_t s);
 
@@ -225,6 +230,8 @@ hipError_t launch_patch_seed(const float* xhat, const float* rgb, float* g, int 
                              int r2, int mode, hipStream_t s);
 hipError_t launch_patch_seed_dev(const float* xhat, const float* rgb, float* g, int H, int W, const int* patch, int mode,
                                  hipStream_t s);
+// the same for n items, rectangle and loss kind per item from the device ian_brush_item table (7 words per item)
+hipError_t launch_patch_seed_batch(const float* xhat, const float* rgb, float* g, int H, int W, const int* items, int n, hipStream_t s);
 // backward of dec_out-like layer: g NCHW [n,Cout,2H,2W] (already multiplied by act') -> dx NHWC [n,H,W,Cin]
 hipError_t launch_deconv_out_bwd(const float* g, const float* w, float* dx, const float* yfwd, const float* scale,
                                  int n, int H, int W, int Cin, int Cout, int act, hipStream_t s);
@@ -232,6 +239,10 @@ hipError_t launch_deconv_out_bwd(const float* g, const float* w, float* dx, cons
 hipError_t launch_deconv_out_bwd_seed(const float* xhat, const float* rgb, const int* patch, int mode, int out_act,
                                       const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale, int H,
                                       int W, int Cin, int Cout, int act, hipStream_t s);
+// ... and for n items (grid y = item; xhat, rgb NCHW [n,Cout,2H,2W], dx / yfwd NHWC [n,H,W,Cin])
+hipError_t launch_deconv_out_bwd_seed_batch(const float* xhat, const float* rgb, const int* items, int n, int out_act, const float* oscale,
+                                            const float* w, float* dx, const float* yfwd, const float* scale, int H, int W, int Cin,
+                                            int Cout, int act, hipStream_t s);
 // elementwise: g = g * act'(y) * scale  (NCHW small tensors, c channels of hw pixels)
 hipError_t launch_dact_nchw(float* g, const float* y, const float* scale, int n, int c, int hw, int act,
                             hipStream_t s);
@@ -327,6 +338,8 @@ struct PhotoBlendArgs {
   int radius;
 };
 hipError_t launch_photo_blend(const PhotoBlendArgs& a, hipStream_t s);
+// n images at once (blockIdx.y = item): every pointer of `a` is the base of an [n]-leading array, the weights are shared
+hipError_t launch_photo_blend_batch(const PhotoBlendArgs& a, int n, hipStream_t s);
 hipError_t launch_latent_update(float* z, const float* g, const float* cg, int n, float* z_mirror, float* g_mirror, hipStream_t s);
 hipError_t launch_keep_warm(const int* flag, long long max_ticks, hipStream_t s);   // experiment: see kernels_npe.hip
 hipError_t launch_to_uint8(const float* x, unsigned char* y, long long n, hipStream_t s);

@@ -419,6 +419,15 @@ int ian_brush_step(ian_handle* h, int32_t c1, int32_t r1, int32_t c2, int32_t r2
   return 0;
 }
 
+int ian_grad_batch(ian_handle* h, int32_t n, const ian_brush_item* items, const float* rgb, const float* z, float* dz, void* stream) {
+  return batch_common(h, n, items, rgb, z, nullptr, dz, nullptr, nullptr, stream, false);
+}
+
+int ian_brush_step_batch(ian_handle* h, int32_t n, const ian_brush_item* items, const float* rgb, const float* z, float* z_new, float* dz,
+                         float* x, const ian_photo_batch_args* photo, void* stream) {
+  return batch_common(h, n, items, rgb, z, z_new, dz, x, photo, stream, true);
+}
+
 int ian_autotune(ian_handle* h, int32_t n, int32_t what, void* stream) {
   int rc = check_ready(h, n);
   if (rc) return rc;
@@ -598,6 +607,7 @@ int ian_set_option(ian_handle* h, const char* key, int32_t value) {
   }
   ++h->alloc_epoch;
   h->dec_cache_valid = false;   // the resident activations were produced under the previous options
+  h->batch.cache_valid = false;
   return 0;
 }
 
@@ -631,6 +641,9 @@ void ian_destroy(ian_handle* h) {
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->d_patch) (void)hipFree(h->d_patch);
   for (void* p : {(void*)h->d_recon, (void*)h->d_error, (void*)h->d_im, (void*)h->d_mask, (void*)h->d_u8})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)h->batch.d_items, (void*)h->batch.d_rgb, (void*)h->batch.d_recon, (void*)h->batch.d_error, (void*)h->batch.d_out,
+                  (void*)h->batch.d_im, (void*)h->batch.d_mask})
     if (p) (void)hipFree(p);
   for (auto& e : h->ev_pool) {
     (void)hipEventDestroy(e.first);

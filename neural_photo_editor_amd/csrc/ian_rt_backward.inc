@@ -16,8 +16,15 @@ struct ProducerEpi {
   int scale_period = 0;
 };
 
+// Several editors (ian_grad_batch / ian_brush_step_batch): d_items = the device copy of n ian_brush_item records (rectangle, loss
+// kind, coef, gscale per item); mode / c1..r2 / d_patch are unused then, d_rgb is [n,3,H,W].  update: the latent's backward also
+// applies each item's brush update to the z slot (*updated = it did).  Without d_items: today's batch-1 launches, unchanged.
 int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2, const float* d_rgb, hipStream_t st,
-                         const int* d_patch = nullptr) {
+                         const int* d_patch = nullptr, int n = 1, const int* d_items = nullptr, bool update = false,
+                         bool* updated = nullptr) {
+  const bool batched = d_items != nullptr;
+  if (!batched) n = 1;
+  if (updated) *updated = false;
   std::vector<OpPlan*> dec;
   for (auto& op : h->ops)
     if (op.d.segment == IAN_SEG_DEC) dec.push_back(&op);
@@ -29,15 +36,23 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
   if (last.d.dst != h->desc.out_slot) return fail(h, -9, "imgrad: the last decoder op does not produce l_out");
   Slot& out = h->slots[last.d.dst];
   const int H = out.h, W = out.w;
-  if (c1 < 0 || r1 < 0 || c2 > W || r2 > H) return fail(h, -7, "patch (%d,%d,%d,%d) outside the %dx%d image", c1, r1, c2, r2, W, H);
+  if (!batched && (c1 < 0 || r1 < 0 || c2 > W || r2 > H)) return fail(h, -7, "patch (%d,%d,%d,%d) outside the %dx%d image", c1, r1, c2, r2, W, H);
   if (!h->d_gseed) {
     HIPCHK(h, hipMalloc((void**)&h->d_gseed, (size_t)3 * H * W * sizeof(float)));
+    h->gseed_cap = (size_t)3 * H * W;
     ++h->alloc_epoch;
   }
-  // interactive loop + image-producing deconv (IAN_simple): seed, tanh' and the first backward-data in one launch
-  const bool fused_seed = d_patch && last.d.kind == IAN_OP_DECONV5S2 && last.edge;
+  const bool fused_seed = (d_patch || batched) && last.d.kind == IAN_OP_DECONV5S2 && last.edge;
+  if (batched && !fused_seed && (size_t)n * 3 * H * W > h->gseed_cap) {   // the batch-1 graphs captured the old seed buffer: the epoch moves
+    HIPCHK(h, hipFree(h->d_gseed));
+    h->gseed_cap = (size_t)n * 3 * H * W;
+    HIPCHK(h, hipMalloc((void**)&h->d_gseed, h->gseed_cap * sizeof(float)));
+    ++h->alloc_epoch;
+  }
+  // interactive loop + image-producing deconv (IAN_simple): seed, tanh' and the first backward-data in one launch (fused_seed above)
   if (fused_seed) {
-  } else if (d_patch) HIPCHK(h, launch_patch_seed_dev(out.d, d_rgb, h->d_gseed, H, W, d_patch, mode, st));
+  } else if (batched) HIPCHK(h, launch_patch_seed_batch(out.d, d_rgb, h->d_gseed, H, W, d_items, n, st));
+  else if (d_patch) HIPCHK(h, launch_patch_seed_dev(out.d, d_rgb, h->d_gseed, H, W, d_patch, mode, st));
   else HIPCHK(h, launch_patch_seed(out.d, d_rgb, h->d_gseed, H, W, c1, r1, c2, r2, mode, st));  // dL/dX_hat, NCHW
 
   std::vector<char> touched(nslots, 0);
@@ -55,11 +70,11 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
   };
   auto pass_to = [&](const float* gs, int ss, int coff, int slot, int C) -> int {
     Slot& t = h->slots[slot];
-    int rc = ensure_slot(h, slot, 1, true);
+    int rc = ensure_slot(h, slot, n, true);
     if (rc) return rc;
     ProducerEpi e = epi_of(slot);
     if (e.scale_period) return fail(h, -9, "imgrad: identity edge into a per-feature batch-norm is not supported");
-    HIPCHK(h, launch_grad_pass(gs, ss, coff, t.g, e.yfwd, t.cs, e.scale, (long long)t.h * t.w, C, e.act, touched[slot], st));
+    HIPCHK(h, launch_grad_pass(gs, ss, coff, t.g, e.yfwd, t.cs, e.scale, (long long)n * t.h * t.w, C, e.act, touched[slot], st));
     touched[slot] = 1;
     return 0;
   };
@@ -73,28 +88,31 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
       BetaBwdArgs a;
       for (int c = 0; c < 3; ++c) {
         Slot& m = h->slots[srcs[c]];
-        if ((rc = ensure_slot(h, srcs[c], 1, true))) return rc;
+        if ((rc = ensure_slot(h, srcs[c], n, true))) return rc;
         ProducerEpi e = epi_of(srcs[c]);
         a.v[c] = m.d; a.g[c] = m.g; a.scale[c] = e.scale; a.act[c] = e.act; a.accumulate[c] = touched[srcs[c]];
         touched[srcs[c]] = 1;
       }
       Slot& m0 = h->slots[srcs[0]];
-      HIPCHK(h, launch_beta_bwd(h->d_gseed, a, 1, m0.h * m0.w, m0.cs, st));
+      HIPCHK(h, launch_beta_bwd(h->d_gseed, a, n, m0.h * m0.w, m0.cs, st));
       continue;
     }
     if (kind == IAN_OP_DECONV5S2 && op.edge) {  // image-producing deconv (IAN_simple dec_out)
       if (op.d.dst != h->desc.out_slot) return fail(h, -9, "imgrad: edge deconv '%s' must produce l_out", op.name.c_str());
       Slot& in = h->slots[op.d.src];
       if (touched[op.d.src]) return fail(h, -9, "imgrad: '%s' input has several consumers", op.name.c_str());
-      if ((rc = ensure_slot(h, op.d.src, 1, true))) return rc;
+      if ((rc = ensure_slot(h, op.d.src, n, true))) return rc;
       ProducerEpi e = epi_of(op.d.src);
       if (e.scale_period) return fail(h, -9, "imgrad: per-feature batch-norm directly under the image deconv");
-      if (fused_seed) {
+      if (fused_seed && batched) {
+        HIPCHK(h, launch_deconv_out_bwd_seed_batch(out.d, d_rgb, d_items, n, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd, e.scale,
+                                                   op.d.in_h, op.d.in_w, in.cs, op.d.cout, e.act, st));
+      } else if (fused_seed) {
         HIPCHK(h, launch_deconv_out_bwd_seed(out.d, d_rgb, d_patch, mode, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd, e.scale,
                                              op.d.in_h, op.d.in_w, in.cs, op.d.cout, e.act, st));
       } else {
-        HIPCHK(h, launch_dact_nchw(h->d_gseed, out.d, op.d_scale, 1, out.c, H * W, op.d.act, st));
-        HIPCHK(h, launch_deconv_out_bwd(h->d_gseed, op.d_edge_w, in.g, e.yfwd, e.scale, 1, op.d.in_h, op.d.in_w, in.cs,
+        HIPCHK(h, launch_dact_nchw(h->d_gseed, out.d, op.d_scale, n, out.c, H * W, op.d.act, st));
+        HIPCHK(h, launch_deconv_out_bwd(h->d_gseed, op.d_edge_w, in.g, e.yfwd, e.scale, n, op.d.in_h, op.d.in_w, in.cs,
                                         op.d.cout, e.act, st));
       }
       touched[op.d.src] = 1;
@@ -108,15 +126,22 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
       case IAN_OP_MDC3: {
         if (!op.bwd.valid) return fail(h, -9, "imgrad: op '%s' has no backward-data form", op.name.c_str());
         Slot& in = h->slots[op.d.src];
-        if ((rc = ensure_slot(h, op.d.src, 1, true))) return rc;
+        if ((rc = ensure_slot(h, op.d.src, n, true))) return rc;
         ProducerEpi pe = epi_of(op.d.src);
         TgEpilogue e;
         e.scale = pe.scale; e.shift = nullptr; e.yfwd = pe.yfwd; e.act = pe.act; e.scale_period = pe.scale_period;
         e.res = touched[op.d.src] ? in.g : nullptr;
         e.mode = TG_EPI_BWD;
         const int ystride = (kind == IAN_OP_DENSE) ? (int)in.per_image() : in.cs;
-        if (kind == IAN_OP_DENSE && h->opt.dense_gemv && !pe.scale && !pe.yfwd && pe.act == IAN_ACT_NONE && op.d.flat_c <= 0 &&
-            (op.bwd.Cin & 3) == 0 && op.bwd.Cout <= ystride) {
+        const bool gemv = kind == IAN_OP_DENSE && h->opt.dense_gemv && !pe.scale && !pe.yfwd && pe.act == IAN_ACT_NONE && op.d.flat_c <= 0 &&
+                          (op.bwd.Cin & 3) == 0 && op.bwd.Cout <= ystride;
+        if (gemv && batched && (size_t)op.bwd.Cin <= o.per_image() && (o.per_image() & 3) == 0) {
+          // several editors: each weight row streamed once per block of items; the brush update rides along (ian_brush_step_batch)
+          const bool upd = update && op.d.src == h->desc.z_slot && !e.res;
+          HIPCHK(h, launch_dense_bwd_gemv_batch(o.g, (int)o.per_image(), op.bwd.d_w, op.bwd.Cout, op.bwd.Cin, n, e.res, in.g, ystride,
+                                                upd ? in.d : nullptr, d_items, st));
+          if (upd && updated) *updated = true;
+        } else if (gemv && !batched) {
           // the latent's own layer: slab [in][out], row j contiguous in the (permuted) output index = o.g's order
           // ian_brush_step: the same launch applies the latent update (h->upd set by the caller; the latent's row = this output)
           const bool upd = h->upd.cg && op.d.src == h->desc.z_slot && !e.res && h->opt.fuse_latent_update;
@@ -125,13 +150,13 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
           h->upd.done = upd;
         } else {
           B1Params bp;
-          if (kind == IAN_OP_DECONV5S2 && b1_fill(h, op, 1, o, in, bp)) {
+          if (!batched && kind == IAN_OP_DECONV5S2 && b1_fill(h, op, 1, o, in, bp)) {
             bp.x = o.g; bp.y = in.g; bp.scale = e.scale; bp.yfwd = e.yfwd; bp.res = e.res; bp.act = e.act; bp.bwd = 1;
             bp.scale_period = e.scale_period;
 #ifdef IAN_ABLATION
             HIPCHK(h, launch_b1conv(bp, 1, st));
 #endif
-          } else if ((rc = run_tapgemm(h, op.bwd, 1, o.g, in.g, ystride, e, st))) return rc;
+          } else if ((rc = run_tapgemm(h, op.bwd, n, o.g, in.g, ystride, e, st))) return rc;
         }
         touched[op.d.src] = 1;
         if (kind == IAN_OP_MDC3 && op.d.src2 >= 0)  // residual operand of the fused ElemwiseSum: identity edge

@@ -13,6 +13,7 @@ void warm_release(ian_handle* h) {
 }
 void enter_stream(ian_handle* h, hipStream_t st) {
   warm_release(h);     // whatever comes next must not queue behind the keep-warm kernel
+  h->batch.cache_valid = false;   // the batched calls' resident activations survive only until the next call
   if (h->last_pending && h->last_stream != st) (void)hipStreamSynchronize(h->last_stream);
   h->last_stream = st;
   h->last_pending = true;   // cleared by callers that synchronise before returning
@@ -308,6 +309,168 @@ int enqueue_photo_blend(ian_handle* h, const uint8_t* recon, const float* error,
   return 0;
 }
 
+// ----- several editors: n brush events in one submission (ian_grad_batch / ian_brush_step_batch) ----------------------------
+// buffers of the batched calls only: no captured batch-1 graph references them, so growing one does not move alloc_epoch
+template <typename T>
+int grow_dev(ian_handle* h, T** p, size_t* cap, size_t need, bool* grew = nullptr) {
+  if (grew) *grew = false;
+  if (need <= *cap) return 0;
+  if (*p) HIPCHK(h, hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  HIPCHK(h, hipMalloc((void**)p, need * sizeof(T)));
+  *cap = need;
+  if (grew) *grew = true;
+  return 0;
+}
 
+// a host input goes up only when its bytes differ from the last upload (the shadow copy is the upload source); device inputs are
+// used in place
+template <typename T>
+int upload_batch_cached(ian_handle* h, const T* src, size_t cnt, T** d, size_t* cap, std::vector<T>& shadow, hipStream_t st,
+                        const T** out) {
+  if (is_device_ptr(src)) {
+    *out = src;
+    return 0;
+  }
+  bool grew = false;
+  int rc = grow_dev(h, d, cap, cnt, &grew);
+  if (rc) return rc;
+  if (grew || shadow.size() != cnt || memcmp(shadow.data(), src, cnt * sizeof(T)) != 0) {
+    shadow.assign(src, src + cnt);
+    HIPCHK(h, hipMemcpyAsync(*d, shadow.data(), cnt * sizeof(T), hipMemcpyHostToDevice, st));
+  }
+  *out = *d;
+  return 0;
+}
+
+constexpr int BATCH_MAX = 256;
+
+// The decoder's forward at batch nc with every layer's activation kept (the backward sweep reads them), its output written.
+int batch_forward(ian_handle* h, const float* z, int nc, hipStream_t st) {
+  int rc;
+  if (z && (rc = set_latent_input(h, h->desc.z_slot, z, nc, st))) return rc;
+  h->keep_layer_acts = true;
+  rc = run_segment(h, IAN_SEG_DEC, nc, st);
+  h->keep_layer_acts = false;
+  if (rc) return rc;
+  for (auto& op : h->ops) {   // every activation the backward sweep may read holds nc images (no kernel may run past a buffer)
+    if (op.d.segment != IAN_SEG_DEC) continue;
+    for (int sl : {op.d.src, op.d.src2, op.d.src3, op.d.dst}) {
+      if (sl < 0) continue;
+      const Slot& s = h->slots[sl];
+      if (!s.d || s.cap < s.per_image() * (size_t)nc) return fail(h, -9, "batched brush: activation of slot %d was not materialised", sl);
+    }
+  }
+  return 0;
+}
+
+// Item i is one single-image call on (z[i], items[i], rgb[i]).  Per pass of at most opt.brush_pass items: the decoder forward (skipped when
+// the activations the previous ian_brush_step_batch left resident belong to these very latents), the batched seed + backward sweep,
+// [the brush update fused into the latent's GEMV and the forward at z_new,] [the batched photo blend].  Then the outputs, with one
+// synchronisation when any of them is host memory.  All launches on the caller's stream.
+int batch_common(ian_handle* h, int n, const ian_brush_item* items, const float* rgb, const float* z, float* z_new, float* dz, float* x,
+                 const ian_photo_batch_args* photo, void* stream, bool step) {
+  const char* fn = step ? "ian_brush_step_batch" : "ian_grad_batch";
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: n = %d outside 1..%d", fn, n, BATCH_MAX);
+  if (!items || !z || (step ? !z_new : !dz)) return fail(h, -1, "null pointer passed to %s", fn);
+  if (is_device_ptr(items)) return fail(h, -7, "%s: items must be a host array", fn);
+  Slot& out = h->slots[h->desc.out_slot];
+  bool any_rgb = false;
+  for (int i = 0; i < n; ++i) {   // everything is checked before anything is enqueued or written
+    const ian_brush_item& it = items[i];
+    if (it.mode != 0 && it.mode != 1) return fail(h, -7, "%s: item %d has mode %d (0 = imgrad, 1 = imgradRGB)", fn, i, it.mode);
+    if (it.mode == 1 && !rgb) return fail(h, -1, "%s: item %d has mode 1 (imgradRGB) but rgb is NULL", fn, i);
+    if (it.c1 < 0 || it.r1 < 0 || it.c2 > out.w || it.r2 > out.h)
+      return fail(h, -7, "%s: item %d: patch (%d,%d,%d,%d) outside the %dx%d image", fn, i, it.c1, it.r1, it.c2, it.r2, out.w, out.h);
+    any_rgb = any_rgb || it.mode == 1;
+  }
+  if (photo) {
+    if (!photo->recon || !photo->error || !photo->gauss_half || !photo->im) return fail(h, -1, "null pointer passed to the photo blend of %s", fn);
+    if (photo->radius < 0 || photo->radius > 7) return fail(h, -7, "%s: photo blend radius %d outside 0..7", fn, photo->radius);
+    if (out.h != 64 || out.w != 64 || out.c != 3) return fail(h, -7, "%s: the photo blend needs a 3x64x64 image", fn);
+  }
+  if (photo && is_device_ptr(photo->gauss_half)) return fail(h, -7, "%s: gauss_half must be a host array", fn);
+  const int pass = h->opt.brush_pass;   // items per forward / backward / forward pass
+  const int zl = h->desc.num_latents;
+  Slot& zs = h->slots[h->desc.z_slot];
+  const size_t img = out.per_image();
+  auto& B = h->batch;
+  const bool hit = n <= pass && !is_device_ptr(z) && B.cache_valid && B.cache_n == n && getenv("IAN_NO_DEC_CACHE") == nullptr &&
+                   memcmp(B.cache_z.data(), z, (size_t)n * zl * sizeof(float)) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  enter_stream(h, st);   // also ends the resident-activation cache: re-armed below when this call leaves z_new resident
+  TotalTimer tt(h, st);
+  h->dec_cache_valid = false;   // the batch-1 activations are overwritten
+  h->pin_img_valid = false;
+  size_t items_cap = B.d_items ? (size_t)BATCH_MAX * 7 : 0;
+  if ((rc = grow_dev(h, &B.d_items, &items_cap, (size_t)BATCH_MAX * 7))) return rc;
+  B.items_shadow.assign(reinterpret_cast<const int32_t*>(items), reinterpret_cast<const int32_t*>(items) + (size_t)7 * n);
+  HIPCHK(h, hipMemcpyAsync(B.d_items, B.items_shadow.data(), (size_t)7 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const float* d_rgb = nullptr;
+  if (any_rgb && (rc = upload_batch_cached(h, rgb, (size_t)n * img, &B.d_rgb, &B.rgb_cap, B.rgb_cache, st, &d_rgb))) return rc;
+  PhotoBlendArgs pa;
+  memset(&pa, 0, sizeof pa);
+  const bool im_dev = photo && is_device_ptr(photo->im), mask_dev = photo && photo->mask && is_device_ptr(photo->mask);
+  if (photo) {
+    if ((rc = upload_batch_cached(h, photo->recon, (size_t)n * img, &B.d_recon, &B.recon_cap, B.recon_cache, st, &pa.recon))) return rc;
+    if ((rc = upload_batch_cached(h, photo->error, (size_t)n * img, &B.d_error, &B.error_cap, B.error_cache, st, &pa.error))) return rc;
+    if (!im_dev && (rc = grow_dev(h, &B.d_im, &B.im_cap, (size_t)BATCH_MAX * img))) return rc;
+    if (photo->mask && !mask_dev && (rc = grow_dev(h, &B.d_mask, &B.mask_cap, (size_t)BATCH_MAX * 64 * 64))) return rc;
+    for (int i = 0; i <= photo->radius; ++i) pa.w[i] = photo->gauss_half[i];
+    pa.radius = photo->radius;
+  }
+  if ((rc = grow_dev(h, &B.d_out, &B.out_cap, (size_t)2 * BATCH_MAX * zl))) return rc;
+  float* st_z = B.d_out;                           // staging of host outputs: z_new rows | dz rows
+  float* st_g = B.d_out + (size_t)BATCH_MAX * zl;
+  const bool z_new_dev = step && is_device_ptr(z_new), dz_dev = dz && is_device_ptr(dz), x_dev = x && is_device_ptr(x);
+  for (int off = 0; off < n; off += pass) {
+    const int nc = std::min(pass, n - off);
+    const size_t zo = (size_t)off * zl, io = (size_t)off * img;
+    if (!hit && (rc = batch_forward(h, z + zo, nc, st))) return rc;
+    if ((rc = ensure_slot(h, h->desc.z_slot, nc, true))) return rc;
+    const int* d_it = B.d_items + (size_t)7 * off;
+    bool updated = false;
+    if ((rc = run_decoder_backward(h, 0, 0, 0, 0, 0, d_rgb ? d_rgb + io : nullptr, st, nullptr, nc, d_it, step, &updated))) return rc;
+    if (step) {
+      if (!updated) HIPCHK(h, launch_latent_update_batch(zs.d, zs.g, zs.cs, d_it, nc, zl, st));
+      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;   // sample_at(z_new)
+      HIPCHK(h, launch_rows_copy(zs.d, zs.cs, z_new_dev ? z_new + zo : st_z + zo, zl, nc, zl, st));
+    }
+    if (dz) HIPCHK(h, launch_rows_copy(zs.g, zs.cs, dz_dev ? dz + zo : st_g + zo, zl, nc, zl, st));
+    if (x) HIPCHK(h, hipMemcpyAsync(x + io, out.d, (size_t)nc * img * sizeof(float), x_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    if (photo) {
+      PhotoBlendArgs a = pa;
+      a.xhat = out.d;
+      a.recon += io;
+      a.error += io;
+      a.im = (im_dev ? photo->im : B.d_im) + io;
+      a.mask = photo->mask ? (mask_dev ? photo->mask : B.d_mask) + (size_t)off * 64 * 64 : nullptr;
+      HIPCHK(h, launch_photo_blend_batch(a, nc, st));
+    }
+  }
+  h->slot_stale[h->desc.out_slot] = 0;
+  bool host_out = x && !x_dev;
+  if (step && !z_new_dev) HIPCHK(h, hipMemcpyAsync(z_new, st_z, (size_t)n * zl * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (dz && !dz_dev) HIPCHK(h, hipMemcpyAsync(dz, st_g, (size_t)n * zl * sizeof(float), hipMemcpyDeviceToHost, st));
+  host_out = host_out || (step && !z_new_dev) || (dz && !dz_dev);
+  if (photo) {
+    if (!im_dev) HIPCHK(h, hipMemcpyAsync(photo->im, B.d_im, (size_t)n * img, hipMemcpyDeviceToHost, st));
+    if (photo->mask && !mask_dev)
+      HIPCHK(h, hipMemcpyAsync(photo->mask, B.d_mask, (size_t)n * 64 * 64 * sizeof(double), hipMemcpyDeviceToHost, st));
+    host_out = host_out || !im_dev || (photo->mask && !mask_dev);
+  }
+  if (host_out) {
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->last_pending = false;
+  }
+  if (step && n <= pass && !z_new_dev) {   // one pass: the resident activations belong to z_new, the next event skips its forward
+    B.cache_z.assign(z_new, z_new + (size_t)n * zl);
+    B.cache_n = n;
+    B.cache_valid = true;
+  }
+  return 0;
+}
 }  // namespace
-

@@ -267,7 +267,8 @@ int find_head_plan(ian_handle* h) {
 }
 
 bool head_fused_active(const ian_handle* h, int n) {
-  return h->head.valid && h->opt.head_fused && h->opt.mdc_head && n >= h->opt.head_fused_min_n;
+  // keep_layer_acts: the batched latent brush runs a backward sweep after this forward and needs every layer's activation
+  return h->head.valid && h->opt.head_fused && h->opt.mdc_head && n >= h->opt.head_fused_min_n && !h->keep_layer_acts;
 }
 
 int run_head_fused(ian_handle* h, int n, hipStream_t st) {

@@ -157,6 +157,7 @@ struct Options {
   int dense_gemv = 1;                // batch-1 backward of the dense layer fed by the latent as one GEMV launch
   int dec_out_px = 1;                // ... and, below that batch, 8 lanes per output pixel instead of 16 tile workgroups
   int dec_out_mfma = 1;              // image-producing deconv (IAN_simple dec_out) on the matrix cores for batches >= 4
+  int brush_pass = 256;              // ian_grad_batch / ian_brush_step_batch: items per forward / backward / forward pass (A/B)
   int fuse_latent_update = 1;        // ian_brush_step: the latent update rides in the epilogue of the latent's backward GEMV (round 5)
   int edit_graph = 1;                // batch-1 host-pointer calls (the NPE edit loop) replay captured hipGraphs
   int edit_spin = 1;                 // ... and their final wait polls the stream (hipStreamQuery) before it falls back to hipStreamSynchronize
@@ -199,7 +200,8 @@ struct ian_handle {
   size_t stage_in_cap = 0;
   float* d_stage_out = nullptr;
   size_t stage_out_cap = 0;
-  float* d_gseed = nullptr;  // 3*H*W gradient seed
+  float* d_gseed = nullptr;  // 3*H*W gradient seed (n*3*H*W after a batched brush call)
+  size_t gseed_cap = 0;
   float* d_rgb = nullptr;
   // decoder-forward cache for the interactive loop (NPE.py:205,218: imgradRGB(z) right after sample_at(z)):
   // the batch-1 decoder activations of the last HOST latent are kept; a gradient call on the same latent skips
@@ -249,9 +251,35 @@ struct ian_handle {
   // set around run_decoder_backward by ian_brush_step: the latent's backward GEMV also applies Z += coef * (dZ * gscale) (one launch
   // less per brush event); done = the fused form was taken (else the caller launches latent_update_kernel)
   struct { const float* cg = nullptr; float* z_mirror = nullptr; float* g_mirror = nullptr; bool done = false; } upd;
+  // several editors (ian_grad_batch / ian_brush_step_batch): the device copy of the ian_brush_item table, the brush colour images,
+  // RECON / ERROR (each with the host shadow of its last upload), staging for host outputs, and the resident-activation cache:
+  // bcache_z = the n latents the decoder activations belong to; enter_stream (every other call) clears bcache_valid
+  struct BatchState {
+    int* d_items = nullptr;
+    std::vector<int32_t> items_shadow;
+    float* d_rgb = nullptr;
+    size_t rgb_cap = 0;
+    std::vector<float> rgb_cache;
+    unsigned char* d_recon = nullptr;
+    size_t recon_cap = 0;
+    std::vector<unsigned char> recon_cache;
+    float* d_error = nullptr;
+    size_t error_cap = 0;
+    std::vector<float> error_cache;
+    float* d_out = nullptr;           // z_new rows | dz rows, packed (n * zl each)
+    size_t out_cap = 0;
+    unsigned char* d_im = nullptr;
+    size_t im_cap = 0;
+    double* d_mask = nullptr;
+    size_t mask_cap = 0;
+    std::vector<float> cache_z;
+    int cache_n = 0;
+    bool cache_valid = false;
+  } batch;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot
   int* d_patch = nullptr;
+  bool keep_layer_acts = false;   // set around the forward passes of ian_grad_batch / ian_brush_step_batch: no fused RGB-Beta head
   EditGraph g_fwd, g_bwd[2], g_step[2][2];   // g_step[mode][image wanted]: backward + latent update + forward (ian_brush_step)
   bool graph_failed = false;
   hipStream_t last_stream = nullptr;   // stream of the last call that left work un-synchronised (or nullptr)

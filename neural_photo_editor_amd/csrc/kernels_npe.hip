@@ -37,9 +37,8 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {  // d c b a | a b c d
 }
 
 constexpr int PB_T = 1024;
-__global__ __launch_bounds__(PB_T) void photo_blend_kernel(PhotoBlendArgs a) {
-  __shared__ double m0[64 * 64];
-  __shared__ double m1[64 * 64];
+// one 64x64 image per workgroup of PB_T threads; m0 / m1 are the workgroup's two 64x64 float64 LDS planes
+__device__ __forceinline__ void photo_blend_image(const PhotoBlendArgs& a, double* m0, double* m1) {
   constexpr int H = 64, W = 64, HW = H * W;
   const int tid = threadIdx.x;
   // ---- min(mean_c |DELTA|, 1): float32 until np.min promotes to float64
@@ -93,9 +92,33 @@ __global__ __launch_bounds__(PB_T) void photo_blend_kernel(PhotoBlendArgs a) {
     }
   }
 }
+__global__ __launch_bounds__(PB_T) void photo_blend_kernel(PhotoBlendArgs a) {
+  __shared__ double m0[64 * 64];
+  __shared__ double m1[64 * 64];
+  photo_blend_image(a, m0, m1);
+}
 hipError_t launch_photo_blend(const PhotoBlendArgs& a, hipStream_t s) {
   if (a.radius < 0 || a.radius > 7) return hipErrorInvalidValue;
   hipLaunchKernelGGL(photo_blend_kernel, dim3(1), dim3(PB_T), 0, s, a);
+  return hipGetLastError();
+}
+// several editors (ian_brush_step_batch): blockIdx.y = item, every image / mask at that item's offset, the same arithmetic per element
+__global__ __launch_bounds__(PB_T) void photo_blend_batch_kernel(PhotoBlendArgs a) {
+  __shared__ double m0[64 * 64];
+  __shared__ double m1[64 * 64];
+  constexpr size_t IMG = 3 * 64 * 64, PLANE = 64 * 64;
+  const size_t i = blockIdx.y;
+  PhotoBlendArgs b = a;
+  b.xhat = a.xhat + i * IMG;
+  b.recon = a.recon + i * IMG;
+  b.error = a.error + i * IMG;
+  b.im = a.im + i * IMG;
+  b.mask = a.mask ? a.mask + i * PLANE : nullptr;
+  photo_blend_image(b, m0, m1);
+}
+hipError_t launch_photo_blend_batch(const PhotoBlendArgs& a, int n, hipStream_t s) {
+  if (a.radius < 0 || a.radius > 7 || n < 1 || n > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(photo_blend_batch_kernel, dim3(1, n), dim3(PB_T), 0, s, a);
   return hipGetLastError();
 }
 

@@ -43,7 +43,7 @@ EXPORTS = (
     "ian_create", "ian_load_param", "ian_set_made_masks", "ian_finalize", "ian_encode", "ian_decode",
     "ian_encode_pre_iaf", "ian_iaf", "ian_reconstruct", "ian_grad_rgb", "ian_grad_light", "ian_decode_u8", "ian_photo_blend",
     "ian_read_slot", "ian_read_slot_grad",
-    "ian_brush_step", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
+    "ian_brush_step", "ian_grad_batch", "ian_brush_step_batch", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
 _lib = None
@@ -100,6 +100,8 @@ def load_library():
     lib.ian_decode_u8.argtypes = [vp, fp, i32, fp, vp]
     lib.ian_photo_blend.argtypes = [vp, fp, fp, fp, fp, i32, fp, fp, vp]
     lib.ian_brush_step.argtypes = [vp, i32, i32, i32, i32, fp, fp, C.c_float, C.c_float, fp, fp, fp, C.POINTER(PhotoArgs), vp]
+    lib.ian_grad_batch.argtypes = [vp, i32, C.POINTER(BrushItem), fp, fp, fp, vp]
+    lib.ian_brush_step_batch.argtypes = [vp, i32, C.POINTER(BrushItem), fp, fp, fp, fp, fp, C.POINTER(PhotoBatchArgs), vp]
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
     lib.ian_read_slot_grad.argtypes = [vp, i32, i32, fp, vp]
     lib.ian_profile_enable.argtypes = [vp, i32]
@@ -122,6 +124,18 @@ def load_library():
 
 class PhotoArgs(C.Structure):
     """ian_photo_args (include/ian.h)."""
+    _fields_ = [("recon", C.c_void_p), ("error", C.c_void_p), ("gauss_half", C.c_void_p), ("radius", C.c_int32),
+                ("im", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class BrushItem(C.Structure):
+    """ian_brush_item (include/ian.h): one edit session's event in ian_grad_batch / ian_brush_step_batch."""
+    _fields_ = [("c1", C.c_int32), ("r1", C.c_int32), ("c2", C.c_int32), ("r2", C.c_int32), ("mode", C.c_int32),
+                ("coef", C.c_float), ("gscale", C.c_float)]
+
+
+class PhotoBatchArgs(C.Structure):
+    """ian_photo_batch_args (include/ian.h)."""
     _fields_ = [("recon", C.c_void_p), ("error", C.c_void_p), ("gauss_half", C.c_void_p), ("radius", C.c_int32),
                 ("im", C.c_void_p), ("mask", C.c_void_p)]
 
@@ -230,6 +244,24 @@ class Handle:
         self._check(self.lib.ian_brush_step(self._h, c1, r1, c2, r2, _ptr(rgb) if rgb is not None else null, _ptr(z), coef, gscale,
                                             _ptr(z_new), _ptr(dz) if dz is not None else null, _ptr(x) if x is not None else null,
                                             C.byref(pa) if pa is not None else None, C.c_void_p(stream or 0)))
+
+    def grad_batch(self, items, rgb, z, dz, stream=None):
+        """ian_grad_batch; items = a ctypes array of BrushItem (n = its length)."""
+        self._check(self.lib.ian_grad_batch(self._h, len(items), items, _ptr(rgb) if rgb is not None else C.c_void_p(0), _ptr(z),
+                                            _ptr(dz), C.c_void_p(stream or 0)))
+
+    def brush_step_batch(self, items, rgb, z, z_new, dz=None, x=None, photo=None, stream=None):
+        """ian_brush_step_batch; photo = (recon_u8 [n,3,64,64], error [n,3,64,64], gauss_half, im [n,3,64,64], mask [n,64,64] or None)."""
+        null = C.c_void_p(0)
+        pa = None
+        if photo is not None:
+            recon, err, half, im, mask = photo
+            pa = PhotoBatchArgs(_ptr(recon).value, _ptr(err).value, _ptr(half).value, len(half) - 1, _ptr(im).value,
+                                _ptr(mask).value if mask is not None else None)
+        self._check(self.lib.ian_brush_step_batch(self._h, len(items), items, _ptr(rgb) if rgb is not None else null, _ptr(z),
+                                                  _ptr(z_new), _ptr(dz) if dz is not None else null,
+                                                  _ptr(x) if x is not None else null, C.byref(pa) if pa is not None else None,
+                                                  C.c_void_p(stream or 0)))
 
     def read_slot(self, slot, n):
         h, w, c = self.lowered.slots[slot]
