@@ -707,7 +707,11 @@ __global__ __launch_bounds__(256) void disc_head_kernel(const float* __restrict_
     int am = 0;
     if (p[1] > p[am]) am = 1;
     if (p[2] > p[am]) am = 2;
-    for (int t = 0; t < 2; ++t) a.loss[(size_t)b * 4 + t] = (a.target[t] >= 0) ? -logf(p[a.target[t]]) : 0.f;
+    // -log p[t] as log-sum-exp: log(e0 + e1 + e2) - (z_t - m).  -logf(p[t]) of the normalised p loses digits once p[t] is denormal
+    // (logit gap ~ 87) and is +inf once it underflows (gap ~ 104); this form is finite for any finite logits.
+    const float lse = logf(e0 + e1 + e2);
+    const float z[3] = {z0, z1, z2};
+    for (int t = 0; t < 2; ++t) a.loss[(size_t)b * 4 + t] = (a.target[t] >= 0) ? lse - (z[a.target[t]] - m) : 0.f;
     a.loss[(size_t)b * 4 + 2] = (am == a.acc_target) ? 1.f : 0.f;
     a.loss[(size_t)b * 4 + 3] = 0.f;
   }

@@ -179,13 +179,22 @@ def nnet_sigmoid(x):
 
 def nnet_softmax(x):
     x = T.as_tensor_variable(x)
-    return Variable(lambda v: torch.softmax(v.to(T.F64), dim=-1), [x], x.ndim, floatX_name)
+    out = Variable(lambda v: torch.softmax(v.to(T.F64), dim=-1), [x], x.ndim, floatX_name)
+    out._softmax_of = x                                  # categorical_crossentropy: log(softmax(x)) -> log_softmax(x)
+    return out
 
 
 def categorical_crossentropy(coding_dist, true_dist):
     """theano.tensor.nnet.categorical_crossentropy for a one-of-N matrix ``true_dist`` of the same rank."""
     if true_dist.ndim == coding_dist.ndim:
-        return -T.sum(true_dist * T.log(coding_dist), axis=coding_dist.ndim - 1)
+        x = getattr(coding_dist, "_softmax_of", None)
+        if x is not None:
+            # Theano rewrites log(softmax(x)) into a stable log-softmax (local_log_softmax): finite for any finite x, where
+            # log of the already normalised probabilities is -inf (and 0 * -inf = NaN under the one-hot) once one underflows
+            logp = Variable(lambda v: torch.log_softmax(v.to(T.F64), dim=-1), [x], x.ndim, floatX_name)
+        else:
+            logp = T.log(coding_dist)
+        return -T.sum(true_dist * logp, axis=coding_dist.ndim - 1)
     raise NotImplementedError("integer-vector targets are not used by the reference")
 
 

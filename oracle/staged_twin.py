@@ -30,7 +30,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .train_twin import BN_EPS, DEC_STAGES, ENC_PARAMS, Z_PARAMS, TrainTwin, ortho_res
+from .train_twin import BN_EPS, DEC_STAGES, ENC_PARAMS, Z_PARAMS, TrainTwin, cross_entropy, ortho_res
 
 
 def _rel(a, b):
@@ -93,7 +93,10 @@ class StagedTwin(TrainTwin):
         n = feat.shape[0]
         abs_dif = (act.unsqueeze(3) - act.permute(1, 2, 0).unsqueeze(0)).abs().sum(2) + 1e6 * torch.eye(n, dtype=feat.dtype).unsqueeze(1)
         f = self.stage(tag, "mbf", torch.exp(-abs_dif).sum(2) + b.unsqueeze(0))           # layers.py:507-520
-        return self.stage(tag, "p", torch.softmax(torch.cat([feat, f], 1) @ P["discrimi.W"], 1))
+        z = torch.cat([feat, f], 1) @ P["discrimi.W"]
+        p = self.stage(tag, "p", torch.softmax(z, 1))
+        p.logits = z                                   # cross_entropy: log-sum-exp of this stage's logits (train_twin.cross_entropy)
+        return p
 
     def latent_s(self, h4, eps):
         P, t = self.P, "ZS"
@@ -141,7 +144,7 @@ class StagedTwin(TrainTwin):
         Xgen = self.decoder_s("DG", self.iaf(Z))
         gXg = self.encoder_s("EG", Xgen)
         pXg = self.discriminator_s("EG", gXg[3])
-        ce = lambda p, k: (-torch.log(p[:, k])).mean()
+        ce = cross_entropy
         L = {}
         L["pixel_loss"] = (2 * (Xhat - X + 1e-8).abs()).mean()
         L["kl_div"] = -0.5 * (1 + 2 * ls - mu ** 2 - torch.exp(2 * ls)).mean()

@@ -158,10 +158,11 @@ def single_process_errors(dp, B):
         tr.backward(which)
         tr._finish_allreduce(which)          # world 1: joins the weight-gradient stream (no collective)
         got, want = dp["%s/metrics" % which], np.array([m[k] for k in sorted(m)])
-        # a saturated cross-entropy (-log of a probability that underflowed: +inf on these well-separated synthetic images at
-        # large batches) must saturate identically in both runs; the finite ones agree to 1e-5
+        # the cross-entropy is computed in log-sum-exp form (disc_head_kernel): finite for any finite logits, also on these
+        # well-separated synthetic images at large batches where -log of an underflowed probability used to be +inf.  Every
+        # metric is finite in both runs and they agree to 1e-5
         fin = np.isfinite(want)
-        assert np.array_equal(np.isfinite(got), fin) and np.array_equal(got[~fin], want[~fin]), (which, got, want)
+        assert fin.all() and np.isfinite(got).all(), (which, got, want)
         assert np.allclose(got[fin], want[fin], rtol=1e-5, atol=1e-6), (which, got, want)
         diag["%s/metrics_max_rel" % which] = float(np.max(np.abs(got[fin] - want[fin]) / (np.abs(want[fin]) + 1e-6)))
         diag["%s/metrics_nonfinite_in_both" % which] = int((~fin).sum())
