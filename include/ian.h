@@ -201,6 +201,78 @@ typedef struct ian_photo_batch_args {
 int ian_brush_step_batch(ian_handle* h, int32_t n, const ian_brush_item* items, const float* rgb, const float* z,
                          float* z_new, float* dz, float* x, const ian_photo_batch_args* photo, void* stream);
 
+/* ---- device-resident edit sessions: the state of NPE.py's globals (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) per editor, in
+   device memory, addressed by session id ----
+   A handle owns a pool of `capacity` sessions; a session is GIM, IM, RECON u8[3,64,64], ERROR f32[3,64,64], Z f32[num_latents] and
+   a mode flag (0 = photo, 1 = sample), about 85 KB.  The caller chooses ids in 0..capacity-1 (no allocator); opening an id again
+   overwrites it.  Every call takes 1 <= n <= 256 sessions in ONE submission on the caller's stream, on the batched path at any
+   n; ids / events are host arrays.  Everything is checked before anything is enqueued or written: an id outside the pool, a
+   session that was not opened (brush, set_latent, re-open from stored state), the same session twice in one call, a rectangle
+   outside the image, a mode outside {0,1} or n outside 1..256 return -7 with a message that names the item, and no session
+   changes.  Models whose image is not 3x64x64 return -7.  The captured-graph ian_brush_step stays the lowest-latency path for
+   ONE editor; session calls invalidate its decoder cache and the resident activations of ian_brush_step_batch. */
+
+/* Allocate the pool (0 frees it; growing or shrinking keeps the sessions whose ids remain).  Synchronises the device. */
+int ian_sessions_reserve(ian_handle* h, int32_t capacity);
+/* The photo blend's Gaussian for every later session call, as in ian_photo_batch_args: gauss_half f64[radius+1] (host; the
+   host computes it exactly as scipy does: npe_ops.gaussian_half_kernel), radius 0..7.  NPE.py:224 is sigma 0.7, radius 3.
+   ian_session_brush and ian_session_set_latent with as_sample = 0 return -6 until it was called. */
+int ian_sessions_set_blend(ian_handle* h, const double* gauss_half, int32_t radius);
+
+/* NPE.py:239-274 infer (photos given), :330-340 Reset (photos NULL, source 0: from the stored GIM), :342-345 UpdateGIM (photos
+   NULL, source 1: GIM := IM first) for n sessions.  photos u8[n,3,64,64], host or device (4-byte aligned).  Per session
+     Z     = encode_images(np.asarray([to_tanh(GIM)], dtype=np.float32))     float64 to_tanh, one rounding: NPE.py:257
+     RECON = np.uint8(from_tanh(sample_at(Z)))                               NPE.py:261
+     ERROR = to_tanh(np.float32(GIM)) - to_tanh(np.float32(RECON))           float32: NPE.py:264
+     IM = GIM, mode = photo (SAMPLE_FLAG = 0)
+   with the encoder and decoder run exactly as ian_encode / ian_decode_u8 run them at batch n (bitwise their Z and RECON);
+   the uint8 photo is what crosses the bus, not a 48 KB float image.  shown u8[n,3,64,64] (host or device) or NULL receives IM. */
+int ian_session_open(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t* photos, int32_t source, uint8_t* shown,
+                     void* stream);
+/* z f32[n,num_latents], host or device.
+   as_sample = 1: NPE.py:317-327 sample with the caller's z (the reference draws it with numpy; that stays on the host):
+     Z := z; RECON := np.uint8(from_tanh(sample_at(z))); ERROR := to_tanh(np.float32(IM)) - to_tanh(np.float32(RECON));
+     mode := sample; shown = RECON.
+   as_sample = 0: NPE.py:286-302 paint_latents: Z := z; shown = the photo blend of sample_at(z) against RECON / ERROR in photo
+     mode, np.uint8(from_tanh(sample_at(z))) in sample mode; the stored IM is not changed (IM is local to that callback). */
+int ian_session_set_latent(ian_handle* h, int32_t n, const int32_t* ids, const float* z, int32_t as_sample, uint8_t* shown,
+                           void* stream);
+
+typedef struct ian_session_event {
+  int32_t session;          /* id in the pool */
+  int32_t c1, r1, c2, r2;   /* API.py:66-76 rectangle; an empty one gives a zero gradient */
+  int32_t mode;             /* 1: imgradRGB toward the constant colour rgb (NPE.py:205 myRGB); 0: imgrad (NPE.py:311) */
+  float coef, gscale;       /* Z := Z + coef * (dZ * gscale), the expression of ian_brush_step_batch */
+  float rgb[3];             /* the brush colour in tanh space: np.float32(to_tanh(np.float32(level))) per channel */
+} ian_session_event;
+
+/* NPE.py:192-235 paint / :305-316 scroll for n sessions: per event, on the session's state, the brush gradient (against the
+   constant colour for mode 1), Z := Z + coef * (dZ * gscale), x = sample_at(Z); then what the callback displays:
+     mode 1 on a session in photo mode: the NPE.py:218-231 blend against the session's RECON / ERROR, written to its IM and to
+       shown[i];
+     a session in sample mode, and mode 0 in either mode (NPE.scroll ends in update_photo(None)): shown[i] =
+       np.uint8(from_tanh(x)), IM untouched.
+   Bitwise what ian_brush_step_batch gives for the same latents, boxes and constant-colour rgb images in the same order.
+   Host -> device: the event table (11 words per event); device -> host: shown (u8[n,3,64,64], host or device, or NULL).
+   The forward at Z is skipped when the decoder's activations were left by the previous ian_session_brush for the same
+   ids in the same order at the same latent versions, with no other call in between (IAN_NO_DEC_CACHE switches that off). */
+int ian_session_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, void* stream);
+
+enum ian_session_field {
+  IAN_SESSION_Z = 0,     /* f32[num_latents] */
+  IAN_SESSION_RECON = 1, /* u8[3,64,64] */
+  IAN_SESSION_ERROR = 2, /* f32[3,64,64] */
+  IAN_SESSION_IM = 3,    /* u8[3,64,64] */
+  IAN_SESSION_GIM = 4,   /* u8[3,64,64] */
+  IAN_SESSION_MODE = 5   /* int32: 0 photo, 1 sample */
+};
+/* One field of an opened session -> out (host or device): tests, saving a picture (NPE.py has no counterpart: its state is
+   host globals).  Leaves the resident activations alone. */
+int ian_session_read(ian_handle* h, int32_t id, int32_t what, void* out, void* stream);
+/* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
+   np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
+void ian_session_tanh_table(float* out256);
+
 /* Introspection used by tests, bench.py and profiling (not part of the reference surface). */
 /* Copy the activation of tensor slot `slot` from the last call, converted to NCHW, into out (host or device). */
 int ian_read_slot(ian_handle* h, int32_t slot, int32_t n, float* out, void* stream);

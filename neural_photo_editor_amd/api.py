@@ -22,7 +22,7 @@ import warnings
 import numpy as np
 
 from . import checkpoints, config_loader, lowering, made
-from .lib import BrushItem, Handle
+from .lib import BrushItem, Handle, SessionEvent
 
 BATCH_MAX = 256     # ian_grad_batch / ian_brush_step_batch: 1 <= n <= 256
 
@@ -66,6 +66,205 @@ def pack_brush_items(boxes, n_rgb=None, modes=None, weight=0.0, sign=1.0):
         it.coef = sg[i] * w[i]                 # rounded to float32 by ctypes, as numpy rounds the scalar
         it.gscale = float(1 + (c2 - c1))
     return items
+
+
+def brush_colour(levels):
+    """Brush colour levels (0..255 per channel, NPE.py:87,359 myRGB) -> the tanh-space float32 triple of ian_session_event:
+    np.float32(to_tanh(np.float32(level))), exactly what npe_ops.paint_event feeds brush_step."""
+    from . import npe_ops
+    c = np.float32(npe_ops.to_tanh(np.float32(np.asarray(levels))))
+    if c.shape != (3,):
+        raise ValueError("a brush colour has 3 levels, got shape %s" % (c.shape,))
+    return c
+
+
+def check_session_ids(ids, capacity=None, opened=None):
+    """Session ids of one call -> a contiguous int32 array, or ValueError: 1..256 integers, each inside the pool (when capacity is
+    given), opened (when `opened`, a container of opened ids, is given) and named once."""
+    a = np.asarray(ids)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("ids must be a 1-D array of integers, got shape %s dtype %s" % (a.shape, a.dtype))
+    if not 1 <= a.shape[0] <= BATCH_MAX:
+        raise ValueError("a call holds 1..%d sessions, got %d" % (BATCH_MAX, a.shape[0]))
+    seen = {}
+    for i, v in enumerate(int(t) for t in a):
+        if v < 0 or (capacity is not None and v >= capacity):
+            raise ValueError("item %d: session %d outside the pool%s" % (i, v, "" if capacity is None else " (capacity %d)" % capacity))
+        if opened is not None and v not in opened:
+            raise ValueError("item %d: session %d has not been opened" % (i, v))
+        if v in seen:
+            raise ValueError("item %d: session %d already appears as item %d of this call" % (i, v, seen[v]))
+        seen[v] = i
+    return np.ascontiguousarray(a, np.int32)
+
+
+def pack_session_events(ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, capacity=None, opened=None):
+    """Python arguments of ian_session_brush -> a ctypes array of ian_session_event (include/ian.h), validated before the library
+    sees anything.  ids (n,) session ids; boxes (n,4) or (4,) as (c1, r1, c2, r2), floats truncated as imgrad's int() does;
+    colours (n,3) or (3,) uint8-range levels, or None (then every mode is 0); modes default to 1 with colours and 0 without;
+    weight and sign are scalars or length-n arrays: coef = float32(sign*weight), gscale = float32(1 + (c2 - c1)).
+    capacity / opened (a container of opened ids), when given, bound and vet the ids."""
+    idl = [int(v) for v in check_session_ids(ids, capacity, opened)]
+    n = len(idl)
+    b = np.asarray(boxes)
+    if b.ndim == 1 and b.shape == (4,):
+        b = np.tile(b, (n, 1))
+    if b.ndim != 2 or b.shape != (n, 4):
+        raise ValueError("boxes must have shape (%d,4) or (4,) as (c1,r1,c2,r2), got %s" % (n, b.shape))
+    col = None
+    if colours is not None:
+        col = np.asarray(colours)
+        if col.shape == (3,):
+            col = np.tile(col, (n, 1))
+        if col.shape != (n, 3):
+            raise ValueError("colours must have shape (%d,3) or (3,), got %s" % (n, col.shape))
+    if modes is None:
+        m = [1 if col is not None else 0] * n
+    else:
+        ma = np.asarray(modes).reshape(-1)
+        m = [int(v) for v in (np.tile(ma, n) if ma.shape == (1,) else ma)]
+        if len(m) != n:
+            raise ValueError("modes must be a scalar or have length %d, got %d" % (n, len(m)))
+        for i, v in enumerate(m):
+            if v not in (0, 1):
+                raise ValueError("item %d has mode %d (0 = imgrad, 1 = imgradRGB)" % (i, v))
+        if col is None and any(m):
+            raise ValueError("item %d has mode 1 (imgradRGB) but no colour was given" % m.index(1))
+    def per_item(v, what):
+        a = np.asarray(v, np.float64)
+        if a.ndim == 0:
+            return [float(a)] * n
+        if a.shape != (n,):
+            raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (what, n, a.shape))
+        return [float(t) for t in a]
+    w, sg = per_item(weight, "weight"), per_item(sign, "sign")
+    ev = (SessionEvent * n)()
+    for i in range(n):
+        c1, r1, c2, r2 = [int(v) for v in b[i]]
+        if c1 < 0 or r1 < 0 or c2 > 64 or r2 > 64:
+            raise ValueError("item %d: patch (%d,%d,%d,%d) outside the 64x64 image" % (i, c1, r1, c2, r2))
+        e = ev[i]
+        e.session, e.c1, e.r1, e.c2, e.r2, e.mode = idl[i], c1, r1, c2, r2, m[i]
+        e.coef = sg[i] * w[i]                  # rounded to float32 by ctypes, as numpy rounds the scalar
+        e.gscale = float(1 + (c2 - c1))
+        if col is not None:
+            e.rgb[0], e.rgb[1], e.rgb[2] = [float(v) for v in brush_colour(col[i])]
+    return ev
+
+
+class EditSessions:
+    """Device-resident edit sessions of one model (ian_session_*, include/ian.h): the state NPE.py keeps in host globals per
+    editor (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) lives in device memory under a caller-chosen id in 0..capacity-1.  A call takes
+    up to 256 sessions in one submission and returns what the canvases show: uint8 (n,3,64,64).
+        open    infer (NPE.py:239-274)          reset   Reset (:330-340)           commit  UpdateGIM (:342-345)
+        sample  sample (:317-327), z from the caller                                set_latent  paint_latents (:286-302)
+        paint   NPE.paint (:192-235)            scroll  NPE.scroll (:305-316)      brush   the general form of both"""
+
+    def __init__(self, handle, capacity, zdim, sigma=0.7):
+        from . import npe_ops
+        self._h = handle
+        self._zdim = zdim
+        self.capacity = 0
+        self._opened = set()
+        self.reserve(capacity)
+        self._h.sessions_set_blend(npe_ops.gaussian_half_kernel(sigma, int(4.0 * float(sigma) + 0.5)))
+
+    def reserve(self, capacity):
+        """Grow (or shrink) the pool; sessions whose ids remain keep their state."""
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("a session pool holds at least one session, got %d" % capacity)
+        self._h.sessions_reserve(capacity)
+        self.capacity = capacity
+        self._opened = {v for v in self._opened if v < capacity}
+
+    def _ids(self, ids, need_opened):
+        return check_session_ids(ids, self.capacity, self._opened if need_opened else None)
+
+    def _latents(self, z, n):
+        z = np.ascontiguousarray(np.asarray(z, dtype=np.float32)).reshape(-1, self._zdim)
+        if z.shape[0] != n:
+            raise ValueError("z holds %d latents for %d sessions" % (z.shape[0], n))
+        return z
+
+    def open(self, ids, photos):
+        """infer: photos uint8 (n,3,64,64) (or (3,64,64) for one id) -> IM."""
+        ids = self._ids(ids, False)
+        p = np.asarray(photos)
+        if p.dtype != np.uint8:
+            raise ValueError("photos must be uint8, got %s" % p.dtype)
+        if p.shape == (3, 64, 64):
+            p = p[None]
+        if p.shape != (len(ids), 3, 64, 64):
+            raise ValueError("photos must have shape (%d,3,64,64), got %s" % (len(ids), p.shape))
+        shown = np.empty((len(ids), 3, 64, 64), np.uint8)
+        self._h.session_open(ids, np.ascontiguousarray(p), 0, shown)
+        self._opened.update(int(v) for v in ids)
+        return shown
+
+    def reset(self, ids):
+        """Reset: re-open from the stored GIM."""
+        ids = self._ids(ids, True)
+        shown = np.empty((len(ids), 3, 64, 64), np.uint8)
+        self._h.session_open(ids, None, 0, shown)
+        return shown
+
+    def commit(self, ids):
+        """UpdateGIM: GIM := IM, then Reset."""
+        ids = self._ids(ids, True)
+        shown = np.empty((len(ids), 3, 64, 64), np.uint8)
+        self._h.session_open(ids, None, 1, shown)
+        return shown
+
+    def sample(self, ids, z):
+        """sample with the caller's z (n, zdim): the sessions go to sample mode -> RECON."""
+        ids = self._ids(ids, True)
+        shown = np.empty((len(ids), 3, 64, 64), np.uint8)
+        self._h.session_set_latent(ids, self._latents(z, len(ids)), 1, shown)
+        return shown
+
+    def set_latent(self, ids, z):
+        """paint_latents: Z := z -> the blended photo (photo mode) or the sample (sample mode); the stored IM stays."""
+        ids = self._ids(ids, True)
+        shown = np.empty((len(ids), 3, 64, 64), np.uint8)
+        self._h.session_set_latent(ids, self._latents(z, len(ids)), 0, shown)
+        return shown
+
+    def brush(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0):
+        """n brush events (pack_session_events) in one submission -> shown."""
+        ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
+        shown = np.empty((len(ev), 3, 64, 64), np.uint8)
+        self._h.session_brush(ev, shown)
+        return shown
+
+    def paint(self, ids, boxes, colours_uint8, weight=0.05):
+        """NPE.paint: Z -= weight * grad toward the brush colour (levels 0..255 per channel)."""
+        return self.brush(ids, boxes, colours_uint8, None, weight, -1.0)
+
+    def scroll(self, ids, boxes, signs, weight=0.1):
+        """NPE.scroll: Z += sign(event.delta) * weight * grad of the patch mean."""
+        return self.brush(ids, boxes, None, None, weight, signs)
+
+    def read(self, sid):
+        """-> {"Z" (zdim,), "RECON", "ERROR", "IM", "GIM" (3,64,64), "MODE" int}.  Six synchronising copies (one ian_session_read
+        per field): for tests and for saving a picture, not for the event loop."""
+        sid = int(sid)
+        if not 0 <= sid < self.capacity:
+            raise ValueError("session %d outside the pool (capacity %d)" % (sid, self.capacity))
+        if sid not in self._opened:
+            raise ValueError("session %d has not been opened" % sid)
+        out = {k: self._h.session_read(sid, k) for k in ("Z", "RECON", "ERROR", "IM", "GIM")}
+        out["MODE"] = int(self._h.session_read(sid, "MODE")[0])
+        return out
+
+    def close(self):
+        """Free the pool."""
+        if self.capacity:
+            self._h.sessions_reserve(0)
+            self.capacity = 0
+            self._opened = set()
 
 
 class IAN:
@@ -252,6 +451,11 @@ class IAN:
         if photo is not None:
             return z_new, x, pa[3], pa[4]
         return z_new, x
+
+    def sessions(self, capacity, sigma=0.7):
+        """Device-resident edit sessions of this model (ian_session_*): -> EditSessions with `capacity` ids.  One pool per model:
+        a second call re-sizes it (sessions whose ids remain keep their state) and the earlier object's bookkeeping is stale."""
+        return EditSessions(self._h, capacity, self._zdim, sigma)
 
     # ---- sample_IAN.py function equivalents (SURVEY M3) ----------------------------------------------
     def sampleZ(self, z):

@@ -344,6 +344,46 @@ hipError_t launch_latent_update(float* z, const float* g, const float* cg, int n
 hipError_t launch_keep_warm(const int* flag, long long max_ticks, hipStream_t s);   // experiment: see kernels_npe.hip
 hipError_t launch_to_uint8(const float* x, unsigned char* y, long long n, hipStream_t s);
 
+// device-resident edit sessions (kernels_session.hip; ian_session_*): the pool's arrays, one row per session id
+struct SessionPool {
+  unsigned char* gim;     // GIM   u8 [capacity][3*64*64]
+  unsigned char* im;      // IM    u8 [capacity][3*64*64]
+  unsigned char* recon;   // RECON u8 [capacity][3*64*64]
+  float* error;           // ERROR f32[capacity][3*64*64]
+  float* z;               // Z     f32[capacity][zl]
+  int* mode;              // 0 = photo, 1 = sample (NPE.py SAMPLE_FLAG)
+  int zl;
+};
+// open, input side: row i = photos[i] (u8 [n][3*64*64]) or, without photos, the session's GIM (source 0) / IM (source 1) -> GIM, IM and
+// x[i] = table[byte] (float32 NCHW, the encoder's input slot); ids = device int[n]; table = 256 floats, to_tanh per level
+hipError_t launch_session_open_in(const unsigned char* photos, const SessionPool& P, const int* ids, int source, const float* table,
+                                  float* x, int n, hipStream_t s);
+// open / sample, output side: RECON, ERROR (against IM), Z (row i of the latent slot, stride zs) and the mode flag of session ids[i];
+// shown (or nullptr) [n][3*64*64] receives RECON (shown_recon != 0) or IM
+hipError_t launch_session_store(const float* xhat, const float* zslot, int zs, const SessionPool& P, const int* ids, int new_mode,
+                                int shown_recon, unsigned char* shown, int n, hipStream_t s);
+hipError_t launch_session_gather_z(const SessionPool& P, const int* ids, float* zslot, int zs, int n, hipStream_t s);
+struct SessionBlendArgs {
+  const float* xhat;      // decoder output, NCHW [n][3][64][64]
+  const float* zslot;     // latent slot, row i = item i (stride zs): written back to the session's Z
+  int zs;
+  SessionPool P;
+  const int* ids;         // device int[n]
+  const int* items;       // device ian_brush_item table (7 words per item; word 4 = loss kind) or nullptr = every item paints
+  unsigned char* shown;   // [n][3*64*64]
+  int store;              // photo mode: != 0 the blend also becomes the session's IM
+  double w[8];            // as PhotoBlendArgs
+  int radius;
+};
+hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s);
+// the batched loss seeds with a constant brush colour per item: colour[3*i + co] where launch_patch_seed_batch /
+// launch_deconv_out_bwd_seed_batch read rgb[i][co][y][x]
+hipError_t launch_patch_seed_colour_batch(const float* xhat, const float* colour, float* g, int H, int W, const int* items, int n,
+                                          hipStream_t s);
+hipError_t launch_deconv_out_bwd_seed_colour_batch(const float* xhat, const float* colour, const int* items, int n, int out_act,
+                                                   const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale,
+                                                   int H, int W, int Cin, int Cout, int act, hipStream_t s);
+
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,
                             long long npix, int C, int act, int accumulate, hipStream_t s);

@@ -608,6 +608,7 @@ int ian_set_option(ian_handle* h, const char* key, int32_t value) {
   ++h->alloc_epoch;
   h->dec_cache_valid = false;   // the resident activations were produced under the previous options
   h->batch.cache_valid = false;
+  h->sess.res_valid = false;
   return 0;
 }
 
@@ -645,6 +646,7 @@ void ian_destroy(ian_handle* h) {
   for (void* p : {(void*)h->batch.d_items, (void*)h->batch.d_rgb, (void*)h->batch.d_recon, (void*)h->batch.d_error, (void*)h->batch.d_out,
                   (void*)h->batch.d_im, (void*)h->batch.d_mask})
     if (p) (void)hipFree(p);
+  sessions_free(h);
   for (auto& e : h->ev_pool) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);

@@ -19,9 +19,10 @@ struct ProducerEpi {
 // Several editors (ian_grad_batch / ian_brush_step_batch): d_items = the device copy of n ian_brush_item records (rectangle, loss
 // kind, coef, gscale per item); mode / c1..r2 / d_patch are unused then, d_rgb is [n,3,H,W].  update: the latent's backward also
 // applies each item's brush update to the z slot (*updated = it did).  Without d_items: today's batch-1 launches, unchanged.
+// d_colour (batched only; ian_session_brush): [n][3] constant brush colours that stand in for d_rgb in the seed launches.
 int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2, const float* d_rgb, hipStream_t st,
                          const int* d_patch = nullptr, int n = 1, const int* d_items = nullptr, bool update = false,
-                         bool* updated = nullptr) {
+                         bool* updated = nullptr, const float* d_colour = nullptr) {
   const bool batched = d_items != nullptr;
   if (!batched) n = 1;
   if (updated) *updated = false;
@@ -51,7 +52,8 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
   }
   // interactive loop + image-producing deconv (IAN_simple): seed, tanh' and the first backward-data in one launch (fused_seed above)
   if (fused_seed) {
-  } else if (batched) HIPCHK(h, launch_patch_seed_batch(out.d, d_rgb, h->d_gseed, H, W, d_items, n, st));
+  } else if (batched && d_colour) HIPCHK(h, launch_patch_seed_colour_batch(out.d, d_colour, h->d_gseed, H, W, d_items, n, st));
+  else if (batched) HIPCHK(h, launch_patch_seed_batch(out.d, d_rgb, h->d_gseed, H, W, d_items, n, st));
   else if (d_patch) HIPCHK(h, launch_patch_seed_dev(out.d, d_rgb, h->d_gseed, H, W, d_patch, mode, st));
   else HIPCHK(h, launch_patch_seed(out.d, d_rgb, h->d_gseed, H, W, c1, r1, c2, r2, mode, st));  // dL/dX_hat, NCHW
 
@@ -104,7 +106,10 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
       if ((rc = ensure_slot(h, op.d.src, n, true))) return rc;
       ProducerEpi e = epi_of(op.d.src);
       if (e.scale_period) return fail(h, -9, "imgrad: per-feature batch-norm directly under the image deconv");
-      if (fused_seed && batched) {
+      if (fused_seed && batched && d_colour) {
+        HIPCHK(h, launch_deconv_out_bwd_seed_colour_batch(out.d, d_colour, d_items, n, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd,
+                                                          e.scale, op.d.in_h, op.d.in_w, in.cs, op.d.cout, e.act, st));
+      } else if (fused_seed && batched) {
         HIPCHK(h, launch_deconv_out_bwd_seed_batch(out.d, d_rgb, d_items, n, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd, e.scale,
                                                    op.d.in_h, op.d.in_w, in.cs, op.d.cout, e.act, st));
       } else if (fused_seed) {

@@ -14,6 +14,7 @@ void warm_release(ian_handle* h) {
 void enter_stream(ian_handle* h, hipStream_t st) {
   warm_release(h);     // whatever comes next must not queue behind the keep-warm kernel
   h->batch.cache_valid = false;   // the batched calls' resident activations survive only until the next call
+  h->sess.res_valid = false;      // ... and so do those of ian_session_brush
   if (h->last_pending && h->last_stream != st) (void)hipStreamSynchronize(h->last_stream);
   h->last_stream = st;
   h->last_pending = true;   // cleared by callers that synchronise before returning
@@ -365,6 +366,23 @@ int batch_forward(ian_handle* h, const float* z, int nc, hipStream_t st) {
   return 0;
 }
 
+// What every batched brush call runs between "the latent slot holds nc latents and the decoder's activations belong to them" and its
+// outputs: the batched seed + backward sweep (d_rgb: [nc,3,H,W] colour images, or d_colour: [nc][3] constant colours) and, for a step,
+// the brush update (fused into the latent's GEMV where that form is taken) and the forward at z_new.  Shared by batch_common and
+// the session calls (ian_rt_session.inc).
+int brush_pass_middle(ian_handle* h, int nc, const int* d_it, const float* d_rgb, const float* d_colour, bool step, hipStream_t st) {
+  int rc;
+  Slot& zs = h->slots[h->desc.z_slot];
+  if ((rc = ensure_slot(h, h->desc.z_slot, nc, true))) return rc;
+  bool updated = false;
+  if ((rc = run_decoder_backward(h, 0, 0, 0, 0, 0, d_rgb, st, nullptr, nc, d_it, step, &updated, d_colour))) return rc;
+  if (step) {
+    if (!updated) HIPCHK(h, launch_latent_update_batch(zs.d, zs.g, zs.cs, d_it, nc, h->desc.num_latents, st));
+    if ((rc = batch_forward(h, nullptr, nc, st))) return rc;   // sample_at(z_new)
+  }
+  return 0;
+}
+
 // Item i is one single-image call on (z[i], items[i], rgb[i]).  Per pass of at most opt.brush_pass items: the decoder forward (skipped when
 // the activations the previous ian_brush_step_batch left resident belong to these very latents), the batched seed + backward sweep,
 // [the brush update fused into the latent's GEMV and the forward at z_new,] [the batched photo blend].  Then the outputs, with one
@@ -430,13 +448,9 @@ int batch_common(ian_handle* h, int n, const ian_brush_item* items, const float*
     const int nc = std::min(pass, n - off);
     const size_t zo = (size_t)off * zl, io = (size_t)off * img;
     if (!hit && (rc = batch_forward(h, z + zo, nc, st))) return rc;
-    if ((rc = ensure_slot(h, h->desc.z_slot, nc, true))) return rc;
     const int* d_it = B.d_items + (size_t)7 * off;
-    bool updated = false;
-    if ((rc = run_decoder_backward(h, 0, 0, 0, 0, 0, d_rgb ? d_rgb + io : nullptr, st, nullptr, nc, d_it, step, &updated))) return rc;
+    if ((rc = brush_pass_middle(h, nc, d_it, d_rgb ? d_rgb + io : nullptr, nullptr, step, st))) return rc;
     if (step) {
-      if (!updated) HIPCHK(h, launch_latent_update_batch(zs.d, zs.g, zs.cs, d_it, nc, zl, st));
-      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;   // sample_at(z_new)
       HIPCHK(h, launch_rows_copy(zs.d, zs.cs, z_new_dev ? z_new + zo : st_z + zo, zl, nc, zl, st));
     }
     if (dz) HIPCHK(h, launch_rows_copy(zs.g, zs.cs, dz_dev ? dz + zo : st_g + zo, zl, nc, zl, st));

@@ -1,0 +1,360 @@
+// ian_rt_session.inc -- device-resident edit sessions: the pool, open / set_latent / brush / read by session id.
+// Part of the libian runtime: one translation unit, included by ian_runtime.cpp in this order (see the list there).
+//
+// What NPE.py keeps in host globals per editor (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) is one row per session id in each array of
+// h->sess.pool.  A call names sessions by id; per brush call the only host -> device traffic is the event table (11 words per
+// event) and the only device -> host traffic the canvas images.  The host keeps, per session, whether it was opened and a
+// counter of its latent's versions (the residency key of ian_session_brush is n ids + n counters, not the latents' bytes).
+namespace {
+
+constexpr size_t SESS_IMG = 3 * 64 * 64;
+constexpr int SESS_MAX_CAPACITY = 1 << 20;
+
+// np.asarray([to_tanh(IM)], dtype=np.float32) per uint8 level: float64 2.0*(v/255.0)-1.0, then one rounding to float32
+void session_tanh_table(float* out) {
+  for (int v = 0; v < 256; ++v) {
+    volatile double q = (double)v / 255.0;
+    volatile double t = 2.0 * q;
+    out[v] = (float)(t - 1.0);
+  }
+}
+
+void sessions_free(ian_handle* h) {
+  auto& S = h->sess;
+  SessionPool& P = S.pool;
+  for (void* p : {(void*)P.gim, (void*)P.im, (void*)P.recon, (void*)P.error, (void*)P.z, (void*)P.mode, (void*)S.d_tab, (void*)S.d_tanh,
+                  (void*)S.d_photo, (void*)S.d_shown})
+    if (p) (void)hipFree(p);
+  P = SessionPool{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  S.d_tab = nullptr;
+  S.d_tanh = nullptr;
+  S.d_photo = S.d_shown = nullptr;
+  S.capacity = 0;
+  S.opened.clear();
+  S.version.clear();
+  S.res_valid = false;
+}
+
+// session calls need the 3x64x64 image on both ends (the pool rows, the blend and the open kernels are written for it)
+int session_model_check(ian_handle* h, const char* fn) {
+  const Slot& os = h->slots[h->desc.out_slot];
+  const Slot& xs = h->slots[h->desc.x_slot];
+  if (os.h != 64 || os.w != 64 || os.c != 3 || !os.nchw || xs.h != 64 || xs.w != 64 || xs.c != 3 || !xs.nchw)
+    return fail(h, -7, "%s: edit sessions need a model with a 3x64x64 image", fn);
+  return 0;
+}
+
+int sessions_reserve(ian_handle* h, int capacity) {
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  if ((rc = session_model_check(h, "ian_sessions_reserve"))) return rc;
+  if (capacity < 0 || capacity > SESS_MAX_CAPACITY) return fail(h, -7, "ian_sessions_reserve: capacity %d outside 0..%d", capacity, SESS_MAX_CAPACITY);
+  auto& S = h->sess;
+  HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that move
+  h->last_pending = false;
+  S.res_valid = false;
+  if (capacity == 0) {
+    sessions_free(h);
+    return 0;
+  }
+  const int zl = h->desc.num_latents;
+  if (capacity != S.capacity) {
+    SessionPool N{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, zl};
+    const size_t c = (size_t)capacity, keep = (size_t)std::min(capacity, S.capacity);
+    auto grow = [&](void** dst, const void* src, size_t row_bytes) -> hipError_t {
+      hipError_t e = hipMalloc(dst, c * row_bytes);
+      if (e == hipSuccess && keep) e = hipMemcpy(*dst, src, keep * row_bytes, hipMemcpyDeviceToDevice);
+      return e;
+    };
+    hipError_t e = grow((void**)&N.gim, S.pool.gim, SESS_IMG);
+    if (e == hipSuccess) e = grow((void**)&N.im, S.pool.im, SESS_IMG);
+    if (e == hipSuccess) e = grow((void**)&N.recon, S.pool.recon, SESS_IMG);
+    if (e == hipSuccess) e = grow((void**)&N.error, S.pool.error, SESS_IMG * sizeof(float));
+    if (e == hipSuccess) e = grow((void**)&N.z, S.pool.z, (size_t)zl * sizeof(float));
+    if (e == hipSuccess) e = grow((void**)&N.mode, S.pool.mode, sizeof(int));
+    if (e != hipSuccess) {   // the old pool stays as it was
+      for (void* p : {(void*)N.gim, (void*)N.im, (void*)N.recon, (void*)N.error, (void*)N.z, (void*)N.mode})
+        if (p) (void)hipFree(p);
+      (void)hipGetLastError();
+      return fail(h, -2, "ian_sessions_reserve: %s for %d sessions of %zu bytes", hipGetErrorString(e), capacity,
+                  3 * SESS_IMG + SESS_IMG * sizeof(float) + (size_t)zl * sizeof(float) + sizeof(int));
+    }
+    for (void* p : {(void*)S.pool.gim, (void*)S.pool.im, (void*)S.pool.recon, (void*)S.pool.error, (void*)S.pool.z, (void*)S.pool.mode})
+      if (p) (void)hipFree(p);
+    S.pool = N;
+    S.capacity = capacity;
+    S.opened.resize(c, 0);
+    S.version.resize(c, 0);
+  }
+  if (!S.d_tab) HIPCHK(h, hipMalloc((void**)&S.d_tab, (size_t)BATCH_MAX * 11 * sizeof(int32_t)));
+  if (!S.d_shown) HIPCHK(h, hipMalloc((void**)&S.d_shown, (size_t)BATCH_MAX * SESS_IMG));
+  if (!S.d_tanh) {
+    float tab[256];
+    session_tanh_table(tab);
+    HIPCHK(h, hipMalloc((void**)&S.d_tanh, sizeof tab));
+    HIPCHK(h, hipMemcpy(S.d_tanh, tab, sizeof tab, hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
+int sessions_set_blend(ian_handle* h, const double* gauss_half, int radius) {
+  if (!h) return -1;
+  if (!gauss_half) return fail(h, -1, "null pointer passed to ian_sessions_set_blend");
+  if (radius < 0 || radius > 7) return fail(h, -7, "ian_sessions_set_blend: radius %d outside 0..7", radius);
+  if (is_device_ptr(gauss_half)) return fail(h, -7, "ian_sessions_set_blend: gauss_half must be a host array");
+  for (int i = 0; i < 8; ++i) h->sess.w[i] = i <= radius ? gauss_half[i] : 0.0;
+  h->sess.radius = radius;
+  return 0;
+}
+
+// what every session call checks first: the model, the pool, n; then per item its id (ids[i * stride]).  Nothing is enqueued or
+// written before all of it passed.
+int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int stride, bool need_opened, bool need_blend) {
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  if ((rc = session_model_check(h, fn))) return rc;
+  auto& S = h->sess;
+  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: n = %d outside 1..%d", fn, n, BATCH_MAX);
+  if (!ids) return fail(h, -1, "null pointer passed to %s", fn);
+  if (is_device_ptr(ids)) return fail(h, -7, "%s: the session ids / events must be a host array", fn);
+  if (need_blend && S.radius < 0) return fail(h, -6, "%s: the photo blend's Gaussian is not set (call ian_sessions_set_blend first)", fn);
+  std::map<int, int> first;
+  for (int i = 0; i < n; ++i) {
+    const int id = ids[(size_t)i * stride];
+    if (id < 0 || id >= S.capacity) return fail(h, -7, "%s: item %d: session %d outside the pool (capacity %d)", fn, i, id, S.capacity);
+    if (need_opened && !S.opened[id]) return fail(h, -7, "%s: item %d: session %d has not been opened", fn, i, id);
+    auto ins = first.emplace(id, i);
+    if (!ins.second) return fail(h, -7, "%s: item %d: session %d already appears as item %d of this call", fn, i, id, ins.first->second);
+  }
+  return 0;
+}
+
+// start of the enqueueing part of a session call: stream hand-over, the other paths' caches (as batch_common)
+void session_enter(ian_handle* h, hipStream_t st) {
+  enter_stream(h, st);
+  h->dec_cache_valid = false;   // the batch-1 activations are overwritten
+  h->pin_img_valid = false;
+}
+
+int session_upload_ids(ian_handle* h, int n, const int32_t* ids, hipStream_t st) {
+  auto& S = h->sess;
+  S.tab_shadow.assign(ids, ids + n);
+  HIPCHK(h, hipMemcpyAsync(S.d_tab, S.tab_shadow.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// end of a call: the canvas images to the caller; one synchronisation when host memory was read or written
+int session_finish(ian_handle* h, int n, uint8_t* shown, bool shown_dev, bool host_in, hipStream_t st) {
+  if (shown && !shown_dev) HIPCHK(h, hipMemcpyAsync(shown, h->sess.d_shown, (size_t)n * SESS_IMG, hipMemcpyDeviceToHost, st));
+  if ((shown && !shown_dev) || host_in) {
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->last_pending = false;
+  }
+  return 0;
+}
+
+int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos, int source, uint8_t* shown, void* stream) {
+  const char* fn = "ian_session_open";
+  int rc = session_check(h, fn, n, ids, 1, photos == nullptr, false);
+  if (rc) return rc;
+  if (!photos && source != 0 && source != 1) return fail(h, -7, "%s: source %d (0 = from GIM, 1 = GIM := IM first)", fn, source);
+  auto& S = h->sess;
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);
+  TotalTimer tt(h, st);
+  if ((rc = session_upload_ids(h, n, ids, st))) return rc;
+  const unsigned char* d_photos = photos;
+  const bool host_in = photos && !is_device_ptr(photos);
+  if (host_in) {
+    if (!S.d_photo) HIPCHK(h, hipMalloc((void**)&S.d_photo, (size_t)BATCH_MAX * SESS_IMG));
+    HIPCHK(h, hipMemcpyAsync(S.d_photo, photos, (size_t)n * SESS_IMG, hipMemcpyHostToDevice, st));
+    d_photos = S.d_photo;
+  }
+  Slot& xs = h->slots[h->desc.x_slot];
+  Slot& zs = h->slots[h->desc.z_slot];
+  Slot& out = h->slots[h->desc.out_slot];
+  if ((rc = ensure_slot(h, h->desc.x_slot, n))) return rc;
+  HIPCHK(h, launch_session_open_in(d_photos, S.pool, S.d_tab, source, S.d_tanh, xs.d, n, st));
+  h->slot_stale[h->desc.x_slot] = 0;
+  // the very segments ian_encode and ian_decode_u8 run at this batch: Z and RECON are theirs bit for bit
+  if ((rc = run_segment(h, IAN_SEG_ENC, n, st))) return rc;
+  if ((rc = run_segment(h, IAN_SEG_IAF, n, st))) return rc;
+  if ((rc = run_segment(h, IAN_SEG_DEC, n, st))) return rc;
+  h->slot_stale[h->desc.out_slot] = 0;
+  const bool shown_dev = shown && is_device_ptr(shown);
+  HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.pool, S.d_tab, 0, 0, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
+  for (int i = 0; i < n; ++i) {
+    S.opened[ids[i]] = 1;
+    ++S.version[ids[i]];
+  }
+  return session_finish(h, n, shown, shown_dev, host_in, st);
+}
+
+int session_set_latent(ian_handle* h, int n, const int32_t* ids, const float* z, int as_sample, uint8_t* shown, void* stream) {
+  const char* fn = "ian_session_set_latent";
+  int rc = session_check(h, fn, n, ids, 1, true, as_sample == 0);
+  if (rc) return rc;
+  if (!z) return fail(h, -1, "null pointer passed to %s", fn);
+  if (as_sample != 0 && as_sample != 1) return fail(h, -7, "%s: as_sample %d (0 = paint_latents, 1 = sample)", fn, as_sample);
+  auto& S = h->sess;
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);
+  TotalTimer tt(h, st);
+  if ((rc = session_upload_ids(h, n, ids, st))) return rc;
+  const bool host_in = !is_device_ptr(z);
+  Slot& zs = h->slots[h->desc.z_slot];
+  Slot& out = h->slots[h->desc.out_slot];
+  if ((rc = set_latent_input(h, h->desc.z_slot, z, n, st))) return rc;
+  if ((rc = run_segment(h, IAN_SEG_DEC, n, st))) return rc;   // sample_at(z) at this batch, as ian_decode / ian_decode_u8 run it
+  h->slot_stale[h->desc.out_slot] = 0;
+  const bool shown_dev = shown && is_device_ptr(shown);
+  if (as_sample) {
+    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.pool, S.d_tab, 1, 1, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
+  } else {
+    SessionBlendArgs a;
+    memset(&a, 0, sizeof a);
+    a.xhat = out.d; a.zslot = zs.d; a.zs = zs.cs; a.P = S.pool; a.ids = S.d_tab;
+    a.shown = shown_dev ? shown : S.d_shown;
+    a.store = 0;
+    for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
+    a.radius = S.radius;
+    HIPCHK(h, launch_session_blend(a, n, st));
+  }
+  for (int i = 0; i < n; ++i) ++S.version[ids[i]];
+  return session_finish(h, n, shown, shown_dev, host_in, st);
+}
+
+int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream) {
+  const char* fn = "ian_session_brush";
+  static_assert(sizeof(ian_session_event) == 11 * sizeof(int32_t), "ian_session_event is 11 words");
+  int rc = session_check(h, fn, n, ev ? &ev->session : nullptr, 11, true, true);
+  if (rc) return rc;
+  Slot& out = h->slots[h->desc.out_slot];
+  for (int i = 0; i < n; ++i) {
+    const ian_session_event& e = ev[i];
+    if (e.mode != 0 && e.mode != 1) return fail(h, -7, "%s: item %d has mode %d (0 = imgrad, 1 = imgradRGB toward rgb)", fn, i, e.mode);
+    if (e.c1 < 0 || e.r1 < 0 || e.c2 > out.w || e.r2 > out.h)
+      return fail(h, -7, "%s: item %d: patch (%d,%d,%d,%d) outside the %dx%d image", fn, i, e.c1, e.r1, e.c2, e.r2, out.w, out.h);
+  }
+  auto& S = h->sess;
+  const int pass = h->opt.brush_pass;
+  bool hit = n <= pass && S.res_valid && (int)S.res_ids.size() == n && getenv("IAN_NO_DEC_CACHE") == nullptr;
+  for (int i = 0; hit && i < n; ++i) hit = S.res_ids[i] == ev[i].session && S.res_ver[i] == S.version[ev[i].session];
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);   // also ends the residency: re-armed below
+  TotalTimer tt(h, st);
+  // the event table, rearranged for the kernels: n ian_brush_item records (the shared middle reads them), n ids, n colours
+  S.tab_shadow.resize((size_t)11 * n);
+  int32_t* t_items = S.tab_shadow.data();
+  int32_t* t_ids = t_items + (size_t)7 * n;
+  int32_t* t_col = t_ids + n;
+  for (int i = 0; i < n; ++i) {
+    memcpy(t_items + (size_t)7 * i, &ev[i].c1, 7 * sizeof(int32_t));   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
+    t_ids[i] = ev[i].session;
+    memcpy(t_col + (size_t)3 * i, ev[i].rgb, 3 * sizeof(float));
+  }
+  HIPCHK(h, hipMemcpyAsync(S.d_tab, S.tab_shadow.data(), (size_t)11 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int* d_items = S.d_tab;
+  const int* d_ids = S.d_tab + (size_t)7 * n;
+  const float* d_col = reinterpret_cast<const float*>(S.d_tab + (size_t)8 * n);
+  Slot& zs = h->slots[h->desc.z_slot];
+  const bool shown_dev = shown && is_device_ptr(shown);
+  unsigned char* d_shown = shown_dev ? shown : S.d_shown;
+  for (int off = 0; off < n; off += pass) {
+    const int nc = std::min(pass, n - off);
+    if (!hit) {
+      if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
+      HIPCHK(h, launch_session_gather_z(S.pool, d_ids + off, zs.d, zs.cs, nc, st));
+      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
+    }
+    if ((rc = brush_pass_middle(h, nc, d_items + (size_t)7 * off, nullptr, d_col + (size_t)3 * off, true, st))) return rc;
+    SessionBlendArgs a;
+    memset(&a, 0, sizeof a);
+    a.xhat = out.d; a.zslot = zs.d; a.zs = zs.cs; a.P = S.pool; a.ids = d_ids + off; a.items = d_items + (size_t)7 * off;
+    a.shown = d_shown + (size_t)off * SESS_IMG;
+    a.store = 1;
+    for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
+    a.radius = S.radius;
+    HIPCHK(h, launch_session_blend(a, nc, st));
+  }
+  h->slot_stale[h->desc.out_slot] = 0;
+  for (int i = 0; i < n; ++i) ++S.version[ev[i].session];
+  if ((rc = session_finish(h, n, shown, shown_dev, false, st))) return rc;
+  if (n <= pass) {   // one pass: the resident activations belong to these sessions' new latents
+    S.res_ids.resize(n);
+    S.res_ver.resize(n);
+    for (int i = 0; i < n; ++i) {
+      S.res_ids[i] = ev[i].session;
+      S.res_ver[i] = S.version[ev[i].session];
+    }
+    S.res_valid = true;
+  }
+  return 0;
+}
+
+int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
+  const char* fn = "ian_session_read";
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if (!out) return fail(h, -1, "null pointer passed to %s", fn);
+  if (id < 0 || id >= S.capacity) return fail(h, -7, "%s: session %d outside the pool (capacity %d)", fn, id, S.capacity);
+  if (!S.opened[id]) return fail(h, -7, "%s: session %d has not been opened", fn, id);
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (what) {
+    case IAN_SESSION_Z: src = S.pool.z + (size_t)id * S.pool.zl; bytes = (size_t)S.pool.zl * sizeof(float); break;
+    case IAN_SESSION_RECON: src = S.pool.recon + (size_t)id * SESS_IMG; bytes = SESS_IMG; break;
+    case IAN_SESSION_ERROR: src = S.pool.error + (size_t)id * SESS_IMG; bytes = SESS_IMG * sizeof(float); break;
+    case IAN_SESSION_IM: src = S.pool.im + (size_t)id * SESS_IMG; bytes = SESS_IMG; break;
+    case IAN_SESSION_GIM: src = S.pool.gim + (size_t)id * SESS_IMG; bytes = SESS_IMG; break;
+    case IAN_SESSION_MODE: src = S.pool.mode + id; bytes = sizeof(int32_t); break;
+    default: return fail(h, -7, "%s: field %d (enum ian_session_field)", fn, what);
+  }
+  // a plain copy of pool rows: the decoder's activations are not touched, so the residency of ian_session_brush survives it
+  hipStream_t st = (hipStream_t)stream;
+  if (h->last_pending && h->last_stream != st) HIPCHK(h, hipStreamSynchronize(h->last_stream));
+  const bool dev = is_device_ptr(out);
+  HIPCHK(h, hipMemcpyAsync(out, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (dev) {
+    h->last_stream = st;
+    h->last_pending = true;
+  } else {
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (h->last_stream == st) h->last_pending = false;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ian_sessions_reserve(ian_handle* h, int32_t capacity) {
+  if (!h) return -1;
+  return sessions_reserve(h, capacity);
+}
+int ian_sessions_set_blend(ian_handle* h, const double* gauss_half, int32_t radius) { return sessions_set_blend(h, gauss_half, radius); }
+int ian_session_open(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t* photos, int32_t source, uint8_t* shown, void* stream) {
+  if (!h) return -1;
+  return session_open(h, n, ids, photos, source, shown, stream);
+}
+int ian_session_set_latent(ian_handle* h, int32_t n, const int32_t* ids, const float* z, int32_t as_sample, uint8_t* shown, void* stream) {
+  if (!h) return -1;
+  return session_set_latent(h, n, ids, z, as_sample, shown, stream);
+}
+int ian_session_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, void* stream) {
+  if (!h) return -1;
+  return session_brush(h, n, events, shown, stream);
+}
+int ian_session_read(ian_handle* h, int32_t id, int32_t what, void* out, void* stream) {
+  if (!h) return -1;
+  return session_read(h, id, what, out, stream);
+}
+void ian_session_tanh_table(float* out256) {
+  if (out256) session_tanh_table(out256);
+}
+
+}  // extern "C"

@@ -276,6 +276,25 @@ struct ian_handle {
     int cache_n = 0;
     bool cache_valid = false;
   } batch;
+  // device-resident edit sessions (ian_session_*, ian_rt_session.inc): the pool (one row per session id in each array), what the
+  // host keeps per session (opened, latent version), the small per-call uploads, and the residency key of ian_session_brush: the
+  // decoder activations belong to sessions res_ids, in that order, at latent versions res_ver; enter_stream clears res_valid
+  struct SessionState {
+    int capacity = 0;
+    SessionPool pool = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    std::vector<char> opened;
+    std::vector<uint64_t> version;
+    int* d_tab = nullptr;              // per call: brush = [7n ian_brush_item words | n ids | 3n colours], open / set_latent = n ids
+    std::vector<int32_t> tab_shadow;   // its upload source (outlives the caller's array)
+    float* d_tanh = nullptr;           // to_tanh of the 256 uint8 levels, float32
+    unsigned char* d_photo = nullptr;  // staging of host photos [256][3*64*64]
+    unsigned char* d_shown = nullptr;  // staging of the canvas images [256][3*64*64]
+    double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int radius = -1;                   // -1: ian_sessions_set_blend has not been called
+    std::vector<int32_t> res_ids;
+    std::vector<uint64_t> res_ver;
+    bool res_valid = false;
+  } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot
   int* d_patch = nullptr;

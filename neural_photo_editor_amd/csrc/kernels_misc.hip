@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "ian_internal.h"
+#include "ian_dact.h"   // m_dact
 
 namespace ian {
 
@@ -16,16 +17,6 @@ __device__ __forceinline__ float m_act(float v, int act) {
     case 4: return tanhf(v);
     case 5: return 1.f / (1.f + __expf(-v));
     default: return v;
-  }
-}
-__device__ __forceinline__ float m_dact(float y, int act) {
-  switch (act) {
-    case 1: return y > 0.f ? 1.f : 0.f;
-    case 2: return y > 0.f ? 1.f : 0.2f;
-    case 3: return y > 0.f ? 1.f : y + 1.f;
-    case 4: return 1.f - y * y;
-    case 5: return y * (1.f - y);
-    default: return 1.f;
   }
 }
 

@@ -1,0 +1,250 @@
+// Device-resident edit sessions (ian_session_*, include/ian.h): the state NPE.py's callbacks keep in host globals -- GIM, IM, RECON,
+// ERROR, Z, SAMPLE_FLAG (NPE.py:239-279, 317-345) -- lives in a per-handle pool in HBM, indexed by session id.  These kernels are
+// the pool's side of every call: bandwidth and latency work (a few 12 KB / 48 KB rows per session), never MFMA.
+//   session_open_in_kernel     infer / Reset / UpdateGIM, input side: uint8 photo -> GIM, IM and the encoder's float32 input
+//   session_store_kernel       infer / Reset / sample, output side: RECON, ERROR, Z, mode flag, the canvas image
+//   session_gather_z_kernel    brush: the sessions' latents -> the decoder's latent slot
+//   *_seed_colour_batch_kernel brush: the loss seeds of kernels_misc.hip with a constant brush colour per item (NPE.py:205 myRGB)
+//   session_blend_kernel       brush / paint_latents: photo blend (photo mode) or uint8 image (sample mode) per session, z_new -> pool
+// Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
+#include "ian_internal.h"
+#include "ian_dact.h"   // m_dact, under the default contraction mode
+
+namespace ian {
+
+// ---- loss seeds with a constant colour (default floating-point contraction, as in kernels_misc.hip: same object code per product) ----
+// deconv_out_bwd_seed_batch_kernel (kernels_misc.hip) with the item's brush colour image replaced by its constant colour:
+// colour[3 * item + co] stands where rgb_i[o] stood.  Same grid, same products in the same order per element.  (The launcher also
+// refuses Cout > 3, which the image form does not check: a colour has three channels.)
+__global__ __launch_bounds__(256) void deconv_out_bwd_seed_colour_batch_kernel(const float* __restrict__ xhat, const float* __restrict__ colour,
+                                                                               const int* __restrict__ items, int out_act,
+                                                                               const float* __restrict__ oscale, const float* __restrict__ w,
+                                                                               float* __restrict__ dx, const float* __restrict__ yfwd,
+                                                                               const float* __restrict__ scale, int H, int W, int Cin,
+                                                                               int Cout, int act) {
+  __shared__ int sp[5];
+  __shared__ float sc[4];
+  const int item = blockIdx.y;
+  if (threadIdx.x < 5) sp[threadIdx.x] = items[item * 7 + threadIdx.x];
+  if (threadIdx.x >= 8 && threadIdx.x < 11) sc[threadIdx.x - 8] = colour[item * 3 + (threadIdx.x - 8)];
+  __syncthreads();
+  const int c4n = Cin >> 2;
+  const int idx4 = blockIdx.x * 256 + threadIdx.x;
+  if (idx4 >= H * W * c4n) return;
+  const int ci = (idx4 % c4n) * 4, pix = idx4 / c4n;
+  const int ix = pix % W, iy = pix / W;
+  const int OH = 2 * H, OW = 2 * W;
+  const int c1 = sp[0], r1 = sp[1], c2 = sp[2], r2 = sp[3], mode = sp[4];
+  const float* xh_i = xhat + (size_t)item * Cout * OH * OW;
+  const int cnt = 3 * (r2 - r1) * (c2 - c1);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  if (cnt > 0) {
+    const float inv = 1.f / (float)cnt;
+    const int ky0 = max(0, r1 - (2 * iy - 2)), ky1 = min(5, r2 - (2 * iy - 2));
+    const int kx0 = max(0, c1 - (2 * ix - 2)), kx1 = min(5, c2 - (2 * ix - 2));
+    for (int ky = ky0; ky < ky1; ++ky) {
+      const int oy = 2 * iy - 2 + ky;
+      if ((unsigned)oy >= (unsigned)OH) continue;
+      for (int kx = kx0; kx < kx1; ++kx) {
+        const int ox = 2 * ix - 2 + kx;
+        if ((unsigned)ox >= (unsigned)OW) continue;
+        for (int co = 0; co < Cout; ++co) {
+          const int o = (co * OH + oy) * OW + ox;
+          const float xh = xh_i[o];
+          float gv = (mode == 0) ? inv : 2.f * (xh - sc[co]) * inv;
+          gv = gv * m_dact(xh, out_act) * (oscale ? oscale[co] : 1.f);
+          const float4 wv = *reinterpret_cast<const float4*>(w + ((size_t)(ky * 5 + kx) * 4 + co) * Cin + ci);
+          acc[0] = fmaf(gv, wv.x, acc[0]);
+          acc[1] = fmaf(gv, wv.y, acc[1]);
+          acc[2] = fmaf(gv, wv.z, acc[2]);
+          acc[3] = fmaf(gv, wv.w, acc[3]);
+        }
+      }
+    }
+  }
+  const size_t o4 = ((size_t)item * H * W + pix) * Cin + ci;
+  float4 out;
+  float* op = &out.x;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float d = yfwd ? m_dact(yfwd[o4 + e], act) : 1.f;
+    op[e] = acc[e] * d * (scale ? scale[ci + e] : 1.f);
+  }
+  *reinterpret_cast<float4*>(dx + o4) = out;
+}
+hipError_t launch_deconv_out_bwd_seed_colour_batch(const float* xhat, const float* colour, const int* items, int n, int out_act,
+                                                   const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale,
+                                                   int H, int W, int Cin, int Cout, int act, hipStream_t s) {
+  if ((Cin & 3) || Cout > 3 || n < 1 || n > 65535) return hipErrorInvalidValue;
+  const int total = H * W * (Cin >> 2);
+  hipLaunchKernelGGL(deconv_out_bwd_seed_colour_batch_kernel, dim3((total + 255) / 256, n), dim3(256), 0, s, xhat, colour, items, out_act,
+                     oscale, w, dx, yfwd, scale, H, W, Cin, Cout, act);
+  return hipGetLastError();
+}
+
+// patch_seed_batch_kernel (kernels_misc.hip) likewise: NCHW [n,3,H,W], element i of an image belongs to channel i / (H*W)
+__global__ __launch_bounds__(256) void patch_seed_colour_batch_kernel(const float* __restrict__ xhat, const float* __restrict__ colour,
+                                                                      float* __restrict__ g, int H, int W, const int* __restrict__ items) {
+  __shared__ int sp[5];
+  __shared__ float sc[4];
+  const int item = blockIdx.y;
+  if (threadIdx.x < 5) sp[threadIdx.x] = items[item * 7 + threadIdx.x];
+  if (threadIdx.x >= 8 && threadIdx.x < 11) sc[threadIdx.x - 8] = colour[item * 3 + (threadIdx.x - 8)];
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 3 * H * W) return;
+  const int c1 = sp[0], r1 = sp[1], c2 = sp[2], r2 = sp[3], mode = sp[4];
+  const size_t o = (size_t)item * 3 * H * W + i;
+  const int xx = i % W, yy = (i / W) % H, co = i / (H * W);
+  const int cnt = 3 * (r2 - r1) * (c2 - c1);
+  float v = 0.f;
+  if (yy >= r1 && yy < r2 && xx >= c1 && xx < c2 && cnt > 0) {
+    const float inv = 1.f / (float)cnt;
+    v = (mode == 0) ? inv : 2.f * (xhat[o] - sc[co]) * inv;
+  }
+  g[o] = v;
+}
+hipError_t launch_patch_seed_colour_batch(const float* xhat, const float* colour, float* g, int H, int W, const int* items, int n,
+                                          hipStream_t s) {
+  if (n < 1 || n > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(patch_seed_colour_batch_kernel, dim3((3 * H * W + 255) / 256, n), dim3(256), 0, s, xhat, colour, g, H, W, items);
+  return hipGetLastError();
+}
+
+}  // namespace ian
+
+#include "npe_blend.h"   // floating-point contraction off from here on; np_uint8f, photo_blend_image
+
+namespace ian {
+
+constexpr int S_IMG = 3 * 64 * 64;
+
+// ---- open, input side (NPE.py:244-257 infer, :332-333 Reset, :344 UpdateGIM) --------------------------------------------------
+// grid (S_IMG / 1024, n), a lane owns 4 consecutive bytes.  The source row is photos[i] (a new photo), the session's GIM (Reset) or
+// its IM (UpdateGIM); it becomes GIM and IM, and x[i] = np.asarray([to_tanh(IM)], dtype=np.float32): the host builds `table` with
+// exactly that expression for the 256 levels (float64, one rounding), so the encoder sees the bits the host path uploads.
+__global__ __launch_bounds__(256) void session_open_in_kernel(const unsigned char* __restrict__ photos, SessionPool P,
+                                                              const int* __restrict__ ids, int source, const float* __restrict__ table,
+                                                              float* __restrict__ x) {
+  __shared__ float tab[256];
+  tab[threadIdx.x] = table[threadIdx.x];
+  __syncthreads();
+  const int i = blockIdx.y;
+  const size_t row = (size_t)ids[i] * S_IMG;
+  const int e = (blockIdx.x * 256 + threadIdx.x) * 4;
+  const unsigned char* src = photos ? photos + (size_t)i * S_IMG : (source == 1 ? P.im + row : P.gim + row);
+  const uchar4 v = *reinterpret_cast<const uchar4*>(src + e);
+  *reinterpret_cast<uchar4*>(P.gim + row + e) = v;
+  *reinterpret_cast<uchar4*>(P.im + row + e) = v;
+  *reinterpret_cast<float4*>(x + (size_t)i * S_IMG + e) = make_float4(tab[v.x], tab[v.y], tab[v.z], tab[v.w]);
+}
+hipError_t launch_session_open_in(const unsigned char* photos, const SessionPool& P, const int* ids, int source, const float* table,
+                                  float* x, int n, hipStream_t s) {
+  if (n < 1 || n > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_open_in_kernel, dim3(S_IMG / 1024, n), dim3(256), 0, s, photos, P, ids, source, table, x);
+  return hipGetLastError();
+}
+
+__device__ __forceinline__ float to_tanh_f32(float v) { return (2.0f * (v / 255.0f)) - 1.0f; }   // to_tanh(np.float32(.)): three roundings
+
+// ---- open / sample, output side (NPE.py:261-270, 323-326, 335-338) ---------------------------------------------------------
+//   RECON = uint8(from_tanh(x))            to_uint8_kernel's expression (kernels_npe.hip)
+//   ERROR = to_tanh(float32(IM)) - to_tanh(float32(RECON))       float32, numpy's order, no contraction
+// both scattered to the session's rows; the latent row of the z slot goes to the session's Z, the mode flag is set, and the canvas
+// image (IM after an open, RECON after a sample) is written to shown[i] when asked for.
+__global__ __launch_bounds__(256) void session_store_kernel(const float* __restrict__ xhat, const float* __restrict__ zslot, int zs,
+                                                            SessionPool P, const int* __restrict__ ids, int new_mode, int shown_recon,
+                                                            unsigned char* __restrict__ shown) {
+  const int i = blockIdx.y;
+  const int id = ids[i];
+  const size_t row = (size_t)id * S_IMG;
+  const int e = (blockIdx.x * 256 + threadIdx.x) * 4;
+  const float4 v = *reinterpret_cast<const float4*>(xhat + (size_t)i * S_IMG + e);
+  uchar4 r;
+  r.x = np_uint8f(255.0f * (v.x + 1.0f) / 2.0f);
+  r.y = np_uint8f(255.0f * (v.y + 1.0f) / 2.0f);
+  r.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
+  r.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
+  const uchar4 a = *reinterpret_cast<const uchar4*>(P.im + row + e);
+  float4 err;
+  err.x = to_tanh_f32((float)a.x) - to_tanh_f32((float)r.x);
+  err.y = to_tanh_f32((float)a.y) - to_tanh_f32((float)r.y);
+  err.z = to_tanh_f32((float)a.z) - to_tanh_f32((float)r.z);
+  err.w = to_tanh_f32((float)a.w) - to_tanh_f32((float)r.w);
+  *reinterpret_cast<uchar4*>(P.recon + row + e) = r;
+  *reinterpret_cast<float4*>(P.error + row + e) = err;
+  if (shown) *reinterpret_cast<uchar4*>(shown + (size_t)i * S_IMG + e) = shown_recon ? r : a;
+  if (blockIdx.x == 0) {
+    for (int j = threadIdx.x; j < P.zl; j += 256) P.z[(size_t)id * P.zl + j] = zslot[(size_t)i * zs + j];
+    if (threadIdx.x == 0) P.mode[id] = new_mode;
+  }
+}
+hipError_t launch_session_store(const float* xhat, const float* zslot, int zs, const SessionPool& P, const int* ids, int new_mode,
+                                int shown_recon, unsigned char* shown, int n, hipStream_t s) {
+  if (n < 1 || n > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_store_kernel, dim3(S_IMG / 1024, n), dim3(256), 0, s, xhat, zslot, zs, P, ids, new_mode, shown_recon, shown);
+  return hipGetLastError();
+}
+
+// ---- brush: the sessions' latents into the decoder's latent slot (row i = session ids[i]; the slot's channel padding stays zero) ----
+__global__ __launch_bounds__(128) void session_gather_z_kernel(SessionPool P, const int* __restrict__ ids, float* __restrict__ zslot, int zs) {
+  const int i = blockIdx.x;
+  const size_t src = (size_t)ids[i] * P.zl;
+  for (int j = threadIdx.x; j < P.zl; j += 128) zslot[(size_t)i * zs + j] = P.z[src + j];
+}
+hipError_t launch_session_gather_z(const SessionPool& P, const int* ids, float* zslot, int zs, int n, hipStream_t s) {
+  if (n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_gather_z_kernel, dim3(n), dim3(128), 0, s, P, ids, zslot, zs);
+  return hipGetLastError();
+}
+
+// ---- brush / paint_latents, output side: one workgroup per item ---------------------------------------------------------------
+// A paint event (items[7*i + 4] == 1; items == nullptr: paint_latents) on a session in photo mode: photo_blend_image (NPE.py:218-231 /
+// 296-300) against the session's RECON / ERROR; store != 0 (a brush event) writes the result to the session's IM and copies it to
+// shown[i], store == 0 (paint_latents: IM is local to that callback) writes shown[i] only.
+// A session in sample mode, and a lighten event in either mode (NPE.scroll ends in update_photo(None), NPE.py:313-314):
+// shown[i] = uint8(from_tanh(x)) (NPE.py:110), IM untouched.  The item's latent row goes back to the pool.
+__global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a) {
+  __shared__ double m0[64 * 64];
+  __shared__ double m1[64 * 64];
+  const int i = blockIdx.y;
+  const int id = a.ids[i];
+  const size_t row = (size_t)id * S_IMG;
+  const float* xh = a.xhat + (size_t)i * S_IMG;
+  unsigned char* sh = a.shown + (size_t)i * S_IMG;
+  for (int j = threadIdx.x; j < a.P.zl; j += PB_T) a.P.z[(size_t)id * a.P.zl + j] = a.zslot[(size_t)i * a.zs + j];
+  if (a.P.mode[id] != 0 || (a.items && a.items[i * 7 + 4] == 0)) {   // the plain sample (uniform over the workgroup)
+    for (int e = threadIdx.x * 4; e < S_IMG; e += PB_T * 4) {
+      const float4 v = *reinterpret_cast<const float4*>(xh + e);
+      uchar4 o;
+      o.x = np_uint8f(255.0f * (v.x + 1.0f) / 2.0f);
+      o.y = np_uint8f(255.0f * (v.y + 1.0f) / 2.0f);
+      o.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
+      o.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
+      *reinterpret_cast<uchar4*>(sh + e) = o;
+    }
+    return;
+  }
+  PhotoBlendArgs b;
+  b.xhat = xh;
+  b.recon = a.P.recon + row;
+  b.error = a.P.error + row;
+  b.im = a.store ? a.P.im + row : sh;
+  b.mask = nullptr;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) b.w[k] = a.w[k];
+  b.radius = a.radius;
+  photo_blend_image(b, m0, m1);
+  if (a.store) {   // every thread re-reads exactly the bytes it wrote (p = tid + k * PB_T per channel)
+    for (int p = threadIdx.x; p < 64 * 64; p += PB_T)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sh[c * 64 * 64 + p] = b.im[c * 64 * 64 + p];
+  }
+}
+hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s) {
+  if (a.radius < 0 || a.radius > 7 || n < 1 || n > 65535 || !a.shown) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_blend_kernel, dim3(1, n), dim3(PB_T), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace ian

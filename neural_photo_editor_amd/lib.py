@@ -43,7 +43,9 @@ EXPORTS = (
     "ian_create", "ian_load_param", "ian_set_made_masks", "ian_finalize", "ian_encode", "ian_decode",
     "ian_encode_pre_iaf", "ian_iaf", "ian_reconstruct", "ian_grad_rgb", "ian_grad_light", "ian_decode_u8", "ian_photo_blend",
     "ian_read_slot", "ian_read_slot_grad",
-    "ian_brush_step", "ian_grad_batch", "ian_brush_step_batch", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
+    "ian_brush_step", "ian_grad_batch", "ian_brush_step_batch",
+    "ian_sessions_reserve", "ian_sessions_set_blend", "ian_session_open", "ian_session_set_latent", "ian_session_brush", "ian_session_read",
+    "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
 _lib = None
@@ -102,6 +104,14 @@ def load_library():
     lib.ian_brush_step.argtypes = [vp, i32, i32, i32, i32, fp, fp, C.c_float, C.c_float, fp, fp, fp, C.POINTER(PhotoArgs), vp]
     lib.ian_grad_batch.argtypes = [vp, i32, C.POINTER(BrushItem), fp, fp, fp, vp]
     lib.ian_brush_step_batch.argtypes = [vp, i32, C.POINTER(BrushItem), fp, fp, fp, fp, fp, C.POINTER(PhotoBatchArgs), vp]
+    lib.ian_sessions_reserve.argtypes = [vp, i32]
+    lib.ian_sessions_set_blend.argtypes = [vp, fp, i32]
+    lib.ian_session_open.argtypes = [vp, i32, fp, fp, i32, fp, vp]
+    lib.ian_session_set_latent.argtypes = [vp, i32, fp, fp, i32, fp, vp]
+    lib.ian_session_brush.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, vp]
+    lib.ian_session_read.argtypes = [vp, i32, i32, fp, vp]
+    lib.ian_session_tanh_table.argtypes = [fp]
+    lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
     lib.ian_read_slot_grad.argtypes = [vp, i32, i32, fp, vp]
     lib.ian_profile_enable.argtypes = [vp, i32]
@@ -116,7 +126,7 @@ def load_library():
     lib.ian_destroy.argtypes = [vp]
     lib.ian_destroy.restype = None
     for fn in EXPORTS:
-        if fn not in ("ian_last_error", "ian_version", "ian_destroy"):
+        if fn not in ("ian_last_error", "ian_version", "ian_destroy", "ian_session_tanh_table"):
             getattr(lib, fn).restype = i32
     _lib = lib
     return lib
@@ -138,6 +148,24 @@ class PhotoBatchArgs(C.Structure):
     """ian_photo_batch_args (include/ian.h)."""
     _fields_ = [("recon", C.c_void_p), ("error", C.c_void_p), ("gauss_half", C.c_void_p), ("radius", C.c_int32),
                 ("im", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class SessionEvent(C.Structure):
+    """ian_session_event (include/ian.h): one brush event on a device-resident edit session (ian_session_brush)."""
+    _fields_ = [("session", C.c_int32), ("c1", C.c_int32), ("r1", C.c_int32), ("c2", C.c_int32), ("r2", C.c_int32), ("mode", C.c_int32),
+                ("coef", C.c_float), ("gscale", C.c_float), ("rgb", C.c_float * 3)]
+
+
+# enum ian_session_field (include/ian.h): name -> (code, dtype, shape; None = (num_latents,))
+SESSION_FIELDS = {"Z": (0, np.float32, None), "RECON": (1, np.uint8, (3, 64, 64)), "ERROR": (2, np.float32, (3, 64, 64)),
+                  "IM": (3, np.uint8, (3, 64, 64)), "GIM": (4, np.uint8, (3, 64, 64)), "MODE": (5, np.int32, (1,))}
+
+
+def session_tanh_table():
+    """ian_session_tanh_table: the float32 value the open kernel gives each uint8 level (needs no device)."""
+    out = np.empty(256, np.float32)
+    load_library().ian_session_tanh_table(_ptr(out))
+    return out
 
 
 class IanError(RuntimeError):
@@ -262,6 +290,35 @@ class Handle:
                                                   _ptr(z_new), _ptr(dz) if dz is not None else null,
                                                   _ptr(x) if x is not None else null, C.byref(pa) if pa is not None else None,
                                                   C.c_void_p(stream or 0)))
+
+    # ---- device-resident edit sessions (ian_session_*) ----
+    def sessions_reserve(self, capacity):
+        self._check(self.lib.ian_sessions_reserve(self._h, int(capacity)))
+
+    def sessions_set_blend(self, gauss_half):
+        half = np.ascontiguousarray(gauss_half, np.float64)
+        self._check(self.lib.ian_sessions_set_blend(self._h, _ptr(half), len(half) - 1))
+
+    def session_open(self, ids, photos=None, source=0, shown=None, stream=None):
+        """ian_session_open; ids = int32 array (n = its length), photos u8[n,3,64,64] or None, shown u8[n,3,64,64] or None."""
+        null = C.c_void_p(0)
+        self._check(self.lib.ian_session_open(self._h, len(ids), _ptr(ids), _ptr(photos) if photos is not None else null, int(source),
+                                              _ptr(shown) if shown is not None else null, C.c_void_p(stream or 0)))
+
+    def session_set_latent(self, ids, z, as_sample, shown=None, stream=None):
+        self._check(self.lib.ian_session_set_latent(self._h, len(ids), _ptr(ids), _ptr(z), int(as_sample),
+                                                    _ptr(shown) if shown is not None else C.c_void_p(0), C.c_void_p(stream or 0)))
+
+    def session_brush(self, events, shown=None, stream=None):
+        """ian_session_brush; events = a ctypes array of SessionEvent (n = its length)."""
+        self._check(self.lib.ian_session_brush(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
+                                               C.c_void_p(stream or 0)))
+
+    def session_read(self, sid, what, stream=None):
+        code, dtype, shape = SESSION_FIELDS[what]
+        out = np.empty(shape if shape is not None else (self.lowered.num_latents,), dtype)
+        self._check(self.lib.ian_session_read(self._h, int(sid), code, _ptr(out), C.c_void_p(stream or 0)))
+        return out
 
     def read_slot(self, slot, n):
         h, w, c = self.lowered.slots[slot]

@@ -1,0 +1,127 @@
+"""Device-resident edit sessions against the stateless batched call: events/s of EditSessions.paint (photo mode, a steady set of
+ids: state in HBM, 11 words up per event, 12 KB down) and of IAN.brush_step_batch with host pointers and photo= (per item a 48 KB
+colour image, RECON, ERROR and the latent compared against their shadows, z_new and IM down), in one process, on both configs.
+usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 16 64] [--calls 200] [--repeats 3] [--out FILE]
+  --trace: only the first --n on the first config, sessions only: warm-up, an idle second, then --calls timed calls (for a
+           rocprofv3 --kernel-trace --stats run).
+Per (config, n, path): the median over --calls calls after warm-up, repeated --repeats times (the two paths alternate within a
+repeat); reported are the median of the repeats and their spread (max - min) / median.  Also the host<->device bytes per call of
+both paths.  Prints one JSON line and, with --out, writes it there."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from neural_photo_editor_amd import IAN, synthetic as O  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IMG = 3 * 64 * 64
+
+
+def boxes_for(n, seed=0):
+    rs = np.random.RandomState(seed)
+    c1, r1 = rs.randint(0, 56, n), rs.randint(0, 56, n)
+    return np.stack([c1, r1, c1 + 4 + rs.randint(0, 5, n), r1 + 4 + rs.randint(0, 5, n)], 1)   # NPE brush boxes: 4..8 pixels
+
+
+def median_ms(fn, calls, warmup=10):
+    for _ in range(warmup):
+        fn()
+    lat = []
+    for _ in range(calls):
+        t = time.perf_counter()
+        fn()
+        lat.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(lat))
+
+
+def bytes_per_call(n, zl):
+    """What crosses the bus per call.  Stateless, steady state: the item table and the latents go up (the latents change every
+    call; the colour images, RECON and ERROR are re-uploaded only when their bytes change, but all of them are compared on the
+    host every call), z_new and IM come down."""
+    return {"sessions": {"h2d": 44 * n, "d2h": IMG * n, "host_compare": 0},
+            "stateless": {"h2d": 28 * n + 4 * zl * n, "d2h": 4 * zl * n + IMG * n, "host_compare": n * (4 * IMG + IMG + 4 * IMG)}}
+
+
+def run_arch(arch, ns, calls, repeats):
+    from neural_photo_editor_amd import npe_ops as N
+    m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
+    zl = m.get_zdim()
+    s = m.sessions(max(ns))
+    rows = []
+    for n in ns:
+        ids = np.arange(n)
+        boxes = boxes_for(n)
+        levels = (255, 0, 0)
+        ph = np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8)
+        s.open(ids, ph)
+        st = [s.read(i) for i in ids]
+        recon, error = np.stack([t["RECON"] for t in st]), np.stack([t["ERROR"] for t in st])
+        z = [np.stack([t["Z"] for t in st])]
+        rgb = np.empty((n, 3, 64, 64), np.float32)
+        rgb[:] = N.to_tanh(np.float32(levels)).astype(np.float32)[None, :, None, None]
+
+        def sess():
+            s.paint(ids, boxes, levels)
+
+        def stateless():
+            z[0] = m.brush_step_batch(boxes, z[0], rgb, image=False, photo=(recon, error))[0]
+        res = {"sessions": [], "stateless": []}
+        for _ in range(repeats):
+            res["sessions"].append(median_ms(sess, calls))
+            res["stateless"].append(median_ms(stateless, calls))
+        row = {"n": n, "bytes_per_call": bytes_per_call(n, zl)}
+        for k, v in res.items():
+            med = float(np.median(v))
+            row[k] = {"p50_ms": round(med, 4), "events_per_s": round(n * 1e3 / med, 1), "spread": round((max(v) - min(v)) / med, 4),
+                      "repeats_ms": [round(t, 4) for t in v]}
+        row["sessions_over_stateless"] = round(row["sessions"]["events_per_s"] / row["stateless"]["events_per_s"], 3)
+        rows.append(row)
+    m.close()
+    return rows
+
+
+def trace_run(arch, n, calls):
+    m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
+    s = m.sessions(n)
+    ids, boxes = np.arange(n), boxes_for(n)
+    s.open(ids, np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8))
+    for _ in range(5):
+        s.paint(ids, boxes, (255, 0, 0))
+    time.sleep(1.0)
+    t = time.perf_counter()
+    for _ in range(calls):
+        s.paint(ids, boxes, (255, 0, 0))
+    return {"arch": arch, "n": n, "calls": calls, "ms_per_call": round((time.perf_counter() - t) * 1e3 / calls, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default=None, help="one config (IAN_simple or IAN)")
+    ap.add_argument("--n", type=int, nargs="*", default=[1, 4, 16, 64])
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    archs = [a.only] if a.only else ["IAN_simple", "IAN"]
+    if a.trace:
+        print(json.dumps(trace_run(archs[0], a.n[0], a.calls)))
+        return
+    res = {"metric": "session_latency", "calls": a.calls, "repeats": a.repeats}
+    for arch in archs:
+        res[arch] = run_arch(arch, a.n, a.calls, a.repeats)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
