@@ -264,11 +264,60 @@ enum ian_session_field {
   IAN_SESSION_ERROR = 2, /* f32[3,64,64] */
   IAN_SESSION_IM = 3,    /* u8[3,64,64] */
   IAN_SESSION_GIM = 4,   /* u8[3,64,64] */
-  IAN_SESSION_MODE = 5   /* int32: 0 photo, 1 sample */
+  IAN_SESSION_MODE = 5,  /* int32: 0 photo, 1 sample */
+  /* full-resolution pools only (-6 without ian_sessions_reserve_hires) */
+  IAN_SESSION_FIELD = 6,      /* f32[3,64,64]: what the last call displayed, see ian_session_render */
+  IAN_SESSION_FIELD_KIND = 7, /* int32: 0 = FIELD is an edit field on top of the source, 1 = FIELD is the sample x itself */
+  IAN_SESSION_SOURCE = 8      /* u8[3,S,S]: the raw full-resolution source (-7 for a session without one) */
 };
 /* One field of an opened session -> out (host or device): tests, saving a picture (NPE.py has no counterpart: its state is
    host globals).  Leaves the resident activations alone. */
 int ian_session_read(ian_handle* h, int32_t id, int32_t what, void* out, void* stream);
+/* ---- full-resolution edit sessions: photos of S x S pixels, S = 64 * scale, edited through the 64x64 model ----
+   What NPE.paint shows, from_tanh(to_tanh(RECON) + MASK*DELTA + (1-MASK)*ERROR) with ERROR = to_tanh(GIM) - to_tanh(RECON), is the
+   photo plus the smooth field MASK*(DELTA - ERROR).  A full-resolution pool keeps the photo at its own size (SRC u8[3,S,S]) and that
+   field (FIELD f32[3,64,64], FIELD_KIND) per session, and renders windows of SRC + 127.5 * bilinear(FIELD) on the device: the
+   unedited part of the photo stays pixel-exact.  FIELD always describes what the last call on the session displayed:
+     open / Reset / commit: zeros, kind 0;  set_latent(as_sample = 1): x, kind 1;
+     a paint event or set_latent(as_sample = 0) on a photo-mode session: float32(MASK * (float64(DELTA) - float64(ERROR))), kind 0;
+     the same on a sample-mode session, and every lighten event (mode 0): x, kind 1 (what these display is the plain sample).
+   The arithmetic, operation by operation, is npe_ops.hires_downsample / edit_field / hires_axis_taps / hires_render (numpy); the
+   device matches them bit for bit.  Without the reservation below nothing of this exists and no other call changes. */
+
+/* scale 1..16 allocates SRC / FIELD / FIELD_KIND for every session of the pool (0 frees them).  Needs ian_sessions_reserve first
+   (-6 otherwise).  Synchronises the device.  Changing the scale drops every session's source (its 64x64 state stays);
+   ian_sessions_reserve(capacity) afterwards resizes the three arrays too, keeping the rows that remain.  An allocation failure
+   (-2) leaves the old pool intact.  3 * S * S + 49 156 bytes per session: 4096 sessions at scale 16 are 12 GB. */
+int ian_sessions_reserve_hires(ian_handle* h, int32_t scale);
+
+/* photos u8[n,3,S,S], host or device (4-byte aligned).  SRC := photos; GIM := the exact integer box mean of SRC over scale x scale
+   blocks, (sum + scale*scale/2) / (scale*scale), computed on the device; then exactly ian_session_open(photos = GIM), in the same
+   submission.  shown u8[n,3,64,64] or NULL receives IM (= GIM).  A plain ian_session_open with 64x64 photos on a session of such
+   a pool clears its source; ian_session_open(source = 1) (commit) on a session with a source first sets SRC := the whole rendered
+   picture, then updates the 64x64 state as always (GIM := IM): SRC's box mean and GIM then differ by rounding. */
+int ian_session_open_hires(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t* photos, uint8_t* shown, void* stream);
+
+typedef struct ian_session_view {
+  int32_t session; /* id in the pool */
+  int32_t x, y;    /* top-left corner of the window in the S x S picture */
+} ian_session_view;
+
+/* Window (x, y, vw, vh) of each view's session at full resolution -> out u8[n,3,vh,vw] (host or device, 4-byte aligned):
+     v = bilinear sample of FIELD at half-pixel centres, edges clamped, float32, every operation rounded on its own
+     kind 0: out = uint8(clip(rint(float32(SRC) + 127.5f * v), 0, 255));   kind 1: out = uint8(clip(rint(127.5f * (v + 1.0f)), 0, 255))
+   (rint rounds ties to even; a zero field returns the source bytes).  x and vw must be multiples of 4 (every lane stores 4 aligned
+   bytes), vw >= 4, vh >= 1, the window inside S x S.  Like ian_session_read it touches neither the decoder's activations nor the
+   residency of ian_session_brush.  The same session may appear several times, as tiles of one picture.
+   -6: no full-resolution reservation.  -7, naming the item, before anything is enqueued: n outside 1..256, an id outside the
+   pool, a session not opened or without a source, a window outside the picture, x or vw not a multiple of 4. */
+int ian_session_render(ian_handle* h, int32_t n, const ian_session_view* views, int32_t vw, int32_t vh, uint8_t* out, void* stream);
+
+/* ian_session_brush followed by ian_session_render of the same sessions, in ONE submission with one synchronisation: the event's
+   64x64 canvas (shown, or NULL) and its full-resolution window (out) come back together.  views[i].session must equal
+   events[i].session (-7). */
+int ian_session_brush_view(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, const ian_session_view* views,
+                           int32_t vw, int32_t vh, uint8_t* out, void* stream);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -22,7 +22,7 @@ import warnings
 import numpy as np
 
 from . import checkpoints, config_loader, lowering, made
-from .lib import BrushItem, Handle, SessionEvent
+from .lib import BrushItem, Handle, SessionEvent, SessionView
 
 BATCH_MAX = 256     # ian_grad_batch / ian_brush_step_batch: 1 <= n <= 256
 
@@ -154,20 +154,84 @@ def pack_session_events(ids, boxes, colours=None, modes=None, weight=0.05, sign=
     return ev
 
 
+def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, sourced=None, events=None):
+    """Python arguments of ian_session_render / ian_session_brush_view -> (a ctypes array of ian_session_view, vw, vh), validated
+    before the library sees anything.  ids (n,) session ids -- the same id may appear several times, as tiles of one picture;
+    origins (n,2) or (2,) as (x, y), the windows' top-left corners in the S x S picture, S = 64 * scale; size = (vw, vh) or one
+    integer for a square window.  x and vw must be multiples of 4, the window inside the picture.  scale is the pool's (None or
+    0: there is no full-resolution reservation).  capacity / opened / sourced (containers of opened ids and of ids that hold a
+    full-resolution source), when given, bound and vet the ids; events (a ctypes array of ian_session_event), when given, must name
+    the same sessions in the same order."""
+    if not scale:
+        raise ValueError("the pool has no full-resolution reservation (reserve_hires)")
+    scale = int(scale)
+    if not 1 <= scale <= 16:
+        raise ValueError("scale must be in 1..16, got %d" % scale)
+    S = 64 * scale
+    a = np.asarray(ids)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("ids must be a 1-D array of integers, got shape %s dtype %s" % (a.shape, a.dtype))
+    n = a.shape[0]
+    if not 1 <= n <= BATCH_MAX:
+        raise ValueError("a call holds 1..%d views, got %d" % (BATCH_MAX, n))
+    sz = np.asarray(size)
+    if sz.ndim == 0:
+        sz = np.tile(sz, 2)
+    if sz.shape != (2,) or not np.issubdtype(sz.dtype, np.integer):
+        raise ValueError("size must be (vw, vh) or one integer, got %r" % (size,))
+    vw, vh = int(sz[0]), int(sz[1])
+    if vw < 1 or vh < 1:
+        raise ValueError("window %d x %d: both sizes must be at least 1" % (vw, vh))
+    if vw % 4:
+        raise ValueError("window width %d is not a multiple of 4" % vw)
+    o = np.asarray(origins)
+    if o.shape == (2,):
+        o = np.tile(o, (n, 1))
+    if o.shape != (n, 2) or not np.issubdtype(o.dtype, np.integer):
+        raise ValueError("origins must be integers of shape (%d,2) or (2,) as (x, y), got %s %s" % (n, o.dtype, o.shape))
+    if events is not None and len(events) != n:
+        raise ValueError("%d views for %d events" % (n, len(events)))
+    views = (SessionView * n)()
+    for i in range(n):
+        sid, x, y = int(a[i]), int(o[i, 0]), int(o[i, 1])
+        if sid < 0 or (capacity is not None and sid >= capacity):
+            raise ValueError("item %d: session %d outside the pool%s" % (i, sid, "" if capacity is None else " (capacity %d)" % capacity))
+        if events is not None and events[i].session != sid:
+            raise ValueError("item %d: the view names session %d, the event session %d" % (i, sid, events[i].session))
+        if opened is not None and sid not in opened:
+            raise ValueError("item %d: session %d has not been opened" % (i, sid))
+        if sourced is not None and sid not in sourced:
+            raise ValueError("item %d: session %d has no full-resolution source (open_hires)" % (i, sid))
+        if x % 4:
+            raise ValueError("item %d: window x %d is not a multiple of 4" % (i, x))
+        if x < 0 or y < 0 or x + vw > S or y + vh > S:
+            raise ValueError("item %d: window (%d,%d) + %d x %d outside the %d x %d picture" % (i, x, y, vw, vh, S, S))
+        v = views[i]
+        v.session, v.x, v.y = sid, x, y
+    return views, vw, vh
+
+
 class EditSessions:
     """Device-resident edit sessions of one model (ian_session_*, include/ian.h): the state NPE.py keeps in host globals per
     editor (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) lives in device memory under a caller-chosen id in 0..capacity-1.  A call takes
     up to 256 sessions in one submission and returns what the canvases show: uint8 (n,3,64,64).
         open    infer (NPE.py:239-274)          reset   Reset (:330-340)           commit  UpdateGIM (:342-345)
         sample  sample (:317-327), z from the caller                                set_latent  paint_latents (:286-302)
-        paint   NPE.paint (:192-235)            scroll  NPE.scroll (:305-316)      brush   the general form of both"""
+        paint   NPE.paint (:192-235)            scroll  NPE.scroll (:305-316)      brush   the general form of both
+    Photos larger than 64x64 (no counterpart in NPE.py): reserve_hires(scale) keeps every session's photo at 64*scale pixels a side;
+        open_hires  infer from the full-size photo     render  windows of the edited picture at full size
+        brush_view / paint(view=) / scroll(view=)      the event and its window in one submission"""
 
     def __init__(self, handle, capacity, zdim, sigma=0.7):
         from . import npe_ops
         self._h = handle
         self._zdim = zdim
         self.capacity = 0
+        self.scale = 0                  # full-resolution reservation: photos are (3, 64*scale, 64*scale); 0 = none
         self._opened = set()
+        self._sourced = set()           # ids whose SRC holds a photo
         self.reserve(capacity)
         self._h.sessions_set_blend(npe_ops.gaussian_half_kernel(sigma, int(4.0 * float(sigma) + 0.5)))
 
@@ -179,6 +243,18 @@ class EditSessions:
         self._h.sessions_reserve(capacity)
         self.capacity = capacity
         self._opened = {v for v in self._opened if v < capacity}
+        self._sourced = {v for v in self._sourced if v < capacity}
+
+    def reserve_hires(self, scale):
+        """Keep every session's photo at (3, 64*scale, 64*scale), scale in 1..16; 0 frees that again.  Changing the scale drops the
+        sessions' sources (their 64x64 state stays)."""
+        scale = int(scale)
+        if not 0 <= scale <= 16:
+            raise ValueError("scale must be in 0..16, got %d" % scale)
+        self._h.sessions_reserve_hires(scale)
+        if scale != self.scale:
+            self._sourced = set()
+        self.scale = scale
 
     def _ids(self, ids, need_opened):
         return check_session_ids(ids, self.capacity, self._opened if need_opened else None)
@@ -202,7 +278,47 @@ class EditSessions:
         shown = np.empty((len(ids), 3, 64, 64), np.uint8)
         self._h.session_open(ids, np.ascontiguousarray(p), 0, shown)
         self._opened.update(int(v) for v in ids)
+        self._sourced.difference_update(int(v) for v in ids)
         return shown
+
+    def open_hires(self, ids, photos):
+        """infer from full-size photos: uint8 (n,3,S,S), S = 64*scale (or (3,S,S) for one id) -> IM, the 64x64 box mean."""
+        if not self.scale:
+            raise ValueError("the pool has no full-resolution reservation (reserve_hires)")
+        ids = self._ids(ids, False)
+        S = 64 * self.scale
+        p = np.asarray(photos)
+        if p.dtype != np.uint8:
+            raise ValueError("photos must be uint8, got %s" % p.dtype)
+        if p.shape == (3, S, S):
+            p = p[None]
+        if p.shape != (len(ids), 3, S, S):
+            raise ValueError("photos must have shape (%d,3,%d,%d), got %s" % (len(ids), S, S, p.shape))
+        shown = np.empty((len(ids), 3, 64, 64), np.uint8)
+        self._h.session_open_hires(ids, np.ascontiguousarray(p), shown)
+        self._opened.update(int(v) for v in ids)
+        self._sourced.update(int(v) for v in ids)
+        return shown
+
+    def _views(self, ids, origins, size, events=None):
+        return pack_session_views(ids, origins, size, self.scale, self.capacity, self._opened, self._sourced, events)
+
+    def render(self, ids, origins, size):
+        """Windows of the pictures at full resolution, as last displayed -> uint8 (n,3,vh,vw).  origins (n,2) or (2,) as (x, y),
+        size (vw, vh) or one integer; x and vw multiples of 4.  The same id may appear several times (tiles)."""
+        views, vw, vh = self._views(ids, origins, size)
+        out = np.empty((len(views), 3, vh, vw), np.uint8)
+        self._h.session_render(views, vw, vh, out)
+        return out
+
+    def brush_view(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, origins=(0, 0), size=64):
+        """brush, and window i of session ids[i] at full resolution after its event, in ONE submission -> (shown, out)."""
+        ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
+        views, vw, vh = self._views(ids, origins, size, ev)
+        shown = np.empty((len(ev), 3, 64, 64), np.uint8)
+        out = np.empty((len(ev), 3, vh, vw), np.uint8)
+        self._h.session_brush_view(ev, views, vw, vh, out, shown)
+        return shown, out
 
     def reset(self, ids):
         """Reset: re-open from the stored GIM."""
@@ -239,17 +355,23 @@ class EditSessions:
         self._h.session_brush(ev, shown)
         return shown
 
-    def paint(self, ids, boxes, colours_uint8, weight=0.05):
-        """NPE.paint: Z -= weight * grad toward the brush colour (levels 0..255 per channel)."""
+    def paint(self, ids, boxes, colours_uint8, weight=0.05, view=None):
+        """NPE.paint: Z -= weight * grad toward the brush colour (levels 0..255 per channel).  view = (origins, size): also the
+        full-resolution windows, as brush_view -> (shown, out)."""
+        if view is not None:
+            return self.brush_view(ids, boxes, colours_uint8, None, weight, -1.0, *view)
         return self.brush(ids, boxes, colours_uint8, None, weight, -1.0)
 
-    def scroll(self, ids, boxes, signs, weight=0.1):
-        """NPE.scroll: Z += sign(event.delta) * weight * grad of the patch mean."""
+    def scroll(self, ids, boxes, signs, weight=0.1, view=None):
+        """NPE.scroll: Z += sign(event.delta) * weight * grad of the patch mean.  view = (origins, size): as in paint."""
+        if view is not None:
+            return self.brush_view(ids, boxes, None, None, weight, signs, *view)
         return self.brush(ids, boxes, None, None, weight, signs)
 
     def read(self, sid):
-        """-> {"Z" (zdim,), "RECON", "ERROR", "IM", "GIM" (3,64,64), "MODE" int}.  Six synchronising copies (one ian_session_read
-        per field): for tests and for saving a picture, not for the event loop."""
+        """-> {"Z" (zdim,), "RECON", "ERROR", "IM", "GIM" (3,64,64), "MODE" int}; in a full-resolution pool also "FIELD" (3,64,64),
+        "FIELD_KIND" int and, for a session that holds one, "SOURCE" (3,S,S).  One synchronising copy (ian_session_read) per field:
+        for tests and for saving a picture, not for the event loop."""
         sid = int(sid)
         if not 0 <= sid < self.capacity:
             raise ValueError("session %d outside the pool (capacity %d)" % (sid, self.capacity))
@@ -257,6 +379,11 @@ class EditSessions:
             raise ValueError("session %d has not been opened" % sid)
         out = {k: self._h.session_read(sid, k) for k in ("Z", "RECON", "ERROR", "IM", "GIM")}
         out["MODE"] = int(self._h.session_read(sid, "MODE")[0])
+        if self.scale:
+            out["FIELD"] = self._h.session_read(sid, "FIELD")
+            out["FIELD_KIND"] = int(self._h.session_read(sid, "FIELD_KIND")[0])
+            if sid in self._sourced:
+                out["SOURCE"] = self._h.session_read(sid, "SOURCE", scale=self.scale)
         return out
 
     def close(self):
@@ -264,7 +391,9 @@ class EditSessions:
         if self.capacity:
             self._h.sessions_reserve(0)
             self.capacity = 0
+            self.scale = 0
             self._opened = set()
+            self._sourced = set()
 
 
 class IAN:

@@ -336,6 +336,8 @@ struct PhotoBlendArgs {
   double* mask;                // MASK float64 [64][64] or nullptr
   double w[8];                 // Gaussian weights, centre outwards (scipy _gaussian_kernel1d)
   int radius;
+  float* field;                // nullptr, or float32 [3][64][64]: float32(MASK * (float64(DELTA) - float64(ERROR))), the edit field of
+                               // full-resolution sessions (npe_ops.edit_field); the other outputs do not depend on it
 };
 hipError_t launch_photo_blend(const PhotoBlendArgs& a, hipStream_t s);
 // n images at once (blockIdx.y = item): every pointer of `a` is the base of an [n]-leading array, the weights are shared
@@ -353,6 +355,11 @@ struct SessionPool {
   float* z;               // Z     f32[capacity][zl]
   int* mode;              // 0 = photo, 1 = sample (NPE.py SAMPLE_FLAG)
   int zl;
+  // full-resolution sessions (ian_sessions_reserve_hires); all nullptr / 0 without that reservation, and then nothing below is touched
+  unsigned char* src;     // SRC   u8 [capacity][3*S*S], S = 64 * scale: the photo at its own resolution
+  float* field;           // FIELD f32[capacity][3*64*64]: what the last call displayed, as an edit field (kind 0) or as x (kind 1)
+  int* kind;              // FIELD_KIND
+  int scale;              // 1..16
 };
 // open, input side: row i = photos[i] (u8 [n][3*64*64]) or, without photos, the session's GIM (source 0) / IM (source 1) -> GIM, IM and
 // x[i] = table[byte] (float32 NCHW, the encoder's input slot); ids = device int[n]; table = 256 floats, to_tanh per level
@@ -376,6 +383,13 @@ struct SessionBlendArgs {
   int radius;
 };
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s);
+// full-resolution open, input side: SRC row of ids[i] := photos[i] (u8 [n][3*S*S]; nullptr: the row already holds the photo), its exact
+// box mean -> GIM, IM and x[i] = table[byte], the outputs of launch_session_open_in
+hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,
+                                     hipStream_t s);
+// npe_ops.hires_render of n windows: views = device int[n][3] (session, x, y), every window vw x vh with x and vw multiples of 4.
+// out u8 [n][3][vh][vw]; out == nullptr: the whole picture (vw = vh = S, x = y = 0) written over the session's own SRC row
+hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s);
 // the batched loss seeds with a constant brush colour per item: colour[3*i + co] where launch_patch_seed_batch /
 // launch_deconv_out_bwd_seed_batch read rgb[i][co][y][x]
 hipError_t launch_patch_seed_colour_batch(const float* xhat, const float* colour, float* g, int H, int W, const int* items, int n,

@@ -294,6 +294,12 @@ struct ian_handle {
     std::vector<int32_t> res_ids;
     std::vector<uint64_t> res_ver;
     bool res_valid = false;
+    // full-resolution sessions (ian_sessions_reserve_hires): pool.src / field / kind / scale, and per session whether SRC holds a photo
+    std::vector<char> has_src;
+    int* d_views = nullptr;              // per call: n ian_session_view records
+    std::vector<int32_t> views_shadow;   // their upload source
+    unsigned char* d_out = nullptr;      // staging of rendered windows for a host `out`, grown on demand
+    size_t out_cap = 0;
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

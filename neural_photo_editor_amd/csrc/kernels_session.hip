@@ -6,6 +6,8 @@
 //   session_gather_z_kernel    brush: the sessions' latents -> the decoder's latent slot
 //   *_seed_colour_batch_kernel brush: the loss seeds of kernels_misc.hip with a constant brush colour per item (NPE.py:205 myRGB)
 //   session_blend_kernel       brush / paint_latents: photo blend (photo mode) or uint8 image (sample mode) per session, z_new -> pool
+//   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
+//   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
 #include "ian_internal.h"
 #include "ian_dact.h"   // m_dact, under the default contraction mode
@@ -174,9 +176,14 @@ __global__ __launch_bounds__(256) void session_store_kernel(const float* __restr
   *reinterpret_cast<uchar4*>(P.recon + row + e) = r;
   *reinterpret_cast<float4*>(P.error + row + e) = err;
   if (shown) *reinterpret_cast<uchar4*>(shown + (size_t)i * S_IMG + e) = shown_recon ? r : a;
+  // full-resolution pools: a sample displays x itself (kind 1), an open / Reset / commit the unedited photo (a zero field, kind 0)
+  if (P.field) *reinterpret_cast<float4*>(P.field + row + e) = new_mode ? v : make_float4(0.f, 0.f, 0.f, 0.f);
   if (blockIdx.x == 0) {
     for (int j = threadIdx.x; j < P.zl; j += 256) P.z[(size_t)id * P.zl + j] = zslot[(size_t)i * zs + j];
-    if (threadIdx.x == 0) P.mode[id] = new_mode;
+    if (threadIdx.x == 0) {
+      P.mode[id] = new_mode;
+      if (P.kind) P.kind[id] = new_mode;
+    }
   }
 }
 hipError_t launch_session_store(const float* xhat, const float* zslot, int zs, const SessionPool& P, const int* ids, int new_mode,
@@ -222,7 +229,9 @@ __global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a)
       o.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
       o.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
       *reinterpret_cast<uchar4*>(sh + e) = o;
+      if (a.P.field) *reinterpret_cast<float4*>(a.P.field + row + e) = v;   // full-resolution pools: what is displayed is x (kind 1)
     }
+    if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 1;
     return;
   }
   PhotoBlendArgs b;
@@ -231,10 +240,12 @@ __global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a)
   b.error = a.P.error + row;
   b.im = a.store ? a.P.im + row : sh;
   b.mask = nullptr;
+  b.field = a.P.field ? a.P.field + row : nullptr;   // full-resolution pools: the blend as an edit field (kind 0)
 #pragma unroll
   for (int k = 0; k < 8; ++k) b.w[k] = a.w[k];
   b.radius = a.radius;
   photo_blend_image(b, m0, m1);
+  if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 0;
   if (a.store) {   // every thread re-reads exactly the bytes it wrote (p = tid + k * PB_T per channel)
     for (int p = threadIdx.x; p < 64 * 64; p += PB_T)
 #pragma unroll
@@ -244,6 +255,148 @@ __global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a)
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s) {
   if (a.radius < 0 || a.radius > 7 || n < 1 || n > 65535 || !a.shown) return hipErrorInvalidValue;
   hipLaunchKernelGGL(session_blend_kernel, dim3(1, n), dim3(PB_T), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---- full-resolution sessions (the arithmetic is npe_ops.hires_downsample / hires_axis_taps / hires_render) ------------
+// The photo lives in the pool at S x S, S = 64 * scale; the 64x64 state above is that of its exact box mean.  What a call displays is
+// kept as FIELD / FIELD_KIND, and a window of the picture at full size is SRC + 127.5 * bilinear(FIELD) (kind 0: the unedited part of
+// the photo stays pixel-exact) or 127.5 * (bilinear(FIELD) + 1) (kind 1: FIELD holds x, a sample has no photo under it).
+
+// open, input side.  grid (64, 3, n): one workgroup per row of one channel of the 64x64 picture, i.e. scale rows of S bytes of the
+// photo; lane q < 16 * scale owns the uchar4 at byte 4q of each of those rows (consecutive lanes, consecutive bytes), copies it to SRC
+// (photos == nullptr: the row is there already) and adds its bytes to the integer sum of the 64x64 pixel they fall in.  Integer
+// sums are exact in any order; (sum + s*s/2) / (s*s) is hires_downsample.  Lanes 0..15 then write GIM, IM and x as
+// session_open_in_kernel does.  photos may be the SRC rows themselves, so neither pointer is __restrict__.
+__global__ __launch_bounds__(256) void session_hires_open_kernel(const unsigned char* photos, SessionPool P, const int* __restrict__ ids,
+                                                                 const float* __restrict__ table, float* __restrict__ x) {
+  __shared__ float tab[256];
+  __shared__ int sum[64];
+  for (int j = threadIdx.x; j < 256; j += blockDim.x) tab[j] = table[j];
+  if (threadIdx.x < 64) sum[threadIdx.x] = 0;
+  __syncthreads();
+  const int s = P.scale, S = 64 * s;
+  const int gy = blockIdx.x, c = blockIdx.y, i = blockIdx.z;
+  const int id = ids[i];
+  const size_t plane = (size_t)S * S, first = (size_t)gy * s * S;
+  unsigned char* dst = P.src + ((size_t)id * 3 + c) * plane + first;
+  const unsigned char* in = photos ? photos + ((size_t)i * 3 + c) * plane + first : dst;
+  const int q = threadIdx.x;
+  if (q < 16 * s) {
+    int acc[4] = {0, 0, 0, 0};
+    for (int r = 0; r < s; ++r) {
+      const uchar4 v = *reinterpret_cast<const uchar4*>(in + (size_t)r * S + 4 * q);
+      if (photos) *reinterpret_cast<uchar4*>(dst + (size_t)r * S + 4 * q) = v;
+      acc[0] += v.x;
+      acc[1] += v.y;
+      acc[2] += v.z;
+      acc[3] += v.w;
+    }
+    int bin = (4 * q) / s, t = acc[0];   // bytes of one 64x64 pixel are summed in the lane first: one LDS add per pixel touched
+#pragma unroll
+    for (int e = 1; e < 4; ++e) {
+      const int b = (4 * q + e) / s;
+      if (b != bin) {
+        atomicAdd(&sum[bin], t);
+        bin = b;
+        t = 0;
+      }
+      t += acc[e];
+    }
+    atomicAdd(&sum[bin], t);
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    const int e = threadIdx.x * 4, d = s * s, half = d / 2;
+    uchar4 v;
+    v.x = (unsigned char)((sum[e] + half) / d);
+    v.y = (unsigned char)((sum[e + 1] + half) / d);
+    v.z = (unsigned char)((sum[e + 2] + half) / d);
+    v.w = (unsigned char)((sum[e + 3] + half) / d);
+    const size_t o = (size_t)c * 64 * 64 + gy * 64 + e;
+    *reinterpret_cast<uchar4*>(P.gim + (size_t)id * S_IMG + o) = v;
+    *reinterpret_cast<uchar4*>(P.im + (size_t)id * S_IMG + o) = v;
+    *reinterpret_cast<float4*>(x + (size_t)i * S_IMG + o) = make_float4(tab[v.x], tab[v.y], tab[v.z], tab[v.w]);
+  }
+}
+hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,
+                                     hipStream_t s) {
+  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_hires_open_kernel, dim3(64, 3, n), dim3((16 * P.scale + 63) / 64 * 64), 0, s, photos, P, ids, table, x);
+  return hipGetLastError();
+}
+
+// hires_axis_taps for one output coordinate: half-pixel centres in integers, a = 2Y + 1 - s in (-2s, 128s), i0 = floor(a / 2s) >= -1,
+// t = float32(a - 2s * i0) / float32(2s) (one division), both taps clamped to 0..63
+__device__ __forceinline__ void hires_taps(int Y, int s, int& lo, int& hi, float& t) {
+  const int s2 = 2 * s, a = 2 * Y + 1 - s;
+  const int i0 = (a + s2) / s2 - 1;   // a + 2s > 0: truncation is the floor
+  t = (float)(a - s2 * i0) / (float)s2;
+  lo = min(max(i0, 0), 63);
+  hi = min(max(i0 + 1, 0), 63);
+}
+
+// render.  grid (bands of RENDER_BAND output rows, 3, n); a lane owns 4 consecutive output bytes: one uchar4 load of SRC, one uchar4
+// store.  The band's field rows -- at most ceil((RENDER_BAND - 1) / s) + 2 <= RENDER_BAND + 2 consecutive rows of 64 floats -- go to LDS
+// once; every tap reads from there.  All arithmetic is float32 with contraction off, in hires_render's order.
+// Band height: the traffic is 2 bytes per output byte plus the staged rows, so the band only has to keep the staging small against
+// 8 * vw bytes of output and the grid large; 8 rows give 384 workgroups (1.5 per CU) for ONE whole 1024 x 1024 picture and
+// 2 uchar4 per lane at a 256-wide window.
+// out == nullptr: the whole picture over the session's own SRC row (commit): every lane stores exactly the bytes it loaded, so
+// this is safe in place; SRC and out are therefore not __restrict__.
+constexpr int RENDER_BAND = 8;
+__global__ __launch_bounds__(256) void session_render_kernel(SessionPool P, const int* __restrict__ views, int vw, int vh, unsigned char* out) {
+  __shared__ float f[(RENDER_BAND + 2) * 64];
+  const int s = P.scale, S = 64 * s;
+  const int c = blockIdx.y, i = blockIdx.z;
+  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
+  const int y0 = blockIdx.x * RENDER_BAND, rows = min(RENDER_BAND, vh - y0);
+  int fr0, fr1, unused;
+  float tunused;
+  hires_taps(vy + y0, s, fr0, unused, tunused);
+  hires_taps(vy + y0 + rows - 1, s, unused, fr1, tunused);
+  const int nfr = min(fr1 - fr0 + 1, RENDER_BAND + 2);
+  const float* frow = P.field + ((size_t)id * 3 + c) * (64 * 64) + fr0 * 64;
+  for (int j = threadIdx.x; j < nfr * 64; j += 256) f[j] = frow[j];
+  __syncthreads();
+  const int kind = P.kind[id];
+  const unsigned char* src = P.src + ((size_t)id * 3 + c) * S * S;
+  unsigned char* dst = out ? out + ((size_t)i * 3 + c) * vh * vw : P.src + ((size_t)id * 3 + c) * S * S;
+  const int dstride = out ? vw : S;
+  const int L = vw >> 2;
+  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
+    const int ry = idx / L, cx = (idx - ry * L) * 4;
+    const int Y = vy + y0 + ry;
+    int r0, r1;
+    float ty;
+    hires_taps(Y, s, r0, r1, ty);
+    const float* top = f + (r0 - fr0) * 64;
+    const float* bot = f + (r1 - fr0) * 64;
+    uchar4 pv = make_uchar4(0, 0, 0, 0);
+    if (kind == 0) pv = *reinterpret_cast<const uchar4*>(src + (size_t)Y * S + vx + cx);
+    const unsigned char pb[4] = {pv.x, pv.y, pv.z, pv.w};
+    unsigned char ob[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      int c0, c1;
+      float tx;
+      hires_taps(vx + cx + e, s, c0, c1, tx);
+      const float a0 = top[c0], a1 = bot[c0];
+      const float t = a0 + tx * (top[c1] - a0);
+      const float b = a1 + tx * (bot[c1] - a1);
+      const float v = t + ty * (b - t);
+      const float qv = kind == 0 ? (float)pb[e] + 127.5f * v : 127.5f * (v + 1.0f);
+      ob[e] = (unsigned char)fminf(fmaxf(rintf(qv), 0.0f), 255.0f);
+    }
+    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : vx + cx)) = make_uchar4(ob[0], ob[1], ob[2], ob[3]);
+  }
+}
+hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s) {
+  const int S = 64 * P.scale;
+  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || vw < 4 || (vw & 3) || vh < 1 || vw > S || vh > S)
+    return hipErrorInvalidValue;
+  if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_render_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, P, views, vw, vh, out);
   return hipGetLastError();
 }
 

@@ -80,6 +80,7 @@ __device__ __forceinline__ void photo_blend_image(const PhotoBlendArgs& a, doubl
       const double t64 = 2.0 * ((double)rb / 255.0) - 1.0;   // to_tanh(RECON): uint8 -> float64
       const double v = 255.0 * ((t64 + D) + 1.0) / 2.0;
       a.im[c * HW + p] = np_uint8(v);
+      if (a.field) a.field[c * HW + p] = (float)(mask * ((double)delta - (double)a.error[c * HW + p]));   // npe_ops.edit_field
     }
   }
 }

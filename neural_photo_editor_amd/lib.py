@@ -45,6 +45,7 @@ EXPORTS = (
     "ian_read_slot", "ian_read_slot_grad",
     "ian_brush_step", "ian_grad_batch", "ian_brush_step_batch",
     "ian_sessions_reserve", "ian_sessions_set_blend", "ian_session_open", "ian_session_set_latent", "ian_session_brush", "ian_session_read",
+    "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -110,6 +111,10 @@ def load_library():
     lib.ian_session_set_latent.argtypes = [vp, i32, fp, fp, i32, fp, vp]
     lib.ian_session_brush.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, vp]
     lib.ian_session_read.argtypes = [vp, i32, i32, fp, vp]
+    lib.ian_sessions_reserve_hires.argtypes = [vp, i32]
+    lib.ian_session_open_hires.argtypes = [vp, i32, fp, fp, fp, vp]
+    lib.ian_session_render.argtypes = [vp, i32, C.POINTER(SessionView), i32, i32, fp, vp]
+    lib.ian_session_brush_view.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, C.POINTER(SessionView), i32, i32, fp, vp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -156,9 +161,15 @@ class SessionEvent(C.Structure):
                 ("coef", C.c_float), ("gscale", C.c_float), ("rgb", C.c_float * 3)]
 
 
-# enum ian_session_field (include/ian.h): name -> (code, dtype, shape; None = (num_latents,))
+class SessionView(C.Structure):
+    """ian_session_view (include/ian.h): one window of a full-resolution session (ian_session_render / ian_session_brush_view)."""
+    _fields_ = [("session", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+# enum ian_session_field (include/ian.h): name -> (code, dtype, shape; None = (num_latents,); "S" = (3, 64*scale, 64*scale))
 SESSION_FIELDS = {"Z": (0, np.float32, None), "RECON": (1, np.uint8, (3, 64, 64)), "ERROR": (2, np.float32, (3, 64, 64)),
-                  "IM": (3, np.uint8, (3, 64, 64)), "GIM": (4, np.uint8, (3, 64, 64)), "MODE": (5, np.int32, (1,))}
+                  "IM": (3, np.uint8, (3, 64, 64)), "GIM": (4, np.uint8, (3, 64, 64)), "MODE": (5, np.int32, (1,)),
+                  "FIELD": (6, np.float32, (3, 64, 64)), "FIELD_KIND": (7, np.int32, (1,)), "SOURCE": (8, np.uint8, "S")}
 
 
 def session_tanh_table():
@@ -314,8 +325,29 @@ class Handle:
         self._check(self.lib.ian_session_brush(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
                                                C.c_void_p(stream or 0)))
 
-    def session_read(self, sid, what, stream=None):
+    def sessions_reserve_hires(self, scale):
+        self._check(self.lib.ian_sessions_reserve_hires(self._h, int(scale)))
+
+    def session_open_hires(self, ids, photos, shown=None, stream=None):
+        """ian_session_open_hires; ids = int32 array (n = its length), photos u8[n,3,S,S], shown u8[n,3,64,64] or None."""
+        self._check(self.lib.ian_session_open_hires(self._h, len(ids), _ptr(ids), _ptr(photos),
+                                                    _ptr(shown) if shown is not None else C.c_void_p(0), C.c_void_p(stream or 0)))
+
+    def session_render(self, views, vw, vh, out, stream=None):
+        """ian_session_render; views = a ctypes array of SessionView (n = its length), out u8[n,3,vh,vw]."""
+        self._check(self.lib.ian_session_render(self._h, len(views), views, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def session_brush_view(self, events, views, vw, vh, out, shown=None, stream=None):
+        """ian_session_brush_view; events / views = ctypes arrays of SessionEvent / SessionView of the same length."""
+        self._check(self.lib.ian_session_brush_view(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
+                                                    views, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def session_read(self, sid, what, stream=None, scale=0):
         code, dtype, shape = SESSION_FIELDS[what]
+        if shape == "S":
+            if not 1 <= int(scale) <= 16:       # the library writes 3 * S * S bytes: never into a buffer sized from a wrong scale
+                raise ValueError("reading %s needs the pool's scale (1..16), got %r" % (what, scale))
+            shape = (3, 64 * int(scale), 64 * int(scale))
         out = np.empty(shape if shape is not None else (self.lowered.num_latents,), dtype)
         self._check(self.lib.ian_session_read(self._h, int(sid), code, _ptr(out), C.c_void_p(stream or 0)))
         return out

@@ -122,3 +122,74 @@ def photo_blend(model, Z, recon_uint8, error):
     if hasattr(model, "photo_blend"):
         return model.photo_blend(z, recon_uint8, error)
     return photo_blend_host(model.sample_at(z)[0], recon_uint8, error)
+
+
+# ---- full-resolution sessions (ian_sessions_reserve_hires, include/ian.h) ------------------------------------------------
+# The reference has no counterpart (NPE.py:152: "This 64 may need to change if the canvas size changes"), so these four functions ARE
+# the specification: the device (kernels_session.hip) matches them bit for bit.  s is the pool's integer scale, 1 <= s <= 16; a source
+# photo is uint8 (3, 64*s, 64*s).
+HIRES_MAX_SCALE = 16
+
+
+def _hires_scale(s):
+    if int(s) != s or not 1 <= int(s) <= HIRES_MAX_SCALE:
+        raise ValueError("scale must be an integer in 1..%d, got %r" % (HIRES_MAX_SCALE, s))
+    return int(s)
+
+
+def hires_downsample(src, s):
+    """uint8 (3, 64s, 64s) -> uint8 (3,64,64): the exact integer box mean, (sum of the s x s block + (s*s)//2) // (s*s)."""
+    s = _hires_scale(s)
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or src.shape != (3, 64 * s, 64 * s):
+        raise ValueError("a source photo at scale %d is uint8 (3,%d,%d), got %s %s" % (s, 64 * s, 64 * s, src.dtype, src.shape))
+    total = src.reshape(3, 64, s, 64, s).sum(axis=(2, 4), dtype=np.int64)
+    return np.uint8((total + (s * s) // 2) // (s * s))
+
+
+def edit_field(x, recon_uint8, error, mask):
+    """What the photo blend adds to the photo, in tanh units: IM = from_tanh(to_tanh(RECON) + MASK*DELTA + (1-MASK)*ERROR) and
+    ERROR = to_tanh(GIM) - to_tanh(RECON) give IM = GIM + 127.5 * MASK*(DELTA - ERROR).  DELTA is the blend's own float32 delta, the
+    product is float64 (MASK is the float64 mask photo_blend_host returns), rounded to float32 once.  -> float32 (3,64,64)."""
+    DELTA = np.asarray(x, np.float32) - to_tanh(np.float32(np.asarray(recon_uint8)))
+    return np.float32(np.asarray(mask, np.float64) * (np.float64(DELTA) - np.float64(np.asarray(error))))
+
+
+def hires_axis_taps(s, lo, cnt):
+    """Bilinear taps of output coordinates Y = lo .. lo+cnt-1 of a 64s-long axis into the 64-long field axis, half-pixel centres,
+    in integers: a = 2Y + 1 - s, i0 = floor(a / 2s), k = a - 2s*i0 in [0, 2s), t = float32(k) / float32(2s) (one float32
+    division).  -> (clip(i0, 0, 63), clip(i0 + 1, 0, 63), t): the edges are clamped."""
+    s = _hires_scale(s)
+    Y = np.arange(int(lo), int(lo) + int(cnt), dtype=np.int64)
+    a = 2 * Y + 1 - s
+    i0 = a // (2 * s)                        # floor division
+    k = a - 2 * s * i0
+    t = np.float32(k) / np.float32(2 * s)
+    return np.clip(i0, 0, 63), np.clip(i0 + 1, 0, 63), t
+
+
+def hires_render(src, field, kind, s, vx, vy, vw, vh):
+    """Window (vx, vy, vw, vh) of the full-resolution picture -> uint8 (3, vh, vw).  float32 throughout, every operation rounded on its
+    own (no fma):  per field row  r = A + tx*(B - A)  (A, B = the field at the two column taps);  v = top + ty*(bot - top);
+    kind 0 (photo plus edit field)  q = float32(src) + 127.5f*v;   kind 1 (field holds the sample x)  q = 127.5f*(v + 1.0f);
+    out = uint8(clip(rint(q), 0, 255)), ties to even.  A zero field returns the source bytes."""
+    s = _hires_scale(s)
+    S = 64 * s
+    vx, vy, vw, vh = int(vx), int(vy), int(vw), int(vh)
+    if vw < 1 or vh < 1 or vx < 0 or vy < 0 or vx + vw > S or vy + vh > S:
+        raise ValueError("window (%d,%d) + %d x %d outside the %d x %d picture" % (vx, vy, vw, vh, S, S))
+    if kind not in (0, 1):
+        raise ValueError("kind must be 0 (photo plus field) or 1 (plain sample), got %r" % (kind,))
+    F = np.asarray(field, np.float32)
+    c0, c1, tx = hires_axis_taps(s, vx, vw)
+    r0, r1, ty = hires_axis_taps(s, vy, vh)
+    A = F[:, :, c0]
+    rows = A + tx * (F[:, :, c1] - A)        # (3,64,vw): a field row's horizontal pass is the same for every output row that taps it
+    top = rows[:, r0]
+    v = top + ty[None, :, None] * (rows[:, r1] - top)
+    if kind == 0:
+        q = np.float32(np.asarray(src)[:, vy:vy + vh, vx:vx + vw]) + np.float32(127.5) * v
+    else:
+        q = np.float32(127.5) * (v + np.float32(1.0))
+    assert q.dtype == np.float32
+    return np.uint8(np.clip(np.rint(q), 0, 255))
