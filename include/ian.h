@@ -268,7 +268,10 @@ enum ian_session_field {
   /* full-resolution pools only (-6 without ian_sessions_reserve_hires) */
   IAN_SESSION_FIELD = 6,      /* f32[3,64,64]: what the last call displayed, see ian_session_render */
   IAN_SESSION_FIELD_KIND = 7, /* int32: 0 = FIELD is an edit field on top of the source, 1 = FIELD is the sample x itself */
-  IAN_SESSION_SOURCE = 8      /* u8[3,S,S]: the raw full-resolution source (-7 for a session without one) */
+  IAN_SESSION_SOURCE = 8,     /* u8[3,S,S]: the raw full-resolution source (-7 for a session without one) */
+  /* pools with the local reservation only (-6 without ian_sessions_reserve_local) */
+  IAN_SESSION_UMASK = 9, /* f64[64,64] */
+  IAN_SESSION_LOCAL = 10 /* int32 flags */
 };
 /* One field of an opened session -> out (host or device): tests, saving a picture (NPE.py has no counterpart: its state is
    host globals).  Leaves the resident activations alone. */
@@ -317,6 +320,43 @@ int ian_session_render(ian_handle* h, int32_t n, const ian_session_view* views, 
    events[i].session (-7). */
 int ian_session_brush_view(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, const ian_session_view* views,
                            int32_t vw, int32_t vh, uint8_t* out, void* stream);
+
+/* ---- local edits: the edit stays where the user painted ----
+   NPE.paint's MASK comes from |DELTA| anywhere in the picture, so a stroke on the hair can change the mouth.  The reference left three
+   tools for that: USER_MASK ("currently not implemented", NPE.py:58-59, :221), the brush falloff gk (NPE.py:167-175) and dampen
+   (NPE.py:184-189, commented out at :227 and :298).  A pool with the reservation below keeps per session UMASK f64[64,64] (where the
+   user has brushed) and LOCAL (int32 flags: bit 0 = local, bit 1 = dampen).  For an opened session with flags != 0:
+     a mode-1 event of ian_session_brush / ian_session_brush_view on a photo-mode session, bit 0 set: first
+       UMASK := max(UMASK, F), F[y][x] = falloff[dy] * falloff[dx] with gk's distances to the rectangle (0 inside it; an empty
+       rectangle adds nothing); then the blend with MASK_L = MASK * UMASK in place of MASK:
+       D = MASK_L*DELTA + (1-MASK_L)*ERROR; IM = uint8(from_tanh(to_tanh(RECON) + D)); FIELD = float32(MASK_L * (DELTA - ERROR));
+     bit 1: with t = to_tanh(float32(RECON)), D := thresh - t where t + D > thresh, and FIELD = float32(D - ERROR); bit 1 alone
+       uses the plain MASK and leaves UMASK untouched;
+     ian_session_set_latent(as_sample = 0) on a photo-mode session: the same blend with the current UMASK, no footprint added (an
+       edit on the latent canvas shows only where the user has brushed);
+     lighten events, sample-mode sessions and as_sample = 1: as without the flags.
+   ian_session_open (all three sources) and ian_session_open_hires clear the session's UMASK in the same submission (USER_MASK *= 0,
+   NPE.py:267, :337) and keep LOCAL; a commit on a session with a full-resolution source renders first.  A session with flags 0 gives
+   byte for byte the results of a pool without the reservation, and such a pool runs the kernels it always ran.  The arithmetic,
+   operation by operation in float64, is npe_ops.local_falloff_table / local_footprint / umask_paint / photo_blend_local (numpy); the
+   device matches them bit for bit. */
+
+/* on = 1 allocates UMASK and LOCAL for every session of the pool, both zero; on = 0 frees them and forgets the falloff table.  Needs
+   ian_sessions_reserve first (-6 otherwise).  Synchronises the device.  ian_sessions_reserve(capacity) afterwards resizes both
+   arrays too, keeping the rows that remain (new rows are zero).  An allocation failure (-2) leaves the old pool intact.
+   32 772 bytes per session. */
+int ian_sessions_reserve_local(ian_handle* h, int32_t on);
+/* The footprint's falloff and the dampen threshold for every later call: falloff64 f64[64] (host; npe_ops.local_falloff_table:
+   exp(-(d*d/64.0)/(2*sigma*sigma)), sigma 0.3 in NPE.py:170), falloff64[d] at d pixels from the rectangle along one axis.  -7 for a
+   table whose entry 0 is not 1.0 or that has an entry outside [0,1] or a NaN; -6 without the reservation.  NPE.py:187's threshold is
+   0.75.  Events and set_latent(as_sample = 0) that name a session with flags != 0 return -6 until this was called.  Synchronises
+   the device. */
+int ian_sessions_set_local(ian_handle* h, const double* falloff64, double dampen_thresh);
+/* LOCAL[ids[i]] := flags[i] (0..3; bit 0 local, bit 1 dampen) and UMASK[ids[i]] := 0, whichever flags are given, for n opened
+   sessions in one submission.  ids and flags are host arrays.  Like ian_session_read it leaves the decoder's resident activations
+   and the residency of ian_session_brush alone.  -6 without the reservation; -7, naming the item, before anything is enqueued: n
+   outside 1..256, an id outside the pool, a session not opened, an id given twice, flags outside 0..3. */
+int ian_session_local(ian_handle* h, int32_t n, const int32_t* ids, const int32_t* flags, void* stream);
 
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */

@@ -213,6 +213,30 @@ def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, so
     return views, vw, vh
 
 
+def pack_session_local(ids, local=True, dampen=False, flags=None, capacity=None, opened=None):
+    """Python arguments of ian_session_local -> (ids int32 (n,), flags int32 (n,)), validated before the library sees anything.
+    local and dampen are booleans, one for all or one per session: flags = local + 2 * dampen.  flags, when given, replaces both: a
+    scalar or (n,) integers in 0..3 (bit 0 local, bit 1 dampen).  capacity / opened (a container of opened ids), when given, bound and
+    vet the ids."""
+    idv = check_session_ids(ids, capacity, opened)
+    n = len(idv)
+    def per_item(v, what, top):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            a = np.tile(a, n)
+        if a.shape != (n,) or not (np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_):
+            raise ValueError("%s must be one value or %d values of an integer or boolean type, got %s %s" % (what, n, a.dtype, a.shape))
+        for i, t in enumerate(int(t) for t in a):
+            if not 0 <= t <= top:
+                raise ValueError("item %d: %s %d outside 0..%d" % (i, what, t, top))
+        return a.astype(np.int32)
+    if flags is not None:
+        f = per_item(flags, "flags", 3)
+    else:
+        f = per_item(local, "local", 1) + 2 * per_item(dampen, "dampen", 1)
+    return idv, np.ascontiguousarray(f, np.int32)
+
+
 class EditSessions:
     """Device-resident edit sessions of one model (ian_session_*, include/ian.h): the state NPE.py keeps in host globals per
     editor (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) lives in device memory under a caller-chosen id in 0..capacity-1.  A call takes
@@ -222,7 +246,9 @@ class EditSessions:
         paint   NPE.paint (:192-235)            scroll  NPE.scroll (:305-316)      brush   the general form of both
     Photos larger than 64x64 (no counterpart in NPE.py): reserve_hires(scale) keeps every session's photo at 64*scale pixels a side;
         open_hires  infer from the full-size photo     render  windows of the edited picture at full size
-        brush_view / paint(view=) / scroll(view=)      the event and its window in one submission"""
+        brush_view / paint(view=) / scroll(view=)      the event and its window in one submission
+    Local edits (NPE.py's unimplemented USER_MASK, gk and dampen): reserve_local() keeps a user mask per session;
+        set_local(ids, local, dampen)  from then on a paint on those sessions changes the photo only around the strokes made since"""
 
     def __init__(self, handle, capacity, zdim, sigma=0.7):
         from . import npe_ops
@@ -230,6 +256,7 @@ class EditSessions:
         self._zdim = zdim
         self.capacity = 0
         self.scale = 0                  # full-resolution reservation: photos are (3, 64*scale, 64*scale); 0 = none
+        self.local = False              # local reservation: UMASK and the LOCAL flags per session
         self._opened = set()
         self._sourced = set()           # ids whose SRC holds a photo
         self.reserve(capacity)
@@ -255,6 +282,33 @@ class EditSessions:
         if scale != self.scale:
             self._sourced = set()
         self.scale = scale
+
+    def reserve_local(self, on=True, sigma=0.3, dampen_thresh=0.75):
+        """Keep a user mask (UMASK float64 (64,64)) and the LOCAL flags per session, 32 772 bytes each, and set the brush footprint's
+        falloff (npe_ops.local_falloff_table(sigma); NPE.py:170 has 0.3) and the dampen threshold (NPE.py:187 has 0.75).  on=False
+        frees them again.  Sessions start with flags 0: nothing changes until set_local."""
+        from . import npe_ops
+        if not on:
+            self._h.sessions_reserve_local(False)
+            self.local = False
+            return
+        sigma, dampen_thresh = float(sigma), float(dampen_thresh)
+        if not (sigma > 0.0 and np.isfinite(sigma)):
+            raise ValueError("sigma must be a positive number, got %r" % (sigma,))
+        if not np.isfinite(dampen_thresh):
+            raise ValueError("dampen_thresh must be finite, got %r" % (dampen_thresh,))
+        table = npe_ops.local_falloff_table(sigma)
+        self._h.sessions_reserve_local(True)
+        self._h.sessions_set_local(table, dampen_thresh)
+        self.local = True
+
+    def set_local(self, ids, local=True, dampen=False, flags=None):
+        """The sessions' LOCAL flags (bit 0 local: the blend is masked by where the user has brushed; bit 1 dampen), one value for
+        all or one per session; their user masks are cleared, whichever flags are given."""
+        if not self.local:
+            raise ValueError("the pool has no local reservation (reserve_local)")
+        idv, f = pack_session_local(ids, local, dampen, flags, self.capacity, self._opened)
+        self._h.session_local(idv, f)
 
     def _ids(self, ids, need_opened):
         return check_session_ids(ids, self.capacity, self._opened if need_opened else None)
@@ -370,7 +424,8 @@ class EditSessions:
 
     def read(self, sid):
         """-> {"Z" (zdim,), "RECON", "ERROR", "IM", "GIM" (3,64,64), "MODE" int}; in a full-resolution pool also "FIELD" (3,64,64),
-        "FIELD_KIND" int and, for a session that holds one, "SOURCE" (3,S,S).  One synchronising copy (ian_session_read) per field:
+        "FIELD_KIND" int and, for a session that holds one, "SOURCE" (3,S,S); in a pool with the local reservation also "UMASK"
+        float64 (64,64) and "LOCAL" int.  One synchronising copy (ian_session_read) per field:
         for tests and for saving a picture, not for the event loop."""
         sid = int(sid)
         if not 0 <= sid < self.capacity:
@@ -384,6 +439,9 @@ class EditSessions:
             out["FIELD_KIND"] = int(self._h.session_read(sid, "FIELD_KIND")[0])
             if sid in self._sourced:
                 out["SOURCE"] = self._h.session_read(sid, "SOURCE", scale=self.scale)
+        if self.local:
+            out["UMASK"] = self._h.session_read(sid, "UMASK")
+            out["LOCAL"] = int(self._h.session_read(sid, "LOCAL")[0])
         return out
 
     def close(self):
@@ -392,6 +450,7 @@ class EditSessions:
             self._h.sessions_reserve(0)
             self.capacity = 0
             self.scale = 0
+            self.local = False
             self._opened = set()
             self._sourced = set()
 

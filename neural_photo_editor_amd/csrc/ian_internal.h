@@ -339,6 +339,14 @@ struct PhotoBlendArgs {
   float* field;                // nullptr, or float32 [3][64][64]: float32(MASK * (float64(DELTA) - float64(ERROR))), the edit field of
                                // full-resolution sessions (npe_ops.edit_field); the other outputs do not depend on it
 };
+// what photo_blend_image<true> takes besides (local edit sessions; npe_ops.photo_blend_local / umask_paint)
+struct PhotoLocalArgs {
+  double* umask;               // the session's UMASK float64 [64][64]: MASK_L = MASK * UMASK; nullptr: MASK_L = MASK
+  const double* falloff;       // float64 [64], npe_ops.local_falloff_table; nullptr, or an empty box: no footprint is added to UMASK
+  int c1, r1, c2, r2;          // the brush rectangle whose footprint is max-ed into UMASK first
+  int dampen;                  // != 0: D = where(to_tanh(float32(RECON)) + D > thresh, thresh - to_tanh(float32(RECON)), D)
+  double thresh;
+};
 hipError_t launch_photo_blend(const PhotoBlendArgs& a, hipStream_t s);
 // n images at once (blockIdx.y = item): every pointer of `a` is the base of an [n]-leading array, the weights are shared
 hipError_t launch_photo_blend_batch(const PhotoBlendArgs& a, int n, hipStream_t s);
@@ -360,6 +368,9 @@ struct SessionPool {
   float* field;           // FIELD f32[capacity][3*64*64]: what the last call displayed, as an edit field (kind 0) or as x (kind 1)
   int* kind;              // FIELD_KIND
   int scale;              // 1..16
+  // local edits (ian_sessions_reserve_local); both nullptr without that reservation, and then session_blend_kernel runs as ever
+  double* umask;          // UMASK f64[capacity][64*64]: where the user has brushed (npe_ops.umask_paint)
+  int* local;             // LOCAL int[capacity]: bit 0 = the blend is masked by UMASK, bit 1 = dampen
 };
 // open, input side: row i = photos[i] (u8 [n][3*64*64]) or, without photos, the session's GIM (source 0) / IM (source 1) -> GIM, IM and
 // x[i] = table[byte] (float32 NCHW, the encoder's input slot); ids = device int[n]; table = 256 floats, to_tanh per level
@@ -381,8 +392,13 @@ struct SessionBlendArgs {
   int store;              // photo mode: != 0 the blend also becomes the session's IM
   double w[8];            // as PhotoBlendArgs
   int radius;
+  const double* falloff;  // pools with the local reservation: device f64[64] (ian_sessions_set_local) and the dampen threshold
+  double thresh;
 };
+// P.umask == nullptr: session_blend_kernel; otherwise session_blend_local_kernel, which reads the sessions' LOCAL flags
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s);
+// UMASK row of session ids[i] := 0 and, with flags (device int[n]), LOCAL[ids[i]] := flags[i]
+hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const int* flags, int n, hipStream_t s);
 // full-resolution open, input side: SRC row of ids[i] := photos[i] (u8 [n][3*S*S]; nullptr: the row already holds the photo), its exact
 // box mean -> GIM, IM and x[i] = table[byte], the outputs of launch_session_open_in
 hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,

@@ -9,6 +9,10 @@
 // Full-resolution sessions (ian_sessions_reserve_hires, DESIGN.md 4.3) add three arrays: SRC (the photo at S x S, S = 64 * scale), FIELD
 // and FIELD_KIND (what the last call displayed, as something ian_session_render can apply to SRC), and a per-session host flag
 // "SRC holds a photo".  Without that reservation pool.src / field / kind are null and no kernel touches them.
+//
+// Local edits (ian_sessions_reserve_local, DESIGN.md 4.4) add UMASK (where the user has brushed) and the LOCAL flags per session, and
+// per handle the falloff table of the brush footprint.  Without that reservation pool.umask / local are null, launch_session_blend
+// runs session_blend_kernel, and no other kernel is launched.
 namespace {
 
 constexpr size_t SESS_IMG = 3 * 64 * 64;
@@ -27,9 +31,14 @@ void sessions_free(ian_handle* h) {
   auto& S = h->sess;
   SessionPool& P = S.pool;
   for (void* p : {(void*)P.gim, (void*)P.im, (void*)P.recon, (void*)P.error, (void*)P.z, (void*)P.mode, (void*)S.d_tab, (void*)S.d_tanh,
-                  (void*)S.d_photo, (void*)S.d_shown, (void*)P.src, (void*)P.field, (void*)P.kind, (void*)S.d_views, (void*)S.d_out})
+                  (void*)S.d_photo, (void*)S.d_shown, (void*)P.src, (void*)P.field, (void*)P.kind, (void*)S.d_views, (void*)S.d_out,
+                  (void*)P.umask, (void*)P.local, (void*)S.d_falloff, (void*)S.d_ltab})
     if (p) (void)hipFree(p);
   P = SessionPool{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  S.d_falloff = nullptr;
+  S.d_ltab = nullptr;
+  S.falloff_set = false;
+  S.local_flags.clear();
   S.d_tab = nullptr;
   S.d_tanh = nullptr;
   S.d_photo = S.d_shown = nullptr;
@@ -44,6 +53,7 @@ void sessions_free(ian_handle* h) {
 }
 
 size_t sess_src_bytes(int scale) { return 3 * (size_t)(64 * scale) * (size_t)(64 * scale); }
+constexpr size_t SESS_UMASK = 64 * 64 * sizeof(double);
 
 // session calls need the 3x64x64 image on both ends (the pool rows, the blend and the open kernels are written for it)
 int session_model_check(ian_handle* h, const char* fn) {
@@ -88,23 +98,35 @@ int sessions_reserve(ian_handle* h, int capacity) {
       if (e == hipSuccess) e = grow((void**)&N.field, S.pool.field, SESS_IMG * sizeof(float));
       if (e == hipSuccess) e = grow((void**)&N.kind, S.pool.kind, sizeof(int));
     }
+    if (S.pool.umask) {   // a pool with the local reservation: UMASK and LOCAL follow the capacity, new rows are zero
+      auto grow0 = [&](void** dst, const void* src, size_t row_bytes) -> hipError_t {
+        hipError_t g = grow(dst, src, row_bytes);
+        if (g == hipSuccess && c > keep) g = hipMemset((char*)*dst + keep * row_bytes, 0, (c - keep) * row_bytes);
+        return g;
+      };
+      if (e == hipSuccess) e = grow0((void**)&N.umask, S.pool.umask, SESS_UMASK);
+      if (e == hipSuccess) e = grow0((void**)&N.local, S.pool.local, sizeof(int));
+      if (e == hipSuccess) e = hipDeviceSynchronize();   // the zeros are there before any stream reads them
+    }
     if (e != hipSuccess) {   // the old pool stays as it was
       for (void* p : {(void*)N.gim, (void*)N.im, (void*)N.recon, (void*)N.error, (void*)N.z, (void*)N.mode, (void*)N.src, (void*)N.field,
-                      (void*)N.kind})
+                      (void*)N.kind, (void*)N.umask, (void*)N.local})
         if (p) (void)hipFree(p);
       (void)hipGetLastError();
       return fail(h, -2, "ian_sessions_reserve: %s for %d sessions of %zu bytes", hipGetErrorString(e), capacity,
                   3 * SESS_IMG + SESS_IMG * sizeof(float) + (size_t)zl * sizeof(float) + sizeof(int) +
-                      (N.scale ? sess_src_bytes(N.scale) + SESS_IMG * sizeof(float) + sizeof(int) : 0));
+                      (N.scale ? sess_src_bytes(N.scale) + SESS_IMG * sizeof(float) + sizeof(int) : 0) +
+                      (S.pool.umask ? SESS_UMASK + sizeof(int) : 0));
     }
     for (void* p : {(void*)S.pool.gim, (void*)S.pool.im, (void*)S.pool.recon, (void*)S.pool.error, (void*)S.pool.z, (void*)S.pool.mode,
-                    (void*)S.pool.src, (void*)S.pool.field, (void*)S.pool.kind})
+                    (void*)S.pool.src, (void*)S.pool.field, (void*)S.pool.kind, (void*)S.pool.umask, (void*)S.pool.local})
       if (p) (void)hipFree(p);
     S.pool = N;
     S.capacity = capacity;
     S.opened.resize(c, 0);
     S.version.resize(c, 0);
     S.has_src.resize(c, 0);
+    S.local_flags.resize(c, 0);
   }
   if (!S.d_tab) HIPCHK(h, hipMalloc((void**)&S.d_tab, (size_t)BATCH_MAX * 11 * sizeof(int32_t)));
   if (!S.d_shown) HIPCHK(h, hipMalloc((void**)&S.d_shown, (size_t)BATCH_MAX * SESS_IMG));
@@ -185,6 +207,118 @@ int sessions_set_blend(ian_handle* h, const double* gauss_half, int radius) {
   if (is_device_ptr(gauss_half)) return fail(h, -7, "ian_sessions_set_blend: gauss_half must be a host array");
   for (int i = 0; i < 8; ++i) h->sess.w[i] = i <= radius ? gauss_half[i] : 0.0;
   h->sess.radius = radius;
+  return 0;
+}
+
+int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int stride, bool need_opened, bool need_blend);
+
+int sessions_reserve_local(ian_handle* h, int on) {
+  const char* fn = "ian_sessions_reserve_local";
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  if ((rc = session_model_check(h, fn))) return rc;
+  auto& S = h->sess;
+  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if (on != 0 && on != 1) return fail(h, -7, "%s: on = %d (0 frees, 1 allocates)", fn, on);
+  HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that are freed
+  h->last_pending = false;
+  SessionPool& P = S.pool;
+  if (!on) {   // everything of the feature goes, the table too: a later reservation starts from nothing
+    for (void* p : {(void*)P.umask, (void*)P.local, (void*)S.d_falloff, (void*)S.d_ltab})
+      if (p) (void)hipFree(p);
+    P.umask = nullptr;
+    P.local = nullptr;
+    S.d_falloff = nullptr;
+    S.d_ltab = nullptr;
+    S.falloff_set = false;
+    std::fill(S.local_flags.begin(), S.local_flags.end(), 0);
+    return 0;
+  }
+  if (P.umask) return 0;
+  const size_t c = (size_t)S.capacity;
+  double* umask = nullptr;
+  int* local = nullptr;
+  double* falloff = nullptr;
+  int* ltab = nullptr;
+  hipError_t e = hipMalloc((void**)&umask, c * SESS_UMASK);
+  if (e == hipSuccess) e = hipMemset(umask, 0, c * SESS_UMASK);
+  if (e == hipSuccess) e = hipMalloc((void**)&local, c * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(local, 0, c * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&falloff, 64 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&ltab, (size_t)BATCH_MAX * 2 * sizeof(int32_t));
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // the zeros are there before any stream reads them
+  if (e != hipSuccess) {   // the old pool stays as it was
+    for (void* p : {(void*)umask, (void*)local, (void*)falloff, (void*)ltab})
+      if (p) (void)hipFree(p);
+    (void)hipGetLastError();
+    return fail(h, -2, "%s: %s for %d sessions of %zu bytes", fn, hipGetErrorString(e), S.capacity, SESS_UMASK + sizeof(int));
+  }
+  P.umask = umask;
+  P.local = local;
+  S.d_falloff = falloff;
+  S.d_ltab = ltab;
+  S.falloff_set = false;
+  S.local_flags.assign(c, 0);
+  return 0;
+}
+
+int sessions_set_local(ian_handle* h, const double* falloff64, double dampen_thresh) {
+  const char* fn = "ian_sessions_set_local";
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  if ((rc = session_model_check(h, fn))) return rc;
+  if (!falloff64) return fail(h, -1, "null pointer passed to %s", fn);
+  auto& S = h->sess;
+  if (!S.pool.umask) return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
+  if (is_device_ptr(falloff64)) return fail(h, -7, "%s: falloff64 must be a host array", fn);
+  if (!(falloff64[0] == 1.0)) return fail(h, -7, "%s: falloff64[0] = %g, not 1.0 (the footprint is 1 inside the brush rectangle)", fn, falloff64[0]);
+  for (int i = 0; i < 64; ++i)
+    if (!(falloff64[i] >= 0.0 && falloff64[i] <= 1.0)) return fail(h, -7, "%s: falloff64[%d] = %g outside [0,1]", fn, i, falloff64[i]);
+  if (!std::isfinite(dampen_thresh)) return fail(h, -7, "%s: dampen_thresh %g is not finite", fn, dampen_thresh);
+  HIPCHK(h, hipDeviceSynchronize());   // a pending blend may still read the old table
+  h->last_pending = false;
+  HIPCHK(h, hipMemcpy(S.d_falloff, falloff64, 64 * sizeof(double), hipMemcpyHostToDevice));
+  S.dampen_thresh = dampen_thresh;
+  S.falloff_set = true;
+  return 0;
+}
+
+// ian_session_brush / ian_session_set_latent(as_sample = 0) on a pool with the local reservation: a session whose LOCAL flags are not
+// 0 needs the table.  Checked with everything else, before anything is enqueued.
+int session_local_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int stride) {
+  auto& S = h->sess;
+  if (!S.pool.umask || S.falloff_set) return 0;
+  for (int i = 0; i < n; ++i) {
+    const int id = ids[(size_t)i * stride];
+    if (S.local_flags[id])
+      return fail(h, -6, "%s: item %d: session %d has local flags %d, but the falloff table is not set (call ian_sessions_set_local first)",
+                  fn, i, id, (int)S.local_flags[id]);
+  }
+  return 0;
+}
+
+int session_local(ian_handle* h, int n, const int32_t* ids, const int32_t* flags, void* stream) {
+  const char* fn = "ian_session_local";
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if (S.capacity > 0 && !S.pool.umask) return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
+  if ((rc = session_check(h, fn, n, ids, 1, true, false))) return rc;
+  if (!flags) return fail(h, -1, "null pointer passed to %s", fn);
+  if (is_device_ptr(flags)) return fail(h, -7, "%s: the flags must be a host array", fn);
+  for (int i = 0; i < n; ++i)
+    if (flags[i] < 0 || flags[i] > 3) return fail(h, -7, "%s: item %d: flags %d outside 0..3 (bit 0 = local, bit 1 = dampen)", fn, i, flags[i]);
+  // writes pool rows only, as ian_session_read reads them: the decoder's activations and the residency of ian_session_brush survive it
+  hipStream_t st = (hipStream_t)stream;
+  if (h->last_pending && h->last_stream != st) HIPCHK(h, hipStreamSynchronize(h->last_stream));
+  S.ltab_shadow.resize((size_t)2 * n);
+  memcpy(S.ltab_shadow.data(), ids, (size_t)n * sizeof(int32_t));
+  memcpy(S.ltab_shadow.data() + n, flags, (size_t)n * sizeof(int32_t));
+  HIPCHK(h, hipMemcpyAsync(S.d_ltab, S.ltab_shadow.data(), (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(h, launch_session_local_set(S.pool, S.d_ltab, S.d_ltab + n, n, st));
+  for (int i = 0; i < n; ++i) S.local_flags[ids[i]] = (char)flags[i];
+  h->last_stream = st;
+  h->last_pending = true;
   return 0;
 }
 
@@ -341,6 +475,7 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
   h->slot_stale[h->desc.out_slot] = 0;
   const bool shown_dev = shown && is_device_ptr(shown);
   HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.pool, S.d_tab, 0, 0, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
+  if (S.pool.umask) HIPCHK(h, launch_session_local_set(S.pool, S.d_tab, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:267, :337); LOCAL stays
   for (int i = 0; i < n; ++i) {
     S.opened[ids[i]] = 1;
     ++S.version[ids[i]];
@@ -355,6 +490,7 @@ int session_set_latent(ian_handle* h, int n, const int32_t* ids, const float* z,
   if (rc) return rc;
   if (!z) return fail(h, -1, "null pointer passed to %s", fn);
   if (as_sample != 0 && as_sample != 1) return fail(h, -7, "%s: as_sample %d (0 = paint_latents, 1 = sample)", fn, as_sample);
+  if (as_sample == 0 && (rc = session_local_check(h, fn, n, ids, 1))) return rc;
   auto& S = h->sess;
   hipStream_t st = (hipStream_t)stream;
   session_enter(h, st);
@@ -377,6 +513,7 @@ int session_set_latent(ian_handle* h, int n, const int32_t* ids, const float* z,
     a.store = 0;
     for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
     a.radius = S.radius;
+    a.falloff = S.d_falloff; a.thresh = S.dampen_thresh;
     HIPCHK(h, launch_session_blend(a, n, st));
   }
   for (int i = 0; i < n; ++i) ++S.version[ids[i]];
@@ -398,6 +535,7 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
     if (e.c1 < 0 || e.r1 < 0 || e.c2 > out.w || e.r2 > out.h)
       return fail(h, -7, "%s: item %d: patch (%d,%d,%d,%d) outside the %dx%d image", fn, i, e.c1, e.r1, e.c2, e.r2, out.w, out.h);
   }
+  if ((rc = session_local_check(h, fn, n, &ev->session, 11))) return rc;
   auto& S = h->sess;
   unsigned char* d_out = nullptr;
   bool out_dev = false;
@@ -444,6 +582,7 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
     a.store = 1;
     for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
     a.radius = S.radius;
+    a.falloff = S.d_falloff; a.thresh = S.dampen_thresh;
     HIPCHK(h, launch_session_blend(a, nc, st));
   }
   h->slot_stale[h->desc.out_slot] = 0;
@@ -500,6 +639,8 @@ int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
     if (what == IAN_SESSION_SOURCE && !S.has_src[id])
       return fail(h, -7, "%s: session %d has no full-resolution source (open it with ian_session_open_hires)", fn, id);
   }
+  if ((what == IAN_SESSION_UMASK || what == IAN_SESSION_LOCAL) && !S.pool.umask)
+    return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
   const void* src = nullptr;
   size_t bytes = 0;
   switch (what) {
@@ -512,6 +653,8 @@ int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
     case IAN_SESSION_FIELD: src = S.pool.field + (size_t)id * SESS_IMG; bytes = SESS_IMG * sizeof(float); break;
     case IAN_SESSION_FIELD_KIND: src = S.pool.kind + id; bytes = sizeof(int32_t); break;
     case IAN_SESSION_SOURCE: bytes = sess_src_bytes(S.pool.scale); src = S.pool.src + (size_t)id * bytes; break;
+    case IAN_SESSION_UMASK: src = S.pool.umask + (size_t)id * (64 * 64); bytes = SESS_UMASK; break;
+    case IAN_SESSION_LOCAL: src = S.pool.local + id; bytes = sizeof(int32_t); break;
     default: return fail(h, -7, "%s: field %d (enum ian_session_field)", fn, what);
   }
   // a plain copy of pool rows: the decoder's activations are not touched, so the residency of ian_session_brush survives it
@@ -570,6 +713,18 @@ int ian_session_brush(ian_handle* h, int32_t n, const ian_session_event* events,
 int ian_session_read(ian_handle* h, int32_t id, int32_t what, void* out, void* stream) {
   if (!h) return -1;
   return session_read(h, id, what, out, stream);
+}
+int ian_sessions_reserve_local(ian_handle* h, int32_t on) {
+  if (!h) return -1;
+  return sessions_reserve_local(h, on);
+}
+int ian_sessions_set_local(ian_handle* h, const double* falloff64, double dampen_thresh) {
+  if (!h) return -1;
+  return sessions_set_local(h, falloff64, dampen_thresh);
+}
+int ian_session_local(ian_handle* h, int32_t n, const int32_t* ids, const int32_t* flags, void* stream) {
+  if (!h) return -1;
+  return session_local(h, n, ids, flags, stream);
 }
 void ian_session_tanh_table(float* out256) {
   if (out256) session_tanh_table(out256);

@@ -300,6 +300,14 @@ struct ian_handle {
     std::vector<int32_t> views_shadow;   // their upload source
     unsigned char* d_out = nullptr;      // staging of rendered windows for a host `out`, grown on demand
     size_t out_cap = 0;
+    // local edits (ian_sessions_reserve_local): pool.umask / local, the host's copy of every session's LOCAL flags (what the device
+    // array holds: only ian_session_local writes either), the falloff table and the dampen threshold of ian_sessions_set_local
+    std::vector<char> local_flags;
+    double* d_falloff = nullptr;         // f64[64]
+    bool falloff_set = false;
+    double dampen_thresh = 0.75;
+    int* d_ltab = nullptr;               // per ian_session_local call: [n ids | n flags]
+    std::vector<int32_t> ltab_shadow;    // its upload source
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

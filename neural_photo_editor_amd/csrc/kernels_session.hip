@@ -6,6 +6,8 @@
 //   session_gather_z_kernel    brush: the sessions' latents -> the decoder's latent slot
 //   *_seed_colour_batch_kernel brush: the loss seeds of kernels_misc.hip with a constant brush colour per item (NPE.py:205 myRGB)
 //   session_blend_kernel       brush / paint_latents: photo blend (photo mode) or uint8 image (sample mode) per session, z_new -> pool
+//   session_blend_local_kernel the same in a pool with the local reservation: per-session user mask, brush footprint, dampen
+//   session_local_set_kernel   local edits: a session's UMASK := 0 (every open) and its LOCAL flags (ian_session_local)
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
@@ -252,9 +254,93 @@ __global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a)
       for (int c = 0; c < 3; ++c) sh[c * 64 * 64 + p] = b.im[c * 64 * 64 + p];
   }
 }
+
+// The same for a pool with the local reservation (ian_sessions_reserve_local); session_blend_kernel above stays the code of every other
+// pool.  The session's LOCAL flags choose, uniformly over the workgroup, what the blend does (npe_ops.photo_blend_local).  Bit 0: a
+// paint event first max-es the footprint of its rectangle into the session's UMASK (set_latent, items == nullptr, adds none), then
+// MASK_L = MASK * UMASK; bit 1: dampen.  Flags 0 take the same LOCAL instantiation with both switched off: MASK and D go through the
+// operations of session_blend_kernel.  Sample mode and lighten events never look at the flags.  Mixed batches are one launch.
+__global__ __launch_bounds__(PB_T) void session_blend_local_kernel(SessionBlendArgs a) {
+  __shared__ double m0[64 * 64];
+  __shared__ double m1[64 * 64];
+  const int i = blockIdx.y;
+  const int id = a.ids[i];
+  const size_t row = (size_t)id * S_IMG;
+  const float* xh = a.xhat + (size_t)i * S_IMG;
+  unsigned char* sh = a.shown + (size_t)i * S_IMG;
+  for (int j = threadIdx.x; j < a.P.zl; j += PB_T) a.P.z[(size_t)id * a.P.zl + j] = a.zslot[(size_t)i * a.zs + j];
+  if (a.P.mode[id] != 0 || (a.items && a.items[i * 7 + 4] == 0)) {   // the plain sample, as in session_blend_kernel
+    for (int e = threadIdx.x * 4; e < S_IMG; e += PB_T * 4) {
+      const float4 v = *reinterpret_cast<const float4*>(xh + e);
+      uchar4 o;
+      o.x = np_uint8f(255.0f * (v.x + 1.0f) / 2.0f);
+      o.y = np_uint8f(255.0f * (v.y + 1.0f) / 2.0f);
+      o.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
+      o.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
+      *reinterpret_cast<uchar4*>(sh + e) = o;
+      if (a.P.field) *reinterpret_cast<float4*>(a.P.field + row + e) = v;
+    }
+    if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 1;
+    return;
+  }
+  const int flags = a.P.local[id];
+  PhotoLocalArgs l;
+  l.umask = (flags & 1) ? a.P.umask + (size_t)id * (64 * 64) : nullptr;
+  l.falloff = a.items ? a.falloff : nullptr;
+  l.c1 = l.r1 = l.c2 = l.r2 = 0;
+  if (a.items) {
+    // a rectangle that is empty or not inside the image (the host refuses the latter) adds no footprint: the table has 64 entries
+    const int c1 = a.items[i * 7], r1 = a.items[i * 7 + 1], c2 = a.items[i * 7 + 2], r2 = a.items[i * 7 + 3];
+    if (c1 >= 0 && r1 >= 0 && c2 <= 64 && r2 <= 64 && c1 < c2 && r1 < r2) {
+      l.c1 = c1;
+      l.r1 = r1;
+      l.c2 = c2;
+      l.r2 = r2;
+    }
+  }
+  l.dampen = flags & 2;
+  l.thresh = a.thresh;
+  PhotoBlendArgs b;
+  b.xhat = xh;
+  b.recon = a.P.recon + row;
+  b.error = a.P.error + row;
+  b.im = a.store ? a.P.im + row : sh;
+  b.mask = nullptr;
+  b.field = a.P.field ? a.P.field + row : nullptr;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) b.w[k] = a.w[k];
+  b.radius = a.radius;
+  photo_blend_image<true>(b, m0, m1, &l);
+  if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 0;
+  if (a.store) {   // every thread re-reads exactly the bytes it wrote (p = tid + k * PB_T per channel)
+    for (int p = threadIdx.x; p < 64 * 64; p += PB_T)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sh[c * 64 * 64 + p] = b.im[c * 64 * 64 + p];
+  }
+}
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s) {
   if (a.radius < 0 || a.radius > 7 || n < 1 || n > 65535 || !a.shown) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_blend_kernel, dim3(1, n), dim3(PB_T), 0, s, a);
+  if (a.P.umask) {
+    if (!a.P.local) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(session_blend_local_kernel, dim3(1, n), dim3(PB_T), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(session_blend_kernel, dim3(1, n), dim3(PB_T), 0, s, a);
+  }
+  return hipGetLastError();
+}
+
+// ---- local edits: UMASK row of session ids[i] := 0 (open / Reset / commit: USER_MASK *= 0, NPE.py:267, :337) and, with flags,
+// LOCAL[ids[i]] := flags[i] (ian_session_local).  One workgroup per session, a lane stores 16 bytes at a time.
+__global__ __launch_bounds__(256) void session_local_set_kernel(SessionPool P, const int* __restrict__ ids, const int* __restrict__ flags) {
+  const int i = blockIdx.x;
+  const int id = ids[i];
+  double2* row = reinterpret_cast<double2*>(P.umask + (size_t)id * (64 * 64));
+  for (int j = threadIdx.x; j < 64 * 64 / 2; j += 256) row[j] = make_double2(0.0, 0.0);
+  if (flags && threadIdx.x == 0) P.local[id] = flags[i];
+}
+hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const int* flags, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || !P.umask || !P.local) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_local_set_kernel, dim3(n), dim3(256), 0, s, P, ids, flags);
   return hipGetLastError();
 }
 

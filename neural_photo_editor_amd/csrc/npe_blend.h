@@ -28,8 +28,13 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {  // d c b a | a b c d
 }
 
 constexpr int PB_T = 1024;
-// one 64x64 image per workgroup of PB_T threads; m0 / m1 are the workgroup's two 64x64 float64 LDS planes
-__device__ __forceinline__ void photo_blend_image(const PhotoBlendArgs& a, double* m0, double* m1) {
+// one 64x64 image per workgroup of PB_T threads; m0 / m1 are the workgroup's two 64x64 float64 LDS planes.
+// LOCAL (session_blend_local_kernel only; npe_ops.photo_blend_local): in the last pass the thread that owns a pixel reads its UMASK
+// value once, max-es it with the brush footprint (two loads from the 64-entry falloff table, one product: npe_ops.local_footprint),
+// writes it back once and multiplies MASK by it; dampen replaces D where to_tanh(float32(RECON)) + D passes the threshold.  Every
+// branch on l is uniform over the workgroup.  The instantiation without LOCAL is the code it always was.
+template <bool LOCAL = false>
+__device__ __forceinline__ void photo_blend_image(const PhotoBlendArgs& a, double* m0, double* m1, const PhotoLocalArgs* l = nullptr) {
   constexpr int H = 64, W = 64, HW = H * W;
   const int tid = threadIdx.x;
   // ---- min(mean_c |DELTA|, 1): float32 until np.min promotes to float64
@@ -67,8 +72,22 @@ __device__ __forceinline__ void photo_blend_image(const PhotoBlendArgs& a, doubl
   __syncthreads();
   // ---- IM = uint8(from_tanh(to_tanh(RECON) + MASK*DELTA + (1-MASK)*ERROR)), float64
   for (int p = tid; p < HW; p += PB_T) {
-    const double mask = m0[p];
+    double mask = m0[p];
     if (a.mask) a.mask[p] = mask;
+    if constexpr (LOCAL) {
+      if (l->umask) {
+        double u = l->umask[p];
+        if (l->falloff && l->c2 > l->c1 && l->r2 > l->r1) {   // umask_paint: np.maximum(U, t[dy] * t[dx]); the table has no NaN
+          const int y = p / W, x = p % W;
+          const int dx = x < l->c1 ? l->c1 - x : (x >= l->c2 ? x - l->c2 + 1 : 0);   // 0..63 for 0 <= c1 < c2 <= 64 (the launcher checks)
+          const int dy = y < l->r1 ? l->r1 - y : (y >= l->r2 ? y - l->r2 + 1 : 0);
+          const double f = l->falloff[dy] * l->falloff[dx];
+          u = u < f ? f : u;
+          l->umask[p] = u;
+        }
+        mask = mask * u;   // MASK_L
+      }
+    }
     const double om = 1.0 - mask;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -76,11 +95,20 @@ __device__ __forceinline__ void photo_blend_image(const PhotoBlendArgs& a, doubl
       const float r = (float)rb;
       const float tt = (2.0f * (r / 255.0f)) - 1.0f;
       const float delta = a.xhat[c * HW + p] - tt;
-      const double D = mask * (double)delta + om * (double)a.error[c * HW + p];
+      double D = mask * (double)delta + om * (double)a.error[c * HW + p];
+      bool damp = false;
+      if constexpr (LOCAL) {
+        if (l->dampen) {   // NPE.py:184-189 as np.where(float64(t32) + D > thresh, thresh - float64(t32), D)
+          damp = true;
+          const double s = (double)tt + D;
+          if (s > l->thresh) D = l->thresh - (double)tt;
+        }
+      }
       const double t64 = 2.0 * ((double)rb / 255.0) - 1.0;   // to_tanh(RECON): uint8 -> float64
       const double v = 255.0 * ((t64 + D) + 1.0) / 2.0;
       a.im[c * HW + p] = np_uint8(v);
-      if (a.field) a.field[c * HW + p] = (float)(mask * ((double)delta - (double)a.error[c * HW + p]));   // npe_ops.edit_field
+      if (a.field)   // npe_ops.edit_field; dampened: float32(D - float64(ERROR))
+        a.field[c * HW + p] = damp ? (float)(D - (double)a.error[c * HW + p]) : (float)(mask * ((double)delta - (double)a.error[c * HW + p]));
     }
   }
 }

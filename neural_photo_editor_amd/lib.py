@@ -46,6 +46,7 @@ EXPORTS = (
     "ian_brush_step", "ian_grad_batch", "ian_brush_step_batch",
     "ian_sessions_reserve", "ian_sessions_set_blend", "ian_session_open", "ian_session_set_latent", "ian_session_brush", "ian_session_read",
     "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
+    "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -115,6 +116,9 @@ def load_library():
     lib.ian_session_open_hires.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_render.argtypes = [vp, i32, C.POINTER(SessionView), i32, i32, fp, vp]
     lib.ian_session_brush_view.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, C.POINTER(SessionView), i32, i32, fp, vp]
+    lib.ian_sessions_reserve_local.argtypes = [vp, i32]
+    lib.ian_sessions_set_local.argtypes = [vp, fp, C.c_double]
+    lib.ian_session_local.argtypes = [vp, i32, fp, fp, vp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -169,7 +173,8 @@ class SessionView(C.Structure):
 # enum ian_session_field (include/ian.h): name -> (code, dtype, shape; None = (num_latents,); "S" = (3, 64*scale, 64*scale))
 SESSION_FIELDS = {"Z": (0, np.float32, None), "RECON": (1, np.uint8, (3, 64, 64)), "ERROR": (2, np.float32, (3, 64, 64)),
                   "IM": (3, np.uint8, (3, 64, 64)), "GIM": (4, np.uint8, (3, 64, 64)), "MODE": (5, np.int32, (1,)),
-                  "FIELD": (6, np.float32, (3, 64, 64)), "FIELD_KIND": (7, np.int32, (1,)), "SOURCE": (8, np.uint8, "S")}
+                  "FIELD": (6, np.float32, (3, 64, 64)), "FIELD_KIND": (7, np.int32, (1,)), "SOURCE": (8, np.uint8, "S"),
+                  "UMASK": (9, np.float64, (64, 64)), "LOCAL": (10, np.int32, (1,))}
 
 
 def session_tanh_table():
@@ -341,6 +346,23 @@ class Handle:
         """ian_session_brush_view; events / views = ctypes arrays of SessionEvent / SessionView of the same length."""
         self._check(self.lib.ian_session_brush_view(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
                                                     views, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def sessions_reserve_local(self, on=True):
+        self._check(self.lib.ian_sessions_reserve_local(self._h, int(bool(on))))
+
+    def sessions_set_local(self, falloff64, dampen_thresh=0.75):
+        """ian_sessions_set_local; falloff64 = 64 float64 values (npe_ops.local_falloff_table)."""
+        t = np.ascontiguousarray(falloff64, np.float64)
+        if t.shape != (64,):
+            raise ValueError("the falloff table has 64 entries, got shape %s" % (t.shape,))
+        self._check(self.lib.ian_sessions_set_local(self._h, _ptr(t), float(dampen_thresh)))
+
+    def session_local(self, ids, flags, stream=None):
+        """ian_session_local; ids, flags = int32 arrays of the same length n."""
+        ids, flags = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(flags, np.int32)
+        if ids.ndim != 1 or flags.shape != ids.shape:
+            raise ValueError("ids and flags must be 1-D arrays of the same length, got %s and %s" % (ids.shape, flags.shape))
+        self._check(self.lib.ian_session_local(self._h, len(ids), _ptr(ids), _ptr(flags), C.c_void_p(stream or 0)))
 
     def session_read(self, sid, what, stream=None, scale=0):
         code, dtype, shape = SESSION_FIELDS[what]

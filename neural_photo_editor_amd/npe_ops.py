@@ -193,3 +193,75 @@ def hires_render(src, field, kind, s, vx, vy, vw, vh):
         q = np.float32(127.5) * (v + np.float32(1.0))
     assert q.dtype == np.float32
     return np.uint8(np.clip(np.rint(q), 0, 255))
+
+
+# ---- local edits (ian_sessions_reserve_local / ian_session_local, include/ian.h) -------------------------------------
+# NPE.py declares USER_MASK "currently not implemented" (NPE.py:58-59, :221), offers gk (NPE.py:167-175) for "changes to MASK ... more
+# localized to the brush location" and dampen (NPE.py:184-189) as a commented-out alternative for D (NPE.py:227, :298).  These four
+# functions ARE the specification of what the sessions make of them: float64, every operation rounded on its own, and the device
+# (kernels_session.hip, npe_blend.h) matches them bit for bit.
+LOCAL_SIGMA = 0.3         # NPE.py:170
+LOCAL_IM = 64             # NPE.py:171
+DAMPEN_THRESH = 0.75      # NPE.py:187
+
+
+def local_falloff_table(sigma=LOCAL_SIGMA, im=LOCAL_IM):
+    """f64[64]: t[d] = exp(-(d**2 / float(im)) / (2 * sigma**2)), the falloff at d pixels from the brush rectangle along one axis;
+    t[0] == 1.0.  The host computes it (as it computes the blend's Gaussian); the device only multiplies two of its entries."""
+    d = np.arange(64)
+    return np.exp(-(d ** 2 / float(im)) / (2 * sigma ** 2))
+
+
+def _axis_distance(lo, hi):
+    """gk's distance of pixel j to the half-open interval [lo, hi): lo - j before it, 0 inside, j - hi + 1 after it."""
+    j = np.arange(64)
+    return np.where(j < lo, lo - j, np.where(j >= hi, j - hi + 1, 0))
+
+
+def local_footprint(c1, r1, c2, r2, t):
+    """f64[64,64]: F = t[dy][:,None] * t[dx][None,:] (one float64 product per pixel) on gk's distance grids: 1.0 inside the brush
+    rectangle, falling off with the distance to it.  gk takes exp of the SUM of the two exponents; the separable form differs from
+    it by rounding only.  The rectangle must not be empty (0 <= c1 < c2 <= 64, 0 <= r1 < r2 <= 64)."""
+    c1, r1, c2, r2 = int(c1), int(r1), int(c2), int(r2)
+    if not (0 <= c1 < c2 <= 64 and 0 <= r1 < r2 <= 64):
+        raise ValueError("a footprint needs a non-empty rectangle inside the 64x64 image, got (%d,%d,%d,%d)" % (c1, r1, c2, r2))
+    t = np.asarray(t, np.float64)
+    return t[_axis_distance(r1, r2)][:, None] * t[_axis_distance(c1, c2)][None, :]
+
+
+def umask_paint(U, box, t):
+    """USER_MASK after a stroke: np.maximum(U, local_footprint(box)).  Exact and idempotent, and the result of several strokes does
+    not depend on their order.  An empty rectangle (c2 <= c1 or r2 <= r1) leaves U as it is."""
+    c1, r1, c2, r2 = [int(v) for v in box]
+    U = np.asarray(U, np.float64)
+    if c2 <= c1 or r2 <= r1:
+        return U.copy()
+    return np.maximum(U, local_footprint(c1, r1, c2, r2, t))
+
+
+def photo_blend_local(xhat, recon_uint8, error, U=None, half=None, dampen=False, thresh=DAMPEN_THRESH):
+    """photo_blend_host with the user mask and / or dampen -> (IM uint8, MASK_L float64, FIELD float32).
+      MASK    exactly photo_blend_host's (half = gaussian_half_kernel(...): the same filter through separable_reflect_filter, which
+              equals scipy's bit for bit; None: scipy's own with BLEND_SIGMA)
+      MASK_L  = MASK * U (U float64 (64,64)), or MASK when U is None
+      D       = MASK_L*DELTA + (1-MASK_L)*ERROR
+      dampen  (NPE.py:184-189): t32 = to_tanh(float32(RECON)); s = float64(t32) + D; D = where(s > thresh, thresh - float64(t32), D)
+      IM      = uint8(from_tanh(to_tanh(RECON) + D))
+      FIELD   = float32(MASK_L * (float64(DELTA) - float64(ERROR))) (edit_field with MASK_L); with dampen float32(D - float64(ERROR))"""
+    RECON = np.asarray(recon_uint8)
+    ERROR = np.asarray(error)
+    t32 = to_tanh(np.float32(RECON))
+    DELTA = np.asarray(xhat, np.float32) - t32
+    m = np.min([np.mean(np.abs(DELTA), axis=0), np.ones((64, 64))], axis=0)
+    MASK = gaussian_filter(m, BLEND_SIGMA) if half is None else separable_reflect_filter(m, np.asarray(half, np.float64))
+    MASK_L = MASK if U is None else MASK * np.asarray(U, np.float64)
+    D = MASK_L * DELTA + (1 - MASK_L) * ERROR
+    if dampen:
+        s = np.float64(t32) + D
+        D = np.where(s > thresh, thresh - np.float64(t32), D)
+        FIELD = np.float32(D - np.float64(ERROR))
+    else:
+        FIELD = np.float32(MASK_L * (np.float64(DELTA) - np.float64(ERROR)))
+    with np.errstate(invalid="ignore"):
+        IM = np.uint8(from_tanh(to_tanh(RECON) + D))
+    return IM, MASK_L, FIELD

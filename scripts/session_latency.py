@@ -1,7 +1,10 @@
 """Device-resident edit sessions against the stateless batched call: events/s of EditSessions.paint (photo mode, a steady set of
 ids: state in HBM, 11 words up per event, 12 KB down) and of IAN.brush_step_batch with host pointers and photo= (per item a 48 KB
 colour image, RECON, ERROR and the latent compared against their shadows, z_new and IM down), in one process, on both configs.
-usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 16 64] [--calls 200] [--repeats 3] [--out FILE]
+usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 16 64] [--calls 200] [--repeats 3] [--out FILE] [--local]
+  --local: the same event stream on a pool with the local reservation and flags 3 (user mask + dampen) on every session: per item
+           the blend also reads, max-es and writes the session's 32 KB UMASK.  Compare against a run without --local in the same
+           process order on the same build.
   --trace: only the first --n on the first config, sessions only: warm-up, an idle second, then --calls timed calls (for a
            rocprofv3 --kernel-trace --stats run).
 Per (config, n, path): the median over --calls calls after warm-up, repeated --repeats times (the two paths alternate within a
@@ -47,11 +50,13 @@ def bytes_per_call(n, zl):
             "stateless": {"h2d": 28 * n + 4 * zl * n, "d2h": 4 * zl * n + IMG * n, "host_compare": n * (4 * IMG + IMG + 4 * IMG)}}
 
 
-def run_arch(arch, ns, calls, repeats):
+def run_arch(arch, ns, calls, repeats, local=False):
     from neural_photo_editor_amd import npe_ops as N
     m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
     zl = m.get_zdim()
     s = m.sessions(max(ns))
+    if local:
+        s.reserve_local()
     rows = []
     for n in ns:
         ids = np.arange(n)
@@ -59,6 +64,8 @@ def run_arch(arch, ns, calls, repeats):
         levels = (255, 0, 0)
         ph = np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8)
         s.open(ids, ph)
+        if local:
+            s.set_local(ids, flags=3)
         st = [s.read(i) for i in ids]
         recon, error = np.stack([t["RECON"] for t in st]), np.stack([t["ERROR"] for t in st])
         z = [np.stack([t["Z"] for t in st])]
@@ -85,18 +92,21 @@ def run_arch(arch, ns, calls, repeats):
     return rows
 
 
-def trace_run(arch, n, calls):
+def trace_run(arch, n, calls, local=False):
     m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
     s = m.sessions(n)
     ids, boxes = np.arange(n), boxes_for(n)
     s.open(ids, np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8))
+    if local:
+        s.reserve_local()
+        s.set_local(ids, flags=3)
     for _ in range(5):
         s.paint(ids, boxes, (255, 0, 0))
     time.sleep(1.0)
     t = time.perf_counter()
     for _ in range(calls):
         s.paint(ids, boxes, (255, 0, 0))
-    return {"arch": arch, "n": n, "calls": calls, "ms_per_call": round((time.perf_counter() - t) * 1e3 / calls, 4)}
+    return {"arch": arch, "n": n, "calls": calls, "local": bool(local), "ms_per_call": round((time.perf_counter() - t) * 1e3 / calls, 4)}
 
 
 def main():
@@ -106,15 +116,16 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--local", action="store_true", help="local reservation, flags 3 (user mask + dampen) on every session")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     archs = [a.only] if a.only else ["IAN_simple", "IAN"]
     if a.trace:
-        print(json.dumps(trace_run(archs[0], a.n[0], a.calls)))
+        print(json.dumps(trace_run(archs[0], a.n[0], a.calls, a.local)))
         return
-    res = {"metric": "session_latency", "calls": a.calls, "repeats": a.repeats}
+    res = {"metric": "session_latency", "calls": a.calls, "repeats": a.repeats, "local": bool(a.local)}
     for arch in archs:
-        res[arch] = run_arch(arch, a.n, a.calls, a.repeats)
+        res[arch] = run_arch(arch, a.n, a.calls, a.repeats, a.local)
     line = json.dumps(res)
     print(line)
     if a.out:

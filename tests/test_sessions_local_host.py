@@ -1,0 +1,261 @@
+"""CPU tests of local edits in edit sessions (ian_sessions_reserve_local, ian_sessions_set_local, ian_session_local): the numpy functions
+that specify the arithmetic (npe_ops.local_falloff_table, local_footprint, umask_paint, photo_blend_local), the packer (every
+validation before any library call) and the header / export list agreement."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from neural_photo_editor_amd import api, npe_ops as N
+from neural_photo_editor_amd import lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_EXPORTS = ("ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local")
+BOXES = [(0, 0, 4, 4), (60, 60, 64, 64), (20, 30, 37, 47), (0, 63, 1, 64), (5, 9, 6, 10)]
+
+
+def direct_falloff(c1, r1, c2, r2, sigma=0.3, im=64):
+    """exp of the SUM of the two exponents on distance grids built pixel by pixel: 0 inside the rectangle, the count of pixels to its
+    nearest edge outside (what gk's concatenated ranges hold, up to the sign it squares away)."""
+    x = np.zeros((im, im))
+    y = np.zeros((im, im))
+    for j in range(im):
+        x[:, j] = c1 - j if j < c1 else (j - c2 + 1 if j >= c2 else 0)
+        y[j, :] = r1 - j if j < r1 else (j - r2 + 1 if j >= r2 else 0)
+    return np.exp(-(x ** 2 / float(im) + y ** 2 / float(im)) / (2 * sigma ** 2))
+
+
+# ---- the arithmetic ---------------------------------------------------------------------------------------------------------
+def test_falloff_table():
+    t = N.local_falloff_table()
+    assert t.dtype == np.float64 and t.shape == (64,) and t[0] == 1.0
+    assert np.all(np.diff(t) < 0) and np.all(t > 0) and np.all(t <= 1)
+    for d in (1, 7, 63):
+        assert t[d] == np.exp(-(d ** 2 / 64.0) / (2 * 0.3 ** 2))
+    assert np.array_equal(N.local_falloff_table(0.3, 64), t)
+    assert not np.array_equal(N.local_falloff_table(0.5), t)
+
+
+@pytest.mark.parametrize("box", BOXES)
+def test_footprint_against_the_direct_formula(box):
+    """rtol 2e-13: the exponent's magnitude reaches 689, so one rounding of the sum moves the result by 689 * 2^-53 = 7.7e-14, plus a
+    few ulp for the two exp calls and the product.  Measured: 5.7e-14 worst over these boxes."""
+    c1, r1, c2, r2 = box
+    F = N.local_footprint(c1, r1, c2, r2, N.local_falloff_table())
+    want = direct_falloff(c1, r1, c2, r2)
+    assert F.dtype == np.float64 and F.shape == (64, 64)
+    print("worst relative difference", box, float(np.max(np.abs(F - want) / want)))
+    assert np.allclose(F, want, rtol=2e-13, atol=0)
+    assert np.all(F[r1:r2, c1:c2] == 1.0)                                # inside the box exactly 1
+    outside = np.ones((64, 64), bool)
+    outside[r1:r2, c1:c2] = False
+    assert np.all(F[outside] < 1.0)
+    assert F.min() >= np.finfo(np.float64).tiny                          # still a normal number in the far corner
+
+
+def test_smallest_footprint_value_is_normal():
+    F = N.local_footprint(0, 0, 1, 1, N.local_falloff_table())
+    assert F[63, 63] == F.min() and 5e-300 < F.min() < 6e-300
+
+
+def test_footprint_refuses_an_empty_or_outside_rectangle():
+    t = N.local_falloff_table()
+    for box in ((4, 4, 4, 8), (4, 4, 8, 4), (8, 4, 4, 8), (-1, 0, 4, 4), (0, 0, 65, 4)):
+        with pytest.raises(ValueError):
+            N.local_footprint(*box, t)
+
+
+def test_umask_paint_is_idempotent_order_free_and_ignores_an_empty_box():
+    t = N.local_falloff_table()
+    U0 = np.zeros((64, 64))
+    a, b, c = (3, 5, 11, 9), (8, 7, 20, 30), (50, 1, 64, 6)
+    Ua = N.umask_paint(U0, a, t)
+    assert np.array_equal(Ua, N.local_footprint(*a, t))
+    assert np.array_equal(N.umask_paint(Ua, a, t), Ua)                   # idempotent
+    orders = [(a, b, c), (c, a, b), (b, c, a), (c, b, a)]
+    results = []
+    for order in orders:
+        U = U0
+        for box in order:
+            U = N.umask_paint(U, box, t)
+        results.append(U)
+    for U in results[1:]:
+        assert np.array_equal(U, results[0])
+    assert not np.array_equal(results[0], Ua)
+    for empty in ((4, 4, 4, 8), (4, 4, 8, 4), (9, 9, 3, 12), (0, 0, 0, 0)):
+        out = N.umask_paint(Ua, empty, t)
+        assert np.array_equal(out, Ua) and out is not Ua
+    assert np.all(U0 == 0)                                               # the input is left alone
+
+
+def blend_inputs(seed=5, bright=True):
+    """RECON with every level up to 255 (bright pixels, level 224 and above, are what dampen acts on), a GIM near it and an x that
+    moves a patch a lot and the rest a little."""
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:64, 0:64]
+    base = 127.5 + 127.5 * np.sin(xx / 9.0 + rs.uniform(0, 6, (3, 1, 1))) * np.cos(yy / 11.0 + rs.uniform(0, 6, (3, 1, 1)))
+    recon = np.uint8(np.clip(base + rs.randint(-6, 7, (3, 64, 64)), 0, 255 if bright else 200))
+    gim = np.uint8(np.clip(recon.astype(int) + rs.randint(-9, 10, recon.shape), 0, 255))
+    error = N.to_tanh(np.float32(gim)) - N.to_tanh(np.float32(recon))
+    x = np.float32(N.to_tanh(np.float32(recon))) + rs.uniform(-0.03, 0.03, recon.shape).astype(np.float32)
+    x[:, 20:40, 10:30] += np.float32(0.4)
+    return x, recon, error
+
+
+def test_dampen_where_form_equals_the_three_term_expression():
+    """NPE.py's dampen is a sum of three terms, each of which lives on one side of the threshold test: minus the input and the
+    threshold where input + correct passes it, the correction where it does not.  Here the three terms are built one by one by
+    masked assignment into zeros and added in that order, every sum rounded in float64.  The where form must give the same VALUES."""
+    x, recon, error = blend_inputs()
+    thresh = 0.75
+    t32 = N.to_tanh(np.float32(recon))
+    _, mask = N.photo_blend_host(x, recon, error)
+    delta = np.asarray(x, np.float32) - t32
+    correct = mask * delta + (1 - mask) * error                          # D before dampen, float64
+    m = (t32 + correct) > thresh
+    minus_input, kept, cap = np.zeros(m.shape), np.zeros(m.shape), np.zeros(m.shape)
+    minus_input[m] = -np.float64(t32[m])
+    kept[~m] = correct[~m]
+    cap[m] = thresh
+    three = (minus_input + kept) + cap
+    count = int(m.sum())
+    assert 0 < count < m.size, count                                    # both branches are in the input
+    im, mask_l, field = N.photo_blend_local(x, recon, error, None, None, True, thresh)
+    assert np.array_equal(mask_l, mask)
+    D = np.where((np.float64(t32) + correct) > thresh, thresh - np.float64(t32), correct)
+    assert np.array_equal(D, three)
+    assert np.array_equal(field, np.float32(D - np.float64(error)))
+    with np.errstate(invalid="ignore"):
+        assert np.array_equal(im, np.uint8(N.from_tanh(N.to_tanh(recon) + three)))
+    im_plain = N.photo_blend_host(x, recon, error)[0]
+    assert (im != im_plain).any() and (im == im_plain).any()
+    # dampened pixels show the threshold's level or less
+    assert np.all(im[m] <= int(N.from_tanh(thresh)) + 1)
+
+
+def test_without_mask_and_dampen_it_is_photo_blend_host_and_edit_field():
+    x, recon, error = blend_inputs(seed=9)
+    im, mask_l, field = N.photo_blend_local(x, recon, error, None, None, False, 0.75)
+    im_h, mask_h = N.photo_blend_host(x, recon, error)
+    assert im.dtype == np.uint8 and np.array_equal(im, im_h)
+    assert mask_l.dtype == np.float64 and np.array_equal(mask_l, mask_h)
+    assert field.dtype == np.float32 and np.array_equal(field, N.edit_field(x, recon, error, mask_h))
+    # the restated filter (what the device runs) gives the same mask as scipy's
+    im2, mask2, field2 = N.photo_blend_local(x, recon, error, None, N.gaussian_half_kernel(), False, 0.75)
+    assert np.array_equal(im2, im) and np.array_equal(mask2, mask_l) and np.array_equal(field2, field)
+
+
+def test_user_mask_confines_the_edit():
+    x, recon, error = blend_inputs(seed=11)
+    t = N.local_falloff_table()
+    gim_level = np.uint8(N.from_tanh(N.to_tanh(recon) + np.float64(error)))   # U = 0: the byte image of RECON + ERROR
+    im0, m0, f0 = N.photo_blend_local(x, recon, error, np.zeros((64, 64)), None, False, 0.75)
+    assert np.array_equal(im0, gim_level) and not m0.any() and not f0.any()
+    U = N.umask_paint(np.zeros((64, 64)), (12, 22, 20, 30), t)
+    im, mask_l, field = N.photo_blend_local(x, recon, error, U, None, False, 0.75)
+    _, mask = N.photo_blend_host(x, recon, error)
+    assert np.array_equal(mask_l, mask * U)
+    assert np.array_equal(field, N.edit_field(x, recon, error, mask * U))
+    assert (im != N.photo_blend_host(x, recon, error)[0]).any()
+    assert np.array_equal(im[:, 50:, 50:], gim_level[:, 50:, 50:])       # far from the stroke nothing moves
+    assert (im[:, 22:30, 12:20] != gim_level[:, 22:30, 12:20]).any()
+
+
+# ---- the packer ---------------------------------------------------------------------------------------------------------------
+class StubHandle:
+    """Records every call that would reach the library."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def record(*a, **k):
+            self.calls.append((name, a))
+        return record
+
+
+def stub_sessions(capacity=8, opened=(0, 1, 2, 3), reserve=True):
+    h = StubHandle()
+    s = api.EditSessions(h, capacity, 100)
+    if reserve:
+        s.reserve_local()
+    s._opened = set(opened)
+    h.calls.clear()
+    return s, h
+
+
+def test_packer_forms_the_flags():
+    ids, f = api.pack_session_local([3, 1, 2])
+    assert ids.dtype == np.int32 and f.dtype == np.int32 and list(ids) == [3, 1, 2] and list(f) == [1, 1, 1]
+    assert list(api.pack_session_local([3, 1], local=False, dampen=True)[1]) == [2, 2]
+    assert list(api.pack_session_local([3, 1], local=[True, False], dampen=[True, True])[1]) == [3, 2]
+    assert list(api.pack_session_local([3, 1, 0], flags=[0, 3, 2])[1]) == [0, 3, 2]
+    assert list(api.pack_session_local(5, flags=3)[1]) == [3]
+
+
+@pytest.mark.parametrize("call", [
+    lambda s: s.set_local([0], flags=4),                                      # flags outside 0..3
+    lambda s: s.set_local([0, 1], flags=[1, 4]),
+    lambda s: s.set_local([0], flags=-1),
+    lambda s: s.set_local([0], local=2),
+    lambda s: s.set_local([0], flags=1.0),                                    # flags are integers
+    lambda s: s.set_local([0, 1], flags=[1]),                                 # one per session
+    lambda s: s.set_local([0, 1, 0]),                                         # an id given twice
+    lambda s: s.set_local([0, 8]),                                            # an id out of range
+    lambda s: s.set_local([-1]),
+    lambda s: s.set_local([]),                                                # n = 0
+    lambda s: s.set_local(list(range(257))),
+    lambda s: s.set_local([4]),                                               # a session not opened
+    lambda s: s.reserve_local(sigma=0.0),
+    lambda s: s.reserve_local(sigma=float("nan")),
+    lambda s: s.reserve_local(dampen_thresh=float("inf")),
+])
+def test_invalid_input_raises_before_any_library_call(call):
+    s, h = stub_sessions()
+    with pytest.raises(ValueError):
+        call(s)
+    assert h.calls == []
+
+
+def test_without_the_reservation_set_local_is_refused():
+    s, h = stub_sessions(reserve=False)
+    with pytest.raises(ValueError, match="no local reservation"):
+        s.set_local([0])
+    assert h.calls == []
+
+
+def test_valid_calls_reach_the_library():
+    s, h = stub_sessions(reserve=False)
+    s.reserve_local(sigma=0.5, dampen_thresh=0.6)
+    assert [c[0] for c in h.calls] == ["sessions_reserve_local", "sessions_set_local"]
+    table, thresh = h.calls[1][1]
+    assert np.array_equal(table, N.local_falloff_table(0.5)) and thresh == 0.6 and s.local
+    h.calls.clear()
+    s.set_local([2, 0], local=True, dampen=[False, True])
+    (name, (ids, flags)), = h.calls
+    assert name == "session_local" and list(ids) == [2, 0] and list(flags) == [1, 3]
+    s.reserve_local(False)
+    assert not s.local and h.calls[-1][0] == "sessions_reserve_local"
+
+
+# ---- the C ABI ----------------------------------------------------------------------------------------------------------------
+def test_header_and_export_list_agree_on_the_new_names():
+    header = open(os.path.join(ROOT, "include", "ian.h")).read()
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    declared = set(re.findall(r"\b(ian_[a-z_0-9]+)\s*\(", code))
+    for name in NEW_EXPORTS:
+        assert name in declared and name in L.EXPORTS, name
+    assert {n for n in declared if n.endswith("_local")} == set(NEW_EXPORTS)
+    assert {n for n in L.EXPORTS if n.endswith("_local")} == set(NEW_EXPORTS)
+    assert re.search(r"IAN_SESSION_UMASK\s*=\s*9\b", code) and re.search(r"IAN_SESSION_LOCAL\s*=\s*10\b", code)
+    assert L.SESSION_FIELDS["UMASK"] == (9, np.float64, (64, 64)) and L.SESSION_FIELDS["LOCAL"][0] == 10
+    lib = L.load_library()
+    protos = {name: argt for _, name, argt in L.parse_header_prototypes(os.path.join(ROOT, "include", "ian.h"))}
+    for name in NEW_EXPORTS:
+        fn = getattr(lib, name)
+        assert fn.restype is ctypes.c_int32
+        assert len(fn.argtypes) == len(protos[name]), name
+    assert protos["ian_sessions_set_local"] == ["ptr", "ptr", "double"]
+    assert lib.ian_sessions_set_local.argtypes[2] is ctypes.c_double
