@@ -27,6 +27,26 @@ from .lib import BrushItem, Handle, SessionEvent, SessionView
 BATCH_MAX = 256     # ian_grad_batch / ian_brush_step_batch: 1 <= n <= 256
 
 
+def per_item(v, what, n, top=None):
+    """One value for all n items, or one per item -> n values: floats, or (top given) integers or booleans in 0..top as int32."""
+    if top is None:
+        a = np.asarray(v, np.float64)
+        if a.ndim == 0:
+            return [float(a)] * n
+        if a.shape != (n,):
+            raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (what, n, a.shape))
+        return [float(t) for t in a]
+    a = np.asarray(v)
+    if a.ndim == 0:
+        a = np.tile(a, n)
+    if a.shape != (n,) or not (np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_):
+        raise ValueError("%s must be one value or %d values of an integer or boolean type, got %s %s" % (what, n, a.dtype, a.shape))
+    for i, t in enumerate(int(t) for t in a):
+        if not 0 <= t <= top:
+            raise ValueError("item %d: %s %d outside 0..%d" % (i, what, t, top))
+    return a.astype(np.int32)
+
+
 def pack_brush_items(boxes, n_rgb=None, modes=None, weight=0.0, sign=1.0):
     """Python arguments of the batched brush calls -> a ctypes array of ian_brush_item (include/ian.h), validated before the
     library sees anything.  boxes (n,4) as (c1, r1, c2, r2) -- floats from Tk are truncated as imgrad's int() does; n_rgb = the
@@ -50,14 +70,7 @@ def pack_brush_items(boxes, n_rgb=None, modes=None, weight=0.0, sign=1.0):
             raise ValueError("modes must be 0 (imgrad) or 1 (imgradRGB)")
         if n_rgb is None and any(m):
             raise ValueError("item %d has mode 1 (imgradRGB) but no RGB was given" % m.index(1))
-    def per_item(v, what):
-        a = np.asarray(v, np.float64)
-        if a.ndim == 0:
-            return [float(a)] * n
-        if a.shape != (n,):
-            raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (what, n, a.shape))
-        return [float(t) for t in a]
-    w, sg = per_item(weight, "weight"), per_item(sign, "sign")
+    w, sg = per_item(weight, "weight", n), per_item(sign, "sign", n)
     items = (BrushItem * n)()
     for i in range(n):
         c1, r1, c2, r2 = [int(v) for v in b[i]]
@@ -78,23 +91,23 @@ def brush_colour(levels):
     return c
 
 
-def check_session_ids(ids, capacity=None, opened=None):
+def check_session_ids(ids, capacity=None, opened=None, repeats=False, what="sessions"):
     """Session ids of one call -> a contiguous int32 array, or ValueError: 1..256 integers, each inside the pool (when capacity is
-    given), opened (when `opened`, a container of opened ids, is given) and named once."""
+    given), opened (when `opened`, a container of opened ids, is given) and, unless `repeats`, named once."""
     a = np.asarray(ids)
     if a.ndim == 0:
         a = a.reshape(1)
     if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
         raise ValueError("ids must be a 1-D array of integers, got shape %s dtype %s" % (a.shape, a.dtype))
     if not 1 <= a.shape[0] <= BATCH_MAX:
-        raise ValueError("a call holds 1..%d sessions, got %d" % (BATCH_MAX, a.shape[0]))
+        raise ValueError("a call holds 1..%d %s, got %d" % (BATCH_MAX, what, a.shape[0]))
     seen = {}
     for i, v in enumerate(int(t) for t in a):
         if v < 0 or (capacity is not None and v >= capacity):
             raise ValueError("item %d: session %d outside the pool%s" % (i, v, "" if capacity is None else " (capacity %d)" % capacity))
         if opened is not None and v not in opened:
             raise ValueError("item %d: session %d has not been opened" % (i, v))
-        if v in seen:
+        if v in seen and not repeats:
             raise ValueError("item %d: session %d already appears as item %d of this call" % (i, v, seen[v]))
         seen[v] = i
     return np.ascontiguousarray(a, np.int32)
@@ -132,14 +145,7 @@ def pack_session_events(ids, boxes, colours=None, modes=None, weight=0.05, sign=
                 raise ValueError("item %d has mode %d (0 = imgrad, 1 = imgradRGB)" % (i, v))
         if col is None and any(m):
             raise ValueError("item %d has mode 1 (imgradRGB) but no colour was given" % m.index(1))
-    def per_item(v, what):
-        a = np.asarray(v, np.float64)
-        if a.ndim == 0:
-            return [float(a)] * n
-        if a.shape != (n,):
-            raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (what, n, a.shape))
-        return [float(t) for t in a]
-    w, sg = per_item(weight, "weight"), per_item(sign, "sign")
+    w, sg = per_item(weight, "weight", n), per_item(sign, "sign", n)
     ev = (SessionEvent * n)()
     for i in range(n):
         c1, r1, c2, r2 = [int(v) for v in b[i]]
@@ -168,14 +174,8 @@ def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, so
     if not 1 <= scale <= 16:
         raise ValueError("scale must be in 1..16, got %d" % scale)
     S = 64 * scale
-    a = np.asarray(ids)
-    if a.ndim == 0:
-        a = a.reshape(1)
-    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
-        raise ValueError("ids must be a 1-D array of integers, got shape %s dtype %s" % (a.shape, a.dtype))
+    a = check_session_ids(ids, capacity, opened, repeats=True, what="views")
     n = a.shape[0]
-    if not 1 <= n <= BATCH_MAX:
-        raise ValueError("a call holds 1..%d views, got %d" % (BATCH_MAX, n))
     sz = np.asarray(size)
     if sz.ndim == 0:
         sz = np.tile(sz, 2)
@@ -196,12 +196,8 @@ def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, so
     views = (SessionView * n)()
     for i in range(n):
         sid, x, y = int(a[i]), int(o[i, 0]), int(o[i, 1])
-        if sid < 0 or (capacity is not None and sid >= capacity):
-            raise ValueError("item %d: session %d outside the pool%s" % (i, sid, "" if capacity is None else " (capacity %d)" % capacity))
         if events is not None and events[i].session != sid:
             raise ValueError("item %d: the view names session %d, the event session %d" % (i, sid, events[i].session))
-        if opened is not None and sid not in opened:
-            raise ValueError("item %d: session %d has not been opened" % (i, sid))
         if sourced is not None and sid not in sourced:
             raise ValueError("item %d: session %d has no full-resolution source (open_hires)" % (i, sid))
         if x % 4:
@@ -220,20 +216,10 @@ def pack_session_local(ids, local=True, dampen=False, flags=None, capacity=None,
     vet the ids."""
     idv = check_session_ids(ids, capacity, opened)
     n = len(idv)
-    def per_item(v, what, top):
-        a = np.asarray(v)
-        if a.ndim == 0:
-            a = np.tile(a, n)
-        if a.shape != (n,) or not (np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_):
-            raise ValueError("%s must be one value or %d values of an integer or boolean type, got %s %s" % (what, n, a.dtype, a.shape))
-        for i, t in enumerate(int(t) for t in a):
-            if not 0 <= t <= top:
-                raise ValueError("item %d: %s %d outside 0..%d" % (i, what, t, top))
-        return a.astype(np.int32)
     if flags is not None:
-        f = per_item(flags, "flags", 3)
+        f = per_item(flags, "flags", n, 3)
     else:
-        f = per_item(local, "local", 1) + 2 * per_item(dampen, "dampen", 1)
+        f = per_item(local, "local", n, 1) + 2 * per_item(dampen, "dampen", n, 1)
     return idv, np.ascontiguousarray(f, np.int32)
 
 
@@ -319,18 +305,22 @@ class EditSessions:
             raise ValueError("z holds %d latents for %d sessions" % (z.shape[0], n))
         return z
 
-    def open(self, ids, photos):
-        """infer: photos uint8 (n,3,64,64) (or (3,64,64) for one id) -> IM."""
-        ids = self._ids(ids, False)
+    @staticmethod
+    def _photos(photos, n, S):
         p = np.asarray(photos)
         if p.dtype != np.uint8:
             raise ValueError("photos must be uint8, got %s" % p.dtype)
-        if p.shape == (3, 64, 64):
+        if p.shape == (3, S, S):
             p = p[None]
-        if p.shape != (len(ids), 3, 64, 64):
-            raise ValueError("photos must have shape (%d,3,64,64), got %s" % (len(ids), p.shape))
+        if p.shape != (n, 3, S, S):
+            raise ValueError("photos must have shape (%d,3,%d,%d), got %s" % (n, S, S, p.shape))
+        return np.ascontiguousarray(p)
+
+    def open(self, ids, photos):
+        """infer: photos uint8 (n,3,64,64) (or (3,64,64) for one id) -> IM."""
+        ids = self._ids(ids, False)
         shown = np.empty((len(ids), 3, 64, 64), np.uint8)
-        self._h.session_open(ids, np.ascontiguousarray(p), 0, shown)
+        self._h.session_open(ids, self._photos(photos, len(ids), 64), 0, shown)
         self._opened.update(int(v) for v in ids)
         self._sourced.difference_update(int(v) for v in ids)
         return shown
@@ -340,16 +330,8 @@ class EditSessions:
         if not self.scale:
             raise ValueError("the pool has no full-resolution reservation (reserve_hires)")
         ids = self._ids(ids, False)
-        S = 64 * self.scale
-        p = np.asarray(photos)
-        if p.dtype != np.uint8:
-            raise ValueError("photos must be uint8, got %s" % p.dtype)
-        if p.shape == (3, S, S):
-            p = p[None]
-        if p.shape != (len(ids), 3, S, S):
-            raise ValueError("photos must have shape (%d,3,%d,%d), got %s" % (len(ids), S, S, p.shape))
         shown = np.empty((len(ids), 3, 64, 64), np.uint8)
-        self._h.session_open_hires(ids, np.ascontiguousarray(p), shown)
+        self._h.session_open_hires(ids, self._photos(photos, len(ids), 64 * self.scale), shown)
         self._opened.update(int(v) for v in ids)
         self._sourced.update(int(v) for v in ids)
         return shown

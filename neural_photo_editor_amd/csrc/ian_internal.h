@@ -354,7 +354,9 @@ hipError_t launch_latent_update(float* z, const float* g, const float* cg, int n
 hipError_t launch_keep_warm(const int* flag, long long max_ticks, hipStream_t s);   // experiment: see kernels_npe.hip
 hipError_t launch_to_uint8(const float* x, unsigned char* y, long long n, hipStream_t s);
 
-// device-resident edit sessions (kernels_session.hip; ian_session_*): the pool's arrays, one row per session id
+// device-resident edit sessions (kernels_session.hip; ian_session_*): the pool's arrays, one row per session id.  Passed to kernels by
+// value.  The runtime allocates, moves, frees and reads every pointer member through its row in SESS_COLUMNS (ian_rt_session.inc): a
+// new array is a member here and a row there.
 struct SessionPool {
   unsigned char* gim;     // GIM   u8 [capacity][3*64*64]
   unsigned char* im;      // IM    u8 [capacity][3*64*64]

@@ -6,17 +6,163 @@
 // event) and the only device -> host traffic the canvas images.  The host keeps, per session, whether it was opened and a
 // counter of its latent's versions (the residency key of ian_session_brush is n ids + n counters, not the latents' bytes).
 //
-// Full-resolution sessions (ian_sessions_reserve_hires, DESIGN.md 4.3) add three arrays: SRC (the photo at S x S, S = 64 * scale), FIELD
-// and FIELD_KIND (what the last call displayed, as something ian_session_render can apply to SRC), and a per-session host flag
-// "SRC holds a photo".  Without that reservation pool.src / field / kind are null and no kernel touches them.
-//
-// Local edits (ian_sessions_reserve_local, DESIGN.md 4.4) add UMASK (where the user has brushed) and the LOCAL flags per session, and
-// per handle the falloff table of the brush footprint.  Without that reservation pool.umask / local are null, launch_session_blend
-// runs session_blend_kernel, and no other kernel is launched.
+// The pool's arrays are described once, in SESS_COLUMNS: member, bytes per session, owning reservation, whether fresh rows start at
+// zero, and the ian_session_field that reads it.  Allocation, the copy of the surviving rows, rollback, freeing, the byte count of
+// the -2 messages and ian_session_read are loops over that table; SESS_SCRATCH does the same for the per-handle device buffers.
+// Three reservations own them (sess_free_group frees exactly one):
+//   base   ian_sessions_reserve        GIM IM RECON ERROR Z MODE; reserve(0) frees all three groups
+//   hires  ian_sessions_reserve_hires  SRC (the photo at S x S, S = 64 * scale), FIELD and FIELD_KIND (what the last call displayed,
+//          as something ian_session_render can apply to SRC; DESIGN.md 4.3), and a per-session host flag "SRC holds a photo"
+//   local  ian_sessions_reserve_local  UMASK (where the user has brushed) and the LOCAL flags, and per handle the falloff table of
+//          the brush footprint (DESIGN.md 4.4)
+// Without a reservation its pointers are null, no kernel touches them, and launch_session_blend runs session_blend_kernel.
 namespace {
 
 constexpr size_t SESS_IMG = 3 * 64 * 64;
 constexpr int SESS_MAX_CAPACITY = 1 << 20;
+size_t sess_src_bytes(int scale) { return 3 * (size_t)(64 * scale) * (size_t)(64 * scale); }
+
+enum SessGroup { SESS_BASE, SESS_HIRES, SESS_LOCAL };
+struct SessColumn {
+  size_t at;                                  // offsetof(SessionPool, member): the struct goes to kernels by value and stays as it is
+  size_t (*row_bytes)(const SessionPool&);    // bytes per session
+  SessGroup group;
+  bool zero;                                  // rows that were not copied from an old pool start at zero
+  int field;                                  // the ian_session_field that reads it
+};
+#define SESS_COL(member, bytes, group, zero, field) {offsetof(SessionPool, member), [](const SessionPool& P) -> size_t { (void)P; return bytes; }, group, zero, field}
+const SessColumn SESS_COLUMNS[] = {
+    SESS_COL(gim, SESS_IMG, SESS_BASE, false, IAN_SESSION_GIM),
+    SESS_COL(im, SESS_IMG, SESS_BASE, false, IAN_SESSION_IM),
+    SESS_COL(recon, SESS_IMG, SESS_BASE, false, IAN_SESSION_RECON),
+    SESS_COL(error, SESS_IMG * sizeof(float), SESS_BASE, false, IAN_SESSION_ERROR),
+    SESS_COL(z, (size_t)P.zl * sizeof(float), SESS_BASE, false, IAN_SESSION_Z),
+    SESS_COL(mode, sizeof(int), SESS_BASE, false, IAN_SESSION_MODE),
+    SESS_COL(src, sess_src_bytes(P.scale), SESS_HIRES, false, IAN_SESSION_SOURCE),
+    SESS_COL(field, SESS_IMG * sizeof(float), SESS_HIRES, true, IAN_SESSION_FIELD),   // zero: a session opened before the reservation
+    SESS_COL(kind, sizeof(int), SESS_HIRES, true, IAN_SESSION_FIELD_KIND),            // reads as "nothing edited"
+    SESS_COL(umask, 64 * 64 * sizeof(double), SESS_LOCAL, true, IAN_SESSION_UMASK),
+    SESS_COL(local, sizeof(int), SESS_LOCAL, true, IAN_SESSION_LOCAL),
+};
+#undef SESS_COL
+using SessionScratch = ian_handle::SessionScratch;
+struct SessScratchBuf {
+  size_t at;      // offsetof(SessionScratch, member)
+  size_t bytes;   // allocated with its group; 0: by the call that first needs it
+  SessGroup group;
+};
+const SessScratchBuf SESS_SCRATCH[] = {
+    {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 11 * sizeof(int32_t), SESS_BASE},
+    {offsetof(SessionScratch, d_photo), 0, SESS_BASE},
+    {offsetof(SessionScratch, d_shown), (size_t)BATCH_MAX * SESS_IMG, SESS_BASE},
+    {offsetof(SessionScratch, d_tanh), 256 * sizeof(float), SESS_BASE},   // last of its group: a failed build never leaves it without its upload
+    {offsetof(SessionScratch, d_views), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HIRES},
+    {offsetof(SessionScratch, d_out), 0, SESS_HIRES},
+    {offsetof(SessionScratch, d_falloff), 64 * sizeof(double), SESS_LOCAL},
+    {offsetof(SessionScratch, d_ltab), (size_t)BATCH_MAX * 2 * sizeof(int32_t), SESS_LOCAL},
+};
+
+// the pointer member at byte `at` of a SessionPool / SessionScratch (members of several pointer types: copied, not aliased)
+void* slot_get(const void* base, size_t at) {
+  void* p;
+  memcpy(&p, (const char*)base + at, sizeof p);
+  return p;
+}
+void slot_set(void* base, size_t at, void* p) { memcpy((char*)base + at, &p, sizeof p); }
+
+bool sess_has(const SessionPool& P, SessGroup g) {
+  for (const SessColumn& c : SESS_COLUMNS)
+    if (c.group == g) return slot_get(&P, c.at) != nullptr;
+  return false;
+}
+size_t sess_row_bytes(const SessionPool& P, unsigned groups) {
+  size_t sum = 0;
+  for (const SessColumn& c : SESS_COLUMNS)
+    if (groups >> c.group & 1) sum += c.row_bytes(P);
+  return sum;
+}
+// every column of `groups` that N lacks: rows for `capacity` sessions, the first `keep` copied from O, the others zero where the
+// column asks for it; the zeros are there before any stream reads them
+hipError_t sess_build(SessionPool& N, const SessionPool& O, unsigned groups, size_t capacity, size_t keep) {
+  bool zeroed = false;
+  for (const SessColumn& c : SESS_COLUMNS) {
+    if (!(groups >> c.group & 1) || slot_get(&N, c.at)) continue;
+    const size_t row = c.row_bytes(N);
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, capacity * row);
+    if (e != hipSuccess) return e;
+    slot_set(&N, c.at, p);
+    if (keep) e = hipMemcpy(p, slot_get(&O, c.at), keep * row, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && c.zero && capacity > keep) {
+      e = hipMemset((char*)p + keep * row, 0, (capacity - keep) * row);
+      zeroed = true;
+    }
+    if (e != hipSuccess) return e;
+  }
+  return zeroed ? hipDeviceSynchronize() : hipSuccess;
+}
+// frees the columns of `groups` that A holds and B does not
+void sess_drop(SessionPool& A, const SessionPool& B, unsigned groups = ~0u) {
+  for (const SessColumn& c : SESS_COLUMNS) {
+    void* p = slot_get(&A, c.at);
+    if (!(groups >> c.group & 1) || !p || p == slot_get(&B, c.at)) continue;
+    (void)hipFree(p);
+    slot_set(&A, c.at, nullptr);
+  }
+}
+// a failed build: the half-built pool N goes, the handle's pool stays as it was
+int sess_build_failed(ian_handle* h, const char* fn, hipError_t e, SessionPool& N, unsigned groups, int capacity) {
+  sess_drop(N, h->sess.pool);
+  (void)hipGetLastError();
+  return fail(h, -2, "%s: %s for %d sessions of %zu bytes", fn, hipGetErrorString(e), capacity, sess_row_bytes(N, groups));
+}
+hipError_t scratch_build(SessionScratch& S, SessGroup g) {
+  for (const SessScratchBuf& b : SESS_SCRATCH) {
+    if (b.group != g || !b.bytes || slot_get(&S, b.at)) continue;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, b.bytes);
+    if (e != hipSuccess) return e;
+    slot_set(&S, b.at, p);
+  }
+  return hipSuccess;
+}
+void scratch_free(SessionScratch& S, SessGroup g) {
+  for (const SessScratchBuf& b : SESS_SCRATCH) {
+    if (b.group != g) continue;
+    if (void* p = slot_get(&S, b.at)) (void)hipFree(p);
+    slot_set(&S, b.at, nullptr);
+  }
+}
+// everything one reservation owns: its columns, its scratch, and what the host keeps about them
+void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
+  sess_drop(S.pool, SessionPool{}, 1u << g);
+  scratch_free(S, g);
+  if (g == SESS_HIRES) {
+    S.pool.scale = 0;
+    S.out_cap = 0;
+    std::fill(S.has_src.begin(), S.has_src.end(), 0);
+  } else if (g == SESS_LOCAL) {   // the table too: a later reservation starts from nothing
+    S.falloff_set = false;
+    std::fill(S.local_flags.begin(), S.local_flags.end(), 0);
+  } else {
+    S.pool.zl = 0;
+    S.capacity = 0;
+    S.opened.clear(); S.version.clear(); S.has_src.clear(); S.local_flags.clear();
+    S.res_valid = false;
+  }
+}
+// ian_sessions_reserve(0) and ian_destroy: w, radius (ian_sessions_set_blend) and dampen_thresh stay
+void sessions_free(ian_handle* h) {
+  for (SessGroup g : {SESS_LOCAL, SESS_HIRES, SESS_BASE}) sess_free_group(h->sess, g);
+}
+// the refusal of a call that needs the pool (SESS_BASE) or one of the other reservations
+int session_need(ian_handle* h, const char* fn, SessGroup g) {
+  const auto& S = h->sess;
+  if (g == SESS_BASE) return S.capacity > 0 ? 0 : fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if (sess_has(S.pool, g)) return 0;
+  if (g == SESS_HIRES) return fail(h, -6, "%s: no full-resolution reservation (call ian_sessions_reserve_hires first)", fn);
+  return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
+}
 
 // np.asarray([to_tanh(IM)], dtype=np.float32) per uint8 level: float64 2.0*(v/255.0)-1.0, then one rounding to float32
 void session_tanh_table(float* out) {
@@ -27,36 +173,10 @@ void session_tanh_table(float* out) {
   }
 }
 
-void sessions_free(ian_handle* h) {
-  auto& S = h->sess;
-  SessionPool& P = S.pool;
-  for (void* p : {(void*)P.gim, (void*)P.im, (void*)P.recon, (void*)P.error, (void*)P.z, (void*)P.mode, (void*)S.d_tab, (void*)S.d_tanh,
-                  (void*)S.d_photo, (void*)S.d_shown, (void*)P.src, (void*)P.field, (void*)P.kind, (void*)S.d_views, (void*)S.d_out,
-                  (void*)P.umask, (void*)P.local, (void*)S.d_falloff, (void*)S.d_ltab})
-    if (p) (void)hipFree(p);
-  P = SessionPool{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  S.d_falloff = nullptr;
-  S.d_ltab = nullptr;
-  S.falloff_set = false;
-  S.local_flags.clear();
-  S.d_tab = nullptr;
-  S.d_tanh = nullptr;
-  S.d_photo = S.d_shown = nullptr;
-  S.d_views = nullptr;
-  S.d_out = nullptr;
-  S.out_cap = 0;
-  S.capacity = 0;
-  S.opened.clear();
-  S.version.clear();
-  S.has_src.clear();
-  S.res_valid = false;
-}
-
-size_t sess_src_bytes(int scale) { return 3 * (size_t)(64 * scale) * (size_t)(64 * scale); }
-constexpr size_t SESS_UMASK = 64 * 64 * sizeof(double);
-
-// session calls need the 3x64x64 image on both ends (the pool rows, the blend and the open kernels are written for it)
-int session_model_check(ian_handle* h, const char* fn) {
+// a finalized handle, and the 3x64x64 image on both ends (the pool rows, the blend and the open kernels are written for it)
+int session_ready(ian_handle* h, const char* fn) {
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
   const Slot& os = h->slots[h->desc.out_slot];
   const Slot& xs = h->slots[h->desc.x_slot];
   if (os.h != 64 || os.w != 64 || os.c != 3 || !os.nchw || xs.h != 64 || xs.w != 64 || xs.c != 3 || !xs.nchw)
@@ -65,10 +185,10 @@ int session_model_check(ian_handle* h, const char* fn) {
 }
 
 int sessions_reserve(ian_handle* h, int capacity) {
-  int rc = check_ready(h, 1);
+  const char* fn = "ian_sessions_reserve";
+  int rc = session_ready(h, fn);
   if (rc) return rc;
-  if ((rc = session_model_check(h, "ian_sessions_reserve"))) return rc;
-  if (capacity < 0 || capacity > SESS_MAX_CAPACITY) return fail(h, -7, "ian_sessions_reserve: capacity %d outside 0..%d", capacity, SESS_MAX_CAPACITY);
+  if (capacity < 0 || capacity > SESS_MAX_CAPACITY) return fail(h, -7, "%s: capacity %d outside 0..%d", fn, capacity, SESS_MAX_CAPACITY);
   auto& S = h->sess;
   HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that move
   h->last_pending = false;
@@ -77,50 +197,17 @@ int sessions_reserve(ian_handle* h, int capacity) {
     sessions_free(h);
     return 0;
   }
-  const int zl = h->desc.num_latents;
-  if (capacity != S.capacity) {
-    SessionPool N{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, zl};
-    N.scale = S.pool.scale;
-    const size_t c = (size_t)capacity, keep = (size_t)std::min(capacity, S.capacity);
-    auto grow = [&](void** dst, const void* src, size_t row_bytes) -> hipError_t {
-      hipError_t e = hipMalloc(dst, c * row_bytes);
-      if (e == hipSuccess && keep) e = hipMemcpy(*dst, src, keep * row_bytes, hipMemcpyDeviceToDevice);
-      return e;
-    };
-    hipError_t e = grow((void**)&N.gim, S.pool.gim, SESS_IMG);
-    if (e == hipSuccess) e = grow((void**)&N.im, S.pool.im, SESS_IMG);
-    if (e == hipSuccess) e = grow((void**)&N.recon, S.pool.recon, SESS_IMG);
-    if (e == hipSuccess) e = grow((void**)&N.error, S.pool.error, SESS_IMG * sizeof(float));
-    if (e == hipSuccess) e = grow((void**)&N.z, S.pool.z, (size_t)zl * sizeof(float));
-    if (e == hipSuccess) e = grow((void**)&N.mode, S.pool.mode, sizeof(int));
-    if (N.scale) {   // a full-resolution pool: its three arrays follow the capacity
-      if (e == hipSuccess) e = grow((void**)&N.src, S.pool.src, sess_src_bytes(N.scale));
-      if (e == hipSuccess) e = grow((void**)&N.field, S.pool.field, SESS_IMG * sizeof(float));
-      if (e == hipSuccess) e = grow((void**)&N.kind, S.pool.kind, sizeof(int));
-    }
-    if (S.pool.umask) {   // a pool with the local reservation: UMASK and LOCAL follow the capacity, new rows are zero
-      auto grow0 = [&](void** dst, const void* src, size_t row_bytes) -> hipError_t {
-        hipError_t g = grow(dst, src, row_bytes);
-        if (g == hipSuccess && c > keep) g = hipMemset((char*)*dst + keep * row_bytes, 0, (c - keep) * row_bytes);
-        return g;
-      };
-      if (e == hipSuccess) e = grow0((void**)&N.umask, S.pool.umask, SESS_UMASK);
-      if (e == hipSuccess) e = grow0((void**)&N.local, S.pool.local, sizeof(int));
-      if (e == hipSuccess) e = hipDeviceSynchronize();   // the zeros are there before any stream reads them
-    }
-    if (e != hipSuccess) {   // the old pool stays as it was
-      for (void* p : {(void*)N.gim, (void*)N.im, (void*)N.recon, (void*)N.error, (void*)N.z, (void*)N.mode, (void*)N.src, (void*)N.field,
-                      (void*)N.kind, (void*)N.umask, (void*)N.local})
-        if (p) (void)hipFree(p);
-      (void)hipGetLastError();
-      return fail(h, -2, "ian_sessions_reserve: %s for %d sessions of %zu bytes", hipGetErrorString(e), capacity,
-                  3 * SESS_IMG + SESS_IMG * sizeof(float) + (size_t)zl * sizeof(float) + sizeof(int) +
-                      (N.scale ? sess_src_bytes(N.scale) + SESS_IMG * sizeof(float) + sizeof(int) : 0) +
-                      (S.pool.umask ? SESS_UMASK + sizeof(int) : 0));
-    }
-    for (void* p : {(void*)S.pool.gim, (void*)S.pool.im, (void*)S.pool.recon, (void*)S.pool.error, (void*)S.pool.z, (void*)S.pool.mode,
-                    (void*)S.pool.src, (void*)S.pool.field, (void*)S.pool.kind, (void*)S.pool.umask, (void*)S.pool.local})
-      if (p) (void)hipFree(p);
+  if (capacity != S.capacity) {   // a new pool with the groups the old one has: every column follows the capacity
+    SessionPool N = S.pool;
+    N.zl = h->desc.num_latents;
+    unsigned groups = 1u << SESS_BASE;
+    for (SessGroup g : {SESS_HIRES, SESS_LOCAL})
+      if (sess_has(S.pool, g)) groups |= 1u << g;
+    for (const SessColumn& c : SESS_COLUMNS) slot_set(&N, c.at, nullptr);
+    const size_t c = (size_t)capacity;
+    hipError_t e = sess_build(N, S.pool, groups, c, (size_t)std::min(capacity, S.capacity));
+    if (e != hipSuccess) return sess_build_failed(h, fn, e, N, groups, capacity);
+    sess_drop(S.pool, N);
     S.pool = N;
     S.capacity = capacity;
     S.opened.resize(c, 0);
@@ -128,74 +215,50 @@ int sessions_reserve(ian_handle* h, int capacity) {
     S.has_src.resize(c, 0);
     S.local_flags.resize(c, 0);
   }
-  if (!S.d_tab) HIPCHK(h, hipMalloc((void**)&S.d_tab, (size_t)BATCH_MAX * 11 * sizeof(int32_t)));
-  if (!S.d_shown) HIPCHK(h, hipMalloc((void**)&S.d_shown, (size_t)BATCH_MAX * SESS_IMG));
-  if (!S.d_tanh) {
+  const bool had_table = S.d_tanh != nullptr;   // the table is uploaded once, when its buffer is new
+  HIPCHK(h, scratch_build(S, SESS_BASE));
+  if (!had_table) {
     float tab[256];
     session_tanh_table(tab);
-    HIPCHK(h, hipMalloc((void**)&S.d_tanh, sizeof tab));
     HIPCHK(h, hipMemcpy(S.d_tanh, tab, sizeof tab, hipMemcpyHostToDevice));
   }
   return 0;
 }
 
+// ian_sessions_reserve_hires / _local: what N lacks of group g, and the group's scratch, at the pool's capacity, then N becomes the pool
+int sess_add_group(ian_handle* h, const char* fn, SessionPool& N, SessGroup g) {
+  auto& S = h->sess;
+  const bool had = sess_has(S.pool, g);
+  hipError_t e = sess_build(N, S.pool, 1u << g, (size_t)S.capacity, 0);
+  if (e == hipSuccess) e = scratch_build(S, g);
+  if (e != hipSuccess) {
+    if (!had) scratch_free(S, g);
+    return sess_build_failed(h, fn, e, N, 1u << g, S.capacity);
+  }
+  sess_drop(S.pool, N);
+  S.pool = N;
+  return 0;
+}
+
 int sessions_reserve_hires(ian_handle* h, int scale) {
   const char* fn = "ian_sessions_reserve_hires";
-  int rc = check_ready(h, 1);
+  int rc = session_ready(h, fn);
   if (rc) return rc;
-  if ((rc = session_model_check(h, fn))) return rc;
   auto& S = h->sess;
-  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (scale < 0 || scale > 16) return fail(h, -7, "%s: scale %d outside 0..16", fn, scale);
   HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that are freed
   h->last_pending = false;
   if (scale == S.pool.scale) return 0;
-  SessionPool& P = S.pool;
   if (scale == 0) {
-    for (void* p : {(void*)P.src, (void*)P.field, (void*)P.kind, (void*)S.d_views, (void*)S.d_out})
-      if (p) (void)hipFree(p);
-    P.src = nullptr;
-    P.field = nullptr;
-    P.kind = nullptr;
-    P.scale = 0;
-    S.d_views = nullptr;
-    S.d_out = nullptr;
-    S.out_cap = 0;
-    std::fill(S.has_src.begin(), S.has_src.end(), 0);
+    sess_free_group(S, SESS_HIRES);
     return 0;
   }
-  // a new scale: a new SRC array (no photo survives, its size differs); FIELD and FIELD_KIND are allocated once, zeroed so that a
-  // session opened before this call reads as "nothing edited"
-  const size_t c = (size_t)S.capacity;
-  unsigned char* src = nullptr;
-  float* field = P.field;
-  int* kind = P.kind;
-  int* views = S.d_views;
-  hipError_t e = hipMalloc((void**)&src, c * sess_src_bytes(scale));
-  if (e == hipSuccess && !field) {
-    e = hipMalloc((void**)&field, c * SESS_IMG * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(field, 0, c * SESS_IMG * sizeof(float));
-  }
-  if (e == hipSuccess && !kind) {
-    e = hipMalloc((void**)&kind, c * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(kind, 0, c * sizeof(int));
-  }
-  if (e == hipSuccess && !views) e = hipMalloc((void**)&views, (size_t)BATCH_MAX * 3 * sizeof(int32_t));
-  if (e != hipSuccess) {   // the old pool stays as it was
-    if (src) (void)hipFree(src);
-    if (field && field != P.field) (void)hipFree(field);
-    if (kind && kind != P.kind) (void)hipFree(kind);
-    if (views && views != S.d_views) (void)hipFree(views);
-    (void)hipGetLastError();
-    return fail(h, -2, "%s: %s for %d sessions of %zu bytes", fn, hipGetErrorString(e), S.capacity,
-                sess_src_bytes(scale) + SESS_IMG * sizeof(float) + sizeof(int));
-  }
-  if (P.src) (void)hipFree(P.src);
-  P.src = src;
-  P.field = field;
-  P.kind = kind;
-  P.scale = scale;
-  S.d_views = views;
+  // a new scale: a new SRC array (no photo survives, its size differs); FIELD and FIELD_KIND are built once
+  SessionPool N = S.pool;
+  N.scale = scale;
+  N.src = nullptr;
+  if ((rc = sess_add_group(h, fn, N, SESS_HIRES))) return rc;
   std::fill(S.has_src.begin(), S.has_src.end(), 0);
   return 0;
 }
@@ -210,66 +273,34 @@ int sessions_set_blend(ian_handle* h, const double* gauss_half, int radius) {
   return 0;
 }
 
-int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int stride, bool need_opened, bool need_blend);
-
 int sessions_reserve_local(ian_handle* h, int on) {
   const char* fn = "ian_sessions_reserve_local";
-  int rc = check_ready(h, 1);
+  int rc = session_ready(h, fn);
   if (rc) return rc;
-  if ((rc = session_model_check(h, fn))) return rc;
   auto& S = h->sess;
-  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (on != 0 && on != 1) return fail(h, -7, "%s: on = %d (0 frees, 1 allocates)", fn, on);
   HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that are freed
   h->last_pending = false;
-  SessionPool& P = S.pool;
-  if (!on) {   // everything of the feature goes, the table too: a later reservation starts from nothing
-    for (void* p : {(void*)P.umask, (void*)P.local, (void*)S.d_falloff, (void*)S.d_ltab})
-      if (p) (void)hipFree(p);
-    P.umask = nullptr;
-    P.local = nullptr;
-    S.d_falloff = nullptr;
-    S.d_ltab = nullptr;
-    S.falloff_set = false;
-    std::fill(S.local_flags.begin(), S.local_flags.end(), 0);
+  if (!on) {
+    sess_free_group(S, SESS_LOCAL);
     return 0;
   }
-  if (P.umask) return 0;
-  const size_t c = (size_t)S.capacity;
-  double* umask = nullptr;
-  int* local = nullptr;
-  double* falloff = nullptr;
-  int* ltab = nullptr;
-  hipError_t e = hipMalloc((void**)&umask, c * SESS_UMASK);
-  if (e == hipSuccess) e = hipMemset(umask, 0, c * SESS_UMASK);
-  if (e == hipSuccess) e = hipMalloc((void**)&local, c * sizeof(int));
-  if (e == hipSuccess) e = hipMemset(local, 0, c * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&falloff, 64 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&ltab, (size_t)BATCH_MAX * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = hipDeviceSynchronize();   // the zeros are there before any stream reads them
-  if (e != hipSuccess) {   // the old pool stays as it was
-    for (void* p : {(void*)umask, (void*)local, (void*)falloff, (void*)ltab})
-      if (p) (void)hipFree(p);
-    (void)hipGetLastError();
-    return fail(h, -2, "%s: %s for %d sessions of %zu bytes", fn, hipGetErrorString(e), S.capacity, SESS_UMASK + sizeof(int));
-  }
-  P.umask = umask;
-  P.local = local;
-  S.d_falloff = falloff;
-  S.d_ltab = ltab;
+  if (sess_has(S.pool, SESS_LOCAL)) return 0;
+  SessionPool N = S.pool;
+  if ((rc = sess_add_group(h, fn, N, SESS_LOCAL))) return rc;
   S.falloff_set = false;
-  S.local_flags.assign(c, 0);
+  S.local_flags.assign((size_t)S.capacity, 0);
   return 0;
 }
 
 int sessions_set_local(ian_handle* h, const double* falloff64, double dampen_thresh) {
   const char* fn = "ian_sessions_set_local";
-  int rc = check_ready(h, 1);
+  int rc = session_ready(h, fn);
   if (rc) return rc;
-  if ((rc = session_model_check(h, fn))) return rc;
   if (!falloff64) return fail(h, -1, "null pointer passed to %s", fn);
   auto& S = h->sess;
-  if (!S.pool.umask) return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
+  if ((rc = session_need(h, fn, SESS_LOCAL))) return rc;
   if (is_device_ptr(falloff64)) return fail(h, -7, "%s: falloff64 must be a host array", fn);
   if (!(falloff64[0] == 1.0)) return fail(h, -7, "%s: falloff64[0] = %g, not 1.0 (the footprint is 1 inside the brush rectangle)", fn, falloff64[0]);
   for (int i = 0; i < 64; ++i)
@@ -297,39 +328,31 @@ int session_local_check(ian_handle* h, const char* fn, int n, const int32_t* ids
   return 0;
 }
 
-int session_local(ian_handle* h, int n, const int32_t* ids, const int32_t* flags, void* stream) {
-  const char* fn = "ian_session_local";
-  int rc = check_ready(h, 1);
-  if (rc) return rc;
-  auto& S = h->sess;
-  if (S.capacity > 0 && !S.pool.umask) return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
-  if ((rc = session_check(h, fn, n, ids, 1, true, false))) return rc;
-  if (!flags) return fail(h, -1, "null pointer passed to %s", fn);
-  if (is_device_ptr(flags)) return fail(h, -7, "%s: the flags must be a host array", fn);
-  for (int i = 0; i < n; ++i)
-    if (flags[i] < 0 || flags[i] > 3) return fail(h, -7, "%s: item %d: flags %d outside 0..3 (bit 0 = local, bit 1 = dampen)", fn, i, flags[i]);
-  // writes pool rows only, as ian_session_read reads them: the decoder's activations and the residency of ian_session_brush survive it
-  hipStream_t st = (hipStream_t)stream;
+// A call that only reads or writes pool rows (ian_session_local, _render, _read): the decoder's activations and the residency of
+// ian_session_brush survive it.  Enter: the stream hand-over; leave: a device result leaves the stream pending, a host result is
+// synchronised.
+int session_rows_enter(ian_handle* h, hipStream_t st) {
   if (h->last_pending && h->last_stream != st) HIPCHK(h, hipStreamSynchronize(h->last_stream));
-  S.ltab_shadow.resize((size_t)2 * n);
-  memcpy(S.ltab_shadow.data(), ids, (size_t)n * sizeof(int32_t));
-  memcpy(S.ltab_shadow.data() + n, flags, (size_t)n * sizeof(int32_t));
-  HIPCHK(h, hipMemcpyAsync(S.d_ltab, S.ltab_shadow.data(), (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(h, launch_session_local_set(S.pool, S.d_ltab, S.d_ltab + n, n, st));
-  for (int i = 0; i < n; ++i) S.local_flags[ids[i]] = (char)flags[i];
-  h->last_stream = st;
-  h->last_pending = true;
+  return 0;
+}
+int session_rows_leave(ian_handle* h, hipStream_t st, bool device_result) {
+  if (device_result) {
+    h->last_stream = st;
+    h->last_pending = true;
+  } else {
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (h->last_stream == st) h->last_pending = false;
+  }
   return 0;
 }
 
 // what every session call checks first: the model, the pool, n; then per item its id (ids[i * stride]).  Nothing is enqueued or
 // written before all of it passed.
 int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int stride, bool need_opened, bool need_blend) {
-  int rc = check_ready(h, 1);
+  int rc = session_ready(h, fn);
   if (rc) return rc;
-  if ((rc = session_model_check(h, fn))) return rc;
   auto& S = h->sess;
-  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: n = %d outside 1..%d", fn, n, BATCH_MAX);
   if (!ids) return fail(h, -1, "null pointer passed to %s", fn);
   if (is_device_ptr(ids)) return fail(h, -7, "%s: the session ids / events must be a host array", fn);
@@ -343,6 +366,28 @@ int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int 
     if (!ins.second) return fail(h, -7, "%s: item %d: session %d already appears as item %d of this call", fn, i, id, ins.first->second);
   }
   return 0;
+}
+
+int session_local(ian_handle* h, int n, const int32_t* ids, const int32_t* flags, void* stream) {
+  const char* fn = "ian_session_local";
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if (S.capacity > 0 && (rc = session_need(h, fn, SESS_LOCAL))) return rc;
+  if ((rc = session_check(h, fn, n, ids, 1, true, false))) return rc;
+  if (!flags) return fail(h, -1, "null pointer passed to %s", fn);
+  if (is_device_ptr(flags)) return fail(h, -7, "%s: the flags must be a host array", fn);
+  for (int i = 0; i < n; ++i)
+    if (flags[i] < 0 || flags[i] > 3) return fail(h, -7, "%s: item %d: flags %d outside 0..3 (bit 0 = local, bit 1 = dampen)", fn, i, flags[i]);
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  S.ltab_shadow.resize((size_t)2 * n);
+  memcpy(S.ltab_shadow.data(), ids, (size_t)n * sizeof(int32_t));
+  memcpy(S.ltab_shadow.data() + n, flags, (size_t)n * sizeof(int32_t));
+  HIPCHK(h, hipMemcpyAsync(S.d_ltab, S.ltab_shadow.data(), (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(h, launch_session_local_set(S.pool, S.d_ltab, S.d_ltab + n, n, st));
+  for (int i = 0; i < n; ++i) S.local_flags[ids[i]] = (char)flags[i];
+  return session_rows_leave(h, st, true);
 }
 
 // start of the enqueueing part of a session call: stream hand-over, the other paths' caches (as batch_common)
@@ -381,8 +426,7 @@ int session_view_check(ian_handle* h, const char* fn, int n, const ian_session_v
   int rc = check_ready(h, 1);
   if (rc) return rc;
   auto& S = h->sess;
-  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
-  if (S.pool.scale <= 0) return fail(h, -6, "%s: no full-resolution reservation (call ian_sessions_reserve_hires first)", fn);
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
   if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: n = %d outside 1..%d", fn, n, BATCH_MAX);
   if (!views || !out) return fail(h, -1, "null pointer passed to %s", fn);
   if (is_device_ptr(views)) return fail(h, -7, "%s: the views must be a host array", fn);
@@ -419,12 +463,8 @@ int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, 
 int session_render_target(ian_handle* h, uint8_t* out, size_t bytes, unsigned char** d_out, bool* out_dev) {
   auto& S = h->sess;
   *out_dev = is_device_ptr(out);
-  if (*out_dev) {
-    *d_out = out;
-    return 0;
-  }
-  int rc = grow_dev(h, &S.d_out, &S.out_cap, bytes);
-  *d_out = S.d_out;
+  int rc = *out_dev ? 0 : grow_dev(h, &S.d_out, &S.out_cap, bytes);
+  *d_out = *out_dev ? out : S.d_out;
   return rc;
 }
 
@@ -434,7 +474,7 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
   if (rc) return rc;
   if (!photos && source != 0 && source != 1) return fail(h, -7, "%s: source %d (0 = from GIM, 1 = GIM := IM first)", fn, source);
   auto& S = h->sess;
-  if (hires && S.pool.scale <= 0) return fail(h, -6, "%s: no full-resolution reservation (call ian_sessions_reserve_hires first)", fn);
+  if (hires && (rc = session_need(h, fn, SESS_HIRES))) return rc;
   if (hires && !photos) return fail(h, -1, "null pointer passed to %s", fn);
   hipStream_t st = (hipStream_t)stream;
   session_enter(h, st);
@@ -484,6 +524,21 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
   return session_finish(h, n, shown, shown_dev, host_in, st);
 }
 
+// the blend of `ids` (device) after the decoder ran at their latents: items == nullptr is paint_latents, store != 0 a brush event
+SessionBlendArgs session_blend_args(ian_handle* h, const int* ids, const int* items, unsigned char* shown, int store) {
+  const auto& S = h->sess;
+  const Slot& zs = h->slots[h->desc.z_slot];
+  SessionBlendArgs a;
+  memset(&a, 0, sizeof a);
+  a.xhat = h->slots[h->desc.out_slot].d; a.zslot = zs.d; a.zs = zs.cs; a.P = S.pool; a.ids = ids; a.items = items;
+  a.shown = shown;
+  a.store = store;
+  for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
+  a.radius = S.radius;
+  a.falloff = S.d_falloff; a.thresh = S.dampen_thresh;
+  return a;
+}
+
 int session_set_latent(ian_handle* h, int n, const int32_t* ids, const float* z, int as_sample, uint8_t* shown, void* stream) {
   const char* fn = "ian_session_set_latent";
   int rc = session_check(h, fn, n, ids, 1, true, as_sample == 0);
@@ -506,15 +561,7 @@ int session_set_latent(ian_handle* h, int n, const int32_t* ids, const float* z,
   if (as_sample) {
     HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.pool, S.d_tab, 1, 1, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
   } else {
-    SessionBlendArgs a;
-    memset(&a, 0, sizeof a);
-    a.xhat = out.d; a.zslot = zs.d; a.zs = zs.cs; a.P = S.pool; a.ids = S.d_tab;
-    a.shown = shown_dev ? shown : S.d_shown;
-    a.store = 0;
-    for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
-    a.radius = S.radius;
-    a.falloff = S.d_falloff; a.thresh = S.dampen_thresh;
-    HIPCHK(h, launch_session_blend(a, n, st));
+    HIPCHK(h, launch_session_blend(session_blend_args(h, S.d_tab, nullptr, shown_dev ? shown : S.d_shown, 0), n, st));
   }
   for (int i = 0; i < n; ++i) ++S.version[ids[i]];
   return session_finish(h, n, shown, shown_dev, host_in, st);
@@ -575,15 +622,7 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
       if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
     }
     if ((rc = brush_pass_middle(h, nc, d_items + (size_t)7 * off, nullptr, d_col + (size_t)3 * off, true, st))) return rc;
-    SessionBlendArgs a;
-    memset(&a, 0, sizeof a);
-    a.xhat = out.d; a.zslot = zs.d; a.zs = zs.cs; a.P = S.pool; a.ids = d_ids + off; a.items = d_items + (size_t)7 * off;
-    a.shown = d_shown + (size_t)off * SESS_IMG;
-    a.store = 1;
-    for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
-    a.radius = S.radius;
-    a.falloff = S.d_falloff; a.thresh = S.dampen_thresh;
-    HIPCHK(h, launch_session_blend(a, nc, st));
+    HIPCHK(h, launch_session_blend(session_blend_args(h, d_ids + off, d_items + (size_t)7 * off, d_shown + (size_t)off * SESS_IMG, 1), nc, st));
   }
   h->slot_stale[h->desc.out_slot] = 0;
   for (int i = 0; i < n; ++i) ++S.version[ev[i].session];
@@ -610,19 +649,11 @@ int session_render(ian_handle* h, int n, const ian_session_view* views, int vw, 
   bool out_dev = false;
   const size_t bytes = (size_t)n * 3 * (size_t)vh * (size_t)vw;
   if ((rc = session_render_target(h, out, bytes, &d_out, &out_dev))) return rc;
-  // reads pool rows only, as ian_session_read: the decoder's activations and the residency of ian_session_brush survive it
   hipStream_t st = (hipStream_t)stream;
-  if (h->last_pending && h->last_stream != st) HIPCHK(h, hipStreamSynchronize(h->last_stream));
+  if ((rc = session_rows_enter(h, st))) return rc;
   if ((rc = session_render_enqueue(h, n, views, vw, vh, d_out, st))) return rc;
-  if (out_dev) {
-    h->last_stream = st;
-    h->last_pending = true;
-  } else {
-    HIPCHK(h, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (h->last_stream == st) h->last_pending = false;
-  }
-  return 0;
+  if (!out_dev) HIPCHK(h, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+  return session_rows_leave(h, st, out_dev);
 }
 
 int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
@@ -630,46 +661,24 @@ int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
   int rc = check_ready(h, 1);
   if (rc) return rc;
   auto& S = h->sess;
-  if (S.capacity <= 0) return fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (!out) return fail(h, -1, "null pointer passed to %s", fn);
   if (id < 0 || id >= S.capacity) return fail(h, -7, "%s: session %d outside the pool (capacity %d)", fn, id, S.capacity);
   if (!S.opened[id]) return fail(h, -7, "%s: session %d has not been opened", fn, id);
-  if (what >= IAN_SESSION_FIELD && what <= IAN_SESSION_SOURCE) {
-    if (S.pool.scale <= 0) return fail(h, -6, "%s: no full-resolution reservation (call ian_sessions_reserve_hires first)", fn);
-    if (what == IAN_SESSION_SOURCE && !S.has_src[id])
-      return fail(h, -7, "%s: session %d has no full-resolution source (open it with ian_session_open_hires)", fn, id);
-  }
-  if ((what == IAN_SESSION_UMASK || what == IAN_SESSION_LOCAL) && !S.pool.umask)
-    return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
-  const void* src = nullptr;
-  size_t bytes = 0;
-  switch (what) {
-    case IAN_SESSION_Z: src = S.pool.z + (size_t)id * S.pool.zl; bytes = (size_t)S.pool.zl * sizeof(float); break;
-    case IAN_SESSION_RECON: src = S.pool.recon + (size_t)id * SESS_IMG; bytes = SESS_IMG; break;
-    case IAN_SESSION_ERROR: src = S.pool.error + (size_t)id * SESS_IMG; bytes = SESS_IMG * sizeof(float); break;
-    case IAN_SESSION_IM: src = S.pool.im + (size_t)id * SESS_IMG; bytes = SESS_IMG; break;
-    case IAN_SESSION_GIM: src = S.pool.gim + (size_t)id * SESS_IMG; bytes = SESS_IMG; break;
-    case IAN_SESSION_MODE: src = S.pool.mode + id; bytes = sizeof(int32_t); break;
-    case IAN_SESSION_FIELD: src = S.pool.field + (size_t)id * SESS_IMG; bytes = SESS_IMG * sizeof(float); break;
-    case IAN_SESSION_FIELD_KIND: src = S.pool.kind + id; bytes = sizeof(int32_t); break;
-    case IAN_SESSION_SOURCE: bytes = sess_src_bytes(S.pool.scale); src = S.pool.src + (size_t)id * bytes; break;
-    case IAN_SESSION_UMASK: src = S.pool.umask + (size_t)id * (64 * 64); bytes = SESS_UMASK; break;
-    case IAN_SESSION_LOCAL: src = S.pool.local + id; bytes = sizeof(int32_t); break;
-    default: return fail(h, -7, "%s: field %d (enum ian_session_field)", fn, what);
-  }
-  // a plain copy of pool rows: the decoder's activations are not touched, so the residency of ian_session_brush survives it
+  const SessColumn* col = nullptr;
+  for (const SessColumn& c : SESS_COLUMNS)
+    if (c.field == what) col = &c;
+  if (col && col->group != SESS_BASE && (rc = session_need(h, fn, col->group))) return rc;
+  if (what == IAN_SESSION_SOURCE && !S.has_src[id])
+    return fail(h, -7, "%s: session %d has no full-resolution source (open it with ian_session_open_hires)", fn, id);
+  if (!col) return fail(h, -7, "%s: field %d (enum ian_session_field)", fn, what);
+  const size_t bytes = col->row_bytes(S.pool);
+  const char* src = (const char*)slot_get(&S.pool, col->at) + (size_t)id * bytes;
   hipStream_t st = (hipStream_t)stream;
-  if (h->last_pending && h->last_stream != st) HIPCHK(h, hipStreamSynchronize(h->last_stream));
+  if ((rc = session_rows_enter(h, st))) return rc;
   const bool dev = is_device_ptr(out);
   HIPCHK(h, hipMemcpyAsync(out, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  if (dev) {
-    h->last_stream = st;
-    h->last_pending = true;
-  } else {
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (h->last_stream == st) h->last_pending = false;
-  }
-  return 0;
+  return session_rows_leave(h, st, dev);
 }
 
 }  // namespace
@@ -677,54 +686,42 @@ int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
 extern "C" {
 
 int ian_sessions_reserve(ian_handle* h, int32_t capacity) {
-  if (!h) return -1;
-  return sessions_reserve(h, capacity);
+  return h ? sessions_reserve(h, capacity) : -1;
 }
 int ian_sessions_set_blend(ian_handle* h, const double* gauss_half, int32_t radius) { return sessions_set_blend(h, gauss_half, radius); }
 int ian_session_open(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t* photos, int32_t source, uint8_t* shown, void* stream) {
-  if (!h) return -1;
-  return session_open(h, n, ids, photos, source, shown, stream, false);
+  return h ? session_open(h, n, ids, photos, source, shown, stream, false) : -1;
 }
 int ian_sessions_reserve_hires(ian_handle* h, int32_t scale) {
-  if (!h) return -1;
-  return sessions_reserve_hires(h, scale);
+  return h ? sessions_reserve_hires(h, scale) : -1;
 }
 int ian_session_open_hires(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t* photos, uint8_t* shown, void* stream) {
-  if (!h) return -1;
-  return session_open(h, n, ids, photos, 0, shown, stream, true);
+  return h ? session_open(h, n, ids, photos, 0, shown, stream, true) : -1;
 }
 int ian_session_render(ian_handle* h, int32_t n, const ian_session_view* views, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
-  if (!h) return -1;
-  return session_render(h, n, views, vw, vh, out, stream);
+  return h ? session_render(h, n, views, vw, vh, out, stream) : -1;
 }
 int ian_session_brush_view(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, const ian_session_view* views,
                            int32_t vw, int32_t vh, uint8_t* out, void* stream) {
-  if (!h) return -1;
-  return session_brush(h, n, events, shown, stream, true, views, vw, vh, out);
+  return h ? session_brush(h, n, events, shown, stream, true, views, vw, vh, out) : -1;
 }
 int ian_session_set_latent(ian_handle* h, int32_t n, const int32_t* ids, const float* z, int32_t as_sample, uint8_t* shown, void* stream) {
-  if (!h) return -1;
-  return session_set_latent(h, n, ids, z, as_sample, shown, stream);
+  return h ? session_set_latent(h, n, ids, z, as_sample, shown, stream) : -1;
 }
 int ian_session_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, void* stream) {
-  if (!h) return -1;
-  return session_brush(h, n, events, shown, stream);
+  return h ? session_brush(h, n, events, shown, stream) : -1;
 }
 int ian_session_read(ian_handle* h, int32_t id, int32_t what, void* out, void* stream) {
-  if (!h) return -1;
-  return session_read(h, id, what, out, stream);
+  return h ? session_read(h, id, what, out, stream) : -1;
 }
 int ian_sessions_reserve_local(ian_handle* h, int32_t on) {
-  if (!h) return -1;
-  return sessions_reserve_local(h, on);
+  return h ? sessions_reserve_local(h, on) : -1;
 }
 int ian_sessions_set_local(ian_handle* h, const double* falloff64, double dampen_thresh) {
-  if (!h) return -1;
-  return sessions_set_local(h, falloff64, dampen_thresh);
+  return h ? sessions_set_local(h, falloff64, dampen_thresh) : -1;
 }
 int ian_session_local(ian_handle* h, int32_t n, const int32_t* ids, const int32_t* flags, void* stream) {
-  if (!h) return -1;
-  return session_local(h, n, ids, flags, stream);
+  return h ? session_local(h, n, ids, flags, stream) : -1;
 }
 void ian_session_tanh_table(float* out256) {
   if (out256) session_tanh_table(out256);

@@ -278,36 +278,40 @@ struct ian_handle {
   } batch;
   // device-resident edit sessions (ian_session_*, ian_rt_session.inc): the pool (one row per session id in each array), what the
   // host keeps per session (opened, latent version), the small per-call uploads, and the residency key of ian_session_brush: the
-  // decoder activations belong to sessions res_ids, in that order, at latent versions res_ver; enter_stream clears res_valid
-  struct SessionState {
+  // decoder activations belong to sessions res_ids, in that order, at latent versions res_ver; enter_stream clears res_valid.
+  // The device buffers beside the pool, as plain data: SESS_SCRATCH (ian_rt_session.inc) names each once, with the reservation that
+  // owns it and its size; nothing else allocates or frees them.
+  struct SessionScratch {
+    int* d_tab = nullptr;              // per call: brush = [7n ian_brush_item words | n ids | 3n colours], open / set_latent = n ids
+    float* d_tanh = nullptr;           // to_tanh of the 256 uint8 levels, float32
+    unsigned char* d_photo = nullptr;  // staging of host photos [256][3*64*64], allocated by the first open that needs it
+    unsigned char* d_shown = nullptr;  // staging of the canvas images [256][3*64*64]
+    int* d_views = nullptr;            // full-resolution: per call n ian_session_view records
+    unsigned char* d_out = nullptr;    // full-resolution: staging of rendered windows for a host `out`, grown on demand (out_cap)
+    double* d_falloff = nullptr;       // local edits: f64[64], the table of ian_sessions_set_local
+    int* d_ltab = nullptr;             // local edits: per ian_session_local call [n ids | n flags]
+  };
+  struct SessionState : SessionScratch {
     int capacity = 0;
     SessionPool pool = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     std::vector<char> opened;
     std::vector<uint64_t> version;
-    int* d_tab = nullptr;              // per call: brush = [7n ian_brush_item words | n ids | 3n colours], open / set_latent = n ids
-    std::vector<int32_t> tab_shadow;   // its upload source (outlives the caller's array)
-    float* d_tanh = nullptr;           // to_tanh of the 256 uint8 levels, float32
-    unsigned char* d_photo = nullptr;  // staging of host photos [256][3*64*64]
-    unsigned char* d_shown = nullptr;  // staging of the canvas images [256][3*64*64]
+    std::vector<int32_t> tab_shadow;   // upload source of d_tab (outlives the caller's array)
     double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int radius = -1;                   // -1: ian_sessions_set_blend has not been called
     std::vector<int32_t> res_ids;
     std::vector<uint64_t> res_ver;
     bool res_valid = false;
-    // full-resolution sessions (ian_sessions_reserve_hires): pool.src / field / kind / scale, and per session whether SRC holds a photo
+    // full-resolution sessions (ian_sessions_reserve_hires): per session whether SRC holds a photo
     std::vector<char> has_src;
-    int* d_views = nullptr;              // per call: n ian_session_view records
-    std::vector<int32_t> views_shadow;   // their upload source
-    unsigned char* d_out = nullptr;      // staging of rendered windows for a host `out`, grown on demand
+    std::vector<int32_t> views_shadow;   // upload source of d_views
     size_t out_cap = 0;
-    // local edits (ian_sessions_reserve_local): pool.umask / local, the host's copy of every session's LOCAL flags (what the device
-    // array holds: only ian_session_local writes either), the falloff table and the dampen threshold of ian_sessions_set_local
+    // local edits (ian_sessions_reserve_local): the host's copy of every session's LOCAL flags (what the device array holds: only
+    // ian_session_local writes either), whether the falloff table is set, and the dampen threshold of ian_sessions_set_local
     std::vector<char> local_flags;
-    double* d_falloff = nullptr;         // f64[64]
     bool falloff_set = false;
     double dampen_thresh = 0.75;
-    int* d_ltab = nullptr;               // per ian_session_local call: [n ids | n flags]
-    std::vector<int32_t> ltab_shadow;    // its upload source
+    std::vector<int32_t> ltab_shadow;    // upload source of d_ltab
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

@@ -150,9 +150,18 @@ hipError_t launch_session_open_in(const unsigned char* photos, const SessionPool
 }
 
 __device__ __forceinline__ float to_tanh_f32(float v) { return (2.0f * (v / 255.0f)) - 1.0f; }   // to_tanh(np.float32(.)): three roundings
+// uint8(from_tanh(x)) of four values (NPE.py:110, :261): to_uint8_kernel's expression (kernels_npe.hip), contraction off
+__device__ __forceinline__ uchar4 from_tanh_u8(const float4 v) {
+  uchar4 r;
+  r.x = np_uint8f(255.0f * (v.x + 1.0f) / 2.0f);
+  r.y = np_uint8f(255.0f * (v.y + 1.0f) / 2.0f);
+  r.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
+  r.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
+  return r;
+}
 
 // ---- open / sample, output side (NPE.py:261-270, 323-326, 335-338) ---------------------------------------------------------
-//   RECON = uint8(from_tanh(x))            to_uint8_kernel's expression (kernels_npe.hip)
+//   RECON = uint8(from_tanh(x))            from_tanh_u8
 //   ERROR = to_tanh(float32(IM)) - to_tanh(float32(RECON))       float32, numpy's order, no contraction
 // both scattered to the session's rows; the latent row of the z slot goes to the session's Z, the mode flag is set, and the canvas
 // image (IM after an open, RECON after a sample) is written to shown[i] when asked for.
@@ -164,11 +173,7 @@ __global__ __launch_bounds__(256) void session_store_kernel(const float* __restr
   const size_t row = (size_t)id * S_IMG;
   const int e = (blockIdx.x * 256 + threadIdx.x) * 4;
   const float4 v = *reinterpret_cast<const float4*>(xhat + (size_t)i * S_IMG + e);
-  uchar4 r;
-  r.x = np_uint8f(255.0f * (v.x + 1.0f) / 2.0f);
-  r.y = np_uint8f(255.0f * (v.y + 1.0f) / 2.0f);
-  r.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
-  r.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
+  const uchar4 r = from_tanh_u8(v);
   const uchar4 a = *reinterpret_cast<const uchar4*>(P.im + row + e);
   float4 err;
   err.x = to_tanh_f32((float)a.x) - to_tanh_f32((float)r.x);
@@ -213,9 +218,13 @@ hipError_t launch_session_gather_z(const SessionPool& P, const int* ids, float* 
 // shown[i], store == 0 (paint_latents: IM is local to that callback) writes shown[i] only.
 // A session in sample mode, and a lighten event in either mode (NPE.scroll ends in update_photo(None), NPE.py:313-314):
 // shown[i] = uint8(from_tanh(x)) (NPE.py:110), IM untouched.  The item's latent row goes back to the pool.
-__global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a) {
-  __shared__ double m0[64 * 64];
-  __shared__ double m1[64 * 64];
+// LOCAL: a pool with the local reservation (ian_sessions_reserve_local).  The session's LOCAL flags choose, uniformly over the
+// workgroup, what the blend does (npe_ops.photo_blend_local).  Bit 0: a paint event first max-es the footprint of its rectangle into
+// the session's UMASK (set_latent, items == nullptr, adds none), then MASK_L = MASK * UMASK; bit 1: dampen.  Flags 0 take the same
+// LOCAL instantiation with both switched off: MASK and D go through the operations of the plain one.  Sample mode and lighten events
+// never look at the flags.  Mixed batches are one launch.
+template <bool LOCAL>
+__device__ __forceinline__ void session_blend_body(const SessionBlendArgs& a, double* m0, double* m1) {
   const int i = blockIdx.y;
   const int id = a.ids[i];
   const size_t row = (size_t)id * S_IMG;
@@ -225,16 +234,30 @@ __global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a)
   if (a.P.mode[id] != 0 || (a.items && a.items[i * 7 + 4] == 0)) {   // the plain sample (uniform over the workgroup)
     for (int e = threadIdx.x * 4; e < S_IMG; e += PB_T * 4) {
       const float4 v = *reinterpret_cast<const float4*>(xh + e);
-      uchar4 o;
-      o.x = np_uint8f(255.0f * (v.x + 1.0f) / 2.0f);
-      o.y = np_uint8f(255.0f * (v.y + 1.0f) / 2.0f);
-      o.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
-      o.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
-      *reinterpret_cast<uchar4*>(sh + e) = o;
+      *reinterpret_cast<uchar4*>(sh + e) = from_tanh_u8(v);
       if (a.P.field) *reinterpret_cast<float4*>(a.P.field + row + e) = v;   // full-resolution pools: what is displayed is x (kind 1)
     }
     if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 1;
     return;
+  }
+  PhotoLocalArgs l;
+  if constexpr (LOCAL) {
+    const int flags = a.P.local[id];
+    l.umask = (flags & 1) ? a.P.umask + (size_t)id * (64 * 64) : nullptr;
+    l.falloff = a.items ? a.falloff : nullptr;
+    l.c1 = l.r1 = l.c2 = l.r2 = 0;
+    if (a.items) {
+      // a rectangle that is empty or not inside the image (the host refuses the latter) adds no footprint: the table has 64 entries
+      const int c1 = a.items[i * 7], r1 = a.items[i * 7 + 1], c2 = a.items[i * 7 + 2], r2 = a.items[i * 7 + 3];
+      if (c1 >= 0 && r1 >= 0 && c2 <= 64 && r2 <= 64 && c1 < c2 && r1 < r2) {
+        l.c1 = c1;
+        l.r1 = r1;
+        l.c2 = c2;
+        l.r2 = r2;
+      }
+    }
+    l.dampen = flags & 2;
+    l.thresh = a.thresh;
   }
   PhotoBlendArgs b;
   b.xhat = xh;
@@ -246,7 +269,7 @@ __global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a)
 #pragma unroll
   for (int k = 0; k < 8; ++k) b.w[k] = a.w[k];
   b.radius = a.radius;
-  photo_blend_image(b, m0, m1);
+  photo_blend_image<LOCAL>(b, m0, m1, LOCAL ? &l : nullptr);
   if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 0;
   if (a.store) {   // every thread re-reads exactly the bytes it wrote (p = tid + k * PB_T per channel)
     for (int p = threadIdx.x; p < 64 * 64; p += PB_T)
@@ -254,69 +277,16 @@ __global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a)
       for (int c = 0; c < 3; ++c) sh[c * 64 * 64 + p] = b.im[c * 64 * 64 + p];
   }
 }
-
-// The same for a pool with the local reservation (ian_sessions_reserve_local); session_blend_kernel above stays the code of every other
-// pool.  The session's LOCAL flags choose, uniformly over the workgroup, what the blend does (npe_ops.photo_blend_local).  Bit 0: a
-// paint event first max-es the footprint of its rectangle into the session's UMASK (set_latent, items == nullptr, adds none), then
-// MASK_L = MASK * UMASK; bit 1: dampen.  Flags 0 take the same LOCAL instantiation with both switched off: MASK and D go through the
-// operations of session_blend_kernel.  Sample mode and lighten events never look at the flags.  Mixed batches are one launch.
+__global__ __launch_bounds__(PB_T) void session_blend_kernel(SessionBlendArgs a) {
+  __shared__ double m0[64 * 64];
+  __shared__ double m1[64 * 64];
+  session_blend_body<false>(a, m0, m1);
+}
+// session_blend_kernel stays the code of every pool without the local reservation
 __global__ __launch_bounds__(PB_T) void session_blend_local_kernel(SessionBlendArgs a) {
   __shared__ double m0[64 * 64];
   __shared__ double m1[64 * 64];
-  const int i = blockIdx.y;
-  const int id = a.ids[i];
-  const size_t row = (size_t)id * S_IMG;
-  const float* xh = a.xhat + (size_t)i * S_IMG;
-  unsigned char* sh = a.shown + (size_t)i * S_IMG;
-  for (int j = threadIdx.x; j < a.P.zl; j += PB_T) a.P.z[(size_t)id * a.P.zl + j] = a.zslot[(size_t)i * a.zs + j];
-  if (a.P.mode[id] != 0 || (a.items && a.items[i * 7 + 4] == 0)) {   // the plain sample, as in session_blend_kernel
-    for (int e = threadIdx.x * 4; e < S_IMG; e += PB_T * 4) {
-      const float4 v = *reinterpret_cast<const float4*>(xh + e);
-      uchar4 o;
-      o.x = np_uint8f(255.0f * (v.x + 1.0f) / 2.0f);
-      o.y = np_uint8f(255.0f * (v.y + 1.0f) / 2.0f);
-      o.z = np_uint8f(255.0f * (v.z + 1.0f) / 2.0f);
-      o.w = np_uint8f(255.0f * (v.w + 1.0f) / 2.0f);
-      *reinterpret_cast<uchar4*>(sh + e) = o;
-      if (a.P.field) *reinterpret_cast<float4*>(a.P.field + row + e) = v;
-    }
-    if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 1;
-    return;
-  }
-  const int flags = a.P.local[id];
-  PhotoLocalArgs l;
-  l.umask = (flags & 1) ? a.P.umask + (size_t)id * (64 * 64) : nullptr;
-  l.falloff = a.items ? a.falloff : nullptr;
-  l.c1 = l.r1 = l.c2 = l.r2 = 0;
-  if (a.items) {
-    // a rectangle that is empty or not inside the image (the host refuses the latter) adds no footprint: the table has 64 entries
-    const int c1 = a.items[i * 7], r1 = a.items[i * 7 + 1], c2 = a.items[i * 7 + 2], r2 = a.items[i * 7 + 3];
-    if (c1 >= 0 && r1 >= 0 && c2 <= 64 && r2 <= 64 && c1 < c2 && r1 < r2) {
-      l.c1 = c1;
-      l.r1 = r1;
-      l.c2 = c2;
-      l.r2 = r2;
-    }
-  }
-  l.dampen = flags & 2;
-  l.thresh = a.thresh;
-  PhotoBlendArgs b;
-  b.xhat = xh;
-  b.recon = a.P.recon + row;
-  b.error = a.P.error + row;
-  b.im = a.store ? a.P.im + row : sh;
-  b.mask = nullptr;
-  b.field = a.P.field ? a.P.field + row : nullptr;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) b.w[k] = a.w[k];
-  b.radius = a.radius;
-  photo_blend_image<true>(b, m0, m1, &l);
-  if (a.P.kind && threadIdx.x == 0) a.P.kind[id] = 0;
-  if (a.store) {   // every thread re-reads exactly the bytes it wrote (p = tid + k * PB_T per channel)
-    for (int p = threadIdx.x; p < 64 * 64; p += PB_T)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) sh[c * 64 * 64 + p] = b.im[c * 64 * 64 + p];
-  }
+  session_blend_body<true>(a, m0, m1);
 }
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s) {
   if (a.radius < 0 || a.radius > 7 || n < 1 || n > 65535 || !a.shown) return hipErrorInvalidValue;

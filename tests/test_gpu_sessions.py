@@ -11,11 +11,10 @@ import numpy as np
 import pytest
 
 from oracle import ian_oracle as O
+from session_helpers import ROOT, assert_fields as assert_session, const_rgb, model_pool, refused, session_events as events
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CFG = os.path.join(ROOT, "neural_photo_editor_amd", "configs")
 CAP = 16
 
 _cache = {}
@@ -24,9 +23,7 @@ _cache = {}
 def model_for(arch):
     """One model and one pool per arch, kept across tests."""
     if arch not in _cache:
-        from neural_photo_editor_amd import IAN
-        m = IAN(os.path.join(CFG, arch + ".py"), True, params=O.make_params(arch, 1))
-        _cache[arch] = (m, m.sessions(CAP))
+        _cache[arch] = model_pool(arch)
     return _cache[arch]
 
 
@@ -41,11 +38,6 @@ def host_open(m, ph):
     RECON = m.sample_at_uint8(Z)
     return [dict(Z=Z[i].copy(), RECON=RECON[i], ERROR=N.to_tanh(np.float32(ph[i])) - N.to_tanh(np.float32(RECON[i])), IM=ph[i].copy(),
                  GIM=ph[i].copy(), MODE=0) for i in range(len(ph))]
-
-
-def assert_session(got, want, what=("Z", "RECON", "ERROR", "IM", "GIM", "MODE"), tag=None):
-    for k in what:
-        assert np.array_equal(got[k], want[k]), (tag, k)
 
 
 @pytest.mark.parametrize("arch", O.ARCHS)
@@ -65,13 +57,6 @@ def test_open_equals_the_stateless_calls_bitwise(arch, n):
 
 
 # ---- the brush script: the pool against a host-side model driven by brush_step_batch ----------------------------------------
-def const_rgb(levels):
-    from neural_photo_editor_amd import npe_ops as N
-    rgb = np.zeros((3, 64, 64), np.float32)
-    rgb[0], rgb[1], rgb[2] = levels                      # myRGB[0] (NPE.py:87,359)
-    return np.float32(N.to_tanh(np.float32(rgb)))          # what NPE.py:205 passes to imgradRGB
-
-
 def model_brush(m, M, ids, boxes, colours, modes, weight, sign):
     """One stateless call on the host-held state of sessions `ids`, in that order -> shown; M is updated as NPE.py updates its globals."""
     from neural_photo_editor_amd import npe_ops as N
@@ -280,7 +265,7 @@ def test_reference_executed_session_through_sessions(batched):
 
 @pytest.mark.parametrize("arch", O.ARCHS)
 def test_failures_name_the_item_and_leave_state_alone(arch):
-    from neural_photo_editor_amd.lib import IanError, SessionEvent
+    from neural_photo_editor_amd.lib import SessionEvent
     m, s = model_for(arch)
     h = m.handle
     ids = [0, 1, 2]                          # session 15 is opened by no test of this module
@@ -289,13 +274,6 @@ def test_failures_name_the_item_and_leave_state_alone(arch):
     before = [s.read(i) for i in ids]
     z = O.make_latents(2, seed=3)
     shown = np.full((2, 3, 64, 64), 7, np.uint8)
-
-    def events(sessions, box=(0, 0, 4, 4), mode=1):
-        ev = (SessionEvent * len(sessions))()
-        for e, sid in zip(ev, sessions):
-            e.session, e.mode, e.coef, e.gscale = sid, mode, -0.05, 5.0
-            e.c1, e.r1, e.c2, e.r2 = box
-        return ev
 
     i32 = lambda v: np.asarray(v, np.int32)
     bad = [
@@ -316,9 +294,7 @@ def test_failures_name_the_item_and_leave_state_alone(arch):
         ("n = 257", lambda: h.session_open(i32(np.arange(257)), None, 0, None)),
     ]
     for needle, call in bad:
-        with pytest.raises(IanError, match=needle) as ei:
-            call()
-        assert "error -7" in str(ei.value), str(ei.value)
+        refused(call, needle, -7)
         assert np.all(shown == 7)
         for i, b in zip(ids, before):
             assert_session(s.read(i), b, tag=needle)

@@ -2,19 +2,15 @@
 EditSessions.reserve_hires / open_hires / render / brush_view).  Every comparison is np.array_equal: the numpy functions of npe_ops
 (hires_downsample, edit_field, hires_axis_taps, hires_render) specify the arithmetic and the device matches them bit for bit; the
 64x64 state is held against a second pool WITHOUT the reservation, driven by the existing calls, which shows they are unchanged."""
-import os
-
 import numpy as np
 import pytest
 
 from oracle import ian_oracle as O
+from session_helpers import KEYS64, assert_fields, const_rgb, model_pool, refused, session_events as events, session_views as views, sources
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CFG = os.path.join(ROOT, "neural_photo_editor_amd", "configs")
 CAP = 16
-KEYS64 = ("Z", "RECON", "ERROR", "IM", "GIM", "MODE")
 
 _cache = {}
 
@@ -23,23 +19,11 @@ def pools(arch="IAN_simple"):
     """Two models with the same synthetic parameters, one pool each: (model, full-resolution pool, model, plain pool).  The
     stateless calls of a test go to the SECOND model, so that the first handle sees session calls only (its residency survives)."""
     if arch not in _cache:
-        from neural_photo_editor_amd import IAN
-        mh = IAN(os.path.join(CFG, arch + ".py"), True, params=O.make_params(arch, 1))
-        mp = IAN(os.path.join(CFG, arch + ".py"), True, params=O.make_params(arch, 1))
-        _cache[arch] = (mh, mh.sessions(CAP), mp, mp.sessions(CAP))
+        _cache[arch] = model_pool(arch) + model_pool(arch)
     mh, sh, mp, sp = _cache[arch]
     if sh.capacity != CAP:
         sh.reserve(CAP)
     return mh, sh, mp, sp
-
-
-def sources(n, s, seed):
-    """Smooth pictures plus noise: block means that are no multiples of anything, every byte value present."""
-    rs = np.random.RandomState(seed)
-    S = 64 * s
-    yy, xx = np.mgrid[0:S, 0:S]
-    base = 127.5 + 100.0 * np.sin(xx / (5.0 * s) + rs.uniform(0, 6, (n, 3, 1, 1))) * np.cos(yy / (7.0 * s) + rs.uniform(0, 6, (n, 3, 1, 1)))
-    return np.uint8(np.clip(base + rs.randint(-40, 41, (n, 3, S, S)), 0, 255))
 
 
 def windows(S):
@@ -59,8 +43,7 @@ def assert_renders(sh, ids, want, s, tag):
 
 
 def assert_same64(a, b, tag):
-    for k in KEYS64:
-        assert np.array_equal(a[k], b[k]), (tag, k)
+    assert_fields(a, b, KEYS64, tag)
 
 
 # ---- 1. open --------------------------------------------------------------------------------------------------------------------
@@ -88,13 +71,6 @@ def test_open_hires_is_open_of_the_box_mean(s, n):
 
 
 # ---- 2. the brush script ---------------------------------------------------------------------------------------------------------
-def const_rgb(levels):
-    from neural_photo_editor_amd import npe_ops as N
-    rgb = np.zeros((3, 64, 64), np.float32)
-    rgb[0], rgb[1], rgb[2] = levels
-    return np.float32(N.to_tanh(np.float32(rgb)))
-
-
 def expected_fields(mp, M, ids, boxes, colours, modes, weight, sign):
     """The stateless call on the host-held state of sessions `ids` (as test_gpu_sessions.model_brush) -> {id: (FIELD, KIND)}; M's
     latents move on."""
@@ -219,8 +195,7 @@ def test_brush_view_is_brush_then_render():
     assert (got[0][1] != src[:, :, 36:36 + 57, 40:40 + 88][0]).any()       # the window shows an edit
     for a, b in zip(A, B):
         ga, gb = sh.read(a), sh.read(b)
-        for k in KEYS64 + ("FIELD", "FIELD_KIND", "SOURCE"):
-            assert np.array_equal(ga[k], gb[k]), k
+        assert_fields(ga, gb, KEYS64 + ("FIELD", "FIELD_KIND", "SOURCE"))
 
 
 # ---- 4. commit -------------------------------------------------------------------------------------------------------------------
@@ -281,7 +256,6 @@ def test_scale_16_whole_picture():
 
 # ---- 6. refusals ---------------------------------------------------------------------------------------------------------------
 def test_refusals_return_their_code_and_change_nothing():
-    from neural_photo_editor_amd.lib import IanError, SessionEvent, SessionView
     s = 2
     S = 64 * s
     mh, sh, mp, sp = pools()
@@ -294,19 +268,6 @@ def test_refusals_return_their_code_and_change_nothing():
     before = [sh.read(i) for i in ids]
     out = np.full((2, 3, 16, 16), 7, np.uint8)
     shown = np.full((2, 3, 64, 64), 7, np.uint8)
-
-    def views(items):
-        v = (SessionView * len(items))()
-        for d, (sid, x, y) in zip(v, items):
-            d.session, d.x, d.y = sid, x, y
-        return v
-
-    def events(sessions):
-        ev = (SessionEvent * len(sessions))()
-        for e, sid in zip(ev, sessions):
-            e.session, e.mode, e.coef, e.gscale = sid, 1, -0.05, 5.0
-            e.c1, e.r1, e.c2, e.r2 = 0, 0, 4, 4
-        return ev
 
     ok = [(0, 0, 0), (1, 0, 0)]
     bad = [
@@ -332,14 +293,11 @@ def test_refusals_return_their_code_and_change_nothing():
         ("item 1", lambda: h.session_brush_view(events([0, 0]), views([(0, 0, 0), (0, 0, 0)]), 16, 16, out, shown)),   # the event's checks
     ]
     for needle, call in bad:
-        with pytest.raises(IanError, match=needle) as ei:
-            call()
-        assert "error -7" in str(ei.value), str(ei.value)
+        refused(call, needle, -7)
         assert np.all(out == 7) and np.all(shown == 7)
         for i, b in zip(ids, before):
             got = sh.read(i)
-            for k in ("SOURCE", "FIELD", "Z"):
-                assert np.array_equal(got[k], b[k]), (needle, i, k)
+            assert_fields(got, b, ("SOURCE", "FIELD", "Z"), (needle, i))
     # -6: a pool without the reservation
     hp = mp.handle
     sp.open([0, 1], sources(2, 1, 57))
@@ -352,9 +310,7 @@ def test_refusals_return_their_code_and_change_nothing():
     ]
     z0 = sp.read(0)["Z"]
     for call in no_res:
-        with pytest.raises(IanError, match="no full-resolution reservation") as ei:
-            call()
-        assert "error -6" in str(ei.value), str(ei.value)
+        refused(call, "no full-resolution reservation", -6)
     assert np.all(out == 7) and np.array_equal(sp.read(0)["Z"], z0)
     # the Python surface refuses the same before the library is called, and the handle still works
     with pytest.raises(ValueError):
@@ -365,7 +321,7 @@ def test_refusals_return_their_code_and_change_nothing():
 
 # ---- 7. pool upkeep --------------------------------------------------------------------------------------------------------------
 def test_pool_upkeep_keeps_sources_and_fields():
-    from neural_photo_editor_amd.lib import IanError, SessionView
+    from neural_photo_editor_amd.lib import IanError
     s = 2
     S = 64 * s
     mh, sh, _, _ = pools()
@@ -376,25 +332,20 @@ def test_pool_upkeep_keeps_sources_and_fields():
     sh.paint(ids, (8, 8, 30, 30), (10, 200, 30), weight=0.5)
     before = [sh.read(i) for i in ids]
     whole = sh.render(ids, (0, 0), S)
-    one = (SessionView * 1)()
-    one[0].session, one[0].x, one[0].y = 6, 0, 0
+    one = views([(6, 0, 0)])
     out = np.empty((1, 3, 8, 8), np.uint8)
     try:
         sh.reserve(40)                                                        # growing keeps the rows
         for i, b in zip(ids, before):
             got = sh.read(i)
-            for k in KEYS64 + ("SOURCE", "FIELD", "FIELD_KIND"):
-                assert np.array_equal(got[k], b[k]), ("grown", i, k)
+            assert_fields(got, b, KEYS64 + ("SOURCE", "FIELD", "FIELD_KIND"), ("grown", i))
         sh.open_hires([39], src[:1])
         assert np.array_equal(sh.render([39, 1], (0, 0), S), np.stack([src[0], whole[0]]))
         sh.reserve(4)                                                         # shrinking keeps the ids that remain
         got = sh.read(1)
-        for k in KEYS64 + ("SOURCE", "FIELD", "FIELD_KIND"):
-            assert np.array_equal(got[k], before[0][k]), ("shrunk", k)
+        assert_fields(got, before[0], KEYS64 + ("SOURCE", "FIELD", "FIELD_KIND"), "shrunk")
         assert np.array_equal(sh.render([1], (0, 0), S)[0], whole[0])
-        with pytest.raises(IanError, match="outside the pool") as ei:
-            mh.handle.session_render(one, 8, 8, out)
-        assert "error -7" in str(ei.value)
+        refused(lambda: mh.handle.session_render(one, 8, 8, out), "outside the pool", -7)
     finally:
         sh.reserve(CAP)
     # a plain open clears the source flag
@@ -402,20 +353,55 @@ def test_pool_upkeep_keeps_sources_and_fields():
     mh.handle.session_render(one, 8, 8, out)
     assert np.array_equal(out[0], src[1][:, :8, :8])
     sh.open([6], src[1:, :, :64, :64].copy())
-    with pytest.raises(IanError, match="no full-resolution source") as ei:
-        mh.handle.session_render(one, 8, 8, out)
-    assert "error -7" in str(ei.value)
+    refused(lambda: mh.handle.session_render(one, 8, 8, out), "no full-resolution source", -7)
     assert "SOURCE" not in sh.read(6) and not sh.read(6)["FIELD"].any()
     # reserve_hires(0) frees; the 64x64 state stays
     z1 = sh.read(1)["Z"]
     sh.reserve_hires(0)
     one[0].session = 1
-    with pytest.raises(IanError, match="no full-resolution reservation") as ei:
-        mh.handle.session_render(one, 8, 8, out)
-    assert "error -6" in str(ei.value)
+    refused(lambda: mh.handle.session_render(one, 8, 8, out), "no full-resolution reservation", -6)
     got = sh.read(1)
     assert np.array_equal(got["Z"], z1) and "FIELD" not in got
     # and back: a new reservation starts without sources
     sh.reserve_hires(s)
     with pytest.raises(IanError, match="no full-resolution source"):
         mh.handle.session_render(one, 8, 8, out)
+
+
+# ---- 8. another scale, and the whole pool freed -------------------------------------------------------------------------------------
+def test_scale_change_keeps_fields_and_drops_sources():
+    mh, sh, _, _ = pools()
+    sh.reserve_hires(1)
+    sh.open_hires([5], sources(1, 1, 91))
+    sh.paint([5], (8, 8, 30, 30), (10, 200, 30), weight=0.5)
+    before = sh.read(5)
+    assert before["FIELD"].any() and "SOURCE" in before
+    sh.reserve_hires(2)
+    got = sh.read(5)
+    assert "SOURCE" not in got
+    assert_fields(got, before, KEYS64 + ("FIELD", "FIELD_KIND"))
+    refused(lambda: mh.handle.session_render(views([(5, 0, 0)]), 8, 8, np.empty((1, 3, 8, 8), np.uint8)), "no full-resolution source", -7)
+    big = sources(1, 2, 92)
+    sh.open_hires([5], big)
+    assert np.array_equal(sh.render([5], (0, 0), 128), big)
+
+
+def test_free_and_come_back_keeps_the_blend_and_drops_both_reservations():
+    """On the raw handle: ian_sessions_reserve(0), then a pool again without ian_sessions_set_blend."""
+    mh, sh, mp, sp = pools()
+    h, ids, ph = mh.handle, np.asarray([2], np.int32), sources(1, 1, 95)
+    sh.reserve_hires(2)
+    sh.reserve_local()
+    try:
+        h.sessions_reserve(0)
+        refused(lambda: h.session_read(2, "Z"), "no session pool", -6)
+        h.sessions_reserve(4)
+        shown, want = np.empty((1, 3, 64, 64), np.uint8), np.empty((1, 3, 64, 64), np.uint8)
+        for hd, out in ((h, shown), (mp.handle, want)):
+            hd.session_open(ids, ph, 0, out)
+            hd.session_brush(events([2], box=(8, 8, 30, 30)), out)
+        assert np.array_equal(shown, want)
+        refused(lambda: h.session_read(2, "FIELD"), "no full-resolution reservation", -6)
+        refused(lambda: h.session_read(2, "UMASK"), "no local reservation", -6)
+    finally:
+        _cache["IAN_simple"] = (mh, mh.sessions(CAP), mp, sp)

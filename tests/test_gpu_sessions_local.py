@@ -3,19 +3,16 @@ set_local).  Every comparison is np.array_equal: the numpy functions of npe_ops 
 photo_blend_local) specify the arithmetic and the device matches them bit for bit.  The host model of a brush call is the stateless
 brush_step_batch on a SECOND model (for x and the new latents) followed by those numpy functions; sessions with flags 0 are held
 against a second pool WITHOUT the reservation, which shows that nothing that exists has changed."""
-import os
-
 import numpy as np
 import pytest
 
 from oracle import ian_oracle as O
+import session_helpers as H
+from session_helpers import KEYS64, assert_fields, const_rgb, model_pool, refused, session_events as events
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CFG = os.path.join(ROOT, "neural_photo_editor_amd", "configs")
 CAP = 16
-KEYS64 = ("Z", "RECON", "ERROR", "IM", "GIM", "MODE")
 IDS = [9, 2, 14]
 THRESH = 0.75
 
@@ -26,28 +23,14 @@ def pools(arch="IAN_simple"):
     """Two models with the same synthetic parameters, one pool each: (model, pool with the local reservation, model, plain pool).  The
     stateless calls of a test go to the SECOND model, so that the first handle sees session calls only."""
     if arch not in _cache:
-        from neural_photo_editor_amd import IAN
-        ml = IAN(os.path.join(CFG, arch + ".py"), True, params=O.make_params(arch, 1))
-        mp = IAN(os.path.join(CFG, arch + ".py"), True, params=O.make_params(arch, 1))
-        sl = ml.sessions(CAP)
-        sl.reserve_local()
-        _cache[arch] = (ml, sl, mp, mp.sessions(CAP))
+        _cache[arch] = model_pool(arch) + model_pool(arch)
+        _cache[arch][1].reserve_local()
     return _cache[arch]
 
 
 def sources(n, seed):
     """Smooth pictures plus noise, every byte value present: the bright pixels (level 224 and above) are what make dampen fire."""
-    rs = np.random.RandomState(seed)
-    yy, xx = np.mgrid[0:64, 0:64]
-    base = 127.5 + 100.0 * np.sin(xx / 5.0 + rs.uniform(0, 6, (n, 3, 1, 1))) * np.cos(yy / 7.0 + rs.uniform(0, 6, (n, 3, 1, 1)))
-    return np.uint8(np.clip(base + rs.randint(-40, 41, (n, 3, 64, 64)), 0, 255))
-
-
-def const_rgb(levels):
-    from neural_photo_editor_amd import npe_ops as N
-    rgb = np.zeros((3, 64, 64), np.float32)
-    rgb[0], rgb[1], rgb[2] = levels
-    return np.float32(N.to_tanh(np.float32(rgb)))
+    return H.sources(n, 1, seed)
 
 
 def dampened_count(x, recon, error, mask_l):
@@ -113,8 +96,7 @@ def test_sessions_with_flags_0_give_the_results_of_a_pool_without_the_reservatio
         assert np.array_equal(got, want), (step, name)
         for i in IDS:
             a, b = sl.read(i), sp.read(i)
-            for k in KEYS64:
-                assert np.array_equal(a[k], b[k]), (step, name, i, k)
+            assert_fields(a, b, KEYS64, (step, name, i))
             assert a["LOCAL"] == 0 and not a["UMASK"].any() and "UMASK" not in b
 
 
@@ -146,8 +128,7 @@ def test_brush_script_equals_the_host_model(arch, flags):
         assert np.array_equal(shown, want), (arch, flags, step)
         for i in IDS:
             got = sl.read(i)
-            for k in ("IM", "UMASK", "Z", "MODE", "LOCAL", "RECON", "ERROR", "GIM"):
-                assert np.array_equal(got[k], M[i][k]), (arch, flags, step, i, k)
+            assert_fields(got, M[i], ("IM", "UMASK", "Z", "MODE", "LOCAL", "RECON", "ERROR", "GIM"), (arch, flags, step, i))
         umask_after.append(M[9]["UMASK"].copy())
     # what keeps the comparisons above from passing vacuously, on the numpy side
     assert stats["differs"] > 0
@@ -235,8 +216,7 @@ def test_open_reset_commit_and_set_local_clear_umask_and_keep_local():
         sl.reserve(CAP + 4)
         for i, b in zip(ids, before):
             got = sl.read(i)
-            for k in KEYS64 + ("UMASK", "LOCAL"):
-                assert np.array_equal(got[k], b[k]), ("grown", i, k)
+            assert_fields(got, b, KEYS64 + ("UMASK", "LOCAL"), ("grown", i))
         sl.open([CAP + 3], ph[:1])
         got = sl.read(CAP + 3)
         assert got["LOCAL"] == 0 and not got["UMASK"].any()
@@ -246,8 +226,7 @@ def test_open_reset_commit_and_set_local_clear_umask_and_keep_local():
     finally:
         sl.reserve(CAP)
     got = sl.read(1)
-    for k in KEYS64 + ("UMASK", "LOCAL"):
-        assert np.array_equal(got[k], before[0][k]), ("shrunk", k)
+    assert_fields(got, before[0], KEYS64 + ("UMASK", "LOCAL"), "shrunk")
 
 
 # ---- 5. full resolution ----------------------------------------------------------------------------------------------------------
@@ -299,7 +278,7 @@ def test_full_resolution_field_and_windows():
 # ---- 6. refusals -----------------------------------------------------------------------------------------------------------------
 def test_refusals_return_their_code_and_change_nothing():
     from neural_photo_editor_amd import npe_ops as N
-    from neural_photo_editor_amd.lib import IanError, SessionEvent
+    from neural_photo_editor_amd.lib import IanError
     ml, sl, mp, sp = pools()
     hl, hp = ml.handle, mp.handle
     ids = [0, 1, 2]
@@ -314,15 +293,7 @@ def test_refusals_return_their_code_and_change_nothing():
     def unchanged(tag):
         for i, b in zip(ids, before):
             got = sl.read(i)
-            for k in keys:
-                assert np.array_equal(got[k], b[k]), (tag, i, k)
-
-    def events(sessions):
-        ev = (SessionEvent * len(sessions))()
-        for e, sid in zip(ev, sessions):
-            e.session, e.mode, e.coef, e.gscale = sid, 1, -0.05, 5.0
-            e.c1, e.r1, e.c2, e.r2 = 0, 0, 4, 4
-        return ev
+            assert_fields(got, b, keys, (tag, i))
 
     good = N.local_falloff_table()
 
@@ -346,9 +317,7 @@ def test_refusals_return_their_code_and_change_nothing():
         (r"falloff64\[9\]", lambda: hl.sessions_set_local(table(d9=float("nan")), THRESH)),     # a NaN
     ]
     for needle, call in bad:
-        with pytest.raises(IanError, match=needle) as ei:
-            call()
-        assert "error -7" in str(ei.value), str(ei.value)
+        refused(call, needle, -7)
         unchanged(needle)
     # the table that was set is still the one in use
     sl.paint([0], (40, 40, 44, 44), (200, 100, 50), weight=0.5)
@@ -358,23 +327,18 @@ def test_refusals_return_their_code_and_change_nothing():
     shown = np.full((1, 3, 64, 64), 7, np.uint8)
     for call in (lambda: hp.session_local([0, 1], [1, 1]), lambda: hp.sessions_set_local(good, THRESH),
                  lambda: hp.session_read(0, "UMASK"), lambda: hp.session_read(0, "LOCAL")):
-        with pytest.raises(IanError, match="no local reservation") as ei:
-            call()
-        assert "error -6" in str(ei.value), str(ei.value)
+        refused(call, "no local reservation", -6)
     # -6: a session with flags, but no falloff table yet (the reservation made through the C ABI alone)
     try:
         hp.sessions_reserve_local(True)
         hp.session_local([0, 2], [1, 0])
         z = np.ascontiguousarray(O.make_latents(1, seed=5), np.float32)
         for call in (lambda: hp.session_brush(events([1, 0]), shown), lambda: hp.session_set_latent(np.asarray([0], np.int32), z, 0, shown)):
-            with pytest.raises(IanError, match="falloff table is not set") as ei:
-                call()
-            assert "error -6" in str(ei.value), str(ei.value)
+            refused(call, "falloff table is not set", -6)
             assert np.all(shown == 7)
         for i, b in zip(ids, before_p):
             got = sp.read(i)
-            for k in KEYS64:
-                assert np.array_equal(got[k], b[k]), (i, k)
+            assert_fields(got, b, KEYS64, i)
             assert not hp.session_read(i, "UMASK").any() and int(hp.session_read(i, "LOCAL")[0]) == (1 if i == 0 else 0)
         hp.session_brush(events([2, 1]), None)                            # sessions with flags 0 need no table
         assert not np.array_equal(sp.read(2)["Z"], before_p[2]["Z"]) and np.array_equal(sp.read(0)["Z"], before_p[0]["Z"])
@@ -392,3 +356,35 @@ def test_refusals_return_their_code_and_change_nothing():
     sl.set_local(ids, flags=0)
     for i in ids:
         assert sl.read(i)["LOCAL"] == 0
+
+
+# ---- 7. both reservations through a resize: all eleven arrays move together -------------------------------------------------------
+def test_resize_with_both_reservations_keeps_every_field_and_window():
+    s, ids = 2, [1, 3]
+    ml, sl, _, _ = pools()
+    keys = KEYS64 + ("FIELD", "FIELD_KIND", "SOURCE", "UMASK", "LOCAL")
+    try:
+        sl.reserve(4)
+        sl.reserve_hires(s)
+        sl.open_hires(ids, H.sources(2, s, 81))
+        sl.set_local(ids, flags=[1, 3])
+        sl.paint(ids, (8, 8, 30, 30), (10, 200, 30), weight=0.5)
+        before = [sl.read(i) for i in ids]
+        assert all(set(b) == set(keys) and b["UMASK"].any() and b["FIELD"].any() for b in before)
+        windows = sl.render(ids, (40, 36), 8)
+        sl.reserve(7)
+        for i, b in zip(ids, before):
+            got = sl.read(i)
+            assert_fields(got, b, keys, ("grown", i))
+        assert np.array_equal(sl.render(ids, (40, 36), 8), windows)
+        sl.open([6], sources(1, 82))
+        got = sl.read(6)
+        assert not got["UMASK"].any() and got["LOCAL"] == 0 and not got["FIELD"].any() and got["FIELD_KIND"] == 0
+        sl.reserve(3)
+        got = sl.read(1)
+        assert_fields(got, before[0], keys, "shrunk")
+        assert np.array_equal(sl.render([1], (40, 36), 8), windows[:1])
+        refused(lambda: ml.handle.session_read(3, "Z"), "outside the pool", -7)
+    finally:
+        sl.reserve_hires(0)
+        sl.reserve(CAP)

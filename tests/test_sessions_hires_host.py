@@ -2,10 +2,9 @@
 ian_session_brush_view): the numpy functions that specify the arithmetic (npe_ops.hires_*, edit_field), the view struct's layout
 against the header, the view packer (every validation before any library call) and the header / export list agreement."""
 import ctypes
-import os
+import functools
 import re
 import shutil
-import subprocess
 import time
 
 import numpy as np
@@ -13,8 +12,9 @@ import pytest
 
 from neural_photo_editor_amd import api, npe_ops as N
 from neural_photo_editor_amd import lib as L
+from session_helpers import HEADER, StubHandle, header_code, run_c, stub_sessions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+stub_sessions = functools.partial(stub_sessions, sourced=(0, 1, 2), scale=3)
 SCALES = [1, 2, 3, 5, 16]
 NEW_EXPORTS = ("ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view")
 
@@ -139,20 +139,13 @@ def test_session_view_layout_matches_header(tmp_path):
              '  printf("%zu %zu %zu %zu\\n", sizeof(ian_session_view), offsetof(ian_session_view, session), offsetof(ian_session_view, x), '
              'offsetof(ian_session_view, y));',
              '  printf("%d %d %d\\n", IAN_SESSION_FIELD, IAN_SESSION_FIELD_KIND, IAN_SESSION_SOURCE);', '  return 0;', '}']
-    src = tmp_path / "view.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "view"
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
-                   check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
+    out = run_c(tmp_path, lines)
     assert out[0].split() == ["12", "0", "4", "8"]
     assert out[1].split() == [str(L.SESSION_FIELDS[k][0]) for k in ("FIELD", "FIELD_KIND", "SOURCE")] == ["6", "7", "8"]
 
 
 def test_header_declares_exactly_what_the_library_exports_for_the_new_names():
-    header = open(os.path.join(ROOT, "include", "ian.h")).read()
-    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    declared = set(re.findall(r"\b(ian_[a-z_0-9]+)\s*\(", code))
+    declared = set(re.findall(r"\b(ian_[a-z_0-9]+)\s*\(", header_code()))
     for name in NEW_EXPORTS:
         assert name in declared and name in L.EXPORTS, name
     assert {n for n in declared if "hires" in n or "render" in n or "view" in n} == set(NEW_EXPORTS)
@@ -161,34 +154,12 @@ def test_header_declares_exactly_what_the_library_exports_for_the_new_names():
     for name in NEW_EXPORTS:
         fn = getattr(lib, name)
         assert fn.restype is ctypes.c_int32
-    protos = {name: argt for _, name, argt in L.parse_header_prototypes(os.path.join(ROOT, "include", "ian.h"))}
+    protos = {name: argt for _, name, argt in L.parse_header_prototypes(HEADER)}
     for name in NEW_EXPORTS:
         assert len(getattr(lib, name).argtypes) == len(protos[name]), name
 
 
 # ---- the packer ---------------------------------------------------------------------------------------------------------------
-class StubHandle:
-    """Records every call that would reach the library."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def record(*a, **k):
-            self.calls.append(name)
-        return record
-
-
-def stub_sessions(capacity=8, opened=(0, 1, 2, 3), sourced=(0, 1, 2), scale=3):
-    h = StubHandle()
-    s = api.EditSessions(h, capacity, 100)
-    s.reserve_hires(scale)
-    s._opened = set(opened)
-    s._sourced = set(sourced)
-    h.calls.clear()
-    return s, h
-
-
 def test_packer_broadcasts_and_fills_the_views():
     views, vw, vh = api.pack_session_views([2, 2, 0], [(0, 0), (96, 0), (4, 191)], (96, 1), 3)
     assert (vw, vh) == (96, 1) and len(views) == 3

@@ -2,17 +2,17 @@
 against the header, the event packer (broadcasting, truncation, every validation before any library call), the uint8 -> tanh table
 of the open kernel and the brush colour conversion."""
 import ctypes
-import os
+import functools
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from neural_photo_editor_amd import api, npe_ops
 from neural_photo_editor_amd import lib as L
+from session_helpers import run_c, stub_sessions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+stub_sessions = functools.partial(stub_sessions, opened=(0, 1, 2))
 
 
 def test_session_event_layout_matches_header(tmp_path):
@@ -26,12 +26,7 @@ def test_session_event_layout_matches_header(tmp_path):
         lines.append('  printf("%s %%zu\\n", offsetof(ian_session_event, %s));' % (fname, fname))
     lines += ['  printf("enum %d %d %d %d %d %d\\n", IAN_SESSION_Z, IAN_SESSION_RECON, IAN_SESSION_ERROR, IAN_SESSION_IM, IAN_SESSION_GIM, '
               'IAN_SESSION_MODE);', '  return 0;', '}']
-    src = tmp_path / "ev.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "ev"
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
-                   check=True)
-    out = [l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n") if l]
+    out = [l.split() for l in run_c(tmp_path, lines)]
     assert out[0] == ["size", "44"] and ctypes.sizeof(cls) == 44            # 11 words per event
     seen = 0
     for field, val in out[1:-1]:
@@ -86,26 +81,6 @@ def test_packer_broadcasts_truncates_and_forms_coef_gscale():
     items = api.pack_brush_items(np.array([(1.9, 2.2, 10.7, 12.0)]), 1, None, 0.05, -1.0)
     e = api.pack_session_events([0], np.array([(1.9, 2.2, 10.7, 12.0)]), (0, 0, 0))[0]
     assert (e.c1, e.r1, e.c2, e.r2, e.mode, e.coef, e.gscale) == tuple(getattr(items[0], f) for f, _ in L.BrushItem._fields_)
-
-
-class StubHandle:
-    """Records every call that would reach the library."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def record(*a, **k):
-            self.calls.append(name)
-        return record
-
-
-def stub_sessions(capacity=8, opened=(0, 1, 2)):
-    h = StubHandle()
-    s = api.EditSessions(h, capacity, 100)
-    s._opened = set(opened)
-    h.calls.clear()
-    return s, h
 
 
 @pytest.mark.parametrize("call", [

@@ -2,7 +2,7 @@
 that specify the arithmetic (npe_ops.local_falloff_table, local_footprint, umask_paint, photo_blend_local), the packer (every
 validation before any library call) and the header / export list agreement."""
 import ctypes
-import os
+import functools
 import re
 
 import numpy as np
@@ -10,8 +10,9 @@ import pytest
 
 from neural_photo_editor_amd import api, npe_ops as N
 from neural_photo_editor_amd import lib as L
+from session_helpers import HEADER, header_code, stub_sessions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+stub_sessions = functools.partial(stub_sessions, reserve=True, args=True)
 NEW_EXPORTS = ("ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local")
 BOXES = [(0, 0, 4, 4), (60, 60, 64, 64), (20, 30, 37, 47), (0, 63, 1, 64), (5, 9, 6, 10)]
 
@@ -164,28 +165,6 @@ def test_user_mask_confines_the_edit():
 
 
 # ---- the packer ---------------------------------------------------------------------------------------------------------------
-class StubHandle:
-    """Records every call that would reach the library."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def record(*a, **k):
-            self.calls.append((name, a))
-        return record
-
-
-def stub_sessions(capacity=8, opened=(0, 1, 2, 3), reserve=True):
-    h = StubHandle()
-    s = api.EditSessions(h, capacity, 100)
-    if reserve:
-        s.reserve_local()
-    s._opened = set(opened)
-    h.calls.clear()
-    return s, h
-
-
 def test_packer_forms_the_flags():
     ids, f = api.pack_session_local([3, 1, 2])
     assert ids.dtype == np.int32 and f.dtype == np.int32 and list(ids) == [3, 1, 2] and list(f) == [1, 1, 1]
@@ -242,8 +221,7 @@ def test_valid_calls_reach_the_library():
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------
 def test_header_and_export_list_agree_on_the_new_names():
-    header = open(os.path.join(ROOT, "include", "ian.h")).read()
-    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    code = header_code()
     declared = set(re.findall(r"\b(ian_[a-z_0-9]+)\s*\(", code))
     for name in NEW_EXPORTS:
         assert name in declared and name in L.EXPORTS, name
@@ -252,7 +230,7 @@ def test_header_and_export_list_agree_on_the_new_names():
     assert re.search(r"IAN_SESSION_UMASK\s*=\s*9\b", code) and re.search(r"IAN_SESSION_LOCAL\s*=\s*10\b", code)
     assert L.SESSION_FIELDS["UMASK"] == (9, np.float64, (64, 64)) and L.SESSION_FIELDS["LOCAL"][0] == 10
     lib = L.load_library()
-    protos = {name: argt for _, name, argt in L.parse_header_prototypes(os.path.join(ROOT, "include", "ian.h"))}
+    protos = {name: argt for _, name, argt in L.parse_header_prototypes(HEADER)}
     for name in NEW_EXPORTS:
         fn = getattr(lib, name)
         assert fn.restype is ctypes.c_int32
