@@ -110,7 +110,33 @@ struct TgReduceParams {
   int M, qw_shift, qhw_shift, so, OH, OW, Cout, y_stride;
 };
 
-constexpr int TG_VARIANT_BF16X3 = 5;   // TgParams::variant of tapgemm_bf16x3_kernel (opt-in, ian_set_option("tg_bf16x3", 1))
+// TgParams::variant: the K-loop schedules of tapgemm_kernel (described at the head of kernels_tapgemm.hip).  The numbers are the
+// values of the options tg_variant / tg_variant_force and of the tune cache; this enum and the two predicates below are the
+// ONE place that says which of them exist.
+enum TgSchedule {
+  TG_SCHED_PLAIN = 0,        // ablation: compiler-scheduled
+  TG_SCHED_SPLIT = 1,        // LDS stores between the two halves of the MFMAs
+  TG_SCHED_ROTATED = 2,      // last k group's MFMAs behind the barrier
+  TG_SCHED_DMA = 3,          // ablation: LDS-DMA staging
+  TG_SCHED_QUEUE3 = 4,       // register queue, three K-steps of loads in flight
+  TG_VARIANT_BF16X3 = 5,     // not a schedule of tapgemm_kernel: tapgemm_bf16x3_kernel (opt-in, ian_set_option("tg_bf16x3", 1))
+  TG_SCHED_ROTATED_PIN = 6,  // 2 with every fragment read pinned
+  TG_SCHED_AHEAD2 = 7,       // rotated, two K-steps of loads in flight, per-tap addressing
+  TG_SCHED_AHEAD3 = 8,       // ablation: 7's structure with three K-steps in flight
+  TG_ABL2_FIRST = 10, TG_ABL2_LAST = 12,   // ablation: timing-only variants of schedule 2 (WRONG results)
+  TG_ABL7_FIRST = 17, TG_ABL7_LAST = 23,   // ablation: timing-only variants of schedule 7 (WRONG results)
+};
+// the schedules every build carries: option values, autotune candidates, tune-cache entries
+static inline bool tg_schedule_shipped(int v) {
+  return v == TG_SCHED_SPLIT || v == TG_SCHED_ROTATED || v == TG_SCHED_QUEUE3 || v == TG_SCHED_ROTATED_PIN || v == TG_SCHED_AHEAD2;
+}
+// "is v a K-loop schedule this library can launch": libian_ablation.so adds the negative results and the timing-only variants
+static inline bool tg_schedule_valid(int v) {
+#ifdef IAN_ABLATION
+  if (v == TG_SCHED_PLAIN || v == TG_SCHED_DMA || v == TG_SCHED_AHEAD3 || (v >= TG_ABL2_FIRST && v <= TG_ABL2_LAST) || (v >= TG_ABL7_FIRST && v <= TG_ABL7_LAST)) return true;
+#endif
+  return tg_schedule_shipped(v);
+}
 enum TgConfig { TG_128x128 = 0, TG_128x64 = 1, TG_64x64 = 2, TG_32x128 = 3, TG_256x128 = 4, TG_128x32 = 5,
                 TG_128x128W8 = 6 /* 128x128 tile, 8 waves of 64x32 */, TG_128x64W8 = 7 /* 128x64 tile, 8 waves of 32x32 */,
                 TG_NCONFIG = 8 };
@@ -152,7 +178,7 @@ static inline bool tg_bf16x3_supported(int cfg) {
 // puts the same bytes on the MFMA-bound kernel's critical path): there every request is answered with 0 chunks.
 static inline bool tg_stats_supported(int cfg, int variant) {
 #ifdef IAN_ABLATION
-  return cfg != TG_256x128 && (variant == 1 || variant == 2);
+  return cfg != TG_256x128 && (variant == TG_SCHED_SPLIT || variant == TG_SCHED_ROTATED);
 #else
   (void)cfg; (void)variant;
   return false;

@@ -104,15 +104,13 @@ std::vector<TgChoice> tune_candidates(const ian_handle* h, const TgLayer& L, int
       // launch (kernels_tapgemm.hip, fused 1 / 2) instead of paying a reduce launch that costs as much as their K loop
       const int nfuse = (ms > 0 && M <= h->opt.tg_fuse_max_m && tg_fuse_supported(cfg)) ? 1 + h->opt.tg_fuse_tune : 1;
       for (int fu = 0; fu < nfuse; ++fu)
-        for (int var : {1, 2, 4, 6, 7, 8}) {   // 3 (LDS-DMA staging) measured 5 % slower on every 5x5 layer: selectable, not a candidate
-          if (var != 1 && bf16x3_applies(h, M, nimg) && tg_bf16x3_supported(cfg)) continue;   // one schedule there
-          if (var == 6 && !h->opt.tg_tune_pin) continue;   // A/B switch: the pinned form of schedule 2 as a candidate (round 6)
-          if (var == 4 && (M > 1024 || cfg == TG_256x128)) continue;
-#ifndef IAN_ABLATION
-          if (var == 8) continue;   // libian_ablation.so only
-#endif
-          if (var == 8 && (h->opt.tg_tune_deep < 2 || tg_shape(cfg).bm * tg_shape(cfg).bn > 128 * 64)) continue;   // three K-steps in flight: the small tiles
-          if (var == 7 && (!h->opt.tg_tune_deep || cfg == TG_256x128)) continue;   // two K-steps of loads in flight in the rotated schedule (round 6)   // the three-deep load queue is for latency-bound items (few images)
+        for (int var : {TG_SCHED_SPLIT, TG_SCHED_ROTATED, TG_SCHED_QUEUE3, TG_SCHED_ROTATED_PIN, TG_SCHED_AHEAD2, TG_SCHED_AHEAD3}) {   // DMA staging measured 5 % slower on every 5x5 layer: selectable, not a candidate
+          if (!tg_schedule_valid(var)) continue;   // AHEAD3: libian_ablation.so only
+          if (var != TG_SCHED_SPLIT && bf16x3_applies(h, M, nimg) && tg_bf16x3_supported(cfg)) continue;   // one schedule there
+          if (var == TG_SCHED_ROTATED_PIN && !h->opt.tg_tune_pin) continue;   // A/B switch: the pinned form of schedule 2 as a candidate (round 6)
+          if (var == TG_SCHED_QUEUE3 && (M > 1024 || cfg == TG_256x128)) continue;
+          if (var == TG_SCHED_AHEAD3 && (h->opt.tg_tune_deep < 2 || tg_shape(cfg).bm * tg_shape(cfg).bn > 128 * 64)) continue;   // three K-steps in flight: the small tiles
+          if (var == TG_SCHED_AHEAD2 && (!h->opt.tg_tune_deep || cfg == TG_256x128)) continue;   // two K-steps of loads in flight in the rotated schedule (round 6)   // the three-deep load queue is for latency-bound items (few images)
           TgChoice c;
           c.cfg = cfg;
           c.max_steps = ms;
@@ -222,7 +220,7 @@ void tune_cache_load(TuneCache& c) {
   char dir[16], name[256];
   int n, cfg, ms, var, fu;
   while (fscanf(f, "%d %15s %255s %d %d %d %d", &n, dir, name, &cfg, &ms, &var, &fu) == 7) {
-    if (n <= 0 || cfg < 0 || cfg >= TG_NCONFIG || ms < 0 || fu < 0 || fu > 2 || (var != 1 && var != 2 && var != 4 && var != 6 && var != 7)) continue;
+    if (n <= 0 || cfg < 0 || cfg >= TG_NCONFIG || ms < 0 || fu < 0 || fu > 2 || !tg_schedule_shipped(var)) continue;
     TgChoice ch;
     ch.cfg = cfg;
     ch.max_steps = ms;

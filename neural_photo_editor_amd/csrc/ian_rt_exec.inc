@@ -55,12 +55,12 @@ int run_tapgemm(ian_handle* h, TgLayer& L, int nimg, const float* x, float* y, i
   p.si = L.si; p.by = L.by; p.bx = L.bx; p.so = L.so;
   p.OH = L.OH; p.OW = L.OW; p.Cout = L.Cout; p.y_stride = y_stride; p.CoutPad = L.CoutPad;
   const size_t xb = (size_t)nimg * L.IH * L.IW * L.Cin * sizeof(float);
-  if (xb > 0xFFFF0000ull) return fail(h, -7, "batch %d makes a %zu-byte activation: above the 4 GiB buffer-descriptor range, split the batch", nimg, xb);   // < TG_OOB (kernels_tapgemm.hip)
+  if (xb > 0xFFFF0000ull) return fail(h, -7, "batch %d makes a %zu-byte activation: above the 4 GiB buffer-descriptor range, split the batch", nimg, xb);   // <= TG_OOB_TAP (kernels_tapgemm.hip)
   p.x_bytes = (unsigned)xb;
   p.w_bytes = (unsigned)(L.w_floats * sizeof(float));
   const bool bf = S->bf16x3 && (epi.mode == TG_EPI_FWD ? h->opt.tg_bf16x3_fwd : h->opt.tg_bf16x3_bwd) != 0;
   p.variant = bf ? TG_VARIANT_BF16X3 : (h->opt.tg_variant_force >= 0 ? h->opt.tg_variant_force : (S->variant >= 0 ? S->variant : h->opt.tg_variant));
-  if (p.variant == 7 && L.Cin > 16384) p.variant = 2;   // schedule 7 keeps the channel chunk of a K-step in a scalar offset < 64 KB on top of TG_OOB
+  if (p.variant == TG_SCHED_AHEAD2 && L.Cin > 16384) p.variant = TG_SCHED_ROTATED;   // schedule 7 keeps the channel chunk of a K-step in a scalar offset < 64 KB on top of TG_OOB_TAP
   p.wsplit = nullptr;
   p.bf_sched = h->opt.tg_bf16x3_sched;
   p.noepi = h->opt.tg_noepi;

@@ -608,7 +608,7 @@ int ian_layer_head6_backward(ian_layer* l0, ian_layer* l1, ian_layer* l2, const 
     // (round 6: 480 -> 330 us per call at 128 images)
     {
       TgChoice c;
-      c.cfg = TG_128x128W8; c.max_steps = 0; c.variant = 7; c.fused = 0;
+      c.cfg = TG_128x128W8; c.max_steps = 0; c.variant = TG_SCHED_AHEAD2; c.fused = 0;
       l0->h6_helper->op.bwd.choice[(int)npix] = c;
     }
     std::vector<int> tp(ntaps);

@@ -15,22 +15,11 @@ bool apply_option(Options& o, const std::string& k, int value) {
   else if (k == "tg_prefer_nosplit") o.tg_prefer_nosplit = value;
   else if (k == "tg_nosplit_min_out") o.tg_nosplit_min_out = value;
   else if (k == "tg_variant") {
-#ifdef IAN_ABLATION
-    const bool ok = (value >= 0 && value <= 4) || (value >= 6 && value <= 8) || (value >= 10 && value <= 12) || (value >= 17 && value <= 23);
-#else
-    const bool ok = value == 1 || value == 2 || value == 4 || value == 6 || value == 7;   // 0 / 3 (negative results) and 10..12 (timing-only, wrong results)
-                                                              // exist in libian_ablation.so only (IAN_ABLATION_BUILD=1)
-#endif
-    if (!ok) return false;
+    if (!tg_schedule_valid(value)) return false;   // ian_internal.h: the negative results and the timing-only variants exist in libian_ablation.so only
     o.tg_variant = value;
   }
   else if (k == "tg_variant_force") {
-#ifdef IAN_ABLATION
-    const bool ok = value == -1 || (value >= 0 && value <= 4) || (value >= 6 && value <= 8) || (value >= 10 && value <= 12) || (value >= 17 && value <= 23);
-#else
-    const bool ok = value == -1 || value == 1 || value == 2 || value == 4 || value == 6 || value == 7;
-#endif
-    if (!ok) return false;
+    if (value != -1 && !tg_schedule_valid(value)) return false;
     o.tg_variant_force = value;
   }
   else if (k == "tg_noepi") {

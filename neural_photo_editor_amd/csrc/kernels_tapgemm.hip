@@ -22,6 +22,19 @@
 //     groups that share a weight slab dealt to one XCD (block b runs on XCD b%8) for L2 reuse;
 //   * epilogue fuses residual add, folded batch-norm scale/shift and the activation (forward), or
 //     the activation derivative (backward-data chain of the latent brush, API.py:59,64).
+//
+// K-loop schedules (enum TgSchedule in ian_internal.h; template parameter VAR, option tg_variant).  Same arithmetic, same summation
+// order -> bitwise identical results:
+//   1: loads -> kk 0,1 -> LDS stores -> kk 2,3 -> barrier         (stores hidden under the second half's MFMAs)
+//   2: rotated: the fragments of the last k group are read before the barrier and their MFMAs issued after it,
+//      covering the barrier, the next tile's global-load issue and the first fragment reads of the new buffer
+//   4: the loads of three K-steps in flight (register queue): for items of few K-steps with little MFMA work each (batch 1)
+//   6: 2 with every fragment read pinned where the source puts it
+//   7: 2 with the loads of two K-steps in flight and per-tap operand addressing -- the production schedule
+//   5 is not a schedule of tapgemm_kernel: it selects tapgemm_bf16x3_kernel (opt-in).
+// libian_ablation.so only (IAN_ABLATION): 0 loads -> 64 MFMAs -> LDS stores -> barrier (compiler-scheduled); 3 as 2 with LDS-DMA staging
+// into an XOR-swizzled unpadded image (no staging registers, no ds_write); 8 as 7 with three K-steps in flight; and the TIMING-ONLY
+// ablations 10 .. 12 (of 2) and 17 .. 23 (of 7), whose results are wrong.
 #include "ian_internal.h"
 
 namespace ian {
@@ -399,14 +412,32 @@ __device__ __forceinline__ void tg_store_stats(const TgParams& p, const TgItem& 
   (void)NW;
 }
 
-// VAR selects the K-loop schedule (same arithmetic, same summation order -> bitwise identical results):
-//   0: loads -> 64 MFMAs -> LDS stores -> barrier                (compiler-scheduled)
-//   1: loads -> kk 0,1 -> LDS stores -> kk 2,3 -> barrier         (stores hidden under the second half's MFMAs)
-//   3: as 2, but the tiles travel global -> LDS by LDS-DMA into an XOR-swizzled unpadded image (no staging registers,
-//      no ds_write)
-//   4: the loads of three K-steps in flight (register queue): for items of few K-steps with little MFMA work each (batch 1)
-//   2: rotated: the fragments of the last k group are read before the barrier and their MFMAs issued after it,
-//      covering the barrier, the next tile's global-load issue and the first fragment reads of the new buffer
+// Out-of-range vector offsets of the operand gather: the hardware returns zeros for them.  The host admits operand extents of at most
+// 0xFFFF0000 bytes (ian_rt_exec.inc); each constant must stay beyond that, without wrapping, under the largest offset its addressing
+// form adds on top:
+constexpr unsigned TG_OOB_STEP = 0xFFFFFFF0u;    // per-step form (schedules 0 1 2 3 4 6 8): the channel chunk is part of the vector offset; one 16-byte load, immediate 0
+constexpr unsigned TG_OOB_STEP16 = 0xFFFFFFE0u;  // per-step form of tapgemm_bf16x3_kernel: two 16-byte loads per row, immediates 0 and 16
+constexpr unsigned TG_OOB_TAP = 0xFFFF0000u;     // per-tap form (schedule 7): + the channel chunk as a scalar offset < 64 KB (Cin <= 16384, ian_rt_exec.inc)
+
+// the final K-step of the rotated schedules (2 6 7 8): k group 0 is in (av, bv) already.  PIN: schedule 6
+template <int FM, int FN, bool PIN>
+__device__ __forceinline__ void tg_last_step(const float* a_s, const float* b_s, float4 (&av)[FM], float4 (&bv)[FN], float4 (&aw)[FM], float4 (&bw)[FN],
+                                             f32x16 (&acc)[FM][FN]) {
+  tg_frag_load<FM, FN>(a_s, b_s, 1, aw, bw);
+  if (PIN) __builtin_amdgcn_sched_barrier(0);
+  tg_frag_mfma<FM, FN>(av, bv, acc);
+  if (PIN) __builtin_amdgcn_sched_barrier(0);
+  tg_frag_load<FM, FN>(a_s, b_s, 2, av, bv);
+  if (PIN) __builtin_amdgcn_sched_barrier(0);
+  tg_frag_mfma<FM, FN>(aw, bw, acc);
+  if (PIN) __builtin_amdgcn_sched_barrier(0);
+  tg_frag_load<FM, FN>(a_s, b_s, 3, aw, bw);
+  if (PIN) __builtin_amdgcn_sched_barrier(0);
+  tg_frag_mfma<FM, FN>(av, bv, acc);
+  tg_frag_mfma<FM, FN>(aw, bw, acc);
+}
+
+// VAR selects the K-loop schedule (listed at the head of this file).
 // STATS: the instantiation whose epilogue also produces the stored tensor's batch statistics (TgStats; training step only).  A
 // separate kernel so that the inference launches keep their register budget: the statistics epilogue holds 16 rows of
 // addresses and operands per lane and raised the 64x64 tile from 63 to 114 VGPRs, the 4-wave 128x128 tile from 148 to 236.
@@ -489,7 +520,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);                 \
-      RA[j] = buf_load4(xrsrc, ok ? a_off[j] + doff : 0xFFFFFFF0u, 0);                                   \
+      RA[j] = buf_load4(xrsrc, ok ? a_off[j] + doff : TG_OOB_STEP, 0);                                   \
     }                                                                                                    \
     const unsigned wsoff = w_cls + (unsigned)tap * slab_bytes + (unsigned)(cstep << 7);                         \
     _Pragma("unroll") for (int j = 0; j < B_CH; ++j) RB[j] = buf_load4(wrsrc, w_row + j * w_rstep, wsoff); \
@@ -510,10 +541,10 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = live_ & ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);         \
-      RA[j] = buf_load4(xrsrc, ok ? a_off[j] + doff : 0xFFFFFFF0u, 0);                                   \
+      RA[j] = buf_load4(xrsrc, ok ? a_off[j] + doff : TG_OOB_STEP, 0);                                   \
     }                                                                                                    \
     const unsigned wsoff = live_ ? w_cls + (unsigned)tap * slab_bytes + (unsigned)(cstep << 7) : 0u;     \
-    _Pragma("unroll") for (int j = 0; j < B_CH; ++j) RB[j] = buf_load4(wrsrc, live_ ? w_row + j * w_rstep : 0xFFFFFFF0u, wsoff); \
+    _Pragma("unroll") for (int j = 0; j < B_CH; ++j) RB[j] = buf_load4(wrsrc, live_ ? w_row + j * w_rstep : TG_OOB_STEP, wsoff); \
     if (++cstep == kpt) {                                                                                \
       cstep = 0;                                                                                         \
       ++tap;                                                                                             \
@@ -551,7 +582,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);                 \
-      tg_dma16(xrsrc, As3 + ((buf) * BM + wave * 8 + RS * j) * 32, ok ? a_off[j] + doff : 0xFFFFFFF0u, 0);  \
+      tg_dma16(xrsrc, As3 + ((buf) * BM + wave * 8 + RS * j) * 32, ok ? a_off[j] + doff : TG_OOB_STEP, 0);  \
     }                                                                                                    \
     const unsigned wsoff = w_cls + (unsigned)tap * slab_bytes + (unsigned)(cstep << 7);                  \
     _Pragma("unroll") for (int j = 0; j < B_CH; ++j)                                                     \
@@ -598,24 +629,24 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
       tg_frag_mfma<FM, FN>(aw, bw, acc);
     }
 #undef TG_DMA_TILE
-  } else if (VAR != 4 && VAR != 7 && VAR != 8 && !(VAR >= 17 && VAR <= 25)) {
+  } else if (VAR != 4 && VAR != 7 && VAR != 8 && !(VAR >= TG_ABL7_FIRST && VAR <= TG_ABL7_LAST)) {
   TG_LOAD_TILE_FIRST();
   TG_STORE_TILE(0);
   __syncthreads();
   }
   if (DMA) {
-  } else if (VAR == 7 || (VAR >= 17 && VAR <= 25)) {
+  } else if (VAR == 7 || (VAR >= TG_ABL7_FIRST && VAR <= TG_ABL7_LAST)) {
     // ---- VAR 7 (round 6) = the production schedule: the rotated schedule of VAR 2 with
     //  (a) the loads of TWO K-steps in flight.  In VAR 2 the tile of step s+1 is requested at the top of step s and written to LDS
     //      after the second k group: the barrier makes every wave of the workgroup wait for the slowest load.  Here the tile written
     //      in step s was requested in step s-1, into the second of two staging register sets (the loop is unrolled by two so that LDS
     //      buffer and register set are compile-time constants); steps that request nothing are peeled off the end, so no load is
     //      ever issued past the item;
-    //  (b) NO vector arithmetic per K-step.  Timing-only ablations of (a) (17 .. 25 below, scripts/exp/tg_ablate7.py) put 5.5 % of the
+    //  (b) NO vector arithmetic per K-step.  Timing-only ablations of (a) (17 .. 23 below, scripts/exp/tg_ablate7.py) put 5.5 % of the
     //      batch-64 step on the tap fetch + the ~20 VALU instructions that built the load offsets every K-step -- more than the loads
     //      themselves (2.4 %), the LDS stores (1.5 %), the barrier (0.2 %) or the fragment reads (0): a VALU instruction of ANY wave
     //      takes its issue cycles from the matrix pipe of its SIMD.  The bounds test and pixel offset of a tile row depend on the TAP
-    //      only, so they are computed once per tap into a_vo[] (kpt = Cin / 32 K-steps apart; an out-of-image row gets TG_OOB), and
+    //      only, so they are computed once per tap into a_vo[] (kpt = Cin / 32 K-steps apart; an out-of-image row gets TG_OOB_TAP), and
     //      the channel chunk of the step travels in the scalar offset of the buffer instruction.
     // VAR 17 .. 23 (libian_ablation.so): TIMING-ONLY ablations (results are wrong) -- without the global loads and LDS stores (17), without
     // the barrier (18), without the fragment reads (19), 17 + 18 (20), all three (21), loads issued and awaited but nothing written to LDS
@@ -624,10 +655,9 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
     // Same MFMA order -> same bits as 1 / 2 / 4 / 6.
     constexpr bool NOLOAD = VAR == 17 || VAR == 20 || VAR == 21 || VAR == 23, NOBAR = VAR == 18 || VAR == 20 || VAR == 21, NOFRAG = VAR == 19 || VAR == 21;
     constexpr bool NOSTORE = VAR == 17 || VAR == 20 || VAR == 21 || VAR == 22, TOUCH = VAR == 22;
-    constexpr unsigned TG_OOB = 0xFFFF0000u;          // + a scalar offset < 64 KB stays beyond every extent the host admits (ian_rt_exec.inc)
     float4 ra1[A_CH], rb1[B_CH];
     float4 av[FM], bv[FN], aw[FM], bw[FN];
-    unsigned a_vo[A_CH];                              // byte offset of (tile row j, current tap, channel 0), or TG_OOB
+    unsigned a_vo[A_CH];                              // byte offset of (tile row j, current tap, channel 0), or TG_OOB_TAP
     unsigned w_so = 0;                                // byte offset of the current tap's weight slab (wave-uniform)
 #define TG_TAP_SETUP() TG_TAP_SETUP_TP(p.taps[cl.tap0 + min(tap, cl.ntaps - 1)])
 #define TG_TAP_SETUP_TP(TP)                                                                              \
@@ -637,7 +667,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);                 \
-      a_vo[j] = ok ? a_off[j] + toff : TG_OOB;                                                           \
+      a_vo[j] = ok ? a_off[j] + toff : TG_OOB_TAP;                                                       \
     }                                                                                                    \
     w_so = w_cls + (unsigned)tap * slab_bytes;                                                           \
   }
@@ -699,17 +729,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
 #undef TG_LOAD7
 #undef TG_TAP_SETUP
 #undef TG_TAP_SETUP_TP
-    {
-      const float* a_s = a_base + cur * BM * TG_LDS;
-      const float* b_s = b_base + cur * BN * TG_LDS;
-      tg_frag_load<FM, FN>(a_s, b_s, 1, aw, bw);
-      tg_frag_mfma<FM, FN>(av, bv, acc);
-      tg_frag_load<FM, FN>(a_s, b_s, 2, av, bv);
-      tg_frag_mfma<FM, FN>(aw, bw, acc);
-      tg_frag_load<FM, FN>(a_s, b_s, 3, aw, bw);
-      tg_frag_mfma<FM, FN>(av, bv, acc);
-      tg_frag_mfma<FM, FN>(aw, bw, acc);
-    }
+    tg_last_step<FM, FN, false>(a_base + cur * BM * TG_LDS, b_base + cur * BN * TG_LDS, av, bv, aw, bw, acc);
   } else if (VAR == 8) {
     // ---- VAR 8 (round 6): VAR 7 with the loads of THREE K-steps in flight (three staging sets; six steps per trip so that buffer
     // index and register set stay compile-time constants).  For the tiles whose K-step is short against an L2 / Infinity Cache
@@ -773,17 +793,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
       }
     }
 #undef TG_DSTEP
-    {
-      const float* a_s = a_base + cur * BM * TG_LDS;
-      const float* b_s = b_base + cur * BN * TG_LDS;
-      tg_frag_load<FM, FN>(a_s, b_s, 1, aw, bw);
-      tg_frag_mfma<FM, FN>(av, bv, acc);
-      tg_frag_load<FM, FN>(a_s, b_s, 2, av, bv);
-      tg_frag_mfma<FM, FN>(aw, bw, acc);
-      tg_frag_load<FM, FN>(a_s, b_s, 3, aw, bw);
-      tg_frag_mfma<FM, FN>(av, bv, acc);
-      tg_frag_mfma<FM, FN>(aw, bw, acc);
-    }
+    tg_last_step<FM, FN, false>(a_base + cur * BM * TG_LDS, b_base + cur * BN * TG_LDS, av, bv, aw, bw, acc);
   } else if (VAR == 4) {
     // ---- VAR 4: register queue three tiles deep.  With few images an item is a handful of K-steps whose 16-64 MFMAs
     // (0.4-1.7 us) cannot cover a 1-2 us weight fetch from the Infinity Cache: the one-step prefetch of the other schedules
@@ -889,22 +899,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
       tg_frag_mfma<FM, FN>(aw, bw, acc);   // kk 3 of the previous buffer: covers the new buffer's first reads
       TG_PIN();
     }
-    {
-      const float* a_s = a_base + cur * BM * TG_LDS;
-      const float* b_s = b_base + cur * BN * TG_LDS;
-      tg_frag_load<FM, FN>(a_s, b_s, 1, aw, bw);
-      TG_PIN();
-      tg_frag_mfma<FM, FN>(av, bv, acc);
-      TG_PIN();
-      tg_frag_load<FM, FN>(a_s, b_s, 2, av, bv);
-      TG_PIN();
-      tg_frag_mfma<FM, FN>(aw, bw, acc);
-      TG_PIN();
-      tg_frag_load<FM, FN>(a_s, b_s, 3, aw, bw);
-      TG_PIN();
-      tg_frag_mfma<FM, FN>(av, bv, acc);
-      tg_frag_mfma<FM, FN>(aw, bw, acc);
-    }
+    tg_last_step<FM, FN, PIN>(a_base + cur * BM * TG_LDS, b_base + cur * BN * TG_LDS, av, bv, aw, bw, acc);
 #undef TG_PIN
   }
 #undef TG_LOAD_TILE
@@ -1183,14 +1178,14 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_bf
     for (int j = 0; j < A_CH; ++j) {
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;
       const bool ok = live & ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);
-      const unsigned o = ok ? a_off[j] + doff : 0xFFFFFFE0u;
+      const unsigned o = ok ? a_off[j] + doff : TG_OOB_STEP16;
       R.a[2 * j] = buf_load4(xrsrc, o, 0);
       R.a[2 * j + 1] = buf_load4(xrsrc, o, 16);
     }
     const unsigned wsoff = w_cls + (unsigned)tap * slab_bytes + (unsigned)(cstep << 5) * WB;
 #pragma unroll
     for (int j = 0; j < B_CH; ++j) {
-      const unsigned o = live ? w_row + j * w_rstep : 0xFFFFFFE0u;
+      const unsigned o = live ? w_row + j * w_rstep : TG_OOB_STEP16;
       if (BSPLIT) {
         R.b[2 * j] = buf_load4(wrsrc, o, wsoff);
         R.b[2 * j + 1] = buf_load4(wrsrc, o, live ? wsoff + w_lo : 0);
@@ -1388,18 +1383,22 @@ hipError_t launch_wsplit(const float* w, unsigned short* out, long long n, hipSt
   return hipGetLastError();
 }
 
-template <int BM, int BN, int WM, int WN, bool BSPLIT, int SCHED>
-static hipError_t launch_bf16x3_v(const TgParams& p, int nitems, hipStream_t s) {
-  static bool attr_set = false;
-  const size_t lds = (size_t)2 * 2 * (BM + BN) * TGB_ROWB;
-  auto k = tapgemm_bf16x3_kernel<BM, BN, WM, WN, BSPLIT, SCHED>;
+// first launch of a kernel: admit its dynamic LDS size; then launch
+template <class K>
+static hipError_t tg_launch(K k, bool& attr_set, size_t lds, int nthreads, const TgParams& p, int nitems, hipStream_t s) {
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
-  hipLaunchKernelGGL(k, dim3(nitems), dim3(64 * WM * WN), lds, s, p);
+  hipLaunchKernelGGL(k, dim3(nitems), dim3(nthreads), lds, s, p);
   return hipGetLastError();
+}
+
+template <int BM, int BN, int WM, int WN, bool BSPLIT, int SCHED>
+static hipError_t launch_bf16x3_v(const TgParams& p, int nitems, hipStream_t s) {
+  static bool attr_set = false;
+  return tg_launch(tapgemm_bf16x3_kernel<BM, BN, WM, WN, BSPLIT, SCHED>, attr_set, (size_t)2 * 2 * (BM + BN) * TGB_ROWB, 64 * WM * WN, p, nitems, s);
 }
 template <int BM, int BN, int WM, int WN>
 static hipError_t launch_bf16x3(const TgParams& p, int nitems, hipStream_t s) {
@@ -1501,16 +1500,7 @@ __global__ __launch_bounds__(256) void tapgemm_reduce_kernel(const TgReduceParam
 template <int BM, int BN, int WM, int WN, int VAR, bool STATS = false>
 static hipError_t launch_var(const TgParams& p, int nitems, hipStream_t s) {
   static bool attr_set = false;
-  const size_t lds = (size_t)2 * (BM + BN) * TG_LDS * sizeof(float);
-  auto k = tapgemm_kernel<BM, BN, WM, WN, VAR, STATS>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k, dim3(nitems), dim3(64 * WM * WN), lds, s, p);
-  return hipGetLastError();
+  return tg_launch(tapgemm_kernel<BM, BN, WM, WN, VAR, STATS>, attr_set, (size_t)2 * (BM + BN) * TG_LDS * sizeof(float), 64 * WM * WN, p, nitems, s);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -1518,8 +1508,8 @@ static hipError_t launch_cfg(const TgParams& p, int nitems, hipStream_t s) {
   if (p.epi.st.mode) {   // == tg_stats_supported(cfg, variant) on the host: the register-staged schedules of the tiles up to 128 x 128
 #ifdef IAN_ABLATION      // libian_ablation.so only: measured 4 % SLOWER per training update than the colstats passes
     if constexpr (BM * BN <= 128 * 128) {
-      if (p.variant == 1) return launch_var<BM, BN, WM, WN, 1, true>(p, nitems, s);
-      if (p.variant == 2) return launch_var<BM, BN, WM, WN, 2, true>(p, nitems, s);
+      if (p.variant == TG_SCHED_SPLIT) return launch_var<BM, BN, WM, WN, TG_SCHED_SPLIT, true>(p, nitems, s);
+      if (p.variant == TG_SCHED_ROTATED) return launch_var<BM, BN, WM, WN, TG_SCHED_ROTATED, true>(p, nitems, s);
     }
 #endif
     return hipErrorInvalidValue;
@@ -1528,31 +1518,35 @@ static hipError_t launch_cfg(const TgParams& p, int nitems, hipStream_t s) {
     case TG_VARIANT_BF16X3:   // opt-in: split-bf16 operands, 3 MFMAs per product; tiles whose rows fill whole staging passes only
       if constexpr (BM % (16 * WM * WN) == 0 && BN % (16 * WM * WN) == 0 && BM * BN <= 128 * 128) return launch_bf16x3<BM, BN, WM, WN>(p, nitems, s);   // == tg_bf16x3_supported(cfg)
       else return hipErrorInvalidValue;
-    // the three production schedules (autotune candidates): 1 and 2 register-staged, 4 = three K-steps of loads in flight
-    case 1: return launch_var<BM, BN, WM, WN, 1>(p, nitems, s);
-    case 2: return launch_var<BM, BN, WM, WN, 2>(p, nitems, s);
-    case 4: return launch_var<BM, BN, WM, WN, 4>(p, nitems, s);
-    case 6: return launch_var<BM, BN, WM, WN, 6>(p, nitems, s);
-    case 7: return launch_var<BM, BN, WM, WN, 7>(p, nitems, s);
+    // the production schedules (autotune candidates): tg_schedule_shipped, ian_internal.h
+    case TG_SCHED_SPLIT: return launch_var<BM, BN, WM, WN, TG_SCHED_SPLIT>(p, nitems, s);
+    case TG_SCHED_ROTATED: return launch_var<BM, BN, WM, WN, TG_SCHED_ROTATED>(p, nitems, s);
+    case TG_SCHED_QUEUE3: return launch_var<BM, BN, WM, WN, TG_SCHED_QUEUE3>(p, nitems, s);
+    case TG_SCHED_ROTATED_PIN: return launch_var<BM, BN, WM, WN, TG_SCHED_ROTATED_PIN>(p, nitems, s);
+    case TG_SCHED_AHEAD2: return launch_var<BM, BN, WM, WN, TG_SCHED_AHEAD2>(p, nitems, s);
 #ifdef IAN_ABLATION   // libian_ablation.so only (IAN_ABLATION_BUILD=1; tests/test_gpu_ablation.py, scripts/ablate_tapgemm.sh):
                       // negative results kept runnable -- schedule 0 (compiler-scheduled) and 3 (LDS-DMA staging, measured 5 %
-                      // slower) give the SAME bits as 1 / 2 / 4; 10..12 are timing-only ablations whose RESULTS ARE WRONG.
-                      // The shipped library contains none of them and rejects the option values.
-    case 0: return launch_var<BM, BN, WM, WN, 0>(p, nitems, s);
-    case 8: if constexpr (BM * BN <= 128 * 64) return launch_var<BM, BN, WM, WN, 8>(p, nitems, s); else return launch_var<BM, BN, WM, WN, 7>(p, nitems, s);   // three K-steps in flight (small tiles): measured no better than 7
-    case 17: return launch_var<BM, BN, WM, WN, 17>(p, nitems, s);   // 17 .. 21: timing-only ablations of schedule 7 (WRONG results)
+                      // slower) give the SAME bits as 1 / 2 / 4; 10..12 and 17..23 are timing-only ablations whose RESULTS ARE WRONG.
+                      // The shipped library contains none of them and rejects the option values (tg_schedule_valid).
+    case TG_SCHED_PLAIN: return launch_var<BM, BN, WM, WN, TG_SCHED_PLAIN>(p, nitems, s);
+    case TG_SCHED_DMA: return launch_var<BM, BN, WM, WN, TG_SCHED_DMA>(p, nitems, s);
+    case TG_SCHED_AHEAD3:   // three K-steps in flight (small tiles): measured no better than 7
+      if constexpr (BM * BN <= 128 * 64) return launch_var<BM, BN, WM, WN, TG_SCHED_AHEAD3>(p, nitems, s);
+      else return launch_var<BM, BN, WM, WN, TG_SCHED_AHEAD2>(p, nitems, s);
+    case 10: if (BM == 64 && BN == 64) return launch_var<64, 64, 2, 2, 10>(p, nitems, s); return launch_var<BM, BN, WM, WN, TG_SCHED_ROTATED>(p, nitems, s);
+    case 11: if (BM == 64 && BN == 64) return launch_var<64, 64, 2, 2, 11>(p, nitems, s); return launch_var<BM, BN, WM, WN, TG_SCHED_ROTATED>(p, nitems, s);
+    case 12: if (BM == 64 && BN == 64) return launch_var<64, 64, 2, 2, 12>(p, nitems, s); return launch_var<BM, BN, WM, WN, TG_SCHED_ROTATED>(p, nitems, s);
+    case 17: return launch_var<BM, BN, WM, WN, 17>(p, nitems, s);   // 17 .. 23: timing-only ablations of schedule 7
     case 18: return launch_var<BM, BN, WM, WN, 18>(p, nitems, s);
     case 19: return launch_var<BM, BN, WM, WN, 19>(p, nitems, s);
     case 20: return launch_var<BM, BN, WM, WN, 20>(p, nitems, s);
     case 21: return launch_var<BM, BN, WM, WN, 21>(p, nitems, s);
     case 22: return launch_var<BM, BN, WM, WN, 22>(p, nitems, s);
     case 23: return launch_var<BM, BN, WM, WN, 23>(p, nitems, s);
-    case 3: return launch_var<BM, BN, WM, WN, 3>(p, nitems, s);
-    case 10: if (BM == 64 && BN == 64) return launch_var<64, 64, 2, 2, 10>(p, nitems, s); return launch_var<BM, BN, WM, WN, 2>(p, nitems, s);
-    case 11: if (BM == 64 && BN == 64) return launch_var<64, 64, 2, 2, 11>(p, nitems, s); return launch_var<BM, BN, WM, WN, 2>(p, nitems, s);
-    case 12: if (BM == 64 && BN == 64) return launch_var<64, 64, 2, 2, 12>(p, nitems, s); return launch_var<BM, BN, WM, WN, 2>(p, nitems, s);
 #endif
-    default: return hipErrorInvalidValue;   // unknown K-loop schedule: refuse rather than silently pick one
+    default:   // every number that tg_schedule_valid (ian_internal.h) admits has its case above: refuse the rest rather than silently pick a schedule
+      static_assert(TG_ABL2_FIRST == 10 && TG_ABL2_LAST == 12 && TG_ABL7_FIRST == 17 && TG_ABL7_LAST == 23, "the timing-only cases above");
+      return hipErrorInvalidValue;
   }
 }
 

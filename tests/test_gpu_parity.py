@@ -105,10 +105,10 @@ def test_every_tile_config_and_split_policy(cfg):
     try:
         from neural_photo_editor_amd.lib import is_ablation_build
         outs = []
-        # K-loop schedules: 1 / 2 / 4 are the product's (autotune candidates); 0 (compiler-scheduled) and 3 (LDS-DMA staging,
-        # measured slower) exist in libian_ablation.so only (tests/test_gpu_ablation.py runs this test against it).
+        # K-loop schedules: 1 / 2 / 4 / 6 / 7 are the product's (autotune candidates); 0 (compiler-scheduled), 3 (LDS-DMA staging,
+        # measured slower) and 8 exist in libian_ablation.so only (tests/test_gpu_ablation.py runs this test against it).
         # Same arithmetic in the same order -> identical bits.
-        for var in ((0, 1, 2, 3, 4, 7, 8) if is_ablation_build() else (1, 2, 4, 7)):
+        for var in ((0, 1, 2, 3, 4, 6, 7, 8) if is_ablation_build() else (1, 2, 4, 6, 7)):
             m.handle.set_option("tg_variant", var)
             m.handle.set_option("tg_cfg", cfg)
             m.handle.set_option("tg_split", 1)
@@ -208,6 +208,28 @@ def test_decoder_forward_cache_is_transparent():
     assert np.array_equal(m.imgradRGB(26, 26, 30, 30, rgb, z1), cold1) and np.array_equal(m.imgradRGB(26, 26, 30, 30, rgb2, z1), a)
     m.sample_at(np.concatenate([z1, z2]))                                    # batch 2: not cacheable
     assert np.array_equal(m.imgrad(26, 26, 30, 30, z1), m.imgrad(26, 26, 30, 30, z1.copy()))
+
+
+@pytest.mark.parametrize("arch", O.ARCHS)
+def test_fast_epilogue_equals_the_general_form(arch):
+    """tg_fast_epilogue = 1 (the default: 32-bit buffer-descriptor stores, scale / shift once per column) against the general
+    tg_store form, bit for bit.  3 images: ragged M on enc_conv3 / enc_conv4 (192 and 48 rows), full tiles elsewhere, the
+    stride-2 deconv classes; full IAN supplies `res`, the brush gradient the BWD mode with `yfwd`.  IAN_simple's dense layers
+    (scale_period != 0) take the general path under both settings."""
+    m, _, _ = model_for(arch)
+    x = O.make_images(3, seed=7)
+    z = O.make_latents(1, seed=31)
+    out = {}
+    os.environ["IAN_NO_DEC_CACHE"] = "1"
+    try:
+        for fast in (0, 1):
+            m.handle.set_option("tg_fast_epilogue", fast)
+            out[fast] = (m.reconstruct(x), m.imgradRGB(10, 20, 30, 40, red_rgb(), z))
+    finally:
+        del os.environ["IAN_NO_DEC_CACHE"]
+        m.handle.set_option("tg_fast_epilogue", 1)
+    assert np.array_equal(out[0][0], out[1][0])
+    assert np.array_equal(out[0][1], out[1][1])
 
 
 def test_device_pointers_equal_host_pointers():
