@@ -358,6 +358,52 @@ int ian_sessions_set_local(ian_handle* h, const double* falloff64, double dampen
    outside 1..256, an id outside the pool, a session not opened, an id given twice, flags outside 0..3. */
 int ian_session_local(ian_handle* h, int32_t n, const int32_t* ids, const int32_t* flags, void* stream);
 
+/* ---- undo and redo: one history per session, on the device ----
+   Every brush event overwrites the session's Z, UMASK, IM and FIELD in place.  A pool with the reservation below keeps, per session, a
+   ring of saved states in device memory; the host keeps only a list length and a cursor per session.  A saved state is the session's
+   Z row and, in a pool that had the local reservation when the history was reserved, its UMASK row.  IM, FIELD, FIELD_KIND and the
+   canvas are not saved: they are a function of (Z, UMASK, RECON, ERROR, mode, LOCAL) and are recomputed on restore.
+   Per session: entries E[0..len-1], a cursor c (0 <= c <= len; c == len: the live state is not in the list).
+     mark     (ian_session_mark, "a stroke begins"): the entries after the cursor go; with `depth` entries the oldest goes; the live
+              state becomes the last entry, c = len.
+     undo k   1 <= k <= c: from the tip (c == len) the live state is first saved behind the list, so that redo can come back to it;
+              c -= k, live := E[c].
+     redo k   1 <= k <= len - 1 - c: c += k, live := E[c].
+     edited   any other call that writes Z without clearing (ian_session_brush, _brush_view, ian_session_set_latent with as_sample = 0)
+              with c < len: the entries after E[c] go and c = len; the state the user came back to stays an undo target (the oldest
+              entry goes when that makes depth + 1 of them).
+     clear    len = c = 0: every call that rewrites RECON / ERROR / GIM or zeroes UMASK (ian_session_open with all three sources,
+              ian_session_open_hires, ian_session_set_latent with as_sample = 1, ian_session_local), and a change of the depth.
+   So `depth` is the largest number of steps that can be undone.  Restoring a state means, in one submission: UMASK and Z := the saved
+   rows; x = the decoder at Z at batch n exactly as ian_session_set_latent runs it; on a photo-mode session the blend of
+   ian_session_set_latent(as_sample = 0) -- the session's LOCAL flags, the restored UMASK, no footprint -- but stored:
+   IM := shown := blend, FIELD := the edit field, kind 0; on a sample-mode session shown = uint8(from_tanh(x)), IM untouched,
+   FIELD := x, kind 1.  After an undo IM is therefore the blend at the restored latent, even if the last thing displayed in that
+   state was a lighten event's plain sample.  Without the reservation no call launches, moves or computes anything it did not before. */
+
+/* depth 1..64 allocates the rings for every session of the pool (0 frees them); every history starts empty.  Needs
+   ian_sessions_reserve first (-6 otherwise).  Synchronises the device.  The same depth again changes nothing; another depth builds new
+   rings and clears every history.  ian_sessions_reserve(capacity) afterwards resizes the rings with the rest: the sessions whose ids
+   remain keep their histories.  An allocation failure (-2) leaves the old pool intact.  While a history is reserved,
+   ian_sessions_reserve_local with another `on` than the pool has returns -6: free the history first.
+   (depth + 1) * (4 * num_latents + 32 768) bytes per session with the local reservation, (depth + 1) * 4 * num_latents without: depth
+   16 and 100 latents are 563 856 or 6 800 bytes. */
+int ian_sessions_reserve_history(ian_handle* h, int32_t depth);
+/* Saves the live state of n opened sessions as a new last entry ("mark" above): one launch.  ids is a host array.  Like
+   ian_session_read it leaves the decoder's resident activations and the residency of ian_session_brush alone.  -6 without the
+   reservation; -7, naming the item, before anything is enqueued: n outside 1..256, an id outside the pool, a session not opened, an
+   id given twice. */
+int ian_session_mark(ian_handle* h, int32_t n, const int32_t* ids, void* stream);
+/* steps[i] > 0 undoes that many marks on session ids[i], < 0 redoes as many (steps NULL: one undo each); one submission on the
+   caller's stream.  shown u8[n,3,64,64] (host or device) or NULL receives what the canvases show.  ids and steps are host arrays.
+   -6: no history reservation, ian_sessions_set_blend not called, a session with LOCAL flags but no falloff table.  -7, naming the item,
+   before anything is enqueued or any counter moves: n outside 1..256, an id outside the pool, a session not opened, an id given
+   twice, steps[i] == 0, more undo or redo steps than the session has (the message gives the count it has). */
+int ian_session_undo(ian_handle* h, int32_t n, const int32_t* ids, const int32_t* steps, uint8_t* shown, void* stream);
+/* out[0] = the pool's depth, out[1] = how many steps ian_session_undo can undo on this opened session now, out[2] = how many it can
+   redo.  Host only: no device state is touched.  -6 without the reservation, -7 for an id outside the pool or not opened. */
+int ian_session_history(ian_handle* h, int32_t id, int32_t out[3]);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -223,6 +223,24 @@ def pack_session_local(ids, local=True, dampen=False, flags=None, capacity=None,
     return idv, np.ascontiguousarray(f, np.int32)
 
 
+def pack_session_undo(ids, steps=1, capacity=None, opened=None):
+    """Python arguments of ian_session_undo -> (ids int32 (n,), steps int32 (n,)), validated before the library sees anything.
+    steps is one integer for all or one per session: > 0 undoes that many marks, < 0 redoes as many; 0, a non-integer and more than
+    the largest depth (64) either way are refused.  Whether a session HAS that many steps only the library knows.  capacity / opened
+    (a container of opened ids), when given, bound and vet the ids."""
+    idv = check_session_ids(ids, capacity, opened)
+    n = len(idv)
+    a = np.asarray(steps)
+    if a.ndim == 0:
+        a = np.tile(a, n)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("steps must be one integer or %d integers, got %s %s" % (n, a.dtype, a.shape))
+    for i, t in enumerate(int(t) for t in a):
+        if t == 0 or not -64 <= t <= 64:
+            raise ValueError("item %d: steps %d (1..64 undoes, -1..-64 redoes)" % (i, t))
+    return idv, np.ascontiguousarray(a, np.int32)
+
+
 class EditSessions:
     """Device-resident edit sessions of one model (ian_session_*, include/ian.h): the state NPE.py keeps in host globals per
     editor (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) lives in device memory under a caller-chosen id in 0..capacity-1.  A call takes
@@ -234,7 +252,9 @@ class EditSessions:
         open_hires  infer from the full-size photo     render  windows of the edited picture at full size
         brush_view / paint(view=) / scroll(view=)      the event and its window in one submission
     Local edits (NPE.py's unimplemented USER_MASK, gk and dampen): reserve_local() keeps a user mask per session;
-        set_local(ids, local, dampen)  from then on a paint on those sessions changes the photo only around the strokes made since"""
+        set_local(ids, local, dampen)  from then on a paint on those sessions changes the photo only around the strokes made since
+    Undo (no counterpart in NPE.py): reserve_history(depth) keeps a ring of saved latents (and user masks) per session on the device;
+        mark(ids)  a stroke begins     undo(ids, steps) / redo(ids, steps)  back and forth -> shown     history(sid)  what is possible"""
 
     def __init__(self, handle, capacity, zdim, sigma=0.7):
         from . import npe_ops
@@ -243,6 +263,7 @@ class EditSessions:
         self.capacity = 0
         self.scale = 0                  # full-resolution reservation: photos are (3, 64*scale, 64*scale); 0 = none
         self.local = False              # local reservation: UMASK and the LOCAL flags per session
+        self.history_depth = 0          # history reservation: how many marks a session can undo; 0 = none
         self._opened = set()
         self._sourced = set()           # ids whose SRC holds a photo
         self.reserve(capacity)
@@ -295,6 +316,54 @@ class EditSessions:
             raise ValueError("the pool has no local reservation (reserve_local)")
         idv, f = pack_session_local(ids, local, dampen, flags, self.capacity, self._opened)
         self._h.session_local(idv, f)
+
+    def reserve_history(self, depth=16):
+        """Keep up to `depth` (1..64) undoable states per session in device memory: (depth + 1) * (4 * zdim [+ 32 768 with the local
+        reservation]) bytes each; 0 frees them.  Another depth clears every history.  Reserve the local edits first: while a history
+        exists the library refuses to add or free them."""
+        depth = int(depth)
+        if not 0 <= depth <= 64:
+            raise ValueError("depth must be in 0..64, got %d" % depth)
+        self._h.sessions_reserve_history(depth)
+        self.history_depth = depth
+
+    def _need_history(self):
+        if not self.history_depth:
+            raise ValueError("the pool has no history reservation (reserve_history)")
+
+    def mark(self, ids):
+        """A stroke begins: the sessions' current states become undo targets (their redo tails go)."""
+        self._need_history()
+        self._h.session_mark(self._ids(ids, True))
+
+    def undo(self, ids, steps=1):
+        """Back `steps` marks (one value for all or one per session) -> what the canvases show, uint8 (n,3,64,64): the stored blend
+        at the restored latent (photo mode) or the sample (sample mode)."""
+        self._need_history()
+        idv, st = pack_session_undo(ids, steps, self.capacity, self._opened)
+        shown = np.empty((len(idv), 3, 64, 64), np.uint8)
+        self._h.session_undo(idv, st, shown)
+        return shown
+
+    def redo(self, ids, steps=1):
+        """Forward again `steps` states that undo went back over -> shown, as undo."""
+        self._need_history()
+        idv, st = pack_session_undo(ids, steps, self.capacity, self._opened)
+        shown = np.empty((len(idv), 3, 64, 64), np.uint8)
+        self._h.session_undo(idv, -st, shown)
+        return shown
+
+    def history(self, sid):
+        """-> {"depth", "undo", "redo"}: the pool's depth and how many steps undo / redo can take on this session now.  The library
+        owns the counters; nothing touches the device."""
+        self._need_history()
+        sid = int(sid)
+        if not 0 <= sid < self.capacity:
+            raise ValueError("session %d outside the pool (capacity %d)" % (sid, self.capacity))
+        if sid not in self._opened:
+            raise ValueError("session %d has not been opened" % sid)
+        depth, undo, redo = self._h.session_history(sid)
+        return {"depth": depth, "undo": undo, "redo": redo}
 
     def _ids(self, ids, need_opened):
         return check_session_ids(ids, self.capacity, self._opened if need_opened else None)
@@ -433,6 +502,7 @@ class EditSessions:
             self.capacity = 0
             self.scale = 0
             self.local = False
+            self.history_depth = 0
             self._opened = set()
             self._sourced = set()
 

@@ -400,6 +400,15 @@ struct SessionPool {
   double* umask;          // UMASK f64[capacity][64*64]: where the user has brushed (npe_ops.umask_paint)
   int* local;             // LOCAL int[capacity]: bit 0 = the blend is masked by UMASK, bit 1 = dampen
 };
+// undo history (ian_sessions_reserve_history): a ring of depth + 1 saved states per session, slot k of session id in row
+// id * (depth + 1) + k of each array.  All nullptr / 0 without that reservation.  Beside the pool, not in it: SessionPool goes to every
+// session kernel by value, and a member more would move the arguments of all of them; only the two history kernels take this one.
+// The runtime manages these pointers through SESS_COLUMNS like the pool's.
+struct SessionRings {
+  float* hist_z;          // f32[capacity][depth+1][zl]: saved Z rows
+  double* hist_umask;     // f64[capacity][depth+1][64*64]: saved UMASK rows; nullptr when the pool had no local reservation
+  int depth;              // 1..64
+};
 // open, input side: row i = photos[i] (u8 [n][3*64*64]) or, without photos, the session's GIM (source 0) / IM (source 1) -> GIM, IM and
 // x[i] = table[byte] (float32 NCHW, the encoder's input slot); ids = device int[n]; table = 256 floats, to_tanh per level
 hipError_t launch_session_open_in(const unsigned char* photos, const SessionPool& P, const int* ids, int source, const float* table,
@@ -427,6 +436,13 @@ struct SessionBlendArgs {
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s);
 // UMASK row of session ids[i] := 0 and, with flags (device int[n]), LOCAL[ids[i]] := flags[i]
 hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const int* flags, int n, hipStream_t s);
+// undo history.  ids / save / load = device int[n]; slots are 0..depth (a slot outside that range is skipped).
+// save: ring slot save[i] of session ids[i] := its live Z row (and UMASK row, when hist_umask exists)
+hipError_t launch_session_history_save(const SessionPool& P, const SessionRings& R, const int* ids, const int* save, int n, hipStream_t s);
+// move: the same save where save[i] >= 0, then ring slot load[i] -> row i of the latent slot (stride zs; the blend that follows writes
+// it back to the session's Z) and -> the session's UMASK row
+hipError_t launch_session_history_move(const SessionPool& P, const SessionRings& R, const int* ids, const int* save, const int* load,
+                                       float* zslot, int zs, int n, hipStream_t s);
 // full-resolution open, input side: SRC row of ids[i] := photos[i] (u8 [n][3*S*S]; nullptr: the row already holds the photo), its exact
 // box mean -> GIM, IM and x[i] = table[byte], the outputs of launch_session_open_in
 hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,

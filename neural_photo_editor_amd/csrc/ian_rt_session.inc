@@ -2,19 +2,22 @@
 // Part of the libian runtime: one translation unit, included by ian_runtime.cpp in this order (see the list there).
 //
 // What NPE.py keeps in host globals per editor (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) is one row per session id in each array of
-// h->sess.pool.  A call names sessions by id; per brush call the only host -> device traffic is the event table (11 words per
-// event) and the only device -> host traffic the canvas images.  The host keeps, per session, whether it was opened and a
-// counter of its latent's versions (the residency key of ian_session_brush is n ids + n counters, not the latents' bytes).
+// h->sess.arr.pool (SessionPool).  A call names sessions by id; per brush call the only host -> device traffic is the event table
+// (11 words per event) and the only device -> host traffic the canvas images.  The host keeps, per session, whether it was opened
+// and a counter of its latent's versions (the residency key of ian_session_brush is n ids + n counters, not the latents' bytes).
 //
-// The pool's arrays are described once, in SESS_COLUMNS: member, bytes per session, owning reservation, whether fresh rows start at
-// zero, and the ian_session_field that reads it.  Allocation, the copy of the surviving rows, rollback, freeing, the byte count of
-// the -2 messages and ian_session_read are loops over that table; SESS_SCRATCH does the same for the per-handle device buffers.
-// Three reservations own them (sess_free_group frees exactly one):
-//   base   ian_sessions_reserve        GIM IM RECON ERROR Z MODE; reserve(0) frees all three groups
+// The pool's arrays (and the history's rings beside it: SessionArrays) are described once, in SESS_COLUMNS: member, bytes per
+// session, owning reservation, whether fresh rows start at zero, and the ian_session_field that reads it.  Allocation, the copy of
+// the surviving rows, rollback, freeing, the byte count of the -2 messages and ian_session_read are loops over that table;
+// SESS_SCRATCH does the same for the per-handle device buffers.
+// Four reservations own them (sess_free_group frees exactly one):
+//   base   ian_sessions_reserve        GIM IM RECON ERROR Z MODE; reserve(0) frees all four groups
 //   hires  ian_sessions_reserve_hires  SRC (the photo at S x S, S = 64 * scale), FIELD and FIELD_KIND (what the last call displayed,
 //          as something ian_session_render can apply to SRC; DESIGN.md 4.3), and a per-session host flag "SRC holds a photo"
 //   local  ian_sessions_reserve_local  UMASK (where the user has brushed) and the LOCAL flags, and per handle the falloff table of
 //          the brush footprint (DESIGN.md 4.4)
+//   history ian_sessions_reserve_history  per session a ring of depth + 1 saved states: its Z rows and, when the local reservation
+//          exists at that moment, its UMASK rows; per session on the host the list and cursor of ian_session_history.h (DESIGN.md 4.5)
 // Without a reservation its pointers are null, no kernel touches them, and launch_session_blend runs session_blend_kernel.
 namespace {
 
@@ -22,27 +25,33 @@ constexpr size_t SESS_IMG = 3 * 64 * 64;
 constexpr int SESS_MAX_CAPACITY = 1 << 20;
 size_t sess_src_bytes(int scale) { return 3 * (size_t)(64 * scale) * (size_t)(64 * scale); }
 
-enum SessGroup { SESS_BASE, SESS_HIRES, SESS_LOCAL };
+enum SessGroup { SESS_BASE, SESS_HIRES, SESS_LOCAL, SESS_HISTORY };
+using SessionArrays = ian_handle::SessionState::SessionArrays;
 struct SessColumn {
-  size_t at;                                  // offsetof(SessionPool, member): the struct goes to kernels by value and stays as it is
-  size_t (*row_bytes)(const SessionPool&);    // bytes per session
+  size_t at;                                  // offsetof(SessionArrays, pool.member / rings.member): both structs go to kernels by value
+  size_t (*row_bytes)(const SessionArrays&);  // bytes per session; 0: this pool does not have the column
   SessGroup group;
   bool zero;                                  // rows that were not copied from an old pool start at zero
-  int field;                                  // the ian_session_field that reads it
+  int field;                                  // the ian_session_field that reads it; -1: none
 };
-#define SESS_COL(member, bytes, group, zero, field) {offsetof(SessionPool, member), [](const SessionPool& P) -> size_t { (void)P; return bytes; }, group, zero, field}
+#define SESS_COL(member, bytes, group, zero, field)                                                            \
+  {offsetof(SessionArrays, member), [](const SessionArrays& A) -> size_t {                                     \
+     const SessionPool& P = A.pool; const SessionRings& R = A.rings; (void)P; (void)R; return bytes; }, group, zero, field}
 const SessColumn SESS_COLUMNS[] = {
-    SESS_COL(gim, SESS_IMG, SESS_BASE, false, IAN_SESSION_GIM),
-    SESS_COL(im, SESS_IMG, SESS_BASE, false, IAN_SESSION_IM),
-    SESS_COL(recon, SESS_IMG, SESS_BASE, false, IAN_SESSION_RECON),
-    SESS_COL(error, SESS_IMG * sizeof(float), SESS_BASE, false, IAN_SESSION_ERROR),
-    SESS_COL(z, (size_t)P.zl * sizeof(float), SESS_BASE, false, IAN_SESSION_Z),
-    SESS_COL(mode, sizeof(int), SESS_BASE, false, IAN_SESSION_MODE),
-    SESS_COL(src, sess_src_bytes(P.scale), SESS_HIRES, false, IAN_SESSION_SOURCE),
-    SESS_COL(field, SESS_IMG * sizeof(float), SESS_HIRES, true, IAN_SESSION_FIELD),   // zero: a session opened before the reservation
-    SESS_COL(kind, sizeof(int), SESS_HIRES, true, IAN_SESSION_FIELD_KIND),            // reads as "nothing edited"
-    SESS_COL(umask, 64 * 64 * sizeof(double), SESS_LOCAL, true, IAN_SESSION_UMASK),
-    SESS_COL(local, sizeof(int), SESS_LOCAL, true, IAN_SESSION_LOCAL),
+    SESS_COL(pool.gim, SESS_IMG, SESS_BASE, false, IAN_SESSION_GIM),
+    SESS_COL(pool.im, SESS_IMG, SESS_BASE, false, IAN_SESSION_IM),
+    SESS_COL(pool.recon, SESS_IMG, SESS_BASE, false, IAN_SESSION_RECON),
+    SESS_COL(pool.error, SESS_IMG * sizeof(float), SESS_BASE, false, IAN_SESSION_ERROR),
+    SESS_COL(pool.z, (size_t)P.zl * sizeof(float), SESS_BASE, false, IAN_SESSION_Z),
+    SESS_COL(pool.mode, sizeof(int), SESS_BASE, false, IAN_SESSION_MODE),
+    SESS_COL(pool.src, sess_src_bytes(P.scale), SESS_HIRES, false, IAN_SESSION_SOURCE),
+    SESS_COL(pool.field, SESS_IMG * sizeof(float), SESS_HIRES, true, IAN_SESSION_FIELD),   // zero: a session opened before the reservation
+    SESS_COL(pool.kind, sizeof(int), SESS_HIRES, true, IAN_SESSION_FIELD_KIND),            // reads as "nothing edited"
+    SESS_COL(pool.umask, 64 * 64 * sizeof(double), SESS_LOCAL, true, IAN_SESSION_UMASK),
+    SESS_COL(pool.local, sizeof(int), SESS_LOCAL, true, IAN_SESSION_LOCAL),
+    // the rings: no zero fill, a slot is never read before it was written.  After umask: hist_umask exists where umask does.
+    SESS_COL(rings.hist_z, (size_t)(R.depth + 1) * P.zl * sizeof(float), SESS_HISTORY, false, -1),
+    SESS_COL(rings.hist_umask, P.umask ? (size_t)(R.depth + 1) * 64 * 64 * sizeof(double) : 0, SESS_HISTORY, false, -1),
 };
 #undef SESS_COL
 using SessionScratch = ian_handle::SessionScratch;
@@ -60,9 +69,10 @@ const SessScratchBuf SESS_SCRATCH[] = {
     {offsetof(SessionScratch, d_out), 0, SESS_HIRES},
     {offsetof(SessionScratch, d_falloff), 64 * sizeof(double), SESS_LOCAL},
     {offsetof(SessionScratch, d_ltab), (size_t)BATCH_MAX * 2 * sizeof(int32_t), SESS_LOCAL},
+    {offsetof(SessionScratch, d_htab), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HISTORY},
 };
 
-// the pointer member at byte `at` of a SessionPool / SessionScratch (members of several pointer types: copied, not aliased)
+// the pointer member at byte `at` of a SessionArrays / SessionScratch (members of several pointer types: copied, not aliased)
 void* slot_get(const void* base, size_t at) {
   void* p;
   memcpy(&p, (const char*)base + at, sizeof p);
@@ -70,12 +80,12 @@ void* slot_get(const void* base, size_t at) {
 }
 void slot_set(void* base, size_t at, void* p) { memcpy((char*)base + at, &p, sizeof p); }
 
-bool sess_has(const SessionPool& P, SessGroup g) {
+bool sess_has(const SessionArrays& P, SessGroup g) {
   for (const SessColumn& c : SESS_COLUMNS)
     if (c.group == g) return slot_get(&P, c.at) != nullptr;
   return false;
 }
-size_t sess_row_bytes(const SessionPool& P, unsigned groups) {
+size_t sess_row_bytes(const SessionArrays& P, unsigned groups) {
   size_t sum = 0;
   for (const SessColumn& c : SESS_COLUMNS)
     if (groups >> c.group & 1) sum += c.row_bytes(P);
@@ -83,11 +93,12 @@ size_t sess_row_bytes(const SessionPool& P, unsigned groups) {
 }
 // every column of `groups` that N lacks: rows for `capacity` sessions, the first `keep` copied from O, the others zero where the
 // column asks for it; the zeros are there before any stream reads them
-hipError_t sess_build(SessionPool& N, const SessionPool& O, unsigned groups, size_t capacity, size_t keep) {
+hipError_t sess_build(SessionArrays& N, const SessionArrays& O, unsigned groups, size_t capacity, size_t keep) {
   bool zeroed = false;
   for (const SessColumn& c : SESS_COLUMNS) {
     if (!(groups >> c.group & 1) || slot_get(&N, c.at)) continue;
     const size_t row = c.row_bytes(N);
+    if (!row) continue;
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, capacity * row);
     if (e != hipSuccess) return e;
@@ -102,7 +113,7 @@ hipError_t sess_build(SessionPool& N, const SessionPool& O, unsigned groups, siz
   return zeroed ? hipDeviceSynchronize() : hipSuccess;
 }
 // frees the columns of `groups` that A holds and B does not
-void sess_drop(SessionPool& A, const SessionPool& B, unsigned groups = ~0u) {
+void sess_drop(SessionArrays& A, const SessionArrays& B, unsigned groups = ~0u) {
   for (const SessColumn& c : SESS_COLUMNS) {
     void* p = slot_get(&A, c.at);
     if (!(groups >> c.group & 1) || !p || p == slot_get(&B, c.at)) continue;
@@ -111,8 +122,8 @@ void sess_drop(SessionPool& A, const SessionPool& B, unsigned groups = ~0u) {
   }
 }
 // a failed build: the half-built pool N goes, the handle's pool stays as it was
-int sess_build_failed(ian_handle* h, const char* fn, hipError_t e, SessionPool& N, unsigned groups, int capacity) {
-  sess_drop(N, h->sess.pool);
+int sess_build_failed(ian_handle* h, const char* fn, hipError_t e, SessionArrays& N, unsigned groups, int capacity) {
+  sess_drop(N, h->sess.arr);
   (void)hipGetLastError();
   return fail(h, -2, "%s: %s for %d sessions of %zu bytes", fn, hipGetErrorString(e), capacity, sess_row_bytes(N, groups));
 }
@@ -135,32 +146,36 @@ void scratch_free(SessionScratch& S, SessGroup g) {
 }
 // everything one reservation owns: its columns, its scratch, and what the host keeps about them
 void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
-  sess_drop(S.pool, SessionPool{}, 1u << g);
+  sess_drop(S.arr, SessionArrays{}, 1u << g);
   scratch_free(S, g);
   if (g == SESS_HIRES) {
-    S.pool.scale = 0;
+    S.arr.pool.scale = 0;
     S.out_cap = 0;
     std::fill(S.has_src.begin(), S.has_src.end(), 0);
   } else if (g == SESS_LOCAL) {   // the table too: a later reservation starts from nothing
     S.falloff_set = false;
     std::fill(S.local_flags.begin(), S.local_flags.end(), 0);
+  } else if (g == SESS_HISTORY) {
+    S.arr.rings.depth = 0;
+    std::fill(S.hist.begin(), S.hist.end(), SessionHistory{});
   } else {
-    S.pool.zl = 0;
+    S.arr.pool.zl = 0;
     S.capacity = 0;
-    S.opened.clear(); S.version.clear(); S.has_src.clear(); S.local_flags.clear();
+    S.opened.clear(); S.version.clear(); S.has_src.clear(); S.local_flags.clear(); S.hist.clear();
     S.res_valid = false;
   }
 }
 // ian_sessions_reserve(0) and ian_destroy: w, radius (ian_sessions_set_blend) and dampen_thresh stay
 void sessions_free(ian_handle* h) {
-  for (SessGroup g : {SESS_LOCAL, SESS_HIRES, SESS_BASE}) sess_free_group(h->sess, g);
+  for (SessGroup g : {SESS_HISTORY, SESS_LOCAL, SESS_HIRES, SESS_BASE}) sess_free_group(h->sess, g);
 }
 // the refusal of a call that needs the pool (SESS_BASE) or one of the other reservations
 int session_need(ian_handle* h, const char* fn, SessGroup g) {
   const auto& S = h->sess;
   if (g == SESS_BASE) return S.capacity > 0 ? 0 : fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
-  if (sess_has(S.pool, g)) return 0;
+  if (sess_has(S.arr, g)) return 0;
   if (g == SESS_HIRES) return fail(h, -6, "%s: no full-resolution reservation (call ian_sessions_reserve_hires first)", fn);
+  if (g == SESS_HISTORY) return fail(h, -6, "%s: no history reservation (call ian_sessions_reserve_history first)", fn);
   return fail(h, -6, "%s: no local reservation (call ian_sessions_reserve_local first)", fn);
 }
 
@@ -198,22 +213,23 @@ int sessions_reserve(ian_handle* h, int capacity) {
     return 0;
   }
   if (capacity != S.capacity) {   // a new pool with the groups the old one has: every column follows the capacity
-    SessionPool N = S.pool;
-    N.zl = h->desc.num_latents;
+    SessionArrays N = S.arr;
+    N.pool.zl = h->desc.num_latents;
     unsigned groups = 1u << SESS_BASE;
-    for (SessGroup g : {SESS_HIRES, SESS_LOCAL})
-      if (sess_has(S.pool, g)) groups |= 1u << g;
+    for (SessGroup g : {SESS_HIRES, SESS_LOCAL, SESS_HISTORY})
+      if (sess_has(S.arr, g)) groups |= 1u << g;
     for (const SessColumn& c : SESS_COLUMNS) slot_set(&N, c.at, nullptr);
     const size_t c = (size_t)capacity;
-    hipError_t e = sess_build(N, S.pool, groups, c, (size_t)std::min(capacity, S.capacity));
+    hipError_t e = sess_build(N, S.arr, groups, c, (size_t)std::min(capacity, S.capacity));
     if (e != hipSuccess) return sess_build_failed(h, fn, e, N, groups, capacity);
-    sess_drop(S.pool, N);
-    S.pool = N;
+    sess_drop(S.arr, N);
+    S.arr = N;
     S.capacity = capacity;
     S.opened.resize(c, 0);
     S.version.resize(c, 0);
     S.has_src.resize(c, 0);
     S.local_flags.resize(c, 0);
+    S.hist.resize(c);   // the surviving ids keep their histories: their rings moved with the rest
   }
   const bool had_table = S.d_tanh != nullptr;   // the table is uploaded once, when its buffer is new
   HIPCHK(h, scratch_build(S, SESS_BASE));
@@ -226,17 +242,17 @@ int sessions_reserve(ian_handle* h, int capacity) {
 }
 
 // ian_sessions_reserve_hires / _local: what N lacks of group g, and the group's scratch, at the pool's capacity, then N becomes the pool
-int sess_add_group(ian_handle* h, const char* fn, SessionPool& N, SessGroup g) {
+int sess_add_group(ian_handle* h, const char* fn, SessionArrays& N, SessGroup g) {
   auto& S = h->sess;
-  const bool had = sess_has(S.pool, g);
-  hipError_t e = sess_build(N, S.pool, 1u << g, (size_t)S.capacity, 0);
+  const bool had = sess_has(S.arr, g);
+  hipError_t e = sess_build(N, S.arr, 1u << g, (size_t)S.capacity, 0);
   if (e == hipSuccess) e = scratch_build(S, g);
   if (e != hipSuccess) {
     if (!had) scratch_free(S, g);
     return sess_build_failed(h, fn, e, N, 1u << g, S.capacity);
   }
-  sess_drop(S.pool, N);
-  S.pool = N;
+  sess_drop(S.arr, N);
+  S.arr = N;
   return 0;
 }
 
@@ -249,15 +265,15 @@ int sessions_reserve_hires(ian_handle* h, int scale) {
   if (scale < 0 || scale > 16) return fail(h, -7, "%s: scale %d outside 0..16", fn, scale);
   HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that are freed
   h->last_pending = false;
-  if (scale == S.pool.scale) return 0;
+  if (scale == S.arr.pool.scale) return 0;
   if (scale == 0) {
     sess_free_group(S, SESS_HIRES);
     return 0;
   }
   // a new scale: a new SRC array (no photo survives, its size differs); FIELD and FIELD_KIND are built once
-  SessionPool N = S.pool;
-  N.scale = scale;
-  N.src = nullptr;
+  SessionArrays N = S.arr;
+  N.pool.scale = scale;
+  N.pool.src = nullptr;
   if ((rc = sess_add_group(h, fn, N, SESS_HIRES))) return rc;
   std::fill(S.has_src.begin(), S.has_src.end(), 0);
   return 0;
@@ -280,14 +296,17 @@ int sessions_reserve_local(ian_handle* h, int on) {
   auto& S = h->sess;
   if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (on != 0 && on != 1) return fail(h, -7, "%s: on = %d (0 frees, 1 allocates)", fn, on);
+  if (sess_has(S.arr, SESS_HISTORY) && (on != 0) != sess_has(S.arr, SESS_LOCAL))   // the saved states would lose or lack their UMASK rows
+    return fail(h, -6, "%s: the pool has a history reservation made %s the local one: free the history first (ian_sessions_reserve_history(0))",
+                fn, on ? "without" : "with");
   HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that are freed
   h->last_pending = false;
   if (!on) {
     sess_free_group(S, SESS_LOCAL);
     return 0;
   }
-  if (sess_has(S.pool, SESS_LOCAL)) return 0;
-  SessionPool N = S.pool;
+  if (sess_has(S.arr, SESS_LOCAL)) return 0;
+  SessionArrays N = S.arr;
   if ((rc = sess_add_group(h, fn, N, SESS_LOCAL))) return rc;
   S.falloff_set = false;
   S.local_flags.assign((size_t)S.capacity, 0);
@@ -318,7 +337,7 @@ int sessions_set_local(ian_handle* h, const double* falloff64, double dampen_thr
 // 0 needs the table.  Checked with everything else, before anything is enqueued.
 int session_local_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int stride) {
   auto& S = h->sess;
-  if (!S.pool.umask || S.falloff_set) return 0;
+  if (!S.arr.pool.umask || S.falloff_set) return 0;
   for (int i = 0; i < n; ++i) {
     const int id = ids[(size_t)i * stride];
     if (S.local_flags[id])
@@ -368,6 +387,17 @@ int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int 
   return 0;
 }
 
+// The undo history's side of every other call, host only, where the call bumps S.version or has rewritten what a saved state is
+// measured against: `clear` for a call that rewrites RECON / ERROR / GIM or zeroes UMASK (the saved states no longer belong to the
+// picture), otherwise `edited` (the latent was written: the redo tail goes).
+void session_history_note(decltype(ian_handle::sess)& S, int id, bool clear) {
+  if (!S.arr.rings.depth) return;
+  if (clear)
+    session_history_clear(S.hist[id]);
+  else
+    session_history_edited(S.hist[id], S.arr.rings.depth);
+}
+
 int session_local(ian_handle* h, int n, const int32_t* ids, const int32_t* flags, void* stream) {
   const char* fn = "ian_session_local";
   int rc = check_ready(h, 1);
@@ -385,8 +415,11 @@ int session_local(ian_handle* h, int n, const int32_t* ids, const int32_t* flags
   memcpy(S.ltab_shadow.data(), ids, (size_t)n * sizeof(int32_t));
   memcpy(S.ltab_shadow.data() + n, flags, (size_t)n * sizeof(int32_t));
   HIPCHK(h, hipMemcpyAsync(S.d_ltab, S.ltab_shadow.data(), (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(h, launch_session_local_set(S.pool, S.d_ltab, S.d_ltab + n, n, st));
-  for (int i = 0; i < n; ++i) S.local_flags[ids[i]] = (char)flags[i];
+  HIPCHK(h, launch_session_local_set(S.arr.pool, S.d_ltab, S.d_ltab + n, n, st));
+  for (int i = 0; i < n; ++i) {
+    S.local_flags[ids[i]] = (char)flags[i];
+    session_history_note(S, ids[i], true);
+  }
   return session_rows_leave(h, st, true);
 }
 
@@ -430,7 +463,7 @@ int session_view_check(ian_handle* h, const char* fn, int n, const ian_session_v
   if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: n = %d outside 1..%d", fn, n, BATCH_MAX);
   if (!views || !out) return fail(h, -1, "null pointer passed to %s", fn);
   if (is_device_ptr(views)) return fail(h, -7, "%s: the views must be a host array", fn);
-  const int Sz = 64 * S.pool.scale;
+  const int Sz = 64 * S.arr.pool.scale;
   if (vw < 1 || vh < 1) return fail(h, -7, "%s: window %d x %d: both sizes must be at least 1", fn, vw, vh);
   if (vw & 3) return fail(h, -7, "%s: window width %d is not a multiple of 4", fn, vw);
   for (int i = 0; i < n; ++i) {
@@ -455,7 +488,7 @@ int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, 
   S.views_shadow.resize((size_t)3 * n);
   memcpy(S.views_shadow.data(), views, (size_t)n * sizeof(ian_session_view));
   HIPCHK(h, hipMemcpyAsync(S.d_views, S.views_shadow.data(), (size_t)n * sizeof(ian_session_view), hipMemcpyHostToDevice, st));
-  HIPCHK(h, launch_session_render(S.pool, S.d_views, vw, vh, d_out, n, st));
+  HIPCHK(h, launch_session_render(S.arr.pool, S.d_views, vw, vh, d_out, n, st));
   return 0;
 }
 
@@ -483,20 +516,20 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
   const unsigned char* d_photos = photos;
   const bool host_in = photos && !is_device_ptr(photos);
   if (host_in && hires) {   // straight into the sessions' SRC rows: no staging of n * 3 * S * S bytes
-    const size_t row = sess_src_bytes(S.pool.scale);
+    const size_t row = sess_src_bytes(S.arr.pool.scale);
     for (int i = 0; i < n; ++i)
-      HIPCHK(h, hipMemcpyAsync(S.pool.src + (size_t)ids[i] * row, photos + (size_t)i * row, row, hipMemcpyHostToDevice, st));
+      HIPCHK(h, hipMemcpyAsync(S.arr.pool.src + (size_t)ids[i] * row, photos + (size_t)i * row, row, hipMemcpyHostToDevice, st));
     d_photos = nullptr;
   } else if (host_in) {
     if (!S.d_photo) HIPCHK(h, hipMalloc((void**)&S.d_photo, (size_t)BATCH_MAX * SESS_IMG));
     HIPCHK(h, hipMemcpyAsync(S.d_photo, photos, (size_t)n * SESS_IMG, hipMemcpyHostToDevice, st));
     d_photos = S.d_photo;
   }
-  if (!photos && source == 1 && S.pool.scale > 0) {   // commit: what is displayed becomes the full-resolution photo as well
+  if (!photos && source == 1 && S.arr.pool.scale > 0) {   // commit: what is displayed becomes the full-resolution photo as well
     std::vector<ian_session_view> whole;
     for (int i = 0; i < n; ++i)
       if (S.has_src[ids[i]]) whole.push_back(ian_session_view{ids[i], 0, 0});
-    const int Sz = 64 * S.pool.scale;
+    const int Sz = 64 * S.arr.pool.scale;
     if (!whole.empty() && (rc = session_render_enqueue(h, (int)whole.size(), whole.data(), Sz, Sz, nullptr, st))) return rc;
   }
   Slot& xs = h->slots[h->desc.x_slot];
@@ -504,9 +537,9 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
   Slot& out = h->slots[h->desc.out_slot];
   if ((rc = ensure_slot(h, h->desc.x_slot, n))) return rc;
   if (hires)
-    HIPCHK(h, launch_session_hires_open(d_photos, S.pool, S.d_tab, S.d_tanh, xs.d, n, st));
+    HIPCHK(h, launch_session_hires_open(d_photos, S.arr.pool, S.d_tab, S.d_tanh, xs.d, n, st));
   else
-    HIPCHK(h, launch_session_open_in(d_photos, S.pool, S.d_tab, source, S.d_tanh, xs.d, n, st));
+    HIPCHK(h, launch_session_open_in(d_photos, S.arr.pool, S.d_tab, source, S.d_tanh, xs.d, n, st));
   h->slot_stale[h->desc.x_slot] = 0;
   // the very segments ian_encode and ian_decode_u8 run at this batch: Z and RECON are theirs bit for bit
   if ((rc = run_segment(h, IAN_SEG_ENC, n, st))) return rc;
@@ -514,11 +547,12 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
   if ((rc = run_segment(h, IAN_SEG_DEC, n, st))) return rc;
   h->slot_stale[h->desc.out_slot] = 0;
   const bool shown_dev = shown && is_device_ptr(shown);
-  HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.pool, S.d_tab, 0, 0, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
-  if (S.pool.umask) HIPCHK(h, launch_session_local_set(S.pool, S.d_tab, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:267, :337); LOCAL stays
+  HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, S.d_tab, 0, 0, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
+  if (S.arr.pool.umask) HIPCHK(h, launch_session_local_set(S.arr.pool, S.d_tab, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:267, :337); LOCAL stays
   for (int i = 0; i < n; ++i) {
     S.opened[ids[i]] = 1;
     ++S.version[ids[i]];
+    session_history_note(S, ids[i], true);
     if (photos) S.has_src[ids[i]] = hires ? 1 : 0;   // a 64x64 photo leaves nothing at full resolution to edit
   }
   return session_finish(h, n, shown, shown_dev, host_in, st);
@@ -530,7 +564,7 @@ SessionBlendArgs session_blend_args(ian_handle* h, const int* ids, const int* it
   const Slot& zs = h->slots[h->desc.z_slot];
   SessionBlendArgs a;
   memset(&a, 0, sizeof a);
-  a.xhat = h->slots[h->desc.out_slot].d; a.zslot = zs.d; a.zs = zs.cs; a.P = S.pool; a.ids = ids; a.items = items;
+  a.xhat = h->slots[h->desc.out_slot].d; a.zslot = zs.d; a.zs = zs.cs; a.P = S.arr.pool; a.ids = ids; a.items = items;
   a.shown = shown;
   a.store = store;
   for (int i = 0; i < 8; ++i) a.w[i] = S.w[i];
@@ -559,12 +593,131 @@ int session_set_latent(ian_handle* h, int n, const int32_t* ids, const float* z,
   h->slot_stale[h->desc.out_slot] = 0;
   const bool shown_dev = shown && is_device_ptr(shown);
   if (as_sample) {
-    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.pool, S.d_tab, 1, 1, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
+    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, S.d_tab, 1, 1, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
   } else {
     HIPCHK(h, launch_session_blend(session_blend_args(h, S.d_tab, nullptr, shown_dev ? shown : S.d_shown, 0), n, st));
   }
-  for (int i = 0; i < n; ++i) ++S.version[ids[i]];
+  for (int i = 0; i < n; ++i) {
+    ++S.version[ids[i]];
+    session_history_note(S, ids[i], as_sample != 0);
+  }
   return session_finish(h, n, shown, shown_dev, host_in, st);
+}
+
+int sessions_reserve_history(ian_handle* h, int depth) {
+  const char* fn = "ian_sessions_reserve_history";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
+  if (depth < 0 || depth > SESSION_HISTORY_MAX_DEPTH) return fail(h, -7, "%s: depth %d outside 0..%d", fn, depth, SESSION_HISTORY_MAX_DEPTH);
+  HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that are freed
+  h->last_pending = false;
+  if (depth == S.arr.rings.depth) return 0;
+  if (depth == 0) {
+    sess_free_group(S, SESS_HISTORY);
+    return 0;
+  }
+  // another depth: new rings (a slot's place depends on the depth), every history starts empty
+  SessionArrays N = S.arr;
+  N.rings.depth = depth;
+  N.rings.hist_z = nullptr;
+  N.rings.hist_umask = nullptr;
+  if ((rc = sess_add_group(h, fn, N, SESS_HISTORY))) return rc;
+  S.hist.assign((size_t)S.capacity, SessionHistory{});
+  return 0;
+}
+
+// ian_session_mark / ian_session_undo: the reservation, then what every session call checks
+int session_history_check(ian_handle* h, const char* fn, int n, const int32_t* ids, bool need_blend) {
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  if (h->sess.capacity > 0 && (rc = session_need(h, fn, SESS_HISTORY))) return rc;
+  return session_check(h, fn, n, ids, 1, true, need_blend);
+}
+
+int session_mark(ian_handle* h, int n, const int32_t* ids, void* stream) {
+  const char* fn = "ian_session_mark";
+  int rc = session_history_check(h, fn, n, ids, false);
+  if (rc) return rc;
+  auto& S = h->sess;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  std::vector<SessionHistory> next((size_t)n);   // the counters move only after the enqueue succeeded
+  S.htab_shadow.resize((size_t)2 * n);
+  for (int i = 0; i < n; ++i) {
+    next[i] = S.hist[ids[i]];
+    S.htab_shadow[i] = ids[i];
+    S.htab_shadow[(size_t)n + i] = session_history_mark(next[i], S.arr.rings.depth);
+  }
+  HIPCHK(h, hipMemcpyAsync(S.d_htab, S.htab_shadow.data(), (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(h, launch_session_history_save(S.arr.pool, S.arr.rings, S.d_htab, S.d_htab + n, n, st));
+  for (int i = 0; i < n; ++i) S.hist[ids[i]] = next[i];
+  return session_rows_leave(h, st, true);
+}
+
+// steps[i] > 0 undoes, < 0 redoes (nullptr: one undo each).  One submission: the slot table up, the move kernel (tip save where
+// needed, the saved state into the decoder's latent slot and the UMASK row), the decoder at batch n as ian_session_set_latent runs it,
+// the blend of set_latent(as_sample = 0) but stored (IM := shown := blend, FIELD the edit field; sample mode: shown = uint8(from_tanh(x)),
+// FIELD := x), shown down.
+int session_undo(ian_handle* h, int n, const int32_t* ids, const int32_t* steps, uint8_t* shown, void* stream) {
+  const char* fn = "ian_session_undo";
+  int rc = session_history_check(h, fn, n, ids, true);
+  if (rc) return rc;
+  if ((rc = session_local_check(h, fn, n, ids, 1))) return rc;
+  if (steps && is_device_ptr(steps)) return fail(h, -7, "%s: the steps must be a host array", fn);
+  auto& S = h->sess;
+  for (int i = 0; i < n; ++i) {
+    const int k = steps ? steps[i] : 1;
+    const SessionHistory& H = S.hist[ids[i]];
+    if (k == 0) return fail(h, -7, "%s: item %d: steps 0 (> 0 undoes, < 0 redoes)", fn, i);
+    if (k > 0 && k > session_history_undoable(H))
+      return fail(h, -7, "%s: item %d: %d undo steps asked, session %d has %d", fn, i, k, ids[i], session_history_undoable(H));
+    if (k < 0 && (k < -SESSION_HISTORY_MAX_DEPTH || -k > session_history_redoable(H)))
+      return fail(h, -7, "%s: item %d: %lld redo steps asked, session %d has %d", fn, i, -(long long)k, ids[i], session_history_redoable(H));
+  }
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);   // the residency of ian_session_brush ends: the activations belong to the latents that are replaced
+  TotalTimer tt(h, st);
+  std::vector<SessionHistory> next((size_t)n);   // the counters move only after every enqueue succeeded
+  S.htab_shadow.resize((size_t)3 * n);
+  for (int i = 0; i < n; ++i) {
+    const int k = steps ? steps[i] : 1;
+    int save = -1;
+    next[i] = S.hist[ids[i]];
+    const int load = k > 0 ? session_history_undo(next[i], S.arr.rings.depth, k, &save) : session_history_redo(next[i], S.arr.rings.depth, -k);
+    S.htab_shadow[i] = ids[i];
+    S.htab_shadow[(size_t)n + i] = save;
+    S.htab_shadow[(size_t)2 * n + i] = load;
+  }
+  HIPCHK(h, hipMemcpyAsync(S.d_htab, S.htab_shadow.data(), (size_t)3 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  Slot& zs = h->slots[h->desc.z_slot];
+  if ((rc = ensure_slot(h, h->desc.z_slot, n))) return rc;
+  HIPCHK(h, launch_session_history_move(S.arr.pool, S.arr.rings, S.d_htab, S.d_htab + n, S.d_htab + (size_t)2 * n, zs.d, zs.cs, n, st));
+  if ((rc = run_segment(h, IAN_SEG_DEC, n, st))) return rc;   // sample_at(z) at this batch, as ian_session_set_latent runs it
+  h->slot_stale[h->desc.out_slot] = 0;
+  const bool shown_dev = shown && is_device_ptr(shown);
+  HIPCHK(h, launch_session_blend(session_blend_args(h, S.d_htab, nullptr, shown_dev ? shown : S.d_shown, 1), n, st));
+  for (int i = 0; i < n; ++i) ++S.version[ids[i]];
+  if ((rc = session_finish(h, n, shown, shown_dev, false, st))) return rc;
+  for (int i = 0; i < n; ++i) S.hist[ids[i]] = next[i];   // not `edited`: this call is what moves the cursor
+  return 0;
+}
+
+int session_history(ian_handle* h, int id, int32_t* out) {
+  const char* fn = "ian_session_history";
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if (S.capacity > 0 && (rc = session_need(h, fn, SESS_HISTORY))) return rc;
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
+  if (!out) return fail(h, -1, "null pointer passed to %s", fn);
+  if (id < 0 || id >= S.capacity) return fail(h, -7, "%s: session %d outside the pool (capacity %d)", fn, id, S.capacity);
+  if (!S.opened[id]) return fail(h, -7, "%s: session %d has not been opened", fn, id);
+  out[0] = S.arr.rings.depth;
+  out[1] = session_history_undoable(S.hist[id]);
+  out[2] = session_history_redoable(S.hist[id]);
+  return 0;
 }
 
 // with_view: ian_session_brush_view: after the brush, in the same submission, window i of session views[i].session (== ev[i].session)
@@ -618,14 +771,17 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
     const int nc = std::min(pass, n - off);
     if (!hit) {
       if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
-      HIPCHK(h, launch_session_gather_z(S.pool, d_ids + off, zs.d, zs.cs, nc, st));
+      HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
       if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
     }
     if ((rc = brush_pass_middle(h, nc, d_items + (size_t)7 * off, nullptr, d_col + (size_t)3 * off, true, st))) return rc;
     HIPCHK(h, launch_session_blend(session_blend_args(h, d_ids + off, d_items + (size_t)7 * off, d_shown + (size_t)off * SESS_IMG, 1), nc, st));
   }
   h->slot_stale[h->desc.out_slot] = 0;
-  for (int i = 0; i < n; ++i) ++S.version[ev[i].session];
+  for (int i = 0; i < n; ++i) {
+    ++S.version[ev[i].session];
+    session_history_note(S, ev[i].session, false);
+  }
   if (with_view && (rc = session_render_enqueue(h, n, views, vw, vh, d_out, st))) return rc;
   if ((rc = session_finish(h, n, shown, shown_dev, false, st, with_view && !out_dev ? win : nullptr, out_bytes))) return rc;
   if (n <= pass) {   // one pass: the resident activations belong to these sessions' new latents
@@ -667,13 +823,13 @@ int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
   if (!S.opened[id]) return fail(h, -7, "%s: session %d has not been opened", fn, id);
   const SessColumn* col = nullptr;
   for (const SessColumn& c : SESS_COLUMNS)
-    if (c.field == what) col = &c;
+    if (c.field >= 0 && c.field == what) col = &c;
   if (col && col->group != SESS_BASE && (rc = session_need(h, fn, col->group))) return rc;
   if (what == IAN_SESSION_SOURCE && !S.has_src[id])
     return fail(h, -7, "%s: session %d has no full-resolution source (open it with ian_session_open_hires)", fn, id);
   if (!col) return fail(h, -7, "%s: field %d (enum ian_session_field)", fn, what);
-  const size_t bytes = col->row_bytes(S.pool);
-  const char* src = (const char*)slot_get(&S.pool, col->at) + (size_t)id * bytes;
+  const size_t bytes = col->row_bytes(S.arr);
+  const char* src = (const char*)slot_get(&S.arr, col->at) + (size_t)id * bytes;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = session_rows_enter(h, st))) return rc;
   const bool dev = is_device_ptr(out);
@@ -722,6 +878,18 @@ int ian_sessions_set_local(ian_handle* h, const double* falloff64, double dampen
 }
 int ian_session_local(ian_handle* h, int32_t n, const int32_t* ids, const int32_t* flags, void* stream) {
   return h ? session_local(h, n, ids, flags, stream) : -1;
+}
+int ian_sessions_reserve_history(ian_handle* h, int32_t depth) {
+  return h ? sessions_reserve_history(h, depth) : -1;
+}
+int ian_session_mark(ian_handle* h, int32_t n, const int32_t* ids, void* stream) {
+  return h ? session_mark(h, n, ids, stream) : -1;
+}
+int ian_session_undo(ian_handle* h, int32_t n, const int32_t* ids, const int32_t* steps, uint8_t* shown, void* stream) {
+  return h ? session_undo(h, n, ids, steps, shown, stream) : -1;
+}
+int ian_session_history(ian_handle* h, int32_t id, int32_t out[3]) {
+  return h ? session_history(h, id, out) : -1;
 }
 void ian_session_tanh_table(float* out256) {
   if (out256) session_tanh_table(out256);

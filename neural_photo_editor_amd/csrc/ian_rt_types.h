@@ -290,10 +290,15 @@ struct ian_handle {
     unsigned char* d_out = nullptr;    // full-resolution: staging of rendered windows for a host `out`, grown on demand (out_cap)
     double* d_falloff = nullptr;       // local edits: f64[64], the table of ian_sessions_set_local
     int* d_ltab = nullptr;             // local edits: per ian_session_local call [n ids | n flags]
+    int* d_htab = nullptr;             // undo history: per ian_session_mark / _undo call [n ids | n save slots | n load slots]
   };
   struct SessionState : SessionScratch {
     int capacity = 0;
-    SessionPool pool = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    struct SessionArrays {             // every device array SESS_COLUMNS describes: the pool the kernels take, and the history's rings
+      SessionPool pool;
+      SessionRings rings;
+    };
+    SessionArrays arr = {};
     std::vector<char> opened;
     std::vector<uint64_t> version;
     std::vector<int32_t> tab_shadow;   // upload source of d_tab (outlives the caller's array)
@@ -312,6 +317,10 @@ struct ian_handle {
     bool falloff_set = false;
     double dampen_thresh = 0.75;
     std::vector<int32_t> ltab_shadow;    // upload source of d_ltab
+    // undo history (ian_sessions_reserve_history): per session the list of saved states and the cursor (ian_session_history.h); the
+    // depth is arr.rings.depth.  The host is the only owner of these counters.
+    std::vector<SessionHistory> hist;
+    std::vector<int32_t> htab_shadow;    // upload source of d_htab
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

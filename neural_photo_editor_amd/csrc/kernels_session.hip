@@ -10,6 +10,7 @@
 //   session_local_set_kernel   local edits: a session's UMASK := 0 (every open) and its LOCAL flags (ian_session_local)
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
+//   session_history_save_kernel / _move_kernel   undo history: a session's Z and UMASK rows to and from its ring of saved states
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
 #include "ian_internal.h"
 #include "ian_dact.h"   // m_dact, under the default contraction mode
@@ -112,6 +113,69 @@ hipError_t launch_patch_seed_colour_batch(const float* xhat, const float* colour
                                           hipStream_t s) {
   if (n < 1 || n > 65535) return hipErrorInvalidValue;
   hipLaunchKernelGGL(patch_seed_colour_batch_kernel, dim3((3 * H * W + 255) / 256, n), dim3(256), 0, s, xhat, colour, g, H, W, items);
+  return hipGetLastError();
+}
+
+// ---- undo history: copies between a session's live rows and its ring of saved states, one workgroup per session -------
+// A saved state is the session's Z row and, in a pool that had the local reservation when the history was reserved, its UMASK row.
+// Slot k of session id is row id * (depth + 1) + k of SessionRings' hist_z / hist_umask (size_t throughout).  Nothing is computed, so contraction does
+// not matter here.  A lane moves 16 bytes at consecutive addresses: double2 for UMASK (2048 per row), float4 for Z when vec != 0 (the
+// launcher sets it when zl and every row stride are multiples of 4 floats: both shipped configs, zl = 100), otherwise float by
+// float; vec is uniform over the launch.
+constexpr int HIST_T = 256;
+__device__ __forceinline__ void hist_copy_z(float* dst, const float* src, int zl, int vec) {
+  if (vec) {
+    for (int j = threadIdx.x; j < (zl >> 2); j += HIST_T) reinterpret_cast<float4*>(dst)[j] = reinterpret_cast<const float4*>(src)[j];
+  } else {
+    for (int j = threadIdx.x; j < zl; j += HIST_T) dst[j] = src[j];
+  }
+}
+__device__ __forceinline__ void hist_copy_umask(double* dst, const double* src) {
+  for (int j = threadIdx.x; j < 64 * 64 / 2; j += HIST_T) reinterpret_cast<double2*>(dst)[j] = reinterpret_cast<const double2*>(src)[j];
+}
+
+// mark: slot save[i] of session ids[i] := its live state
+__global__ __launch_bounds__(HIST_T) void session_history_save_kernel(SessionPool P, SessionRings R, const int* __restrict__ ids,
+                                                                      const int* __restrict__ save, int vec) {
+  const int i = blockIdx.x;
+  const int id = ids[i], sv = save[i];
+  if ((unsigned)sv > (unsigned)R.depth) return;   // never sent by the host; a slot outside the ring is not written
+  const size_t row = (size_t)id * (R.depth + 1) + sv;
+  hist_copy_z(R.hist_z + row * P.zl, P.z + (size_t)id * P.zl, P.zl, vec);
+  if (R.hist_umask) hist_copy_umask(R.hist_umask + row * (64 * 64), P.umask + (size_t)id * (64 * 64));
+}
+hipError_t launch_session_history_save(const SessionPool& P, const SessionRings& R, const int* ids, const int* save, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || !R.hist_z || !P.z || R.depth < 1 || (R.hist_umask && !P.umask)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_history_save_kernel, dim3(n), dim3(HIST_T), 0, s, P, R, ids, save, (P.zl & 3) == 0 ? 1 : 0);
+  return hipGetLastError();
+}
+
+// undo / redo: where save[i] >= 0 the live state goes to that slot first (the tip, so that redo can come back to it); then slot
+// load[i] goes to row i of the decoder's latent slot (stride zs, as session_gather_z_kernel writes it; the blend that follows writes
+// the row back to the session's Z) and to the session's UMASK row.
+// No barrier between the two copies: the load overwrites the UMASK row the save has just read, but lane t saves exactly the 16-byte
+// pieces t, t + 256, ... that it later overwrites (hist_copy_umask walks the row the same way both times), so every piece is read
+// and written by one lane, in program order.  Z is saved from the session's row and loaded into the latent slot: no overlap at all.
+__global__ __launch_bounds__(HIST_T) void session_history_move_kernel(SessionPool P, SessionRings R, const int* __restrict__ ids,
+                                                                      const int* __restrict__ save, const int* __restrict__ load,
+                                                                      float* zslot, int zs, int vec) {
+  const int i = blockIdx.x;
+  const int id = ids[i], sv = save[i], ld = load[i];
+  if ((unsigned)ld > (unsigned)R.depth || sv > R.depth) return;   // never sent by the host
+  const size_t ring = (size_t)id * (R.depth + 1);
+  double* um = R.hist_umask ? P.umask + (size_t)id * (64 * 64) : nullptr;
+  if (sv >= 0) {
+    hist_copy_z(R.hist_z + (ring + sv) * P.zl, P.z + (size_t)id * P.zl, P.zl, vec);
+    if (um) hist_copy_umask(R.hist_umask + (ring + sv) * (64 * 64), um);
+  }
+  hist_copy_z(zslot + (size_t)i * zs, R.hist_z + (ring + ld) * P.zl, P.zl, vec);
+  if (um) hist_copy_umask(um, R.hist_umask + (ring + ld) * (64 * 64));
+}
+hipError_t launch_session_history_move(const SessionPool& P, const SessionRings& R, const int* ids, const int* save, const int* load,
+                                       float* zslot, int zs, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || !R.hist_z || !P.z || R.depth < 1 || (R.hist_umask && !P.umask) || !zslot || zs < P.zl) return hipErrorInvalidValue;
+  const int vec = (P.zl & 3) == 0 && (zs & 3) == 0 && (reinterpret_cast<uintptr_t>(zslot) & 15) == 0;
+  hipLaunchKernelGGL(session_history_move_kernel, dim3(n), dim3(HIST_T), 0, s, P, R, ids, save, load, zslot, zs, vec);
   return hipGetLastError();
 }
 

@@ -47,6 +47,7 @@ EXPORTS = (
     "ian_sessions_reserve", "ian_sessions_set_blend", "ian_session_open", "ian_session_set_latent", "ian_session_brush", "ian_session_read",
     "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
+    "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -119,6 +120,10 @@ def load_library():
     lib.ian_sessions_reserve_local.argtypes = [vp, i32]
     lib.ian_sessions_set_local.argtypes = [vp, fp, C.c_double]
     lib.ian_session_local.argtypes = [vp, i32, fp, fp, vp]
+    lib.ian_sessions_reserve_history.argtypes = [vp, i32]
+    lib.ian_session_mark.argtypes = [vp, i32, fp, vp]
+    lib.ian_session_undo.argtypes = [vp, i32, fp, fp, fp, vp]
+    lib.ian_session_history.argtypes = [vp, i32, fp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -364,6 +369,33 @@ class Handle:
             raise ValueError("ids and flags must be 1-D arrays of the same length, got %s and %s" % (ids.shape, flags.shape))
         self._check(self.lib.ian_session_local(self._h, len(ids), _ptr(ids), _ptr(flags), C.c_void_p(stream or 0)))
 
+    def sessions_reserve_history(self, depth):
+        self._check(self.lib.ian_sessions_reserve_history(self._h, int(depth)))
+
+    def session_mark(self, ids, stream=None):
+        """ian_session_mark; ids = int32 array (n = its length)."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        if ids.ndim != 1:
+            raise ValueError("ids must be a 1-D array, got shape %s" % (ids.shape,))
+        self._check(self.lib.ian_session_mark(self._h, len(ids), _ptr(ids), C.c_void_p(stream or 0)))
+
+    def session_undo(self, ids, steps=None, shown=None, stream=None):
+        """ian_session_undo; ids and steps (or None: one undo each) = int32 arrays of the same length n, shown u8[n,3,64,64] or None."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        if steps is not None:
+            steps = np.ascontiguousarray(steps, np.int32)
+        if ids.ndim != 1 or (steps is not None and steps.shape != ids.shape):
+            raise ValueError("ids and steps must be 1-D arrays of the same length, got %s and %s" % (ids.shape, None if steps is None else steps.shape))
+        null = C.c_void_p(0)
+        self._check(self.lib.ian_session_undo(self._h, len(ids), _ptr(ids), _ptr(steps) if steps is not None else null,
+                                              _ptr(shown) if shown is not None else null, C.c_void_p(stream or 0)))
+
+    def session_history(self, sid):
+        """ian_session_history -> (depth, undoable, redoable) of one opened session; host only."""
+        out = np.zeros(3, np.int32)
+        self._check(self.lib.ian_session_history(self._h, int(sid), _ptr(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def session_read(self, sid, what, stream=None, scale=0):
         code, dtype, shape = SESSION_FIELDS[what]
         if shape == "S":
@@ -432,7 +464,7 @@ def parse_header_prototypes(path):
         if args and args != "void":
             for a in args.split(","):
                 a = " ".join(a.split())
-                argt.append("ptr" if "*" in a else a.rsplit(" ", 1)[0].replace("const ", "").strip())
+                argt.append("ptr" if "*" in a or "[" in a else a.rsplit(" ", 1)[0].replace("const ", "").strip())
         out.append((ret, name, argt))
     return out
 

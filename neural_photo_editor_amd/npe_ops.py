@@ -265,3 +265,82 @@ def photo_blend_local(xhat, recon_uint8, error, U=None, half=None, dampen=False,
     with np.errstate(invalid="ignore"):
         IM = np.uint8(from_tanh(to_tanh(RECON) + D))
     return IM, MASK_L, FIELD
+
+
+# ---- undo history of an edit session (ian_session_mark / ian_session_undo, include/ian.h) -----------------------------
+# No arithmetic: the bookkeeping of which saved state is where.  csrc/ian_session_history.h is the same specification in C++; the two
+# return the same physical slots for the same operations.
+class SessionHistory:
+    """One session's history: saved states E[0..len-1], a cursor c (0 <= c <= len; c == len: the live state is not in the list,
+    c < len: it is E[c]) in a ring of depth + 1 physical slots, entry k in slot (base + k) % (depth + 1).  Every method returns the
+    physical slots to save the live state into / to load it from; what a slot holds is the caller's.
+    c == len implies len <= depth, c < len implies len <= depth + 1: at most `depth` steps can be undone, and the slot beyond them
+    holds the tip that the first undo saves."""
+
+    def __init__(self, depth):
+        depth = int(depth)
+        if not 1 <= depth <= 64:
+            raise ValueError("depth must be in 1..64, got %d" % depth)
+        self.depth = depth
+        self.base = self.len = self.cur = 0
+
+    def _slot(self, k):
+        return (self.base + k) % (self.depth + 1)
+
+    def _drop_oldest(self):
+        self.base = (self.base + 1) % (self.depth + 1)
+        self.len -= 1
+        self.cur = max(self.cur - 1, 0)
+
+    @property
+    def undoable(self):
+        return self.cur
+
+    @property
+    def redoable(self):
+        return self.len - 1 - self.cur if self.cur < self.len else 0
+
+    def mark(self):
+        """A stroke begins: the redo tail goes, the oldest entry too when the list is full -> the slot to save the live state into."""
+        if self.cur < self.len:
+            self.len = self.cur
+        if self.len == self.depth:
+            self.cur = self.len
+            self._drop_oldest()
+        slot = self._slot(self.len)
+        self.len += 1
+        self.cur = self.len
+        return slot
+
+    def undo(self, k=1):
+        """-> (the slot to save the tip into first, or -1; the slot to load)."""
+        k = int(k)
+        if not 1 <= k <= self.undoable:
+            raise ValueError("%d undo steps asked, %d available" % (k, self.undoable))
+        save = -1
+        if self.cur == self.len:
+            save = self._slot(self.len)
+            self.len += 1
+        self.cur -= k
+        return save, self._slot(self.cur)
+
+    def redo(self, k=1):
+        """-> the slot to load."""
+        k = int(k)
+        if not 1 <= k <= self.redoable:
+            raise ValueError("%d redo steps asked, %d available" % (k, self.redoable))
+        self.cur += k
+        return self._slot(self.cur)
+
+    def edited(self):
+        """The latent was written by something other than undo / redo: the redo tail goes, the state the user came back to stays an
+        undo target (the oldest entry goes when that makes depth + 1 of them)."""
+        if self.cur >= self.len:
+            return
+        self.len = self.cur + 1
+        self.cur = self.len
+        if self.len > self.depth:
+            self._drop_oldest()
+
+    def clear(self):
+        self.base = self.len = self.cur = 0

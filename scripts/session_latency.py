@@ -2,9 +2,15 @@
 ids: state in HBM, 11 words up per event, 12 KB down) and of IAN.brush_step_batch with host pointers and photo= (per item a 48 KB
 colour image, RECON, ERROR and the latent compared against their shadows, z_new and IM down), in one process, on both configs.
 usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 16 64] [--calls 200] [--repeats 3] [--out FILE] [--local]
+                                                    [--history]
   --local: the same event stream on a pool with the local reservation and flags 3 (user mask + dampen) on every session: per item
            the blend also reads, max-es and writes the session's 32 KB UMASK.  Compare against a run without --local in the same
            process order on the same build.
+  --history: the undo history instead of the comparison with the stateless call, sessions only, depth 16:
+           mark_paint_undo  one iteration = mark, paint, undo (three calls; events/s counts iterations)
+           undo             one ian_session_undo per call, undo and redo alternating on a marked stroke
+           set_latent       the same sessions' latents through set_latent (host z): what an undo should cost, less one small launch
+           paint_unused_history  paint in the pool with the history reserved but never marked, to hold against paint without --history
   --trace: only the first --n on the first config, sessions only: warm-up, an idle second, then --calls timed calls (for a
            rocprofv3 --kernel-trace --stats run).
 Per (config, n, path): the median over --calls calls after warm-up, repeated --repeats times (the two paths alternate within a
@@ -92,6 +98,54 @@ def run_arch(arch, ns, calls, repeats, local=False):
     return rows
 
 
+def run_history(arch, ns, calls, repeats, depth=16):
+    m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
+    s = m.sessions(max(ns))
+    s.reserve_history(depth)
+    rows = []
+    for n in ns:
+        ids = np.arange(n)
+        boxes = boxes_for(n)
+        levels = (255, 0, 0)
+        s.open(ids, np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8))
+        z = np.stack([s.read(i)["Z"] for i in ids])
+        back = [True]
+
+        def paint_unused():
+            s.paint(ids, boxes, levels)
+
+        def mark_paint_undo():
+            s.mark(ids)
+            s.paint(ids, boxes, levels)
+            s.undo(ids)
+
+        def undo():
+            (s.undo if back[0] else s.redo)(ids)
+            back[0] = not back[0]
+
+        def set_latent():
+            s.set_latent(ids, z)
+        res = {"paint_unused_history": [], "mark_paint_undo": [], "undo": [], "set_latent": []}
+        for _ in range(repeats):
+            res["paint_unused_history"].append(median_ms(paint_unused, calls))      # first: nothing has been marked yet
+        for _ in range(repeats):
+            res["mark_paint_undo"].append(median_ms(mark_paint_undo, calls))
+            s.mark(ids)
+            s.paint(ids, boxes, levels)
+            back[0] = True
+            res["undo"].append(median_ms(undo, 2 * (calls // 2), warmup=10))         # an even number of calls: ends where it began
+            res["set_latent"].append(median_ms(set_latent, calls))
+        row = {"n": n, "depth": depth, "ring_bytes_per_session": (depth + 1) * 4 * m.get_zdim()}
+        for k, v in res.items():
+            med = float(np.median(v))
+            row[k] = {"p50_ms": round(med, 4), "events_per_s": round(n * 1e3 / med, 1), "spread": round((max(v) - min(v)) / med, 4),
+                      "repeats_ms": [round(t, 4) for t in v]}
+        row["undo_over_set_latent"] = round(row["undo"]["p50_ms"] / row["set_latent"]["p50_ms"], 3)
+        rows.append(row)
+    m.close()
+    return rows
+
+
 def trace_run(arch, n, calls, local=False):
     m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
     s = m.sessions(n)
@@ -117,15 +171,16 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--local", action="store_true", help="local reservation, flags 3 (user mask + dampen) on every session")
+    ap.add_argument("--history", action="store_true", help="undo history: mark + paint + undo, undo alone, set_latent, paint with an unused history")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     archs = [a.only] if a.only else ["IAN_simple", "IAN"]
     if a.trace:
         print(json.dumps(trace_run(archs[0], a.n[0], a.calls, a.local)))
         return
-    res = {"metric": "session_latency", "calls": a.calls, "repeats": a.repeats, "local": bool(a.local)}
+    res = {"metric": "session_history_latency" if a.history else "session_latency", "calls": a.calls, "repeats": a.repeats, "local": bool(a.local)}
     for arch in archs:
-        res[arch] = run_arch(arch, a.n, a.calls, a.repeats, a.local)
+        res[arch] = run_history(arch, a.n, a.calls, a.repeats) if a.history else run_arch(arch, a.n, a.calls, a.repeats, a.local)
     line = json.dumps(res)
     print(line)
     if a.out:
