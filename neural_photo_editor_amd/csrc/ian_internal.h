@@ -3,42 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ian_tg_types.h"
+
 namespace ian {
 
-// ---------------------------------------------------------------------------------------------
-// "tap GEMM": every dense-channel layer of the IAN (5x5/s2 conv, 5x5/s2 transposed conv split into
-// its 4 output-parity classes, composite multiscale-dilated 3x3, dense) is one implicit GEMM
-//     C[m][co] = sum_t sum_ci  X[pixel(m) + d_t][ci] * Wt[t][co][ci]
-// over a list of taps t = (dy,dx, weight slab).  m enumerates (image, qy, qx) of a per-class output
-// grid; input pixel = q*si + b + d_t, output pixel = q*so + p_class.
-// ---------------------------------------------------------------------------------------------
-struct TgTap {
-  int dy, dx;
-};
-struct TgClass {
-  int ntaps, tap0;  // taps[tap0 .. tap0+ntaps)
-  int py, px;       // output parity offset
-  long long w_off;  // float offset of this class's first weight slab; slab t at w_off + t*CoutPad*Cin
-};
-struct TgItem {  // one workgroup's job (host-built table, 64 B = one s_load_dwordx16)
-  int cls, m0, n0;
-  int ks0, ks1;  // K-step range [ks0,ks1) of 32-channel steps over (tap, ci-chunk)
-  int slab;      // split-K: slab tile index; -1 = direct epilogue
-  int tile;      // split-K: index of the output tile in the TgTile table (fused combine: counter + slab range)
-  // the item's TgClass and the tap its K range starts in, COPIED here (fill_item_class, ian_rt_schedule.inc) so that the kernel's
-  // prologue is one table fetch instead of three dependent ones (item -> class -> tap: ~0.5-1 us each from a cold L2, before the
-  // first operand load can be addressed); the tables stay as they are for the taps after the first and for the split-bf16 kernel
-  int ntaps, tap0, py, px;
-  int dy0, dx0;  // taps[tap0 + ks0 / (Cin / 32)]
-  int pad1;
-  long long w_off;
-};
-static_assert(sizeof(TgItem) == 64, "TgItem is fetched as one 64-byte scalar load");
-struct TgTile {  // reduce pass: one output tile
-  int cls, m0, n0, slab0, nsplit;
-  int py, px;  // the class's output parity offset, copied here so that the reduce pass needs ONE table load, not two dependent ones
-  int pad2;
-};
+// the tap GEMM's host-built tables (TgTap, TgTapE, TgClass, TgItem, TgTile) and its two row orders: ian_tg_types.h
 
 enum { TG_EPI_FWD = 0, TG_EPI_BWD = 1 };
 
@@ -79,9 +48,11 @@ struct TgParams {
   float* slab;
   const TgItem* items;
   const TgClass* classes;
-  const TgTap* taps;
+  const TgTap* taps;         // the layer's list (tapgemm_bf16x3_kernel)
+  const TgTapE* ttaps;       // the schedule's per-tile lists (tapgemm_kernel; TgItem::tap0 indexes it)
   TgEpilogue epi;
-  int M;                     // images * QH * QW
+  int M;                     // rows: images * QH * QW, position-major QH * QW << b_shift
+  int b_shift, nimg;         // row order (ian_tg_types.h): b_shift < 0 image-major, else position-major with 1 << b_shift >= nimg rows per position
   int IH, IW, Cin;           // Cin = padded input channels = pixel stride of x (multiple of 32)
   int qw_shift, qhw_shift;   // QW = 1<<qw_shift, QH*QW = 1<<qhw_shift
   int si, by, bx;            // input coordinate = q*si + b + d
@@ -108,6 +79,7 @@ struct TgReduceParams {
   const TgClass* classes;
   TgEpilogue epi;
   int M, qw_shift, qhw_shift, so, OH, OW, Cout, y_stride;
+  int b_shift, nimg;   // row order, as TgParams
 };
 
 // TgParams::variant: the K-loop schedules of tapgemm_kernel (described at the head of kernels_tapgemm.hip).  The numbers are the

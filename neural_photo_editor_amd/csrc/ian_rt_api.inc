@@ -473,8 +473,8 @@ int ian_autotune(ian_handle* h, int32_t n, int32_t what, void* stream) {
       if ((rc = tune_layer(h, op.fwd, n, st, [&]() { return run_op_fwd(h, *opp, n, st); }, &best, &ms))) break;
       cache[tune_key(n, dir_fwd, op.name)] = best;
       if (verbose)
-        fprintf(stderr, "[ian_autotune] n=%d fwd %-14s -> tile %s, max K-steps/item %d, schedule %d, combine %d : %.1f us (%.1f TF/s)\n", n,
-                op.name.c_str(), cfg_names[best.cfg], best.max_steps, best.variant, best.fused, ms * 1e3,
+        fprintf(stderr, "[ian_autotune] n=%d fwd %-14s -> tile %s, max K-steps/item %d, schedule %d, combine %d, position-major %d : %.1f us (%.1f TF/s)\n", n,
+                op.name.c_str(), cfg_names[best.cfg], best.max_steps, best.variant, best.fused, best.pos_major, ms * 1e3,
                 2.0 * op.fwd.macs_per_image() * n / (ms * 1e-3) / 1e12);
     }
   }

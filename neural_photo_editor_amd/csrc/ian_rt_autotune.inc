@@ -10,61 +10,11 @@ struct TuneCand {
   float ms;
 };
 
-// Workgroups of a tile shape one CU holds at once (LDS of the two staging buffers, 160 KB per CU; waves per SIMD <= 8 is never the
-// limit for these shapes): what "one round" of a launch is.
-static int tg_slots(int cfg) {
-  const TgShape sh = tg_shape(cfg);
-  const size_t lds = (size_t)2 * (sh.bm + sh.bn) * 36 * sizeof(float);
-  int per_cu = (int)((160u << 10) / lds);
-  const int waves = (cfg == TG_128x128W8 || cfg == TG_128x64W8) ? 8 : 4;
-  per_cu = std::min(per_cu, 32 / waves);
-  return 256 * std::max(1, per_cu);
-}
-
-// Split limits worth timing for one tile shape, from a model instead of powers of two only (round 6): for every limit 8 .. max the
-// item list the scheduler would build is dealt longest-first onto `slots` machines (each item costs its K-steps + a fixed
-// prologue / epilogue allowance); the limits with the shortest makespans are returned.  conv4 at batch 64 is the case that
-// motivated it: 64 tiles x 400 K-steps fill the 512 slots of the 8-wave 128x128 tile exactly with limit 50 -- 64 gives 448
-// items, 32 gives 832 (1.6 rounds) -- and the tuner never saw 50.
-static std::vector<int> model_split_limits(const TgLayer& L, int tiles, int kpt, int slots, int max_ksteps, int keep) {
-  std::vector<std::pair<double, int>> scored;
-  std::vector<int> lens;
-  for (int ms = 8; ms < max_ksteps; ++ms) {
-    lens.clear();
-    long long nitems = 0;
-    for (auto& c : L.classes) {
-      const int ks = c.ntaps * kpt;
-      const int ns = std::max(1, (ks + ms - 1) / ms), per = (ks + ns - 1) / ns, ns2 = (ks + per - 1) / per;
-      for (int k = 0; k < ns2; ++k) lens.push_back(std::min(per, ks - k * per));
-      nitems += (long long)ns2 * tiles;
-    }
-    if (nitems > 8192) continue;
-    // every length occurs `tiles` times: longest-first onto the least loaded of `slots` machines == round-robin fill by length
-    std::sort(lens.begin(), lens.end(), std::greater<int>());
-    std::priority_queue<double, std::vector<double>, std::greater<double>> load;
-    for (int k = 0; k < slots; ++k) load.push(0.0);
-    double makespan = 0;
-    for (int len : lens)
-      for (int t = 0; t < tiles; ++t) {
-        const double v = load.top() + len + 4.0;
-        load.pop();
-        load.push(v);
-        makespan = std::max(makespan, v);
-      }
-    scored.push_back({makespan + 0.002 * (double)nitems / slots, ms});   // ties: fewer slabs
-  }
-  std::sort(scored.begin(), scored.end());
-  std::vector<int> out;
-  double last = -1;
-  for (auto& sc : scored) {
-    if ((int)out.size() >= keep) break;
-    if (sc.first == last) continue;   // the same item list under another limit
-    last = sc.first;
-    out.push_back(sc.second);
-  }
-  return out;
-}
-
+// Split limits worth timing for one tile shape come from a model instead of powers of two only (round 6; tg_model_split_limits,
+// ian_tg_plan.h): for every limit 8 .. max the item list the planner would build -- from the real K-steps of every tile, which differ
+// between tiles once a position-major plan skips taps -- is dealt longest-first onto tg_slots machines, and the limits with the
+// shortest makespans are timed.  conv4 at batch 64 is the case that motivated it: 64 tiles x 400 K-steps fill the 512 slots of the
+// 8-wave 128x128 tile exactly with limit 50 -- 64 gives 448 items, 32 gives 832 (1.6 rounds) -- and the tuner never saw 50.
 std::vector<TgChoice> tune_candidates(const ian_handle* h, const TgLayer& L, int nimg) {
   const int M = nimg * L.QH * L.QW;
   std::vector<int> cfgs;
@@ -84,19 +34,27 @@ std::vector<TgChoice> tune_candidates(const ian_handle* h, const TgLayer& L, int
   }
   int max_ksteps = 0;
   for (auto& c : L.classes) max_ksteps = std::max(max_ksteps, c.ntaps * (L.Cin / 32));
+  const bool pm_allowed = pos_major_allowed(h, L, nimg);
   std::vector<TgChoice> out;
   for (int cfg : cfgs) {
     const TgShape sh = tg_shape(cfg);
-    const long long tiles = (long long)((M + sh.bm - 1) / sh.bm) * ((L.Cout + sh.bn - 1) / sh.bn);
+    // image-major rows, then -- where the option admits it and the planner's list is shorter than the full one -- position-major rows
+    for (int pm = 0; pm < (pm_allowed && !(bf16x3_applies(h, M, nimg) && tg_bf16x3_supported(cfg)) ? 2 : 1); ++pm) {
+    std::vector<int> tile_ks;
+    long long steps_full = 0, steps = 0;
+    tg_tile_ksteps(plan_input(h, L, nimg, cfg, 0, pm), tile_ks, &steps_full);
+    for (int k : tile_ks) steps += k;
+    if (pm && (steps >= steps_full || h->opt.tg_pos_major == 2)) continue;   // nothing to skip; forced mode: the first pass is position-major already
+    const long long tiles = (long long)tile_ks.size() / (long long)L.classes.size();   // per class
     std::vector<int> limits = {0, 4, 8, 16, 32, 64, 128, 256};
     if (h->opt.tg_tune_model && M > 64 && tiles * (long long)L.classes.size() < 2ll * tg_slots(cfg))   // enough tiles: nothing to split
-      for (int ms : model_split_limits(L, (int)tiles, L.Cin / 32, tg_slots(cfg), max_ksteps, 3))
+      for (int ms : tg_model_split_limits(tile_ks, tg_slots(cfg), max_ksteps, 3))
         if (std::find(limits.begin(), limits.end(), ms) == limits.end()) limits.push_back(ms);
     for (int ms : limits) {
       if (ms > 0 && ms >= max_ksteps) continue;  // would not split anything
       if (ms > 0) {
         long long slabs = 0;
-        for (auto& c : L.classes) slabs += tiles * ((c.ntaps * (L.Cin / 32) + ms - 1) / ms);
+        for (int k : tile_ks) slabs += (k + ms - 1) / ms;
         if (slabs * sh.bm * sh.bn * 4 > (512ll << 20)) continue;  // slab workspace cap
         if (slabs > 16384) continue;
       }
@@ -116,8 +74,10 @@ std::vector<TgChoice> tune_candidates(const ian_handle* h, const TgLayer& L, int
           c.max_steps = ms;
           c.variant = var;
           c.fused = fu;
+          c.pos_major = pm_allowed ? pm : -1;
           out.push_back(c);
         }
+    }
     }
   }
   return out;
@@ -147,7 +107,7 @@ template <typename F>
 int tune_layer(ian_handle* h, TgLayer& L, int nimg, hipStream_t st, F&& run, TgChoice* best_out, float* best_ms) {
   TgChoice best;
   float bms = 1e30f;
-  // IAN_TUNE_LOG=<file>: every candidate's time, appended as "<M> <Cin> <Cout> <classes> <cfg> <max_steps> <variant> <fused> <us>" (a measurement
+  // IAN_TUNE_LOG=<file>: every candidate's time, appended as "<M> <Cin> <Cout> <classes> <cfg> <max_steps> <variant> <fused> <pos_major> <us>" (a measurement
   // aid: which tile / split / schedule loses by how much on which layer; the choice itself is unaffected)
   const char* logp = getenv("IAN_TUNE_LOG");
   FILE* logf = logp ? fopen(logp, "a") : nullptr;
@@ -157,7 +117,7 @@ int tune_layer(ian_handle* h, TgLayer& L, int nimg, hipStream_t st, F&& run, TgC
     free_schedule_for(L, nimg);
     float ms = 0;
     int rc = time_launches(h, st, 5, run, &ms);
-    if (logf) fprintf(logf, "%d %d %d %d %d %d %d %d %.2f%s\n", nimg * L.QH * L.QW, L.Cin, L.Cout, (int)L.classes.size(), c.cfg, c.max_steps, c.variant, c.fused, ms * 1000.f, rc ? " FAILED" : "");
+    if (logf) fprintf(logf, "%d %d %d %d %d %d %d %d %d %.2f%s\n", nimg * L.QH * L.QW, L.Cin, L.Cout, (int)L.classes.size(), c.cfg, c.max_steps, c.variant, c.fused, c.pos_major, ms * 1000.f, rc ? " FAILED" : "");
     if (rc) { if (logf) fclose(logf); return rc; }
     timed.push_back({c, ms});
     if (ms < bms) {
@@ -183,7 +143,7 @@ int tune_layer(ian_handle* h, TgLayer& L, int nimg, hipStream_t st, F&& run, TgC
       }
     bms = 1e30f;
     for (size_t k = 0; k < nf; ++k) {
-      if (logf) fprintf(logf, "%d %d %d %d %d %d %d %d %.2f final\n", nimg * L.QH * L.QW, L.Cin, L.Cout, (int)L.classes.size(), timed[k].ch.cfg, timed[k].ch.max_steps, timed[k].ch.variant, timed[k].ch.fused, best_round[k] * 1000.f);
+      if (logf) fprintf(logf, "%d %d %d %d %d %d %d %d %d %.2f final\n", nimg * L.QH * L.QW, L.Cin, L.Cout, (int)L.classes.size(), timed[k].ch.cfg, timed[k].ch.max_steps, timed[k].ch.variant, timed[k].ch.fused, timed[k].ch.pos_major, best_round[k] * 1000.f);
       if (best_round[k] < bms) {
         bms = best_round[k];
         best = timed[k].ch;
@@ -202,10 +162,10 @@ int tune_layer(ian_handle* h, TgLayer& L, int nimg, hipStream_t st, F&& run, TgC
 // choices, so that repeated processes (e.g. the rocprofv3 passes of one profile) run the very same kernels.
 typedef std::map<std::string, TgChoice> TuneCache;
 std::string tune_key(int n, const char* dir, const std::string& name) { return std::to_string(n) + " " + dir + " " + name; }
-// File format: first line "ian-tune-cache <format version>", then "<batch> <dir> <layer> <cfg> <max_steps> <variant> <fused>" per line.  A
+// File format: first line "ian-tune-cache <format version>", then "<batch> <dir> <layer> <cfg> <max_steps> <variant> <fused> <pos_major>" per line (format 3 added the row order).  A
 // file without that header (an older 6-field format would shift every later field by one) or with another version is IGNORED, and
 // every field is range-checked: a stale or corrupt cache must never reach a kernel as an out-of-range schedule (ADVICE r5).
-constexpr int TUNE_CACHE_FORMAT = 2;
+constexpr int TUNE_CACHE_FORMAT = 3;
 void tune_cache_load(TuneCache& c) {
   const char* path = getenv("IAN_TUNE_CACHE");
   if (!path) return;
@@ -218,14 +178,15 @@ void tune_cache_load(TuneCache& c) {
     return;
   }
   char dir[16], name[256];
-  int n, cfg, ms, var, fu;
-  while (fscanf(f, "%d %15s %255s %d %d %d %d", &n, dir, name, &cfg, &ms, &var, &fu) == 7) {
-    if (n <= 0 || cfg < 0 || cfg >= TG_NCONFIG || ms < 0 || fu < 0 || fu > 2 || !tg_schedule_shipped(var)) continue;
+  int n, cfg, ms, var, fu, pm;
+  while (fscanf(f, "%d %15s %255s %d %d %d %d %d", &n, dir, name, &cfg, &ms, &var, &fu, &pm) == 8) {
+    if (n <= 0 || cfg < 0 || cfg >= TG_NCONFIG || ms < 0 || fu < 0 || fu > 2 || pm < -1 || pm > 1 || !tg_schedule_shipped(var)) continue;
     TgChoice ch;
     ch.cfg = cfg;
     ch.max_steps = ms;
     ch.variant = var;
     ch.fused = fu;
+    ch.pos_major = pm;
     c[tune_key(n, dir, name)] = ch;
   }
   fclose(f);
@@ -236,7 +197,7 @@ void tune_cache_store(const TuneCache& c) {
   FILE* f = fopen(path, "w");
   if (!f) return;
   fprintf(f, "ian-tune-cache %d\n", TUNE_CACHE_FORMAT);
-  for (auto& kv : c) fprintf(f, "%s %d %d %d %d\n", kv.first.c_str(), kv.second.cfg, kv.second.max_steps, kv.second.variant, kv.second.fused);
+  for (auto& kv : c) fprintf(f, "%s %d %d %d %d %d\n", kv.first.c_str(), kv.second.cfg, kv.second.max_steps, kv.second.variant, kv.second.fused, kv.second.pos_major);
   fclose(f);
 }
 

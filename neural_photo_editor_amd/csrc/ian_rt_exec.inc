@@ -34,15 +34,15 @@ int run_tapgemm(ian_handle* h, TgLayer& L, int nimg, const float* x, float* y, i
   if (rc) return rc;
   TgParams p;
   p.x = x; p.w = L.d_w; p.y = y; p.slab = h->d_slab;
-  p.items = S->d_items; p.classes = L.d_classes; p.taps = L.d_taps;
+  p.items = S->d_items; p.classes = L.d_classes; p.taps = L.d_taps; p.ttaps = S->d_ttaps;
   p.epi = epi;
-  p.M = nimg * L.QH * L.QW;
+  p.M = S->M; p.b_shift = S->b_shift; p.nimg = nimg;
   p.variant = h->opt.tg_variant_force >= 0 ? h->opt.tg_variant_force : (S->variant >= 0 ? S->variant : h->opt.tg_variant);
   h->stats_chunks_last = 0;
   if (h->stats_next.mode) {   // one-shot request of the training step: statistics of the stored tensor in this launch's epilogue
     const TgShape sh = tg_shape(S->cfg);
     const long long chunks = (long long)((p.M + sh.bm - 1) / sh.bm) * (long long)L.classes.size();
-    if (S->ntiles == 0 && chunks * 2 * L.Cout <= h->stats_cap && chunks < (1 << 16) && tg_stats_supported(S->cfg, p.variant)) {
+    if (S->ntiles == 0 && !S->pos_major && chunks * 2 * L.Cout <= h->stats_cap && chunks < (1 << 16) && tg_stats_supported(S->cfg, p.variant)) {
       p.epi.st = h->stats_next;
       p.epi.st.C = L.Cout;
       p.epi.st.ncls = (int)L.classes.size();
@@ -100,7 +100,7 @@ int run_tapgemm(ian_handle* h, TgLayer& L, int nimg, const float* x, float* y, i
     TgReduceParams r;
     r.slab = h->d_slab; r.y = y; r.tiles = S->d_tiles; r.classes = L.d_classes; r.epi = epi;
     r.M = p.M; r.qw_shift = p.qw_shift; r.qhw_shift = p.qhw_shift; r.so = L.so; r.OH = L.OH; r.OW = L.OW;
-    r.Cout = L.Cout; r.y_stride = y_stride;
+    r.Cout = L.Cout; r.y_stride = y_stride; r.b_shift = p.b_shift; r.nimg = nimg;
     HIPCHK(h, launch_tapgemm_reduce(S->cfg, r, S->ntiles, (S->max_nsplit >= 8 && h->opt.tg_reduce_kp > 1) ? 4 : 1, st));
   }
   if (ev) {

@@ -243,6 +243,7 @@ int ian_layer_create(const ian_op_desc* desc, int32_t deconv_flip, ian_layer** o
   }
   std::unique_ptr<ian_layer> l(new ian_layer());
   ian_handle* h = &l->ctx;
+  h->opt.tg_pos_major = 0;   // the training step keeps image-major rows (its statistics epilogues are defined in that order); IAN_OPTS may say otherwise
   apply_env_options(h->opt);
   h->desc.deconv_flip = deconv_flip;
   h->finalized = true;

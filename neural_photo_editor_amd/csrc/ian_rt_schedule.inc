@@ -1,4 +1,4 @@
-// ian_rt_schedule.inc -- tapgemm scheduling: tiles, split-K, heavy-first + XCD-aware item order.
+// ian_rt_schedule.inc -- tapgemm scheduling: tile shape, row order and split policy per launch; the item list itself is ian_tg_plan.h's.
 // Part of the libian runtime: one translation unit, included by ian_runtime.cpp in this order (see the list there).
 namespace {
 
@@ -32,6 +32,41 @@ static inline bool bf16x3_applies(const ian_handle* h, int M, int nimg) {
   return h->opt.tg_bf16x3 && M >= h->opt.tg_bf16x3_min_m && nimg >= h->opt.tg_bf16x3_min_images;
 }
 
+// Workgroups of a tile shape one CU holds at once (LDS of the two staging buffers, 160 KB per CU; waves per SIMD <= 8 is never the
+// limit for these shapes): what "one round" of a launch is.
+static int tg_slots(int cfg) {
+  const TgShape sh = tg_shape(cfg);
+  const size_t lds = (size_t)2 * (sh.bm + sh.bn) * 36 * sizeof(float);
+  int per_cu = (int)((160u << 10) / lds);
+  const int waves = (cfg == TG_128x128W8 || cfg == TG_128x64W8) ? 8 : 4;
+  per_cu = std::min(per_cu, 32 / waves);
+  return 256 * std::max(1, per_cu);
+}
+
+// the planner's view of a layer at one batch, tile shape and split limit (ian_tg_plan.h)
+static TgPlanIn plan_input(const ian_handle* h, const TgLayer& L, int nimg, int cfg, int max_steps, int pos_major) {
+  const TgShape sh = tg_shape(cfg);
+  TgPlanIn in;
+  in.nimg = nimg; in.QH = L.QH; in.QW = L.QW; in.IH = L.IH; in.IW = L.IW; in.si = L.si; in.by = L.by; in.bx = L.bx;
+  in.Cin = L.Cin; in.Cout = L.Cout;
+  in.classes = L.classes.data(); in.ncls = (int)L.classes.size(); in.taps = L.taps.data(); in.ntaps_total = (int)L.taps.size();
+  in.bm = sh.bm; in.bn = sh.bn; in.pos_major = pos_major; in.max_steps = max_steps;
+  in.opt_split = h->opt.tg_split; in.opt_no_split_items = h->opt.tg_no_split_items; in.opt_target_items = h->opt.tg_target_items;
+  in.opt_min_steps = h->opt.tg_min_steps; in.xcd_group = h->opt.tg_xcd_group; in.xcd_spatial = h->opt.tg_xcd_spatial;
+  return in;
+}
+
+// May a launch of this layer over nimg images take position-major rows (option tg_pos_major)?  2: always (tests: any batch, ragged rows
+// of a position are padding).  1: batches that are a power of two >= 64 -- a tile then covers at most two positions -- unless the
+// split-bf16 kernel (image-major only) takes the launch or a statistics request is waiting: the statistics' chunk boundaries are defined
+// in the image-major row order (TgStats), and a request that meets a position-major schedule later is declined like one that meets a
+// split one (run_tapgemm).
+static bool pos_major_allowed(const ian_handle* h, const TgLayer& L, int nimg) {
+  if (bf16x3_applies(h, nimg * L.QH * L.QW, nimg) || ilog2_exact(L.QH * L.QW) < 0) return false;
+  if (h->opt.tg_pos_major == 2) return true;
+  return h->opt.tg_pos_major == 1 && nimg >= 64 && ilog2_exact(nimg) >= 0 && h->stats_next.mode == 0;
+}
+
 void build_schedule(const ian_handle* h, const TgLayer& L, int nimg, Schedule& S, const TgChoice& ch) {
   const int M = nimg * L.QH * L.QW;
   S.cfg = (ch.cfg >= 0 && ch.cfg < TG_NCONFIG && L.CoutPad % tg_shape(ch.cfg).bn == 0) ? ch.cfg : pick_config(h, L, M);
@@ -40,125 +75,36 @@ void build_schedule(const ian_handle* h, const TgLayer& L, int nimg, Schedule& S
   if (!tg_fuse_supported(S.cfg) || S.fused < 0 || S.fused > 2) S.fused = 0;   // the large tiles are compiled without the in-launch combine; anything out of range = reduce launch
   S.bf16x3 = bf16x3_applies(h, M, nimg) && tg_bf16x3_supported(S.cfg);
   if (S.bf16x3) S.fused = 0;   // the split-bf16 kernel writes plain slabs: always the reduce launch
-  const TgShape sh = tg_shape(S.cfg);
-  const int tiles_m = (M + sh.bm - 1) / sh.bm;
-  const int tiles_n = (L.Cout + sh.bn - 1) / sh.bn;
-  const int kpt = L.Cin / 32;
-  const int ncls = (int)L.classes.size();
-  long long total_steps = 0;
-  int total_tiles = 0;
-  for (auto& c : L.classes) {
-    total_steps += (long long)tiles_m * tiles_n * c.ntaps * kpt;
-    total_tiles += tiles_m * tiles_n;
+  // row order: forced by the option, the tuner's choice, or -- untuned -- position-major where the launch model predicts a shorter launch
+  const bool allowed = pos_major_allowed(h, L, nimg) && !S.bf16x3;
+  TgPlan P;
+  if (allowed && h->opt.tg_pos_major != 2 && ch.pos_major < 0) {
+    TgPlan Q;
+    tg_plan(plan_input(h, L, nimg, S.cfg, ch.max_steps, 0), P);
+    tg_plan(plan_input(h, L, nimg, S.cfg, ch.max_steps, 1), Q);
+    auto makespan = [&](const TgPlan& pl) {
+      std::vector<int> lens;
+      for (auto& it : pl.items)
+        if (it.ks1 > it.ks0) lens.push_back(it.ks1 - it.ks0);
+      return tg_model_makespan(lens, 0, tg_slots(S.cfg));
+    };
+    if (Q.steps < P.steps && makespan(Q) < makespan(P)) P = std::move(Q);
+  } else {
+    tg_plan(plan_input(h, L, nimg, S.cfg, ch.max_steps, allowed && (h->opt.tg_pos_major == 2 || ch.pos_major == 1) ? 1 : 0), P);
   }
-  int steps_per_item = 1 << 30;
-  bool split = false;
-  if (ch.max_steps > 0) {
-    steps_per_item = ch.max_steps;
-  } else if (ch.max_steps < 0 && h->opt.tg_split && total_tiles < h->opt.tg_no_split_items) {
-    long long spi = (total_steps + h->opt.tg_target_items - 1) / h->opt.tg_target_items;
-    steps_per_item = (int)std::max<long long>(spi, h->opt.tg_min_steps);
-  }
-  for (auto& c : L.classes)
-    if (c.ntaps * kpt > steps_per_item) split = true;
-  struct Group {
-    std::vector<TgItem> items;
-    int weight;
-  };
-  std::vector<Group> groups;
-  int gm = std::max(1, h->opt.tg_xcd_group), gn = std::max(1, h->opt.tg_xcd_group);
-  S.h_tiles.clear();
-  S.max_nsplit = 1;
-  size_t slab_next = 0;
-  // tile -> slab bookkeeping
-  std::vector<std::vector<int>> nsplit_c(ncls);
-  for (int c = 0; c < ncls; ++c) {
-    const int ksteps = L.classes[c].ntaps * kpt;
-    int ns = 1;
-    if (split) ns = std::max(1, (ksteps + steps_per_item - 1) / steps_per_item);
-    const int per = (ksteps + ns - 1) / ns;
-    ns = (ksteps + per - 1) / per;
-    if (split) S.max_nsplit = std::max(S.max_nsplit, ns);
-    // slab indices: tile-major so that the reduce pass reads contiguous slabs
-    std::vector<int> slab0((size_t)tiles_m * tiles_n, -1), tile_id((size_t)tiles_m * tiles_n, -1);
-    if (split) {
-      for (int mt = 0; mt < tiles_m; ++mt)
-        for (int nt = 0; nt < tiles_n; ++nt) {
-          slab0[(size_t)mt * tiles_n + nt] = (int)slab_next;
-          tile_id[(size_t)mt * tiles_n + nt] = (int)S.h_tiles.size();
-          TgTile t{c, mt * sh.bm, nt * sh.bn, (int)slab_next, ns, L.classes[c].py, L.classes[c].px, 0};
-          S.h_tiles.push_back(t);
-          slab_next += ns;
-        }
-    }
-    for (int s = 0; s < ns; ++s) {
-      const int k0 = s * per, k1 = std::min(ksteps, (s + 1) * per);
-      for (int nb = 0; nb < tiles_n; nb += gn)
-        for (int mb = 0; mb < tiles_m; mb += gm) {
-          Group g;
-          g.weight = k1 - k0;
-          for (int nt = nb; nt < std::min(tiles_n, nb + gn); ++nt)
-            for (int mt = mb; mt < std::min(tiles_m, mb + gm); ++mt) {
-              TgItem it{c, mt * sh.bm, nt * sh.bn, k0, k1, split ? slab0[(size_t)mt * tiles_n + nt] + s : -1,
-                        tile_id[(size_t)mt * tiles_n + nt], 0};
-              g.items.push_back(it);
-            }
-          groups.push_back(std::move(g));
-        }
-    }
-  }
-  std::stable_sort(groups.begin(), groups.end(), [](const Group& a, const Group& b) { return a.weight > b.weight; });
-  // deal supergroups to the 8 XCDs (block b runs on XCD b%8; observed, used for speed only): always to the least-loaded list.
-  // Groups arrive heavy first; inside a run of EQUAL weight they are in (class, K-slice, N block, M block) order.
-  // tg_xcd_spatial (round-4 experiment, default OFF): cut such a run into 8 CONTIGUOUS pieces, one per XCD, so that spatial
-  // neighbours share an L2.  Measured at batch 64 (profiles/r04_*): step time unchanged (1.5137 vs 1.5122 ms), HBM fetch per
-  // tapgemm launch UP from 85 to 122 MB -- round-robin dealing of 8x8-tile supergroups already keeps a group's halo and weight
-  // slab in one L2, and contiguous pieces put all K-slices / N blocks of a piece on one XCD at the same time, which evicts more.
-  // The order of items changes, no item's K range or summation order does: results are bitwise the same either way.
-  std::vector<std::vector<TgItem>> lists(8);
-  std::vector<long long> load(8, 0);
-  for (size_t g0 = 0; g0 < groups.size();) {
-    size_t g1 = g0 + 1;
-    while (g1 < groups.size() && groups[g1].weight == groups[g0].weight && groups[g1].items.size() == groups[g0].items.size()) ++g1;
-    const size_t run = g1 - g0;
-    if (h->opt.tg_xcd_spatial && run >= 8) {
-      // XCDs ordered by current load: the least loaded one takes the first (possibly one-longer) piece
-      int order[8] = {0, 1, 2, 3, 4, 5, 6, 7};
-      std::stable_sort(order, order + 8, [&](int a, int b) { return load[a] < load[b]; });
-      for (size_t k = 0; k < run; ++k) {
-        const int x = order[(k * 8) / run];
-        Group& g = groups[g0 + k];
-        for (auto& it : g.items) lists[x].push_back(it);
-        load[x] += (long long)g.weight * g.items.size();
-      }
-    } else {
-      for (size_t k = g0; k < g1; ++k) {
-        Group& g = groups[k];
-        int best = 0;
-        for (int x = 1; x < 8; ++x)
-          if (load[x] < load[best]) best = x;
-        for (auto& it : g.items) lists[best].push_back(it);
-        load[best] += (long long)g.weight * g.items.size();
-      }
-    }
-    g0 = g1;
-  }
-  size_t longest = 0;
-  for (auto& l : lists) longest = std::max(longest, l.size());
-  S.h_items.clear();
-  const TgItem empty{0, 0, 0, 0, 0, -1, 0, 0};
-  for (size_t k = 0; k < longest; ++k)
-    for (int x = 0; x < 8; ++x) S.h_items.push_back(k < lists[x].size() ? lists[x][k] : empty);
-  while (!S.h_items.empty() && S.h_items.back().ks0 >= S.h_items.back().ks1) S.h_items.pop_back();
-  for (auto& it : S.h_items) {   // the item carries its class and first tap (TgItem, ian_internal.h)
-    const TgClass& c = L.classes[it.cls];
-    it.ntaps = c.ntaps; it.tap0 = c.tap0; it.py = c.py; it.px = c.px; it.w_off = c.w_off;
-    const TgTap& t = L.taps[c.tap0 + std::min(std::max(c.ntaps - 1, 0), it.ks0 / std::max(1, kpt))];
-    it.dy0 = t.dy; it.dx0 = t.dx;
-  }
+  S.pos_major = P.b_shift >= 0;
+  if (S.pos_major) S.fused = 0;   // the in-launch combine skips row quads beyond M: an image-major notion
+  S.M = P.M;
+  S.b_shift = P.b_shift;
+  S.steps = P.steps;
+  S.steps_full = P.steps_full;
+  S.max_nsplit = P.max_nsplit;
+  S.h_items = std::move(P.items);
+  S.h_tiles = std::move(P.tiles);
+  S.h_ttaps = std::move(P.taptab);
   S.nitems = (int)S.h_items.size();
-  S.ntiles = split ? (int)S.h_tiles.size() : 0;
-  S.slab_tiles = slab_next;
+  S.ntiles = P.split ? (int)S.h_tiles.size() : 0;
+  S.slab_tiles = P.slab_tiles;
 }
 
 int get_schedule(ian_handle* h, TgLayer& L, int nimg, Schedule** out) {
@@ -170,6 +116,7 @@ int get_schedule(ian_handle* h, TgLayer& L, int nimg, Schedule** out) {
     int rc;
     if ((rc = upload(h, S.h_items, &S.d_items))) return rc;
     if ((rc = upload(h, S.h_tiles, &S.d_tiles))) return rc;
+    if ((rc = upload(h, S.h_ttaps, &S.d_ttaps))) return rc;
     if (S.ntiles > 0) {
       HIPCHK(h, hipMalloc((void**)&S.d_counters, S.ntiles * sizeof(int)));
       HIPCHK(h, hipMemset(S.d_counters, 0, S.ntiles * sizeof(int)));
@@ -198,6 +145,7 @@ void free_schedule_for(TgLayer& L, int nimg) {
   if (it == L.sched.end()) return;
   if (it->second.d_items) (void)hipFree(it->second.d_items);
   if (it->second.d_tiles) (void)hipFree(it->second.d_tiles);
+  if (it->second.d_ttaps) (void)hipFree(it->second.d_ttaps);
   if (it->second.d_counters) (void)hipFree(it->second.d_counters);
   if (it->second.d_raw) (void)hipFree(it->second.d_raw);
   L.sched.erase(it);
@@ -207,6 +155,7 @@ void free_schedules(TgLayer& L) {
   for (auto& kv : L.sched) {
     if (kv.second.d_items) (void)hipFree(kv.second.d_items);
     if (kv.second.d_tiles) (void)hipFree(kv.second.d_tiles);
+    if (kv.second.d_ttaps) (void)hipFree(kv.second.d_ttaps);
     if (kv.second.d_counters) (void)hipFree(kv.second.d_counters);
     if (kv.second.d_raw) (void)hipFree(kv.second.d_raw);
   }

@@ -35,6 +35,12 @@ struct Schedule {
   int max_nsplit = 1;
   std::vector<TgItem> h_items;  // kept for tests / debugging
   std::vector<TgTile> h_tiles;
+  // row order and tap lists (ian_tg_types.h, ian_tg_plan.h): M rows; position-major schedules carry b_shift >= 0 and per-tile tap lists
+  bool pos_major = false;
+  int M = 0, b_shift = -1;
+  long long steps = 0, steps_full = 0;   // K-steps the launch executes / would with every tile listing every tap
+  TgTapE* d_ttaps = nullptr;             // the schedule's tap table (TgItem::tap0 indexes it)
+  std::vector<TgTapE> h_ttaps;
 };
 
 struct TgChoice {  // autotuned (or forced) schedule shape for one (layer, batch)
@@ -42,6 +48,7 @@ struct TgChoice {  // autotuned (or forced) schedule shape for one (layer, batch
   int max_steps = -1;  // -1 = heuristic, 0 = never split K, >0 = split so that no item exceeds this many K-steps
   int variant = -1;    // K-loop schedule of tapgemm_kernel, -1 = the handle's option
   int fused = -1;      // split-K combine: -1 = the handle's option (tg_fuse for small M), 0 reduce launch, 1 in-launch slabs, 2 atomics
+  int pos_major = -1;  // row order: -1 = the launch model decides where option tg_pos_major admits it, 0 image-major, 1 position-major
 };
 
 // one linear map executed by the tapgemm kernel (forward or backward-data form of an op)
@@ -102,6 +109,9 @@ struct Options {
   int tg_min_steps = 16;      // never make a K-range shorter than this many 32-channel steps
   int tg_no_split_items = 384;  // do not split when tiles alone give at least this many workgroups
   int tg_split = 1;
+  int tg_pos_major = 1;       // position-major tile rows with the out-of-image taps of a tile skipped (ian_tg_plan.h): 0 off, 1 auto (batches
+                              // that are a power of two >= 64, per layer where the tuner / the launch model finds it faster), 2 forced for
+                              // any batch (tests).  Training layer contexts default to 0.
   int tg_xcd_group = 8;       // supergroup edge (tiles) dealt to one XCD
   int tg_xcd_spatial = 0;            // experiment (round 4, OFF): equal-weight runs of tile groups dealt to the XCDs in contiguous pieces instead of
                                      // round-robin.  Measured: same step time, HBM fetch per tapgemm launch 85 -> 122 MB at batch 64

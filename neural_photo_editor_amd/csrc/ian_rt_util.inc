@@ -10,6 +10,7 @@ bool apply_option(Options& o, const std::string& k, int value) {
   else if (k == "tg_min_steps") o.tg_min_steps = std::max(1, value);
   else if (k == "tg_no_split_items") o.tg_no_split_items = value;
   else if (k == "tg_split") o.tg_split = value;
+  else if (k == "tg_pos_major") { if (value < 0 || value > 2) return false; o.tg_pos_major = value; }
   else if (k == "tg_xcd_group") o.tg_xcd_group = std::max(1, value);
   else if (k == "tg_xcd_spatial") o.tg_xcd_spatial = value;
   else if (k == "tg_prefer_nosplit") o.tg_prefer_nosplit = value;

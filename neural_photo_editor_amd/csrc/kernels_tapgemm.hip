@@ -211,6 +211,25 @@ __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t rsrc, unsigned
   return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, 0, 0));
 }
 
+// One row m of the implicit GEMM -> its image and its position in the class grid, for both row orders (ian_tg_types.h): image-major
+// m = (n, qy, qx), position-major m = pos * Bp + n with the rows n >= nimg of every position padding.  The ONE place that knows the
+// order: the prologues of the two kernels, the three epilogues and the reduce pass call it, always outside the K loop.
+struct TgRow {
+  int n, qy, qx;
+  bool valid;
+};
+__device__ __forceinline__ TgRow tg_row(int m, int M, int qw_shift, int qhw_shift, int b_shift, int nimg) {
+  const bool pm = b_shift >= 0;   // uniform over the launch
+  const int n = pm ? (m & ((1 << b_shift) - 1)) : (m >> qhw_shift);
+  const int rem = pm ? (m >> b_shift) : (m & ((1 << qhw_shift) - 1));
+  TgRow r;
+  r.n = n;
+  r.qy = rem >> qw_shift;
+  r.qx = rem & ((1 << qw_shift) - 1);
+  r.valid = (m < M) & (n < nimg);   // image-major: n < nimg says the same as m < M
+  return r;
+}
+
 // The epilogue of a tile whose columns all exist and whose affine is per channel (round 6).  Behind the K loop every wave of a SIMD runs
 // this at the same time with no MFMA left to hide it: a timing-only build that returns after the K loop (tg_noepi) put 5 % of the batch-64
 // step behind it, and the general form below spends ~40 vector instructions per stored value (64-bit addresses, the per-value scale /
@@ -223,7 +242,6 @@ __device__ __forceinline__ void tg_store_fast(const TgParams& p, const TgItem& i
                                               f32x16 (&acc)[BM / WM / 32][BN / WN / 32], int wm, int wn, int lane) {
   constexpr int FM = BM / WM / 32, FN = BN / WN / 32;
   const TgEpilogue& e = p.epi;
-  const int qhw_mask = (1 << p.qhw_shift) - 1, qw_mask = (1 << p.qw_shift) - 1;
   const int rhalf = 4 * (lane >> 5);
   const int c0 = it.n0 + wn * (BN / WN) + (lane & 31);
   float sc[FN], sh[FN];
@@ -237,19 +255,19 @@ __device__ __forceinline__ void tg_store_fast(const TgParams& p, const TgItem& i
   const __amdgpu_buffer_rsrc_t fr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e.yfwd ? e.yfwd : p.y), 0, p.y_bytes, 0x00020000);
   const unsigned colb = (unsigned)c0 * 4u, ystr = (unsigned)p.y_stride * 4u;
   const bool fwd = e.mode == TG_EPI_FWD, has_res = e.res != nullptr, has_yf = e.yfwd != nullptr;
-  const bool ident = p.so == 1 && cl.py == 0 && cl.px == 0 && (1 << p.qw_shift) == p.OW && (1 << p.qhw_shift) == p.OH * p.OW;   // wave-uniform
+  const bool ident = p.so == 1 && cl.py == 0 && cl.px == 0 && (1 << p.qw_shift) == p.OW && (1 << p.qhw_shift) == p.OH * p.OW && p.b_shift < 0;   // wave-uniform
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = it.m0 + wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + rhalf;
       unsigned pix = (unsigned)m;                    // stride-1 layers whose output map is the tile-row map: the pixel IS the row
+      const TgRow rw = tg_row(m, p.M, p.qw_shift, p.qhw_shift, p.b_shift, p.nimg);
       if (!ident) {
-        const int n = m >> p.qhw_shift, rem = m & qhw_mask;
-        const int oy = (rem >> p.qw_shift) * p.so + cl.py, ox = (rem & qw_mask) * p.so + cl.px;
-        pix = (unsigned)((n * p.OH + oy) * p.OW + ox);
+        const int oy = rw.qy * p.so + cl.py, ox = rw.qx * p.so + cl.px;
+        pix = (unsigned)((rw.n * p.OH + oy) * p.OW + ox);
       }
-      const unsigned off = (m < p.M) ? pix * ystr + colb : TG_OOB_Y;
+      const unsigned off = rw.valid ? pix * ystr + colb : TG_OOB_Y;
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         const unsigned o = off + (unsigned)(j * 128);
@@ -276,7 +294,6 @@ __device__ __forceinline__ void tg_store(const TgParams& p, const TgItem& it, co
     tg_store_fast<BM, BN, WM, WN>(p, it, cl, acc, wm, wn, lane);
     return;
   }
-  const int qhw_mask = (1 << p.qhw_shift) - 1, qw_mask = (1 << p.qw_shift) - 1;
   const int col_l = lane & 31;
   const int rhalf = 4 * (lane >> 5);
 #pragma unroll
@@ -285,11 +302,10 @@ __device__ __forceinline__ void tg_store(const TgParams& p, const TgItem& it, co
     for (int r = 0; r < 16; ++r) {
       const int row = wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + rhalf;
       const int m = it.m0 + row;
-      if (m >= p.M) continue;
-      const int n = m >> p.qhw_shift;
-      const int rem = m & qhw_mask;
-      const int oy = (rem >> p.qw_shift) * p.so + cl.py, ox = (rem & qw_mask) * p.so + cl.px;
-      const size_t pix = ((size_t)n * p.OH + oy) * p.OW + ox;
+      const TgRow rw = tg_row(m, p.M, p.qw_shift, p.qhw_shift, p.b_shift, p.nimg);
+      if (!rw.valid) continue;
+      const int oy = rw.qy * p.so + cl.py, ox = rw.qx * p.so + cl.px;
+      const size_t pix = ((size_t)rw.n * p.OH + oy) * p.OW + ox;
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         const int c = it.n0 + wn * (BN / WN) + j * 32 + col_l;
@@ -310,7 +326,6 @@ __device__ __forceinline__ void tg_store_stats(const TgParams& p, const TgItem& 
                                                f32x16 (&acc)[BM / WM / 32][BN / WN / 32], int wm, int wn, int lane, double* red) {
   constexpr int FM = BM / WM / 32, FN = BN / WN / 32, NW = WM * WN, CW = BN / WN;   // CW: columns of one wave
   const TgStats& st = p.epi.st;
-  const int qhw_mask = (1 << p.qhw_shift) - 1, qw_mask = (1 << p.qw_shift) - 1;
   const int col_l = lane & 31, half = lane >> 5;
   const int rhalf = 4 * half;
   double d1[FN], d2[FN];
@@ -334,11 +349,10 @@ __device__ __forceinline__ void tg_store_stats(const TgParams& p, const TgItem& 
     for (int r = 0; r < 16; ++r) {
       const int row = wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + rhalf;
       const int m = it.m0 + row;
-      ok[r] = m < p.M;
-      const int n = m >> p.qhw_shift;
-      const int rem = m & qhw_mask;
-      const int oy = (rem >> p.qw_shift) * p.so + cl.py, ox = (rem & qw_mask) * p.so + cl.px;
-      yo[r] = ok[r] ? (((size_t)n * p.OH + oy) * p.OW + ox) * p.y_stride : 0;
+      const TgRow rw = tg_row(m, p.M, p.qw_shift, p.qhw_shift, p.b_shift, p.nimg);
+      ok[r] = rw.valid;
+      const int oy = rw.qy * p.so + cl.py, ox = rw.qx * p.so + cl.px;
+      yo[r] = ok[r] ? (((size_t)rw.n * p.OH + oy) * p.OW + ox) * p.y_stride : 0;
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         const int c = it.n0 + wn * CW + j * 32 + col_l;
@@ -458,12 +472,14 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
   TG_CLK_BEGIN();
   const TgItem it = p.items[blockIdx.x];
   if (it.ks0 >= it.ks1) return;  // padding item
-  // the item carries its class and the tap its K range starts in (TgItem, ian_internal.h): ONE table fetch in front of the first
-  // operand load instead of three dependent ones (item -> p.classes[cls] -> p.taps[tap0 + ..])
+  // the item carries its class and the tap its K range starts in (TgItem, ian_tg_types.h): ONE table fetch in front of the first
+  // operand load instead of three dependent ones (item -> p.classes[cls] -> tap table).  cl.tap0 / cl.ntaps are the TILE's tap list
+  // in the schedule's table p.ttaps: the taps of the class that some valid row of the tile reads inside the image (every tap, for an
+  // image-major schedule), each with the index of its weight slab in the class.
   TgClass cl;
   cl.ntaps = it.ntaps; cl.tap0 = it.tap0; cl.py = it.py; cl.px = it.px; cl.w_off = it.w_off;
-  TgTap tp_first;
-  tp_first.dy = it.dy0; tp_first.dx = it.dx0;
+  TgTapE tp_first;
+  tp_first.dy = it.dy0; tp_first.dx = it.dx0; tp_first.slab = it.slab0; tp_first.pad = 0;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -483,17 +499,13 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
   const int c4 = DMA ? (((tid & 7) ^ ((r0 >> 1) & 7)) * 4) : (tid & 7) * 4;
   int a_iy0[A_CH], a_ix0[A_CH];
   unsigned a_off[A_CH];  // byte offsets (may wrap for halo pixels; those are replaced by the OOB offset)
-  const int qhw_mask = (1 << p.qhw_shift) - 1, qw_mask = (1 << p.qw_shift) - 1;
 #pragma unroll
   for (int j = 0; j < A_CH; ++j) {
-    const int m = it.m0 + r0 + RS * j;
-    const int n = m >> p.qhw_shift;
-    const int rem = m & qhw_mask;
-    const int qy = rem >> p.qw_shift, qx = rem & qw_mask;
-    const int iy0 = qy * p.si + p.by, ix0 = qx * p.si + p.bx;
-    a_iy0[j] = (m < p.M) ? iy0 : -100000;  // invalid rows fail every bounds test
+    const TgRow rw = tg_row(it.m0 + r0 + RS * j, p.M, p.qw_shift, p.qhw_shift, p.b_shift, p.nimg);
+    const int iy0 = rw.qy * p.si + p.by, ix0 = rw.qx * p.si + p.bx;
+    a_iy0[j] = rw.valid ? iy0 : -100000;  // invalid rows fail every bounds test
     a_ix0[j] = ix0;
-    a_off[j] = (unsigned)((((n * p.IH + iy0) * p.IW + ix0) * p.Cin + c4) * 4);
+    a_off[j] = (unsigned)((((rw.n * p.IH + iy0) * p.IW + ix0) * p.Cin + c4) * 4);
   }
   const int kpt = p.Cin >> 5;  // K-steps per tap
   const unsigned slab_bytes = (unsigned)p.CoutPad * (unsigned)p.Cin * 4u;
@@ -512,17 +524,17 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-#define TG_LOAD_INTO(RA, RB) TG_LOAD_INTO_TP(RA, RB, p.taps[cl.tap0 + tap])
+#define TG_LOAD_INTO(RA, RB) TG_LOAD_INTO_TP(RA, RB, p.ttaps[cl.tap0 + tap])
 #define TG_LOAD_INTO_TP(RA, RB, TP)                                                                      \
   {                                                                                                      \
-    const TgTap tp = TP;                                                                                 \
+    const TgTapE tp = TP;                                                                                \
     const unsigned doff = (unsigned)(((tp.dy * p.IW + tp.dx) * p.Cin + (cstep << 5)) * 4);               \
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);                 \
       RA[j] = buf_load4(xrsrc, ok ? a_off[j] + doff : TG_OOB_STEP, 0);                                   \
     }                                                                                                    \
-    const unsigned wsoff = w_cls + (unsigned)tap * slab_bytes + (unsigned)(cstep << 7);                         \
+    const unsigned wsoff = w_cls + (unsigned)tp.slab * slab_bytes + (unsigned)(cstep << 7);              \
     _Pragma("unroll") for (int j = 0; j < B_CH; ++j) RB[j] = buf_load4(wrsrc, w_row + j * w_rstep, wsoff); \
     if (++cstep == kpt) {                                                                                \
       cstep = 0;                                                                                         \
@@ -536,14 +548,14 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
 #define TG_LOAD_LIVE_INTO(RA, RB, LIVE)                                                                  \
   {                                                                                                      \
     const bool live_ = (LIVE);                                                                           \
-    const TgTap tp = p.taps[cl.tap0 + (live_ ? tap : 0)];                                                \
+    const TgTapE tp = p.ttaps[cl.tap0 + (live_ ? tap : 0)];                                              \
     const unsigned doff = (unsigned)(((tp.dy * p.IW + tp.dx) * p.Cin + (cstep << 5)) * 4);               \
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = live_ & ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);         \
       RA[j] = buf_load4(xrsrc, ok ? a_off[j] + doff : TG_OOB_STEP, 0);                                   \
     }                                                                                                    \
-    const unsigned wsoff = live_ ? w_cls + (unsigned)tap * slab_bytes + (unsigned)(cstep << 7) : 0u;     \
+    const unsigned wsoff = live_ ? w_cls + (unsigned)tp.slab * slab_bytes + (unsigned)(cstep << 7) : 0u; \
     _Pragma("unroll") for (int j = 0; j < B_CH; ++j) RB[j] = buf_load4(wrsrc, live_ ? w_row + j * w_rstep : TG_OOB_STEP, wsoff); \
     if (++cstep == kpt) {                                                                                \
       cstep = 0;                                                                                         \
@@ -577,14 +589,14 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
     float* Bs3 = smem + 2 * BM * 32;   // [2][BN][32]
 #define TG_DMA_TILE(buf)                                                                                 \
   {                                                                                                      \
-    const TgTap tp = p.taps[cl.tap0 + tap];                                                              \
+    const TgTapE tp = p.ttaps[cl.tap0 + tap];                                                            \
     const unsigned doff = (unsigned)(((tp.dy * p.IW + tp.dx) * p.Cin + (cstep << 5)) * 4);               \
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);                 \
       tg_dma16(xrsrc, As3 + ((buf) * BM + wave * 8 + RS * j) * 32, ok ? a_off[j] + doff : TG_OOB_STEP, 0);  \
     }                                                                                                    \
-    const unsigned wsoff = w_cls + (unsigned)tap * slab_bytes + (unsigned)(cstep << 7);                  \
+    const unsigned wsoff = w_cls + (unsigned)tp.slab * slab_bytes + (unsigned)(cstep << 7);              \
     _Pragma("unroll") for (int j = 0; j < B_CH; ++j)                                                     \
       tg_dma16(wrsrc, Bs3 + ((buf) * BN + wave * 8 + RS * j) * 32, w_row + j * w_rstep, wsoff);          \
     if (++cstep == kpt) {                                                                                \
@@ -659,17 +671,17 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_ke
     float4 av[FM], bv[FN], aw[FM], bw[FN];
     unsigned a_vo[A_CH];                              // byte offset of (tile row j, current tap, channel 0), or TG_OOB_TAP
     unsigned w_so = 0;                                // byte offset of the current tap's weight slab (wave-uniform)
-#define TG_TAP_SETUP() TG_TAP_SETUP_TP(p.taps[cl.tap0 + min(tap, cl.ntaps - 1)])
+#define TG_TAP_SETUP() TG_TAP_SETUP_TP(p.ttaps[cl.tap0 + min(tap, cl.ntaps - 1)])
 #define TG_TAP_SETUP_TP(TP)                                                                              \
   {                                                                                                      \
-    const TgTap tp = TP;                                                                                 \
+    const TgTapE tp = TP;                                                                                \
     const unsigned toff = (unsigned)(((tp.dy * p.IW + tp.dx) * p.Cin) * 4);                              \
     _Pragma("unroll") for (int j = 0; j < A_CH; ++j) {                                                   \
       const int iy = a_iy0[j] + tp.dy, ix = a_ix0[j] + tp.dx;                                            \
       const bool ok = ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);                 \
       a_vo[j] = ok ? a_off[j] + toff : TG_OOB_TAP;                                                       \
     }                                                                                                    \
-    w_so = w_cls + (unsigned)tap * slab_bytes;                                                           \
+    w_so = w_cls + (unsigned)tp.slab * slab_bytes;                                                       \
   }
 #define TG_LOAD7(RA, RB)                                                                                 \
   {                                                                                                      \
@@ -1135,17 +1147,13 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 4) void tapgemm_bf
   const int c8 = (tid & 3) * 8;
   int a_iy0[A_CH], a_ix0[A_CH];
   unsigned a_off[A_CH];
-  const int qhw_mask = (1 << p.qhw_shift) - 1, qw_mask = (1 << p.qw_shift) - 1;
 #pragma unroll
   for (int j = 0; j < A_CH; ++j) {
-    const int m = it.m0 + r0 + RS * j;
-    const int n = m >> p.qhw_shift;
-    const int rem = m & qhw_mask;
-    const int qy = rem >> p.qw_shift, qx = rem & qw_mask;
-    const int iy0 = qy * p.si + p.by, ix0 = qx * p.si + p.bx;
-    a_iy0[j] = (m < p.M) ? iy0 : -100000;
+    const TgRow rw = tg_row(it.m0 + r0 + RS * j, p.M, p.qw_shift, p.qhw_shift, p.b_shift, p.nimg);
+    const int iy0 = rw.qy * p.si + p.by, ix0 = rw.qx * p.si + p.bx;
+    a_iy0[j] = rw.valid ? iy0 : -100000;
     a_ix0[j] = ix0;
-    a_off[j] = (unsigned)((((n * p.IH + iy0) * p.IW + ix0) * p.Cin + c8) * 4);
+    a_off[j] = (unsigned)((((rw.n * p.IH + iy0) * p.IW + ix0) * p.Cin + c8) * 4);
   }
   const int kpt = p.Cin >> 5;
   const unsigned slab_bytes = (unsigned)p.CoutPad * (unsigned)p.Cin * (unsigned)WB;
@@ -1433,9 +1441,9 @@ __device__ __forceinline__ void tg_reduce_body(const TgReduceParams& p) {
   const int rem_t = threadIdx.x % (CG * RPI);
   const int cg = rem_t % CG;
   const int row = (blockIdx.x % RG) * RPI + rem_t / CG;
-  const int qhw_mask = (1 << p.qhw_shift) - 1, qw_mask = (1 << p.qw_shift) - 1;
   const int m = t.m0 + row;
-  const bool live = m < p.M;
+  const TgRow rw = tg_row(m, p.M, p.qw_shift, p.qhw_shift, p.b_shift, p.nimg);
+  const bool live = rw.valid;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (live) {
     const int per = (t.nsplit + KP - 1) / KP;
@@ -1472,10 +1480,8 @@ __device__ __forceinline__ void tg_reduce_body(const TgReduceParams& p) {
     }
   }
   if (!live) return;
-  const int n = m >> p.qhw_shift;
-  const int rem = m & qhw_mask;
-  const int oy = (rem >> p.qw_shift) * p.so + t.py, ox = (rem & qw_mask) * p.so + t.px;
-  const size_t pix = ((size_t)n * p.OH + oy) * p.OW + ox;
+  const int oy = rw.qy * p.so + t.py, ox = rw.qx * p.so + t.px;
+  const size_t pix = ((size_t)rw.n * p.OH + oy) * p.OW + ox;
   const int c = t.n0 + cg * 4;
   const size_t yoff = pix * p.y_stride + c;
   const float v[4] = {s.x, s.y, s.z, s.w};
