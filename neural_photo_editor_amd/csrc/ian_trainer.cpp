@@ -56,6 +56,7 @@ const std::vector<DecStage>& dec_stages() {  // (deconv, cin, cout, in_hw, block
   return s;
 }
 const std::vector<int> HEAD_SCALES = {2, 3, 4};
+const std::pair<const char*, int> HEADS[5] = {{"R", 128}, {"G_a", 128}, {"G_b", 2}, {"B_a", 128}, {"B_b", 4}};   // RGB-Beta head MDCLs: name, cin
 inline int cs(int c) { return (c + 31) / 32 * 32; }
 
 std::vector<std::string> mdcl_names(const std::string& name, const std::vector<int>& scales) {
@@ -73,12 +74,23 @@ struct Shape {
   }
 };
 
-struct Group {  // one Adam instance: flat device buffers in the reference (Theano) layouts
-  std::vector<std::string> names;
-  std::map<std::string, std::pair<int64_t, Shape>> off;  // name -> (offset, shape)
+enum GroupId { G_ENC = 0, G_Z = 1, G_DEC = 2, G_STATS = 3 };  // encoder_params, Z_params, decoder_params; batch-norm running averages
+
+struct Group {  // flat device buffers in the reference (Theano) layouts; 0..2 are one Adam instance each, G_STATS is not trainable
+  std::vector<int> params;  // indices into ian_trainer::params, in declaration order
   int64_t numel = 0;
   float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
   int t = 0;
+};
+struct Param {
+  std::string name;
+  int group;
+  int64_t off;
+  Shape shape;
+};
+struct PRef {  // a parameter resolved by name at finalize: index into ian_trainer::params (mark, touched), value, gradient (null: running average)
+  int id = -1;
+  float *p = nullptr, *g = nullptr;
 };
 
 struct BN {  // Lasagne batch_norm in training mode: state of one normalisation in one pass
@@ -89,16 +101,49 @@ struct BN {  // Lasagne batch_norm in training mode: state of one normalisation 
 };
 
 struct LayerRef {
+  std::string key;
+  int kind = 0;
   ian_layer* l = nullptr;
-  std::vector<std::string> pnames;  // empty: weights are set elsewhere (the MinibatchLayer's normalised theta)
+  std::vector<int> ids;               // its parameters as mark() / ian_layer_set_params / ian_layer_backward_weight take them; empty:
+  std::vector<const float*> values;   // weights are set elsewhere (the MinibatchLayer's normalised theta)
+  std::vector<float*> grads;
+};
+struct Layers {  // every layer of IAN.py:67-228 by its Theano name (build_layers); enc_conv[1..4]; stage[i] = deconv, MDCL, MDCL2 of dec_stages()[i]
+  LayerRef *enc_conv[5], *enc_fc1, *enc_mu, *enc_logsigma, *mb, *l_dec_fc2, *stage[3][3], *dec_conv4, *R, *G_a, *G_b, *B_a, *B_b;
 };
 
-typedef std::map<std::string, float*> Bufs;
+// "linear layer + batch-norm + activation" of one pass -- Lasagne's batch_norm(layer) in training mode: built when the pass's buffers are
+// allocated (make_unit), run by unit_forward / unit_backward
+struct Unit {
+  LayerRef* L = nullptr;
+  BN bn;
+  float *y = nullptr, *a = nullptr;     // the layer's raw output, the normalised and activated output
+  float *dA = nullptr, *dy = nullptr;   // gradient wrt a (what the backward starts from), wrt y (dy == dA: in place)
+  int64_t rows = 0;
+  int C = 0, stride = 0, act = 0;
+  int ld = 0;                           // pixel stride handed to the layer calls (0 = the layer's own round_up(cout, 32))
+  bool epilogue = false;                // conv / deconv / MDCL: the GEMMs can carry the batch statistics in their epilogue (fused_stats)
+  PRef gamma, beta, run_mean, run_inv_std;
+};
+struct EncPass {  // encoder(X | X_hat | X_gen) + discriminator head; a[1..4] / da[1..4]: lrelu outputs of enc_conv1..4 and their gradients
+  float *x, *dx, *a[5], *da[5], *feat, *dfeat, *act, *dact, *mb, *dmb, *act_all, *dmb_all, *p, *loss, *dlogits;
+  Unit u[5];      // u[2..4]: enc_conv<i> + bnorm<i> + lrelu
+};
+struct ZPass {
+  Unit fc1, mu, ls;
+  float *z0, *z, *dz0, *kl;
+};
+struct DecPass {  // decoder(z | IAF(Z_rand))
+  float *h0, *dh0;
+  Unit stage[3][3];   // per dec_stages() entry: deconv, MDCL, MDCL2 (+ the block's input), each + bnorm<j> + lrelu
+  Unit u4;            // dec_conv4 + bnorm_dc4 + lrelu
+  float *R, *G, *B, *Ga, *Ba, *RG, *gR, *gG, *gB, *dRG, *dRt, *xhat, *dxhat, *tmp_img, *dz;
+};
 
 struct Bucket {  // a slice of one group's flat gradient buffer = one all-reduce message
-  int group;     // 0 encoder_params, 1 Z_params, 2 decoder_params
+  int group;     // GroupId
   int64_t lo, hi;
-  std::set<std::string> names;
+  std::set<int> params;
   int ready;     // index (1-based) of the last gradient write that lands in [lo, hi); 0: nothing writes it
   bool fired;
 };
@@ -113,10 +158,13 @@ struct ian_trainer {
   bool finalized = false;
   std::map<std::string, Shape> shapes;             // every parameter the graph owns
   std::map<std::string, std::vector<float>> host;  // values loaded before finalize
-  Group enc, zp, dec, stats;                       // stats: batch-norm running averages (not trainable)
-  std::map<std::string, Group*> where;
-  std::map<std::string, LayerRef> layers;
-  std::vector<std::string> layer_order;
+  Group grp[4];                                    // by GroupId
+  std::vector<Param> params;                       // every parameter that lives in a group
+  std::map<std::string, int> pindex;               // name -> index into params (the caller-facing entries and finalize only)
+  std::deque<LayerRef> layers;                     // in creation order
+  Layers L;
+  struct { PRef enc_conv1_b, mb_theta, mb_lws, mb_b, discrimi_W, l_dec_fc2_b; } pr;   // parameters the passes touch outside a layer or unit
+  std::string unresolved;                          // first name finalize could not resolve (finalize fails with it)
   std::vector<float*> allocs;
   std::map<const void*, size_t> alloc_floats;      // size of every allocation (ian_trainer_buffer)
   std::vector<float> masks[3];
@@ -128,9 +176,13 @@ struct ian_trainer {
   float *ws_loss = nullptr, *scalars = nullptr, *mb_W = nullptr, *mb_dW = nullptr, *mb_colscale = nullptr, *ortho_vals = nullptr;
   size_t ws_stats_cap = 0, gbuf_cap = 0;
   bool oom = false;                                 // a device allocation failed (checked at the end of finalize)
-  std::set<std::string> dirty, touched;
-  Bufs EX, EH, EG, ZS, DZ, DG;
-  std::map<std::string, BN> bnEX, bnEH, bnEG, bnZ, bnDZ, bnDG;
+  bool dirty[3] = {false, false, false};            // groups whose packed weights are stale (refresh_weights)
+  std::vector<char> touched;                        // per parameter: its gradient has been written in this sweep (the next write accumulates)
+  EncPass EX, EH, EG;
+  ZPass ZS;
+  DecPass DZ, DG;
+  std::map<std::string, float*> bufs;               // "<pass>.<name>" -> buffer and "<pass>.<bn>" -> statistics, filled by the *_alloc
+  std::map<std::string, BN*> bns;                   // functions: what ian_trainer_buffer serves (the step path does not look names up)
   float *zgen = nullptr, *zgen0 = nullptr, *xin = nullptr, *zin = nullptr, *epsin = nullptr;
   const float* X = nullptr;
   const float* eps = nullptr;
@@ -169,7 +221,7 @@ struct ian_trainer {
   std::map<int, std::vector<Bucket>> plans;         // per update kind (0 gen, 1 discrim)
   std::map<int, int> plan_key;
   std::vector<Bucket>* buckets = nullptr;           // the plan this sweep follows (nullptr: record, reduce at the end)
-  std::vector<std::vector<std::string>> evlog;      // gradient writes of this sweep, in issue order
+  std::vector<std::vector<int>> evlog;              // gradient writes of this sweep (parameter indices), in issue order
   int which_now = 0, nfired = 0;
   std::deque<OverlapRec> overlap_log;               // last few sweeps (tests/test_gpu_dp.py, bench.py)
   int measure_exposed = 0;
@@ -209,6 +261,7 @@ int tfail(ian_trainer* t, int code, const char* fmt, ...) {
     const int rc_ = (expr);                                                                           \
     if (rc_) return tfail(t, rc_, "%s failed (%d): %s", #expr, rc_, ian_layer_last_error(layer) ? ian_layer_last_error(layer) : "?"); \
   } while (0)
+#define LCALL(L, fn, ...) TL((L)->l, fn((L)->l, __VA_ARGS__))   // a call on a LayerRef*: the line names its layer once
 #define THIP(expr)                                                                                    \
   do {                                                                                                \
     const hipError_t e_ = (expr);                                                                     \
@@ -233,71 +286,77 @@ float* dalloc(ian_trainer* t, size_t floats) {   // zero-filled device floats; a
 }
 double* dalloc64(ian_trainer* t, size_t doubles) { return reinterpret_cast<double*>(dalloc(t, 2 * doubles)); }
 
-void add_param(ian_trainer* t, Group& g, const std::string& name, std::vector<int64_t> shape) {
+void add_param(ian_trainer* t, int group, const std::string& name, std::vector<int64_t> shape) {
+  Group& g = t->grp[group];
   Shape s{shape};
   t->shapes[name] = s;
-  g.names.push_back(name);
-  g.off[name] = {g.numel, s};
+  t->pindex[name] = (int)t->params.size();
+  g.params.push_back((int)t->params.size());
+  t->params.push_back({name, group, g.numel, s});
   g.numel += (s.numel() + 3) / 4 * 4;  // keep every tensor 16-byte aligned
-  t->where[name] = &g;
 }
-float* P(ian_trainer* t, const std::string& n) {
-  Group* g = t->where.at(n);
-  return g->p + g->off.at(n).first;
+// Names are resolved here, once, while ian_trainer_finalize wires the graph (the groups' buffers exist by then): a name that is not
+// declared is remembered and makes finalize fail; the step path holds PRef / LayerRef* / Unit and never looks a name up.
+PRef param(ian_trainer* t, const std::string& name) {
+  PRef r;
+  auto it = t->pindex.find(name);
+  if (it == t->pindex.end()) {
+    if (t->unresolved.empty()) t->unresolved = name;
+    return r;
+  }
+  const Param& q = t->params[it->second];
+  const Group& g = t->grp[q.group];
+  r.id = it->second;
+  r.p = g.p + q.off;
+  r.g = g.g ? g.g + q.off : nullptr;
+  return r;
 }
-float* G(ian_trainer* t, const std::string& n) {
-  Group* g = t->where.at(n);
-  return g->g + g->off.at(n).first;
-}
-int64_t numel_of(ian_trainer* t, const std::string& n) { return t->where.at(n)->off.at(n).second.numel(); }
-
 void declare_parameters(ian_trainer* t) {
   const int Z = t->cfg.num_latents;
-  add_param(t, t->enc, "enc_conv1.W", {128, 3, 5, 5});
-  add_param(t, t->enc, "enc_conv1.b", {128});
+  add_param(t, G_ENC, "enc_conv1.W", {128, 3, 5, 5});
+  add_param(t, G_ENC, "enc_conv1.b", {128});
   for (int i = 2; i <= 4; ++i) {
     const std::string s = std::to_string(i);
-    add_param(t, t->enc, "enc_conv" + s + ".W", {ENC_WIDTHS[i - 1], ENC_WIDTHS[i - 2], 5, 5});
-    add_param(t, t->enc, "bnorm" + s + ".beta", {ENC_WIDTHS[i - 1]});
-    add_param(t, t->enc, "bnorm" + s + ".gamma", {ENC_WIDTHS[i - 1]});
+    add_param(t, G_ENC, "enc_conv" + s + ".W", {ENC_WIDTHS[i - 1], ENC_WIDTHS[i - 2], 5, 5});
+    add_param(t, G_ENC, "bnorm" + s + ".beta", {ENC_WIDTHS[i - 1]});
+    add_param(t, G_ENC, "bnorm" + s + ".gamma", {ENC_WIDTHS[i - 1]});
   }
-  add_param(t, t->enc, "minibatch_discrim.theta", {1024, 500, 5});
-  add_param(t, t->enc, "minibatch_discrim.log_weight_scale", {500, 5});
-  add_param(t, t->enc, "minibatch_discrim.b", {500});
-  add_param(t, t->enc, "discrimi.W", {1524, 3});
-  add_param(t, t->zp, "enc_fc1.W", {16384, 1000});
-  add_param(t, t->zp, "bnorm_enc_fc1.beta", {1000});
-  add_param(t, t->zp, "bnorm_enc_fc1.gamma", {1000});
+  add_param(t, G_ENC, "minibatch_discrim.theta", {1024, 500, 5});
+  add_param(t, G_ENC, "minibatch_discrim.log_weight_scale", {500, 5});
+  add_param(t, G_ENC, "minibatch_discrim.b", {500});
+  add_param(t, G_ENC, "discrimi.W", {1524, 3});
+  add_param(t, G_Z, "enc_fc1.W", {16384, 1000});
+  add_param(t, G_Z, "bnorm_enc_fc1.beta", {1000});
+  add_param(t, G_Z, "bnorm_enc_fc1.gamma", {1000});
   for (const char* nm : {"enc_mu", "enc_logsigma"}) {
     const std::string bn = std::string(nm) == "enc_mu" ? "mu_bnorm" : "ls_bnorm";
-    add_param(t, t->zp, std::string(nm) + ".W", {1000, Z});
-    add_param(t, t->zp, bn + ".beta", {Z});
-    add_param(t, t->zp, bn + ".gamma", {Z});
+    add_param(t, G_Z, std::string(nm) + ".W", {1000, Z});
+    add_param(t, G_Z, bn + ".beta", {Z});
+    add_param(t, G_Z, bn + ".gamma", {Z});
   }
-  add_param(t, t->dec, "l_dec_fc2.W", {Z, 8192});
-  add_param(t, t->dec, "l_dec_fc2.b", {8192});
+  add_param(t, G_DEC, "l_dec_fc2.W", {Z, 8192});
+  add_param(t, G_DEC, "l_dec_fc2.b", {8192});
   auto add_mdcl = [&](const std::string& name, int co, int ci, const std::vector<int>& sc) {
     auto names = mdcl_names(name, sc);
-    add_param(t, t->dec, names[0], {co, ci, 3, 3});
-    for (size_t i = 1; i < names.size(); ++i) add_param(t, t->dec, names[i], {co});
+    add_param(t, G_DEC, names[0], {co, ci, 3, 3});
+    for (size_t i = 1; i < names.size(); ++i) add_param(t, G_DEC, names[i], {co});
   };
   for (const DecStage& s : dec_stages()) {
     const std::string blk = s.blk;
-    add_param(t, t->dec, std::string(s.dc) + ".W", {s.ci, s.co, 5, 5});
-    add_param(t, t->dec, blk + "bnorm0.beta", {s.co});
-    add_param(t, t->dec, blk + "bnorm0.gamma", {s.co});
+    add_param(t, G_DEC, std::string(s.dc) + ".W", {s.ci, s.co, 5, 5});
+    add_param(t, G_DEC, blk + "bnorm0.beta", {s.co});
+    add_param(t, G_DEC, blk + "bnorm0.gamma", {s.co});
     add_mdcl(blk, s.co, s.co, s.scales);
-    add_param(t, t->dec, blk + "bnorm1.beta", {s.co});
-    add_param(t, t->dec, blk + "bnorm1.gamma", {s.co});
+    add_param(t, G_DEC, blk + "bnorm1.beta", {s.co});
+    add_param(t, G_DEC, blk + "bnorm1.gamma", {s.co});
     add_mdcl(blk + "2", s.co, s.co, s.scales);
-    add_param(t, t->dec, blk + "bnorm2.beta", {s.co});
-    add_param(t, t->dec, blk + "bnorm2.gamma", {s.co});
+    add_param(t, G_DEC, blk + "bnorm2.beta", {s.co});
+    add_param(t, G_DEC, blk + "bnorm2.gamma", {s.co});
   }
-  add_param(t, t->dec, "dec_conv4.W", {128, 128, 5, 5});
-  add_param(t, t->dec, "bnorm_dc4.beta", {128});
-  add_param(t, t->dec, "bnorm_dc4.gamma", {128});
-  const std::pair<const char*, int> heads[5] = {{"R", 128}, {"G_a", 128}, {"G_b", 2}, {"B_a", 128}, {"B_b", 4}};
-  for (auto& h : heads) add_mdcl(h.first, 2, h.second, HEAD_SCALES);
+  add_param(t, G_DEC, "dec_conv4.W", {128, 128, 5, 5});
+  add_param(t, G_DEC, "bnorm_dc4.beta", {128});
+  add_param(t, G_DEC, "bnorm_dc4.gamma", {128});
+  for (auto& h : HEADS) add_mdcl(h.first, 2, h.second, HEAD_SCALES);
   // batch-norm running averages (not trainable; Lasagne BatchNormLayer alpha = 0.1): what the deterministic graphs of
   // API.py / sample_IAN.py normalise with after training
   std::vector<std::pair<std::string, int>> bns = {{"bnorm2", 256}, {"bnorm3", 512}, {"bnorm4", 1024}, {"bnorm_enc_fc1", 1000},
@@ -305,7 +364,7 @@ void declare_parameters(ian_trainer* t) {
   for (const DecStage& s : dec_stages())
     for (int j = 0; j < 3; ++j) bns.push_back({std::string(s.blk) + "bnorm" + std::to_string(j), s.co});
   for (auto& b : bns)
-    for (const char* sfx : {".mean", ".inv_std"}) add_param(t, t->stats, b.first + sfx, {b.second});
+    for (const char* sfx : {".mean", ".inv_std"}) add_param(t, G_STATS, b.first + sfx, {b.second});
   // frozen MADE parameters (never trained: train_IAN.py:184-194)
   for (const char* m : {"l_IAF_mu", "l_IAF_ls"})
     for (const char* l : {"_input", "_output_W", "_output_D"}) {
@@ -314,8 +373,8 @@ void declare_parameters(ian_trainer* t) {
     }
 }
 
-int make_layer(ian_trainer* t, const std::string& key, int kind, int cin, int cout, int in_h, int in_w, const std::vector<int>& scales,
-               const int* flat, const int* unflat, std::vector<std::string> pnames) {
+int make_layer(ian_trainer* t, LayerRef** out, const std::string& key, int kind, int cin, int cout, int in_h, int in_w, const std::vector<int>& scales,
+               const int* flat, const int* unflat, const std::vector<std::string>& pnames) {
   ian_op_desc d;
   memset(&d, 0, sizeof d);
   d.kind = kind; d.cin = cin; d.cout = cout; d.in_h = in_h; d.in_w = in_w;
@@ -325,41 +384,49 @@ int make_layer(ian_trainer* t, const std::string& key, int kind, int cin, int co
   d.n_scales = (int)scales.size();
   for (size_t i = 0; i < scales.size(); ++i) d.scales[i] = scales[i];
   LayerRef r;
+  r.key = key;
+  r.kind = kind;
   const int rc = ian_layer_create(&d, t->cfg.deconv_flip ? 1 : 0, &r.l);
   if (rc) return tfail(t, rc, "ian_layer_create(%s) failed (%d)%s", key.c_str(), rc, rc == -10 ? ": no HIP device, libian has no CPU fallback" : "");
-  r.pnames = pnames;
-  t->layers[key] = r;
-  t->layer_order.push_back(key);
+  for (auto& nme : pnames) {
+    const PRef p = param(t, nme);
+    r.ids.push_back(p.id); r.values.push_back(p.p); r.grads.push_back(p.g);
+  }
+  t->layers.push_back(r);
+  *out = &t->layers.back();
   return 0;
 }
 
 int build_layers(ian_trainer* t) {
   const int Z = t->cfg.num_latents;
+  Layers& L = t->L;
   int cin = 3, rc;
   for (int i = 0; i < 4; ++i) {
     const std::string nm = "enc_conv" + std::to_string(i + 1);
-    if ((rc = make_layer(t, nm, IAN_OP_CONV5S2, cin, ENC_WIDTHS[i], 64 >> i, 64 >> i, {}, nullptr, nullptr, {nm + ".W"}))) return rc;
+    if ((rc = make_layer(t, &L.enc_conv[i + 1], nm, IAN_OP_CONV5S2, cin, ENC_WIDTHS[i], 64 >> i, 64 >> i, {}, nullptr, nullptr, {nm + ".W"}))) return rc;
     cin = ENC_WIDTHS[i];
   }
   const int flat[3] = {1024, 4, 4}, unflat[3] = {512, 4, 4};
-  if ((rc = make_layer(t, "enc_fc1", IAN_OP_DENSE, 16384, 1000, 1, 1, {}, flat, nullptr, {"enc_fc1.W"}))) return rc;
-  if ((rc = make_layer(t, "enc_mu", IAN_OP_DENSE, 1000, Z, 1, 1, {}, nullptr, nullptr, {"enc_mu.W"}))) return rc;
-  if ((rc = make_layer(t, "enc_logsigma", IAN_OP_DENSE, 1000, Z, 1, 1, {}, nullptr, nullptr, {"enc_logsigma.W"}))) return rc;
-  if ((rc = make_layer(t, "mb", IAN_OP_DENSE, 1024, 2500, 1, 1, {}, nullptr, nullptr, {}))) return rc;  // weights = normalised theta (layers.py:494)
-  if ((rc = make_layer(t, "l_dec_fc2", IAN_OP_DENSE, Z, 8192, 1, 1, {}, nullptr, unflat, {"l_dec_fc2.W"}))) return rc;
-  for (const DecStage& s : dec_stages()) {
+  if ((rc = make_layer(t, &L.enc_fc1, "enc_fc1", IAN_OP_DENSE, 16384, 1000, 1, 1, {}, flat, nullptr, {"enc_fc1.W"}))) return rc;
+  if ((rc = make_layer(t, &L.enc_mu, "enc_mu", IAN_OP_DENSE, 1000, Z, 1, 1, {}, nullptr, nullptr, {"enc_mu.W"}))) return rc;
+  if ((rc = make_layer(t, &L.enc_logsigma, "enc_logsigma", IAN_OP_DENSE, 1000, Z, 1, 1, {}, nullptr, nullptr, {"enc_logsigma.W"}))) return rc;
+  if ((rc = make_layer(t, &L.mb, "mb", IAN_OP_DENSE, 1024, 2500, 1, 1, {}, nullptr, nullptr, {}))) return rc;  // weights = normalised theta (layers.py:494)
+  if ((rc = make_layer(t, &L.l_dec_fc2, "l_dec_fc2", IAN_OP_DENSE, Z, 8192, 1, 1, {}, nullptr, unflat, {"l_dec_fc2.W"}))) return rc;
+  for (size_t si = 0; si < dec_stages().size(); ++si) {
+    const DecStage& s = dec_stages()[si];
     const std::string blk = s.blk;
-    if ((rc = make_layer(t, s.dc, IAN_OP_DECONV5S2, s.ci, s.co, s.hw, s.hw, {}, nullptr, nullptr, {std::string(s.dc) + ".W"}))) return rc;
-    if ((rc = make_layer(t, blk, IAN_OP_MDC3, s.co, s.co, 2 * s.hw, 2 * s.hw, s.scales, nullptr, nullptr, mdcl_names(blk, s.scales)))) return rc;
-    if ((rc = make_layer(t, blk + "2", IAN_OP_MDC3, s.co, s.co, 2 * s.hw, 2 * s.hw, s.scales, nullptr, nullptr, mdcl_names(blk + "2", s.scales)))) return rc;
+    LayerRef** l = t->L.stage[si];
+    if ((rc = make_layer(t, &l[0], s.dc, IAN_OP_DECONV5S2, s.ci, s.co, s.hw, s.hw, {}, nullptr, nullptr, {std::string(s.dc) + ".W"}))) return rc;
+    if ((rc = make_layer(t, &l[1], blk, IAN_OP_MDC3, s.co, s.co, 2 * s.hw, 2 * s.hw, s.scales, nullptr, nullptr, mdcl_names(blk, s.scales)))) return rc;
+    if ((rc = make_layer(t, &l[2], blk + "2", IAN_OP_MDC3, s.co, s.co, 2 * s.hw, 2 * s.hw, s.scales, nullptr, nullptr, mdcl_names(blk + "2", s.scales)))) return rc;
   }
-  if ((rc = make_layer(t, "dec_conv4", IAN_OP_DECONV5S2, 128, 128, 32, 32, {}, nullptr, nullptr, {"dec_conv4.W"}))) return rc;
-  const std::pair<const char*, int> heads[5] = {{"R", 128}, {"G_a", 128}, {"G_b", 2}, {"B_a", 128}, {"B_b", 4}};
-  for (auto& h : heads)
-    if ((rc = make_layer(t, h.first, IAN_OP_MDC3, h.second, 2, 64, 64, HEAD_SCALES, nullptr, nullptr, mdcl_names(h.first, HEAD_SCALES)))) return rc;
+  if ((rc = make_layer(t, &L.dec_conv4, "dec_conv4", IAN_OP_DECONV5S2, 128, 128, 32, 32, {}, nullptr, nullptr, {"dec_conv4.W"}))) return rc;
+  LayerRef** heads[5] = {&L.R, &L.G_a, &L.G_b, &L.B_a, &L.B_b};
+  for (int i = 0; i < 5; ++i)
+    if ((rc = make_layer(t, heads[i], HEADS[i].first, IAN_OP_MDC3, HEADS[i].second, 2, 64, 64, HEAD_SCALES, nullptr, nullptr, mdcl_names(HEADS[i].first, HEAD_SCALES))))
+      return rc;
   return 0;
 }
-ian_layer* lay(ian_trainer* t, const std::string& n) { return t->layers.at(n).l; }
 
 BN make_bn(ian_trainer* t, int C) {
   BN b;
@@ -368,86 +435,105 @@ BN make_bn(ian_trainer* t, int C) {
   b.mean = dalloc(t, C); b.inv_std = dalloc(t, C); b.scale = dalloc(t, C); b.shift = dalloc(t, C);
   return b;
 }
+float* buf(ian_trainer* t, const std::string& pass, const std::string& name, size_t floats) {  // allocate and enter in the registry
+  return t->bufs[pass + "." + name] = dalloc(t, floats);
+}
+// u.y / u.a / u.dA / u.dy are set by the caller; `bnorm`: Theano name of the normalisation (<bnorm>.gamma | beta | mean | inv_std),
+// `key`: its name in ian_trainer_buffer
+void make_unit(ian_trainer* t, Unit& u, const std::string& pass, const std::string& key, LayerRef* L, const std::string& bnorm, int64_t rows, int C,
+               int stride, int ld, int act) {
+  u.L = L;
+  u.bn = make_bn(t, C);
+  t->bns[pass + "." + key] = &u.bn;
+  u.rows = rows; u.C = C; u.stride = stride; u.ld = ld; u.act = act;
+  u.epilogue = L->kind != IAN_OP_DENSE;
+  u.gamma = param(t, bnorm + ".gamma"); u.beta = param(t, bnorm + ".beta");
+  u.run_mean = param(t, bnorm + ".mean"); u.run_inv_std = param(t, bnorm + ".inv_std");
+}
 
-void enc_alloc(ian_trainer* t, Bufs& E, std::map<std::string, BN>& bn) {
+void enc_alloc(ian_trainer* t, EncPass& E, const std::string& pass) {
   const size_t n = t->n;
-  E["x"] = dalloc(t, n * 64 * 64 * 32); E["dx"] = dalloc(t, n * 64 * 64 * 32);
-  for (int i = 0; i < 4; ++i) {
-    const int hw = 32 >> i, w = ENC_WIDTHS[i];
-    const std::string s = std::to_string(i + 1);
-    E["a" + s] = dalloc(t, n * hw * hw * w); E["da" + s] = dalloc(t, n * hw * hw * w);
-    if (i > 0) {
-      E["y" + s] = dalloc(t, n * hw * hw * w);
-      bn["bn" + s] = make_bn(t, w);
+  E.x = buf(t, pass, "x", n * 64 * 64 * 32); E.dx = buf(t, pass, "dx", n * 64 * 64 * 32);
+  for (int i = 1; i <= 4; ++i) {
+    const int hw = 64 >> i, w = ENC_WIDTHS[i - 1];
+    const std::string s = std::to_string(i);
+    E.a[i] = buf(t, pass, "a" + s, n * hw * hw * w); E.da[i] = buf(t, pass, "da" + s, n * hw * hw * w);
+    if (i > 1) {
+      Unit& u = E.u[i];
+      u.y = buf(t, pass, "y" + s, n * hw * hw * w); u.a = E.a[i]; u.dA = u.dy = E.da[i];
+      make_unit(t, u, pass, "bn" + s, t->L.enc_conv[i], "bnorm" + s, (int64_t)n * hw * hw, w, w, 0, IAN_ACT_LRELU);
     }
   }
-  E["feat"] = dalloc(t, n * 1024); E["dfeat"] = dalloc(t, n * 1024);
-  E["act"] = dalloc(t, n * cs(2500)); E["dact"] = dalloc(t, n * cs(2500));
-  E["mb"] = dalloc(t, n * cs(1524)); E["dmb"] = dalloc(t, n * cs(1524));
+  E.feat = buf(t, pass, "feat", n * 1024); E.dfeat = buf(t, pass, "dfeat", n * 1024);
+  E.act = buf(t, pass, "act", n * cs(2500)); E.dact = buf(t, pass, "dact", n * cs(2500));
+  E.mb = buf(t, pass, "mb", n * cs(1524)); E.dmb = buf(t, pass, "dmb", n * cs(1524));
   if (t->exact) {  // MinibatchLayer over the GLOBAL minibatch (layers.py:506-524): all ranks' activations / feature gradients
-    E["act_all"] = dalloc(t, (size_t)t->N * cs(2500));
-    E["dmb_all"] = dalloc(t, (size_t)t->N * cs(1524));
+    E.act_all = buf(t, pass, "act_all", (size_t)t->N * cs(2500));
+    E.dmb_all = buf(t, pass, "dmb_all", (size_t)t->N * cs(1524));
   }
-  E["p"] = dalloc(t, n * 3); E["loss"] = dalloc(t, n * 4); E["dlogits"] = dalloc(t, n * 4);
+  E.p = buf(t, pass, "p", n * 3); E.loss = buf(t, pass, "loss", n * 4); E.dlogits = buf(t, pass, "dlogits", n * 4);
 }
 void z_alloc(ian_trainer* t) {
   const size_t n = t->n;
-  Bufs& Z = t->ZS;
-  Z["y_fc1"] = dalloc(t, n * 1024); Z["f"] = dalloc(t, n * 1024); Z["df"] = dalloc(t, n * 1024);
-  t->bnZ["bn_fc1"] = make_bn(t, 1000);
-  for (const char* nm : {"mu", "ls"}) {
-    Z[std::string("y_") + nm] = dalloc(t, n * 128); Z[nm] = dalloc(t, n * 128); Z[std::string("d") + nm] = dalloc(t, n * 128);
-    t->bnZ[std::string("bn_") + nm] = make_bn(t, t->cfg.num_latents);
+  const int Zd = t->cfg.num_latents;
+  ZPass& S = t->ZS;
+  S.fc1.y = buf(t, "ZS", "y_fc1", n * 1024); S.fc1.a = buf(t, "ZS", "f", n * 1024); S.fc1.dA = S.fc1.dy = buf(t, "ZS", "df", n * 1024);
+  make_unit(t, S.fc1, "ZS", "bn_fc1", t->L.enc_fc1, "bnorm_enc_fc1", n, 1000, 1024, 1024, IAN_ACT_RELU);
+  const struct { Unit* u; const char* nm; LayerRef* L; const char* bnorm; } lat[2] = {{&S.mu, "mu", t->L.enc_mu, "mu_bnorm"},
+                                                                                   {&S.ls, "ls", t->L.enc_logsigma, "ls_bnorm"}};
+  for (auto& l : lat) {
+    const std::string nm = l.nm;
+    l.u->y = buf(t, "ZS", "y_" + nm, n * 128); l.u->a = buf(t, "ZS", nm, n * 128); l.u->dA = l.u->dy = buf(t, "ZS", "d" + nm, n * 128);
+    make_unit(t, *l.u, "ZS", "bn_" + nm, l.L, l.bnorm, n, Zd, 128, 128, 0);
   }
   {  // the two latent normalisations read the same input in the same stage: their float64 sums lie side by side so that the
      // data-parallel `exact` step combines both with ONE all-gather per direction (z_forward / z_backward)
-    const int Zd = t->cfg.num_latents;
     double *js = dalloc64(t, 4 * Zd), *jb = dalloc64(t, 4 * Zd);
-    t->bnZ["bn_mu"].sums = js; t->bnZ["bn_ls"].sums = js ? js + 2 * Zd : nullptr;
-    t->bnZ["bn_mu"].bsums = jb; t->bnZ["bn_ls"].bsums = jb ? jb + 2 * Zd : nullptr;
+    S.mu.bn.sums = js; S.ls.bn.sums = js ? js + 2 * Zd : nullptr;
+    S.mu.bn.bsums = jb; S.ls.bn.bsums = jb ? jb + 2 * Zd : nullptr;
   }
-  Z["z0"] = dalloc(t, n * 128); Z["z"] = dalloc(t, n * 128); Z["dz0"] = dalloc(t, n * 128); Z["kl"] = dalloc(t, n * 100);
+  S.z0 = buf(t, "ZS", "z0", n * 128); S.z = buf(t, "ZS", "z", n * 128); S.dz0 = buf(t, "ZS", "dz0", n * 128); S.kl = buf(t, "ZS", "kl", n * 100);
 }
-void dec_alloc(ian_trainer* t, Bufs& D, std::map<std::string, BN>& bn) {
+void dec_alloc(ian_trainer* t, DecPass& D, const std::string& pass) {
   const size_t n = t->n;
-  D["h0"] = dalloc(t, n * 16 * 512); D["dh0"] = dalloc(t, n * 16 * 512);
-  for (const DecStage& s : dec_stages()) {
-    const size_t e = n * (2 * s.hw) * (2 * s.hw) * s.co;
+  D.h0 = buf(t, pass, "h0", n * 16 * 512); D.dh0 = buf(t, pass, "dh0", n * 16 * 512);
+  for (size_t si = 0; si < dec_stages().size(); ++si) {
+    const DecStage& s = dec_stages()[si];
+    const int64_t rows = (int64_t)n * (2 * s.hw) * (2 * s.hw);
     const std::string blk = s.blk;
-    for (const char* nm : {"x", "a", "b", "c", "e", "h", "dx", "da", "dc", "dh"}) D[blk + "_" + nm] = dalloc(t, e);
-    for (int j = 0; j < 3; ++j) bn[blk + "_bn" + std::to_string(j)] = make_bn(t, s.co);
+    Unit* u = D.stage[si];   // x = deconv(h); a = lrelu(bn0(x)); c = lrelu(bn1(b = MDCL(a))); h = lrelu(bn2(e = x + MDCL2(c)))
+    const std::pair<const char*, float**> slots[10] = {{"x", &u[0].y}, {"a", &u[0].a}, {"b", &u[1].y}, {"c", &u[1].a}, {"e", &u[2].y},
+                                                       {"h", &u[2].a}, {"dx", &u[0].dy}, {"da", &u[0].dA}, {"dc", &u[1].dA}, {"dh", &u[2].dA}};
+    for (auto& sl : slots) *sl.second = buf(t, pass, blk + "_" + sl.first, (size_t)rows * s.co);
+    u[1].dy = u[1].dA; u[2].dy = u[2].dA;
+    for (int j = 0; j < 3; ++j)
+      make_unit(t, u[j], pass, blk + "_bn" + std::to_string(j), t->L.stage[si][j], blk + "bnorm" + std::to_string(j), rows, s.co, s.co, 0, IAN_ACT_LRELU);
   }
-  D["y4"] = dalloc(t, n * 4096 * 128); D["h4"] = dalloc(t, n * 4096 * 128); D["dh4"] = dalloc(t, n * 4096 * 128);
-  bn["bn4"] = make_bn(t, 128);
-  for (const char* nm : {"R", "G", "B", "Ga", "Ba", "RG", "gR", "gG", "gB", "dRG", "dRt"}) D[nm] = dalloc(t, n * 4096 * 32);
-  D["xhat"] = dalloc(t, n * 3 * 4096); D["dxhat"] = dalloc(t, n * 3 * 4096); D["tmp_img"] = dalloc(t, n * 3 * 4096);
-  D["dz"] = dalloc(t, n * 128);
+  D.u4.y = buf(t, pass, "y4", n * 4096 * 128); D.u4.a = buf(t, pass, "h4", n * 4096 * 128); D.u4.dA = D.u4.dy = buf(t, pass, "dh4", n * 4096 * 128);
+  make_unit(t, D.u4, pass, "bn4", t->L.dec_conv4, "bnorm_dc4", (int64_t)n * 4096, 128, 128, 0, IAN_ACT_LRELU);
+  const std::pair<const char*, float**> maps[11] = {{"R", &D.R}, {"G", &D.G}, {"B", &D.B}, {"Ga", &D.Ga}, {"Ba", &D.Ba}, {"RG", &D.RG},
+                                                    {"gR", &D.gR}, {"gG", &D.gG}, {"gB", &D.gB}, {"dRG", &D.dRG}, {"dRt", &D.dRt}};
+  for (auto& m : maps) *m.second = buf(t, pass, m.first, n * 4096 * 32);
+  D.xhat = buf(t, pass, "xhat", n * 3 * 4096); D.dxhat = buf(t, pass, "dxhat", n * 3 * 4096); D.tmp_img = buf(t, pass, "tmp_img", n * 3 * 4096);
+  D.dz = buf(t, pass, "dz", n * 128);
 }
 
 // ---- parameter refresh (after every optimiser update): reference layout -> kernel layouts -------------------------
 int refresh_weights(ian_trainer* t) {
-  if (t->dirty.empty()) return 0;
-  auto gname = [&](const std::string& p) -> std::string {
-    Group* g = t->where.at(p);
-    return g == &t->enc ? "enc" : (g == &t->zp ? "Z" : "dec");
-  };
-  for (const std::string& key : t->layer_order) {
-    LayerRef& r = t->layers[key];
-    if (r.pnames.empty() || !t->dirty.count(gname(r.pnames[0]))) continue;
-    std::vector<const float*> ptrs;
-    for (auto& p : r.pnames) ptrs.push_back(P(t, p));
-    TL(r.l, ian_layer_set_params(r.l, ptrs.data(), (int)ptrs.size(), t->st));
+  if (!t->dirty[G_ENC] && !t->dirty[G_Z] && !t->dirty[G_DEC]) return 0;
+  for (LayerRef& r : t->layers) {
+    if (r.ids.empty() || !t->dirty[t->params[r.ids[0]].group]) continue;
+    LCALL(&r, ian_layer_set_params, r.values.data(), (int)r.values.size(), t->st);
   }
-  if (t->dirty.count("enc")) {
-    TK(ian_k_mb_weight(P(t, "minibatch_discrim.theta"), P(t, "minibatch_discrim.log_weight_scale"), t->mb_W, t->mb_colscale, 1024, 2500, t->st));
+  if (t->dirty[G_ENC]) {
+    TK(ian_k_mb_weight(t->pr.mb_theta.p, t->pr.mb_lws.p, t->mb_W, t->mb_colscale, 1024, 2500, t->st));
     const float* w = t->mb_W;
-    TL(lay(t, "mb"), ian_layer_set_params(lay(t, "mb"), &w, 1, t->st));
+    LCALL(t->L.mb, ian_layer_set_params, &w, 1, t->st);
   }
-  if (t->dirty.count("dec")) TK(ian_k_gather(P(t, "l_dec_fc2.b"), t->fc2_perm, t->fc2_bias, 8192, t->st));
-  t->dirty.clear();
+  if (t->dirty[G_DEC]) TK(ian_k_gather(t->pr.l_dec_fc2_b.p, t->fc2_perm, t->fc2_bias, 8192, t->st));
+  t->dirty[G_ENC] = t->dirty[G_Z] = t->dirty[G_DEC] = false;
   return 0;
 }
-
 // ---- building blocks ------------------------------------------------------------------------------------------------
 int chunks(const ian_trainer* t, int64_t rows) {
   // chunk SIZE depends on the per-image extent only (one image, or 512 rows of one): include/ian_train.h, ian_k_colstats
@@ -466,8 +552,6 @@ int ws_for(ian_trainer* t, int64_t rows, int C, double** out) {
   *out = t->ws_stats;
   return 0;
 }
-Group& group_of(ian_trainer* t, int g) { return g == 0 ? t->enc : (g == 1 ? t->zp : t->dec); }
-int group_index(ian_trainer* t, const Group* g) { return g == &t->enc ? 0 : (g == &t->zp ? 1 : 2); }
 int next_event(ian_trainer* t, hipEvent_t* e) {
   if (t->ev_used == t->events.size()) {
     hipEvent_t ne;
@@ -483,7 +567,7 @@ int next_event(ian_trainer* t, hipEvent_t* e) {
 // of a bucket is a property of the whole backward sweep of an update kind: every gradient write is reported through mark();
 // the first sweep of a kind records the order, later sweeps fire a bucket right after its last write.
 int fire(ian_trainer* t, Bucket& b) {
-  Group& g = group_of(t, b.group);
+  Group& g = t->grp[b.group];
   hipEvent_t e;
   int rc;
   if ((rc = next_event(t, &e))) return rc;
@@ -502,19 +586,19 @@ int fire(ian_trainer* t, Bucket& b) {
   while (t->overlap_log.size() > 256) t->overlap_log.pop_front();
   return 0;
 }
-int mark(ian_trainer* t, const std::vector<std::string>& names) {  // the gradients of `names` have just been written (issued)
-  for (auto& n : names) t->touched.insert(n);
-  t->evlog.push_back(names);
+int mark(ian_trainer* t, const std::vector<int>& ids) {  // the gradients of these parameters have just been written (issued)
+  for (int id : ids) t->touched[id] = 1;
+  t->evlog.push_back(ids);
   if (!t->buckets) return 0;
   const int ev = (int)t->evlog.size();
   for (Bucket& b : *t->buckets) {
     if (b.fired) {
-      for (auto& n : names)
-        if (b.names.count(n)) {
+      for (int id : ids)
+        if (b.params.count(id)) {
           t->plans.erase(t->which_now);            // stale plan: the next sweep of this kind re-records it
           t->buckets = nullptr;
           return tfail(t, -31, "gradient of %s written after its bucket was handed to the all-reduce (write order changed since the "
-                               "plan was recorded; plan dropped)", n.c_str());
+                               "plan was recorded; plan dropped)", t->params[id].name.c_str());
         }
     } else if (b.ready == ev) {
       int rc = fire(t, b);
@@ -524,23 +608,21 @@ int mark(ian_trainer* t, const std::vector<std::string>& names) {  // the gradie
   return 0;
 }
 std::vector<Bucket> make_plan(ian_trainer* t, int which) {  // buckets of the groups this update kind moves, with their last writes
-  std::map<std::string, int> last;
+  std::vector<int> last(t->params.size(), 0);
   for (size_t i = 0; i < t->evlog.size(); ++i)
-    for (auto& n : t->evlog[i]) last[n] = (int)i + 1;
+    for (int id : t->evlog[i]) last[id] = (int)i + 1;
   const int64_t step = t->bucket_bytes / 4 > 0 ? t->bucket_bytes / 4 : 1;
   std::vector<Bucket> plan;
-  for (int gi : {which == 0 ? 2 : 0, 1}) {
-    Group& g = group_of(t, gi);
+  for (int gi : {which == 0 ? G_DEC : G_ENC, G_Z}) {
+    const Group& g = t->grp[gi];
     for (int64_t o = 0; o < g.numel; o += step) {
       Bucket b;
       b.group = gi; b.lo = o; b.hi = o + step < g.numel ? o + step : g.numel; b.ready = 0; b.fired = false;
-      for (auto& nm : g.names) {
-        const auto& of = g.off.at(nm);
-        const int64_t po = of.first, cnt = of.second.numel();
+      for (int id : g.params) {
+        const int64_t po = t->params[id].off, cnt = t->params[id].shape.numel();
         if (po < b.hi && po + cnt > b.lo) {
-          b.names.insert(nm);
-          auto it = last.find(nm);
-          if (it != last.end() && it->second > b.ready) b.ready = it->second;
+          b.params.insert(id);
+          if (last[id] > b.ready) b.ready = last[id];
         }
       }
       plan.push_back(b);
@@ -557,7 +639,7 @@ int begin_backward(ian_trainer* t, int which) {
   if (jrc) return jrc;
   t->ev_used = 0;
   t->gev_which[t->gpar] = which;
-  t->touched.clear();
+  t->touched.assign(t->params.size(), 0);
   t->evlog.clear();
   t->which_now = which;
   t->nfired = 0;
@@ -579,6 +661,16 @@ int begin_backward(ian_trainer* t, int which) {
     }
   return 0;
 }
+void fold_exposed(ian_trainer* t) {   // fold a pending exposed-time measurement in (the caller knows that its events have completed or waits)
+  if (!t->ex_pending) return;
+  float ms = 0.f;
+  if (hipEventSynchronize(t->ex1) == hipSuccess && hipEventElapsedTime(&ms, t->ex0, t->ex1) == hipSuccess) {
+    t->exposed_ms[t->ex_which] += ms;
+    t->exposed_n[t->ex_which] += 1;
+  }
+  (void)hipGetLastError();
+  t->ex_pending = false;
+}
 int finish_allreduce(ian_trainer* t, int which) {  // after backward: reduce what has not been handed over yet, then the compute stream waits
   int rc;
   if ((rc = join_side_stream(t))) return rc;
@@ -594,15 +686,7 @@ int finish_allreduce(ian_trainer* t, int which) {  // after backward: reduce wha
   for (size_t i = t->overlap_log.size() >= (size_t)t->nfired ? t->overlap_log.size() - t->nfired : 0; i < t->overlap_log.size(); ++i)
     t->overlap_log[i].writes_in_backward = writes;
   // how long the COMPUTE stream stalls on communication = the part of the all-reduce backward did not hide
-  if (t->measure_exposed && t->ex_pending) {       // fold the previous measurement in (its events have completed long ago)
-    float ms = 0.f;
-    if (hipEventSynchronize(t->ex1) == hipSuccess && hipEventElapsedTime(&ms, t->ex0, t->ex1) == hipSuccess) {
-      t->exposed_ms[t->ex_which] += ms;
-      t->exposed_n[t->ex_which] += 1;
-    }
-    (void)hipGetLastError();
-    t->ex_pending = false;
-  }
+  if (t->measure_exposed) fold_exposed(t);   // the previous measurement: its events have completed long ago
   if (t->measure_exposed) {
     if (!t->ex0) { THIP(hipEventCreate(&t->ex0)); THIP(hipEventCreate(&t->ex1)); }
     THIP(hipEventRecord(t->ex0, t->st));
@@ -672,99 +756,107 @@ int allreduce_ordered(ian_trainer* t, double* sums, int width) {
   return 0;
 }
 
-int acc(ian_trainer* t, const std::string& pname, const float* src, int64_t count, float alpha = 1.f) {  // grad[pname] (+)= alpha * src
-  TK(ian_k_axpy(alpha, src, G(t, pname), count, t->touched.count(pname) ? 1 : 0, t->st));
-  return mark(t, {pname});
+int acc(ian_trainer* t, const PRef& p, const float* src, int64_t count, float alpha = 1.f) {  // grad[p] (+)= alpha * src
+  TK(ian_k_axpy(alpha, src, p.g, count, t->touched[p.id] ? 1 : 0, t->st));
+  return mark(t, {p.id});
 }
-int acc64(ian_trainer* t, const std::string& pname, const double* src, int64_t count, double alpha = 1.0) {  // from float64 column sums
-  TK(ian_k_axpy_f64(alpha, src, G(t, pname), count, t->touched.count(pname) ? 1 : 0, t->st));
-  return mark(t, {pname});
+int acc64(ian_trainer* t, const PRef& p, const double* src, int64_t count, double alpha = 1.0) {  // from float64 column sums
+  TK(ian_k_axpy_f64(alpha, src, p.g, count, t->touched[p.id] ? 1 : 0, t->st));
+  return mark(t, {p.id});
 }
 // ---- GEMM-epilogue statistics (include/ian_train.h ian_layer_stats_next) ------------------------------------------------
 bool fuse_stats(const ian_trainer* t) { return t->fused_stats && !t->exact; }
-int arm_fwd_stats(ian_trainer* t, const std::string& lname) {      // the layer's next forward also sums v, v*v per row tile
+int arm_fwd_stats(ian_trainer* t, LayerRef* L) {      // the layer's next forward also sums v, v*v per row tile
   if (!fuse_stats(t)) return 0;
-  TL(lay(t, lname), ian_layer_stats_next(lay(t, lname), 1, nullptr, nullptr, nullptr, nullptr, 0, t->ws_stats, (int64_t)t->ws_stats_cap));
+  LCALL(L, ian_layer_stats_next, 1, nullptr, nullptr, nullptr, nullptr, 0, t->ws_stats, (int64_t)t->ws_stats_cap);
   return 0;
 }
-int arm_bwd_stats(ian_trainer* t, const std::string& lname, const BN& bn, const float* a, const float* yraw, int act) {
+int arm_bwd_stats(ian_trainer* t, LayerRef* L, const Unit& below) {
   if (!fuse_stats(t)) return 0;   // the layer's next backward-data also sums g = dA act'(a) and g xhat of the gradient it stores
-  TL(lay(t, lname), ian_layer_stats_next(lay(t, lname), 2, a, yraw, bn.mean, bn.inv_std, act, t->ws_stats, (int64_t)t->ws_stats_cap));
+  LCALL(L, ian_layer_stats_next, 2, below.a, below.y, below.bn.mean, below.bn.inv_std, below.act, t->ws_stats, (int64_t)t->ws_stats_cap);
   return 0;
 }
-int armed_chunks(ian_trainer* t, const std::string& lname) { return fuse_stats(t) ? ian_layer_stats_chunks(lay(t, lname)) : 0; }
+int armed_chunks(ian_trainer* t, LayerRef* L) { return fuse_stats(t) ? ian_layer_stats_chunks(L->l) : 0; }
 
+// ---- the unit: linear layer + batch-norm + activation -----------------------------------------------------------------------
 // exact mode, after the per-rank sums have been combined over the ranks: affine, apply, running averages (same running_math as the
 // fused single-process second stage: data-parallel checkpoints carry bit-identical running averages)
-int bn_forward_finish(ian_trainer* t, BN& bn, const float* y, float* a, int64_t rows, int C, int stride, const float* gamma, const float* beta,
-                      int act, int64_t count_rows, float* rm, float* ri) {
-  bn.count = (float)(count_rows * t->world);
-  TK(ian_k_bn_make_affine(bn.sums, bn.count, BN_EPS, gamma, beta, C, bn.mean, bn.inv_std, bn.scale, bn.shift, t->st));
-  TK(ian_k_affine(y, a, bn.scale, bn.shift, rows, C, stride, act, t->st));
-  if (rm) TK(ian_k_bn_running(rm, bn.mean, ri, bn.inv_std, C, 0.9f, 0.1f, t->st));
+int bn_forward_finish(ian_trainer* t, Unit& u, bool running) {
+  BN& bn = u.bn;
+  bn.count = (float)(u.rows * t->world);
+  TK(ian_k_bn_make_affine(bn.sums, bn.count, BN_EPS, u.gamma.p, u.beta.p, u.C, bn.mean, bn.inv_std, bn.scale, bn.shift, t->st));
+  TK(ian_k_affine(u.y, u.a, bn.scale, bn.shift, u.rows, u.C, u.stride, u.act, t->st));
+  if (running && t->update_running) TK(ian_k_bn_running(u.run_mean.p, bn.mean, u.run_inv_std.p, bn.inv_std, u.C, 0.9f, 0.1f, t->st));
   return 0;
 }
-// pre > 0: the producing GEMM already left `pre` chunk partials in the statistics workspace (arm_fwd_stats)
-int bn_forward(ian_trainer* t, BN& bn, const float* y, float* a, int64_t rows, int C, int stride, const float* gamma, const float* beta, int act,
-               int64_t count_rows, const char* running, int pre = 0) {
+// a = act(bn(y)).  pre > 0: the producing GEMM already left `pre` chunk partials in the statistics workspace (arm_fwd_stats)
+int bn_forward(ian_trainer* t, Unit& u, bool running, int pre) {
+  BN& bn = u.bn;
   double* ws = t->ws_stats;
   int rc;
-  if (pre <= 0 && (rc = ws_for(t, rows, C, &ws))) return rc;   // (pre > 0: the partials are already in the workspace -- it must not move)
-  float *rm = nullptr, *ri = nullptr;
-  if (running && t->update_running) {  // r = (1 - alpha) r + alpha * batch   (Lasagne BatchNormLayer alpha = 0.1)
-    rm = P(t, std::string(running) + ".mean");
-    ri = P(t, std::string(running) + ".inv_std");
-  }
+  if (pre <= 0 && (rc = ws_for(t, u.rows, u.C, &ws))) return rc;   // (pre > 0: the partials are already in the workspace -- it must not move)
+  const bool upd = running && t->update_running;  // r = (1 - alpha) r + alpha * batch   (Lasagne BatchNormLayer alpha = 0.1)
+  float *rm = upd ? u.run_mean.p : nullptr, *ri = upd ? u.run_inv_std.p : nullptr;
   if (!t->exact) {  // no collective between the two stages: one fused second stage
-    bn.count = (float)count_rows;
+    bn.count = (float)u.rows;
     if (pre > 0)
-      TK(ian_k_bn_finish(t->ws_stats, pre, C, bn.sums, bn.count, BN_EPS, gamma, beta, bn.mean, bn.inv_std, bn.scale, bn.shift, rm, ri, 0.9f, 0.1f, t->st));
+      TK(ian_k_bn_finish(t->ws_stats, pre, u.C, bn.sums, bn.count, BN_EPS, u.gamma.p, u.beta.p, bn.mean, bn.inv_std, bn.scale, bn.shift, rm, ri, 0.9f, 0.1f,
+                         t->st));
     else
-      TK(ian_k_bn_stats_affine(y, rows, C, stride, ws, chunks(t, rows), bn.sums, bn.count, BN_EPS, gamma, beta, bn.mean, bn.inv_std, bn.scale,
-                               bn.shift, rm, ri, 0.9f, 0.1f, t->st));
-    TK(ian_k_affine(y, a, bn.scale, bn.shift, rows, C, stride, act, t->st));
+      TK(ian_k_bn_stats_affine(u.y, u.rows, u.C, u.stride, ws, chunks(t, u.rows), bn.sums, bn.count, BN_EPS, u.gamma.p, u.beta.p, bn.mean, bn.inv_std,
+                               bn.scale, bn.shift, rm, ri, 0.9f, 0.1f, t->st));
+    TK(ian_k_affine(u.y, u.a, bn.scale, bn.shift, u.rows, u.C, u.stride, u.act, t->st));
     return 0;
   }
-  TK(ian_k_colstats(0, y, nullptr, nullptr, nullptr, nullptr, rows, C, stride, 0, ws, chunks(t, rows), bn.sums, t->st));
-  if ((rc = allreduce_ordered(t, bn.sums, 2 * C))) return rc;
-  return bn_forward_finish(t, bn, y, a, rows, C, stride, gamma, beta, act, count_rows, rm, ri);
+  TK(ian_k_colstats(0, u.y, nullptr, nullptr, nullptr, nullptr, u.rows, u.C, u.stride, 0, ws, chunks(t, u.rows), bn.sums, t->st));
+  if ((rc = allreduce_ordered(t, bn.sums, 2 * u.C))) return rc;
+  return bn_forward_finish(t, u, running);
 }
-int bn_backward_finish(ian_trainer* t, BN& bn, const float* dA, const float* a, const float* y, float* dy, int64_t rows, int C, int stride, int act,
-                       const std::string& gname, const std::string& bname, bool want_w);
-int bn_backward(ian_trainer* t, BN& bn, const float* dA, const float* a, const float* y, float* dy, int64_t rows, int C, int stride, int act,
-                const std::string& gname, const std::string& bname, bool want_w, int pre = 0) {
-  double* ws = t->ws_stats;
+int unit_forward(ian_trainer* t, Unit& u, const float* x, bool running, const float* res = nullptr) {  // y = L(x) (+ res); a = act(bn(y))
   int rc;
-  if (pre <= 0 && (rc = ws_for(t, rows, C, &ws))) return rc;
-  if (!t->exact) {
-    float *gb = nullptr, *gg = nullptr;
-    int ab = 0, ag = 0;
-    if (want_w) {
-      gb = G(t, bname); gg = G(t, gname);
-      ab = t->touched.count(bname) ? 1 : 0; ag = t->touched.count(gname) ? 1 : 0;
-    }
-    if (pre > 0) TK(ian_k_bn_bwd_finish(t->ws_stats, pre, C, bn.bsums, gb, ab, gg, ag, t->st));   // partials from the GEMM that stored dA
-    else TK(ian_k_bn_bwd_stats(dA, a, y, bn.mean, bn.inv_std, rows, C, stride, act, ws, chunks(t, rows), bn.bsums, gb, ab, gg, ag, t->st));
-    if (want_w && (rc = mark(t, {bname, gname}))) return rc;
-    TK(ian_k_bn_bwd(dA, a, y, bn.mean, bn.inv_std, bn.scale, bn.bsums, bn.count, dy, rows, C, stride, act, t->st));
-    return 0;
-  }
-  TK(ian_k_colstats(1, dA, a, y, bn.mean, bn.inv_std, rows, C, stride, act, ws, chunks(t, rows), bn.bsums, t->st));
-  if ((rc = allreduce_ordered(t, bn.bsums, 2 * C))) return rc;
-  return bn_backward_finish(t, bn, dA, a, y, dy, rows, C, stride, act, gname, bname, want_w);
+  if (u.epilogue && (rc = arm_fwd_stats(t, u.L))) return rc;
+  LCALL(u.L, ian_layer_forward, x, t->n, u.y, u.ld, nullptr, res, 0, t->st);
+  return bn_forward(t, u, running, u.epilogue ? armed_chunks(t, u.L) : 0);
 }
-int bn_backward_finish(ian_trainer* t, BN& bn, const float* dA, const float* a, const float* y, float* dy, int64_t rows, int C, int stride, int act,
-                       const std::string& gname, const std::string& bname, bool want_w) {
+
+const float* act_input(const Unit& u) { return u.act ? u.a : nullptr; }   // what act' is evaluated on (no activation: nothing)
+// exact mode, after the gradient statistics have been combined over the ranks
+int bn_backward_finish(ian_trainer* t, Unit& u, bool want_w) {
+  BN& bn = u.bn;
   int rc;
   if (want_w) {
     // with exact statistics every rank already holds the GLOBAL dbeta / dgamma: pre-divide so that the gradient all-reduce
     // (a sum over ranks) restores them
     const double sc = 1.0 / t->world;
-    if ((rc = acc64(t, bname, bn.bsums, C, sc))) return rc;
-    if ((rc = acc64(t, gname, bn.bsums + C, C, sc))) return rc;
+    if ((rc = acc64(t, u.beta, bn.bsums, u.C, sc))) return rc;
+    if ((rc = acc64(t, u.gamma, bn.bsums + u.C, u.C, sc))) return rc;
   }
-  TK(ian_k_bn_bwd(dA, a, y, bn.mean, bn.inv_std, bn.scale, bn.bsums, bn.count, dy, rows, C, stride, act, t->st));
+  TK(ian_k_bn_bwd(u.dA, act_input(u), u.y, bn.mean, bn.inv_std, bn.scale, bn.bsums, bn.count, u.dy, u.rows, u.C, u.stride, u.act, t->st));
   return 0;
+}
+// dy = d loss / dy from dA; want_w: dbeta, dgamma.  pre > 0: partials from the GEMM that stored dA (arm_bwd_stats)
+int bn_backward(ian_trainer* t, Unit& u, bool want_w, int pre) {
+  BN& bn = u.bn;
+  const float* a = act_input(u);
+  double* ws = t->ws_stats;
+  int rc;
+  if (pre <= 0 && (rc = ws_for(t, u.rows, u.C, &ws))) return rc;
+  if (!t->exact) {
+    float *gb = nullptr, *gg = nullptr;
+    int ab = 0, ag = 0;
+    if (want_w) {
+      gb = u.beta.g; gg = u.gamma.g;
+      ab = t->touched[u.beta.id] ? 1 : 0; ag = t->touched[u.gamma.id] ? 1 : 0;
+    }
+    if (pre > 0) TK(ian_k_bn_bwd_finish(t->ws_stats, pre, u.C, bn.bsums, gb, ab, gg, ag, t->st));
+    else TK(ian_k_bn_bwd_stats(u.dA, a, u.y, bn.mean, bn.inv_std, u.rows, u.C, u.stride, u.act, ws, chunks(t, u.rows), bn.bsums, gb, ab, gg, ag, t->st));
+    if (want_w && (rc = mark(t, {u.beta.id, u.gamma.id}))) return rc;
+    TK(ian_k_bn_bwd(u.dA, a, u.y, bn.mean, bn.inv_std, bn.scale, bn.bsums, bn.count, u.dy, u.rows, u.C, u.stride, u.act, t->st));
+    return 0;
+  }
+  TK(ian_k_colstats(1, u.dA, a, u.y, bn.mean, bn.inv_std, u.rows, u.C, u.stride, u.act, ws, chunks(t, u.rows), bn.bsums, t->st));
+  if ((rc = allreduce_ordered(t, bn.bsums, 2 * u.C))) return rc;
+  return bn_backward_finish(t, u, want_w);
 }
 // The weight-gradient stream.  wgrad_priority = 1: created with the LOWEST stream priority the device offers, so that the dispatcher
 // prefers the compute stream's workgroups whenever both streams have some ready: a data-path GEMM then keeps the whole chip, and
@@ -815,340 +907,260 @@ int join_side_stream(ian_trainer* t) {  // the compute stream waits for every we
   t->ev_used = 0;
   return 0;
 }
-int wgrad(ian_trainer* t, const std::string& lname, const float* x, const float* dy) {
-  LayerRef& r = t->layers.at(lname);
-  std::vector<float*> g;
-  for (auto& p : r.pnames) g.push_back(G(t, p));
+int wgrad(ian_trainer* t, LayerRef* r, const float* x, const float* dy) {
   hipStream_t ws;
   int rc_ = side_stream(t, &ws);
   if (rc_) return rc_;
-  TL(r.l, ian_layer_backward_weight(r.l, x, dy, t->n, g.data(), (int)g.size(), t->touched.count(r.pnames[0]) ? 1 : 0, ws));
-  return mark(t, r.pnames);
+  LCALL(r, ian_layer_backward_weight, x, dy, t->n, r->grads.data(), (int)r->grads.size(), t->touched[r->ids[0]] ? 1 : 0, ws);
+  return mark(t, r->ids);
 }
-int head_backward(ian_trainer* t, const float* x, const float* dR, const float* dG, const float* dB, float* dx, bool want_w,
-                  const BN* arm = nullptr, const float* arm_a = nullptr, const float* arm_y = nullptr, int* pre = nullptr) {
-  if (pre) *pre = 0;
-  const char* names[3] = {"R", "G_a", "B_a"};
-  const float* dys[3] = {dR, dG, dB};
+// the layer of a unit, from u.dy: weight gradients (want_w; x = the layer's input), then dx (+)= dy (*) W^T (dx null: not needed).
+// `below`: the unit whose dA this writes -- with fused_stats the statistics of its batch-norm backward ride on the launch; pre: their chunk count
+int layer_backward(ian_trainer* t, Unit& u, const float* x, bool want_w, int& pre, float* dx, int accumulate, Unit* below) {
+  int rc;
+  pre = 0;
+  if (want_w && (rc = wgrad(t, u.L, x, u.dy))) return rc;
+  if (!dx) return 0;
+  const bool ride = below && u.epilogue;
+  if (ride && (rc = arm_bwd_stats(t, u.L, *below))) return rc;
+  LCALL(u.L, ian_layer_backward_data, u.dy, t->n, dx, below ? below->ld : 0, accumulate, t->st);
+  if (ride) pre = armed_chunks(t, u.L);
+  return 0;
+}
+// backward of the whole unit from u.dA.  pre: in, chunk partials the launch that stored u.dA left (0: none); out, the same for `below`.
+// dskip: gradient of a second reader of y (the residual edge of an MD block), added to dy before the layer's backward
+int unit_backward(ian_trainer* t, Unit& u, const float* x, bool want_w, int& pre, float* dx, int accumulate, Unit* below, const float* dskip = nullptr) {
+  int rc;
+  if ((rc = bn_backward(t, u, want_w, pre))) return rc;
+  if (dskip) TK(ian_k_axpy(1.f, dskip, u.dy, u.rows * u.C, 1, t->st));
+  return layer_backward(t, u, x, want_w, pre, dx, accumulate, below);
+}
+// R, G_a, B_a from their three seeds -> D.u4.dA; *pre: chunk partials for bnorm_dc4's backward, which ride on the GEMM that stores it
+int head_backward(ian_trainer* t, DecPass& D, bool want_w, int* pre) {
+  *pre = 0;
+  LayerRef* hl[3] = {t->L.R, t->L.G_a, t->L.B_a};
+  const float *x = D.u4.a, *dys[3] = {D.gR, D.gG, D.gB};
+  float* dx = D.u4.dA;
   bool accs[3];
-  for (int i = 0; i < 3; ++i) accs[i] = t->touched.count(t->layers.at(names[i]).pnames[0]) > 0;
+  for (int i = 0; i < 3; ++i) accs[i] = t->touched[hl[i]->ids[0]] != 0;
   if (t->head6 && accs[0] == accs[1] && accs[1] == accs[2]) {
-    std::vector<float*> g[3];
-    for (int i = 0; i < 3; ++i)
-      for (auto& p : t->layers.at(names[i]).pnames) g[i].push_back(G(t, p));
-    if (arm && fuse_stats(t)) {   // bnorm_dc4's backward statistics ride on the GEMM that stores dh4
-      const int arc = arm_bwd_stats(t, "R", *arm, arm_a, arm_y, IAN_ACT_LRELU);
-      if (arc) return arc;
-    }
-    const int rc = ian_layer_head6_backward(lay(t, "R"), lay(t, "G_a"), lay(t, "B_a"), x, dR, dG, dB, t->n, 32, dx, 128, 0,
-                                            want_w ? g[0].data() : nullptr, want_w ? g[1].data() : nullptr, want_w ? g[2].data() : nullptr,
-                                            want_w ? (int)g[0].size() : 0, accs[0] ? 1 : 0, t->st);
+    int rc = arm_bwd_stats(t, hl[0], D.u4);
+    if (rc) return rc;
+    rc = ian_layer_head6_backward(hl[0]->l, hl[1]->l, hl[2]->l, x, dys[0], dys[1], dys[2], t->n, 32, dx, 128, 0, want_w ? hl[0]->grads.data() : nullptr,
+                                  want_w ? hl[1]->grads.data() : nullptr, want_w ? hl[2]->grads.data() : nullptr,
+                                  want_w ? (int)hl[0]->grads.size() : 0, accs[0] ? 1 : 0, t->st);
     if (rc == 0) {
-      if (pre) *pre = armed_chunks(t, "R");
+      *pre = armed_chunks(t, hl[0]);
       if (want_w)
         for (int i = 0; i < 3; ++i) {
-          const int mrc = mark(t, t->layers.at(names[i]).pnames);
+          const int mrc = mark(t, hl[i]->ids);
           if (mrc) return mrc;
         }
       return 0;
     }
-    (void)ian_layer_stats_next(lay(t, "R"), 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0);   // the per-layer fallback accumulates dx in three launches
-    if (rc != -4) return tfail(t, rc, "ian_layer_head6_backward failed (%d): %s", rc, ian_layer_last_error(lay(t, "R")));
+    (void)ian_layer_stats_next(hl[0]->l, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0);   // the per-layer fallback accumulates dx in three launches
+    if (rc != -4) return tfail(t, rc, "ian_layer_head6_backward failed (%d): %s", rc, ian_layer_last_error(hl[0]->l));
   }
   for (int i = 0; i < 3; ++i) {
     int rc;
-    if (want_w && (rc = wgrad(t, names[i], x, dys[i]))) return rc;
-    TL(lay(t, names[i]), ian_layer_backward_data(lay(t, names[i]), dys[i], t->n, dx, 0, i > 0 ? 1 : 0, t->st));
+    if (want_w && (rc = wgrad(t, hl[i], x, dys[i]))) return rc;
+    LCALL(hl[i], ian_layer_backward_data, dys[i], t->n, dx, 0, i > 0 ? 1 : 0, t->st);
   }
   return 0;
 }
 
 // ---- encoder pass (IAN.py:71-110 + discriminator head :209-216), training mode ------------------------------------------
-int enc_forward(ian_trainer* t, Bufs& E, std::map<std::string, BN>& bn, const float* x_nchw, int t0, int t1, int acc_target, bool running) {
+int enc_forward(ian_trainer* t, EncPass& E, const float* x_nchw, int t0, int t1, int acc_target, bool running) {
   const int n = t->n;
   int rc;
-  TK(ian_k_nchw_to_nhwc(x_nchw, E["x"], n, 4096, 3, 32, t->st));
-  TL(lay(t, "enc_conv1"), ian_layer_forward(lay(t, "enc_conv1"), E["x"], n, E["a1"], 0, P(t, "enc_conv1.b"), nullptr, IAN_ACT_LRELU, t->st));
-  for (int i = 2; i <= 4; ++i) {
-    const int w = ENC_WIDTHS[i - 1], hw = 64 >> i;
-    const std::string s = std::to_string(i), sp = std::to_string(i - 1), bnn = "bnorm" + s;
-    if ((rc = arm_fwd_stats(t, "enc_conv" + s))) return rc;
-    TL(lay(t, "enc_conv" + s), ian_layer_forward(lay(t, "enc_conv" + s), E["a" + sp], n, E["y" + s], 0, nullptr, nullptr, 0, t->st));
-    if ((rc = bn_forward(t, bn["bn" + s], E["y" + s], E["a" + s], (int64_t)n * hw * hw, w, w, P(t, bnn + ".gamma"), P(t, bnn + ".beta"),
-                         IAN_ACT_LRELU, (int64_t)n * hw * hw, running ? bnn.c_str() : nullptr, armed_chunks(t, "enc_conv" + s))))
-      return rc;
-  }
-  TK(ian_k_globalpool(E["a4"], E["feat"], n, 16, 1024, 1024, 1024, t->st));
-  TL(lay(t, "mb"), ian_layer_forward(lay(t, "mb"), E["feat"], n, E["act"], cs(2500), nullptr, nullptr, 0, t->st));
-  const float* act_all = E["act"];
+  TK(ian_k_nchw_to_nhwc(x_nchw, E.x, n, 4096, 3, 32, t->st));
+  LCALL(t->L.enc_conv[1], ian_layer_forward, E.x, n, E.a[1], 0, t->pr.enc_conv1_b.p, nullptr, IAN_ACT_LRELU, t->st);   // bias, no batch-norm (:71-80)
+  for (int i = 2; i <= 4; ++i)
+    if ((rc = unit_forward(t, E.u[i], E.a[i - 1], running))) return rc;
+  TK(ian_k_globalpool(E.a[4], E.feat, n, 16, 1024, 1024, 1024, t->st));
+  LCALL(t->L.mb, ian_layer_forward, E.feat, n, E.act, cs(2500), nullptr, nullptr, 0, t->st);
+  const float* act_all = E.act;
   int nall = n, row0 = 0;
   if (t->exact) {  // the kernel features couple every sample with every other one of the GLOBAL minibatch (layers.py:506-520)
-    if ((rc = gather(t, E["act"], E["act_all"], (int64_t)n * cs(2500), "the MinibatchLayer activations"))) return rc;
-    act_all = E["act_all"]; nall = t->N; row0 = t->rank * n;
+    if ((rc = gather(t, E.act, E.act_all, (int64_t)n * cs(2500), "the MinibatchLayer activations"))) return rc;
+    act_all = E.act_all; nall = t->N; row0 = t->rank * n;
   }
-  TK(ian_k_mb_forward(act_all, nall, cs(2500), row0, n, 500, 5, P(t, "minibatch_discrim.b"), E["feat"], 1024, 1024, E["mb"], cs(1524), t->st));
-  TK(ian_k_disc_head(E["mb"], cs(1524), 1524, P(t, "discrimi.W"), n, t0, t1, acc_target, E["p"], E["loss"], t->st));
+  TK(ian_k_mb_forward(act_all, nall, cs(2500), row0, n, 500, 5, t->pr.mb_b.p, E.feat, 1024, 1024, E.mb, cs(1524), t->st));
+  TK(ian_k_disc_head(E.mb, cs(1524), 1524, t->pr.discrimi_W.p, n, t0, t1, acc_target, E.p, E.loss, t->st));
   return 0;
 }
 // ce = (target0, w0, target1, w1): dlogits = sum w_t (p - onehot(target_t)).  feature_seeded: da1..da4 already hold the
 // feature-loss seeds (train_IAN.py:244).  want_w: accumulate encoder_params gradients.
-int enc_backward(ian_trainer* t, Bufs& E, std::map<std::string, BN>& bn, int t0, float w0, int t1, float w1, bool feature_seeded, bool want_w,
-                 bool want_dx) {
+int enc_backward(ian_trainer* t, EncPass& E, int t0, float w0, int t1, float w1, bool feature_seeded, bool want_w, bool want_dx) {
   const int n = t->n;
+  const auto& pr = t->pr;
   int rc;
-  TK(ian_k_disc_head_bwd(E["p"], P(t, "discrimi.W"), 1524, n, t0, w0, t1, w1, E["dlogits"], E["dmb"], cs(1524), t->st));
+  TK(ian_k_disc_head_bwd(E.p, pr.discrimi_W.p, 1524, n, t0, w0, t1, w1, E.dlogits, E.dmb, cs(1524), t->st));
   if (want_w) {
-    TK(ian_k_disc_head_wgrad(E["mb"], cs(1524), 1524, n, E["dlogits"], G(t, "discrimi.W"), t->touched.count("discrimi.W") ? 1 : 0, t->st));
-    if ((rc = mark(t, {"discrimi.W"}))) return rc;
+    TK(ian_k_disc_head_wgrad(E.mb, cs(1524), 1524, n, E.dlogits, pr.discrimi_W.g, t->touched[pr.discrimi_W.id] ? 1 : 0, t->st));
+    if ((rc = mark(t, {pr.discrimi_W.id}))) return rc;
     // db[k] = sum_b df[b,k] : column sums of dmb[:, 1024:1524]
-    TK(ian_k_colstats(2, E["dmb"] + 1024, nullptr, nullptr, nullptr, nullptr, n, 500, cs(1524), 0, t->ws_stats, n < 256 ? n : 256, t->tmp_vals, t->st));
-    if ((rc = acc64(t, "minibatch_discrim.b", t->tmp_vals, 500))) return rc;
+    TK(ian_k_colstats(2, E.dmb + 1024, nullptr, nullptr, nullptr, nullptr, n, 500, cs(1524), 0, t->ws_stats, n < 256 ? n : 256, t->tmp_vals, t->st));
+    if ((rc = acc64(t, pr.mb_b, t->tmp_vals, 500))) return rc;
   }
   {
-    const float *act_all = E["act"], *dmb_all = E["dmb"];
+    const float *act_all = E.act, *dmb_all = E.dmb;
     int nall = n, row0 = 0;
     if (t->exact) {  // a sample's activations feed every other sample's kernel features: their gradients come from all ranks
-      if ((rc = gather(t, E["dmb"], E["dmb_all"], (int64_t)n * cs(1524), "the MinibatchLayer gradients"))) return rc;
-      act_all = E["act_all"]; dmb_all = E["dmb_all"]; nall = t->N; row0 = t->rank * n;
+      if ((rc = gather(t, E.dmb, E.dmb_all, (int64_t)n * cs(1524), "the MinibatchLayer gradients"))) return rc;
+      act_all = E.act_all; dmb_all = E.dmb_all; nall = t->N; row0 = t->rank * n;
     }
-    TK(ian_k_mb_backward(act_all, nall, cs(2500), row0, n, 500, 5, dmb_all + 1024, cs(1524), E["dact"], cs(2500), t->st));
+    TK(ian_k_mb_backward(act_all, nall, cs(2500), row0, n, 500, 5, dmb_all + 1024, cs(1524), E.dact, cs(2500), t->st));
   }
-  TK(ian_k_grad_pass(E["dmb"], cs(1524), 0, E["dfeat"], nullptr, 1024, n, 1024, 0, 0, t->st));  // direct path of the concat (layers.py:524)
-  TL(lay(t, "mb"), ian_layer_backward_data(lay(t, "mb"), E["dact"], n, E["dfeat"], 1024, 1, t->st));
+  TK(ian_k_grad_pass(E.dmb, cs(1524), 0, E.dfeat, nullptr, 1024, n, 1024, 0, 0, t->st));  // direct path of the concat (layers.py:524)
+  LCALL(t->L.mb, ian_layer_backward_data, E.dact, n, E.dfeat, 1024, 1, t->st);
   if (want_w) {
     float* dW = t->mb_dW;
-    TL(lay(t, "mb"), ian_layer_backward_weight(lay(t, "mb"), E["feat"], E["dact"], n, &dW, 1, 0, t->st));
-    TK(ian_k_mb_weight_bwd(P(t, "minibatch_discrim.theta"), t->mb_colscale, t->mb_dW, G(t, "minibatch_discrim.theta"),
-                           G(t, "minibatch_discrim.log_weight_scale"), 1024, 2500, t->touched.count("minibatch_discrim.theta") ? 1 : 0, t->st));
-    if ((rc = mark(t, {"minibatch_discrim.theta", "minibatch_discrim.log_weight_scale"}))) return rc;
+    LCALL(t->L.mb, ian_layer_backward_weight, E.feat, E.dact, n, &dW, 1, 0, t->st);
+    TK(ian_k_mb_weight_bwd(pr.mb_theta.p, t->mb_colscale, t->mb_dW, pr.mb_theta.g, pr.mb_lws.g, 1024, 2500, t->touched[pr.mb_theta.id] ? 1 : 0, t->st));
+    if ((rc = mark(t, {pr.mb_theta.id, pr.mb_lws.id}))) return rc;
   }
-  TK(ian_k_globalpool_bwd(E["dfeat"], E["da4"], n, 16, 1024, 1024, 1024, feature_seeded ? 1 : 0, t->st));
-  int pre_next = 0;   // chunk partials the previous backward-data GEMM left for the next batch-norm backward (0: run colstats)
-  for (int i = 4; i >= 2; --i) {
-    const int w = ENC_WIDTHS[i - 1], hw = 64 >> i;
-    const std::string s = std::to_string(i), sp = std::to_string(i - 1);
-    float *da = E["da" + s], *a = E["a" + s], *y = E["y" + s];
-    if ((rc = bn_backward(t, bn["bn" + s], da, a, y, da, (int64_t)n * hw * hw, w, w, IAN_ACT_LRELU, "bnorm" + s + ".gamma", "bnorm" + s + ".beta", want_w,
-                          pre_next)))
-      return rc;
-    if (want_w && (rc = wgrad(t, "enc_conv" + s, E["a" + sp], da))) return rc;
-    // the gradient this launch stores is the input of the next normalisation down (bnorm<i-1>): its statistics ride along
-    if (i - 1 >= 2 && (rc = arm_bwd_stats(t, "enc_conv" + s, bn["bn" + sp], E["a" + sp], E["y" + sp], IAN_ACT_LRELU))) return rc;
-    TL(lay(t, "enc_conv" + s), ian_layer_backward_data(lay(t, "enc_conv" + s), da, n, E["da" + sp], 0, feature_seeded ? 1 : 0, t->st));
-    pre_next = i - 1 >= 2 ? armed_chunks(t, "enc_conv" + s) : 0;
-  }
+  TK(ian_k_globalpool_bwd(E.dfeat, E.da[4], n, 16, 1024, 1024, 1024, feature_seeded ? 1 : 0, t->st));
+  int pre = 0;   // chunk partials the previous backward-data GEMM left for the next batch-norm backward (0: run colstats)
+  for (int i = 4; i >= 2; --i)   // the gradient enc_conv<i> stores is the input of the next normalisation down (bnorm<i-1>); enc_conv1 has none
+    if ((rc = unit_backward(t, E.u[i], E.a[i - 1], want_w, pre, E.da[i - 1], feature_seeded ? 1 : 0, i > 2 ? &E.u[i - 1] : nullptr))) return rc;
   // enc_conv1: bias + lrelu, no batch-norm (IAN.py:71-80)
   if (want_w) {
-    TK(ian_k_colstats(2, E["da1"], E["a1"], nullptr, nullptr, nullptr, (int64_t)n * 1024, 128, 128, IAN_ACT_LRELU, t->ws_stats, 256, t->tmp_vals, t->st));
-    if ((rc = acc64(t, "enc_conv1.b", t->tmp_vals, 128))) return rc;
+    TK(ian_k_colstats(2, E.da[1], E.a[1], nullptr, nullptr, nullptr, (int64_t)n * 1024, 128, 128, IAN_ACT_LRELU, t->ws_stats, 256, t->tmp_vals, t->st));
+    if ((rc = acc64(t, pr.enc_conv1_b, t->tmp_vals, 128))) return rc;
   }
-  TK(ian_k_bn_bwd(E["da1"], E["a1"], nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, E["da1"], (int64_t)n * 1024, 128, 128, IAN_ACT_LRELU, t->st));
-  if (want_w && (rc = wgrad(t, "enc_conv1", E["x"], E["da1"]))) return rc;
-  if (want_dx) TL(lay(t, "enc_conv1"), ian_layer_backward_data(lay(t, "enc_conv1"), E["da1"], n, E["dx"], 0, 0, t->st));
+  TK(ian_k_bn_bwd(E.da[1], E.a[1], nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, E.da[1], (int64_t)n * 1024, 128, 128, IAN_ACT_LRELU, t->st));
+  if (want_w && (rc = wgrad(t, t->L.enc_conv[1], E.x, E.da[1]))) return rc;
+  if (want_dx) LCALL(t->L.enc_conv[1], ian_layer_backward_data, E.da[1], n, E.dx, 0, 0, t->st);
   return 0;
 }
 
 // ---- latent path (IAN.py:114-128): enc_fc1 -> (mu, logsigma) -> z0 = mu + e^ls * eps -> IAF ------------------------------
 int z_forward(ian_trainer* t, const float* a4, const float* eps) {
   const int n = t->n, Z = t->cfg.num_latents;
-  Bufs& S = t->ZS;
+  ZPass& S = t->ZS;
   int rc;
-  TL(lay(t, "enc_fc1"), ian_layer_forward(lay(t, "enc_fc1"), a4, n, S["y_fc1"], 1024, nullptr, nullptr, 0, t->st));
-  if ((rc = bn_forward(t, t->bnZ["bn_fc1"], S["y_fc1"], S["f"], n, 1000, 1024, P(t, "bnorm_enc_fc1.gamma"), P(t, "bnorm_enc_fc1.beta"), IAN_ACT_RELU, n,
-                       "bnorm_enc_fc1")))
-    return rc;
-  const char* trip[2][3] = {{"mu", "enc_mu", "mu_bnorm"}, {"ls", "enc_logsigma", "ls_bnorm"}};
+  if ((rc = unit_forward(t, S.fc1, a4, true))) return rc;
   if (!t->exact) {
-    for (auto& tr : trip) {
-      const std::string nm = tr[0], bnn = tr[2];
-      TL(lay(t, tr[1]), ian_layer_forward(lay(t, tr[1]), S["f"], n, S["y_" + nm], 128, nullptr, nullptr, 0, t->st));
-      if ((rc = bn_forward(t, t->bnZ["bn_" + nm], S["y_" + nm], S[nm], n, Z, 128, P(t, bnn + ".gamma"), P(t, bnn + ".beta"), 0, n, tr[2]))) return rc;
-    }
+    for (Unit* u : {&S.mu, &S.ls})
+      if ((rc = unit_forward(t, *u, S.fc1.a, true))) return rc;
   } else {  // both layers, both per-rank statistics, ONE all-gather of the adjacent sums, then both normalisations
     double* ws;
     if ((rc = ws_for(t, n, Z, &ws))) return rc;
-    for (auto& tr : trip) {
-      const std::string nm = tr[0];
-      TL(lay(t, tr[1]), ian_layer_forward(lay(t, tr[1]), S["f"], n, S["y_" + nm], 128, nullptr, nullptr, 0, t->st));
-      TK(ian_k_colstats(0, S["y_" + nm], nullptr, nullptr, nullptr, nullptr, n, Z, 128, 0, ws, chunks(t, n), t->bnZ["bn_" + nm].sums, t->st));
+    for (Unit* u : {&S.mu, &S.ls}) {
+      LCALL(u->L, ian_layer_forward, S.fc1.a, n, u->y, u->ld, nullptr, nullptr, 0, t->st);
+      TK(ian_k_colstats(0, u->y, nullptr, nullptr, nullptr, nullptr, n, Z, u->stride, 0, ws, chunks(t, n), u->bn.sums, t->st));
     }
-    if ((rc = allreduce_ordered(t, t->bnZ["bn_mu"].sums, 4 * Z))) return rc;
-    for (auto& tr : trip) {
-      const std::string nm = tr[0], bnn = tr[2];
-      float *rm = nullptr, *ri = nullptr;
-      if (t->update_running) { rm = P(t, bnn + ".mean"); ri = P(t, bnn + ".inv_std"); }
-      if ((rc = bn_forward_finish(t, t->bnZ["bn_" + nm], S["y_" + nm], S[nm], n, Z, 128, P(t, bnn + ".gamma"), P(t, bnn + ".beta"), 0, n, rm, ri))) return rc;
-    }
+    if ((rc = allreduce_ordered(t, S.mu.bn.sums, 4 * Z))) return rc;
+    for (Unit* u : {&S.mu, &S.ls})
+      if ((rc = bn_forward_finish(t, *u, true))) return rc;
   }
-  TK(ian_k_sample(S["mu"], S["ls"], eps, S["z0"], S["kl"], n, Z, 128, Z, t->st));
-  TK(ian_k_made_iaf(S["z0"], S["z"], t->made_w, t->made_b, n, Z, 128, t->st));
+  TK(ian_k_sample(S.mu.a, S.ls.a, eps, S.z0, S.kl, n, Z, 128, Z, t->st));
+  TK(ian_k_made_iaf(S.z0, S.z, t->made_w, t->made_b, n, Z, 128, t->st));
   return 0;
 }
 // dz = dL/dz (from the decoder) -> gradients of Z_params, including KL and (later) the L2 penalty
 int z_backward(ian_trainer* t, const float* dz, const float* a4) {
   const int n = t->n, Z = t->cfg.num_latents;
-  Bufs& S = t->ZS;
-  int rc;
-  TK(ian_k_made_iaf_bwd(S["z0"], dz, S["dz0"], t->made_w, t->made_b, n, Z, 128, t->st));
+  ZPass& S = t->ZS;
+  int rc, pre = 0;
+  TK(ian_k_made_iaf_bwd(S.z0, dz, S.dz0, t->made_w, t->made_b, n, Z, 128, t->st));
   const float klw = 1.f / ((float)t->N * 100.f);  // d(-0.5*mean(...)) over the GLOBAL batch: factor folded in the kernel's formula
-  TK(ian_k_sample_bwd(S["mu"], S["ls"], t->eps, S["dz0"], S["dmu"], S["dls"], n, Z, 128, Z, klw, t->st));
-  const char* trip[2][3] = {{"mu", "enc_mu", "mu_bnorm"}, {"ls", "enc_logsigma", "ls_bnorm"}};
-  bool first = true;
+  TK(ian_k_sample_bwd(S.mu.a, S.ls.a, t->eps, S.dz0, S.mu.dA, S.ls.dA, n, Z, 128, Z, klw, t->st));
   if (t->exact) {  // both gradient statistics, ONE all-gather (the sums are adjacent: z_alloc)
     double* ws;
     if ((rc = ws_for(t, n, Z, &ws))) return rc;
-    for (auto& tr : trip) {
-      const std::string nm = tr[0];
-      BN& b = t->bnZ["bn_" + nm];
-      TK(ian_k_colstats(1, S["d" + nm], nullptr, S["y_" + nm], b.mean, b.inv_std, n, Z, 128, 0, ws, chunks(t, n), b.bsums, t->st));
-    }
-    if ((rc = allreduce_ordered(t, t->bnZ["bn_mu"].bsums, 4 * Z))) return rc;
+    for (Unit* u : {&S.mu, &S.ls})
+      TK(ian_k_colstats(1, u->dA, nullptr, u->y, u->bn.mean, u->bn.inv_std, n, Z, u->stride, 0, ws, chunks(t, n), u->bn.bsums, t->st));
+    if ((rc = allreduce_ordered(t, S.mu.bn.bsums, 4 * Z))) return rc;
   }
-  for (auto& tr : trip) {
-    const std::string nm = tr[0], bnn = tr[2];
-    float* d = S["d" + nm];
-    if (t->exact) rc = bn_backward_finish(t, t->bnZ["bn_" + nm], d, nullptr, S["y_" + nm], d, n, Z, 128, 0, bnn + ".gamma", bnn + ".beta", true);
-    else rc = bn_backward(t, t->bnZ["bn_" + nm], d, nullptr, S["y_" + nm], d, n, Z, 128, 0, bnn + ".gamma", bnn + ".beta", true);
-    if (rc) return rc;
-    if ((rc = wgrad(t, tr[1], S["f"], d))) return rc;
-    TL(lay(t, tr[1]), ian_layer_backward_data(lay(t, tr[1]), d, n, S["df"], 1024, first ? 0 : 1, t->st));
-    first = false;
+  for (Unit* u : {&S.mu, &S.ls}) {   // both write df = S.fc1.dA: the second accumulates
+    if ((rc = t->exact ? bn_backward_finish(t, *u, true) : bn_backward(t, *u, true, 0))) return rc;
+    if ((rc = layer_backward(t, *u, S.fc1.a, true, pre, S.fc1.dA, u == &S.ls ? 1 : 0, &S.fc1))) return rc;
   }
-  if ((rc = bn_backward(t, t->bnZ["bn_fc1"], S["df"], S["f"], S["y_fc1"], S["df"], n, 1000, 1024, IAN_ACT_RELU, "bnorm_enc_fc1.gamma", "bnorm_enc_fc1.beta",
-                        true)))
-    return rc;
-  return wgrad(t, "enc_fc1", a4, S["df"]);
+  return unit_backward(t, S.fc1, a4, true, pre, nullptr, 0, nullptr);   // the encoder is not trained through the latent path
 }
 
 // ---- decoder pass (IAN.py:129-207), training mode -----------------------------------------------------------------------
-int dec_forward(ian_trainer* t, Bufs& D, std::map<std::string, BN>& bn, const float* zbuf, bool running) {
+int dec_forward(ian_trainer* t, DecPass& D, const float* zbuf, bool running) {
   const int n = t->n;
   int rc;
-  TL(lay(t, "l_dec_fc2"), ian_layer_forward(lay(t, "l_dec_fc2"), zbuf, n, D["h0"], 8192, t->fc2_bias, nullptr, IAN_ACT_LRELU, t->st));
-  const float* h = D["h0"];
-  for (const DecStage& s : dec_stages()) {
-    const std::string blk = s.blk;
-    const int64_t rows = (int64_t)n * (2 * s.hw) * (2 * s.hw);
-    auto g = [&](int j, const char* w) { return P(t, blk + "bnorm" + std::to_string(j) + "." + w); };
-    auto rn = [&](int j) -> std::string { return blk + "bnorm" + std::to_string(j); };
-    if ((rc = arm_fwd_stats(t, s.dc))) return rc;
-    TL(lay(t, s.dc), ian_layer_forward(lay(t, s.dc), h, n, D[blk + "_x"], 0, nullptr, nullptr, 0, t->st));
-    if ((rc = bn_forward(t, bn[blk + "_bn0"], D[blk + "_x"], D[blk + "_a"], rows, s.co, s.co, g(0, "gamma"), g(0, "beta"), IAN_ACT_LRELU, rows,
-                         running ? rn(0).c_str() : nullptr, armed_chunks(t, s.dc))))
-      return rc;
-    if ((rc = arm_fwd_stats(t, blk))) return rc;
-    TL(lay(t, blk), ian_layer_forward(lay(t, blk), D[blk + "_a"], n, D[blk + "_b"], 0, nullptr, nullptr, 0, t->st));
-    if ((rc = bn_forward(t, bn[blk + "_bn1"], D[blk + "_b"], D[blk + "_c"], rows, s.co, s.co, g(1, "gamma"), g(1, "beta"), IAN_ACT_LRELU, rows,
-                         running ? rn(1).c_str() : nullptr, armed_chunks(t, blk))))
-      return rc;
-    if ((rc = arm_fwd_stats(t, blk + "2"))) return rc;
-    TL(lay(t, blk + "2"), ian_layer_forward(lay(t, blk + "2"), D[blk + "_c"], n, D[blk + "_e"], 0, nullptr, D[blk + "_x"], 0, t->st));  // ElemwiseSum (layers.py:415)
-    if ((rc = bn_forward(t, bn[blk + "_bn2"], D[blk + "_e"], D[blk + "_h"], rows, s.co, s.co, g(2, "gamma"), g(2, "beta"), IAN_ACT_LRELU, rows,
-                         running ? rn(2).c_str() : nullptr, armed_chunks(t, blk + "2"))))
-      return rc;
-    h = D[blk + "_h"];
+  LCALL(t->L.l_dec_fc2, ian_layer_forward, zbuf, n, D.h0, 8192, t->fc2_bias, nullptr, IAN_ACT_LRELU, t->st);
+  const float* h = D.h0;
+  for (auto& u : D.stage) {   // IAN.py:139-171: x = deconv(h), then the MD block h = lrelu(bn2(x + MDCL2(lrelu(bn1(MDCL(lrelu(bn0(x))))))))
+    if ((rc = unit_forward(t, u[0], h, running))) return rc;
+    if ((rc = unit_forward(t, u[1], u[0].a, running))) return rc;
+    if ((rc = unit_forward(t, u[2], u[1].a, running, u[0].y))) return rc;  // ElemwiseSum (layers.py:415)
+    h = u[2].a;
   }
+  if ((rc = unit_forward(t, D.u4, h, running))) return rc;
   const int64_t rows = (int64_t)n * 4096;
-  if ((rc = arm_fwd_stats(t, "dec_conv4"))) return rc;
-  TL(lay(t, "dec_conv4"), ian_layer_forward(lay(t, "dec_conv4"), h, n, D["y4"], 0, nullptr, nullptr, 0, t->st));
-  if ((rc = bn_forward(t, bn["bn4"], D["y4"], D["h4"], rows, 128, 128, P(t, "bnorm_dc4.gamma"), P(t, "bnorm_dc4.beta"), IAN_ACT_LRELU, rows,
-                       running ? "bnorm_dc4" : nullptr, armed_chunks(t, "dec_conv4"))))
-    return rc;
+  const float* h4 = D.u4.a;
   const int sg = IAN_ACT_SIGMOID;
+  const Layers& L = t->L;
   // R = sigmoid(MDCL(h4)), G_a, B_a (IAN.py:183-199): the three layers that read the 128-channel map, one pass over it
   int h6 = -4;
-  if (t->head6) h6 = ian_layer_head6_forward(lay(t, "R"), lay(t, "G_a"), lay(t, "B_a"), D["h4"], n, D["R"], D["Ga"], D["Ba"], 32, sg, 0, 0, t->st);
+  if (t->head6) h6 = ian_layer_head6_forward(L.R->l, L.G_a->l, L.B_a->l, h4, n, D.R, D.Ga, D.Ba, 32, sg, 0, 0, t->st);
   if (h6 == -4) {
-    TL(lay(t, "R"), ian_layer_forward(lay(t, "R"), D["h4"], n, D["R"], 0, nullptr, nullptr, sg, t->st));  // IAN.py:183-186
-    TL(lay(t, "G_a"), ian_layer_forward(lay(t, "G_a"), D["h4"], n, D["Ga"], 0, nullptr, nullptr, 0, t->st));
-    TL(lay(t, "B_a"), ian_layer_forward(lay(t, "B_a"), D["h4"], n, D["Ba"], 0, nullptr, nullptr, 0, t->st));
+    LCALL(L.R, ian_layer_forward, h4, n, D.R, 0, nullptr, nullptr, sg, t->st);  // IAN.py:183-186
+    LCALL(L.G_a, ian_layer_forward, h4, n, D.Ga, 0, nullptr, nullptr, 0, t->st);
+    LCALL(L.B_a, ian_layer_forward, h4, n, D.Ba, 0, nullptr, nullptr, 0, t->st);
   } else if (h6) {
-    return tfail(t, h6, "ian_layer_head6_forward failed (%d): %s", h6, ian_layer_last_error(lay(t, "R")));
+    return tfail(t, h6, "ian_layer_head6_forward failed (%d): %s", h6, ian_layer_last_error(L.R->l));
   }
-  TL(lay(t, "G_b"), ian_layer_forward(lay(t, "G_b"), D["R"], n, D["G"], 0, nullptr, D["Ga"], sg, t->st));   // :187-196
-  TK(ian_k_concat2(D["R"], 2, 32, D["G"], 2, 32, D["RG"], 32, rows, t->st));                                // :201
-  TL(lay(t, "B_b"), ian_layer_forward(lay(t, "B_b"), D["RG"], n, D["B"], 0, nullptr, D["Ba"], sg, t->st));  // :197-206
-  TK(ian_k_beta(D["R"], D["G"], D["B"], D["xhat"], n, 4096, 32, t->st));                                    // :207
+  LCALL(L.G_b, ian_layer_forward, D.R, n, D.G, 0, nullptr, D.Ga, sg, t->st);   // :187-196
+  TK(ian_k_concat2(D.R, 2, 32, D.G, 2, 32, D.RG, 32, rows, t->st));            // :201
+  LCALL(L.B_b, ian_layer_forward, D.RG, n, D.B, 0, nullptr, D.Ba, sg, t->st);  // :197-206
+  TK(ian_k_beta(D.R, D.G, D.B, D.xhat, n, 4096, 32, t->st));                   // :207
   return 0;
 }
-// D['dxhat'] (NCHW) -> gradients of decoder_params (want_w) and D['dz'] (want_dz)
-int dec_backward(ian_trainer* t, Bufs& D, std::map<std::string, BN>& bn, const float* zbuf, bool want_w, bool want_dz) {
+// D.dxhat (NCHW) -> gradients of decoder_params (want_w) and D.dz (want_dz)
+int dec_backward(ian_trainer* t, DecPass& D, const float* zbuf, bool want_w, bool want_dz) {
   const int n = t->n;
   const int64_t rows = (int64_t)n * 4096;
   const int sg = IAN_ACT_SIGMOID;
+  const Layers& L = t->L;
   int rc;
-  TK(ian_k_beta_bwd(D["dxhat"], D["R"], D["G"], D["B"], D["gR"], D["gG"], D["gB"], n, 4096, 32, sg, t->st));
+  TK(ian_k_beta_bwd(D.dxhat, D.R, D.G, D.B, D.gR, D.gG, D.gB, n, 4096, 32, sg, t->st));
   // B = sigmoid(B_a(h4) + B_b([R,G]))
-  if (want_w && (rc = wgrad(t, "B_b", D["RG"], D["gB"]))) return rc;
-  TL(lay(t, "B_b"), ian_layer_backward_data(lay(t, "B_b"), D["gB"], n, D["dRG"], 0, 0, t->st));
-  TK(ian_k_grad_pass(D["dRG"], 32, 0, D["gR"], D["R"], 32, rows, 2, sg, 1, t->st));
-  TK(ian_k_grad_pass(D["dRG"], 32, 2, D["gG"], D["G"], 32, rows, 2, sg, 1, t->st));
+  if (want_w && (rc = wgrad(t, L.B_b, D.RG, D.gB))) return rc;
+  LCALL(L.B_b, ian_layer_backward_data, D.gB, n, D.dRG, 0, 0, t->st);
+  TK(ian_k_grad_pass(D.dRG, 32, 0, D.gR, D.R, 32, rows, 2, sg, 1, t->st));
+  TK(ian_k_grad_pass(D.dRG, 32, 2, D.gG, D.G, 32, rows, 2, sg, 1, t->st));
   // G = sigmoid(G_a(h4) + G_b(R))
-  if (want_w && (rc = wgrad(t, "G_b", D["R"], D["gG"]))) return rc;
-  TL(lay(t, "G_b"), ian_layer_backward_data(lay(t, "G_b"), D["gG"], n, D["dRt"], 0, 0, t->st));
-  TK(ian_k_grad_pass(D["dRt"], 32, 0, D["gR"], D["R"], 32, rows, 2, sg, 1, t->st));
+  if (want_w && (rc = wgrad(t, L.G_b, D.R, D.gG))) return rc;
+  LCALL(L.G_b, ian_layer_backward_data, D.gG, n, D.dRt, 0, 0, t->st);
+  TK(ian_k_grad_pass(D.dRt, 32, 0, D.gR, D.R, 32, rows, 2, sg, 1, t->st));
   // R = sigmoid(R(h4)): all three seeds are final here
   int pre = 0;   // chunk partials the GEMM that stored a gradient left for the batch-norm backward that consumes it (0: colstats)
-  if ((rc = head_backward(t, D["h4"], D["gR"], D["gG"], D["gB"], D["dh4"], want_w, &bn["bn4"], D["h4"], D["y4"], &pre))) return rc;
-  // dec_conv4 + bnorm_dc4 + lrelu
-  if ((rc = bn_backward(t, bn["bn4"], D["dh4"], D["h4"], D["y4"], D["dh4"], rows, 128, 128, IAN_ACT_LRELU, "bnorm_dc4.gamma", "bnorm_dc4.beta", want_w,
-                        pre)))
-    return rc;
-  const auto& ST = dec_stages();
-  const std::string last_blk = ST.back().blk;
-  if (want_w && (rc = wgrad(t, "dec_conv4", D[last_blk + "_h"], D["dh4"]))) return rc;
-  if ((rc = arm_bwd_stats(t, "dec_conv4", bn[last_blk + "_bn2"], D[last_blk + "_h"], D[last_blk + "_e"], IAN_ACT_LRELU))) return rc;
-  TL(lay(t, "dec_conv4"), ian_layer_backward_data(lay(t, "dec_conv4"), D["dh4"], n, D[last_blk + "_dh"], 0, 0, t->st));
-  pre = armed_chunks(t, "dec_conv4");
-  for (int si = (int)ST.size() - 1; si >= 0; --si) {
-    const DecStage& s = ST[si];
-    const std::string blk = s.blk;
-    const int64_t r = (int64_t)n * (2 * s.hw) * (2 * s.hw);
-    auto bnn = [&](int j, const char* w) { return blk + "bnorm" + std::to_string(j) + "." + w; };
-    float *dh = D[blk + "_dh"], *dx = D[blk + "_dx"], *da = D[blk + "_da"], *dcg = D[blk + "_dc"];
-    // h = lrelu(bn2(x + d)),  d = MDCL2(c)
-    if ((rc = bn_backward(t, bn[blk + "_bn2"], dh, D[blk + "_h"], D[blk + "_e"], dh, r, s.co, s.co, IAN_ACT_LRELU, bnn(2, "gamma"), bnn(2, "beta"), want_w,
-                          pre)))
-      return rc;
-    if (want_w && (rc = wgrad(t, blk + "2", D[blk + "_c"], dh))) return rc;
-    if ((rc = arm_bwd_stats(t, blk + "2", bn[blk + "_bn1"], D[blk + "_c"], D[blk + "_b"], IAN_ACT_LRELU))) return rc;
-    TL(lay(t, blk + "2"), ian_layer_backward_data(lay(t, blk + "2"), dh, n, dcg, 0, 0, t->st));
-    if ((rc = bn_backward(t, bn[blk + "_bn1"], dcg, D[blk + "_c"], D[blk + "_b"], dcg, r, s.co, s.co, IAN_ACT_LRELU, bnn(1, "gamma"), bnn(1, "beta"), want_w,
-                          armed_chunks(t, blk + "2"))))
-      return rc;
-    if (want_w && (rc = wgrad(t, blk, D[blk + "_a"], dcg))) return rc;
-    if ((rc = arm_bwd_stats(t, blk, bn[blk + "_bn0"], D[blk + "_a"], D[blk + "_x"], IAN_ACT_LRELU))) return rc;
-    TL(lay(t, blk), ian_layer_backward_data(lay(t, blk), dcg, n, da, 0, 0, t->st));
-    if ((rc = bn_backward(t, bn[blk + "_bn0"], da, D[blk + "_a"], D[blk + "_x"], dx, r, s.co, s.co, IAN_ACT_LRELU, bnn(0, "gamma"), bnn(0, "beta"), want_w,
-                          armed_chunks(t, blk))))
-      return rc;
-    TK(ian_k_axpy(1.f, dh, dx, r * s.co, 1, t->st));  // residual edge: dx += d(x+d)
-    const float* src = si == 0 ? D["h0"] : D[std::string(ST[si - 1].blk) + "_h"];
-    if (want_w && (rc = wgrad(t, s.dc, src, dx))) return rc;
-    pre = 0;
-    if (si > 0) {   // the gradient this launch stores enters the previous stage's bnorm2 backward
-      const std::string pb = ST[si - 1].blk;
-      if ((rc = arm_bwd_stats(t, s.dc, bn[pb + "_bn2"], D[pb + "_h"], D[pb + "_e"], IAN_ACT_LRELU))) return rc;
-    }
-    TL(lay(t, s.dc), ian_layer_backward_data(lay(t, s.dc), dx, n, si == 0 ? D["dh0"] : D[std::string(ST[si - 1].blk) + "_dh"], 0, 0, t->st));
-    if (si > 0) pre = armed_chunks(t, s.dc);
+  if ((rc = head_backward(t, D, want_w, &pre))) return rc;
+  // dec_conv4 + bnorm_dc4 + lrelu: its gradient enters the last stage's bnorm2 backward
+  Unit* top = &D.stage[2][2];
+  if ((rc = unit_backward(t, D.u4, top->a, want_w, pre, top->dA, 0, top))) return rc;
+  for (int si = 2; si >= 0; --si) {
+    Unit* u = D.stage[si];
+    Unit* prev = si > 0 ? &D.stage[si - 1][2] : nullptr;   // the previous stage's output unit (stage 0 reads h0 = l_dec_fc2's output)
+    // h = lrelu(bn2(x + d)),  d = MDCL2(c),  c = lrelu(bn1(MDCL(a))),  a = lrelu(bn0(x)),  x = deconv(previous h)
+    if ((rc = unit_backward(t, u[2], u[1].a, want_w, pre, u[1].dA, 0, &u[1]))) return rc;
+    if ((rc = unit_backward(t, u[1], u[0].a, want_w, pre, u[0].dA, 0, &u[0]))) return rc;
+    if ((rc = unit_backward(t, u[0], prev ? prev->a : D.h0, want_w, pre, prev ? prev->dA : D.dh0, 0, prev, u[2].dy))) return rc;  // residual edge: dx += d(x+d)
   }
   // l_dec_fc2: bias + lrelu
-  TK(ian_k_bn_bwd(D["dh0"], D["h0"], nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, D["dh0"], n, 8192, 8192, IAN_ACT_LRELU, t->st));
+  TK(ian_k_bn_bwd(D.dh0, D.h0, nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, D.dh0, n, 8192, 8192, IAN_ACT_LRELU, t->st));
   if (want_w) {
-    if ((rc = wgrad(t, "l_dec_fc2", zbuf, D["dh0"]))) return rc;
-    TK(ian_k_colstats(2, D["dh0"], nullptr, nullptr, nullptr, nullptr, n, 8192, 8192, 0, t->ws_stats, n < 256 ? n : 256, t->tmp_big, t->st));
+    if ((rc = wgrad(t, L.l_dec_fc2, zbuf, D.dh0))) return rc;
+    TK(ian_k_colstats(2, D.dh0, nullptr, nullptr, nullptr, nullptr, n, 8192, 8192, 0, t->ws_stats, n < 256 ? n : 256, t->tmp_big, t->st));
     TK(ian_k_axpy_f64(1.0, t->tmp_big, t->fc2_tmp, 8192, 0, t->st));   // float64 column sums -> float32, (H,W,C) order
     TK(ian_k_gather(t->fc2_tmp, t->fc2_inv, t->fc2_db, 8192, t->st));
-    if ((rc = acc(t, "l_dec_fc2.b", t->fc2_db, 8192))) return rc;
+    if ((rc = acc(t, t->pr.l_dec_fc2_b, t->fc2_db, 8192))) return rc;
   }
-  if (want_dz) TL(lay(t, "l_dec_fc2"), ian_layer_backward_data(lay(t, "l_dec_fc2"), D["dh0"], n, D["dz"], 128, 0, t->st));
+  if (want_dz) LCALL(L.l_dec_fc2, ian_layer_backward_data, D.dh0, n, D.dz, 128, 0, t->st);
   return 0;
 }
 
-
-// ---- timing-only two-chain experiment (see ian_trainer::dual_timing) -------------------------------------------------------------
+// ---- timing-only two-chain experiment (see ian_trainer::dual_timing): all three are inert unless dual_timing is set ----------------
 int chain_fork(ian_trainer* t) {   // stream B starts behind everything issued to the compute stream so far
+  if (!t->dual_timing) return 0;
   if (!t->stB) THIP(hipStreamCreateWithFlags(&t->stB, hipStreamNonBlocking));
   hipEvent_t e;
   THIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1158,6 +1170,7 @@ int chain_fork(ian_trainer* t) {   // stream B starts behind everything issued t
   return 0;
 }
 int chain_join(ian_trainer* t) {   // the compute stream waits for stream B
+  if (!t->dual_timing) return 0;
   hipEvent_t e;
   THIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   THIP(hipEventRecord(e, t->stB));
@@ -1168,11 +1181,12 @@ int chain_join(ian_trainer* t) {   // the compute stream waits for stream B
 struct OnStreamB {                 // everything issued while this object lives goes to stream B
   ian_trainer* t;
   hipStream_t keep;
-  explicit OnStreamB(ian_trainer* tt) : t(tt), keep(tt->st) { t->st = t->stB; }
+  explicit OnStreamB(ian_trainer* tt) : t(tt), keep(tt->st) { if (t->dual_timing) t->st = t->stB; }
   ~OnStreamB() { t->st = keep; }
 };
 
 // ---- the step -----------------------------------------------------------------------------------------------------------
+// TIMING ONLY with dual_timing: the (Z_rand -> decoder -> encoder) chain concurrently on stream B, workspaces shared without protection
 int forward(ian_trainer* t, const float* X, const float* Zr, const float* eps) {  // the three passes of train_IAN.py:116-149
   const int n = t->n, Z = t->cfg.num_latents;
   int rc;
@@ -1183,29 +1197,19 @@ int forward(ian_trainer* t, const float* X, const float* Zr, const float* eps) {
   if ((rc = refresh_weights(t))) return rc;
   t->X = X;
   t->eps = eps;
-  if (t->dual_timing) {   // TIMING ONLY: chain B concurrently on its own stream, workspaces shared without protection
-    if ((rc = chain_fork(t))) return rc;
-    if ((rc = enc_forward(t, t->EX, t->bnEX, X, 0, -1, 0, true))) return rc;
-    if ((rc = z_forward(t, t->EX["a4"], eps))) return rc;
-    if ((rc = dec_forward(t, t->DZ, t->bnDZ, t->ZS["z"], true))) return rc;
-    if ((rc = enc_forward(t, t->EH, t->bnEH, t->DZ["xhat"], 0, 1, 1, false))) return rc;
-    {
-      OnStreamB b(t);
-      TK(ian_k_grad_pass(Zr, Z, 0, t->zgen0, nullptr, 128, n, Z, 0, 0, t->st));
-      TK(ian_k_made_iaf(t->zgen0, t->zgen, t->made_w, t->made_b, n, Z, 128, t->st));
-      if ((rc = dec_forward(t, t->DG, t->bnDG, t->zgen, false))) return rc;
-      if ((rc = enc_forward(t, t->EG, t->bnEG, t->DG["xhat"], 0, 2, 2, false))) return rc;
-    }
-    return chain_join(t);
+  if ((rc = chain_fork(t))) return rc;
+  if ((rc = enc_forward(t, t->EX, X, 0, -1, 0, true))) return rc;           // p_X vs p1
+  if ((rc = z_forward(t, t->EX.a[4], eps))) return rc;
+  if ((rc = dec_forward(t, t->DZ, t->ZS.z, true))) return rc;               // X_hat
+  if ((rc = enc_forward(t, t->EH, t->xhat_override ? t->xhat_override : t->DZ.xhat, 0, 1, 1, false))) return rc;  // p_X_hat
+  {
+    OnStreamB b(t);
+    TK(ian_k_grad_pass(Zr, Z, 0, t->zgen0, nullptr, 128, n, Z, 0, 0, t->st));       // (n,100) -> padded rows
+    TK(ian_k_made_iaf(t->zgen0, t->zgen, t->made_w, t->made_b, n, Z, 128, t->st));  // {l_Z_IAF: Z} (train_IAN.py:149)
+    if ((rc = dec_forward(t, t->DG, t->zgen, false))) return rc;            // X_gen
+    if ((rc = enc_forward(t, t->EG, t->xgen_override ? t->xgen_override : t->DG.xhat, 0, 2, 2, false))) return rc;  // p_X_gen
   }
-  if ((rc = enc_forward(t, t->EX, t->bnEX, X, 0, -1, 0, true))) return rc;  // p_X vs p1
-  if ((rc = z_forward(t, t->EX["a4"], eps))) return rc;
-  if ((rc = dec_forward(t, t->DZ, t->bnDZ, t->ZS["z"], true))) return rc;   // X_hat
-  if ((rc = enc_forward(t, t->EH, t->bnEH, t->xhat_override ? t->xhat_override : t->DZ["xhat"], 0, 1, 1, false))) return rc;  // p_X_hat
-  TK(ian_k_grad_pass(Zr, Z, 0, t->zgen0, nullptr, 128, n, Z, 0, 0, t->st));  // (n,100) -> padded rows
-  TK(ian_k_made_iaf(t->zgen0, t->zgen, t->made_w, t->made_b, n, Z, 128, t->st));  // {l_Z_IAF: Z} (train_IAN.py:149)
-  if ((rc = dec_forward(t, t->DG, t->bnDG, t->zgen, false))) return rc;     // X_gen
-  return enc_forward(t, t->EG, t->bnEG, t->xgen_override ? t->xgen_override : t->DG["xhat"], 0, 2, 2, false);  // p_X_gen
+  return chain_join(t);
 }
 
 // all scalar losses of train_IAN.py:169-250,279: partial sums on the device (+ their all-reduce: issued on EVERY data-parallel step,
@@ -1215,15 +1219,14 @@ int metrics_device(ian_trainer* t) {
   const float N = (float)t->N;   // means are over the GLOBAL batch
   float* s = t->scalars;
   THIP(hipMemsetAsync(s, 0, 64 * sizeof(float), t->st));
-  TK(ian_k_sum_rows(t->EX["loss"], n, 4, 1.f / N, s + 0, t->st));   // [0] discrim_d_loss, [2] acc(p_X)
-  TK(ian_k_sum_rows(t->EH["loss"], n, 4, 1.f / N, s + 4, t->st));   // [4] gen_recon_loss, [5] CE(p_X_hat,p2), [6] acc
-  TK(ian_k_sum_rows(t->EG["loss"], n, 4, 1.f / N, s + 8, t->st));   // [8] gen_sample_loss, [9] CE(p_X_gen,p3), [10] acc
-  TK(ian_k_sum_rows(t->ZS["kl"], n * 100, 1, -0.5f / (N * 100.f), s + 12, t->st));
-  TK(ian_k_pair_loss(t->DZ["xhat"], t->X, nullptr, (int64_t)n * 3 * 4096, 1, 1, 0, 0.f, 0, t->ws_loss, 1024, 1.f / (N * 3.f * 4096.f), s + 16, t->st));
-  for (int i = 0; i < 4; ++i) {
-    const float cnt = (float)((32 >> i) * (32 >> i) * ENC_WIDTHS[i]);
-    const std::string a = "a" + std::to_string(i + 1);
-    TK(ian_k_pair_loss(t->EH[a], t->EX[a], nullptr, (int64_t)n * (int64_t)cnt, 1, 1, 1, 0.f, 0, t->ws_loss, 1024, 1.f / (N * cnt * 4.f), s + 20 + 2 * i, t->st));
+  TK(ian_k_sum_rows(t->EX.loss, n, 4, 1.f / N, s + 0, t->st));   // [0] discrim_d_loss, [2] acc(p_X)
+  TK(ian_k_sum_rows(t->EH.loss, n, 4, 1.f / N, s + 4, t->st));   // [4] gen_recon_loss, [5] CE(p_X_hat,p2), [6] acc
+  TK(ian_k_sum_rows(t->EG.loss, n, 4, 1.f / N, s + 8, t->st));   // [8] gen_sample_loss, [9] CE(p_X_gen,p3), [10] acc
+  TK(ian_k_sum_rows(t->ZS.kl, n * 100, 1, -0.5f / (N * 100.f), s + 12, t->st));
+  TK(ian_k_pair_loss(t->DZ.xhat, t->X, nullptr, (int64_t)n * 3 * 4096, 1, 1, 0, 0.f, 0, t->ws_loss, 1024, 1.f / (N * 3.f * 4096.f), s + 16, t->st));
+  for (int i = 1; i <= 4; ++i) {
+    const float cnt = (float)((64 >> i) * (64 >> i) * ENC_WIDTHS[i - 1]);
+    TK(ian_k_pair_loss(t->EH.a[i], t->EX.a[i], nullptr, (int64_t)n * (int64_t)cnt, 1, 1, 1, 0.f, 0, t->ws_loss, 1024, 1.f / (N * cnt * 4.f), s + 18 + 2 * i, t->st));
   }
   if (t->world > 1) {  // per-rank partial means add up to the global ones
     int rc = t->comm.allreduce_sum(t->comm.ctx, s, 64, t->st);
@@ -1260,70 +1263,65 @@ int backward(ian_trainer* t, bool gen) {  // gradients of the update rules of tr
   int rc;
   if ((rc = begin_backward(t, gen ? 0 : 1))) return rc;
   // ---- shared generator-side loss S = adv_gen + recon_weight*pixel + feature_weight*feature ---------------------------------
-  for (int i = 0; i < 4; ++i) {  // feature_loss seeds (train_IAN.py:244)
-    const float cnt = (float)((32 >> i) * (32 >> i) * ENC_WIDTHS[i]);
-    const std::string a = "a" + std::to_string(i + 1);
-    TK(ian_k_pair_loss(t->EH[a], t->EX[a], t->EH["d" + a], (int64_t)n * (int64_t)cnt, 1, 1, 1, c.feature_weight / (4.f * N * cnt), 0, t->ws_loss, 1024, 0.f,
+  for (int i = 1; i <= 4; ++i) {  // feature_loss seeds (train_IAN.py:244)
+    const float cnt = (float)((64 >> i) * (64 >> i) * ENC_WIDTHS[i - 1]);
+    TK(ian_k_pair_loss(t->EH.a[i], t->EX.a[i], t->EH.da[i], (int64_t)n * (int64_t)cnt, 1, 1, 1, c.feature_weight / (4.f * N * cnt), 0, t->ws_loss, 1024, 0.f,
                        t->scalars + 40, t->st));
   }
-  if ((rc = enc_backward(t, t->EH, t->bnEH, 0, c.agr_weight / N, -1, 0.f, true, false, true))) return rc;  // gen_recon_loss (:247)
-  TK(ian_k_pair_loss(t->DZ["xhat"], t->X, t->DZ["dxhat"], (int64_t)n * 3 * 4096, 1, 1, 0, c.recon_weight / (N * 3.f * 4096.f), 0, t->ws_loss, 1024, 0.f,
+  if ((rc = enc_backward(t, t->EH, 0, c.agr_weight / N, -1, 0.f, true, false, true))) return rc;  // gen_recon_loss (:247)
+  TK(ian_k_pair_loss(t->DZ.xhat, t->X, t->DZ.dxhat, (int64_t)n * 3 * 4096, 1, 1, 0, c.recon_weight / (N * 3.f * 4096.f), 0, t->ws_loss, 1024, 0.f,
                      t->scalars + 40, t->st));  // pixel_loss (:169)
-  TK(ian_k_nhwc_to_nchw(t->EH["dx"], 32, t->DZ["tmp_img"], n, 4096, 3, t->st));
-  TK(ian_k_axpy(1.f, t->DZ["tmp_img"], t->DZ["dxhat"], (int64_t)n * 3 * 4096, 1, t->st));
-  if (t->dual_timing) {   // TIMING ONLY (see forward)
-    if ((rc = chain_fork(t))) return rc;
-    if ((rc = dec_backward(t, t->DZ, t->bnDZ, t->ZS["z"], gen, true))) return rc;
-    if ((rc = z_backward(t, t->DZ["dz"], t->EX["a4"]))) return rc;
-    if (gen) {
-      OnStreamB b(t);
-      if ((rc = enc_backward(t, t->EG, t->bnEG, 0, c.ags_weight / N, -1, 0.f, false, false, true))) return rc;
-      TK(ian_k_nhwc_to_nchw(t->EG["dx"], 32, t->DG["dxhat"], n, 4096, 3, t->st));
-      if ((rc = dec_backward(t, t->DG, t->bnDG, t->zgen, true, false))) return rc;
-    } else {
-      if ((rc = enc_backward(t, t->EX, t->bnEX, 0, c.dd_weight / N, -1, 0.f, false, true, false))) return rc;
-      if ((rc = enc_backward(t, t->EH, t->bnEH, 1, c.dg_weight / N, -1, 0.f, false, true, false))) return rc;
-      OnStreamB b(t);
-      if ((rc = enc_backward(t, t->EG, t->bnEG, 2, c.dg_weight / N, -1, 0.f, false, true, false))) return rc;
-    }
-    return chain_join(t);
-  }
-  if ((rc = dec_backward(t, t->DZ, t->bnDZ, t->ZS["z"], gen, true))) return rc;
-  if ((rc = z_backward(t, t->DZ["dz"], t->EX["a4"]))) return rc;
+  TK(ian_k_nhwc_to_nchw(t->EH.dx, 32, t->DZ.tmp_img, n, 4096, 3, t->st));
+  TK(ian_k_axpy(1.f, t->DZ.tmp_img, t->DZ.dxhat, (int64_t)n * 3 * 4096, 1, t->st));
+  if ((rc = chain_fork(t))) return rc;   // TIMING ONLY with dual_timing (see forward): the X_gen chain's sweeps run on stream B
+  if ((rc = dec_backward(t, t->DZ, t->ZS.z, gen, true))) return rc;
+  if ((rc = z_backward(t, t->DZ.dz, t->EX.a[4]))) return rc;
   if (gen) {
-    if ((rc = enc_backward(t, t->EG, t->bnEG, 0, c.ags_weight / N, -1, 0.f, false, false, true))) return rc;  // gen_sample_loss (:248)
-    TK(ian_k_nhwc_to_nchw(t->EG["dx"], 32, t->DG["dxhat"], n, 4096, 3, t->st));
-    return dec_backward(t, t->DG, t->bnDG, t->zgen, true, false);
+    OnStreamB b(t);
+    if ((rc = enc_backward(t, t->EG, 0, c.ags_weight / N, -1, 0.f, false, false, true))) return rc;  // gen_sample_loss (:248)
+    TK(ian_k_nhwc_to_nchw(t->EG.dx, 32, t->DG.dxhat, n, 4096, 3, t->st));
+    if ((rc = dec_backward(t, t->DG, t->zgen, true, false))) return rc;
+  } else {
+    // ---- discriminator loss, X_hat and X_gen constant (consider_constant, train_IAN.py:253) ----------------------------------
+    if ((rc = enc_backward(t, t->EX, 0, c.dd_weight / N, -1, 0.f, false, true, false))) return rc;  // discrim_d_loss (:234)
+    if ((rc = enc_backward(t, t->EH, 1, c.dg_weight / N, -1, 0.f, false, true, false))) return rc;  // p_X_hat vs p2 (:228)
+    OnStreamB b(t);
+    if ((rc = enc_backward(t, t->EG, 2, c.dg_weight / N, -1, 0.f, false, true, false))) return rc;  // p_X_gen vs p3
   }
-  // ---- discriminator loss, X_hat and X_gen constant (consider_constant, train_IAN.py:253) ------------------------------------
-  if ((rc = enc_backward(t, t->EX, t->bnEX, 0, c.dd_weight / N, -1, 0.f, false, true, false))) return rc;  // discrim_d_loss (:234)
-  if ((rc = enc_backward(t, t->EH, t->bnEH, 1, c.dg_weight / N, -1, 0.f, false, true, false))) return rc;  // p_X_hat vs p2 (:228)
-  return enc_backward(t, t->EG, t->bnEG, 2, c.dg_weight / N, -1, 0.f, false, true, false);                 // p_X_gen vs p3
+  return chain_join(t);
 }
 
 int regularizers(ian_trainer* t, bool gen) {  // train_IAN.py:211-221: L2 on the Z parameters, orthogonal penalty on the 4-D weights
   const ian_train_config& c = t->cfg;
-  for (auto& nme : t->zp.names) {
-    if (nme.size() >= 5 && nme.compare(nme.size() - 5, 5, ".beta") == 0) continue;
-    TK(ian_k_axpy(2.f * c.reg, P(t, nme), G(t, nme), numel_of(t, nme), 1, t->st));
+  const Group& zp = t->grp[G_Z];
+  for (int id : zp.params) {
+    const Param& q = t->params[id];
+    if (q.name.size() >= 5 && q.name.compare(q.name.size() - 5, 5, ".beta") == 0) continue;
+    TK(ian_k_axpy(2.f * c.reg, zp.p + q.off, zp.g + q.off, q.shape.numel(), 1, t->st));
   }
   if (c.ortho < 0.f) return 0;
-  Group& grp = gen ? t->dec : t->enc;
-  for (auto& nme : grp.names) {
-    const Shape& s = grp.off.at(nme).second;
-    if (nme.back() == 'W' && s.d.size() == 4)
-      TK(ian_k_ortho(P(t, nme), G(t, nme), (int)s.d[0], (int)s.d[1], (int)s.d[2], c.ortho, t->ortho_vals, t->st));
+  const Group& grp = t->grp[gen ? G_DEC : G_ENC];
+  for (int id : grp.params) {
+    const Param& q = t->params[id];
+    const Shape& s = q.shape;
+    if (q.name.back() == 'W' && s.d.size() == 4)
+      TK(ian_k_ortho(grp.p + q.off, grp.g + q.off, (int)s.d[0], (int)s.d[1], (int)s.d[2], c.ortho, t->ortho_vals, t->st));
   }
   return 0;
 }
 
-int adam(ian_trainer* t, Group& g, const char* gname) {  // lasagne.updates.adam (App. B.7): one (t, m, v) per group
+int adam(ian_trainer* t, int group) {  // lasagne.updates.adam (App. B.7): one (t, m, v) per group
+  Group& g = t->grp[group];
   g.t += 1;
   const double b1 = t->cfg.beta1, b2 = 0.999;
   const double a_t = t->cfg.learning_rate * sqrt(1.0 - pow(b2, g.t)) / (1.0 - pow(b1, g.t));
   TK(ian_k_adam(g.p, g.g, g.m, g.v, g.numel, (float)a_t, (float)b1, (float)b2, 1e-8f, t->st));
-  t->dirty.insert(gname);
+  t->dirty[group] = true;
   return 0;
+}
+int adam_both(ian_trainer* t, bool gen) {  // update_gen: decoder_params, update_discrim: encoder_params; Z_params in both (train_IAN.py:274-276)
+  const int rc = adam(t, gen ? G_DEC : G_ENC);
+  return rc ? rc : adam(t, G_Z);
 }
 
 bool is_device_ptr(const void* p) {
@@ -1386,14 +1384,22 @@ int ian_trainer_finalize(ian_trainer* t) {
   for (auto& kv : t->shapes)
     if (!t->host.count(kv.first)) return tfail(t, -2, "missing parameter '%s'", kv.first.c_str());
   int rc;
-  for (Group* g : {&t->enc, &t->zp, &t->dec, &t->stats}) {
+  for (int gi = 0; gi < 4; ++gi) {
+    Group* g = &t->grp[gi];
     g->p = dalloc(t, g->numel);
-    if (g != &t->stats) { g->g = dalloc(t, g->numel); g->m = dalloc(t, g->numel); g->v = dalloc(t, g->numel); }
+    if (gi != G_STATS) { g->g = dalloc(t, g->numel); g->m = dalloc(t, g->numel); g->v = dalloc(t, g->numel); }
     if (!g->p) return tfail(t, -20, "out of device memory (parameter groups)");
     std::vector<float> flat((size_t)g->numel, 0.f);
-    for (auto& nme : g->names) memcpy(flat.data() + g->off[nme].first, t->host[nme].data(), t->host[nme].size() * sizeof(float));
+    for (int id : g->params) {
+      const std::vector<float>& v = t->host[t->params[id].name];
+      memcpy(flat.data() + t->params[id].off, v.data(), v.size() * sizeof(float));
+    }
     THIP(hipMemcpy(g->p, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice));
   }
+  t->touched.assign(t->params.size(), 0);
+  t->pr.enc_conv1_b = param(t, "enc_conv1.b"); t->pr.mb_theta = param(t, "minibatch_discrim.theta");
+  t->pr.mb_lws = param(t, "minibatch_discrim.log_weight_scale"); t->pr.mb_b = param(t, "minibatch_discrim.b");
+  t->pr.discrimi_W = param(t, "discrimi.W"); t->pr.l_dec_fc2_b = param(t, "l_dec_fc2.b");
   {  // MADE x2: never trained -> pre-masked constants (layers.py:671,703)
     std::vector<float> w((size_t)6 * Z * Z), b((size_t)6 * Z);
     int k = 0;
@@ -1428,9 +1434,10 @@ int ian_trainer_finalize(ian_trainer* t) {
   t->mb_W = dalloc(t, (size_t)1024 * 2500); t->mb_dW = dalloc(t, (size_t)1024 * 2500); t->mb_colscale = dalloc(t, 2500);
   t->tmp_vals = dalloc64(t, 2048); t->ortho_vals = dalloc(t, 2048);
   if ((rc = build_layers(t))) return rc;
-  enc_alloc(t, t->EX, t->bnEX); enc_alloc(t, t->EH, t->bnEH); enc_alloc(t, t->EG, t->bnEG);
+  enc_alloc(t, t->EX, "EX"); enc_alloc(t, t->EH, "EH"); enc_alloc(t, t->EG, "EG");
   z_alloc(t);
-  dec_alloc(t, t->DZ, t->bnDZ); dec_alloc(t, t->DG, t->bnDG);
+  dec_alloc(t, t->DZ, "DZ"); dec_alloc(t, t->DG, "DG");
+  if (!t->unresolved.empty()) return tfail(t, -2, "the training graph names a parameter that is not declared: '%s'", t->unresolved.c_str());
   t->zgen = dalloc(t, (size_t)t->n * 128); t->zgen0 = dalloc(t, (size_t)t->n * 128);
   t->xin = dalloc(t, (size_t)t->n * 3 * 4096); t->zin = dalloc(t, (size_t)t->n * 100); t->epsin = dalloc(t, (size_t)t->n * 100);
   if (t->oom) return tfail(t, -20, "out of device memory while allocating the training step's buffers (batch %d per GPU)", t->n);
@@ -1445,7 +1452,7 @@ int ian_trainer_finalize(ian_trainer* t) {
                     "differently on N ranks and in one process, so the data-parallel step is NOT guaranteed bit-identical to the "
                     "single-process step (float64 sums: the float32 statistics can differ in the last bit); train_IAN.py's "
                     "semantics are unaffected\n", t->n, t->world);
-  t->dirty = {"enc", "Z", "dec"};
+  t->dirty[G_ENC] = t->dirty[G_Z] = t->dirty[G_DEC] = true;
   t->host.clear();
   t->finalized = true;
   return 0;
@@ -1501,8 +1508,7 @@ int step_body(ian_trainer* t, bool gen, const float* x, const float* zrand, cons
   if ((rc = backward(t, gen))) return rc;
   if ((rc = finish_allreduce(t, gen ? 0 : 1))) return rc;
   if ((rc = regularizers(t, gen))) return rc;
-  if ((rc = adam(t, gen ? t->dec : t->enc, gen ? "dec" : "enc"))) return rc;
-  return adam(t, t->zp, "Z");
+  return adam_both(t, gen);
 }
 // error path of any entry that may have issued work on the trainer's own streams: nothing of it may still be running (and
 // writing the shared buffers) when the caller sees the error code
@@ -1579,8 +1585,7 @@ int ian_trainer_apply_adam(ian_trainer* t, int32_t which) {
   if (!t || !t->finalized || (which != 0 && which != 1)) return -1;
   int rc = join_side_stream(t);
   if (rc) return rc;
-  if ((rc = adam(t, which == 0 ? t->dec : t->enc, which == 0 ? "dec" : "enc"))) return rc;
-  return adam(t, t->zp, "Z");
+  return adam_both(t, which == 0);
 }
 /* One encoder backward sweep of pass 0 = encoder(X), 1 = encoder(X_hat), 2 = encoder(X_gen) with cross-entropy seeds
    dlogits = w0 (p - onehot(t0)) + w1 (p - onehot(t1)) (t < 0: none); reset != 0 starts a fresh gradient sweep first. */
@@ -1590,13 +1595,11 @@ int ian_trainer_enc_backward(ian_trainer* t, int32_t pass, int32_t t0, float w0,
   if (reset) {
     int rc = join_side_stream(t);
     if (rc) return rc;
-    t->touched.clear();
+    t->touched.assign(t->params.size(), 0);
     t->evlog.clear();
     t->buckets = nullptr;
   }
-  Bufs& E = pass == 0 ? t->EX : (pass == 1 ? t->EH : t->EG);
-  auto& bn = pass == 0 ? t->bnEX : (pass == 1 ? t->bnEH : t->bnEG);
-  int rc = enc_backward(t, E, bn, t0, w0, t1, w1, feature_seeded != 0, want_w != 0, want_dx != 0);
+  int rc = enc_backward(t, pass == 0 ? t->EX : (pass == 1 ? t->EH : t->EG), t0, w0, t1, w1, feature_seeded != 0, want_w != 0, want_dx != 0);
   if (!rc) rc = join_side_stream(t);
   if (rc) quiesce(t);
   return rc;
@@ -1609,16 +1612,8 @@ int ian_trainer_buffer(ian_trainer* t, const char* name, void** ptr, int64_t* nu
   const std::string s = name;
   if (s == "scalars") { *ptr = t->scalars; if (numel) *numel = 64; return 0; }
   if (s == "ws_loss") { *ptr = t->ws_loss; if (numel) *numel = 2048; return 0; }
-  const size_t d = s.find('.');
-  if (d == std::string::npos) return tfail(t, -2, "unknown buffer '%s'", name);
-  const std::string ps = s.substr(0, d), rest = s.substr(d + 1);
-  Bufs* B = nullptr;
-  std::map<std::string, BN>* bn = nullptr;
-  if (ps == "EX") { B = &t->EX; bn = &t->bnEX; } else if (ps == "EH") { B = &t->EH; bn = &t->bnEH; } else if (ps == "EG") { B = &t->EG; bn = &t->bnEG; }
-  else if (ps == "ZS") { B = &t->ZS; bn = &t->bnZ; } else if (ps == "DZ") { B = &t->DZ; bn = &t->bnDZ; } else if (ps == "DG") { B = &t->DG; bn = &t->bnDG; }
-  else return tfail(t, -2, "unknown pass in buffer name '%s'", name);
-  auto it = B->find(rest);
-  if (it != B->end()) {
+  auto it = t->bufs.find(s);
+  if (it != t->bufs.end()) {
     *ptr = it->second;
     if (numel) {
       auto sz = t->alloc_floats.find(it->second);
@@ -1626,19 +1621,17 @@ int ian_trainer_buffer(ian_trainer* t, const char* name, void** ptr, int64_t* nu
     }
     return 0;
   }
-  const size_t d2 = rest.rfind('.');
-  if (d2 != std::string::npos) {
-    auto bi = bn->find(rest.substr(0, d2));
-    if (bi != bn->end()) {
-      const std::string f = rest.substr(d2 + 1);
-      BN& b = bi->second;
-      void* p = f == "mean" ? (void*)b.mean : f == "inv_std" ? (void*)b.inv_std : f == "scale" ? (void*)b.scale : f == "shift" ? (void*)b.shift
-                : f == "sums" ? (void*)b.sums : f == "bsums" ? (void*)b.bsums : nullptr;
-      if (p) {
-        *ptr = p;
-        if (numel) *numel = (f == "sums" || f == "bsums") ? 2 * b.C : b.C;
-        return 0;
-      }
+  const size_t d = s.rfind('.');
+  auto bi = d == std::string::npos ? t->bns.end() : t->bns.find(s.substr(0, d));
+  if (bi != t->bns.end()) {
+    const std::string f = s.substr(d + 1);
+    BN& b = *bi->second;
+    void* p = f == "mean" ? (void*)b.mean : f == "inv_std" ? (void*)b.inv_std : f == "scale" ? (void*)b.scale : f == "shift" ? (void*)b.shift
+              : f == "sums" ? (void*)b.sums : f == "bsums" ? (void*)b.bsums : nullptr;
+    if (p) {
+      *ptr = p;
+      if (numel) *numel = (f == "sums" || f == "bsums") ? 2 * b.C : b.C;
+      return 0;
     }
   }
   return tfail(t, -2, "unknown buffer '%s'", name);
@@ -1646,7 +1639,7 @@ int ian_trainer_buffer(ian_trainer* t, const char* name, void** ptr, int64_t* nu
 /* group 0 encoder_params, 1 Z_params, 2 decoder_params, 3 batch-norm running averages: the flat device buffers (reference layouts). */
 int ian_trainer_group(ian_trainer* t, int32_t group, float** p, float** g, float** m, float** v, int64_t* numel) {
   if (!t || !t->finalized || group < 0 || group > 3) return -1;
-  Group& gr = group == 3 ? t->stats : group_of(t, group);
+  Group& gr = t->grp[group];
   if (p) *p = gr.p;
   if (g) *g = gr.g;
   if (m) *m = gr.m;
@@ -1656,18 +1649,18 @@ int ian_trainer_group(ian_trainer* t, int32_t group, float** p, float** g, float
 }
 int ian_trainer_param_info(ian_trainer* t, const char* name, int32_t* group, int64_t* offset, int64_t* numel) {
   if (!t || !name) return -1;
-  auto it = t->where.find(name);
-  if (it == t->where.end()) return tfail(t, -2, "unknown parameter '%s'", name);
-  Group* g = it->second;
-  if (group) *group = g == &t->stats ? 3 : group_index(t, g);
-  if (offset) *offset = g->off.at(name).first;
-  if (numel) *numel = g->off.at(name).second.numel();
+  auto it = t->pindex.find(name);
+  if (it == t->pindex.end()) return tfail(t, -2, "unknown parameter '%s'", name);
+  const Param& q = t->params[it->second];
+  if (group) *group = q.group;
+  if (offset) *offset = q.off;
+  if (numel) *numel = q.shape.numel();
   return 0;
 }
 /* Parameters of `group` were written behind the trainer's back (tests, checkpoint loading): repack before the next forward. */
 int ian_trainer_mark_dirty(ian_trainer* t, int32_t group) {
   if (!t || group < 0 || group > 2) return -1;
-  t->dirty.insert(group == 0 ? "enc" : (group == 1 ? "Z" : "dec"));
+  t->dirty[group] = true;
   return 0;
 }
 /* "exposed_ms_gen" / "exposed_ms_discrim": mean stall of the compute stream on the gradient all-reduce per update of that kind
@@ -1677,15 +1670,7 @@ int ian_trainer_stat(ian_trainer* t, const char* key, double* out) {
   if (!t || !key || !out) return -1;
   const std::string k = key;
   if (k == "exposed_ms_gen" || k == "exposed_ms_discrim") {
-    if (t->ex_pending) {
-      float ms = 0.f;
-      if (hipEventSynchronize(t->ex1) == hipSuccess && hipEventElapsedTime(&ms, t->ex0, t->ex1) == hipSuccess) {
-        t->exposed_ms[t->ex_which] += ms;
-        t->exposed_n[t->ex_which] += 1;
-      }
-      (void)hipGetLastError();
-      t->ex_pending = false;
-    }
+    fold_exposed(t);
     const int w = k == "exposed_ms_gen" ? 0 : 1;
     *out = t->exposed_n[w] ? t->exposed_ms[w] / t->exposed_n[w] : 0.0;
   } else if (k == "gather_ms_gen" || k == "gather_ms_discrim" || k == "gathers_gen" || k == "gathers_discrim") {
@@ -1738,10 +1723,10 @@ int ian_trainer_autotune(ian_trainer* t, void* stream) {
     rc = tfail(t, -20, "hipMemcpy of the autotune operands failed");
   }
   if (!rc) rc = refresh_weights(t);
-  for (auto& key : t->layer_order) {
+  for (LayerRef& r : t->layers) {
     if (rc) break;
-    rc = ian_layer_autotune(t->layers[key].l, t->n, a, b, (int64_t)need, t->st);
-    if (rc) tfail(t, rc, "ian_layer_autotune(%s) failed (%d): %s", key.c_str(), rc, ian_layer_last_error(t->layers[key].l));
+    rc = ian_layer_autotune(r.l, t->n, a, b, (int64_t)need, t->st);
+    if (rc) tfail(t, rc, "ian_layer_autotune(%s) failed (%d): %s", r.key.c_str(), rc, ian_layer_last_error(r.l));
   }
   (void)hipStreamSynchronize(t->st);
   (void)hipFree(a);
@@ -1752,14 +1737,14 @@ int ian_trainer_autotune(ian_trainer* t, void* stream) {
 /* Copy a parameter (trainable, batch-norm running average) or, grad != 0, its gradient of the last step to the host. */
 int ian_trainer_read_param(ian_trainer* t, const char* name, int32_t grad, float* out, int64_t numel) {
   if (!t || !t->finalized || !name || !out) return -1;
-  auto it = t->where.find(name);
-  if (it == t->where.end()) return tfail(t, -2, "unknown parameter '%s'", name);
-  Group* g = it->second;
+  auto it = t->pindex.find(name);
+  if (it == t->pindex.end()) return tfail(t, -2, "unknown parameter '%s'", name);
+  const Param& q = t->params[it->second];
+  const Group* g = &t->grp[q.group];
   if (grad && !g->g) return tfail(t, -2, "'%s' has no gradient (not trainable)", name);
-  const auto& o = g->off.at(name);
-  if (o.second.numel() != numel) return tfail(t, -3, "parameter '%s' has %lld elements", name, (long long)o.second.numel());
+  if (q.shape.numel() != numel) return tfail(t, -3, "parameter '%s' has %lld elements", name, (long long)q.shape.numel());
   THIP(hipDeviceSynchronize());   // the compute stream, the weight-gradient stream and the bucket stream
-  THIP(hipMemcpy(out, (grad ? g->g : g->p) + o.first, numel * sizeof(float), hipMemcpyDeviceToHost));
+  THIP(hipMemcpy(out, (grad ? g->g : g->p) + q.off, numel * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1789,7 +1774,7 @@ int ian_trainer_set_option(ian_trainer* t, const char* key, double value) {
 
 int32_t ian_trainer_adam_steps(ian_trainer* t, int32_t group) {  /* 0 encoder_params, 1 Z_params, 2 decoder_params */
   if (!t) return -1;
-  return group == 0 ? t->enc.t : (group == 1 ? t->zp.t : t->dec.t);
+  return group < 0 || group > 2 ? -1 : t->grp[group].t;
 }
 
 const char* ian_trainer_last_error(ian_trainer* t) { return t ? t->err.c_str() : "null trainer"; }
@@ -1801,11 +1786,12 @@ void ian_trainer_destroy(ian_trainer* t) {
   for (hipEvent_t e : t->events) (void)hipEventDestroy(e);
   if (t->st2) (void)hipStreamDestroy(t->st2);
   if (t->st_comm) (void)hipStreamDestroy(t->st_comm);
+  if (t->stB) (void)hipStreamDestroy(t->stB);
   if (t->ex0) (void)hipEventDestroy(t->ex0);
   if (t->ex1) (void)hipEventDestroy(t->ex1);
   for (auto& pool : t->gev)
     for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  for (auto& kv : t->layers) ian_layer_destroy(kv.second.l);
+  for (LayerRef& r : t->layers) ian_layer_destroy(r.l);
   for (float* p : t->allocs)
     if (p) (void)hipFree(p);
   delete t;
