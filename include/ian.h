@@ -404,6 +404,61 @@ int ian_session_undo(ian_handle* h, int32_t n, const int32_t* ids, const int32_t
    redo.  Host only: no device state is touched.  -6 without the reservation, -7 for an id outside the pool or not opened. */
 int ian_session_history(ian_handle* h, int32_t id, int32_t out[3]);
 
+/* ---- saving and loading whole sessions: the editor state as bytes that can leave the pool ----
+   Everything a session is -- the 64x64 state, the full-resolution source and edit field, the user mask and flags, the ring of undo
+   states with its cursor -- lives in one handle's pool.  A record is that state as plain bytes: keep a project beyond the process,
+   move an editor to another handle or GPU, park an idle editor and give its id to someone else.  One session is one meta block (64
+   bytes, host data) and one body:
+     body = every array of the pool, in the order GIM IM RECON ERROR Z MODE | SRC FIELD FIELD_KIND | UMASK LOCAL | the ring's Z rows,
+            the ring's UMASK rows -- the groups the pool has reserved -- each padded with zeros to a multiple of 16 bytes.
+   Records are canonical: two saves of the same logical state give the same bytes, and no byte of a record comes from memory the
+   session never wrote.  Entry k of the history goes to slot k of the record whatever its place in the ring; slots >= hist_len are
+   zero; SRC of a session without a source is zero.  A load puts entry k into ring slot k, leaves the slots >= hist_len and the SRC
+   row of a record without a source unwritten, and restarts the ring at slot 0.
+   A record belongs to the pool layout it was saved from (num_latents, scale, local, depth): a load into any other layout is
+   refused, never converted.  It is only meaningful with the weights it was edited under; the record carries no fingerprint of them,
+   so keeping the two together is the caller's business. */
+#define IAN_SESSION_RECORD_MAGIC 0x534e4149u /* "IANS" */
+#define IAN_SESSION_RECORD_FORMAT 1
+#define IAN_SESSION_RECORD_MAX_COLUMNS 13
+typedef struct ian_session_meta {
+  uint32_t magic;           /* IAN_SESSION_RECORD_MAGIC */
+  int32_t format;           /* IAN_SESSION_RECORD_FORMAT */
+  int32_t num_latents;      /* the layout of the pool the record came from: the model's latent size, */
+  int32_t scale;            /*   the full-resolution scale (0: no such reservation), */
+  int32_t local;            /*   1 with the local reservation, */
+  int32_t depth;            /*   the history's depth (0: none) */
+  int32_t has_source;       /* what the library keeps per session on the host: 1 when SRC holds a photo, */
+  int32_t local_flags;      /*   the LOCAL flags 0..3, */
+  int32_t hist_len;         /*   the history's entries and cursor (0 <= hist_cur <= hist_len; see ian_session_undo) */
+  int32_t hist_cur;
+  int64_t body_bytes;       /* bytes of one body in this layout: a multiple of 16 */
+  int32_t reserved[4];      /* zero */
+} ian_session_meta;
+
+/* The record layout of this handle's pool.  layout (or NULL) receives magic, format, the four layout fields and body_bytes, the
+   per-session fields zero; offsets (or NULL; room for IAN_SESSION_RECORD_MAX_COLUMNS) the byte offset in the body of every array the
+   pool has, in the order above; ncols (or NULL) how many those are.  Host only: no device state is touched.  -6 without a pool. */
+int ian_session_record_info(ian_handle* h, ian_session_meta* layout, int64_t* offsets, int32_t* ncols);
+/* n opened sessions -> n records in one submission: meta is a host array of n entries, body n * body_bytes bytes, host or device,
+   16-byte aligned.  One upload (4 words per session), one gather kernel straight into a device body; a host body goes through a
+   staging buffer of at most `session_stage_bytes` (ian_set_option; default 64 MiB, never less than one record), as many
+   gather-then-copy passes in stream order as that takes, and one synchronisation.  Like ian_session_read it leaves the decoder's
+   resident activations and the residency of ian_session_brush alone, and it changes no session.
+   -6: no pool.  -7, naming the item, before anything is enqueued: n outside 1..256, an id outside the pool, a session not opened, an
+   id given twice, ids or meta not host arrays, body not 16-byte aligned. */
+int ian_session_save(ian_handle* h, int32_t n, const int32_t* ids, ian_session_meta* meta, void* body, void* stream);
+/* n records -> sessions ids[0..n-1] of this pool, opened or not, in one submission (one upload, one scatter kernel; a host body in
+   copy-then-scatter passes as above).  Afterwards each target is opened, holds the record's state -- source bit, LOCAL flags, history
+   entries and cursor included -- and counts as a new latent version, so that a forward left resident for its old latent is not
+   reused.  No other session and none of the decoder's activations are touched; nothing is displayed: read IM or redisplay.
+   -6: no pool.  -7, naming the item and the field, before anything is enqueued or any host state moves: the cases of
+   ian_session_save (the targets need not be opened); a bad magic or format; num_latents, scale, local, depth or body_bytes other
+   than this pool's (the message gives both values); local_flags outside 0..3, or not 0 in a layout without the local reservation;
+   has_source outside 0..1, or 1 at scale 0; a cursor outside 0 <= hist_cur <= hist_len, hist_len > depth with hist_cur == hist_len,
+   hist_len > depth + 1 otherwise, any entry at depth 0; a reserved word that is not zero. */
+int ian_session_load(ian_handle* h, int32_t n, const int32_t* ids, const ian_session_meta* meta, const void* body, void* stream);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -241,6 +241,101 @@ def pack_session_undo(ids, steps=1, capacity=None, opened=None):
     return idv, np.ascontiguousarray(a, np.int32)
 
 
+class SessionRecords:
+    """n saved sessions (EditSessions.save): `meta`, a structured array of n ian_session_meta entries (npe_ops.SESSION_META_DTYPE),
+    and `body`, uint8 (n, body_bytes) -- a numpy array, or a torch device tensor when the save was asked for device memory.
+    tobytes / frombytes are what a project file on disk is: a 16-byte header ("IANR", format, n, body_bytes), the metas,
+    the bodies."""
+    FILE_MAGIC = b"IANR"
+
+    def __init__(self, meta, body):
+        from . import npe_ops
+        meta = np.asarray(meta)
+        if meta.dtype != npe_ops.SESSION_META_DTYPE or meta.ndim != 1:
+            raise ValueError("meta must be a 1-D array of npe_ops.SESSION_META_DTYPE, got %s %s" % (meta.dtype, meta.shape))
+        self.meta = np.ascontiguousarray(meta)
+        self.body = body if hasattr(body, "data_ptr") else np.ascontiguousarray(body, np.uint8)
+        if len(self.body.shape) != 2 or self.body.shape[0] != len(self.meta):
+            raise ValueError("body must have shape (%d, body_bytes), got %s" % (len(self.meta), tuple(self.body.shape)))
+
+    def __len__(self):
+        return len(self.meta)
+
+    @property
+    def on_device(self):
+        return hasattr(self.body, "data_ptr")
+
+    def host(self):
+        """-> the same records with the body in host memory."""
+        return SessionRecords(self.meta, self.body.cpu().numpy()) if self.on_device else self
+
+    def __getitem__(self, i):
+        """A single record or a slice of them, as SessionRecords."""
+        if isinstance(i, (int, np.integer)):
+            k = range(len(self))[i]
+            i = slice(k, k + 1)
+        return SessionRecords(self.meta[i], self.body[i])
+
+    def tobytes(self):
+        h = self.host()
+        bb = int(h.body.shape[1])
+        head = self.FILE_MAGIC + np.array([1, len(h), bb], "<i4").tobytes()
+        return head + h.meta.tobytes() + h.body.tobytes()
+
+    @classmethod
+    def frombytes(cls, data):
+        from . import npe_ops
+        data = bytes(data)
+        if len(data) < 16 or data[:4] != cls.FILE_MAGIC:
+            raise ValueError("not a session record file")
+        fmt, n, bb = (int(v) for v in np.frombuffer(data, "<i4", 3, 4))
+        if fmt != 1 or n < 0 or bb < 0 or bb % 16 or len(data) != 16 + n * (64 + bb):
+            raise ValueError("a session record file of format %d with %d records of %d bytes cannot be %d bytes long" % (fmt, n, bb, len(data)))
+        meta = np.frombuffer(data, npe_ops.SESSION_META_DTYPE, n, 16).copy()
+        body = np.empty((n, bb), np.uint8)                                # a fresh array: 16-byte aligned, writable
+        body[...] = np.frombuffer(data, np.uint8, n * bb, 16 + 64 * n).reshape(n, bb)
+        return cls(meta, body)
+
+
+def pack_session_records(ids, records, zl, scale=0, local=False, depth=0, capacity=None):
+    """Python arguments of ian_session_load -> (ids int32 (n,), meta (n,), body (n, body_bytes)), validated before the library sees
+    anything: the ids (the targets need not be opened), one record per id, a body of the layout's size, and every meta against the
+    layout (zl, scale, local, depth) of the pool: npe_ops.check_session_meta.  A host body comes back 16-byte aligned."""
+    from . import npe_ops
+    idv = check_session_ids(ids, capacity, None)
+    if not isinstance(records, SessionRecords):
+        raise ValueError("records must be SessionRecords, got %s" % type(records).__name__)
+    n = len(idv)
+    if len(records) != n:
+        raise ValueError("%d records for %d sessions" % (len(records), n))
+    bb = npe_ops.session_record_layout(zl, scale, local, depth)[1]
+    if tuple(records.body.shape) != (n, bb):
+        raise ValueError("body must have shape (%d,%d) for this pool, got %s" % (n, bb, tuple(records.body.shape)))
+    for i in range(n):
+        bad = npe_ops.check_session_meta(records.meta[i], zl, scale, local, depth)
+        if bad:
+            raise ValueError("item %d: the record's %s = %d does not fit this pool (num_latents %d, scale %d, local %d, depth %d, body_bytes %d)"
+                             % (i, bad, int(np.asarray(records.meta[i][bad]).reshape(-1)[0]), zl, scale, int(bool(local)), depth, bb))
+    body = records.body
+    if not records.on_device:
+        if body.dtype != np.uint8:
+            raise ValueError("body must be uint8, got %s" % body.dtype)
+        if not body.flags.c_contiguous or body.ctypes.data % 16:
+            body = _aligned_bytes(body)
+    elif not body.is_contiguous() or body.data_ptr() % 16:
+        raise ValueError("a device body must be contiguous and 16-byte aligned")
+    return idv, records.meta, body
+
+
+def _aligned_bytes(a):
+    """A C-contiguous uint8 copy of `a` whose first byte sits at a multiple of 16."""
+    raw = np.empty(a.size + 16, np.uint8)
+    off = -raw.ctypes.data % 16
+    out = raw[off:off + a.size].reshape(a.shape)
+    out[...] = a
+    return out
+
+
 class EditSessions:
     """Device-resident edit sessions of one model (ian_session_*, include/ian.h): the state NPE.py keeps in host globals per
     editor (GIM, IM, RECON, ERROR, Z, SAMPLE_FLAG) lives in device memory under a caller-chosen id in 0..capacity-1.  A call takes
@@ -254,7 +349,9 @@ class EditSessions:
     Local edits (NPE.py's unimplemented USER_MASK, gk and dampen): reserve_local() keeps a user mask per session;
         set_local(ids, local, dampen)  from then on a paint on those sessions changes the photo only around the strokes made since
     Undo (no counterpart in NPE.py): reserve_history(depth) keeps a ring of saved latents (and user masks) per session on the device;
-        mark(ids)  a stroke begins     undo(ids, steps) / redo(ids, steps)  back and forth -> shown     history(sid)  what is possible"""
+        mark(ids)  a stroke begins     undo(ids, steps) / redo(ids, steps)  back and forth -> shown     history(sid)  what is possible
+    Leaving the pool (no counterpart in NPE.py): save(ids) -> SessionRecords, everything above as bytes; load(ids, records) puts them
+        into any ids of a pool of the same layout: a project file, a move to another handle, parking an idle editor"""
 
     def __init__(self, handle, capacity, zdim, sigma=0.7):
         from . import npe_ops
@@ -364,6 +461,48 @@ class EditSessions:
             raise ValueError("session %d has not been opened" % sid)
         depth, undo, redo = self._h.session_history(sid)
         return {"depth": depth, "undo": undo, "redo": redo}
+
+    def _layout(self):
+        return self._zdim, self.scale, self.local, self.history_depth
+
+    def record_info(self):
+        """The record layout of this pool, from the library -> {"num_latents", "scale", "local", "depth", "body_bytes", "offsets"}:
+        offsets are the byte offsets of the pool's arrays in a body, in npe_ops.session_record_columns' order."""
+        layout, offsets = self._h.session_record_info()
+        out = {k: int(getattr(layout, k)) for k in ("num_latents", "scale", "local", "depth", "body_bytes")}
+        out["offsets"] = offsets
+        return out
+
+    def save(self, ids, device=False):
+        """The whole state of the opened sessions `ids` -- pictures, latent, source, edit field, user mask, flags, undo history and
+        cursor -- as SessionRecords, in one submission; the sessions stay as they are.  device=True keeps the bodies in device
+        memory (a torch uint8 tensor, written on torch's current stream)."""
+        from . import npe_ops
+        idv = self._ids(ids, True)
+        n, bb = len(idv), npe_ops.session_record_layout(*self._layout())[1]
+        meta = np.zeros(n, npe_ops.SESSION_META_DTYPE)
+        if device:
+            import torch
+            body = torch.empty((n, bb), dtype=torch.uint8, device="cuda")
+            self._h.session_save(idv, meta, body, stream=torch.cuda.current_stream().cuda_stream)
+        else:
+            body = np.empty((n, bb), np.uint8)
+            self._h.session_save(idv, meta, body)
+        return SessionRecords(meta, body)
+
+    def load(self, ids, records):
+        """records[i] becomes session ids[i], opened or not: everything save() took, the undo history and its cursor included.  The
+        records must come from a pool of this layout (latent size, scale, local, history depth) and belong to this model's weights.
+        Nothing is displayed: read the session or redisplay it."""
+        idv, meta, body = pack_session_records(ids, records, *self._layout(), capacity=self.capacity)
+        if records.on_device:
+            import torch
+            self._h.session_load(idv, meta, body, stream=torch.cuda.current_stream().cuda_stream)
+        else:
+            self._h.session_load(idv, meta, body)
+        for v, m in zip((int(v) for v in idv), meta):
+            self._opened.add(v)
+            (self._sourced.add if int(m["has_source"]) else self._sourced.discard)(v)
 
     def _ids(self, ids, need_opened):
         return check_session_ids(ids, self.capacity, self._opened if need_opened else None)

@@ -415,6 +415,34 @@ hipError_t launch_session_history_save(const SessionPool& P, const SessionRings&
 // it back to the session's Z) and -> the session's UMASK row
 hipError_t launch_session_history_move(const SessionPool& P, const SessionRings& R, const int* ids, const int* save, const int* load,
                                        float* zslot, int zs, int n, hipStream_t s);
+// saved sessions (ian_session_save / ian_session_load): a record's body is every array the pool has, each padded to 16
+// bytes.  One entry per array, built by the runtime from SESS_COLUMNS; passed to the two kernels by value.
+enum SessionRecordRule { SESS_REC_PLAIN = 0, SESS_REC_SOURCE = 1 /* zero / unwritten without a source */, SESS_REC_RING = 2 /* slots of a history ring */ };
+struct SessionRecordCol {
+  unsigned off;             // byte offset in the body, a multiple of 16
+  unsigned unit;            // bytes of one row (of one ring slot), a multiple of 4; a multiple of 16 takes the 16-byte path
+  unsigned slots;           // 1, or depth + 1 for a ring
+  unsigned short member;    // byte offset of the array's pointer in SessionPool / SessionRings
+  unsigned char in_rings;   // which of the two
+  unsigned char rule;       // SessionRecordRule
+};
+constexpr int SESS_REC_MAX_COLS = 13;
+struct SessionRecordCols {
+  int ncols;
+  unsigned body_bytes;      // a multiple of 16
+  SessionRecordCol col[SESS_REC_MAX_COLS];
+};
+struct SessionRecordBases {   // what the launchers hand the kernels: the pointer of each table entry's array
+  char* p[SESS_REC_MAX_COLS];
+};
+// items = device int[n][4]: session id, has_source, the ring's base slot, the history's length.  body = device bytes [n][body_bytes],
+// 16-byte aligned.  pack: the sessions' rows -> body, history entry k (ring slot (base + k) % slots) -> record slot k, zeros for
+// the slots >= length, for SRC without a source and for the padding.  unpack: body -> rows, record slot k -> ring slot k, and what
+// pack zero-fills is not written.
+hipError_t launch_session_pack(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
+                               unsigned char* body, int n, hipStream_t s);
+hipError_t launch_session_unpack(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
+                                 const unsigned char* body, int n, hipStream_t s);
 // full-resolution open, input side: SRC row of ids[i] := photos[i] (u8 [n][3*S*S]; nullptr: the row already holds the photo), its exact
 // box mean -> GIM, IM and x[i] = table[byte], the outputs of launch_session_open_in
 hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,

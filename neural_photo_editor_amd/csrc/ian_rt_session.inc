@@ -8,7 +8,8 @@
 //
 // The pool's arrays (and the history's rings beside it: SessionArrays) are described once, in SESS_COLUMNS: member, bytes per
 // session, owning reservation, whether fresh rows start at zero, and the ian_session_field that reads it.  Allocation, the copy of
-// the surviving rows, rollback, freeing, the byte count of the -2 messages and ian_session_read are loops over that table;
+// the surviving rows, rollback, freeing, the byte count of the -2 messages, ian_session_read and the body of a saved session
+// (ian_session_save / ian_session_load: whole sessions as bytes, ian_session_record.h) are loops over that table;
 // SESS_SCRATCH does the same for the per-handle device buffers.
 // Four reservations own them (sess_free_group frees exactly one):
 //   base   ian_sessions_reserve        GIM IM RECON ERROR Z MODE; reserve(0) frees all four groups
@@ -64,6 +65,8 @@ const SessScratchBuf SESS_SCRATCH[] = {
     {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 11 * sizeof(int32_t), SESS_BASE},
     {offsetof(SessionScratch, d_photo), 0, SESS_BASE},
     {offsetof(SessionScratch, d_shown), (size_t)BATCH_MAX * SESS_IMG, SESS_BASE},
+    {offsetof(SessionScratch, d_rtab), 0, SESS_BASE},
+    {offsetof(SessionScratch, d_stage), 0, SESS_BASE},
     {offsetof(SessionScratch, d_tanh), 256 * sizeof(float), SESS_BASE},   // last of its group: a failed build never leaves it without its upload
     {offsetof(SessionScratch, d_views), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HIRES},
     {offsetof(SessionScratch, d_out), 0, SESS_HIRES},
@@ -90,6 +93,30 @@ size_t sess_row_bytes(const SessionArrays& P, unsigned groups) {
   for (const SessColumn& c : SESS_COLUMNS)
     if (groups >> c.group & 1) sum += c.row_bytes(P);
   return sum;
+}
+// The body of a saved session (ian_session_save / _load, DESIGN.md 4.6): every column the pool has, in table order, each padded to 16
+// bytes.  A column of the history group is a ring of depth + 1 slots, the column that IAN_SESSION_SOURCE reads follows the session's
+// source bit; nothing else about a column matters here.  -> false: a body beyond 2 GB (the kernels count bytes in 32 bits).
+bool sess_record_cols(const SessionArrays& P, SessionRecordCols& T) {
+  static_assert(sizeof(SESS_COLUMNS) / sizeof(SESS_COLUMNS[0]) <= SESS_REC_MAX_COLS, "SessionRecordCols holds every column");
+  memset(&T, 0, sizeof T);
+  size_t off = 0;
+  for (const SessColumn& c : SESS_COLUMNS) {
+    const size_t row = slot_get(&P, c.at) ? c.row_bytes(P) : 0;
+    if (!row) continue;
+    const bool ring = c.group == SESS_HISTORY, in_rings = c.at >= offsetof(SessionArrays, rings);
+    SessionRecordCol& r = T.col[T.ncols++];
+    r.off = (unsigned)off;
+    r.slots = ring ? (unsigned)P.rings.depth + 1 : 1;
+    r.unit = (unsigned)(row / r.slots);
+    r.member = (unsigned short)(c.at - (in_rings ? offsetof(SessionArrays, rings) : offsetof(SessionArrays, pool)));
+    r.in_rings = in_rings;
+    r.rule = ring ? SESS_REC_RING : (c.field == IAN_SESSION_SOURCE ? SESS_REC_SOURCE : SESS_REC_PLAIN);
+    off += session_record_pad(row);
+    if (off > 0x7fffffffu) return false;
+  }
+  T.body_bytes = (unsigned)off;
+  return true;
 }
 // every column of `groups` that N lacks: rows for `capacity` sessions, the first `keep` copied from O, the others zero where the
 // column asks for it; the zeros are there before any stream reads them
@@ -161,6 +188,7 @@ void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
   } else {
     S.arr.pool.zl = 0;
     S.capacity = 0;
+    S.stage_cap = 0;
     S.opened.clear(); S.version.clear(); S.has_src.clear(); S.local_flags.clear(); S.hist.clear();
     S.res_valid = false;
   }
@@ -837,6 +865,145 @@ int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
   return session_rows_leave(h, st, dev);
 }
 
+// ---- saved sessions (DESIGN.md 4.6) ----------------------------------------------------------------------------------------------
+// the layout of this pool's records
+SessionRecordLayout session_record_layout(const decltype(ian_handle::sess)& S, const SessionRecordCols& T) {
+  SessionRecordLayout L;
+  L.num_latents = S.arr.pool.zl;
+  L.scale = S.arr.pool.scale;
+  L.local = S.arr.pool.umask ? 1 : 0;
+  L.depth = S.arr.rings.depth;
+  L.body_bytes = (long long)T.body_bytes;
+  return L;
+}
+ian_session_meta session_record_meta(const SessionRecordLayout& L) {
+  ian_session_meta m;
+  memset(&m, 0, sizeof m);
+  m.magic = IAN_SESSION_RECORD_MAGIC;
+  m.format = IAN_SESSION_RECORD_FORMAT;
+  m.num_latents = L.num_latents; m.scale = L.scale; m.local = L.local; m.depth = L.depth;
+  m.body_bytes = L.body_bytes;
+  return m;
+}
+
+int session_record_info(ian_handle* h, ian_session_meta* layout, int64_t* offsets, int32_t* ncols) {
+  const char* fn = "ian_session_record_info";
+  static_assert(sizeof(ian_session_meta) == 64, "ian_session_meta is 64 bytes");
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
+  SessionRecordCols T;
+  if (!sess_record_cols(S.arr, T)) return fail(h, -7, "%s: a record of this pool is larger than 2 GB", fn);
+  if (layout) *layout = session_record_meta(session_record_layout(S, T));
+  for (int k = 0; offsets && k < T.ncols; ++k) offsets[k] = T.col[k].off;
+  if (ncols) *ncols = T.ncols;
+  return 0;
+}
+
+// what ian_session_save and ian_session_load check beside the ids, before anything is enqueued
+int session_record_check_args(ian_handle* h, const char* fn, const void* meta, const void* body, SessionRecordCols& T) {
+  if (!meta || !body) return fail(h, -1, "null pointer passed to %s", fn);
+  if (is_device_ptr(meta)) return fail(h, -7, "%s: meta must be a host array", fn);
+  if (reinterpret_cast<uintptr_t>(body) & 15) return fail(h, -7, "%s: body %p is not 16-byte aligned", fn, body);
+  if (!sess_record_cols(h->sess.arr, T)) return fail(h, -7, "%s: a record of this pool is larger than 2 GB", fn);
+  return 0;
+}
+// the per-item table (4 words per item: id, has_source, ring base, history length) up, in the one copy the call makes
+int session_record_upload(ian_handle* h, int n, hipStream_t st) {
+  auto& S = h->sess;
+  if (!S.d_rtab) HIPCHK(h, hipMalloc((void**)&S.d_rtab, (size_t)BATCH_MAX * 4 * sizeof(int32_t)));
+  HIPCHK(h, hipMemcpyAsync(S.d_rtab, S.rtab_shadow.data(), (size_t)4 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  return 0;
+}
+// records per pass through the staging buffer of a host body: what opt.session_stage_bytes holds, at least one; the buffer is there
+int session_record_stage(ian_handle* h, int n, size_t body_bytes, int* per_pass) {
+  auto& S = h->sess;
+  const size_t fit = (size_t)h->opt.session_stage_bytes / body_bytes;
+  *per_pass = (int)std::min<size_t>((size_t)n, std::max<size_t>(fit, 1));
+  return grow_dev(h, &S.d_stage, &S.stage_cap, (size_t)*per_pass * body_bytes);
+}
+
+int session_save(ian_handle* h, int n, const int32_t* ids, ian_session_meta* meta, void* body, void* stream) {
+  const char* fn = "ian_session_save";
+  int rc = session_check(h, fn, n, ids, 1, true, false);
+  if (rc) return rc;
+  SessionRecordCols T;
+  if ((rc = session_record_check_args(h, fn, meta, body, T))) return rc;
+  auto& S = h->sess;
+  const int depth = S.arr.rings.depth;
+  const size_t bb = T.body_bytes;
+  const bool dev = is_device_ptr(body);
+  int per_pass = n;
+  if (!dev && (rc = session_record_stage(h, n, bb, &per_pass))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  S.rtab_shadow.resize((size_t)4 * n);
+  for (int i = 0; i < n; ++i) {
+    const SessionHistory H = depth ? S.hist[ids[i]] : SessionHistory{};
+    int32_t* t = S.rtab_shadow.data() + (size_t)4 * i;
+    t[0] = ids[i]; t[1] = S.has_src[ids[i]] ? 1 : 0; t[2] = session_record_ring_slot(H.base, depth, 0); t[3] = H.len;
+  }
+  if ((rc = session_record_upload(h, n, st))) return rc;
+  for (int off = 0; off < n; off += per_pass) {
+    const int nc = std::min(per_pass, n - off);
+    unsigned char* out = (unsigned char*)body + (size_t)off * bb;
+    HIPCHK(h, launch_session_pack(S.arr.pool, S.arr.rings, T, S.d_rtab + (size_t)4 * off, dev ? out : S.d_stage, nc, st));
+    if (!dev) HIPCHK(h, hipMemcpyAsync(out, S.d_stage, (size_t)nc * bb, hipMemcpyDeviceToHost, st));
+  }
+  const ian_session_meta layout = session_record_meta(session_record_layout(S, T));
+  for (int i = 0; i < n; ++i) {
+    const int32_t* t = S.rtab_shadow.data() + (size_t)4 * i;
+    meta[i] = layout;
+    meta[i].has_source = t[1];
+    meta[i].local_flags = S.local_flags[ids[i]];
+    meta[i].hist_len = t[3];
+    meta[i].hist_cur = depth ? S.hist[ids[i]].cur : 0;
+  }
+  return session_rows_leave(h, st, dev);
+}
+
+int session_load(ian_handle* h, int n, const int32_t* ids, const ian_session_meta* meta, const void* body, void* stream) {
+  const char* fn = "ian_session_load";
+  int rc = session_check(h, fn, n, ids, 1, false, false);
+  if (rc) return rc;
+  SessionRecordCols T;
+  if ((rc = session_record_check_args(h, fn, meta, body, T))) return rc;
+  auto& S = h->sess;
+  const SessionRecordLayout L = session_record_layout(S, T);
+  for (int i = 0; i < n; ++i) {
+    const SessionRecordRefusal r = session_record_check(meta[i], L);
+    if (r.field) return fail(h, -7, "%s: item %d: %s = %lld (this pool: %lld): %s", fn, i, r.field, r.got, r.want, r.why);
+  }
+  const size_t bb = T.body_bytes;
+  const bool dev = is_device_ptr(body);
+  int per_pass = n;
+  if (!dev && (rc = session_record_stage(h, n, bb, &per_pass))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  S.rtab_shadow.resize((size_t)4 * n);
+  for (int i = 0; i < n; ++i) {
+    int32_t* t = S.rtab_shadow.data() + (size_t)4 * i;
+    t[0] = ids[i]; t[1] = meta[i].has_source; t[2] = 0; t[3] = meta[i].hist_len;   // the ring restarts at slot 0
+  }
+  if ((rc = session_record_upload(h, n, st))) return rc;
+  for (int off = 0; off < n; off += per_pass) {
+    const int nc = std::min(per_pass, n - off);
+    const unsigned char* in = (const unsigned char*)body + (size_t)off * bb;
+    if (!dev) HIPCHK(h, hipMemcpyAsync(S.d_stage, in, (size_t)nc * bb, hipMemcpyHostToDevice, st));
+    HIPCHK(h, launch_session_unpack(S.arr.pool, S.arr.rings, T, S.d_rtab + (size_t)4 * off, dev ? in : S.d_stage, nc, st));
+  }
+  for (int i = 0; i < n; ++i) {
+    const int id = ids[i];
+    S.opened[id] = 1;
+    ++S.version[id];   // a forward left resident for this id belongs to the latent that was just replaced
+    S.has_src[id] = (char)meta[i].has_source;
+    S.local_flags[id] = (char)meta[i].local_flags;
+    S.hist[id] = SessionHistory{0, meta[i].hist_len, meta[i].hist_cur};
+  }
+  return session_rows_leave(h, st, dev);
+}
+
 }  // namespace
 
 extern "C" {
@@ -890,6 +1057,15 @@ int ian_session_undo(ian_handle* h, int32_t n, const int32_t* ids, const int32_t
 }
 int ian_session_history(ian_handle* h, int32_t id, int32_t out[3]) {
   return h ? session_history(h, id, out) : -1;
+}
+int ian_session_record_info(ian_handle* h, ian_session_meta* layout, int64_t* offsets, int32_t* ncols) {
+  return h ? session_record_info(h, layout, offsets, ncols) : -1;
+}
+int ian_session_save(ian_handle* h, int32_t n, const int32_t* ids, ian_session_meta* meta, void* body, void* stream) {
+  return h ? session_save(h, n, ids, meta, body, stream) : -1;
+}
+int ian_session_load(ian_handle* h, int32_t n, const int32_t* ids, const ian_session_meta* meta, const void* body, void* stream) {
+  return h ? session_load(h, n, ids, meta, body, stream) : -1;
 }
 void ian_session_tanh_table(float* out256) {
   if (out256) session_tanh_table(out256);

@@ -168,6 +168,7 @@ struct Options {
   int dec_out_px = 1;                // ... and, below that batch, 8 lanes per output pixel instead of 16 tile workgroups
   int dec_out_mfma = 1;              // image-producing deconv (IAN_simple dec_out) on the matrix cores for batches >= 4
   int brush_pass = 256;              // ian_grad_batch / ian_brush_step_batch: items per forward / backward / forward pass (A/B)
+  int session_stage_bytes = 64 << 20; // ian_session_save / _load with a host body: bytes of records per gather-then-copy pass (never less than one record)
   int fuse_latent_update = 1;        // ian_brush_step: the latent update rides in the epilogue of the latent's backward GEMV (round 5)
   int edit_graph = 1;                // batch-1 host-pointer calls (the NPE edit loop) replay captured hipGraphs
   int edit_spin = 1;                 // ... and their final wait polls the stream (hipStreamQuery) before it falls back to hipStreamSynchronize
@@ -301,6 +302,8 @@ struct ian_handle {
     double* d_falloff = nullptr;       // local edits: f64[64], the table of ian_sessions_set_local
     int* d_ltab = nullptr;             // local edits: per ian_session_local call [n ids | n flags]
     int* d_htab = nullptr;             // undo history: per ian_session_mark / _undo call [n ids | n save slots | n load slots]
+    int* d_rtab = nullptr;             // saved sessions: per ian_session_save / _load call n x (id, has_source, ring base, history length); by the first such call
+    unsigned char* d_stage = nullptr;  // saved sessions: staging of records for a host `body`, grown on demand (stage_cap) up to opt.session_stage_bytes
   };
   struct SessionState : SessionScratch {
     int capacity = 0;
@@ -331,6 +334,9 @@ struct ian_handle {
     // depth is arr.rings.depth.  The host is the only owner of these counters.
     std::vector<SessionHistory> hist;
     std::vector<int32_t> htab_shadow;    // upload source of d_htab
+    // saved sessions (ian_session_save / ian_session_load)
+    std::vector<int32_t> rtab_shadow;    // upload source of d_rtab
+    size_t stage_cap = 0;
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

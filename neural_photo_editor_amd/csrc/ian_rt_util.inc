@@ -57,6 +57,7 @@ bool apply_option(Options& o, const std::string& k, int value) {
   else if (k == "dec_out_px") o.dec_out_px = value;
   else if (k == "dense_gemv") o.dense_gemv = value;
   else if (k == "brush_pass") o.brush_pass = value < 1 ? 1 : (value > 256 ? 256 : value);
+  else if (k == "session_stage_bytes") o.session_stage_bytes = std::max(1, value);
   else if (k == "b1_conv") {
 #ifndef IAN_ABLATION
     if (value != 0) return false;             // batch-1 streaming deconv (kernels_b1.hip): measured slower, libian_ablation.so only

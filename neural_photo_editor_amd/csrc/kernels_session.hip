@@ -11,7 +11,10 @@
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
 //   session_history_save_kernel / _move_kernel   undo history: a session's Z and UMASK rows to and from its ring of saved states
+//   session_pack_kernel / session_unpack_kernel  saved sessions: every row of a session, its ring included, to and from one record
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
+#include <cstring>
+
 #include "ian_internal.h"
 #include "ian_dact.h"   // m_dact, under the default contraction mode
 
@@ -176,6 +179,140 @@ hipError_t launch_session_history_move(const SessionPool& P, const SessionRings&
   if (n < 1 || n > 65535 || !R.hist_z || !P.z || R.depth < 1 || (R.hist_umask && !P.umask) || !zslot || zs < P.zl) return hipErrorInvalidValue;
   const int vec = (P.zl & 3) == 0 && (zs & 3) == 0 && (reinterpret_cast<uintptr_t>(zslot) & 15) == 0;
   hipLaunchKernelGGL(session_history_move_kernel, dim3(n), dim3(HIST_T), 0, s, P, R, ids, save, load, zslot, zs, vec);
+  return hipGetLastError();
+}
+
+// ---- saved sessions: the pool's rows of n sessions <-> n records, grid (chunks of the record, n) ---------------------
+// A record's body is every array of the pool, each padded to 16 bytes (SessionRecordCols, built by the runtime from SESS_COLUMNS).  A
+// lane owns REC_PIECES pieces of 16 body bytes, REC_T * 16 bytes apart: consecutive lanes, consecutive addresses on the body's side
+// always, and on the pool's side wherever a row (a ring slot) is a multiple of 16 bytes -- the images, ERROR, FIELD, UMASK, SRC, the
+// rings, Z at 100 latents.  The 4-byte arrays (MODE, FIELD_KIND, LOCAL) and a Z row whose size is no multiple of 16 move word by word
+// on the pool's side.  Which array a piece belongs to is found by walking the table (at most 13 entries, uniform loads); a chunk
+// may span several arrays.  The kernels take the table and the arrays' pointers (SessionRecordBases: the launchers read them out of
+// SessionPool / SessionRings through the table's member offsets) by value.  Nothing is computed.
+// Canonical form: history entry k sits in ring slot (base + k) % slots and goes to record slot k; record slots >= the history's
+// length, the SRC row of a session without a source and the padding are zero in the record and are not written back.
+constexpr int REC_T = 256, REC_PIECES = 4, REC_CHUNK = REC_T * 16 * REC_PIECES;
+struct RecSel {
+  char* base;
+  unsigned off, unit, slots, rule;
+};
+__device__ __forceinline__ RecSel rec_select(const SessionRecordCols& T, const SessionRecordBases& B, unsigned o) {
+  RecSel s = {nullptr, 0u, 16u, 0u, 0u};   // slots 0: nothing to move (never selected: the first array starts at 0)
+#pragma unroll
+  for (int k = 0; k < SESS_REC_MAX_COLS; ++k) {
+    if (k >= T.ncols) break;
+    const SessionRecordCol c = T.col[k];
+    if (o >= c.off) {
+      s.base = B.p[k]; s.off = c.off; s.unit = c.unit; s.slots = c.slots; s.rule = c.rule;
+    }
+  }
+  return s;
+}
+// where the `w`-th byte of an array's part of the record lives in the pool; nullptr: zero in the record, not written back
+__device__ __forceinline__ char* rec_addr(const RecSel& s, const int4 it, unsigned w, bool rotate) {
+  if (w >= s.unit * s.slots) return nullptr;                       // padding
+  if (s.rule == SESS_REC_SOURCE && !it.y) return nullptr;          // no source
+  size_t row = (size_t)it.x;
+  if (s.rule == SESS_REC_RING) {
+    const unsigned k = w / s.unit;
+    if (k >= (unsigned)it.w) return nullptr;                       // not an entry of the history
+    row = row * s.slots + (rotate ? ((unsigned)it.z + k) % s.slots : k);
+    w -= k * s.unit;
+  }
+  return s.base + row * s.unit + w;
+}
+
+__global__ __launch_bounds__(REC_T) void session_pack_kernel(SessionRecordCols T, SessionRecordBases B,
+                                                             const int* __restrict__ items, unsigned char* __restrict__ body) {
+  const int i = blockIdx.y;
+  const int4 it = reinterpret_cast<const int4*>(items)[i];
+  unsigned char* rec = body + (size_t)i * T.body_bytes;
+  uint4 v[REC_PIECES];
+#pragma unroll
+  for (int p = 0; p < REC_PIECES; ++p) {
+    const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
+    v[p] = make_uint4(0u, 0u, 0u, 0u);
+    if (o >= T.body_bytes) continue;
+    const RecSel s = rec_select(T, B, o);
+    const unsigned w = o - s.off;
+    if ((s.unit & 15u) == 0) {
+      if (const char* a = rec_addr(s, it, w, true)) v[p] = *reinterpret_cast<const uint4*>(a);
+    } else {
+      unsigned t[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (const char* a = rec_addr(s, it, w + 4u * j, true)) t[j] = *reinterpret_cast<const unsigned*>(a);
+      v[p] = make_uint4(t[0], t[1], t[2], t[3]);
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < REC_PIECES; ++p) {
+    const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
+    if (o < T.body_bytes) *reinterpret_cast<uint4*>(rec + o) = v[p];
+  }
+}
+__global__ __launch_bounds__(REC_T) void session_unpack_kernel(SessionRecordCols T, SessionRecordBases B,
+                                                               const int* __restrict__ items, const unsigned char* __restrict__ body) {
+  const int i = blockIdx.y;
+  const int4 it = reinterpret_cast<const int4*>(items)[i];
+  const unsigned char* rec = body + (size_t)i * T.body_bytes;
+  uint4 v[REC_PIECES];
+#pragma unroll
+  for (int p = 0; p < REC_PIECES; ++p) {
+    const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
+    v[p] = o < T.body_bytes ? *reinterpret_cast<const uint4*>(rec + o) : make_uint4(0u, 0u, 0u, 0u);
+  }
+#pragma unroll
+  for (int p = 0; p < REC_PIECES; ++p) {
+    const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
+    if (o >= T.body_bytes) continue;
+    const RecSel s = rec_select(T, B, o);
+    const unsigned w = o - s.off;
+    if ((s.unit & 15u) == 0) {
+      if (char* a = rec_addr(s, it, w, false)) *reinterpret_cast<uint4*>(a) = v[p];
+    } else {
+      const unsigned t[4] = {v[p].x, v[p].y, v[p].z, v[p].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (char* a = rec_addr(s, it, w + 4u * j, false)) *reinterpret_cast<unsigned*>(a) = t[j];
+    }
+  }
+}
+// What both launchers refuse: a table that does not describe these arrays (every offset and size is checked here, so that no lane
+// can be sent outside a row), a body that is not 16-byte aligned.  -> B: the arrays' pointers, taken out of P and R here: a kernel
+// that picked a member of a by-value struct by a run-time offset would keep the struct in scratch memory.
+static bool session_record_args_ok(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
+                                   const void* body, int n, SessionRecordBases& B) {
+  if (n < 1 || n > 65535 || !items || !body || (reinterpret_cast<uintptr_t>(body) & 15) || (reinterpret_cast<uintptr_t>(items) & 15)) return false;
+  if (T.ncols < 1 || T.ncols > SESS_REC_MAX_COLS || T.body_bytes == 0 || (T.body_bytes & 15u) || T.col[0].off != 0) return false;
+  memset(&B, 0, sizeof B);
+  unsigned long long end = 0;
+  for (int k = 0; k < T.ncols; ++k) {
+    const SessionRecordCol& c = T.col[k];
+    const size_t holder = c.in_rings ? sizeof(SessionRings) : sizeof(SessionPool);
+    if (c.off != end || c.unit == 0 || (c.unit & 3u) || c.slots < 1 || c.member + sizeof(void*) > holder || c.rule > SESS_REC_RING) return false;
+    if (c.rule == SESS_REC_RING && (!c.in_rings || c.slots != (unsigned)R.depth + 1)) return false;
+    if (c.rule != SESS_REC_RING && c.slots != 1) return false;
+    memcpy(&B.p[k], (c.in_rings ? reinterpret_cast<const char*>(&R) : reinterpret_cast<const char*>(&P)) + c.member, sizeof B.p[k]);
+    if (!B.p[k]) return false;
+    end += ((unsigned long long)c.unit * c.slots + 15ull) & ~15ull;
+    if (end > 0x7fffffffull) return false;
+  }
+  return end == T.body_bytes;
+}
+hipError_t launch_session_pack(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
+                               unsigned char* body, int n, hipStream_t s) {
+  SessionRecordBases B;
+  if (!session_record_args_ok(P, R, T, items, body, n, B)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_pack_kernel, dim3((T.body_bytes + REC_CHUNK - 1) / REC_CHUNK, n), dim3(REC_T), 0, s, T, B, items, body);
+  return hipGetLastError();
+}
+hipError_t launch_session_unpack(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
+                                 const unsigned char* body, int n, hipStream_t s) {
+  SessionRecordBases B;
+  if (!session_record_args_ok(P, R, T, items, body, n, B)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_unpack_kernel, dim3((T.body_bytes + REC_CHUNK - 1) / REC_CHUNK, n), dim3(REC_T), 0, s, T, B, items, body);
   return hipGetLastError();
 }
 

@@ -48,6 +48,7 @@ EXPORTS = (
     "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
+    "ian_session_record_info", "ian_session_save", "ian_session_load",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -124,6 +125,9 @@ def load_library():
     lib.ian_session_mark.argtypes = [vp, i32, fp, vp]
     lib.ian_session_undo.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_history.argtypes = [vp, i32, fp]
+    lib.ian_session_record_info.argtypes = [vp, C.POINTER(SessionMeta), fp, fp]
+    lib.ian_session_save.argtypes = [vp, i32, fp, fp, fp, vp]
+    lib.ian_session_load.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -173,6 +177,16 @@ class SessionEvent(C.Structure):
 class SessionView(C.Structure):
     """ian_session_view (include/ian.h): one window of a full-resolution session (ian_session_render / ian_session_brush_view)."""
     _fields_ = [("session", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+class SessionMeta(C.Structure):
+    """ian_session_meta (include/ian.h): the 64-byte meta block of one saved session; npe_ops.SESSION_META_DTYPE is the same bytes."""
+    _fields_ = [("magic", C.c_uint32), ("format", C.c_int32), ("num_latents", C.c_int32), ("scale", C.c_int32), ("local", C.c_int32),
+                ("depth", C.c_int32), ("has_source", C.c_int32), ("local_flags", C.c_int32), ("hist_len", C.c_int32),
+                ("hist_cur", C.c_int32), ("body_bytes", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+SESSION_RECORD_MAX_COLUMNS = 13     # IAN_SESSION_RECORD_MAX_COLUMNS
 
 
 # enum ian_session_field (include/ian.h): name -> (code, dtype, shape; None = (num_latents,); "S" = (3, 64*scale, 64*scale))
@@ -395,6 +409,23 @@ class Handle:
         out = np.zeros(3, np.int32)
         self._check(self.lib.ian_session_history(self._h, int(sid), _ptr(out)))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def session_record_info(self):
+        """ian_session_record_info -> (the pool's layout as a SessionMeta, the byte offsets of its arrays in a body); host only."""
+        layout = SessionMeta()
+        offsets = np.zeros(SESSION_RECORD_MAX_COLUMNS, np.int64)
+        ncols = np.zeros(1, np.int32)
+        self._check(self.lib.ian_session_record_info(self._h, C.byref(layout), _ptr(offsets), _ptr(ncols)))
+        return layout, [int(v) for v in offsets[:int(ncols[0])]]
+
+    def session_save(self, ids, meta, body, stream=None):
+        """ian_session_save; ids = int32 array (n = its length), meta = n 64-byte entries (host), body = n * body_bytes bytes, a numpy
+        array or a device tensor, 16-byte aligned."""
+        self._check(self.lib.ian_session_save(self._h, len(ids), _ptr(ids), _ptr(meta), _ptr(body), C.c_void_p(stream or 0)))
+
+    def session_load(self, ids, meta, body, stream=None):
+        """ian_session_load; the arguments of session_save, read instead of written."""
+        self._check(self.lib.ian_session_load(self._h, len(ids), _ptr(ids), _ptr(meta), _ptr(body), C.c_void_p(stream or 0)))
 
     def session_read(self, sid, what, stream=None, scale=0):
         code, dtype, shape = SESSION_FIELDS[what]

@@ -344,3 +344,135 @@ class SessionHistory:
 
     def clear(self):
         self.base = self.len = self.cur = 0
+
+
+# ---- saved edit sessions (ian_session_save / ian_session_load): the record, byte for byte, in numpy ---------------------
+SESSION_RECORD_MAGIC = 0x534E4149      # "IANS"
+SESSION_RECORD_FORMAT = 1
+# ian_session_meta (include/ian.h): 64 bytes
+SESSION_META_DTYPE = np.dtype([("magic", "<u4"), ("format", "<i4"), ("num_latents", "<i4"), ("scale", "<i4"), ("local", "<i4"),
+                               ("depth", "<i4"), ("has_source", "<i4"), ("local_flags", "<i4"), ("hist_len", "<i4"), ("hist_cur", "<i4"),
+                               ("body_bytes", "<i8"), ("reserved", "<i4", (4,))])
+
+
+def session_record_columns(zl, scale=0, local=False, depth=0):
+    """The arrays of one record's body, in order: [(name, dtype, shape)].  The 64x64 state always; SOURCE (3, S, S), S = 64 * scale,
+    FIELD and FIELD_KIND with a full-resolution reservation; UMASK and LOCAL with the local one; with a history of `depth` the ring
+    of depth + 1 saved Z rows and, when local, of as many UMASK rows."""
+    zl, scale, depth = int(zl), int(scale), int(depth)
+    if zl < 1 or not 0 <= scale <= 16 or not 0 <= depth <= 64:
+        raise ValueError("a layout has zl >= 1, scale 0..16, depth 0..64, got %d, %d, %d" % (zl, scale, depth))
+    cols = [("GIM", np.uint8, (3, 64, 64)), ("IM", np.uint8, (3, 64, 64)), ("RECON", np.uint8, (3, 64, 64)),
+            ("ERROR", np.float32, (3, 64, 64)), ("Z", np.float32, (zl,)), ("MODE", np.int32, (1,))]
+    if scale:
+        cols += [("SOURCE", np.uint8, (3, 64 * scale, 64 * scale)), ("FIELD", np.float32, (3, 64, 64)), ("FIELD_KIND", np.int32, (1,))]
+    if local:
+        cols += [("UMASK", np.float64, (64, 64)), ("LOCAL", np.int32, (1,))]
+    if depth:
+        cols.append(("HIST_Z", np.float32, (depth + 1, zl)))
+        if local:
+            cols.append(("HIST_UMASK", np.float64, (depth + 1, 64, 64)))
+    return cols
+
+
+def session_record_layout(zl, scale=0, local=False, depth=0):
+    """-> ({name: byte offset in the body}, in body order, and body_bytes): every array starts at a multiple of 16 bytes."""
+    offsets, at = {}, 0
+    for name, dtype, shape in session_record_columns(zl, scale, local, depth):
+        offsets[name] = at
+        at += -(-int(np.prod(shape)) * np.dtype(dtype).itemsize // 16) * 16
+    return offsets, at
+
+
+def session_meta(zl, scale=0, local=False, depth=0, has_source=0, local_flags=0, hist_len=0, hist_cur=0):
+    """One ian_session_meta as a 0-d structured array."""
+    m = np.zeros((), SESSION_META_DTYPE)
+    m["magic"], m["format"] = SESSION_RECORD_MAGIC, SESSION_RECORD_FORMAT
+    m["num_latents"], m["scale"], m["local"], m["depth"] = int(zl), int(scale), int(bool(local)), int(depth)
+    m["has_source"], m["local_flags"], m["hist_len"], m["hist_cur"] = int(has_source), int(local_flags), int(hist_len), int(hist_cur)
+    m["body_bytes"] = session_record_layout(zl, scale, local, depth)[1]
+    return m
+
+
+def check_session_meta(meta, zl, scale=0, local=False, depth=0):
+    """A record's meta against the layout it is to be loaded into -> None, or the name of the first field that is refused
+    (csrc/ian_session_record.h, session_record_check, in its order)."""
+    g = lambda k: int(meta[k])
+    local, depth = int(bool(local)), int(depth)
+    if g("magic") != SESSION_RECORD_MAGIC:
+        return "magic"
+    if g("format") != SESSION_RECORD_FORMAT:
+        return "format"
+    want = {"num_latents": int(zl), "scale": int(scale), "local": local, "depth": depth,
+            "body_bytes": session_record_layout(zl, scale, local, depth)[1]}
+    for k in ("num_latents", "scale", "local", "depth", "body_bytes"):
+        if g(k) != want[k]:
+            return k
+    if not 0 <= g("local_flags") <= 3 or (g("local_flags") and not local):
+        return "local_flags"
+    if g("has_source") not in (0, 1) or (g("has_source") and not scale):
+        return "has_source"
+    ln, cur = g("hist_len"), g("hist_cur")
+    if ln < 0:
+        return "hist_len"
+    if not 0 <= cur <= ln:
+        return "hist_cur"
+    if (depth == 0 and ln) or (cur == ln and ln > depth) or ln > depth + 1:
+        return "hist_len"
+    if any(int(v) for v in np.asarray(meta["reserved"]).reshape(-1)):
+        return "reserved"
+    return None
+
+
+def session_record_pack(fields, history_entries, zl, scale=0, local=False, depth=0, hist_cur=None):
+    """One session -> (meta, body uint8 (body_bytes,)), the canonical record.  fields: what EditSessions.read returns (a session without
+    a full-resolution source has no "SOURCE": those bytes are zero and has_source is 0); history_entries: the history's entries, oldest
+    first, each (Z, UMASK) or Z alone in a layout without the local reservation -- entry k goes to slot k, the other slots are zero;
+    hist_cur: the cursor, len(history_entries) (the tip) when not given."""
+    offsets, body_bytes = session_record_layout(zl, scale, local, depth)
+    body = np.zeros(body_bytes, np.uint8)
+    entries = [e if isinstance(e, (tuple, list)) else (e, None) for e in history_entries]
+    if len(entries) > (depth + 1 if depth else 0):
+        raise ValueError("%d history entries for depth %d" % (len(entries), depth))
+    for name, dtype, shape in session_record_columns(zl, scale, local, depth):
+        if name == "HIST_Z":
+            a = np.zeros(shape, dtype)
+            for k, e in enumerate(entries):
+                a[k] = np.asarray(e[0], dtype).reshape(shape[1:])
+        elif name == "HIST_UMASK":
+            a = np.zeros(shape, dtype)
+            for k, e in enumerate(entries):
+                a[k] = np.asarray(e[1], dtype).reshape(shape[1:])
+        elif name == "SOURCE" and fields.get("SOURCE") is None:
+            continue
+        else:
+            a = np.asarray(fields[name], dtype).reshape(shape)
+        raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        body[offsets[name]:offsets[name] + raw.size] = raw
+    meta = session_meta(zl, scale, local, depth, has_source=int(fields.get("SOURCE") is not None), local_flags=int(fields.get("LOCAL", 0)),
+                        hist_len=len(entries), hist_cur=len(entries) if hist_cur is None else int(hist_cur))
+    return meta, body
+
+
+def session_record_unpack(meta, body):
+    """The inverse of session_record_pack -> (fields, history_entries): scalars as ints, "SOURCE" only with has_source, entries as
+    (Z, UMASK) or Z alone."""
+    zl, scale, local, depth = (int(meta[k]) for k in ("num_latents", "scale", "local", "depth"))
+    offsets, body_bytes = session_record_layout(zl, scale, local, depth)
+    body = np.ascontiguousarray(body, np.uint8).reshape(-1)
+    if body.size != body_bytes or int(meta["body_bytes"]) != body_bytes:
+        raise ValueError("the body holds %d bytes, the meta says %d, the layout has %d" % (body.size, int(meta["body_bytes"]), body_bytes))
+    fields, ring = {}, {}
+    for name, dtype, shape in session_record_columns(zl, scale, local, depth):
+        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        a = body[offsets[name]:offsets[name] + nbytes].copy().view(dtype).reshape(shape)
+        if name.startswith("HIST_"):
+            ring[name] = a
+        elif name == "SOURCE" and not int(meta["has_source"]):
+            continue
+        else:
+            fields[name] = int(a[0]) if shape == (1,) else a
+    entries = []
+    for k in range(int(meta["hist_len"])):
+        entries.append((ring["HIST_Z"][k], ring["HIST_UMASK"][k]) if "HIST_UMASK" in ring else ring["HIST_Z"][k])
+    return fields, entries
