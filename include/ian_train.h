@@ -193,6 +193,15 @@ int ian_k_concat2(const float* a, int32_t ca, int32_t sa, const float* b, int32_
 /* gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c])   (identity edges: concat / residual backward, sigmoid backward) */
 int ian_k_grad_pass(const float* gs, int32_t ss, int32_t coff, float* gd, const float* y, int32_t ds, int64_t npix,
                     int32_t C, int32_t act, int32_t accumulate, void* stream);
+/* the latent brush's loss seeds (API.py:59,64), for unit tests: items = n device rows of ian_brush_item (include/ian.h), or NULL:
+   one item, the rectangle and mode given here.  rgb [n,3,H,W] or, with items, colour [n][3].  g [n,3,H,W] = d loss / d xhat */
+int ian_k_brush_seed(const int32_t* items, int32_t n, int32_t c1, int32_t r1, int32_t c2, int32_t r2, int32_t mode, const float* rgb,
+                     const float* colour, const float* xhat, float* g, int32_t H, int32_t W, void* stream);
+/* ... fused with out_act'(xhat) * oscale and the backward-data of the 5x5 s2 transposed conv that produced xhat [n,Cout,2H,2W]:
+   dx, yfwd NHWC [n,H,W,Cin], w [25][4][Cin]; needs items */
+int ian_k_brush_seed_dec_out(const int32_t* items, int32_t n, const float* rgb, const float* colour, const float* xhat, int32_t out_act,
+                             const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale, int32_t H, int32_t W,
+                             int32_t Cin, int32_t Cout, int32_t act, void* stream);
 /* mode 0: pixel_loss 2|a-b+1e-8| (+ squared error), mode 1: squared error; da (+)= w * d/da; out[2] = scale * sums */
 int ian_k_pair_loss(const float* a, const float* b, float* da, int64_t rows, int32_t C, int32_t stride, int32_t mode, float w,
                     int32_t accumulate, float* workspace, int32_t nblocks, float scale, float* out, void* stream);

@@ -1,6 +1,6 @@
-// ian_dact.h -- the activation derivative the backward kernels share (kernels_misc.hip, kernels_session.hip).  One definition, so
-// that the loss seeds of ian_session_brush stay bitwise those of ian_brush_step_batch.  Include it BEFORE anything that changes the
-// floating-point contraction mode: 1 - y*y is one fma under the default mode in every file.
+// ian_dact.h -- the activation derivative the backward kernels share: grad_pass and beta_bwd (kernels_misc.hip), the latent brush's
+// seed and dec_out backward (kernels_brush.hip).  Include it BEFORE anything that changes the floating-point contraction mode:
+// 1 - y*y is one fma under the default mode in every file.
 #pragma once
 
 namespace ian {

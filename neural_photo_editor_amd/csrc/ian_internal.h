@@ -223,24 +223,24 @@ hipError_t launch_concat2(const float* a, int ca, int sa, const float* b, int cb
 // layout / copy helpers
 hipError_t launch_rows_copy(const float* src, int src_stride, float* dst, int dst_stride, int n, int c, hipStream_t s);
 hipError_t launch_nhwc_to_nchw(const float* src, int stride, float* dst, int n, int hw, int c, hipStream_t s);
-// loss seeds for the latent-brush gradients (API.py:59,64): writes d loss / d x_hat (NCHW [1,3,H,W], zero outside patch)
-hipError_t launch_patch_seed(const float* xhat, const float* rgb, float* g, int H, int W, int c1, int r1, int c2,
-                             int r2, int mode, hipStream_t s);
-hipError_t launch_patch_seed_dev(const float* xhat, const float* rgb, float* g, int H, int W, const int* patch, int mode,
-                                 hipStream_t s);
-// the same for n items, rectangle and loss kind per item from the device ian_brush_item table (7 words per item)
-hipError_t launch_patch_seed_batch(const float* xhat, const float* rgb, float* g, int H, int W, const int* items, int n, hipStream_t s);
+// Where the loss seeds of a latent-brush launch (API.py:59,64; kernels_brush.hip) come from.  Passed to the kernels by value.
+struct BrushSeedSrc {
+  const int* table = nullptr;     // device-readable ian_brush_item rows (7 words: c1, r1, c2, r2, loss kind, coef, gscale), one per
+                                  // item; one event = one row.  nullptr: the rectangle and loss kind below
+  const float* rgb = nullptr;     // the target colour images [n,3,H,W] of the items with loss kind 1 ...
+  const float* colour = nullptr;  // ... or, with a table, their constant target colours [n][3]
+  int c1 = 0, r1 = 0, c2 = 0, r2 = 0, mode = 0;   // without a table (the eager single call, n = 1)
+};
+// d loss / d x_hat of n items: g NCHW [n,3,H,W], zero outside each item's rectangle
+hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, float* g, int H, int W, hipStream_t s);
+// the same seed + the output activation's derivative + the backward-data of the dec_out-like layer below, in one launch (needs a
+// table): xhat NCHW [n,Cout,2H,2W], dx / yfwd NHWC [n,H,W,Cin]
+hipError_t launch_brush_seed_dec_out(const BrushSeedSrc& src, int n, const float* xhat, int out_act, const float* oscale, const float* w,
+                                     float* dx, const float* yfwd, const float* scale, int H, int W, int Cin, int Cout, int act,
+                                     hipStream_t s);
 // backward of dec_out-like layer: g NCHW [n,Cout,2H,2W] (already multiplied by act') -> dx NHWC [n,H,W,Cin]
 hipError_t launch_deconv_out_bwd(const float* g, const float* w, float* dx, const float* yfwd, const float* scale,
                                  int n, int H, int W, int Cin, int Cout, int act, hipStream_t s);
-// batch-1 latent brush: seed (rectangle in device memory) + output activation derivative + the same backward-data, one launch
-hipError_t launch_deconv_out_bwd_seed(const float* xhat, const float* rgb, const int* patch, int mode, int out_act,
-                                      const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale, int H,
-                                      int W, int Cin, int Cout, int act, hipStream_t s);
-// ... and for n items (grid y = item; xhat, rgb NCHW [n,Cout,2H,2W], dx / yfwd NHWC [n,H,W,Cin])
-hipError_t launch_deconv_out_bwd_seed_batch(const float* xhat, const float* rgb, const int* items, int n, int out_act, const float* oscale,
-                                            const float* w, float* dx, const float* yfwd, const float* scale, int H, int W, int Cin,
-                                            int Cout, int act, hipStream_t s);
 // elementwise: g = g * act'(y) * scale  (NCHW small tensors, c channels of hw pixels)
 hipError_t launch_dact_nchw(float* g, const float* y, const float* scale, int n, int c, int hw, int act,
                             hipStream_t s);
@@ -450,13 +450,6 @@ hipError_t launch_session_hires_open(const unsigned char* photos, const SessionP
 // npe_ops.hires_render of n windows: views = device int[n][3] (session, x, y), every window vw x vh with x and vw multiples of 4.
 // out u8 [n][3][vh][vw]; out == nullptr: the whole picture (vw = vh = S, x = y = 0) written over the session's own SRC row
 hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s);
-// the batched loss seeds with a constant brush colour per item: colour[3*i + co] where launch_patch_seed_batch /
-// launch_deconv_out_bwd_seed_batch read rgb[i][co][y][x]
-hipError_t launch_patch_seed_colour_batch(const float* xhat, const float* colour, float* g, int H, int W, const int* items, int n,
-                                          hipStream_t s);
-hipError_t launch_deconv_out_bwd_seed_colour_batch(const float* xhat, const float* colour, const int* items, int n, int out_act,
-                                                   const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale,
-                                                   int H, int W, int Cin, int Cout, int act, hipStream_t s);
 
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,

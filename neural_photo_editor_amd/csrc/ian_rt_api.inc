@@ -360,27 +360,28 @@ int ian_brush_step(ian_handle* h, int32_t c1, int32_t r1, int32_t c2, int32_t r2
   const float* d_rgb = nullptr;
   if (mode == 1 && (rc = upload_rgb_if_changed(h, rgb, st, &d_rgb))) return rc;
   if ((rc = ensure_slot(h, h->desc.z_slot, 1, true))) return rc;
-  int* patch = reinterpret_cast<int*>(h->pin + PIN_IMG + 3 * 64 * 64);
-  patch[0] = c1; patch[1] = r1; patch[2] = c2; patch[3] = r2;
-  memcpy(patch + 4, &coef, sizeof(float));
-  memcpy(patch + 5, &gscale, sizeof(float));
+  ian_brush_item* item = pin_brush_item(h);
+  item->c1 = c1; item->r1 = r1; item->c2 = c2; item->r2 = r2; item->mode = mode;
+  item->coef = coef; item->gscale = gscale;
   h->dec_cache_valid = false;
   const int wx = x ? 1 : 0;
   ian_handle::EditGraph& G = h->g_step[mode][wx];
   h->pin_img_valid = false;
   rc = run_or_replay(h, G, [&]() -> int {
     int r;
+    BrushBackward rq;
+    rq.seed.rgb = d_rgb;
     if (zero_copy(h)) {
       // zero-copy form (round 4): the kernels read the brush rectangle / (coef, gscale) from the pinned block and write the new
       // latent, the gradient and the image into it; the graph holds NO copy node (each was a 4.6 us copy kernel + a boundary)
-      const int* dpatch = reinterpret_cast<const int*>(h->pin_dev + PIN_IMG + 3 * 64 * 64);
-      h->upd.cg = reinterpret_cast<const float*>(dpatch + 4); h->upd.z_mirror = h->pin_dev + PIN_Z; h->upd.g_mirror = h->pin_dev + PIN_DZ;
-      h->upd.done = false;
-      r = run_decoder_backward(h, mode, 0, 0, out.w, out.h, d_rgb, st, dpatch);
-      h->upd.cg = nullptr;
-      if (r) return r;
-      if (!h->upd.done)   // the latent's backward did not take the GEMV form: the update as its own launch
-        HIPCHK(h, launch_latent_update(zs.d, zs.g, reinterpret_cast<const float*>(dpatch + 4), zl, h->pin_dev + PIN_Z, h->pin_dev + PIN_DZ, st));
+      rq.seed.table = reinterpret_cast<const int*>(h->pin_dev + PIN_BRUSH);
+      rq.update = BrushBackward::SINGLE;
+      rq.cg = h->pin_dev + PIN_BRUSH + BRUSH_CG;
+      rq.z_mirror = h->pin_dev + PIN_Z;
+      rq.g_mirror = h->pin_dev + PIN_DZ;
+      if ((r = run_decoder_backward(h, rq, st))) return r;
+      if (!rq.updated)   // the latent's backward did not take the GEMV form: the update as its own launch
+        HIPCHK(h, launch_latent_update(zs.d, zs.g, rq.cg, zl, rq.z_mirror, rq.g_mirror, st));
       h->out_mirror = wx ? h->pin_dev + PIN_IMG : nullptr;
       r = run_segment(h, IAN_SEG_DEC, 1, st);
       h->out_mirror = nullptr;
@@ -389,10 +390,11 @@ int ian_brush_step(ian_handle* h, int32_t c1, int32_t r1, int32_t c2, int32_t r2
       if (wx && !G.mirrors) HIPCHK(h, hipMemcpyAsync(h->pin + PIN_IMG, out.d, out.per_image() * sizeof(float), hipMemcpyDeviceToHost, st));
       return 0;
     }
-    HIPCHK(h, hipMemcpyAsync(h->d_patch, patch, 6 * sizeof(int), hipMemcpyHostToDevice, st));
-    if ((r = run_decoder_backward(h, mode, 0, 0, out.w, out.h, d_rgb, st, h->d_patch))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->d_patch, item, sizeof(ian_brush_item), hipMemcpyHostToDevice, st));
+    rq.seed.table = h->d_patch;
+    if ((r = run_decoder_backward(h, rq, st))) return r;
     HIPCHK(h, hipMemcpyAsync(h->pin + PIN_DZ, zs.g, zs.c * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, launch_latent_update(zs.d, zs.g, reinterpret_cast<const float*>(h->d_patch + 4), zl, nullptr, nullptr, st));
+    HIPCHK(h, launch_latent_update(zs.d, zs.g, reinterpret_cast<const float*>(h->d_patch + BRUSH_CG), zl, nullptr, nullptr, st));
     HIPCHK(h, hipMemcpyAsync(h->pin + PIN_Z, zs.d, zl * sizeof(float), hipMemcpyDeviceToHost, st));
     if ((r = run_segment(h, IAN_SEG_DEC, 1, st))) return r;
     if (wx) HIPCHK(h, hipMemcpyAsync(h->pin + PIN_IMG, out.d, out.per_image() * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -501,7 +503,9 @@ int ian_autotune(ian_handle* h, int32_t n, int32_t what, void* stream) {
         continue;
       }
       cache_dirty = true;
-      rc = tune_layer(h, op.bwd, 1, st, [&]() { return run_decoder_backward(h, 0, out.w / 2 - 2, out.h / 2 - 2, out.w / 2 + 2, out.h / 2 + 2, nullptr, st); }, &best, &ms);
+      BrushBackward rq;   // a 4x4 lighten brush in the middle of the image, as the eager ian_grad sends it
+      rq.seed.c1 = out.w / 2 - 2; rq.seed.r1 = out.h / 2 - 2; rq.seed.c2 = out.w / 2 + 2; rq.seed.r2 = out.h / 2 + 2;
+      rc = tune_layer(h, op.bwd, 1, st, [&]() { return run_decoder_backward(h, rq, st); }, &best, &ms);
       if (!rc) cache[tune_key(1, dir_bwd, op.name)] = best;
       if (!rc && verbose)
         fprintf(stderr, "[ian_autotune] n=1 bwd %-14s -> tile %s, max K-steps/item %d, schedule %d, combine %d : chain %.1f us\n", op.name.c_str(),

@@ -16,16 +16,25 @@ struct ProducerEpi {
   int scale_period = 0;
 };
 
-// Several editors (ian_grad_batch / ian_brush_step_batch): d_items = the device copy of n ian_brush_item records (rectangle, loss
-// kind, coef, gscale per item); mode / c1..r2 / d_patch are unused then, d_rgb is [n,3,H,W].  update: the latent's backward also
-// applies each item's brush update to the z slot (*updated = it did).  Without d_items: today's batch-1 launches, unchanged.
-// d_colour (batched only; ian_session_brush): [n][3] constant brush colours that stand in for d_rgb in the seed launches.
-int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2, const float* d_rgb, hipStream_t st,
-                         const int* d_patch = nullptr, int n = 1, const int* d_items = nullptr, bool update = false,
-                         bool* updated = nullptr, const float* d_colour = nullptr) {
-  const bool batched = d_items != nullptr;
-  if (!batched) n = 1;
-  if (updated) *updated = false;
+// One backward sweep, as its caller asks for it: fill the members by name.
+struct BrushBackward {
+  BrushSeedSrc seed;       // the items' rectangles, loss kinds and target colours
+  int n = 1;               // items = images resident in the decoder's slots
+  bool batch = false;      // the several-editors calls (ian_grad_batch / ian_brush_step_batch / ian_session_brush; n = 1 included): the
+                           // latent's backward is the batched GEMV, no batch-1 kernel runs
+  // the brush update Z += coef * (dZ * gscale) wanted from the latent's backward GEMV (one launch less per event):
+  enum Update { NONE, SINGLE, PER_ITEM } update = NONE;   // PER_ITEM: (coef, gscale) of every row of seed.table
+  const float* cg = nullptr;   // SINGLE: (coef, gscale), device-readable
+  float* z_mirror = nullptr;   // SINGLE: the new latent and the gradient also go there (the pinned host block), or nullptr
+  float* g_mirror = nullptr;
+  bool updated = false;    // out: the GEMV applied the update; otherwise the caller launches it on its own
+};
+
+int run_decoder_backward(ian_handle* h, BrushBackward& rq, hipStream_t st) {
+  const BrushSeedSrc& seed = rq.seed;
+  const int n = rq.n;
+  rq.updated = false;
+  if (n < 1 || (!rq.batch && n != 1)) return fail(h, -7, "imgrad: %d items outside the batched calls", n);
   std::vector<OpPlan*> dec;
   for (auto& op : h->ops)
     if (op.d.segment == IAN_SEG_DEC) dec.push_back(&op);
@@ -37,25 +46,22 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
   if (last.d.dst != h->desc.out_slot) return fail(h, -9, "imgrad: the last decoder op does not produce l_out");
   Slot& out = h->slots[last.d.dst];
   const int H = out.h, W = out.w;
-  if (!batched && (c1 < 0 || r1 < 0 || c2 > W || r2 > H)) return fail(h, -7, "patch (%d,%d,%d,%d) outside the %dx%d image", c1, r1, c2, r2, W, H);
+  if (!seed.table && (seed.c1 < 0 || seed.r1 < 0 || seed.c2 > W || seed.r2 > H))   // a table's rows were checked by the caller that filled it
+    return fail(h, -7, "patch (%d,%d,%d,%d) outside the %dx%d image", seed.c1, seed.r1, seed.c2, seed.r2, W, H);
   if (!h->d_gseed) {
     HIPCHK(h, hipMalloc((void**)&h->d_gseed, (size_t)3 * H * W * sizeof(float)));
     h->gseed_cap = (size_t)3 * H * W;
     ++h->alloc_epoch;
   }
-  const bool fused_seed = (d_patch || batched) && last.d.kind == IAN_OP_DECONV5S2 && last.edge;
-  if (batched && !fused_seed && (size_t)n * 3 * H * W > h->gseed_cap) {   // the batch-1 graphs captured the old seed buffer: the epoch moves
+  // a table + an image-producing deconv (IAN_simple): seed, tanh' and the first backward-data in one launch, inside the sweep below
+  const bool fused_seed = seed.table && last.d.kind == IAN_OP_DECONV5S2 && last.edge;
+  if (!fused_seed && (size_t)n * 3 * H * W > h->gseed_cap) {   // the batch-1 graphs captured the old seed buffer: the epoch moves
     HIPCHK(h, hipFree(h->d_gseed));
     h->gseed_cap = (size_t)n * 3 * H * W;
     HIPCHK(h, hipMalloc((void**)&h->d_gseed, h->gseed_cap * sizeof(float)));
     ++h->alloc_epoch;
   }
-  // interactive loop + image-producing deconv (IAN_simple): seed, tanh' and the first backward-data in one launch (fused_seed above)
-  if (fused_seed) {
-  } else if (batched && d_colour) HIPCHK(h, launch_patch_seed_colour_batch(out.d, d_colour, h->d_gseed, H, W, d_items, n, st));
-  else if (batched) HIPCHK(h, launch_patch_seed_batch(out.d, d_rgb, h->d_gseed, H, W, d_items, n, st));
-  else if (d_patch) HIPCHK(h, launch_patch_seed_dev(out.d, d_rgb, h->d_gseed, H, W, d_patch, mode, st));
-  else HIPCHK(h, launch_patch_seed(out.d, d_rgb, h->d_gseed, H, W, c1, r1, c2, r2, mode, st));  // dL/dX_hat, NCHW
+  if (!fused_seed) HIPCHK(h, launch_brush_seed(seed, n, out.d, h->d_gseed, H, W, st));  // dL/dX_hat, NCHW
 
   std::vector<char> touched(nslots, 0);
   auto epi_of = [&](int slot) {  // what turns a value-gradient of `slot` into its producer's pre-epilogue gradient
@@ -106,15 +112,9 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
       if ((rc = ensure_slot(h, op.d.src, n, true))) return rc;
       ProducerEpi e = epi_of(op.d.src);
       if (e.scale_period) return fail(h, -9, "imgrad: per-feature batch-norm directly under the image deconv");
-      if (fused_seed && batched && d_colour) {
-        HIPCHK(h, launch_deconv_out_bwd_seed_colour_batch(out.d, d_colour, d_items, n, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd,
-                                                          e.scale, op.d.in_h, op.d.in_w, in.cs, op.d.cout, e.act, st));
-      } else if (fused_seed && batched) {
-        HIPCHK(h, launch_deconv_out_bwd_seed_batch(out.d, d_rgb, d_items, n, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd, e.scale,
-                                                   op.d.in_h, op.d.in_w, in.cs, op.d.cout, e.act, st));
-      } else if (fused_seed) {
-        HIPCHK(h, launch_deconv_out_bwd_seed(out.d, d_rgb, d_patch, mode, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd, e.scale,
-                                             op.d.in_h, op.d.in_w, in.cs, op.d.cout, e.act, st));
+      if (fused_seed) {
+        HIPCHK(h, launch_brush_seed_dec_out(seed, n, out.d, op.d.act, op.d_scale, op.d_edge_w, in.g, e.yfwd, e.scale, op.d.in_h, op.d.in_w,
+                                            in.cs, op.d.cout, e.act, st));
       } else {
         HIPCHK(h, launch_dact_nchw(h->d_gseed, out.d, op.d_scale, n, out.c, H * W, op.d.act, st));
         HIPCHK(h, launch_deconv_out_bwd(h->d_gseed, op.d_edge_w, in.g, e.yfwd, e.scale, n, op.d.in_h, op.d.in_w, in.cs,
@@ -140,22 +140,23 @@ int run_decoder_backward(ian_handle* h, int mode, int c1, int r1, int c2, int r2
         const int ystride = (kind == IAN_OP_DENSE) ? (int)in.per_image() : in.cs;
         const bool gemv = kind == IAN_OP_DENSE && h->opt.dense_gemv && !pe.scale && !pe.yfwd && pe.act == IAN_ACT_NONE && op.d.flat_c <= 0 &&
                           (op.bwd.Cin & 3) == 0 && op.bwd.Cout <= ystride;
-        if (gemv && batched && (size_t)op.bwd.Cin <= o.per_image() && (o.per_image() & 3) == 0) {
+        const bool to_latent = op.d.src == h->desc.z_slot && !e.res;   // this launch's output is the latent's whole gradient
+        if (gemv && rq.batch && (size_t)op.bwd.Cin <= o.per_image() && (o.per_image() & 3) == 0) {
           // several editors: each weight row streamed once per block of items; the brush update rides along (ian_brush_step_batch)
-          const bool upd = update && op.d.src == h->desc.z_slot && !e.res;
+          const bool upd = rq.update == BrushBackward::PER_ITEM && to_latent;
           HIPCHK(h, launch_dense_bwd_gemv_batch(o.g, (int)o.per_image(), op.bwd.d_w, op.bwd.Cout, op.bwd.Cin, n, e.res, in.g, ystride,
-                                                upd ? in.d : nullptr, d_items, st));
-          if (upd && updated) *updated = true;
-        } else if (gemv && !batched) {
+                                                upd ? in.d : nullptr, seed.table, st));
+          if (upd) rq.updated = true;
+        } else if (gemv && !rq.batch) {
           // the latent's own layer: slab [in][out], row j contiguous in the (permuted) output index = o.g's order
-          // ian_brush_step: the same launch applies the latent update (h->upd set by the caller; the latent's row = this output)
-          const bool upd = h->upd.cg && op.d.src == h->desc.z_slot && !e.res && h->opt.fuse_latent_update;
-          HIPCHK(h, launch_dense_bwd_gemv(o.g, op.bwd.d_w, op.bwd.Cout, op.bwd.Cin, e.res, in.g, upd ? in.d : nullptr, h->upd.cg,
-                                          h->upd.z_mirror, h->upd.g_mirror, st));
-          h->upd.done = upd;
+          // ian_brush_step: the same launch applies the latent update (the latent's row = this output)
+          const bool upd = rq.update == BrushBackward::SINGLE && to_latent && h->opt.fuse_latent_update;
+          HIPCHK(h, launch_dense_bwd_gemv(o.g, op.bwd.d_w, op.bwd.Cout, op.bwd.Cin, e.res, in.g, upd ? in.d : nullptr, rq.cg, rq.z_mirror,
+                                          rq.g_mirror, st));
+          if (upd) rq.updated = true;
         } else {
           B1Params bp;
-          if (!batched && kind == IAN_OP_DECONV5S2 && b1_fill(h, op, 1, o, in, bp)) {
+          if (!rq.batch && kind == IAN_OP_DECONV5S2 && b1_fill(h, op, 1, o, in, bp)) {
             bp.x = o.g; bp.y = in.g; bp.scale = e.scale; bp.yfwd = e.yfwd; bp.res = e.res; bp.act = e.act; bp.bwd = 1;
             bp.scale_period = e.scale_period;
 #ifdef IAN_ABLATION

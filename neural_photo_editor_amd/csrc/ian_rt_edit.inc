@@ -5,7 +5,7 @@ namespace {
 // ----- stream hand-over between calls ------------------------------------------------------------------------
 // The handle's buffers are shared by every call; a call that returns without synchronising (device output pointers)
 // leaves work pending on its stream.  When the next call runs on ANOTHER stream, wait for that work first.
-constexpr int PIN_WARM_FLAG = 256 + 3 * 64 * 64 + 7;   // int slot of the pinned block the keep-warm kernel polls (behind the 6 brush words)
+constexpr int PIN_WARM_FLAG = 256 + 3 * 64 * 64 + 7;   // int slot of the pinned block the keep-warm kernel polls (behind the 7 brush words)
 void warm_release(ian_handle* h) {
   if (!h->warm_armed) return;
   reinterpret_cast<volatile int*>(h->pin)[PIN_WARM_FLAG] = 1;   // mapped + coherent: the spinning wave sees it and exits
@@ -21,7 +21,12 @@ void enter_stream(ian_handle* h, hipStream_t st) {
 }
 
 // ----- captured graphs for the interactive loop ----------------------------------------------------------------
-constexpr int PIN_Z = 0, PIN_DZ = 128, PIN_IMG = 256, PIN_FLOATS = 256 + 3 * 64 * 64 + 8;
+constexpr int PIN_Z = 0, PIN_DZ = 128, PIN_IMG = 256, PIN_BRUSH = 256 + 3 * 64 * 64, PIN_FLOATS = PIN_BRUSH + 8;
+// The single event's brush words, in the pinned block and in h->d_patch, are one row of the batched calls' table: the seed kernels
+// read the rectangle and loss kind from it, the latent update (coef, gscale) at words 5 and 6.
+static_assert(sizeof(ian_brush_item) == 7 * sizeof(int32_t) && PIN_WARM_FLAG == PIN_BRUSH + 7, "brush words: one ian_brush_item, then the keep-warm flag");
+ian_brush_item* pin_brush_item(ian_handle* h) { return reinterpret_cast<ian_brush_item*>(h->pin + PIN_BRUSH); }
+constexpr int BRUSH_CG = 5;   // word of coef in an ian_brush_item row; gscale follows
 
 bool edit_graph_eligible(const ian_handle* h, void* stream, std::initializer_list<const void*> host_ptrs) {
   if (!h->opt.edit_graph || h->prof || stream != nullptr || h->graph_failed || h->desc.num_latents > 128) return false;
@@ -224,13 +229,17 @@ int grad_common(ian_handle* h, int mode, int c1, int r1, int c2, int r2, const f
     const float* d_rgb = nullptr;
     if (mode == 1 && (rc = upload_rgb_if_changed(h, rgb, st, &d_rgb))) return rc;
     if ((rc = ensure_slot(h, h->desc.z_slot, 1, true))) return rc;
-    int* patch = reinterpret_cast<int*>(h->pin + PIN_IMG + 3 * 64 * 64);
-    patch[0] = c1; patch[1] = r1; patch[2] = c2; patch[3] = r2;
+    ian_brush_item* item = pin_brush_item(h);
+    item->c1 = c1; item->r1 = r1; item->c2 = c2; item->r2 = r2; item->mode = mode;
     rc = run_or_replay(h, h->g_bwd[mode], [&]() -> int {
-      const int* dpatch = h->d_patch;
-      if (zero_copy(h)) dpatch = reinterpret_cast<const int*>(h->pin_dev + PIN_IMG + 3 * 64 * 64);   // read in place: no copy node
-      else HIPCHK(h, hipMemcpyAsync(h->d_patch, patch, 4 * sizeof(int), hipMemcpyHostToDevice, st));
-      int r = run_decoder_backward(h, mode, 0, 0, out.w, out.h, d_rgb, st, dpatch);
+      BrushBackward rq;
+      rq.seed.rgb = d_rgb;
+      if (zero_copy(h)) rq.seed.table = reinterpret_cast<const int*>(h->pin_dev + PIN_BRUSH);   // read in place: no copy node
+      else {
+        HIPCHK(h, hipMemcpyAsync(h->d_patch, item, 5 * sizeof(int), hipMemcpyHostToDevice, st));
+        rq.seed.table = h->d_patch;
+      }
+      int r = run_decoder_backward(h, rq, st);
       if (r) return r;
       HIPCHK(h, hipMemcpyAsync(h->pin + PIN_DZ, zs.g, zs.c * sizeof(float), hipMemcpyDeviceToHost, st));
       return 0;
@@ -247,7 +256,10 @@ int grad_common(ian_handle* h, int mode, int c1, int r1, int c2, int r2, const f
   if ((rc = decode_one_cached(h, z, st))) return rc;
   const float* d_rgb = nullptr;
   if (mode == 1 && (rc = upload_rgb_if_changed(h, rgb, st, &d_rgb))) return rc;
-  if ((rc = run_decoder_backward(h, mode, c1, r1, c2, r2, d_rgb, st))) return rc;
+  BrushBackward rq;   // no table: the rectangle travels in the launch
+  rq.seed.c1 = c1; rq.seed.r1 = r1; rq.seed.c2 = c2; rq.seed.r2 = r2; rq.seed.mode = mode;
+  rq.seed.rgb = d_rgb;
+  if ((rc = run_decoder_backward(h, rq, st))) return rc;
   // result sits in the gradient buffer of the z slot
   if (is_device_ptr(dz)) {
     HIPCHK(h, launch_rows_copy(zs.g, zs.cs, dz, zs.c, 1, zs.c, st));
@@ -374,10 +386,16 @@ int brush_pass_middle(ian_handle* h, int nc, const int* d_it, const float* d_rgb
   int rc;
   Slot& zs = h->slots[h->desc.z_slot];
   if ((rc = ensure_slot(h, h->desc.z_slot, nc, true))) return rc;
-  bool updated = false;
-  if ((rc = run_decoder_backward(h, 0, 0, 0, 0, 0, d_rgb, st, nullptr, nc, d_it, step, &updated, d_colour))) return rc;
+  BrushBackward rq;
+  rq.seed.table = d_it;
+  rq.seed.rgb = d_rgb;
+  rq.seed.colour = d_colour;
+  rq.n = nc;
+  rq.batch = true;
+  rq.update = step ? BrushBackward::PER_ITEM : BrushBackward::NONE;
+  if ((rc = run_decoder_backward(h, rq, st))) return rc;
   if (step) {
-    if (!updated) HIPCHK(h, launch_latent_update_batch(zs.d, zs.g, zs.cs, d_it, nc, h->desc.num_latents, st));
+    if (!rq.updated) HIPCHK(h, launch_latent_update_batch(zs.d, zs.g, zs.cs, d_it, nc, h->desc.num_latents, st));
     if ((rc = batch_forward(h, nullptr, nc, st))) return rc;   // sample_at(z_new)
   }
   return 0;

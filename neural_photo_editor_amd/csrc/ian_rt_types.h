@@ -259,9 +259,6 @@ struct ian_handle {
   long long stats_cap = 0;       // doubles available at stats_next.partial
   int stats_chunks_last = 0;
   float* out_mirror = nullptr;   // set around run_segment(DEC): the batch-1 image kernel also writes the image there
-  // set around run_decoder_backward by ian_brush_step: the latent's backward GEMV also applies Z += coef * (dZ * gscale) (one launch
-  // less per brush event); done = the fused form was taken (else the caller launches latent_update_kernel)
-  struct { const float* cg = nullptr; float* z_mirror = nullptr; float* g_mirror = nullptr; bool done = false; } upd;
   // several editors (ian_grad_batch / ian_brush_step_batch): the device copy of the ian_brush_item table, the brush colour images,
   // RECON / ERROR (each with the host shadow of its last upload), staging for host outputs, and the resident-activation cache:
   // bcache_z = the n latents the decoder activations belong to; enter_stream (every other call) clears bcache_valid

@@ -251,6 +251,24 @@ int ian_k_grad_pass(const float* gs, int32_t ss, int32_t coff, float* gd, const 
   return chk(launch_grad_pass(gs, ss, coff, gd, y, ds, nullptr, npix, C, act, accumulate, ST), "ian_k_grad_pass");
 }
 
+int ian_k_brush_seed(const int32_t* items, int32_t n, int32_t c1, int32_t r1, int32_t c2, int32_t r2, int32_t mode, const float* rgb,
+                     const float* colour, const float* xhat, float* g, int32_t H, int32_t W, void* stream) {
+  if (!xhat || !g || H <= 0 || W <= 0 || (colour && !items)) return bad("ian_k_brush_seed");
+  BrushSeedSrc src;
+  src.table = items; src.rgb = rgb; src.colour = colour;
+  src.c1 = c1; src.r1 = r1; src.c2 = c2; src.r2 = r2; src.mode = mode;
+  return chk(launch_brush_seed(src, n, xhat, g, H, W, ST), "ian_k_brush_seed");
+}
+
+int ian_k_brush_seed_dec_out(const int32_t* items, int32_t n, const float* rgb, const float* colour, const float* xhat, int32_t out_act,
+                             const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale, int32_t H, int32_t W,
+                             int32_t Cin, int32_t Cout, int32_t act, void* stream) {
+  if (!items || !xhat || !w || !dx || H <= 0 || W <= 0 || Cin <= 0 || Cout < 1 || Cout > 4) return bad("ian_k_brush_seed_dec_out");
+  BrushSeedSrc src;
+  src.table = items; src.rgb = rgb; src.colour = colour;
+  return chk(launch_brush_seed_dec_out(src, n, xhat, out_act, oscale, w, dx, yfwd, scale, H, W, Cin, Cout, act, ST), "ian_k_brush_seed_dec_out");
+}
+
 int ian_k_pair_loss(const float* a, const float* b, float* da, int64_t rows, int32_t C, int32_t stride, int32_t mode, float w,
                     int32_t accumulate, float* workspace, int32_t nblocks, float scale, float* out, void* stream) {
   if (!a || !b || !workspace || !out || rows <= 0 || C <= 0 || nblocks <= 0) return bad("ian_k_pair_loss");

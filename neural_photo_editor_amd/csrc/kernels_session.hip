@@ -4,7 +4,6 @@
 //   session_open_in_kernel     infer / Reset / UpdateGIM, input side: uint8 photo -> GIM, IM and the encoder's float32 input
 //   session_store_kernel       infer / Reset / sample, output side: RECON, ERROR, Z, mode flag, the canvas image
 //   session_gather_z_kernel    brush: the sessions' latents -> the decoder's latent slot
-//   *_seed_colour_batch_kernel brush: the loss seeds of kernels_misc.hip with a constant brush colour per item (NPE.py:205 myRGB)
 //   session_blend_kernel       brush / paint_latents: photo blend (photo mode) or uint8 image (sample mode) per session, z_new -> pool
 //   session_blend_local_kernel the same in a pool with the local reservation: per-session user mask, brush footprint, dampen
 //   session_local_set_kernel   local edits: a session's UMASK := 0 (every open) and its LOCAL flags (ian_session_local)
@@ -16,108 +15,8 @@
 #include <cstring>
 
 #include "ian_internal.h"
-#include "ian_dact.h"   // m_dact, under the default contraction mode
 
 namespace ian {
-
-// ---- loss seeds with a constant colour (default floating-point contraction, as in kernels_misc.hip: same object code per product) ----
-// deconv_out_bwd_seed_batch_kernel (kernels_misc.hip) with the item's brush colour image replaced by its constant colour:
-// colour[3 * item + co] stands where rgb_i[o] stood.  Same grid, same products in the same order per element.  (The launcher also
-// refuses Cout > 3, which the image form does not check: a colour has three channels.)
-__global__ __launch_bounds__(256) void deconv_out_bwd_seed_colour_batch_kernel(const float* __restrict__ xhat, const float* __restrict__ colour,
-                                                                               const int* __restrict__ items, int out_act,
-                                                                               const float* __restrict__ oscale, const float* __restrict__ w,
-                                                                               float* __restrict__ dx, const float* __restrict__ yfwd,
-                                                                               const float* __restrict__ scale, int H, int W, int Cin,
-                                                                               int Cout, int act) {
-  __shared__ int sp[5];
-  __shared__ float sc[4];
-  const int item = blockIdx.y;
-  if (threadIdx.x < 5) sp[threadIdx.x] = items[item * 7 + threadIdx.x];
-  if (threadIdx.x >= 8 && threadIdx.x < 11) sc[threadIdx.x - 8] = colour[item * 3 + (threadIdx.x - 8)];
-  __syncthreads();
-  const int c4n = Cin >> 2;
-  const int idx4 = blockIdx.x * 256 + threadIdx.x;
-  if (idx4 >= H * W * c4n) return;
-  const int ci = (idx4 % c4n) * 4, pix = idx4 / c4n;
-  const int ix = pix % W, iy = pix / W;
-  const int OH = 2 * H, OW = 2 * W;
-  const int c1 = sp[0], r1 = sp[1], c2 = sp[2], r2 = sp[3], mode = sp[4];
-  const float* xh_i = xhat + (size_t)item * Cout * OH * OW;
-  const int cnt = 3 * (r2 - r1) * (c2 - c1);
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  if (cnt > 0) {
-    const float inv = 1.f / (float)cnt;
-    const int ky0 = max(0, r1 - (2 * iy - 2)), ky1 = min(5, r2 - (2 * iy - 2));
-    const int kx0 = max(0, c1 - (2 * ix - 2)), kx1 = min(5, c2 - (2 * ix - 2));
-    for (int ky = ky0; ky < ky1; ++ky) {
-      const int oy = 2 * iy - 2 + ky;
-      if ((unsigned)oy >= (unsigned)OH) continue;
-      for (int kx = kx0; kx < kx1; ++kx) {
-        const int ox = 2 * ix - 2 + kx;
-        if ((unsigned)ox >= (unsigned)OW) continue;
-        for (int co = 0; co < Cout; ++co) {
-          const int o = (co * OH + oy) * OW + ox;
-          const float xh = xh_i[o];
-          float gv = (mode == 0) ? inv : 2.f * (xh - sc[co]) * inv;
-          gv = gv * m_dact(xh, out_act) * (oscale ? oscale[co] : 1.f);
-          const float4 wv = *reinterpret_cast<const float4*>(w + ((size_t)(ky * 5 + kx) * 4 + co) * Cin + ci);
-          acc[0] = fmaf(gv, wv.x, acc[0]);
-          acc[1] = fmaf(gv, wv.y, acc[1]);
-          acc[2] = fmaf(gv, wv.z, acc[2]);
-          acc[3] = fmaf(gv, wv.w, acc[3]);
-        }
-      }
-    }
-  }
-  const size_t o4 = ((size_t)item * H * W + pix) * Cin + ci;
-  float4 out;
-  float* op = &out.x;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float d = yfwd ? m_dact(yfwd[o4 + e], act) : 1.f;
-    op[e] = acc[e] * d * (scale ? scale[ci + e] : 1.f);
-  }
-  *reinterpret_cast<float4*>(dx + o4) = out;
-}
-hipError_t launch_deconv_out_bwd_seed_colour_batch(const float* xhat, const float* colour, const int* items, int n, int out_act,
-                                                   const float* oscale, const float* w, float* dx, const float* yfwd, const float* scale,
-                                                   int H, int W, int Cin, int Cout, int act, hipStream_t s) {
-  if ((Cin & 3) || Cout > 3 || n < 1 || n > 65535) return hipErrorInvalidValue;
-  const int total = H * W * (Cin >> 2);
-  hipLaunchKernelGGL(deconv_out_bwd_seed_colour_batch_kernel, dim3((total + 255) / 256, n), dim3(256), 0, s, xhat, colour, items, out_act,
-                     oscale, w, dx, yfwd, scale, H, W, Cin, Cout, act);
-  return hipGetLastError();
-}
-
-// patch_seed_batch_kernel (kernels_misc.hip) likewise: NCHW [n,3,H,W], element i of an image belongs to channel i / (H*W)
-__global__ __launch_bounds__(256) void patch_seed_colour_batch_kernel(const float* __restrict__ xhat, const float* __restrict__ colour,
-                                                                      float* __restrict__ g, int H, int W, const int* __restrict__ items) {
-  __shared__ int sp[5];
-  __shared__ float sc[4];
-  const int item = blockIdx.y;
-  if (threadIdx.x < 5) sp[threadIdx.x] = items[item * 7 + threadIdx.x];
-  if (threadIdx.x >= 8 && threadIdx.x < 11) sc[threadIdx.x - 8] = colour[item * 3 + (threadIdx.x - 8)];
-  __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 3 * H * W) return;
-  const int c1 = sp[0], r1 = sp[1], c2 = sp[2], r2 = sp[3], mode = sp[4];
-  const size_t o = (size_t)item * 3 * H * W + i;
-  const int xx = i % W, yy = (i / W) % H, co = i / (H * W);
-  const int cnt = 3 * (r2 - r1) * (c2 - c1);
-  float v = 0.f;
-  if (yy >= r1 && yy < r2 && xx >= c1 && xx < c2 && cnt > 0) {
-    const float inv = 1.f / (float)cnt;
-    v = (mode == 0) ? inv : 2.f * (xhat[o] - sc[co]) * inv;
-  }
-  g[o] = v;
-}
-hipError_t launch_patch_seed_colour_batch(const float* xhat, const float* colour, float* g, int H, int W, const int* items, int n,
-                                          hipStream_t s) {
-  if (n < 1 || n > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(patch_seed_colour_batch_kernel, dim3((3 * H * W + 255) / 256, n), dim3(256), 0, s, xhat, colour, g, H, W, items);
-  return hipGetLastError();
-}
 
 // ---- undo history: copies between a session's live rows and its ring of saved states, one workgroup per session -------
 // A saved state is the session's Z row and, in a pool that had the local reservation when the history was reserved, its UMASK row.
