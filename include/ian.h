@@ -459,6 +459,79 @@ int ian_session_save(ian_handle* h, int32_t n, const int32_t* ids, ian_session_m
    hist_len > depth + 1 otherwise, any entry at depth 0; a reserved word that is not zero. */
 int ian_session_load(ian_handle* h, int32_t n, const int32_t* ids, const ian_session_meta* meta, const void* body, void* stream);
 
+/* ---- canvases: sessions placed on whole photos, and the composed result ----
+   A full-resolution session is a square of 64 * scale pixels and the pool has one scale.  A real photo is some W x H; the face the
+   model can edit is a square somewhere inside it, and a group photo has several.  With the reservation below photos of any size
+   (canvases) live in device memory, sessions are placed on a canvas as squares -- each with its own integer scale, at any pixel
+   offset -- and one kernel composes windows of the whole photo from the canvas and every placed session's edit field (FIELD /
+   FIELD_KIND of the full-resolution reservation), feathered towards each square's edge.  Per output pixel and channel, float32,
+   every operation rounded on its own:
+     acc = float32(canvas byte); then for every placement whose square covers the pixel, in ascending session id:
+       v = the bilinear sample of its FIELD at the pixel's place in the square, exactly as ian_session_render samples it;
+       w = ry * rx, each r = min(1.0f, float32(2d + 1) / float32(2 * feather * scale)) with d the distance to the nearer edge of
+           the square along that axis (feather 0: w = 1.0f);
+       kind 0: acc = acc + (127.5f * v) * w;   kind 1: t = 127.5f * (v + 1.0f); acc = t where w == 1.0f, else acc + (t - acc) * w;
+     out = uint8(clip(rint(acc), 0, 255)), ties to even.
+   Zero fields return the canvas bytes, no byte outside every square changes, and in the core of a lone placement (w == 1) the
+   result is byte for byte what ian_session_render gives for the crop.  The arithmetic is npe_ops.canvas_crop_mean / canvas_ramp /
+   canvas_compose (numpy); the device matches them bit for bit.  Without the reservation nothing of this exists and no other call
+   launches, moves or computes anything it did not before.  A placement is not part of a saved session (ian_session_save). */
+typedef struct ian_canvas_placement {
+  int32_t session; /* id in the pool */
+  int32_t canvas;  /* id of the canvas, 0..count-1 */
+  int32_t x, y;    /* top-left corner of the square on the canvas, any alignment */
+  int32_t scale;   /* 1..16: the square is 64 * scale pixels a side */
+} ian_canvas_placement;
+typedef struct ian_canvas_window {
+  int32_t canvas; /* id of the canvas */
+  int32_t x, y;   /* top-left corner of the window on the canvas */
+} ian_canvas_window;
+#define IAN_CANVAS_MAX_PLACED 8
+
+/* count 1..64 canvases of up to max_w x max_h pixels (64..8192 each, max_w a multiple of 4): `count` arrays u8[3,max_h,max_w] and
+   a device table of IAN_CANVAS_MAX_PLACED placements per canvas; feather 0..16 is the width of every square's feathered rim in
+   field pixels.  count 0 frees the arrays and every placement.  Needs ian_sessions_reserve and ian_sessions_reserve_hires at any
+   scale first (-6 otherwise): a placement uses FIELD and FIELD_KIND, SRC is not touched.  Synchronises the device.  A second
+   reservation starts from nothing: no canvas holds a picture, no session is placed.  An allocation failure (-2) leaves the old
+   state intact.  While canvases are reserved ian_sessions_reserve_hires(0) returns -6 (the only new refusal of an existing call);
+   ian_sessions_reserve(capacity) drops the placements of the ids that leave the pool, ian_sessions_reserve(0) frees the canvases
+   with everything else. */
+int ian_sessions_reserve_canvas(ian_handle* h, int32_t count, int32_t max_w, int32_t max_h, int32_t feather);
+/* The picture of one canvas: pixels u8[3,hgt,w], host or device; 64 <= w <= max_w, w a multiple of 4, 64 <= hgt <= max_h.  A strided
+   copy into the canvas's array.  Every placement on that canvas is dropped; the sessions keep their 64x64 state. */
+int ian_canvas_put(ian_handle* h, int32_t canvas, int32_t w, int32_t hgt, const uint8_t* pixels, void* stream);
+/* Per item: GIM := the exact integer box mean of the canvas's square (x, y) + 64 * scale over scale x scale blocks, computed on the
+   device straight from the canvas; then exactly ian_session_open(photos = GIM) in the same submission (the UMASK clear, the history
+   clear and a zero FIELD at kind 0 included); the session is placed at (canvas, x, y, scale).  A session already placed moves.
+   shown u8[n,3,64,64] (host or device) or NULL receives IM.  The session counts as opened without a full-resolution source.
+   -6: no canvas reservation.  -7, naming the item, before anything is enqueued: n outside 1..256, an id or a canvas outside its
+   range, a canvas never put, a square outside the canvas, scale outside 1..16, an id given twice, a ninth session on one canvas. */
+int ian_canvas_place(ian_handle* h, int32_t n, const ian_canvas_placement* items, uint8_t* shown, void* stream);
+/* Window (x, y, vw, vh) of each named canvas -> out u8[n,3,vh,vw] (host or device, 4-byte aligned), composed as above over that
+   canvas's placements.  x and vw must be multiples of 4, vw >= 4, vh >= 1, the window inside the canvas's w x hgt.  Like
+   ian_session_render it touches neither the decoder's activations nor the residency of ian_session_brush.  The same canvas may
+   appear several times, as tiles.  -6: no canvas reservation.  -7, naming the item: n outside 1..256, a canvas outside its range or
+   never put, a window outside the picture, x or vw not a multiple of 4. */
+int ian_canvas_compose(ian_handle* h, int32_t n, const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream);
+/* ian_session_brush on n events followed by ian_canvas_compose of m windows, in ONE submission with one synchronisation: what
+   ian_session_brush_view is to ian_session_render.  The events' sessions need not be placed and the windows need not belong to
+   them.  Every check of both calls is made before anything is enqueued. */
+int ian_canvas_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, int32_t m,
+                     const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream);
+/* The canvas becomes the compose of its whole picture, in place; then every session placed on it is placed again where it is: the
+   box mean of the new canvas and the open above, at batch k = the number of sessions placed there.  shown u8[k,3,64,64] (host or
+   device; ascending session id) or NULL.  ian_session_open(source = 1) on a placed session returns -7 and names this call: GIM := IM
+   would bake the unfeathered 64x64 blend into the session.  Reset (source = 0) works as always.  ian_session_open with photos,
+   ian_session_open_hires and ian_session_load on a placed session un-place it; every other session call works on a placed
+   session as on any other, and a compose reads whatever FIELD it left. */
+int ian_canvas_commit(ian_handle* h, int32_t canvas, uint8_t* shown, void* stream);
+/* The picture of one canvas as it is stored (the placed sessions' edits are NOT on it before a commit) -> out u8[3,hgt,w], host or
+   device; wh (host, or NULL) receives w and hgt.  out NULL: only wh. */
+int ian_canvas_read(ian_handle* h, int32_t canvas, uint8_t* out, int32_t wh[2], void* stream);
+/* The sessions placed on one canvas, in ascending session id -> out8 (host; room for IAN_CANVAS_MAX_PLACED) and their count.  Host
+   only: no device state is touched. */
+int ian_canvas_placements(ian_handle* h, int32_t canvas, ian_canvas_placement* out8, int32_t* count);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -209,6 +209,103 @@ def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, so
     return views, vw, vh
 
 
+def _int_pairs(v, n, what):
+    a = np.asarray(v)
+    if a.shape == (2,):
+        a = np.tile(a, (n, 1))
+    if a.shape != (n, 2) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("%s must be integers of shape (%d,2) or (2,) as (x, y), got %s %s" % (what, n, a.dtype, a.shape))
+    return a
+
+
+def _canvas_ids(cids, n, sizes):
+    """One canvas id for all n items or one per item -> n ints, each a canvas of the reservation that holds a picture.
+    sizes = {canvas id: (w, h)} of the canvases that were put, or a list with None for those that were not."""
+    a = np.asarray(cids)
+    if a.ndim == 0:
+        a = np.tile(a, n)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("canvas ids must be one integer or %d integers, got %s %s" % (n, a.dtype, a.shape))
+    out = [int(v) for v in a]
+    for i, c in enumerate(out):
+        if not 0 <= c < len(sizes):
+            raise ValueError("item %d: canvas %d outside 0..%d" % (i, c, len(sizes) - 1))
+        if sizes[c] is None:
+            raise ValueError("item %d: canvas %d holds no picture (canvas_put)" % (i, c))
+    return out
+
+
+def pack_canvas_placements(ids, cids, origins, scales, sizes, placed=None, capacity=None):
+    """Python arguments of ian_canvas_place -> a ctypes array of ian_canvas_placement (include/ian.h), validated before the library
+    sees anything.  ids (n,) session ids, each once; cids one canvas id or (n,); origins (n,2) or (2,) as (x, y), the squares'
+    top-left corners at any alignment; scales one integer or (n,), 1..16: a square is 64 * scale pixels a side and must lie inside
+    its canvas.  sizes = per canvas (w, h) or None for a canvas that holds no picture; placed = {session id: canvas id} as it is now
+    (a session already placed moves), from which the ninth session on one canvas is refused; capacity bounds the ids."""
+    from .lib import CANVAS_MAX_PLACED, CanvasPlacement
+    idv = check_session_ids(ids, capacity)
+    n = len(idv)
+    cv = _canvas_ids(cids, n, sizes)
+    o = _int_pairs(origins, n, "origins")
+    sc = np.asarray(scales)
+    if sc.ndim == 0:
+        sc = np.tile(sc, n)
+    if sc.shape != (n,) or not np.issubdtype(sc.dtype, np.integer):
+        raise ValueError("scales must be one integer or %d integers, got %s %s" % (n, sc.dtype, sc.shape))
+    after = dict(placed or {})
+    items = (CanvasPlacement * n)()
+    for i in range(n):
+        sid, c, x, y, s = int(idv[i]), cv[i], int(o[i, 0]), int(o[i, 1]), int(sc[i])
+        if not 1 <= s <= 16:
+            raise ValueError("item %d: scale %d outside 1..16" % (i, s))
+        w, h = sizes[c]
+        if x < 0 or y < 0 or x + 64 * s > w or y + 64 * s > h:
+            raise ValueError("item %d: square (%d,%d) + %d outside the %d x %d canvas" % (i, x, y, 64 * s, w, h))
+        after.pop(sid, None)                   # a session that moves leaves its square first
+        p = items[i]
+        p.session, p.canvas, p.x, p.y, p.scale = sid, c, x, y, s
+    for i in range(n):
+        after[int(idv[i])] = cv[i]
+        if sum(1 for c in after.values() if c == cv[i]) > CANVAS_MAX_PLACED:
+            raise ValueError("item %d: canvas %d already holds %d sessions" % (i, cv[i], CANVAS_MAX_PLACED))
+    return items
+
+
+def pack_canvas_windows(cids, origins, size, sizes):
+    """Python arguments of ian_canvas_compose / ian_canvas_brush -> (a ctypes array of ian_canvas_window, vw, vh), validated before
+    the library sees anything.  cids (n,) canvas ids -- the same canvas may appear several times, as tiles; origins (n,2) or (2,)
+    as (x, y); size = (vw, vh) or one integer.  x and vw must be multiples of 4, the window inside the canvas's picture.  sizes as in
+    pack_canvas_placements."""
+    from .lib import CanvasWindow
+    a = np.asarray(cids)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    if a.ndim != 1 or not 1 <= a.shape[0] <= BATCH_MAX:
+        raise ValueError("a call holds 1..%d windows, got shape %s" % (BATCH_MAX, a.shape))
+    n = a.shape[0]
+    cv = _canvas_ids(a, n, sizes)
+    sz = np.asarray(size)
+    if sz.ndim == 0:
+        sz = np.tile(sz, 2)
+    if sz.shape != (2,) or not np.issubdtype(sz.dtype, np.integer):
+        raise ValueError("size must be (vw, vh) or one integer, got %r" % (size,))
+    vw, vh = int(sz[0]), int(sz[1])
+    if vw < 1 or vh < 1:
+        raise ValueError("window %d x %d: both sizes must be at least 1" % (vw, vh))
+    if vw % 4:
+        raise ValueError("window width %d is not a multiple of 4" % vw)
+    o = _int_pairs(origins, n, "origins")
+    win = (CanvasWindow * n)()
+    for i in range(n):
+        x, y = int(o[i, 0]), int(o[i, 1])
+        w, h = sizes[cv[i]]
+        if x % 4:
+            raise ValueError("item %d: window x %d is not a multiple of 4" % (i, x))
+        if x < 0 or y < 0 or x + vw > w or y + vh > h:
+            raise ValueError("item %d: window (%d,%d) + %d x %d outside the %d x %d canvas" % (i, x, y, vw, vh, w, h))
+        win[i].canvas, win[i].x, win[i].y = cv[i], x, y
+    return win, vw, vh
+
+
 def pack_session_local(ids, local=True, dampen=False, flags=None, capacity=None, opened=None):
     """Python arguments of ian_session_local -> (ids int32 (n,), flags int32 (n,)), validated before the library sees anything.
     local and dampen are booleans, one for all or one per session: flags = local + 2 * dampen.  flags, when given, replaces both: a
@@ -351,7 +448,15 @@ class EditSessions:
     Undo (no counterpart in NPE.py): reserve_history(depth) keeps a ring of saved latents (and user masks) per session on the device;
         mark(ids)  a stroke begins     undo(ids, steps) / redo(ids, steps)  back and forth -> shown     history(sid)  what is possible
     Leaving the pool (no counterpart in NPE.py): save(ids) -> SessionRecords, everything above as bytes; load(ids, records) puts them
-        into any ids of a pool of the same layout: a project file, a move to another handle, parking an idle editor"""
+        into any ids of a pool of the same layout: a project file, a move to another handle, parking an idle editor
+    Whole photos (no counterpart in NPE.py): reserve_canvases(count, max_w, max_h, feather) keeps photos of any size (canvases) in
+    device memory beside a full-resolution pool; canvas_put(cid, photo) loads one.
+        place(ids, cids, origins, scales)  each session opens on the box mean of a square of its canvas, 64*scale pixels a side
+        compose(cids, origins, size)       windows of the photos with every placed session's edit on top, feathered at the squares' rims
+        brush_compose(..., windows=)       the event and the windows in one submission -> (shown, out)
+        canvas_commit(cid)                 the composed photo becomes the canvas, its sessions start again from it -> shown
+        canvas_read(cid) / placements(cid) the stored photo / [(session, x, y, scale)]
+    open, open_hires and load un-place a session; commit on a placed session is refused (canvas_commit is its form)."""
 
     def __init__(self, handle, capacity, zdim, sigma=0.7):
         from . import npe_ops
@@ -363,6 +468,11 @@ class EditSessions:
         self.history_depth = 0          # history reservation: how many marks a session can undo; 0 = none
         self._opened = set()
         self._sourced = set()           # ids whose SRC holds a photo
+        self.canvases = 0               # canvas reservation: how many photos of up to canvas_max = (max_w, max_h); 0 = none
+        self.canvas_max = (0, 0)
+        self.feather = 0
+        self._canvas_wh = []            # per canvas (w, h) of its picture, None before canvas_put
+        self._placed = {}               # session id -> (canvas id, x, y, scale)
         self.reserve(capacity)
         self._h.sessions_set_blend(npe_ops.gaussian_half_kernel(sigma, int(4.0 * float(sigma) + 0.5)))
 
@@ -375,6 +485,7 @@ class EditSessions:
         self.capacity = capacity
         self._opened = {v for v in self._opened if v < capacity}
         self._sourced = {v for v in self._sourced if v < capacity}
+        self._placed = {v: p for v, p in self._placed.items() if v < capacity}
 
     def reserve_hires(self, scale):
         """Keep every session's photo at (3, 64*scale, 64*scale), scale in 1..16; 0 frees that again.  Changing the scale drops the
@@ -382,6 +493,8 @@ class EditSessions:
         scale = int(scale)
         if not 0 <= scale <= 16:
             raise ValueError("scale must be in 0..16, got %d" % scale)
+        if scale == 0 and self.canvases:
+            raise ValueError("canvases are reserved: free them first (reserve_canvases(0))")
         self._h.sessions_reserve_hires(scale)
         if scale != self.scale:
             self._sourced = set()
@@ -502,6 +615,7 @@ class EditSessions:
             self._h.session_load(idv, meta, body)
         for v, m in zip((int(v) for v in idv), meta):
             self._opened.add(v)
+            self._placed.pop(v, None)
             (self._sourced.add if int(m["has_source"]) else self._sourced.discard)(v)
 
     def _ids(self, ids, need_opened):
@@ -531,6 +645,7 @@ class EditSessions:
         self._h.session_open(ids, self._photos(photos, len(ids), 64), 0, shown)
         self._opened.update(int(v) for v in ids)
         self._sourced.difference_update(int(v) for v in ids)
+        self._unplace(ids)
         return shown
 
     def open_hires(self, ids, photos):
@@ -542,6 +657,7 @@ class EditSessions:
         self._h.session_open_hires(ids, self._photos(photos, len(ids), 64 * self.scale), shown)
         self._opened.update(int(v) for v in ids)
         self._sourced.update(int(v) for v in ids)
+        self._unplace(ids)
         return shown
 
     def _views(self, ids, origins, size, events=None):
@@ -564,6 +680,120 @@ class EditSessions:
         self._h.session_brush_view(ev, views, vw, vh, out, shown)
         return shown, out
 
+    # ---- canvases ----
+    def _unplace(self, ids):
+        for v in ids:
+            self._placed.pop(int(v), None)
+
+    def _need_canvases(self):
+        if not self.canvases:
+            raise ValueError("the pool has no canvas reservation (reserve_canvases)")
+
+    def _canvas(self, cid, need_put=True):
+        self._need_canvases()
+        if int(cid) != cid or not 0 <= int(cid) < self.canvases:
+            raise ValueError("canvas %r outside 0..%d" % (cid, self.canvases - 1))
+        if need_put and self._canvas_wh[int(cid)] is None:
+            raise ValueError("canvas %d holds no picture (canvas_put)" % int(cid))
+        return int(cid)
+
+    def reserve_canvases(self, count, max_w=0, max_h=0, feather=4):
+        """Keep `count` (1..64) photos of up to max_w x max_h pixels (64..8192 each, max_w a multiple of 4) in device memory,
+        3 * max_w * max_h bytes each; feather (0..16) is the width, in 64x64 field pixels, over which a placed session's edit fades
+        towards the edge of its square.  0 frees them and every placement.  Needs reserve_hires first.  A second reservation starts
+        from nothing: no canvas holds a picture, no session is placed."""
+        count, max_w, max_h, feather = int(count), int(max_w), int(max_h), int(feather)
+        if not 0 <= count <= 64:
+            raise ValueError("count must be in 0..64, got %d" % count)
+        if count:
+            if not self.scale:
+                raise ValueError("the pool has no full-resolution reservation (reserve_hires)")
+            if not (64 <= max_w <= 8192 and 64 <= max_h <= 8192):
+                raise ValueError("max_w and max_h must be in 64..8192, got %d x %d" % (max_w, max_h))
+            if max_w % 4:
+                raise ValueError("max_w %d is not a multiple of 4" % max_w)
+            if not 0 <= feather <= 16:
+                raise ValueError("feather must be in 0..16, got %d" % feather)
+        self._h.sessions_reserve_canvas(count, max_w, max_h, feather)
+        self.canvases, self.canvas_max, self.feather = count, ((max_w, max_h) if count else (0, 0)), (feather if count else 0)
+        self._canvas_wh = [None] * count
+        self._placed = {}
+
+    def canvas_put(self, cid, photo):
+        """The picture of canvas cid := photo, uint8 (3,h,w) (a numpy array, or a torch device tensor), 64 <= w <= max_w with w a
+        multiple of 4, 64 <= h <= max_h.  Every session placed on that canvas is un-placed; its 64x64 state stays."""
+        cid = self._canvas(cid, need_put=False)
+        dev = hasattr(photo, "data_ptr")
+        p = photo if dev else np.ascontiguousarray(photo)
+        if str(p.dtype).split(".")[-1] != "uint8" or len(p.shape) != 3 or p.shape[0] != 3:
+            raise ValueError("a canvas photo is uint8 (3,h,w), got %s %s" % (p.dtype, tuple(p.shape)))
+        if dev and not p.is_contiguous():
+            raise ValueError("a device photo must be contiguous")
+        h, w = int(p.shape[1]), int(p.shape[2])
+        if not (64 <= w <= self.canvas_max[0] and 64 <= h <= self.canvas_max[1]):
+            raise ValueError("photo %d x %d outside 64 x 64 .. %d x %d" % (w, h, self.canvas_max[0], self.canvas_max[1]))
+        if w % 4:
+            raise ValueError("photo width %d is not a multiple of 4 (pad it)" % w)
+        self._h.canvas_put(cid, p)
+        self._canvas_wh[cid] = (w, h)
+        self._placed = {v: q for v, q in self._placed.items() if q[0] != cid}
+
+    def place(self, ids, cids, origins, scales):
+        """Sessions ids[i] open on the exact box mean of the square origins[i] + 64*scales[i] of canvas cids[i] (pack_canvas_placements)
+        and are placed there -> IM, uint8 (n,3,64,64).  Exactly open() of that box mean, in one submission; a session already placed moves."""
+        self._need_canvases()
+        items = pack_canvas_placements(ids, cids, origins, scales, self._canvas_wh, {v: q[0] for v, q in self._placed.items()},
+                                       self.capacity)
+        shown = np.empty((len(items), 3, 64, 64), np.uint8)
+        self._h.canvas_place(items, shown)
+        for p in items:
+            self._opened.add(p.session)
+            self._sourced.discard(p.session)
+            self._placed[p.session] = (p.canvas, p.x, p.y, p.scale)
+        return shown
+
+    def _windows(self, cids, origins, size):
+        self._need_canvases()
+        return pack_canvas_windows(cids, origins, size, self._canvas_wh)
+
+    def compose(self, cids, origins, size):
+        """Windows of the canvases with every placed session's edit on top (npe_ops.canvas_compose) -> uint8 (n,3,vh,vw).  origins
+        (n,2) or (2,) as (x, y), size (vw, vh) or one integer; x and vw multiples of 4.  The same canvas may appear several times."""
+        win, vw, vh = self._windows(cids, origins, size)
+        out = np.empty((len(win), 3, vh, vw), np.uint8)
+        self._h.canvas_compose(win, vw, vh, out)
+        return out
+
+    def brush_compose(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, windows=None):
+        """brush on sessions ids, and the windows = (cids, origins, size) of compose() after it, in ONE submission -> (shown, out).
+        The sessions need not be placed, the windows need not show them."""
+        if windows is None or len(windows) != 3:
+            raise ValueError("windows must be (cids, origins, size)")
+        ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
+        win, vw, vh = self._windows(*windows)
+        shown = np.empty((len(ev), 3, 64, 64), np.uint8)
+        out = np.empty((len(win), 3, vh, vw), np.uint8)
+        self._h.canvas_brush(ev, win, vw, vh, out, shown)
+        return shown, out
+
+    def canvas_commit(self, cid):
+        """The canvas becomes its own compose, in place; the sessions placed on it open again on the box means of the new picture, where
+        they are -> IM of those sessions in ascending id, uint8 (k,3,64,64)."""
+        cid = self._canvas(cid)
+        k = sum(1 for q in self._placed.values() if q[0] == cid)
+        shown = np.empty((k, 3, 64, 64), np.uint8)
+        self._h.canvas_commit(cid, shown if k else None)
+        return shown
+
+    def canvas_read(self, cid):
+        """The stored picture of a canvas, uint8 (3,h,w): without the placed sessions' edits until canvas_commit.  A synchronising copy."""
+        return self._h.canvas_read(self._canvas(cid))
+
+    def placements(self, cid):
+        """-> [(session, x, y, scale)] of the sessions placed on canvas cid, in ascending session id."""
+        cid = self._canvas(cid, need_put=False)
+        return sorted((v, q[1], q[2], q[3]) for v, q in self._placed.items() if q[0] == cid)
+
     def reset(self, ids):
         """Reset: re-open from the stored GIM."""
         ids = self._ids(ids, True)
@@ -572,8 +802,11 @@ class EditSessions:
         return shown
 
     def commit(self, ids):
-        """UpdateGIM: GIM := IM, then Reset."""
+        """UpdateGIM: GIM := IM, then Reset.  A session placed on a canvas is refused: canvas_commit is its form."""
         ids = self._ids(ids, True)
+        for i, v in enumerate(int(v) for v in ids):
+            if v in self._placed:
+                raise ValueError("item %d: session %d is placed on canvas %d: commit the canvas instead (canvas_commit)" % (i, v, self._placed[v][0]))
         shown = np.empty((len(ids), 3, 64, 64), np.uint8)
         self._h.session_open(ids, None, 1, shown)
         return shown
@@ -644,6 +877,7 @@ class EditSessions:
             self.history_depth = 0
             self._opened = set()
             self._sourced = set()
+            self.canvases, self.canvas_max, self.feather, self._canvas_wh, self._placed = 0, (0, 0), 0, [], {}
 
 
 class IAN:

@@ -450,6 +450,24 @@ hipError_t launch_session_hires_open(const unsigned char* photos, const SessionP
 // npe_ops.hires_render of n windows: views = device int[n][3] (session, x, y), every window vw x vh with x and vw multiples of 4.
 // out u8 [n][3][vh][vw]; out == nullptr: the whole picture (vw = vh = S, x = y = 0) written over the session's own SRC row
 hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s);
+// canvases (ian_sessions_reserve_canvas): whole photos in device memory and, per canvas, the table of the sessions
+// placed on it.  Beside the pool for SessionRings' reason; only the two canvas kernels take it.  All nullptr / 0 without the reservation.
+constexpr int CANVAS_MAX_PLACED = 8;
+struct SessionCanvases {
+  unsigned char* pix;     // u8 [count][3][max_h][max_w]: row stride max_w whatever a picture's own width (size_t offsets throughout)
+  int* table;             // int[count][CANVAS_MAX_PLACED][4]: (session, x, y, scale) in ascending session id, session -1 ends the list
+  int count, max_w, max_h;
+  int feather;            // 0..16, in field pixels
+};
+// place: items = device int[n][5] (ian_canvas_placement: session, canvas, x, y, scale).  The exact box mean of the canvas's square ->
+// GIM, IM of the session and x[i] = table[byte]: the outputs of launch_session_hires_open, without an SRC copy, the square at any
+// byte alignment, the scale per item.
+hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, const int* items, const float* table, float* x, int n,
+                               hipStream_t s);
+// npe_ops.canvas_compose of n windows: windows = device int[n][3] (canvas, x, y), every window vw x vh with x and vw multiples of 4.
+// out u8 [n][3][vh][vw]; out == nullptr: n == 1 and the window is a whole picture (x = y = 0), written over the canvas itself
+hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, unsigned char* out,
+                                 int n, hipStream_t s);
 
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,

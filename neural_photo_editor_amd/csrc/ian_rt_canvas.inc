@@ -1,0 +1,369 @@
+// ian_rt_canvas.inc -- canvases: whole photos in device memory, edit sessions placed on them as squares, the composed result.
+// Part of the libian runtime: one translation unit, included by ian_runtime.cpp after ian_rt_session.inc (whose helpers it uses, and
+// which declares, at its top, what the session calls need from here).  DESIGN.md 4.7; include/ian.h has the contract.
+//
+// One reservation (ian_sessions_reserve_canvas) owns everything here: `count` pictures u8[3,max_h,max_w] in one allocation, the device
+// table of CANVAS_MAX_PLACED placements per canvas, and the window table of a compose call.  The arrays are per canvas, not per
+// session, so they are not columns of SESS_COLUMNS; a placement is not part of a saved session.  The host owns the placements
+// (S.placed, one entry per session id; S.ctab_shadow, the device table's copy in ascending session id per canvas); a canvas whose
+// list changed is marked dirty and its 8 entries are uploaded on the stream of the call that changed it.  A pool without the
+// reservation has S.canv.pix == nullptr and S.placed empty, and every hook below returns at once.
+namespace {
+
+constexpr int CANVAS_MAX_COUNT = 64, CANVAS_MIN_SIDE = 64, CANVAS_MAX_SIDE = 8192, CANVAS_MAX_FEATHER = 16;
+static_assert(CANVAS_MAX_PLACED == IAN_CANVAS_MAX_PLACED, "the kernels' table and the header agree");
+static_assert(sizeof(ian_canvas_placement) == 5 * sizeof(int32_t), "ian_canvas_placement is 5 words");
+static_assert(sizeof(ian_canvas_window) == 3 * sizeof(int32_t), "ian_canvas_window is 3 words");
+
+size_t canvas_plane_bytes(const SessionCanvases& C) { return (size_t)C.max_h * (size_t)C.max_w; }
+unsigned char* canvas_pixels(const SessionCanvases& C, int canvas) { return C.pix + (size_t)canvas * 3 * canvas_plane_bytes(C); }
+
+void canvases_free(ian_handle* h) {
+  auto& S = h->sess;
+  if (S.canv.pix) (void)hipFree(S.canv.pix);
+  if (S.canv.table) (void)hipFree(S.canv.table);
+  if (S.d_cwin) (void)hipFree(S.d_cwin);
+  S.canv = SessionCanvases{};
+  S.d_cwin = nullptr;
+  S.canvas_wh.clear();
+  S.placed.clear();
+  S.ctab_shadow.clear();
+  S.cdirty.clear();
+}
+
+bool canvas_is_placed(const ian_handle* h, int id) {
+  const auto& S = h->sess;
+  return (size_t)id < S.placed.size() && S.placed[id].canvas >= 0;
+}
+
+// the list of one canvas, rebuilt from S.placed: ascending session id, -1 behind the last
+void canvas_table_rebuild(ian_handle* h, int canvas) {
+  auto& S = h->sess;
+  int32_t* t = S.ctab_shadow.data() + (size_t)canvas * CANVAS_MAX_PLACED * 4;
+  int k = 0;
+  for (size_t id = 0; id < S.placed.size() && k < CANVAS_MAX_PLACED; ++id) {
+    const ian_canvas_placement& p = S.placed[id];
+    if (p.canvas != canvas) continue;
+    t[4 * k] = (int32_t)id; t[4 * k + 1] = p.x; t[4 * k + 2] = p.y; t[4 * k + 3] = p.scale;
+    ++k;
+  }
+  for (; k < CANVAS_MAX_PLACED; ++k) { t[4 * k] = -1; t[4 * k + 1] = t[4 * k + 2] = t[4 * k + 3] = 0; }
+  S.cdirty[canvas] = 1;
+}
+
+void canvas_unplace(ian_handle* h, int id) {
+  if (!canvas_is_placed(h, id)) return;
+  auto& S = h->sess;
+  const int canvas = S.placed[id].canvas;
+  S.placed[id].canvas = -1;
+  canvas_table_rebuild(h, canvas);
+}
+
+int canvas_table_flush(ian_handle* h, hipStream_t st) {
+  auto& S = h->sess;
+  for (size_t c = 0; c < S.cdirty.size(); ++c) {
+    if (!S.cdirty[c]) continue;
+    const size_t at = c * CANVAS_MAX_PLACED * 4;
+    HIPCHK(h, hipMemcpyAsync(S.canv.table + at, S.ctab_shadow.data() + at, CANVAS_MAX_PLACED * 4 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    S.cdirty[c] = 0;
+  }
+  return 0;
+}
+
+// ian_sessions_reserve(capacity) has rebuilt the pool (the device is idle): S.placed follows the capacity
+int canvases_pool_resized(ian_handle* h) {
+  auto& S = h->sess;
+  if (!S.canv.pix) return 0;
+  for (size_t id = (size_t)S.capacity; id < S.placed.size(); ++id) canvas_unplace(h, (int)id);
+  S.placed.resize((size_t)S.capacity, ian_canvas_placement{0, -1, 0, 0, 0});
+  int rc = canvas_table_flush(h, nullptr);
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+int canvas_need(ian_handle* h, const char* fn) {
+  int rc = check_ready(h, 1);
+  if (rc) return rc;
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
+  if (!h->sess.canv.pix) return fail(h, -6, "%s: no canvas reservation (call ian_sessions_reserve_canvas first)", fn);
+  return 0;
+}
+// a canvas id of this reservation that holds a picture; item < 0: the call names one canvas only
+int canvas_check_id(ian_handle* h, const char* fn, int item, int canvas, bool need_put) {
+  auto& S = h->sess;
+  char where[32] = "";
+  if (item >= 0) snprintf(where, sizeof where, "item %d: ", item);
+  if (canvas < 0 || canvas >= S.canv.count) return fail(h, -7, "%s: %scanvas %d outside 0..%d", fn, where, canvas, S.canv.count - 1);
+  if (need_put && !S.canvas_wh[2 * canvas]) return fail(h, -7, "%s: %scanvas %d holds no picture (call ian_canvas_put first)", fn, where, canvas);
+  return 0;
+}
+
+int sessions_reserve_canvas(ian_handle* h, int count, int max_w, int max_h, int feather) {
+  const char* fn = "ian_sessions_reserve_canvas";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
+  if (count < 0 || count > CANVAS_MAX_COUNT) return fail(h, -7, "%s: count %d outside 0..%d", fn, count, CANVAS_MAX_COUNT);
+  if (count > 0) {
+    if (max_w < CANVAS_MIN_SIDE || max_w > CANVAS_MAX_SIDE || max_h < CANVAS_MIN_SIDE || max_h > CANVAS_MAX_SIDE)
+      return fail(h, -7, "%s: %d x %d: both sizes must be in %d..%d", fn, max_w, max_h, CANVAS_MIN_SIDE, CANVAS_MAX_SIDE);
+    if (max_w & 3) return fail(h, -7, "%s: max_w %d is not a multiple of 4", fn, max_w);
+    if (feather < 0 || feather > CANVAS_MAX_FEATHER) return fail(h, -7, "%s: feather %d outside 0..%d", fn, feather, CANVAS_MAX_FEATHER);
+  }
+  HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the arrays that are freed
+  h->last_pending = false;
+  if (count == 0) {
+    canvases_free(h);
+    return 0;
+  }
+  SessionCanvases N = {};
+  N.count = count; N.max_w = max_w; N.max_h = max_h; N.feather = feather;
+  int* cwin = nullptr;
+  const size_t bytes = (size_t)count * 3 * canvas_plane_bytes(N), tbytes = (size_t)count * CANVAS_MAX_PLACED * 4 * sizeof(int32_t);
+  hipError_t e = hipMalloc((void**)&N.pix, bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&N.table, tbytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&cwin, (size_t)BATCH_MAX * 3 * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemset(N.table, 0xff, tbytes);   // every list empty (session -1)
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {   // the old canvases, their pictures and placements stay
+    if (N.pix) (void)hipFree(N.pix);
+    if (N.table) (void)hipFree(N.table);
+    if (cwin) (void)hipFree(cwin);
+    (void)hipGetLastError();
+    return fail(h, -2, "%s: %s for %d canvases of %zu bytes", fn, hipGetErrorString(e), count, 3 * canvas_plane_bytes(N));
+  }
+  canvases_free(h);
+  S.canv = N;
+  S.d_cwin = cwin;
+  S.canvas_wh.assign((size_t)2 * count, 0);
+  S.placed.assign((size_t)S.capacity, ian_canvas_placement{0, -1, 0, 0, 0});
+  S.ctab_shadow.assign((size_t)count * CANVAS_MAX_PLACED * 4, 0);
+  S.cdirty.assign((size_t)count, 0);
+  for (int c = 0; c < count; ++c)
+    for (int k = 0; k < CANVAS_MAX_PLACED; ++k) S.ctab_shadow[((size_t)c * CANVAS_MAX_PLACED + k) * 4] = -1;
+  return 0;
+}
+
+// the three planes of a picture of w x hgt between a packed array [3][hgt][w] and a canvas's rows of max_w bytes
+int canvas_copy(ian_handle* h, int canvas, int w, int hgt, unsigned char* packed, bool to_canvas, hipStream_t st) {
+  const SessionCanvases& C = h->sess.canv;
+  const bool dev = is_device_ptr(packed);
+  for (int c = 0; c < 3; ++c) {
+    unsigned char* cp = canvas_pixels(C, canvas) + (size_t)c * canvas_plane_bytes(C);
+    unsigned char* pp = packed + (size_t)c * hgt * w;
+    if (to_canvas)
+      HIPCHK(h, hipMemcpy2DAsync(cp, (size_t)C.max_w, pp, (size_t)w, (size_t)w, (size_t)hgt, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    else
+      HIPCHK(h, hipMemcpy2DAsync(pp, (size_t)w, cp, (size_t)C.max_w, (size_t)w, (size_t)hgt, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  }
+  return 0;
+}
+
+int canvas_put(ian_handle* h, int canvas, int w, int hgt, const uint8_t* pixels, void* stream) {
+  const char* fn = "ian_canvas_put";
+  int rc = canvas_need(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = canvas_check_id(h, fn, -1, canvas, false))) return rc;
+  if (!pixels) return fail(h, -1, "null pointer passed to %s", fn);
+  if (w < CANVAS_MIN_SIDE || w > S.canv.max_w || hgt < CANVAS_MIN_SIDE || hgt > S.canv.max_h)
+    return fail(h, -7, "%s: picture %d x %d outside %d x %d .. %d x %d", fn, w, hgt, CANVAS_MIN_SIDE, CANVAS_MIN_SIDE, S.canv.max_w, S.canv.max_h);
+  if (w & 3) return fail(h, -7, "%s: width %d is not a multiple of 4", fn, w);
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  if ((rc = canvas_copy(h, canvas, w, hgt, const_cast<uint8_t*>(pixels), true, st))) return rc;
+  for (size_t id = 0; id < S.placed.size(); ++id)   // the squares showed another picture; the sessions keep their 64x64 state
+    if (S.placed[id].canvas == canvas) S.placed[id].canvas = -1;
+  canvas_table_rebuild(h, canvas);
+  if ((rc = canvas_table_flush(h, st))) return rc;
+  S.canvas_wh[2 * canvas] = w;
+  S.canvas_wh[2 * canvas + 1] = hgt;
+  return session_rows_leave(h, st, is_device_ptr(pixels));
+}
+
+int canvas_read(ian_handle* h, int canvas, uint8_t* out, int32_t* wh, void* stream) {
+  const char* fn = "ian_canvas_read";
+  int rc = canvas_need(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = canvas_check_id(h, fn, -1, canvas, true))) return rc;
+  if (wh && is_device_ptr(wh)) return fail(h, -7, "%s: wh must be a host array", fn);
+  const int w = S.canvas_wh[2 * canvas], hgt = S.canvas_wh[2 * canvas + 1];
+  if (wh) { wh[0] = w; wh[1] = hgt; }
+  if (!out) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  if ((rc = canvas_copy(h, canvas, w, hgt, out, false, st))) return rc;
+  return session_rows_leave(h, st, is_device_ptr(out));
+}
+
+int canvas_placements(ian_handle* h, int canvas, ian_canvas_placement* out8, int32_t* count) {
+  const char* fn = "ian_canvas_placements";
+  int rc = canvas_need(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = canvas_check_id(h, fn, -1, canvas, false))) return rc;
+  if (!out8 || !count) return fail(h, -1, "null pointer passed to %s", fn);
+  int k = 0;
+  for (size_t id = 0; id < S.placed.size() && k < CANVAS_MAX_PLACED; ++id)
+    if (S.placed[id].canvas == canvas) {
+      out8[k] = S.placed[id];
+      out8[k++].session = (int32_t)id;
+    }
+  *count = k;
+  return 0;
+}
+
+// the box mean of n squares -> GIM, IM and the encoder's input, then the open every session call ends in; the sessions are placed
+int canvas_place_run(ian_handle* h, int n, const ian_canvas_placement* items, uint8_t* shown, hipStream_t st) {
+  auto& S = h->sess;
+  int rc = 0;
+  // d_tab: n ids (what the open's kernels index), then the n items
+  S.tab_shadow.resize((size_t)6 * n);
+  std::vector<int32_t> ids((size_t)n);
+  for (int i = 0; i < n; ++i) S.tab_shadow[i] = ids[i] = items[i].session;
+  memcpy(S.tab_shadow.data() + n, items, (size_t)n * sizeof(ian_canvas_placement));
+  HIPCHK(h, hipMemcpyAsync(S.d_tab, S.tab_shadow.data(), (size_t)6 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  Slot& xs = h->slots[h->desc.x_slot];
+  if ((rc = ensure_slot(h, h->desc.x_slot, n))) return rc;
+  HIPCHK(h, launch_canvas_place(S.canv, S.arr.pool, S.d_tab + n, S.d_tanh, xs.d, n, st));
+  std::vector<char> touched((size_t)S.canv.count, 0);
+  for (int i = 0; i < n; ++i) {
+    if (S.placed[items[i].session].canvas >= 0) touched[S.placed[items[i].session].canvas] = 1;   // a session that moves
+    S.placed[items[i].session] = items[i];
+    touched[items[i].canvas] = 1;
+  }
+  for (int c = 0; c < S.canv.count; ++c)
+    if (touched[c]) canvas_table_rebuild(h, c);
+  if ((rc = canvas_table_flush(h, st))) return rc;
+  return session_open_finish(h, n, ids.data(), shown, false, 0, st);
+}
+
+int canvas_place(ian_handle* h, int n, const ian_canvas_placement* items, uint8_t* shown, void* stream) {
+  const char* fn = "ian_canvas_place";
+  int rc = canvas_need(h, fn);
+  if (rc) return rc;
+  if ((rc = session_check(h, fn, n, items ? &items->session : nullptr, 5, false, false))) return rc;
+  auto& S = h->sess;
+  std::vector<int> load((size_t)S.canv.count, 0);   // sessions per canvas once every item is placed
+  for (const ian_canvas_placement& p : S.placed)
+    if (p.canvas >= 0) ++load[p.canvas];
+  for (int i = 0; i < n; ++i) {
+    const ian_canvas_placement& p = items[i];
+    if ((rc = canvas_check_id(h, fn, i, p.canvas, true))) return rc;
+    if (p.scale < 1 || p.scale > 16) return fail(h, -7, "%s: item %d: scale %d outside 1..16", fn, i, p.scale);
+    const int w = S.canvas_wh[2 * p.canvas], hgt = S.canvas_wh[2 * p.canvas + 1], side = 64 * p.scale;
+    if (p.x < 0 || p.y < 0 || p.x > w - side || p.y > hgt - side)
+      return fail(h, -7, "%s: item %d: square (%d,%d) + %d outside the %d x %d canvas", fn, i, p.x, p.y, side, w, hgt);
+    if (S.placed[p.session].canvas >= 0) --load[S.placed[p.session].canvas];
+  }
+  for (int i = 0; i < n; ++i)
+    if (++load[items[i].canvas] > CANVAS_MAX_PLACED)
+      return fail(h, -7, "%s: item %d: canvas %d already holds %d sessions", fn, i, items[i].canvas, CANVAS_MAX_PLACED);
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);
+  TotalTimer tt(h, st);
+  return canvas_place_run(h, n, items, shown, st);
+}
+
+// what ian_canvas_compose and ian_canvas_brush check about the windows, before anything is enqueued
+int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_window* w, int vw, int vh, const uint8_t* out) {
+  int rc = canvas_need(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: %d windows outside 1..%d", fn, n, BATCH_MAX);
+  if (!w || !out) return fail(h, -1, "null pointer passed to %s", fn);
+  if (is_device_ptr(w)) return fail(h, -7, "%s: the windows must be a host array", fn);
+  if (vw < 1 || vh < 1) return fail(h, -7, "%s: window %d x %d: both sizes must be at least 1", fn, vw, vh);
+  if (vw & 3) return fail(h, -7, "%s: window width %d is not a multiple of 4", fn, vw);
+  for (int i = 0; i < n; ++i) {
+    if ((rc = canvas_check_id(h, fn, i, w[i].canvas, true))) return rc;
+    const int cw = S.canvas_wh[2 * w[i].canvas], ch = S.canvas_wh[2 * w[i].canvas + 1];
+    if (w[i].x & 3) return fail(h, -7, "%s: item %d: window x %d is not a multiple of 4", fn, i, w[i].x);
+    if (w[i].x < 0 || w[i].y < 0 || w[i].x > cw - vw || w[i].y > ch - vh)
+      return fail(h, -7, "%s: item %d: window (%d,%d) + %d x %d outside the %d x %d canvas", fn, i, w[i].x, w[i].y, vw, vh, cw, ch);
+  }
+  return 0;
+}
+
+// the windows of n canvases into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, one whole picture over its own canvas
+int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st) {
+  auto& S = h->sess;
+  S.cwin_shadow.resize((size_t)3 * n);
+  memcpy(S.cwin_shadow.data(), w, (size_t)n * sizeof(ian_canvas_window));
+  HIPCHK(h, hipMemcpyAsync(S.d_cwin, S.cwin_shadow.data(), (size_t)n * sizeof(ian_canvas_window), hipMemcpyHostToDevice, st));
+  HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_cwin, vw, vh, d_out, n, st));
+  return 0;
+}
+
+int canvas_compose(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, uint8_t* out, void* stream) {
+  const char* fn = "ian_canvas_compose";
+  int rc = canvas_window_check(h, fn, n, w, vw, vh, out);
+  if (rc) return rc;
+  unsigned char* d_out = nullptr;
+  bool out_dev = false;
+  const size_t bytes = (size_t)n * 3 * (size_t)vh * (size_t)vw;
+  if ((rc = session_render_target(h, out, bytes, &d_out, &out_dev))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  if ((rc = canvas_compose_enqueue(h, n, w, vw, vh, d_out, st))) return rc;
+  if (!out_dev) HIPCHK(h, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+  return session_rows_leave(h, st, out_dev);
+}
+
+int canvas_commit(ian_handle* h, int canvas, uint8_t* shown, void* stream) {
+  const char* fn = "ian_canvas_commit";
+  int rc = canvas_need(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = canvas_check_id(h, fn, -1, canvas, true))) return rc;
+  std::vector<ian_canvas_placement> items;
+  for (size_t id = 0; id < S.placed.size(); ++id)
+    if (S.placed[id].canvas == canvas) {
+      items.push_back(S.placed[id]);
+      items.back().session = (int32_t)id;
+    }
+  if (items.empty()) return 0;   // nothing is placed: the compose is the picture itself
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);
+  TotalTimer tt(h, st);
+  const ian_canvas_window whole = {canvas, 0, 0};
+  if ((rc = canvas_compose_enqueue(h, 1, &whole, S.canvas_wh[2 * canvas], S.canvas_wh[2 * canvas + 1], nullptr, st))) return rc;
+  return canvas_place_run(h, (int)items.size(), items.data(), shown, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ian_sessions_reserve_canvas(ian_handle* h, int32_t count, int32_t max_w, int32_t max_h, int32_t feather) {
+  return h ? sessions_reserve_canvas(h, count, max_w, max_h, feather) : -1;
+}
+int ian_canvas_put(ian_handle* h, int32_t canvas, int32_t w, int32_t hgt, const uint8_t* pixels, void* stream) {
+  return h ? canvas_put(h, canvas, w, hgt, pixels, stream) : -1;
+}
+int ian_canvas_place(ian_handle* h, int32_t n, const ian_canvas_placement* items, uint8_t* shown, void* stream) {
+  return h ? canvas_place(h, n, items, shown, stream) : -1;
+}
+int ian_canvas_compose(ian_handle* h, int32_t n, const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
+  return h ? canvas_compose(h, n, windows, vw, vh, out, stream) : -1;
+}
+int ian_canvas_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, int32_t m,
+                     const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
+  if (!h) return -1;
+  if (!windows) return fail(h, -1, "null pointer passed to ian_canvas_brush");
+  return session_brush(h, n, events, shown, stream, false, nullptr, vw, vh, out, m, windows);
+}
+int ian_canvas_commit(ian_handle* h, int32_t canvas, uint8_t* shown, void* stream) {
+  return h ? canvas_commit(h, canvas, shown, stream) : -1;
+}
+int ian_canvas_read(ian_handle* h, int32_t canvas, uint8_t* out, int32_t wh[2], void* stream) {
+  return h ? canvas_read(h, canvas, out, wh, stream) : -1;
+}
+int ian_canvas_placements(ian_handle* h, int32_t canvas, ian_canvas_placement* out8, int32_t* count) {
+  return h ? canvas_placements(h, canvas, out8, count) : -1;
+}
+
+}  // extern "C"

@@ -83,6 +83,16 @@ void* slot_get(const void* base, size_t at) {
 }
 void slot_set(void* base, size_t at, void* p) { memcpy((char*)base + at, &p, sizeof p); }
 
+// canvases (ian_rt_canvas.inc, included after this file): what the session calls need of them.  All of it is a no-op in a pool without
+// the canvas reservation.
+void canvases_free(ian_handle* h);                                  // the arrays, the table, every placement
+int canvases_pool_resized(ian_handle* h);                           // ian_sessions_reserve: the placements of ids that left the pool go
+bool canvas_is_placed(const ian_handle* h, int id);
+void canvas_unplace(ian_handle* h, int id);                         // host side; the table's upload follows with canvas_table_flush
+int canvas_table_flush(ian_handle* h, hipStream_t st);
+int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_window* w, int vw, int vh, const uint8_t* out);
+int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st);
+
 bool sess_has(const SessionArrays& P, SessGroup g) {
   for (const SessColumn& c : SESS_COLUMNS)
     if (c.group == g) return slot_get(&P, c.at) != nullptr;
@@ -195,6 +205,7 @@ void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
 }
 // ian_sessions_reserve(0) and ian_destroy: w, radius (ian_sessions_set_blend) and dampen_thresh stay
 void sessions_free(ian_handle* h) {
+  canvases_free(h);
   for (SessGroup g : {SESS_HISTORY, SESS_LOCAL, SESS_HIRES, SESS_BASE}) sess_free_group(h->sess, g);
 }
 // the refusal of a call that needs the pool (SESS_BASE) or one of the other reservations
@@ -258,6 +269,7 @@ int sessions_reserve(ian_handle* h, int capacity) {
     S.has_src.resize(c, 0);
     S.local_flags.resize(c, 0);
     S.hist.resize(c);   // the surviving ids keep their histories: their rings moved with the rest
+    if ((rc = canvases_pool_resized(h))) return rc;
   }
   const bool had_table = S.d_tanh != nullptr;   // the table is uploaded once, when its buffer is new
   HIPCHK(h, scratch_build(S, SESS_BASE));
@@ -291,6 +303,8 @@ int sessions_reserve_hires(ian_handle* h, int scale) {
   auto& S = h->sess;
   if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (scale < 0 || scale > 16) return fail(h, -7, "%s: scale %d outside 0..16", fn, scale);
+  if (scale == 0 && S.canv.pix)   // the placements' FIELD and FIELD_KIND would go
+    return fail(h, -6, "%s: canvases are reserved: free them first (ian_sessions_reserve_canvas(0))", fn);
   HIPCHK(h, hipDeviceSynchronize());   // pending work may still read or write the rows that are freed
   h->last_pending = false;
   if (scale == S.arr.pool.scale) return 0;
@@ -529,6 +543,7 @@ int session_render_target(ian_handle* h, uint8_t* out, size_t bytes, unsigned ch
   return rc;
 }
 
+int session_open_finish(ian_handle* h, int n, const int32_t* ids, uint8_t* shown, bool host_in, int has_src, hipStream_t st);
 int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos, int source, uint8_t* shown, void* stream, bool hires) {
   const char* fn = hires ? "ian_session_open_hires" : "ian_session_open";
   int rc = session_check(h, fn, n, ids, 1, photos == nullptr, false);
@@ -537,10 +552,15 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
   auto& S = h->sess;
   if (hires && (rc = session_need(h, fn, SESS_HIRES))) return rc;
   if (hires && !photos) return fail(h, -1, "null pointer passed to %s", fn);
+  for (int i = 0; !photos && source == 1 && i < n; ++i)
+    if (canvas_is_placed(h, ids[i]))   // GIM := IM would bake the unfeathered 64x64 blend into the session
+      return fail(h, -7, "%s: item %d: session %d is placed on a canvas: commit the canvas instead (ian_canvas_commit)", fn, i, ids[i]);
   hipStream_t st = (hipStream_t)stream;
   session_enter(h, st);
   TotalTimer tt(h, st);
   if ((rc = session_upload_ids(h, n, ids, st))) return rc;
+  for (int i = 0; photos && i < n; ++i) canvas_unplace(h, ids[i]);   // a new photo: the session leaves its canvas
+  if (photos && (rc = canvas_table_flush(h, st))) return rc;
   const unsigned char* d_photos = photos;
   const bool host_in = photos && !is_device_ptr(photos);
   if (host_in && hires) {   // straight into the sessions' SRC rows: no staging of n * 3 * S * S bytes
@@ -561,13 +581,22 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
     if (!whole.empty() && (rc = session_render_enqueue(h, (int)whole.size(), whole.data(), Sz, Sz, nullptr, st))) return rc;
   }
   Slot& xs = h->slots[h->desc.x_slot];
-  Slot& zs = h->slots[h->desc.z_slot];
-  Slot& out = h->slots[h->desc.out_slot];
   if ((rc = ensure_slot(h, h->desc.x_slot, n))) return rc;
   if (hires)
     HIPCHK(h, launch_session_hires_open(d_photos, S.arr.pool, S.d_tab, S.d_tanh, xs.d, n, st));
   else
     HIPCHK(h, launch_session_open_in(d_photos, S.arr.pool, S.d_tab, source, S.d_tanh, xs.d, n, st));
+  return session_open_finish(h, n, ids, shown, host_in, photos ? (hires ? 1 : 0) : -1, st);
+}
+
+// Every open from here on: the input kernel has written GIM, IM and the encoder's input rows of sessions `ids` (device: S.d_tab[0..n));
+// encode, decode, store, the UMASK clear, what the host keeps per session, shown down.  has_src: 1 / 0 sets the sessions' "SRC
+// holds a photo" flag, -1 leaves it.
+int session_open_finish(ian_handle* h, int n, const int32_t* ids, uint8_t* shown, bool host_in, int has_src, hipStream_t st) {
+  auto& S = h->sess;
+  int rc = 0;
+  Slot& zs = h->slots[h->desc.z_slot];
+  Slot& out = h->slots[h->desc.out_slot];
   h->slot_stale[h->desc.x_slot] = 0;
   // the very segments ian_encode and ian_decode_u8 run at this batch: Z and RECON are theirs bit for bit
   if ((rc = run_segment(h, IAN_SEG_ENC, n, st))) return rc;
@@ -581,7 +610,7 @@ int session_open(ian_handle* h, int n, const int32_t* ids, const uint8_t* photos
     S.opened[ids[i]] = 1;
     ++S.version[ids[i]];
     session_history_note(S, ids[i], true);
-    if (photos) S.has_src[ids[i]] = hires ? 1 : 0;   // a 64x64 photo leaves nothing at full resolution to edit
+    if (has_src >= 0) S.has_src[ids[i]] = (char)has_src;   // a 64x64 photo leaves nothing at full resolution to edit
   }
   return session_finish(h, n, shown, shown_dev, host_in, st);
 }
@@ -750,9 +779,12 @@ int session_history(ian_handle* h, int id, int32_t* out) {
 
 // with_view: ian_session_brush_view: after the brush, in the same submission, window i of session views[i].session (== ev[i].session)
 // -> out, and one synchronisation for both results.
+// windows given: ian_canvas_brush: after the brush, in the same submission, m windows of canvases -> win, likewise.
 int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream, bool with_view = false,
-                  const ian_session_view* views = nullptr, int vw = 0, int vh = 0, uint8_t* win = nullptr) {
-  const char* fn = with_view ? "ian_session_brush_view" : "ian_session_brush";
+                  const ian_session_view* views = nullptr, int vw = 0, int vh = 0, uint8_t* win = nullptr, int m = 0,
+                  const ian_canvas_window* windows = nullptr) {
+  const bool with_canvas = !with_view && (windows != nullptr || m != 0);
+  const char* fn = with_canvas ? "ian_canvas_brush" : (with_view ? "ian_session_brush_view" : "ian_session_brush");
   static_assert(sizeof(ian_session_event) == 11 * sizeof(int32_t), "ian_session_event is 11 words");
   int rc = session_check(h, fn, n, ev ? &ev->session : nullptr, 11, true, true);
   if (rc) return rc;
@@ -767,11 +799,10 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
   auto& S = h->sess;
   unsigned char* d_out = nullptr;
   bool out_dev = false;
-  const size_t out_bytes = (size_t)n * 3 * (size_t)(vh > 0 ? vh : 0) * (size_t)(vw > 0 ? vw : 0);
-  if (with_view) {
-    if ((rc = session_view_check(h, fn, n, views, vw, vh, win, ev))) return rc;
-    if ((rc = session_render_target(h, win, out_bytes, &d_out, &out_dev))) return rc;
-  }
+  const size_t out_bytes = (size_t)(with_canvas ? (m > 0 ? m : 0) : n) * 3 * (size_t)(vh > 0 ? vh : 0) * (size_t)(vw > 0 ? vw : 0);
+  if (with_view && (rc = session_view_check(h, fn, n, views, vw, vh, win, ev))) return rc;
+  if (with_canvas && (rc = canvas_window_check(h, fn, m, windows, vw, vh, win))) return rc;
+  if ((with_view || with_canvas) && (rc = session_render_target(h, win, out_bytes, &d_out, &out_dev))) return rc;
   const int pass = h->opt.brush_pass;
   bool hit = n <= pass && S.res_valid && (int)S.res_ids.size() == n && getenv("IAN_NO_DEC_CACHE") == nullptr;
   for (int i = 0; hit && i < n; ++i) hit = S.res_ids[i] == ev[i].session && S.res_ver[i] == S.version[ev[i].session];
@@ -811,7 +842,8 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
     session_history_note(S, ev[i].session, false);
   }
   if (with_view && (rc = session_render_enqueue(h, n, views, vw, vh, d_out, st))) return rc;
-  if ((rc = session_finish(h, n, shown, shown_dev, false, st, with_view && !out_dev ? win : nullptr, out_bytes))) return rc;
+  if (with_canvas && (rc = canvas_compose_enqueue(h, m, windows, vw, vh, d_out, st))) return rc;
+  if ((rc = session_finish(h, n, shown, shown_dev, false, st, (with_view || with_canvas) && !out_dev ? win : nullptr, out_bytes))) return rc;
   if (n <= pass) {   // one pass: the resident activations belong to these sessions' new latents
     S.res_ids.resize(n);
     S.res_ver.resize(n);
@@ -981,6 +1013,8 @@ int session_load(ian_handle* h, int n, const int32_t* ids, const ian_session_met
   if (!dev && (rc = session_record_stage(h, n, bb, &per_pass))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = session_rows_enter(h, st))) return rc;
+  for (int i = 0; i < n; ++i) canvas_unplace(h, ids[i]);   // another session's state: not where this id was placed
+  if ((rc = canvas_table_flush(h, st))) return rc;
   S.rtab_shadow.resize((size_t)4 * n);
   for (int i = 0; i < n; ++i) {
     int32_t* t = S.rtab_shadow.data() + (size_t)4 * i;

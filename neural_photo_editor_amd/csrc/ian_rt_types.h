@@ -334,6 +334,16 @@ struct ian_handle {
     // saved sessions (ian_session_save / ian_session_load)
     std::vector<int32_t> rtab_shadow;    // upload source of d_rtab
     size_t stage_cap = 0;
+    // canvases (ian_sessions_reserve_canvas, ian_rt_canvas.inc): the device arrays, per canvas the size of its picture (0 x 0: never
+    // put), per session where it is placed (canvas -1: nowhere; sized with the pool while canvases exist, empty otherwise), and the
+    // host's copy of the device table (canv.table), from which a canvas's 8 entries are uploaded whenever they change
+    SessionCanvases canv = {};
+    std::vector<int32_t> canvas_wh;
+    std::vector<ian_canvas_placement> placed;
+    std::vector<int32_t> ctab_shadow;
+    std::vector<char> cdirty;            // per canvas: the device table lags behind ctab_shadow
+    int* d_cwin = nullptr;               // per ian_canvas_compose / _brush / _commit call n ian_canvas_window records
+    std::vector<int32_t> cwin_shadow;    // upload source of d_cwin
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

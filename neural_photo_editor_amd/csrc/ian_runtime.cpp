@@ -37,5 +37,6 @@ using namespace ian;
 #include "ian_rt_backward.inc" // latent-brush backward sweep
 #include "ian_rt_edit.inc"     // interactive loop: streams, captured graphs, decoder cache, photo blend
 #include "ian_rt_session.inc"  // device-resident edit sessions: pool, open / set_latent / brush / read (extern "C": ian_session_*)
+#include "ian_rt_canvas.inc"   // canvases: whole photos, sessions placed on them, the composed result (extern "C": ian_canvas_*)
 #include "ian_rt_api.inc"      // extern "C": include/ian.h
 #include "ian_rt_layer.inc"    // extern "C": ian_layer_* of include/ian_train.h

@@ -9,7 +9,9 @@
 //   session_local_set_kernel   local edits: a session's UMASK := 0 (every open) and its LOCAL flags (ian_session_local)
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
-//   session_history_save_kernel / _move_kernel   undo history: a session's Z and UMASK rows to and from its ring of saved states
+//   canvas_place_kernel        canvases: the exact box mean of a square of a whole photo -> GIM, IM, encoder input (any byte alignment)
+//   canvas_compose_kernel      a window of a whole photo: the canvas plus every placed session's feathered edit field
+//   session_history_save_kernel / _move_kernel  undo history: a session's Z and UMASK rows to and from its ring of saved states
 //   session_pack_kernel / session_unpack_kernel  saved sessions: every row of a session, its ring included, to and from one record
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
 #include <cstring>
@@ -553,6 +555,187 @@ hipError_t launch_session_render(const SessionPool& P, const int* views, int vw,
     return hipErrorInvalidValue;
   if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(session_render_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, P, views, vw, vh, out);
+  return hipGetLastError();
+}
+
+// ---- canvases (the arithmetic is npe_ops.canvas_crop_mean / canvas_ramp / canvas_compose) ------------------------------
+// A canvas is a whole photo of w x hgt pixels in rows of C.max_w bytes; a session is placed on it as a square of 64 * s pixels at
+// (ox, oy), s per placement.
+
+// place, input side: session_hires_open_kernel's job on a square of a canvas.  grid (64, 3, n): one workgroup per row of one channel
+// of the 64x64 picture, i.e. s canvas rows of 64 * s bytes starting at byte ox of ANY alignment.  The loads stay aligned uchar4: lane q
+// owns the uchar4 at byte (ox & ~3) + 4q of each row, 16s lanes when ox % 4 == 0 and 16s + 1 otherwise (257 at s = 16: the lanes
+// loop), and the bytes that fall outside the square are masked out of the sums.  The aligned span ends at most at the next
+// multiple of 4 after ox + 64s <= w, and w % 4 == 0: inside the picture's row.  No SRC copy; GIM, IM and x as the open kernels write them.
+__global__ __launch_bounds__(256) void canvas_place_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ items,
+                                                           const float* __restrict__ table, float* __restrict__ x) {
+  __shared__ float tab[256];
+  __shared__ int sum[64];
+  for (int j = threadIdx.x; j < 256; j += blockDim.x) tab[j] = table[j];
+  if (threadIdx.x < 64) sum[threadIdx.x] = 0;
+  __syncthreads();
+  const int gy = blockIdx.x, c = blockIdx.y, i = blockIdx.z;
+  const int id = items[5 * i], cv = items[5 * i + 1], ox = items[5 * i + 2], oy = items[5 * i + 3], s = items[5 * i + 4];
+  const int S = 64 * s, lead = ox & 3, nq = (lead + S + 3) >> 2;
+  const unsigned char* in = C.pix + (((size_t)cv * 3 + c) * C.max_h + (size_t)oy + (size_t)gy * s) * C.max_w + (ox - lead);
+  for (int q = threadIdx.x; q < nq; q += blockDim.x) {
+    int acc[4] = {0, 0, 0, 0};
+    for (int r = 0; r < s; ++r) {
+      const uchar4 v = *reinterpret_cast<const uchar4*>(in + (size_t)r * C.max_w + 4 * q);
+      acc[0] += v.x;
+      acc[1] += v.y;
+      acc[2] += v.z;
+      acc[3] += v.w;
+    }
+    int bin = -1, t = 0;   // bytes of one 64x64 pixel are summed in the lane first: one LDS add per pixel touched
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int u = 4 * q + e - lead;   // the byte's column in the square
+      if (u < 0 || u >= S) continue;
+      const int b = u / s;
+      if (b != bin) {
+        if (bin >= 0) atomicAdd(&sum[bin], t);
+        bin = b;
+        t = 0;
+      }
+      t += acc[e];
+    }
+    if (bin >= 0) atomicAdd(&sum[bin], t);
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    const int e = threadIdx.x * 4, d = s * s, half = d / 2;
+    uchar4 v;
+    v.x = (unsigned char)((sum[e] + half) / d);
+    v.y = (unsigned char)((sum[e + 1] + half) / d);
+    v.z = (unsigned char)((sum[e + 2] + half) / d);
+    v.w = (unsigned char)((sum[e + 3] + half) / d);
+    const size_t o = (size_t)c * 64 * 64 + gy * 64 + e;
+    *reinterpret_cast<uchar4*>(P.gim + (size_t)id * S_IMG + o) = v;
+    *reinterpret_cast<uchar4*>(P.im + (size_t)id * S_IMG + o) = v;
+    *reinterpret_cast<float4*>(x + (size_t)i * S_IMG + o) = make_float4(tab[v.x], tab[v.y], tab[v.z], tab[v.w]);
+  }
+}
+static bool canvases_ok(const SessionCanvases& C) {
+  return C.pix && C.table && C.count >= 1 && C.max_w >= 64 && C.max_h >= 64 && (C.max_w & 3) == 0 && C.feather >= 0 && C.feather <= 16 &&
+         (reinterpret_cast<uintptr_t>(C.pix) & 3) == 0;
+}
+hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, const int* items, const float* table, float* x, int n,
+                               hipStream_t s) {
+  if (n < 1 || n > 65535 || !canvases_ok(C) || !P.gim || !P.im || !items || !table || !x) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(canvas_place_kernel, dim3(64, 3, n), dim3(256), 0, s, C, P, items, table, x);
+  return hipGetLastError();
+}
+
+// canvas_ramp for one square coordinate u: f2s = 2 * feather * s (0: no feather)
+__device__ __forceinline__ float canvas_ramp1(int u, int S, int f2s) {
+  if (f2s == 0) return 1.0f;
+  const int d = min(u, S - 1 - u);
+  return fminf(1.0f, (float)(2 * d + 1) / (float)f2s);
+}
+
+// compose.  session_render_kernel's shape: grid (bands of RENDER_BAND output rows, 3, n), a lane owns 4 consecutive output bytes: one
+// uchar4 load of the canvas, one uchar4 store.  Lane 0 reads the canvas's placement table and keeps the placements whose squares meet
+// the band (a test that is uniform over the workgroup); each kept placement's tapped field rows -- at most RENDER_BAND + 2 rows of
+// 64 floats -- go to LDS once, 20 KB for 8; the lanes then walk their pixels with the placements in the inner loop, so acc lives in
+// registers.  A band that meets no square is a plain copy.  All arithmetic is float32 with contraction off, in canvas_compose's order.
+// out == nullptr: the window is the whole picture, written over the canvas itself (commit): every lane stores exactly the bytes it
+// loaded and the fields live elsewhere, so overlapping squares are safe in place; neither pointer is __restrict__.
+struct CanvasKept {
+  int ox, oy, s, kind, fr0;
+};
+__global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ windows, int vw, int vh,
+                                                             unsigned char* out) {
+  __shared__ float f[CANVAS_MAX_PLACED][(RENDER_BAND + 2) * 64];
+  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
+  __shared__ int frow_id[CANVAS_MAX_PLACED], frow_n[CANVAS_MAX_PLACED];
+  __shared__ int nkept;
+  const int c = blockIdx.y, i = blockIdx.z;
+  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
+  const int y0 = blockIdx.x * RENDER_BAND, rows = min(RENDER_BAND, vh - y0);
+  const int Y0 = vy + y0, Y1 = Y0 + rows - 1;   // the band's rows on the canvas, both inclusive
+  if (threadIdx.x == 0) {
+    int nk = 0;
+    const int* tb = C.table + (size_t)cv * (CANVAS_MAX_PLACED * 4);
+    for (int k = 0; k < CANVAS_MAX_PLACED; ++k) {
+      const int id = tb[4 * k], ox = tb[4 * k + 1], oy = tb[4 * k + 2], s = tb[4 * k + 3];
+      if (id < 0) break;
+      const int S = 64 * s;
+      if (s < 1 || s > 16 || Y1 < oy || Y0 > oy + S - 1 || vx + vw - 1 < ox || vx > ox + S - 1) continue;
+      int fr0, fr1, unused;
+      float tunused;
+      hires_taps(max(Y0, oy) - oy, s, fr0, unused, tunused);
+      hires_taps(min(Y1, oy + S - 1) - oy, s, unused, fr1, tunused);
+      kept[nk] = CanvasKept{ox, oy, s, P.kind[id], fr0};
+      frow_id[nk] = id;
+      frow_n[nk] = min(fr1 - fr0 + 1, RENDER_BAND + 2);
+      ++nk;
+    }
+    nkept = nk;
+  }
+  __syncthreads();
+  const int nk = nkept;
+  for (int k = 0; k < nk; ++k) {
+    const float* frow = P.field + ((size_t)frow_id[k] * 3 + c) * (64 * 64) + kept[k].fr0 * 64;
+    const int cnt = frow_n[k] * 64;
+    for (int j = threadIdx.x; j < cnt; j += 256) f[k][j] = frow[j];
+  }
+  __syncthreads();
+  const size_t plane = ((size_t)cv * 3 + c) * C.max_h * C.max_w;
+  const unsigned char* src = C.pix + plane;
+  unsigned char* dst = out ? out + ((size_t)i * 3 + c) * vh * vw : C.pix + plane;
+  const int dstride = out ? vw : C.max_w;
+  const int L = vw >> 2;
+  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
+    const int ry = idx / L, cx = (idx - ry * L) * 4;
+    const int Y = Y0 + ry, X = vx + cx;
+    const uchar4 pv = *reinterpret_cast<const uchar4*>(src + (size_t)Y * C.max_w + X);
+    float acc[4] = {(float)pv.x, (float)pv.y, (float)pv.z, (float)pv.w};
+    for (int k = 0; k < nk; ++k) {
+      const CanvasKept q = kept[k];
+      const int S = 64 * q.s, uy = Y - q.oy;
+      if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
+      const int f2s = 2 * C.feather * q.s;
+      int r0, r1;
+      float ty;
+      hires_taps(uy, q.s, r0, r1, ty);
+      const float* top = f[k] + (r0 - q.fr0) * 64;
+      const float* bot = f[k] + (r1 - q.fr0) * 64;
+      const float wy = canvas_ramp1(uy, S, f2s);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ux = X + e - q.ox;
+        if (ux < 0 || ux >= S) continue;
+        int c0, c1;
+        float tx;
+        hires_taps(ux, q.s, c0, c1, tx);
+        const float a0 = top[c0], a1 = bot[c0];
+        const float t = a0 + tx * (top[c1] - a0);
+        const float b = a1 + tx * (bot[c1] - a1);
+        const float v = t + ty * (b - t);
+        const float w = wy * canvas_ramp1(ux, S, f2s);
+        if (q.kind == 0) {
+          acc[e] = acc[e] + (127.5f * v) * w;
+        } else {
+          const float tv = 127.5f * (v + 1.0f);
+          acc[e] = w == 1.0f ? tv : acc[e] + (tv - acc[e]) * w;
+        }
+      }
+    }
+    uchar4 o;
+    o.x = (unsigned char)fminf(fmaxf(rintf(acc[0]), 0.0f), 255.0f);
+    o.y = (unsigned char)fminf(fmaxf(rintf(acc[1]), 0.0f), 255.0f);
+    o.z = (unsigned char)fminf(fmaxf(rintf(acc[2]), 0.0f), 255.0f);
+    o.w = (unsigned char)fminf(fmaxf(rintf(acc[3]), 0.0f), 255.0f);
+    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) = o;
+  }
+}
+hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, unsigned char* out,
+                                 int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || !canvases_ok(C) || !P.field || !P.kind || !windows || vw < 4 || (vw & 3) || vh < 1 || vw > C.max_w || vh > C.max_h)
+    return hipErrorInvalidValue;
+  if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(canvas_compose_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, C, P, windows, vw, vh, out);
   return hipGetLastError();
 }
 

@@ -49,6 +49,8 @@ EXPORTS = (
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
     "ian_session_record_info", "ian_session_save", "ian_session_load",
+    "ian_sessions_reserve_canvas", "ian_canvas_put", "ian_canvas_place", "ian_canvas_compose", "ian_canvas_brush", "ian_canvas_commit",
+    "ian_canvas_read", "ian_canvas_placements",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -128,6 +130,14 @@ def load_library():
     lib.ian_session_record_info.argtypes = [vp, C.POINTER(SessionMeta), fp, fp]
     lib.ian_session_save.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_load.argtypes = [vp, i32, fp, fp, fp, vp]
+    lib.ian_sessions_reserve_canvas.argtypes = [vp, i32, i32, i32, i32]
+    lib.ian_canvas_put.argtypes = [vp, i32, i32, i32, fp, vp]
+    lib.ian_canvas_place.argtypes = [vp, i32, C.POINTER(CanvasPlacement), fp, vp]
+    lib.ian_canvas_compose.argtypes = [vp, i32, C.POINTER(CanvasWindow), i32, i32, fp, vp]
+    lib.ian_canvas_brush.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, i32, C.POINTER(CanvasWindow), i32, i32, fp, vp]
+    lib.ian_canvas_commit.argtypes = [vp, i32, fp, vp]
+    lib.ian_canvas_read.argtypes = [vp, i32, fp, fp, vp]
+    lib.ian_canvas_placements.argtypes = [vp, i32, C.POINTER(CanvasPlacement), fp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -177,6 +187,19 @@ class SessionEvent(C.Structure):
 class SessionView(C.Structure):
     """ian_session_view (include/ian.h): one window of a full-resolution session (ian_session_render / ian_session_brush_view)."""
     _fields_ = [("session", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+class CanvasPlacement(C.Structure):
+    """ian_canvas_placement (include/ian.h): one session placed on a canvas as a square of 64 * scale pixels at (x, y)."""
+    _fields_ = [("session", C.c_int32), ("canvas", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("scale", C.c_int32)]
+
+
+class CanvasWindow(C.Structure):
+    """ian_canvas_window (include/ian.h): one window of a canvas (ian_canvas_compose / ian_canvas_brush)."""
+    _fields_ = [("canvas", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+CANVAS_MAX_PLACED = 8               # IAN_CANVAS_MAX_PLACED
 
 
 class SessionMeta(C.Structure):
@@ -426,6 +449,49 @@ class Handle:
     def session_load(self, ids, meta, body, stream=None):
         """ian_session_load; the arguments of session_save, read instead of written."""
         self._check(self.lib.ian_session_load(self._h, len(ids), _ptr(ids), _ptr(meta), _ptr(body), C.c_void_p(stream or 0)))
+
+    # ---- canvases (ian_sessions_reserve_canvas, ian_canvas_*) ----
+    def sessions_reserve_canvas(self, count, max_w=0, max_h=0, feather=0):
+        self._check(self.lib.ian_sessions_reserve_canvas(self._h, int(count), int(max_w), int(max_h), int(feather)))
+
+    def canvas_put(self, canvas, pixels, stream=None):
+        """ian_canvas_put; pixels u8[3,hgt,w], a contiguous numpy array or a device tensor."""
+        hgt, w = int(pixels.shape[1]), int(pixels.shape[2])
+        self._check(self.lib.ian_canvas_put(self._h, int(canvas), w, hgt, _ptr(pixels), C.c_void_p(stream or 0)))
+
+    def canvas_place(self, items, shown=None, stream=None):
+        """ian_canvas_place; items = a ctypes array of CanvasPlacement (n = its length), shown u8[n,3,64,64] or None."""
+        self._check(self.lib.ian_canvas_place(self._h, len(items), items, _ptr(shown) if shown is not None else C.c_void_p(0),
+                                              C.c_void_p(stream or 0)))
+
+    def canvas_compose(self, windows, vw, vh, out, stream=None):
+        """ian_canvas_compose; windows = a ctypes array of CanvasWindow (n = its length), out u8[n,3,vh,vw]."""
+        self._check(self.lib.ian_canvas_compose(self._h, len(windows), windows, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def canvas_brush(self, events, windows, vw, vh, out, shown=None, stream=None):
+        """ian_canvas_brush; events = a ctypes array of SessionEvent, windows = one of CanvasWindow (m = its length), out u8[m,3,vh,vw]."""
+        self._check(self.lib.ian_canvas_brush(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
+                                              len(windows), windows, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def canvas_commit(self, canvas, shown=None, stream=None):
+        """ian_canvas_commit; shown u8[k,3,64,64] for the k sessions placed on the canvas, or None."""
+        self._check(self.lib.ian_canvas_commit(self._h, int(canvas), _ptr(shown) if shown is not None else C.c_void_p(0),
+                                               C.c_void_p(stream or 0)))
+
+    def canvas_read(self, canvas, stream=None):
+        """ian_canvas_read -> the stored picture of one canvas, u8 (3,hgt,w): two calls, the size first."""
+        wh = np.zeros(2, np.int32)
+        self._check(self.lib.ian_canvas_read(self._h, int(canvas), C.c_void_p(0), _ptr(wh), C.c_void_p(stream or 0)))
+        out = np.empty((3, int(wh[1]), int(wh[0])), np.uint8)
+        self._check(self.lib.ian_canvas_read(self._h, int(canvas), _ptr(out), _ptr(wh), C.c_void_p(stream or 0)))
+        return out
+
+    def canvas_placements(self, canvas):
+        """ian_canvas_placements -> [(session, x, y, scale)] of one canvas in ascending session id; host only."""
+        out = (CanvasPlacement * CANVAS_MAX_PLACED)()
+        count = np.zeros(1, np.int32)
+        self._check(self.lib.ian_canvas_placements(self._h, int(canvas), out, _ptr(count)))
+        return [(p.session, p.x, p.y, p.scale) for p in out[:int(count[0])]]
 
     def session_read(self, sid, what, stream=None, scale=0):
         code, dtype, shape = SESSION_FIELDS[what]

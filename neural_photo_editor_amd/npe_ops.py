@@ -195,6 +195,96 @@ def hires_render(src, field, kind, s, vx, vy, vw, vh):
     return np.uint8(np.clip(np.rint(q), 0, 255))
 
 
+# ---- canvases (ian_sessions_reserve_canvas / ian_canvas_*, include/ian.h) ----------------------------------------------
+# A canvas is a whole photo, uint8 (3, H, W); a session is placed on it as a square of 64*s pixels a side at pixel offset (ox, oy), each
+# placement with its own scale s.  The reference has no counterpart, so these three functions ARE the specification, as hires_* are:
+# float32, every operation rounded on its own, and the device (kernels_session.hip) matches them bit for bit.
+CANVAS_MAX_PLACED = 8
+CANVAS_MAX_FEATHER = 16
+
+
+def _canvas_square(canvas, ox, oy, s):
+    s = _hires_scale(s)
+    canvas = np.asarray(canvas)
+    if canvas.dtype != np.uint8 or canvas.ndim != 3 or canvas.shape[0] != 3:
+        raise ValueError("a canvas is uint8 (3,H,W), got %s %s" % (canvas.dtype, canvas.shape))
+    if int(ox) != ox or int(oy) != oy:
+        raise ValueError("a square's offset is a pair of integers, got (%r,%r)" % (ox, oy))
+    ox, oy, S = int(ox), int(oy), 64 * s
+    if ox < 0 or oy < 0 or ox + S > canvas.shape[2] or oy + S > canvas.shape[1]:
+        raise ValueError("square (%d,%d) + %d outside the %d x %d canvas" % (ox, oy, S, canvas.shape[2], canvas.shape[1]))
+    return canvas, ox, oy, s
+
+
+def canvas_crop_mean(canvas, ox, oy, s):
+    """The 64x64 picture a session placed at (ox, oy) with scale s starts from: hires_downsample of canvas[:, oy:oy+64s, ox:ox+64s]."""
+    canvas, ox, oy, s = _canvas_square(canvas, ox, oy, s)
+    return hires_downsample(np.ascontiguousarray(canvas[:, oy:oy + 64 * s, ox:ox + 64 * s]), s)
+
+
+def canvas_ramp(s, f, lo, cnt):
+    """The feather along one axis of a square of scale s, for square coordinates u = lo .. lo+cnt-1: 1.0f everywhere at f = 0, otherwise
+    d = min(u, 64s-1-u) and r = min(1.0f, float32(2d+1) / float32(2*f*s)) (one float32 division).  f is the feather width in field
+    pixels, 0..16; r == 1 exactly for f*s <= u <= 64s-1-f*s.  A pixel's weight is ry * rx, one float32 product.  -> float32 (cnt,)"""
+    s = _hires_scale(s)
+    if int(f) != f or not 0 <= int(f) <= CANVAS_MAX_FEATHER:
+        raise ValueError("feather must be an integer in 0..%d, got %r" % (CANVAS_MAX_FEATHER, f))
+    f = int(f)
+    u = np.arange(int(lo), int(lo) + int(cnt), dtype=np.int64)
+    if u.size and (u[0] < 0 or u[-1] > 64 * s - 1):
+        raise ValueError("coordinates %d..%d outside the square of %d pixels" % (u[0], u[-1], 64 * s))
+    if f == 0:
+        return np.ones(u.shape, np.float32)
+    d = np.minimum(u, 64 * s - 1 - u)
+    return np.minimum(np.float32(1.0), np.float32(2 * d + 1) / np.float32(2 * f * s))
+
+
+def canvas_compose(canvas, placed, f, vx, vy, vw, vh):
+    """Window (vx, vy, vw, vh) of a canvas with its placed sessions' edits on top -> uint8 (3, vh, vw).  placed = [(ox, oy, s, FIELD,
+    kind), ...] in ascending session id; FIELD float32 (3,64,64) and kind as ian_session_read gives them.  Per pixel and channel
+    acc = float32(canvas byte); then, for every placement whose square covers the pixel, in list order: v = the bilinear sample of
+    FIELD at square coordinates (X-ox, Y-oy) with hires_render's expressions in hires_render's order, w = ry * rx (canvas_ramp), and
+      kind 0:  acc = acc + (127.5f*v)*w
+      kind 1:  t = 127.5f*(v + 1.0f);  acc = t where w == 1.0f, elsewhere acc = acc + (t - acc)*w
+    out = uint8(clip(rint(acc), 0, 255)), ties to even.  Zero fields return the canvas bytes; in the core of a lone placement
+    (w == 1) the result is hires_render(crop, FIELD, kind, s, ...) byte for byte."""
+    canvas = np.asarray(canvas)
+    if canvas.dtype != np.uint8 or canvas.ndim != 3 or canvas.shape[0] != 3:
+        raise ValueError("a canvas is uint8 (3,H,W), got %s %s" % (canvas.dtype, canvas.shape))
+    H, W = canvas.shape[1:]
+    vx, vy, vw, vh = int(vx), int(vy), int(vw), int(vh)
+    if vw < 1 or vh < 1 or vx < 0 or vy < 0 or vx + vw > W or vy + vh > H:
+        raise ValueError("window (%d,%d) + %d x %d outside the %d x %d canvas" % (vx, vy, vw, vh, W, H))
+    if len(placed) > CANVAS_MAX_PLACED:
+        raise ValueError("a canvas holds at most %d placements, got %d" % (CANVAS_MAX_PLACED, len(placed)))
+    acc = np.float32(canvas[:, vy:vy + vh, vx:vx + vw])
+    for (ox, oy, s, field, kind) in placed:
+        _, ox, oy, s = _canvas_square(canvas, ox, oy, s)
+        if kind not in (0, 1):
+            raise ValueError("kind must be 0 (photo plus field) or 1 (plain sample), got %r" % (kind,))
+        S = 64 * s
+        x0, x1, y0, y1 = max(vx, ox), min(vx + vw, ox + S), max(vy, oy), min(vy + vh, oy + S)
+        if x0 >= x1 or y0 >= y1:
+            continue
+        F = np.asarray(field, np.float32)
+        c0, c1, tx = hires_axis_taps(s, x0 - ox, x1 - x0)
+        r0, r1, ty = hires_axis_taps(s, y0 - oy, y1 - y0)
+        A = F[:, :, c0]
+        rows = A + tx * (F[:, :, c1] - A)
+        top = rows[:, r0]
+        v = top + ty[None, :, None] * (rows[:, r1] - top)
+        w = canvas_ramp(s, f, y0 - oy, y1 - y0)[:, None] * canvas_ramp(s, f, x0 - ox, x1 - x0)[None, :]
+        part = acc[:, y0 - vy:y1 - vy, x0 - vx:x1 - vx]
+        if kind == 0:
+            new = part + (np.float32(127.5) * v) * w
+        else:
+            t = np.float32(127.5) * (v + np.float32(1.0))
+            new = np.where(w == np.float32(1.0), t, part + (t - part) * w)
+        assert new.dtype == np.float32 and w.dtype == np.float32
+        acc[:, y0 - vy:y1 - vy, x0 - vx:x1 - vx] = new
+    return np.uint8(np.clip(np.rint(acc), 0, 255))
+
+
 # ---- local edits (ian_sessions_reserve_local / ian_session_local, include/ian.h; DESIGN.md 4.4) -------------------------------------
 # NPE.py declares USER_MASK "currently not implemented" (NPE.py:58-59, :221), offers gk (NPE.py:167-175) for "changes to MASK ... more
 # localized to the brush location" and dampen (NPE.py:184-189) as a commented-out alternative for D (NPE.py:227, :298).  These four

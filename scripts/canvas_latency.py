@@ -1,0 +1,139 @@
+"""Canvases: what a composed window costs.  On a 2048 x 1536 canvas with 1 and 8 placed sessions (scale 4, overlapping in a row, every
+one painted: kind 0 with a non-zero field), for a 256 x 256 window inside the squares and for the whole canvas:
+  compose_device  ian_canvas_compose into a DEVICE buffer, --calls calls back to back and one device synchronisation: microseconds per
+                  call and achieved GB/s against the bytes the kernel has to move, 2 * 3 * vw * vh (one uchar4 load of the canvas and
+                  one uchar4 store per lane; the staged field rows are noise next to that);
+  compose_host    EditSessions.compose (host result: the same plus the device -> host copy of 3 * vw * vh bytes), median;
+  brush / brush_compose   EditSessions.paint of one placed session without and with the window: the price of the window inside the
+                  event's submission, medians.
+The one comparison with something older (`against_render`): one placement at scale 16 and feather 0 composed over a 1024 x 1024 window,
+against ian_session_render of a 1024 x 1024 picture (scale 16) in the same run, both into device buffers, alternating: the two move
+the same bytes.
+usage (GPU box): python scripts/canvas_latency.py [--calls 200] [--repeats 3] [--out FILE]
+Medians over --calls calls after warm-up, repeated --repeats times; reported are the median of the repeats and their spread
+(max - min) / median.  Prints one JSON line and, with --out, writes it there."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from neural_photo_editor_amd import IAN, api, synthetic as O  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CW, CH = 2048, 1536
+
+
+def compose_bytes(n, vw, vh):
+    """Device bytes of one compose call: the canvas read once, the window written once."""
+    return 2 * 3 * vw * vh * n
+
+
+def median_us(fn, calls, warmup=10):
+    for _ in range(warmup):
+        fn()
+    lat = []
+    for _ in range(calls):
+        t = time.perf_counter()
+        fn()
+        lat.append((time.perf_counter() - t) * 1e6)
+    return float(np.median(lat))
+
+
+def stat(v):
+    med = float(np.median(v))
+    return {"p50_us": round(med, 2), "spread": round((max(v) - min(v)) / med, 4), "repeats_us": [round(t, 2) for t in v]}
+
+
+def device_us(call, calls, repeats):
+    """`call` enqueues one launch into a device buffer: microseconds per call over `calls` calls and one synchronisation."""
+    import torch
+
+    def burst():
+        for _ in range(calls):
+            call()
+        torch.cuda.synchronize()
+
+    out = []
+    for _ in range(repeats):
+        burst()
+        t = time.perf_counter()
+        burst()
+        out.append((time.perf_counter() - t) * 1e6 / calls)
+    return out
+
+
+def run(arch, calls, repeats):
+    import torch
+    m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
+    s = m.sessions(16)
+    s.reserve_hires(16)
+    rs = np.random.RandomState(0)
+    rows = []
+    s.reserve_canvases(1, CW, CH, 4)
+    photo = rs.randint(0, 256, (3, CH, CW)).astype(np.uint8)
+    for placed in (1, 8):
+        s.canvas_put(0, photo)                                              # drops the placements of the round before
+        ids = np.arange(placed)
+        origins = [(301 + 200 * k, 403 + 40 * k) for k in range(placed)]       # squares of 256 pixels, neighbours overlap; ox % 4 = 1
+        s.place(ids, 0, origins, 4)
+        s.paint(ids, (20, 20, 44, 44), (255, 0, 0))
+        box = (20, 20, 44, 44)
+        for (vw, vh, origin) in ((256, 256, (400, 450)), (CW, CH, (0, 0))):
+            win, _, _ = api.pack_canvas_windows([0], origin, (vw, vh), [(CW, CH)])
+            d_out = torch.empty((1, 3, vh, vw), dtype=torch.uint8, device="cuda")
+            dev = device_us(lambda: m.handle.canvas_compose(win, vw, vh, d_out), calls, repeats)
+            res = {"compose_host": [], "brush": [], "brush_compose": []}
+            for _ in range(repeats):
+                res["compose_host"].append(median_us(lambda: s.compose([0], origin, (vw, vh)), calls))
+                res["brush"].append(median_us(lambda: s.paint([0], box, (255, 0, 0)), calls))
+                res["brush_compose"].append(median_us(
+                    lambda: s.brush_compose([0], box, (255, 0, 0), windows=([0], origin, (vw, vh))), calls))
+            row = {"placed": placed, "window": [vw, vh], "device_bytes": compose_bytes(1, vw, vh), "d2h_bytes": 3 * vw * vh,
+                   "compose_device": stat(dev)}
+            row["compose_device"]["GBps"] = round(compose_bytes(1, vw, vh) / (row["compose_device"]["p50_us"] * 1e-6) / 1e9, 1)
+            for k, v in res.items():
+                row[k] = stat(v)
+            row["window_adds_us"] = round(row["brush_compose"]["p50_us"] - row["brush"]["p50_us"], 2)
+            rows.append(row)
+    # compose against render: the same 2 * 3 * 1024 * 1024 bytes
+    s.reserve_canvases(1, CW, CH, 0)
+    s.canvas_put(0, photo)
+    s.place([0], 0, (512, 256), 16)
+    s.open_hires([1], rs.randint(0, 256, (1, 3, 1024, 1024)).astype(np.uint8))
+    s.paint([0, 1], (20, 20, 44, 44), (255, 0, 0))
+    win, _, _ = api.pack_canvas_windows([0], (512, 256), 1024, [(CW, CH)])
+    views, _, _ = api.pack_session_views([1], (0, 0), 1024, 16)
+    d_out = torch.empty((1, 3, 1024, 1024), dtype=torch.uint8, device="cuda")
+    comp, rend = [], []
+    for _ in range(repeats):                                                # alternating: the two see the same machine
+        comp += device_us(lambda: m.handle.canvas_compose(win, 1024, 1024, d_out), calls, 1)
+        rend += device_us(lambda: m.handle.session_render(views, 1024, 1024, d_out), calls, 1)
+    against = {"window": [1024, 1024], "device_bytes": compose_bytes(1, 1024, 1024), "compose_device": stat(comp), "render_device": stat(rend)}
+    against["compose_over_render"] = round(against["compose_device"]["p50_us"] / against["render_device"]["p50_us"], 3)
+    m.close()
+    return rows, against
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", default="IAN_simple")
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rows, against = run(a.arch, a.calls, a.repeats)
+    res = {"metric": "canvas_latency", "arch": a.arch, "canvas": [CW, CH], "calls": a.calls, "repeats": a.repeats, "rows": rows,
+           "against_render": against}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
