@@ -373,7 +373,7 @@ int ian_session_local(ian_handle* h, int32_t n, const int32_t* ids, const int32_
               with c < len: the entries after E[c] go and c = len; the state the user came back to stays an undo target (the oldest
               entry goes when that makes depth + 1 of them).
      clear    len = c = 0: every call that rewrites RECON / ERROR / GIM or zeroes UMASK (ian_session_open with all three sources,
-              ian_session_open_hires, ian_session_set_latent with as_sample = 1, ian_session_local), and a change of the depth.
+              ian_session_open_hires, ian_session_set_latent with as_sample = 1, ian_session_local, ian_session_fit), and a change of the depth.
    So `depth` is the largest number of steps that can be undone.  Restoring a state means, in one submission: UMASK and Z := the saved
    rows; x = the decoder at Z at batch n exactly as ian_session_set_latent runs it; on a photo-mode session the blend of
    ian_session_set_latent(as_sample = 0) -- the session's LOCAL flags, the restored UMASK, no footprint -- but stored:
@@ -403,6 +403,41 @@ int ian_session_undo(ian_handle* h, int32_t n, const int32_t* ids, const int32_t
 /* out[0] = the pool's depth, out[1] = how many steps ian_session_undo can undo on this opened session now, out[2] = how many it can
    redo.  Host only: no device state is touched.  -6 without the reservation, -7 for an id outside the pool or not opened. */
 int ian_session_history(ian_handle* h, int32_t id, int32_t out[3]);
+
+/* ---- fitting the latent to the photo: Adam steps on the reconstruction loss, on the device ----
+   An open keeps the encoder's latent, so RECON is as far from the photo as the encoder leaves it and ERROR carries the rest.  This
+   call refines the latent of n opened sessions by gradient descent on the API.py:64 loss against each session's own photo, `steps`
+   Adam steps in ONE submission on the caller's stream, and then ends like Reset at the fitted latent.  Per item:
+     T    = tanh_table[GIM byte]: np.asarray([to_tanh(GIM)], dtype=np.float32), the floats an open feeds the encoder; nothing is uploaded.
+     Z_0  = the session's current Z (after an open the encoder's latent, after edits the edited one).
+     g    = imgradRGB(c1, r1, c2, r2, T, Z_{t-1}) for t = 1..steps: bit for bit what ian_grad_batch returns for that rectangle, that
+            target image and that latent at the same batch size; an empty rectangle gives g = 0.
+     Adam step t in float32, every operation rounded on its own, no contraction, in exactly this order (csrc/ian_fit_step.h,
+     npe_ops.fit_adam_step):
+            m  = (0.9f * m) + (0.1f * g);   v = (0.999f * v) + ((0.001f * g) * g);   mh = m * c1[t];   vh = v * c2[t]
+            Z_t = Z_{t-1} - ((lr * mh) / (sqrtf(vh) + 1e-8f))
+            c1[t] = float32(1.0 / (1.0 - 0.9**t)), c2[t] = float32(1.0 / (1.0 - 0.999**t)), computed in double on the host
+            (npe_ops.fit_adam_consts).  m and v start at zero on every call: they live in a per-handle workspace, not in the pool, so
+            a second call starts a fresh optimiser.  g = 0 leaves Z unchanged (0 / 1e-8f = 0).
+     Then IM := GIM, Z := Z_steps, RECON := uint8(from_tanh(sample_at(Z_steps))) exactly as ian_decode_u8 computes it at that batch,
+     ERROR := to_tanh(float32(GIM)) - to_tanh(float32(RECON)), mode := photo, UMASK := 0 (LOCAL kept), FIELD := 0 at kind 0 (the "SRC
+     holds a photo" flag kept), the history cleared, a new latent version.  The residency of ian_session_brush ends and is not
+     re-armed.  A placement on a canvas stays: GIM does not change.  Any opened session may be fitted, a sample-mode one included
+     (its GIM is still there); it ends in photo mode.
+   shown u8[n,3,64,64] (host or device, or NULL) receives RECON, the one picture the caller does not already have.
+   loss f64[n, steps+1] (host or device, or NULL) receives loss[i][t], t = 0..steps: the API.py:64 loss at Z_t, the float64 mean of
+   (float64(x) - float64(T))**2 over the rectangle, summed in a fixed order (deterministic), 0 for an empty rectangle; with NULL the
+   loss kernel is not launched.  One synchronisation at the end, and only when loss or shown is host memory.
+   steps is 1..512, lr finite and > 0, n 1..256; more than `brush_pass` items (ian_set_option) run as passes, each pass through all
+   its steps before the next starts.  A pool that never calls this launches, moves and computes nothing it did not before.
+   -6: no pool.  -7, naming the item, before anything is enqueued or any host state moves: n outside 1..256, an id outside the pool,
+   a session not opened, an id given twice, a rectangle outside the image, steps outside 1..512, lr not finite or not positive. */
+typedef struct ian_session_fit_item {
+  int32_t session;          /* id in the pool */
+  int32_t c1, r1, c2, r2;   /* API.py:72-76 rectangle the loss is taken over, columns first; (0,0,64,64) = the whole picture */
+} ian_session_fit_item;
+int ian_session_fit(ian_handle* h, int32_t n, const ian_session_fit_item* items, int32_t steps, float lr, double* loss, uint8_t* shown,
+                    void* stream);
 
 /* ---- saving and loading whole sessions: the editor state as bytes that can leave the pool ----
    Everything a session is -- the 64x64 state, the full-resolution source and edit field, the user mask and flags, the ring of undo

@@ -22,7 +22,7 @@ import warnings
 import numpy as np
 
 from . import checkpoints, config_loader, lowering, made
-from .lib import BrushItem, Handle, SessionEvent, SessionView
+from .lib import BrushItem, Handle, SessionEvent, SessionFitItem, SessionView
 
 BATCH_MAX = 256     # ian_grad_batch / ian_brush_step_batch: 1 <= n <= 256
 
@@ -338,6 +338,35 @@ def pack_session_undo(ids, steps=1, capacity=None, opened=None):
     return idv, np.ascontiguousarray(a, np.int32)
 
 
+FIT_MAX_STEPS = 512     # ian_session_fit: 1 <= steps <= 512
+
+
+def pack_session_fit(ids, steps=20, lr=0.02, boxes=None, capacity=None, opened=None):
+    """Python arguments of ian_session_fit -> (a ctypes array of ian_session_fit_item, steps, lr), validated with the library's own
+    rules before the library sees anything.  ids (n,) session ids, each once; boxes (n,4) or (4,) as (c1, r1, c2, r2), floats
+    truncated as imgrad's int() does, None = the whole picture; steps an integer in 1..512; lr finite and > 0 as a float32."""
+    idl = [int(v) for v in check_session_ids(ids, capacity, opened)]
+    n = len(idl)
+    if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= FIT_MAX_STEPS:
+        raise ValueError("steps must be an integer in 1..%d, got %r" % (FIT_MAX_STEPS, steps))
+    lr32 = float(np.float32(lr))
+    if not (np.isfinite(lr32) and lr32 > 0.0):
+        raise ValueError("lr must be finite and positive as a float32, got %r" % (lr,))
+    b = np.asarray((0, 0, 64, 64) if boxes is None else boxes)
+    if b.ndim == 1 and b.shape == (4,):
+        b = np.tile(b, (n, 1))
+    if b.ndim != 2 or b.shape != (n, 4):
+        raise ValueError("boxes must have shape (%d,4) or (4,) as (c1,r1,c2,r2), got %s" % (n, b.shape))
+    items = (SessionFitItem * n)()
+    for i in range(n):
+        c1, r1, c2, r2 = [int(v) for v in b[i]]
+        if c1 < 0 or r1 < 0 or c2 > 64 or r2 > 64:
+            raise ValueError("item %d: rectangle (%d,%d,%d,%d) outside the 64x64 image" % (i, c1, r1, c2, r2))
+        it = items[i]
+        it.session, it.c1, it.r1, it.c2, it.r2 = idl[i], c1, r1, c2, r2
+    return items, int(steps), lr32
+
+
 class SessionRecords:
     """n saved sessions (EditSessions.save): `meta`, a structured array of n ian_session_meta entries (npe_ops.SESSION_META_DTYPE),
     and `body`, uint8 (n, body_bytes) -- a numpy array, or a torch device tensor when the save was asked for device memory.
@@ -447,6 +476,9 @@ class EditSessions:
         set_local(ids, local, dampen)  from then on a paint on those sessions changes the photo only around the strokes made since
     Undo (no counterpart in NPE.py): reserve_history(depth) keeps a ring of saved latents (and user masks) per session on the device;
         mark(ids)  a stroke begins     undo(ids, steps) / redo(ids, steps)  back and forth -> shown     history(sid)  what is possible
+    A closer reconstruction (the encoder + optimisation hybrid the NPE paper compares itself to): fit(ids, steps, lr) runs Adam steps
+        on the device from the sessions' current latents towards their own photos -> (RECON, loss trace); every later edit blends
+        against a smaller ERROR
     Leaving the pool (no counterpart in NPE.py): save(ids) -> SessionRecords, everything above as bytes; load(ids, records) puts them
         into any ids of a pool of the same layout: a project file, a move to another handle, parking an idle editor
     Whole photos (no counterpart in NPE.py): reserve_canvases(count, max_w, max_h, feather) keeps photos of any size (canvases) in
@@ -824,6 +856,18 @@ class EditSessions:
         shown = np.empty((len(ids), 3, 64, 64), np.uint8)
         self._h.session_set_latent(ids, self._latents(z, len(ids)), 0, shown)
         return shown
+
+    def fit(self, ids, steps=20, lr=0.02, boxes=None, want_loss=True):
+        """Fit the sessions' latents to their own photos (ian_session_fit): `steps` Adam steps at learning rate lr on the API.py:64
+        loss between sample_at(Z) and the photo, over boxes (n,4) or (4,) as (c1,r1,c2,r2) (None: the whole picture), all on the
+        device in one submission; then the sessions stand as after reset() but at the fitted latent: RECON and ERROR belong to
+        it, photo mode, user mask and undo history cleared.  -> (RECON uint8 (n,3,64,64), loss float64 (n, steps+1) or None):
+        loss[i, t] is the loss at the latent after t steps.  The defaults 20 and 0.02 are a starting point nobody has measured."""
+        items, steps, lr = pack_session_fit(ids, steps, lr, boxes, self.capacity, self._opened)
+        recon = np.empty((len(items), 3, 64, 64), np.uint8)
+        loss = np.empty((len(items), steps + 1), np.float64) if want_loss else None
+        self._h.session_fit(items, steps, lr, loss, recon)
+        return recon, loss
 
     def brush(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0):
         """n brush events (pack_session_events) in one submission -> shown."""

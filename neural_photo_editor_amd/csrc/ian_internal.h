@@ -230,6 +230,10 @@ struct BrushSeedSrc {
   const float* rgb = nullptr;     // the target colour images [n,3,H,W] of the items with loss kind 1 ...
   const float* colour = nullptr;  // ... or, with a table, their constant target colours [n][3]
   int c1 = 0, r1 = 0, c2 = 0, r2 = 0, mode = 0;   // without a table (the eager single call, n = 1)
+  // ... or, with a table, each item's own photo (ian_session_fit): the target of element o of item i is tanh_tab[gim[ids[i]*12288 + o]]
+  const unsigned char* gim = nullptr;   // the session pool's GIM base, u8 [capacity][3*64*64]
+  const int* ids = nullptr;             // device int[n]: the items' session ids
+  const float* tanh_tab = nullptr;      // device float[256]: to_tanh of the uint8 levels (ian_session_tanh_table)
 };
 // d loss / d x_hat of n items: g NCHW [n,3,H,W], zero outside each item's rectangle
 hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, float* g, int H, int W, hipStream_t s);
@@ -408,6 +412,15 @@ struct SessionBlendArgs {
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s);
 // UMASK row of session ids[i] := 0 and, with flags (device int[n]), LOCAL[ids[i]] := flags[i]
 hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const int* flags, int n, hipStream_t s);
+// ian_session_fit.  begin: IM := GIM of sessions ids[0..n).  adam: rows 0..n-1 of the latent slot z (stride zs) move by one Adam step
+// (ian_fit_step.h) on the gradient rows g (same stride); m, v = the moments, [n][zl]; c1, c2 = the step's bias corrections.
+// loss: loss[i * loss_stride] = the float64 mean of (xhat[i] - table[GIM of ids[i]])^2 over the rectangle of row i of the
+// ian_brush_item table `items`, 0 for an empty one; xhat NCHW [n][3][64][64].
+hipError_t launch_session_fit_begin(const SessionPool& P, const int* ids, int n, hipStream_t s);
+hipError_t launch_session_fit_adam(float* z, const float* g, int zs, float* m, float* v, int n, int zl, float lr, float c1, float c2,
+                                   hipStream_t s);
+hipError_t launch_session_fit_loss(const float* xhat, const SessionPool& P, const int* ids, const int* items, const float* table,
+                                   double* loss, int loss_stride, int n, hipStream_t s);
 // undo history.  ids / save / load = device int[n]; slots are 0..depth (a slot outside that range is skipped).
 // save: ring slot save[i] of session ids[i] := its live Z row (and UMASK row, when hist_umask exists)
 hipError_t launch_session_history_save(const SessionPool& P, const SessionRings& R, const int* ids, const int* save, int n, hipStream_t s);

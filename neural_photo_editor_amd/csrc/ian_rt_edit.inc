@@ -379,17 +379,17 @@ int batch_forward(ian_handle* h, const float* z, int nc, hipStream_t st) {
 }
 
 // What every batched brush call runs between "the latent slot holds nc latents and the decoder's activations belong to them" and its
-// outputs: the batched seed + backward sweep (d_rgb: [nc,3,H,W] colour images, or d_colour: [nc][3] constant colours) and, for a step,
-// the brush update (fused into the latent's GEMV where that form is taken) and the forward at z_new.  Shared by batch_common and
-// the session calls (ian_rt_session.inc).
-int brush_pass_middle(ian_handle* h, int nc, const int* d_it, const float* d_rgb, const float* d_colour, bool step, hipStream_t st) {
+// outputs: the batched seed + backward sweep (seed: the nc rows of the item table and where their targets come from -- rgb: [nc,3,H,W]
+// colour images, colour: [nc][3] constant colours, or gim / ids / tanh_tab: the sessions' own photos) and, for a step, the brush
+// update (fused into the latent's GEMV where that form is taken) and the forward at z_new.  Without a step the latents' gradient
+// rows are left in the z slot's gradient buffer.  Shared by batch_common and the session calls (ian_rt_session.inc).
+int brush_pass_middle(ian_handle* h, int nc, const BrushSeedSrc& seed, bool step, hipStream_t st) {
   int rc;
   Slot& zs = h->slots[h->desc.z_slot];
   if ((rc = ensure_slot(h, h->desc.z_slot, nc, true))) return rc;
+  const int* d_it = seed.table;
   BrushBackward rq;
-  rq.seed.table = d_it;
-  rq.seed.rgb = d_rgb;
-  rq.seed.colour = d_colour;
+  rq.seed = seed;
   rq.n = nc;
   rq.batch = true;
   rq.update = step ? BrushBackward::PER_ITEM : BrushBackward::NONE;
@@ -467,7 +467,10 @@ int batch_common(ian_handle* h, int n, const ian_brush_item* items, const float*
     const size_t zo = (size_t)off * zl, io = (size_t)off * img;
     if (!hit && (rc = batch_forward(h, z + zo, nc, st))) return rc;
     const int* d_it = B.d_items + (size_t)7 * off;
-    if ((rc = brush_pass_middle(h, nc, d_it, d_rgb ? d_rgb + io : nullptr, nullptr, step, st))) return rc;
+    BrushSeedSrc seed;
+    seed.table = d_it;
+    seed.rgb = d_rgb ? d_rgb + io : nullptr;
+    if ((rc = brush_pass_middle(h, nc, seed, step, st))) return rc;
     if (step) {
       HIPCHK(h, launch_rows_copy(zs.d, zs.cs, z_new_dev ? z_new + zo : st_z + zo, zl, nc, zl, st));
     }

@@ -67,6 +67,8 @@ const SessScratchBuf SESS_SCRATCH[] = {
     {offsetof(SessionScratch, d_shown), (size_t)BATCH_MAX * SESS_IMG, SESS_BASE},
     {offsetof(SessionScratch, d_rtab), 0, SESS_BASE},
     {offsetof(SessionScratch, d_stage), 0, SESS_BASE},
+    {offsetof(SessionScratch, d_fit), 0, SESS_BASE},
+    {offsetof(SessionScratch, d_fit_loss), 0, SESS_BASE},
     {offsetof(SessionScratch, d_tanh), 256 * sizeof(float), SESS_BASE},   // last of its group: a failed build never leaves it without its upload
     {offsetof(SessionScratch, d_views), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HIRES},
     {offsetof(SessionScratch, d_out), 0, SESS_HIRES},
@@ -833,7 +835,10 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
       HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
       if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
     }
-    if ((rc = brush_pass_middle(h, nc, d_items + (size_t)7 * off, nullptr, d_col + (size_t)3 * off, true, st))) return rc;
+    BrushSeedSrc seed;
+    seed.table = d_items + (size_t)7 * off;
+    seed.colour = d_col + (size_t)3 * off;
+    if ((rc = brush_pass_middle(h, nc, seed, true, st))) return rc;
     HIPCHK(h, launch_session_blend(session_blend_args(h, d_ids + off, d_items + (size_t)7 * off, d_shown + (size_t)off * SESS_IMG, 1), nc, st));
   }
   h->slot_stale[h->desc.out_slot] = 0;
@@ -854,6 +859,92 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
     S.res_valid = true;
   }
   return 0;
+}
+
+// ian_session_fit (DESIGN.md 4.8): the sessions' latents fitted to their own photos, `steps` Adam steps in one submission.  Per pass
+// of at most opt.brush_pass items every step is: the decoder forward with kept activations, [the loss read-out,] the batched backward
+// sweep seeded from the pool's GIM rows (SEED_PHOTO, no update fused into the GEMV), the Adam kernel on the latent slot.  Then the
+// decoder as ian_decode_u8 runs it, [the last loss,] and the store kernel of an open: the call ends like Reset at the fitted latent.
+constexpr int SESS_FIT_MAX_STEPS = 512;
+int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int steps, float lr, double* loss, uint8_t* shown, void* stream) {
+  const char* fn = "ian_session_fit";
+  static_assert(sizeof(ian_session_fit_item) == 5 * sizeof(int32_t), "ian_session_fit_item is 5 words");
+  int rc = session_check(h, fn, n, items ? &items->session : nullptr, 5, true, false);
+  if (rc) return rc;
+  Slot& out = h->slots[h->desc.out_slot];
+  for (int i = 0; i < n; ++i) {
+    const ian_session_fit_item& e = items[i];
+    if (e.c1 < 0 || e.r1 < 0 || e.c2 > out.w || e.r2 > out.h)
+      return fail(h, -7, "%s: item %d: rectangle (%d,%d,%d,%d) outside the %dx%d image", fn, i, e.c1, e.r1, e.c2, e.r2, out.w, out.h);
+  }
+  if (steps < 1 || steps > SESS_FIT_MAX_STEPS) return fail(h, -7, "%s: steps = %d outside 1..%d", fn, steps, SESS_FIT_MAX_STEPS);
+  if (!std::isfinite(lr) || !(lr > 0.f)) return fail(h, -7, "%s: lr = %g is not a finite positive number", fn, (double)lr);
+  auto& S = h->sess;
+  const int zl = h->desc.num_latents;
+  const int lstride = steps + 1;
+  const bool loss_dev = loss && is_device_ptr(loss);
+  if (!S.d_fit) HIPCHK(h, hipMalloc((void**)&S.d_fit, (size_t)2 * BATCH_MAX * zl * sizeof(float)));
+  if (loss && !loss_dev && !S.d_fit_loss)
+    HIPCHK(h, hipMalloc((void**)&S.d_fit_loss, (size_t)BATCH_MAX * (SESS_FIT_MAX_STEPS + 1) * sizeof(double)));
+  // the bias corrections of every step, in double, rounded once (npe_ops.fit_adam_consts)
+  std::vector<float> c1((size_t)steps + 1), c2((size_t)steps + 1);
+  for (int t = 1; t <= steps; ++t) {
+    c1[t] = (float)(1.0 / (1.0 - std::pow(0.9, (double)t)));
+    c2[t] = (float)(1.0 / (1.0 - std::pow(0.999, (double)t)));
+  }
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);   // also ends the residency of ian_session_brush: not re-armed, the last forward keeps no activations
+  TotalTimer tt(h, st);
+  // the table: n ian_brush_item rows (the rectangle, loss kind 1; coef and gscale unused), then the n ids
+  S.tab_shadow.assign((size_t)8 * n, 0);
+  for (int i = 0; i < n; ++i) {
+    int32_t* row = S.tab_shadow.data() + (size_t)7 * i;
+    row[0] = items[i].c1; row[1] = items[i].r1; row[2] = items[i].c2; row[3] = items[i].r2; row[4] = 1;
+    S.tab_shadow[(size_t)7 * n + i] = items[i].session;
+  }
+  HIPCHK(h, hipMemcpyAsync(S.d_tab, S.tab_shadow.data(), (size_t)8 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int* d_items = S.d_tab;
+  const int* d_ids = S.d_tab + (size_t)7 * n;
+  HIPCHK(h, launch_session_fit_begin(S.arr.pool, d_ids, n, st));   // IM := GIM (NPE.py:332)
+  Slot& zs = h->slots[h->desc.z_slot];
+  double* d_loss = loss ? (loss_dev ? loss : S.d_fit_loss) : nullptr;
+  const bool shown_dev = shown && is_device_ptr(shown);
+  unsigned char* d_shown = shown ? (shown_dev ? shown : S.d_shown) : nullptr;
+  const int pass = h->opt.brush_pass;
+  for (int off = 0; off < n; off += pass) {
+    const int nc = std::min(pass, n - off);
+    if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
+    HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
+    float* m = S.d_fit;
+    float* v = S.d_fit + (size_t)nc * zl;
+    HIPCHK(h, hipMemsetAsync(S.d_fit, 0, (size_t)2 * nc * zl * sizeof(float), st));   // the moments start at zero on every call
+    BrushSeedSrc seed;
+    seed.table = d_items + (size_t)7 * off;
+    seed.gim = S.arr.pool.gim;
+    seed.ids = d_ids + off;
+    seed.tanh_tab = S.d_tanh;
+    auto read_loss = [&](int t) -> hipError_t {
+      return launch_session_fit_loss(out.d, S.arr.pool, d_ids + off, seed.table, S.d_tanh, d_loss + (size_t)off * lstride + t, lstride, nc, st);
+    };
+    for (int t = 1; t <= steps; ++t) {
+      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;   // sample_at(Z_{t-1}), every activation kept
+      if (d_loss) HIPCHK(h, read_loss(t - 1));
+      if ((rc = brush_pass_middle(h, nc, seed, false, st))) return rc;   // g -> the z slot's gradient rows
+      HIPCHK(h, launch_session_fit_adam(zs.d, zs.g, zs.cs, m, v, nc, zl, lr, c1[t], c2[t], st));
+    }
+    if ((rc = run_segment(h, IAN_SEG_DEC, nc, st))) return rc;   // sample_at(Z_steps) at this batch, as ian_decode_u8 runs it
+    if (d_loss) HIPCHK(h, read_loss(steps));
+    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, d_ids + off, 0, 1, d_shown ? d_shown + (size_t)off * SESS_IMG : nullptr, nc, st));
+  }
+  h->slot_stale[h->desc.out_slot] = 0;
+  if (S.arr.pool.umask) HIPCHK(h, launch_session_local_set(S.arr.pool, d_ids, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:337); LOCAL stays
+  for (int i = 0; i < n; ++i) {   // as session_open_finish: a new latent version, the saved states no longer belong to the picture
+    ++S.version[items[i].session];
+    session_history_note(S, items[i].session, true);
+  }
+  const bool loss_host = loss && !loss_dev;
+  if (loss_host) HIPCHK(h, hipMemcpyAsync(loss, S.d_fit_loss, (size_t)n * lstride * sizeof(double), hipMemcpyDeviceToHost, st));
+  return session_finish(h, n, shown, shown_dev, loss_host, st);
 }
 
 int session_render(ian_handle* h, int n, const ian_session_view* views, int vw, int vh, uint8_t* out, void* stream) {
@@ -1091,6 +1182,10 @@ int ian_session_undo(ian_handle* h, int32_t n, const int32_t* ids, const int32_t
 }
 int ian_session_history(ian_handle* h, int32_t id, int32_t out[3]) {
   return h ? session_history(h, id, out) : -1;
+}
+int ian_session_fit(ian_handle* h, int32_t n, const ian_session_fit_item* items, int32_t steps, float lr, double* loss, uint8_t* shown,
+                    void* stream) {
+  return h ? session_fit(h, n, items, steps, lr, loss, shown, stream) : -1;
 }
 int ian_session_record_info(ian_handle* h, ian_session_meta* layout, int64_t* offsets, int32_t* ncols) {
   return h ? session_record_info(h, layout, offsets, ncols) : -1;

@@ -301,6 +301,8 @@ struct ian_handle {
     int* d_htab = nullptr;             // undo history: per ian_session_mark / _undo call [n ids | n save slots | n load slots]
     int* d_rtab = nullptr;             // saved sessions: per ian_session_save / _load call n x (id, has_source, ring base, history length); by the first such call
     unsigned char* d_stage = nullptr;  // saved sessions: staging of records for a host `body`, grown on demand (stage_cap) up to opt.session_stage_bytes
+    float* d_fit = nullptr;            // ian_session_fit: Adam's moments of one pass, m [256][zl] then v [256][zl]; by the first such call
+    double* d_fit_loss = nullptr;      // ian_session_fit: staging of the loss trace for a host `loss`, [256][513]; by the first call that asks for one
   };
   struct SessionState : SessionScratch {
     int capacity = 0;

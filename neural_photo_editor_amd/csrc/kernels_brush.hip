@@ -18,21 +18,38 @@ namespace ian {
 // item blockIdx.y come from is BrushSeedSrc (ian_internal.h); a kernel is compiled per kind of source:
 enum { SEED_IMM = 0,      // the rectangle and loss kind are launch arguments, the target an image (the eager single call)
        SEED_RGB = 1,      // row blockIdx.y of the ian_brush_item table, the target an image rgb [n,3,H,W]
-       SEED_COLOUR = 2 }; // the same table, the target a constant colour [n][3] (ian_session_brush, NPE.py:205 myRGB)
-struct SeedRect { int c1, r1, c2, r2, mode; };
+       SEED_COLOUR = 2,   // the same table, the target a constant colour [n][3] (ian_session_brush, NPE.py:205 myRGB)
+       SEED_PHOTO = 3 };  // the same table, the target the item's own photo: tab[GIM byte] of session ids[item] (ian_session_fit)
+struct SeedRect { int c1, r1, c2, r2, mode, id; };   // id: SEED_PHOTO only, the item's session
+constexpr int SEED_PHOTO_IMG = 3 * 64 * 64;          // a GIM row of the session pool
+template <int KIND> struct SeedLds {                 // ints / floats of LDS a kernel hands to seed_fetch
+  static constexpr int SP = KIND == SEED_PHOTO ? 6 : 5, SC = KIND == SEED_PHOTO ? 256 : 4;
+};
 
 // The table may live in mapped host memory (zero-copy graphs): ONE lane per word fetches it and hands it on through LDS -- a scalar
 // load per wave over PCIe made the fused kernel the longest of the brush event (19.0 us, profiles/r05_batch1_chains.md).  Ends in a
-// barrier: every thread of the workgroup calls it.  sp: 5 ints, sc: 4 floats of LDS (sc receives the item's colour).
+// barrier: every thread of the workgroup calls it.  sp: SeedLds::SP ints, sc: SeedLds::SC floats of LDS (sc receives the item's
+// colour, or for SEED_PHOTO the 256-entry tanh table).
+// SEED_PHOTO stages the 1 KB table in LDS instead of reading it through the cache: with the whole-picture rectangle of a fit every
+// thread of the fused kernel looks up all 75 (tap, channel) targets of its pixel, each a byte load followed by a dependent table
+// load, and the second hop from LDS is a fraction of an L1 hit; the 32 lanes that share a pixel read the same entry (a broadcast,
+// no bank conflict).  Staging costs one load per thread under the barrier the rectangle needs anyway (the workgroups are 256
+// threads, one per entry), as session_open_in_kernel stages it.  The unfused kernel looks up once per thread: there staging neither
+// wins nor loses, and it keeps the one seed_value body.
 template <int KIND>
 __device__ __forceinline__ SeedRect seed_fetch(const BrushSeedSrc& src, int item, int* sp, float* sc) {
-  if (KIND == SEED_IMM) return {src.c1, src.r1, src.c2, src.r2, src.mode};
+  if (KIND == SEED_IMM) return {src.c1, src.r1, src.c2, src.r2, src.mode, 0};
   if (threadIdx.x < 5) sp[threadIdx.x] = src.table[item * 7 + threadIdx.x];
   if (KIND == SEED_COLOUR && threadIdx.x >= 8 && threadIdx.x < 11) sc[threadIdx.x - 8] = src.colour[item * 3 + (threadIdx.x - 8)];
+  if (KIND == SEED_PHOTO) {
+    if (threadIdx.x == 5) sp[5] = src.ids[item];
+    sc[threadIdx.x] = src.tanh_tab[threadIdx.x];
+  }
   __syncthreads();
   // the same five words in every lane: kept in scalar registers, as the launch arguments of SEED_IMM are
   return {__builtin_amdgcn_readfirstlane(sp[0]), __builtin_amdgcn_readfirstlane(sp[1]), __builtin_amdgcn_readfirstlane(sp[2]),
-          __builtin_amdgcn_readfirstlane(sp[3]), __builtin_amdgcn_readfirstlane(sp[4])};
+          __builtin_amdgcn_readfirstlane(sp[3]), __builtin_amdgcn_readfirstlane(sp[4]),
+          KIND == SEED_PHOTO ? __builtin_amdgcn_readfirstlane(sp[5]) : 0};
 }
 // 1/N, or 0 for an empty rectangle
 __device__ __forceinline__ float seed_inv(const SeedRect& R) {
@@ -40,30 +57,33 @@ __device__ __forceinline__ float seed_inv(const SeedRect& R) {
   return cnt > 0 ? 1.f / (float)cnt : 0.f;
 }
 // the seed of element o (channel co, value xh) of the item's image, for an element INSIDE a non-empty rectangle; rgb_i = the item's
-// target image, sc = its colour in LDS: whichever KIND names is read, and only in mode 1
+// target image, sc = its colour in LDS (SEED_PHOTO: the tanh table, gim_i = the session's GIM row): whichever KIND names is read,
+// and only in mode 1
 template <int KIND>
-__device__ __forceinline__ float seed_value(int mode, float inv, float xh, const float* rgb_i, const float* sc, int o, int co) {
-  return (mode == 0) ? inv : 2.f * (xh - (KIND == SEED_COLOUR ? sc[co] : rgb_i[o])) * inv;
+__device__ __forceinline__ float seed_value(int mode, float inv, float xh, const float* rgb_i, const float* sc,
+                                            const unsigned char* gim_i, int o, int co) {
+  return (mode == 0) ? inv : 2.f * (xh - (KIND == SEED_COLOUR ? sc[co] : (KIND == SEED_PHOTO ? sc[gim_i[o]] : rgb_i[o]))) * inv;
 }
 
 // seed only: g NCHW [n,3,H,W]; element i of an image belongs to channel i / (H*W).  Grid (3*H*W / 256, n).
 template <int KIND>
 __global__ __launch_bounds__(256) void brush_seed_kernel(BrushSeedSrc src, const float* __restrict__ xhat, float* __restrict__ g, int H,
                                                          int W) {
-  __shared__ int sp[5];
-  __shared__ float sc[4];
+  __shared__ int sp[SeedLds<KIND>::SP];
+  __shared__ float sc[SeedLds<KIND>::SC];
   const int item = blockIdx.y;
   const SeedRect R = seed_fetch<KIND>(src, item, sp, sc);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 3 * H * W) return;
   const size_t img = (size_t)item * 3 * H * W;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && R.mode) ? src.rgb + img : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && R.mode) ? src.rgb + img : nullptr;
+  const unsigned char* gim_i = KIND == SEED_PHOTO ? src.gim + (size_t)R.id * SEED_PHOTO_IMG : nullptr;
   const int xx = i % W, yy = (i / W) % H;
   float v = 0.f;
   if (yy >= R.r1 && yy < R.r2 && xx >= R.c1 && xx < R.c2) {
     const float inv = seed_inv(R);
-    if (inv > 0.f) v = seed_value<KIND>(R.mode, inv, xh_i[i], rgb_i, sc, i, i / (H * W));
+    if (inv > 0.f) v = seed_value<KIND>(R.mode, inv, xh_i[i], rgb_i, sc, gim_i, i, i / (H * W));
   }
   (g + img)[i] = v;
 }
@@ -73,15 +93,16 @@ __global__ __launch_bounds__(256) void brush_seed_kernel(BrushSeedSrc src, const
 //   gout[co,oy,ox] = seed(co,oy,ox) * out_act'(xhat) * oscale[co]
 //   dx[iy,ix,ci]   = ( sum_{ky,kx,co} gout[co,2iy-2+ky,2ix-2+kx] * w[ky*5+kx][co][ci] ) * act'(yfwd[iy,ix,ci]) * scale[ci]
 // xhat NCHW [n,Cout,2H,2W]; dx, yfwd NHWC [n,H,W,Cin]; w packed [25][4][Cin].  The seed is non-zero only inside the rectangle, so a
-// thread visits only the taps whose output pixel lies in it (most threads: none).  A thread owns four consecutive channels of a
+// thread visits only the taps whose output pixel lies in it (a brush event: most threads none; the whole-picture rectangle of
+// ian_session_fit: every thread all of its taps, see seed_fetch for what that means for SEED_PHOTO's table).  A thread owns four consecutive channels of a
 // pixel (float4 filter loads and stores); grid (H*W*Cin/4 / 256, n).  One event is n = 1 with a one-row table.
 template <int KIND>
 __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc src, const float* __restrict__ xhat, int out_act,
                                                                  const float* __restrict__ oscale, const float* __restrict__ w,
                                                                  float* __restrict__ dx, const float* __restrict__ yfwd,
                                                                  const float* __restrict__ scale, int H, int W, int Cin, int Cout, int act) {
-  __shared__ int sp[5];
-  __shared__ float sc[4];
+  __shared__ int sp[SeedLds<KIND>::SP];
+  __shared__ float sc[SeedLds<KIND>::SC];
   const int item = blockIdx.y;
   const SeedRect R = seed_fetch<KIND>(src, item, sp, sc);
   const int c4n = Cin >> 2;
@@ -92,7 +113,8 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
   const int OH = 2 * H, OW = 2 * W;
   const size_t img = (size_t)item * Cout * OH * OW;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && R.mode) ? src.rgb + img : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && R.mode) ? src.rgb + img : nullptr;
+  const unsigned char* gim_i = KIND == SEED_PHOTO ? src.gim + (size_t)R.id * SEED_PHOTO_IMG : nullptr;
   const float inv = seed_inv(R);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   if (inv > 0.f) {
@@ -107,7 +129,7 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
         for (int co = 0; co < Cout; ++co) {
           const int o = (co * OH + oy) * OW + ox;
           const float xh = xh_i[o];
-          float gv = seed_value<KIND>(R.mode, inv, xh, rgb_i, sc, o, co);
+          float gv = seed_value<KIND>(R.mode, inv, xh, rgb_i, sc, gim_i, o, co);
           gv = gv * m_dact(xh, out_act) * (oscale ? oscale[co] : 1.f);
           const float4 wv = *reinterpret_cast<const float4*>(w + ((size_t)(ky * 5 + kx) * 4 + co) * Cin + ci);
           acc[0] = fmaf(gv, wv.x, acc[0]);
@@ -129,14 +151,19 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
   *reinterpret_cast<float4*>(dx + o4) = out;
 }
 
-static int seed_kind(const BrushSeedSrc& src) { return !src.table ? SEED_IMM : (src.colour ? SEED_COLOUR : SEED_RGB); }
+static int seed_kind(const BrushSeedSrc& src) {
+  return !src.table ? SEED_IMM : (src.gim ? SEED_PHOTO : (src.colour ? SEED_COLOUR : SEED_RGB));
+}
+// a photo target is a GIM row of the pool: 3 x 64 x 64 bytes, with the id list and the table to go with it
+static bool seed_photo_ok(const BrushSeedSrc& src, int C, int H, int W) { return src.ids && src.tanh_tab && C * H * W == SEED_PHOTO_IMG; }
 
 hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, float* g, int H, int W, hipStream_t s) {
   const int kind = seed_kind(src);
-  if (n < 1 || n > 65535 || (kind == SEED_IMM && n != 1)) return hipErrorInvalidValue;
+  if (n < 1 || n > 65535 || (kind == SEED_IMM && n != 1) || (kind == SEED_PHOTO && !seed_photo_ok(src, 3, H, W))) return hipErrorInvalidValue;
   const dim3 grid((3 * H * W + 255) / 256, n);
   if (kind == SEED_IMM) hipLaunchKernelGGL(brush_seed_kernel<SEED_IMM>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_RGB) hipLaunchKernelGGL(brush_seed_kernel<SEED_RGB>, grid, dim3(256), 0, s, src, xhat, g, H, W);
+  else if (kind == SEED_PHOTO) hipLaunchKernelGGL(brush_seed_kernel<SEED_PHOTO>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else hipLaunchKernelGGL(brush_seed_kernel<SEED_COLOUR>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   return hipGetLastError();
 }
@@ -145,8 +172,12 @@ hipError_t launch_brush_seed_dec_out(const BrushSeedSrc& src, int n, const float
                                      hipStream_t s) {
   const int kind = seed_kind(src);   // a colour has three channels; the fused form always reads a table
   if ((Cin & 3) || n < 1 || n > 65535 || kind == SEED_IMM || (kind == SEED_COLOUR && Cout > 3)) return hipErrorInvalidValue;
+  if (kind == SEED_PHOTO && !seed_photo_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
   const dim3 grid((H * W * (Cin >> 2) + 255) / 256, n);
-  if (kind == SEED_RGB)
+  if (kind == SEED_PHOTO)
+    hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_PHOTO>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H, W,
+                       Cin, Cout, act);
+  else if (kind == SEED_RGB)
     hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_RGB>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H, W, Cin,
                        Cout, act);
   else

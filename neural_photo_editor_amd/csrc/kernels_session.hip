@@ -7,6 +7,7 @@
 //   session_blend_kernel       brush / paint_latents: photo blend (photo mode) or uint8 image (sample mode) per session, z_new -> pool
 //   session_blend_local_kernel the same in a pool with the local reservation: per-session user mask, brush footprint, dampen
 //   session_local_set_kernel   local edits: a session's UMASK := 0 (every open) and its LOCAL flags (ian_session_local)
+//   session_fit_begin_kernel / _adam_kernel / _loss_kernel  ian_session_fit: IM := GIM, one Adam step on the latent rows, the loss read-out
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
 //   canvas_place_kernel        canvases: the exact box mean of a square of a whole photo -> GIM, IM, encoder input (any byte alignment)
@@ -220,6 +221,7 @@ hipError_t launch_session_unpack(const SessionPool& P, const SessionRings& R, co
 }  // namespace ian
 
 #include "npe_blend.h"   // floating-point contraction off from here on; np_uint8f, photo_blend_image
+#include "ian_fit_step.h"   // ian_fit_adam_step
 
 namespace ian {
 
@@ -413,6 +415,80 @@ __global__ __launch_bounds__(256) void session_local_set_kernel(SessionPool P, c
 hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const int* flags, int n, hipStream_t s) {
   if (n < 1 || n > 65535 || !P.umask || !P.local) return hipErrorInvalidValue;
   hipLaunchKernelGGL(session_local_set_kernel, dim3(n), dim3(256), 0, s, P, ids, flags);
+  return hipGetLastError();
+}
+
+// ---- ian_session_fit: the latent fitted to the session's own photo by Adam steps, all on the device -----------------
+// IM := GIM of session ids[i], the first thing Reset does (NPE.py:332): session_store_kernel takes ERROR against IM.  grid (S_IMG / 1024, n),
+// a lane owns 4 consecutive bytes.
+__global__ __launch_bounds__(256) void session_fit_begin_kernel(SessionPool P, const int* __restrict__ ids) {
+  const size_t o = (size_t)ids[blockIdx.y] * S_IMG + (size_t)(blockIdx.x * 256 + threadIdx.x) * 4;
+  *reinterpret_cast<uchar4*>(P.im + o) = *reinterpret_cast<const uchar4*>(P.gim + o);
+}
+hipError_t launch_session_fit_begin(const SessionPool& P, const int* ids, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || !P.gim || !P.im) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_fit_begin_kernel, dim3(S_IMG / 1024, n), dim3(256), 0, s, P, ids);
+  return hipGetLastError();
+}
+
+// Adam step t of item blockIdx.x: row i of the latent slot (stride zs) moves by ian_fit_adam_step with g = row i of the slot's
+// gradient; m and v are rows of the workspace, [n][zl] each.  lr and the step's two bias corrections travel in the launch.
+__global__ __launch_bounds__(128) void session_fit_adam_kernel(float* __restrict__ z, const float* __restrict__ g, int zs,
+                                                               float* __restrict__ m, float* __restrict__ v, int zl, float lr, float c1,
+                                                               float c2) {
+  const int i = blockIdx.x;
+  for (int j = threadIdx.x; j < zl; j += 128) {
+    const size_t o = (size_t)i * zs + j, w = (size_t)i * zl + j;
+    float mj = m[w], vj = v[w];
+    z[o] = ian_fit_adam_step(z[o], g[o], &mj, &vj, c1, c2, lr);
+    m[w] = mj;
+    v[w] = vj;
+  }
+}
+hipError_t launch_session_fit_adam(float* z, const float* g, int zs, float* m, float* v, int n, int zl, float lr, float c1, float c2,
+                                   hipStream_t s) {
+  if (n < 1 || n > 65535 || zl < 1 || zs < zl || !z || !g || !m || !v) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_fit_adam_kernel, dim3(n), dim3(128), 0, s, z, g, zs, m, v, zl, lr, c1, c2);
+  return hipGetLastError();
+}
+
+// The API.py:64 loss of item blockIdx.x at the image in xhat: the float64 mean of (float64(x) - float64(T))^2 over the item's
+// rectangle (words 0..3 of its ian_brush_item row), T = table[GIM byte] of session ids[i]; 0 for an empty rectangle.  One workgroup
+// per item.  The order of the sum is fixed: lane t adds the rectangle's elements t, t + 256, ... (channel-major, then rows, then
+// columns) in float64, one rounding per product and per sum, then the 256 partial sums meet in an LDS tree, [t] += [t + half].
+// The rectangle was checked by the host (inside the image); the extents are clamped at 0 all the same.
+__global__ __launch_bounds__(256) void session_fit_loss_kernel(const float* __restrict__ xhat, SessionPool P, const int* __restrict__ ids,
+                                                               const int* __restrict__ items, const float* __restrict__ table,
+                                                               double* __restrict__ loss, int loss_stride) {
+  __shared__ float tab[256];
+  __shared__ double part[256];
+  tab[threadIdx.x] = table[threadIdx.x];
+  __syncthreads();
+  const int i = blockIdx.x;
+  const int c1 = items[i * 7], r1 = items[i * 7 + 1];
+  const int w = max(0, items[i * 7 + 2] - c1), hgt = max(0, items[i * 7 + 3] - r1);
+  const int cnt = 3 * w * hgt;
+  const float* xh = xhat + (size_t)i * S_IMG;
+  const unsigned char* gim = P.gim + (size_t)ids[i] * S_IMG;
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < cnt; k += 256) {
+    const int co = k / (w * hgt), rem = k - co * (w * hgt);
+    const int o = (co * 64 + r1 + rem / w) * 64 + c1 + rem % w;
+    const double d = (double)xh[o] - (double)tab[gim[o]];
+    acc = acc + d * d;
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int half = 128; half >= 1; half >>= 1) {
+    if (threadIdx.x < half) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + half];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[(size_t)i * loss_stride] = cnt > 0 ? part[0] / (double)cnt : 0.0;
+}
+hipError_t launch_session_fit_loss(const float* xhat, const SessionPool& P, const int* ids, const int* items, const float* table,
+                                   double* loss, int loss_stride, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || !xhat || !P.gim || !ids || !items || !table || !loss || loss_stride < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_fit_loss_kernel, dim3(n), dim3(256), 0, s, xhat, P, ids, items, table, loss, loss_stride);
   return hipGetLastError();
 }
 

@@ -48,6 +48,7 @@ EXPORTS = (
     "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
+    "ian_session_fit",
     "ian_session_record_info", "ian_session_save", "ian_session_load",
     "ian_sessions_reserve_canvas", "ian_canvas_put", "ian_canvas_place", "ian_canvas_compose", "ian_canvas_brush", "ian_canvas_commit",
     "ian_canvas_read", "ian_canvas_placements",
@@ -127,6 +128,7 @@ def load_library():
     lib.ian_session_mark.argtypes = [vp, i32, fp, vp]
     lib.ian_session_undo.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_history.argtypes = [vp, i32, fp]
+    lib.ian_session_fit.argtypes = [vp, i32, C.POINTER(SessionFitItem), i32, C.c_float, fp, fp, vp]
     lib.ian_session_record_info.argtypes = [vp, C.POINTER(SessionMeta), fp, fp]
     lib.ian_session_save.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_load.argtypes = [vp, i32, fp, fp, fp, vp]
@@ -187,6 +189,11 @@ class SessionEvent(C.Structure):
 class SessionView(C.Structure):
     """ian_session_view (include/ian.h): one window of a full-resolution session (ian_session_render / ian_session_brush_view)."""
     _fields_ = [("session", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+class SessionFitItem(C.Structure):
+    """ian_session_fit_item (include/ian.h): one session of ian_session_fit and the rectangle its loss is taken over."""
+    _fields_ = [("session", C.c_int32), ("c1", C.c_int32), ("r1", C.c_int32), ("c2", C.c_int32), ("r2", C.c_int32)]
 
 
 class CanvasPlacement(C.Structure):
@@ -432,6 +439,13 @@ class Handle:
         out = np.zeros(3, np.int32)
         self._check(self.lib.ian_session_history(self._h, int(sid), _ptr(out)))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def session_fit(self, items, steps, lr, loss=None, shown=None, stream=None):
+        """ian_session_fit; items = a ctypes array of SessionFitItem (n = its length), loss f64[n, steps+1] or None, shown
+        u8[n,3,64,64] or None."""
+        null = C.c_void_p(0)
+        self._check(self.lib.ian_session_fit(self._h, len(items), items, int(steps), float(lr), _ptr(loss) if loss is not None else null,
+                                             _ptr(shown) if shown is not None else null, C.c_void_p(stream or 0)))
 
     def session_record_info(self):
         """ian_session_record_info -> (the pool's layout as a SessionMeta, the byte offsets of its arrays in a body); host only."""

@@ -566,3 +566,53 @@ def session_record_unpack(meta, body):
     for k in range(int(meta["hist_len"])):
         entries.append((ring["HIST_Z"][k], ring["HIST_UMASK"][k]) if "HIST_UMASK" in ring else ring["HIST_Z"][k])
     return fields, entries
+
+
+# ---- fitting the latent to the photo (ian_session_fit): the optimiser and the loss, operation by operation, in numpy ----
+FIT_MAX_STEPS = 512
+FIT_BETA1, FIT_BETA2, FIT_EPS = np.float32(0.9), np.float32(0.999), np.float32(1e-8)
+FIT_ONE_M_BETA1, FIT_ONE_M_BETA2 = np.float32(0.1), np.float32(0.001)   # the literals 0.1f and 0.001f, not 1 - beta
+_FIT_CONSTS = []
+
+
+def fit_adam_consts(steps):
+    """(c1, c2), float32 arrays of length steps + 1 (entry 0 unused, zero): Adam's bias corrections c1[t] = float32(1 / (1 - 0.9**t))
+    and c2[t] = float32(1 / (1 - 0.999**t)), each computed in float64 and rounded once -- the values the library passes to its kernel."""
+    steps = int(steps)
+    if not 1 <= steps <= FIT_MAX_STEPS:
+        raise ValueError("steps must be in 1..%d, got %d" % (FIT_MAX_STEPS, steps))
+    if not _FIT_CONSTS:     # entry t does not depend on steps: the whole table once
+        c1, c2 = np.zeros(FIT_MAX_STEPS + 1, np.float32), np.zeros(FIT_MAX_STEPS + 1, np.float32)
+        for t in range(1, FIT_MAX_STEPS + 1):
+            c1[t] = np.float32(1.0 / (1.0 - 0.9 ** t))
+            c2[t] = np.float32(1.0 / (1.0 - 0.999 ** t))
+        _FIT_CONSTS.extend((c1, c2))
+    return _FIT_CONSTS[0][:steps + 1].copy(), _FIT_CONSTS[1][:steps + 1].copy()
+
+
+def fit_adam_step(z, g, m, v, t, lr):
+    """Adam step t (1-based) of ian_session_fit on float32 arrays of one shape -> (z_new, m_new, v_new).  Every operation is a
+    float32 numpy operation rounded on its own, in the order of csrc/ian_fit_step.h:
+        m = (0.9f * m) + (0.1f * g);  v = (0.999f * v) + ((0.001f * g) * g);  z - ((lr * (m * c1[t])) / (sqrt(v * c2[t]) + 1e-8f))"""
+    z, g, m, v = (np.asarray(a, np.float32) for a in (z, g, m, v))
+    t = int(t)
+    c1, c2 = fit_adam_consts(t)
+    lr = np.float32(lr)
+    m = (FIT_BETA1 * m) + (FIT_ONE_M_BETA1 * g)
+    v = (FIT_BETA2 * v) + ((FIT_ONE_M_BETA2 * g) * g)
+    mh = m * c1[t]
+    vh = v * c2[t]
+    z_new = z - ((lr * mh) / (np.sqrt(vh) + FIT_EPS))
+    assert z_new.dtype == np.float32 and m.dtype == np.float32 and v.dtype == np.float32
+    return z_new, m, v
+
+
+def fit_loss(x, target, box):
+    """The API.py:64 loss of one image: the float64 mean of (float64(x) - float64(target))**2 over channels x rows r1:r2 x columns
+    c1:c2 of (3,64,64) arrays, box = (c1, r1, c2, r2); 0.0 for an empty rectangle."""
+    c1, r1, c2, r2 = (int(b) for b in box)
+    a = np.asarray(x, np.float64)[:, r1:r2, c1:c2]
+    b = np.asarray(target, np.float64)[:, r1:r2, c1:c2]
+    if a.size == 0:
+        return 0.0
+    return float(np.mean((a - b) ** 2))
