@@ -328,7 +328,7 @@ int ian_brush_step(ian_handle* h, int32_t c1, int32_t r1, int32_t c2, int32_t r2
   const int zl = h->desc.num_latents;
   Slot& zs = h->slots[h->desc.z_slot];
   Slot& out = h->slots[h->desc.out_slot];
-  if (c1 < 0 || r1 < 0 || c2 > out.w || r2 > out.h) return fail(h, -7, "patch (%d,%d,%d,%d) outside the %dx%d image", c1, r1, c2, r2, out.w, out.h);
+  if ((rc = check_rect(h, nullptr, 0, c1, r1, c2, r2, "patch"))) return rc;
   const bool photo_host = photo && !is_device_ptr(photo->recon) && !is_device_ptr(photo->error) && !is_device_ptr(photo->im) &&
                           !(photo->mask && is_device_ptr(photo->mask));
   if (!edit_graph_eligible(h, stream, {rgb}) || (photo && !photo_host)) {

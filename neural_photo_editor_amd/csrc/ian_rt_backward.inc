@@ -46,8 +46,8 @@ int run_decoder_backward(ian_handle* h, BrushBackward& rq, hipStream_t st) {
   if (last.d.dst != h->desc.out_slot) return fail(h, -9, "imgrad: the last decoder op does not produce l_out");
   Slot& out = h->slots[last.d.dst];
   const int H = out.h, W = out.w;
-  if (!seed.table && (seed.c1 < 0 || seed.r1 < 0 || seed.c2 > W || seed.r2 > H))   // a table's rows were checked by the caller that filled it
-    return fail(h, -7, "patch (%d,%d,%d,%d) outside the %dx%d image", seed.c1, seed.r1, seed.c2, seed.r2, W, H);
+  if (!seed.table)   // a table's rows were checked by the caller that filled it
+    if (int rc = check_rect(h, nullptr, 0, seed.c1, seed.r1, seed.c2, seed.r2, "patch")) return rc;
   if (!h->d_gseed) {
     HIPCHK(h, hipMalloc((void**)&h->d_gseed, (size_t)3 * H * W * sizeof(float)));
     h->gseed_cap = (size_t)3 * H * W;

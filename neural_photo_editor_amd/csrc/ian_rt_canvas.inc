@@ -299,18 +299,8 @@ int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int
 }
 
 int canvas_compose(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, uint8_t* out, void* stream) {
-  const char* fn = "ian_canvas_compose";
-  int rc = canvas_window_check(h, fn, n, w, vw, vh, out);
-  if (rc) return rc;
-  unsigned char* d_out = nullptr;
-  bool out_dev = false;
-  const size_t bytes = (size_t)n * 3 * (size_t)vh * (size_t)vw;
-  if ((rc = session_render_target(h, out, bytes, &d_out, &out_dev))) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if ((rc = session_rows_enter(h, st))) return rc;
-  if ((rc = canvas_compose_enqueue(h, n, w, vw, vh, d_out, st))) return rc;
-  if (!out_dev) HIPCHK(h, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
-  return session_rows_leave(h, st, out_dev);
+  if (int rc = canvas_window_check(h, "ian_canvas_compose", n, w, vw, vh, out)) return rc;
+  return window_call(h, n, vw, vh, out, stream, [&](unsigned char* d, hipStream_t st) { return canvas_compose_enqueue(h, n, w, vw, vh, d, st); });
 }
 
 int canvas_commit(ian_handle* h, int canvas, uint8_t* shown, void* stream) {
@@ -354,7 +344,7 @@ int ian_canvas_brush(ian_handle* h, int32_t n, const ian_session_event* events, 
                      const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
   if (!h) return -1;
   if (!windows) return fail(h, -1, "null pointer passed to ian_canvas_brush");
-  return session_brush(h, n, events, shown, stream, false, nullptr, vw, vh, out, m, windows);
+  return session_brush(h, n, events, shown, stream, BrushWindows{BrushWindows::CANVAS, nullptr, windows, m, vw, vh, out});
 }
 int ian_canvas_commit(ian_handle* h, int32_t canvas, uint8_t* shown, void* stream) {
   return h ? canvas_commit(h, canvas, shown, stream) : -1;

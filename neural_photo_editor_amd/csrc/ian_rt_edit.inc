@@ -220,8 +220,7 @@ int grad_common(ian_handle* h, int mode, int c1, int r1, int c2, int r2, const f
   if (!z || !dz) return fail(h, -1, "null pointer passed to ian_grad_*");
   Slot& zs = h->slots[h->desc.z_slot];
   if (edit_graph_eligible(h, stream, {z, dz, rgb})) {
-    Slot& out = h->slots[h->desc.out_slot];
-    if (c1 < 0 || r1 < 0 || c2 > out.w || r2 > out.h) return fail(h, -7, "patch (%d,%d,%d,%d) outside the %dx%d image", c1, r1, c2, r2, out.w, out.h);
+    if ((rc = check_rect(h, nullptr, 0, c1, r1, c2, r2, "patch"))) return rc;
     if ((rc = edit_ctx(h))) return rc;
     hipStream_t st = h->edit_stream;
     enter_stream(h, st);
@@ -419,8 +418,7 @@ int batch_common(ian_handle* h, int n, const ian_brush_item* items, const float*
     const ian_brush_item& it = items[i];
     if (it.mode != 0 && it.mode != 1) return fail(h, -7, "%s: item %d has mode %d (0 = imgrad, 1 = imgradRGB)", fn, i, it.mode);
     if (it.mode == 1 && !rgb) return fail(h, -1, "%s: item %d has mode 1 (imgradRGB) but rgb is NULL", fn, i);
-    if (it.c1 < 0 || it.r1 < 0 || it.c2 > out.w || it.r2 > out.h)
-      return fail(h, -7, "%s: item %d: patch (%d,%d,%d,%d) outside the %dx%d image", fn, i, it.c1, it.r1, it.c2, it.r2, out.w, out.h);
+    if ((rc = check_rect(h, fn, i, it.c1, it.r1, it.c2, it.r2, "patch"))) return rc;
     any_rgb = any_rgb || it.mode == 1;
   }
   if (photo) {

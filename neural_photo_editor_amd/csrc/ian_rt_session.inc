@@ -409,6 +409,15 @@ int session_rows_leave(ian_handle* h, hipStream_t st, bool device_result) {
   return 0;
 }
 
+// one session id: in the pool and, where the call needs it, opened; item < 0: the call names one session only
+int session_check_one(ian_handle* h, const char* fn, int item, int id, bool need_opened) {
+  const bool outside = id < 0 || id >= h->sess.capacity;
+  if (!outside && (!need_opened || h->sess.opened[id])) return 0;   // the common case formats nothing
+  char where[32] = "";
+  if (item >= 0) snprintf(where, sizeof where, "item %d: ", item);
+  if (outside) return fail(h, -7, "%s: %ssession %d outside the pool (capacity %d)", fn, where, id, h->sess.capacity);
+  return fail(h, -7, "%s: %ssession %d has not been opened", fn, where, id);
+}
 // what every session call checks first: the model, the pool, n; then per item its id (ids[i * stride]).  Nothing is enqueued or
 // written before all of it passed.
 int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int stride, bool need_opened, bool need_blend) {
@@ -423,8 +432,7 @@ int session_check(ian_handle* h, const char* fn, int n, const int32_t* ids, int 
   std::map<int, int> first;
   for (int i = 0; i < n; ++i) {
     const int id = ids[(size_t)i * stride];
-    if (id < 0 || id >= S.capacity) return fail(h, -7, "%s: item %d: session %d outside the pool (capacity %d)", fn, i, id, S.capacity);
-    if (need_opened && !S.opened[id]) return fail(h, -7, "%s: item %d: session %d has not been opened", fn, i, id);
+    if ((rc = session_check_one(h, fn, i, id, need_opened))) return rc;
     auto ins = first.emplace(id, i);
     if (!ins.second) return fail(h, -7, "%s: item %d: session %d already appears as item %d of this call", fn, i, id, ins.first->second);
   }
@@ -440,6 +448,11 @@ void session_history_note(decltype(ian_handle::sess)& S, int id, bool clear) {
     session_history_clear(S.hist[id]);
   else
     session_history_edited(S.hist[id], S.arr.rings.depth);
+}
+// a call wrote session id's latent: a new version (what the residency of ian_session_brush is keyed by) and the history's note of it
+void session_latent_written(decltype(ian_handle::sess)& S, int id, bool clear) {
+  ++S.version[id];
+  session_history_note(S, id, clear);
 }
 
 int session_local(ian_handle* h, int n, const int32_t* ids, const int32_t* flags, void* stream) {
@@ -481,13 +494,21 @@ int session_upload_ids(ian_handle* h, int n, const int32_t* ids, hipStream_t st)
   return 0;
 }
 
-// end of a call: the canvas images (and, for ian_session_brush_view, the windows rendered into the staging buffer: out_host with
-// its byte count) to the caller; one synchronisation when host memory was read or written
-int session_finish(ian_handle* h, int n, uint8_t* shown, bool shown_dev, bool host_in, hipStream_t st, uint8_t* out_host = nullptr,
-                   size_t out_bytes = 0) {
-  if (shown && !shown_dev) HIPCHK(h, hipMemcpyAsync(shown, h->sess.d_shown, (size_t)n * SESS_IMG, hipMemcpyDeviceToHost, st));
-  if (out_host) HIPCHK(h, hipMemcpyAsync(out_host, h->sess.d_out, out_bytes, hipMemcpyDeviceToHost, st));
-  if ((shown && !shown_dev) || host_in || out_host) {
+// Where a result array of a call goes.  dev: what the kernels write -- the caller's array when it is device memory, else a staging
+// buffer; nullptr: the call has no such result.  host: the copy down that the end of the call owes; nullptr: none.
+struct ResultTarget { unsigned char* dev; uint8_t* host; };
+// the canvas images: staged in d_shown; need_dev: the kernel (the blend) writes them whether the caller wants them or not
+ResultTarget shown_target(ian_handle* h, uint8_t* shown, bool need_dev) {
+  if (shown && is_device_ptr(shown)) return {shown, nullptr};
+  return {shown || need_dev ? h->sess.d_shown : nullptr, shown};
+}
+// end of a call: the canvas images (and, for ian_session_brush_view / ian_canvas_brush, the rendered windows with their byte count)
+// to the caller; one synchronisation when host memory was read or written
+int session_finish(ian_handle* h, int n, const ResultTarget& shown, bool host_in, hipStream_t st, const ResultTarget& win = {},
+                   size_t win_bytes = 0) {
+  if (shown.host) HIPCHK(h, hipMemcpyAsync(shown.host, shown.dev, (size_t)n * SESS_IMG, hipMemcpyDeviceToHost, st));
+  if (win.host) HIPCHK(h, hipMemcpyAsync(win.host, win.dev, win_bytes, hipMemcpyDeviceToHost, st));
+  if (shown.host || host_in || win.host) {
     HIPCHK(h, hipStreamSynchronize(st));
     h->last_pending = false;
   }
@@ -512,8 +533,7 @@ int session_view_check(ian_handle* h, const char* fn, int n, const ian_session_v
   if (vw & 3) return fail(h, -7, "%s: window width %d is not a multiple of 4", fn, vw);
   for (int i = 0; i < n; ++i) {
     const ian_session_view& v = views[i];
-    if (v.session < 0 || v.session >= S.capacity)
-      return fail(h, -7, "%s: item %d: session %d outside the pool (capacity %d)", fn, i, v.session, S.capacity);
+    if ((rc = session_check_one(h, fn, i, v.session, false))) return rc;
     if (ev && ev[i].session != v.session)
       return fail(h, -7, "%s: item %d: the view names session %d, the event session %d", fn, i, v.session, ev[i].session);
     if (!S.opened[v.session]) return fail(h, -7, "%s: item %d: session %d has not been opened", fn, i, v.session);
@@ -537,12 +557,27 @@ int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, 
 }
 
 // the device buffer a call renders into: the caller's, or the staging buffer grown to the call's size
-int session_render_target(ian_handle* h, uint8_t* out, size_t bytes, unsigned char** d_out, bool* out_dev) {
+int session_render_target(ian_handle* h, uint8_t* out, size_t bytes, ResultTarget* t) {
   auto& S = h->sess;
-  *out_dev = is_device_ptr(out);
-  int rc = *out_dev ? 0 : grow_dev(h, &S.d_out, &S.out_cap, bytes);
-  *d_out = *out_dev ? out : S.d_out;
+  const bool dev = is_device_ptr(out);
+  int rc = dev ? 0 : grow_dev(h, &S.d_out, &S.out_cap, bytes);
+  *t = dev ? ResultTarget{out, nullptr} : ResultTarget{S.d_out, out};
   return rc;
+}
+
+// A call that renders n windows and nothing else (ian_session_render, ian_canvas_compose), after its checks: the render target,
+// session_rows_enter, the caller's enqueue(d_out, st), the copy down for a host array, session_rows_leave.
+template <typename Enqueue>
+int window_call(ian_handle* h, int n, int vw, int vh, uint8_t* out, void* stream, Enqueue enqueue) {
+  const size_t bytes = (size_t)n * 3 * (size_t)vh * (size_t)vw;
+  ResultTarget t = {};
+  int rc = session_render_target(h, out, bytes, &t);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = session_rows_enter(h, st))) return rc;
+  if ((rc = enqueue(t.dev, st))) return rc;
+  if (t.host) HIPCHK(h, hipMemcpyAsync(t.host, t.dev, bytes, hipMemcpyDeviceToHost, st));
+  return session_rows_leave(h, st, !t.host);
 }
 
 int session_open_finish(ian_handle* h, int n, const int32_t* ids, uint8_t* shown, bool host_in, int has_src, hipStream_t st);
@@ -605,16 +640,15 @@ int session_open_finish(ian_handle* h, int n, const int32_t* ids, uint8_t* shown
   if ((rc = run_segment(h, IAN_SEG_IAF, n, st))) return rc;
   if ((rc = run_segment(h, IAN_SEG_DEC, n, st))) return rc;
   h->slot_stale[h->desc.out_slot] = 0;
-  const bool shown_dev = shown && is_device_ptr(shown);
-  HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, S.d_tab, 0, 0, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
+  const ResultTarget sh = shown_target(h, shown, false);
+  HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, S.d_tab, 0, 0, sh.dev, n, st));
   if (S.arr.pool.umask) HIPCHK(h, launch_session_local_set(S.arr.pool, S.d_tab, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:267, :337); LOCAL stays
   for (int i = 0; i < n; ++i) {
     S.opened[ids[i]] = 1;
-    ++S.version[ids[i]];
-    session_history_note(S, ids[i], true);
+    session_latent_written(S, ids[i], true);
     if (has_src >= 0) S.has_src[ids[i]] = (char)has_src;   // a 64x64 photo leaves nothing at full resolution to edit
   }
-  return session_finish(h, n, shown, shown_dev, host_in, st);
+  return session_finish(h, n, sh, host_in, st);
 }
 
 // the blend of `ids` (device) after the decoder ran at their latents: items == nullptr is paint_latents, store != 0 a brush event
@@ -650,17 +684,14 @@ int session_set_latent(ian_handle* h, int n, const int32_t* ids, const float* z,
   if ((rc = set_latent_input(h, h->desc.z_slot, z, n, st))) return rc;
   if ((rc = run_segment(h, IAN_SEG_DEC, n, st))) return rc;   // sample_at(z) at this batch, as ian_decode / ian_decode_u8 run it
   h->slot_stale[h->desc.out_slot] = 0;
-  const bool shown_dev = shown && is_device_ptr(shown);
+  const ResultTarget sh = shown_target(h, shown, as_sample == 0);
   if (as_sample) {
-    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, S.d_tab, 1, 1, shown ? (shown_dev ? shown : S.d_shown) : nullptr, n, st));
+    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, S.d_tab, 1, 1, sh.dev, n, st));
   } else {
-    HIPCHK(h, launch_session_blend(session_blend_args(h, S.d_tab, nullptr, shown_dev ? shown : S.d_shown, 0), n, st));
+    HIPCHK(h, launch_session_blend(session_blend_args(h, S.d_tab, nullptr, sh.dev, 0), n, st));
   }
-  for (int i = 0; i < n; ++i) {
-    ++S.version[ids[i]];
-    session_history_note(S, ids[i], as_sample != 0);
-  }
-  return session_finish(h, n, shown, shown_dev, host_in, st);
+  for (int i = 0; i < n; ++i) session_latent_written(S, ids[i], as_sample != 0);
+  return session_finish(h, n, sh, host_in, st);
 }
 
 int sessions_reserve_history(ian_handle* h, int depth) {
@@ -755,10 +786,10 @@ int session_undo(ian_handle* h, int n, const int32_t* ids, const int32_t* steps,
   HIPCHK(h, launch_session_history_move(S.arr.pool, S.arr.rings, S.d_htab, S.d_htab + n, S.d_htab + (size_t)2 * n, zs.d, zs.cs, n, st));
   if ((rc = run_segment(h, IAN_SEG_DEC, n, st))) return rc;   // sample_at(z) at this batch, as ian_session_set_latent runs it
   h->slot_stale[h->desc.out_slot] = 0;
-  const bool shown_dev = shown && is_device_ptr(shown);
-  HIPCHK(h, launch_session_blend(session_blend_args(h, S.d_htab, nullptr, shown_dev ? shown : S.d_shown, 1), n, st));
+  const ResultTarget sh = shown_target(h, shown, true);
+  HIPCHK(h, launch_session_blend(session_blend_args(h, S.d_htab, nullptr, sh.dev, 1), n, st));
   for (int i = 0; i < n; ++i) ++S.version[ids[i]];
-  if ((rc = session_finish(h, n, shown, shown_dev, false, st))) return rc;
+  if ((rc = session_finish(h, n, sh, false, st))) return rc;
   for (int i = 0; i < n; ++i) S.hist[ids[i]] = next[i];   // not `edited`: this call is what moves the cursor
   return 0;
 }
@@ -771,84 +802,87 @@ int session_history(ian_handle* h, int id, int32_t* out) {
   if (S.capacity > 0 && (rc = session_need(h, fn, SESS_HISTORY))) return rc;
   if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (!out) return fail(h, -1, "null pointer passed to %s", fn);
-  if (id < 0 || id >= S.capacity) return fail(h, -7, "%s: session %d outside the pool (capacity %d)", fn, id, S.capacity);
-  if (!S.opened[id]) return fail(h, -7, "%s: session %d has not been opened", fn, id);
+  if ((rc = session_check_one(h, fn, -1, id, true))) return rc;
   out[0] = S.arr.rings.depth;
   out[1] = session_history_undoable(S.hist[id]);
   out[2] = session_history_redoable(S.hist[id]);
   return 0;
 }
 
-// with_view: ian_session_brush_view: after the brush, in the same submission, window i of session views[i].session (== ev[i].session)
-// -> out, and one synchronisation for both results.
-// windows given: ian_canvas_brush: after the brush, in the same submission, m windows of canvases -> win, likewise.
-int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream, bool with_view = false,
-                  const ian_session_view* views = nullptr, int vw = 0, int vh = 0, uint8_t* win = nullptr, int m = 0,
-                  const ian_canvas_window* windows = nullptr) {
-  const bool with_canvas = !with_view && (windows != nullptr || m != 0);
-  const char* fn = with_canvas ? "ian_canvas_brush" : (with_view ? "ian_session_brush_view" : "ian_session_brush");
+// The table of a brush or a fit in d_tab: n ian_brush_item rows of 7 words (what the shared middle reads), then the n session ids,
+// then, for a brush, the n colours of 3 floats.  fill(i, row, id, colour) writes item i into the zeroed shadow (colour: nullptr
+// without colours); one copy up; -> the three parts on the device.
+struct BrushTable { const int* items; const int* ids; const float* colour; };
+template <typename Fill>
+int brush_table_upload(ian_handle* h, int n, bool colours, hipStream_t st, BrushTable* T, Fill fill) {
+  auto& S = h->sess;
+  const size_t words = (size_t)(colours ? 11 : 8) * n;
+  S.tab_shadow.assign(words, 0);
+  int32_t* t = S.tab_shadow.data();
+  for (int i = 0; i < n; ++i) fill(i, t + (size_t)7 * i, t + (size_t)7 * n + i, colours ? t + (size_t)8 * n + (size_t)3 * i : nullptr);
+  HIPCHK(h, hipMemcpyAsync(S.d_tab, t, words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  *T = BrushTable{S.d_tab, S.d_tab + (size_t)7 * n, colours ? reinterpret_cast<const float*>(S.d_tab + (size_t)8 * n) : nullptr};
+  return 0;
+}
+// What a brush renders after the events, in the same submission, one synchronisation for both results: nothing (ian_session_brush),
+// window i of session views[i].session == ev[i].session (ian_session_brush_view: count == n) or canvas windows (ian_canvas_brush) -> out
+struct BrushWindows {
+  enum Kind { NONE, VIEWS, CANVAS } kind;
+  const ian_session_view* views;       // VIEWS: [count]
+  const ian_canvas_window* windows;    // CANVAS: [count]
+  int count, vw, vh;
+  uint8_t* out;
+};
+int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream, const BrushWindows& W) {
+  const char* fn = W.kind == W.CANVAS ? "ian_canvas_brush" : (W.kind == W.VIEWS ? "ian_session_brush_view" : "ian_session_brush");
   static_assert(sizeof(ian_session_event) == 11 * sizeof(int32_t), "ian_session_event is 11 words");
   int rc = session_check(h, fn, n, ev ? &ev->session : nullptr, 11, true, true);
   if (rc) return rc;
-  Slot& out = h->slots[h->desc.out_slot];
   for (int i = 0; i < n; ++i) {
     const ian_session_event& e = ev[i];
     if (e.mode != 0 && e.mode != 1) return fail(h, -7, "%s: item %d has mode %d (0 = imgrad, 1 = imgradRGB toward rgb)", fn, i, e.mode);
-    if (e.c1 < 0 || e.r1 < 0 || e.c2 > out.w || e.r2 > out.h)
-      return fail(h, -7, "%s: item %d: patch (%d,%d,%d,%d) outside the %dx%d image", fn, i, e.c1, e.r1, e.c2, e.r2, out.w, out.h);
+    if ((rc = check_rect(h, fn, i, e.c1, e.r1, e.c2, e.r2, "patch"))) return rc;
   }
   if ((rc = session_local_check(h, fn, n, &ev->session, 11))) return rc;
   auto& S = h->sess;
-  unsigned char* d_out = nullptr;
-  bool out_dev = false;
-  const size_t out_bytes = (size_t)(with_canvas ? (m > 0 ? m : 0) : n) * 3 * (size_t)(vh > 0 ? vh : 0) * (size_t)(vw > 0 ? vw : 0);
-  if (with_view && (rc = session_view_check(h, fn, n, views, vw, vh, win, ev))) return rc;
-  if (with_canvas && (rc = canvas_window_check(h, fn, m, windows, vw, vh, win))) return rc;
-  if ((with_view || with_canvas) && (rc = session_render_target(h, win, out_bytes, &d_out, &out_dev))) return rc;
+  if (W.kind == W.VIEWS && (rc = session_view_check(h, fn, W.count, W.views, W.vw, W.vh, W.out, ev))) return rc;
+  if (W.kind == W.CANVAS && (rc = canvas_window_check(h, fn, W.count, W.windows, W.vw, W.vh, W.out))) return rc;
+  ResultTarget win = {};
+  const size_t win_bytes = (size_t)W.count * 3 * (size_t)W.vh * (size_t)W.vw;
+  if (W.kind != W.NONE && (rc = session_render_target(h, W.out, win_bytes, &win))) return rc;
   const int pass = h->opt.brush_pass;
   bool hit = n <= pass && S.res_valid && (int)S.res_ids.size() == n && getenv("IAN_NO_DEC_CACHE") == nullptr;
   for (int i = 0; hit && i < n; ++i) hit = S.res_ids[i] == ev[i].session && S.res_ver[i] == S.version[ev[i].session];
   hipStream_t st = (hipStream_t)stream;
   session_enter(h, st);   // also ends the residency: re-armed below
   TotalTimer tt(h, st);
-  // the event table, rearranged for the kernels: n ian_brush_item records (the shared middle reads them), n ids, n colours
-  S.tab_shadow.resize((size_t)11 * n);
-  int32_t* t_items = S.tab_shadow.data();
-  int32_t* t_ids = t_items + (size_t)7 * n;
-  int32_t* t_col = t_ids + n;
-  for (int i = 0; i < n; ++i) {
-    memcpy(t_items + (size_t)7 * i, &ev[i].c1, 7 * sizeof(int32_t));   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
-    t_ids[i] = ev[i].session;
-    memcpy(t_col + (size_t)3 * i, ev[i].rgb, 3 * sizeof(float));
-  }
-  HIPCHK(h, hipMemcpyAsync(S.d_tab, S.tab_shadow.data(), (size_t)11 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  const int* d_items = S.d_tab;
-  const int* d_ids = S.d_tab + (size_t)7 * n;
-  const float* d_col = reinterpret_cast<const float*>(S.d_tab + (size_t)8 * n);
+  BrushTable tab;   // the event table, rearranged for the kernels
+  rc = brush_table_upload(h, n, true, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* colour) {
+    memcpy(row, &ev[i].c1, 7 * sizeof(int32_t));   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
+    *id = ev[i].session;
+    memcpy(colour, ev[i].rgb, 3 * sizeof(float));
+  });
+  if (rc) return rc;
   Slot& zs = h->slots[h->desc.z_slot];
-  const bool shown_dev = shown && is_device_ptr(shown);
-  unsigned char* d_shown = shown_dev ? shown : S.d_shown;
+  const ResultTarget sh = shown_target(h, shown, true);
   for (int off = 0; off < n; off += pass) {
     const int nc = std::min(pass, n - off);
     if (!hit) {
       if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
-      HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
+      HIPCHK(h, launch_session_gather_z(S.arr.pool, tab.ids + off, zs.d, zs.cs, nc, st));
       if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
     }
     BrushSeedSrc seed;
-    seed.table = d_items + (size_t)7 * off;
-    seed.colour = d_col + (size_t)3 * off;
+    seed.table = tab.items + (size_t)7 * off;
+    seed.colour = tab.colour + (size_t)3 * off;
     if ((rc = brush_pass_middle(h, nc, seed, true, st))) return rc;
-    HIPCHK(h, launch_session_blend(session_blend_args(h, d_ids + off, d_items + (size_t)7 * off, d_shown + (size_t)off * SESS_IMG, 1), nc, st));
+    HIPCHK(h, launch_session_blend(session_blend_args(h, tab.ids + off, seed.table, sh.dev + (size_t)off * SESS_IMG, 1), nc, st));
   }
   h->slot_stale[h->desc.out_slot] = 0;
-  for (int i = 0; i < n; ++i) {
-    ++S.version[ev[i].session];
-    session_history_note(S, ev[i].session, false);
-  }
-  if (with_view && (rc = session_render_enqueue(h, n, views, vw, vh, d_out, st))) return rc;
-  if (with_canvas && (rc = canvas_compose_enqueue(h, m, windows, vw, vh, d_out, st))) return rc;
-  if ((rc = session_finish(h, n, shown, shown_dev, false, st, (with_view || with_canvas) && !out_dev ? win : nullptr, out_bytes))) return rc;
+  for (int i = 0; i < n; ++i) session_latent_written(S, ev[i].session, false);
+  if (W.kind == W.VIEWS && (rc = session_render_enqueue(h, W.count, W.views, W.vw, W.vh, win.dev, st))) return rc;
+  if (W.kind == W.CANVAS && (rc = canvas_compose_enqueue(h, W.count, W.windows, W.vw, W.vh, win.dev, st))) return rc;
+  if ((rc = session_finish(h, n, sh, false, st, win, win_bytes))) return rc;
   if (n <= pass) {   // one pass: the resident activations belong to these sessions' new latents
     S.res_ids.resize(n);
     S.res_ver.resize(n);
@@ -872,11 +906,8 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
   int rc = session_check(h, fn, n, items ? &items->session : nullptr, 5, true, false);
   if (rc) return rc;
   Slot& out = h->slots[h->desc.out_slot];
-  for (int i = 0; i < n; ++i) {
-    const ian_session_fit_item& e = items[i];
-    if (e.c1 < 0 || e.r1 < 0 || e.c2 > out.w || e.r2 > out.h)
-      return fail(h, -7, "%s: item %d: rectangle (%d,%d,%d,%d) outside the %dx%d image", fn, i, e.c1, e.r1, e.c2, e.r2, out.w, out.h);
-  }
+  for (int i = 0; i < n; ++i)
+    if ((rc = check_rect(h, fn, i, items[i].c1, items[i].r1, items[i].c2, items[i].r2, "rectangle"))) return rc;
   if (steps < 1 || steps > SESS_FIT_MAX_STEPS) return fail(h, -7, "%s: steps = %d outside 1..%d", fn, steps, SESS_FIT_MAX_STEPS);
   if (!std::isfinite(lr) || !(lr > 0.f)) return fail(h, -7, "%s: lr = %g is not a finite positive number", fn, (double)lr);
   auto& S = h->sess;
@@ -895,36 +926,31 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
   hipStream_t st = (hipStream_t)stream;
   session_enter(h, st);   // also ends the residency of ian_session_brush: not re-armed, the last forward keeps no activations
   TotalTimer tt(h, st);
-  // the table: n ian_brush_item rows (the rectangle, loss kind 1; coef and gscale unused), then the n ids
-  S.tab_shadow.assign((size_t)8 * n, 0);
-  for (int i = 0; i < n; ++i) {
-    int32_t* row = S.tab_shadow.data() + (size_t)7 * i;
+  BrushTable tab;   // the rows: the rectangle, loss kind 1; coef and gscale unused
+  rc = brush_table_upload(h, n, false, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t*) {
     row[0] = items[i].c1; row[1] = items[i].r1; row[2] = items[i].c2; row[3] = items[i].r2; row[4] = 1;
-    S.tab_shadow[(size_t)7 * n + i] = items[i].session;
-  }
-  HIPCHK(h, hipMemcpyAsync(S.d_tab, S.tab_shadow.data(), (size_t)8 * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  const int* d_items = S.d_tab;
-  const int* d_ids = S.d_tab + (size_t)7 * n;
-  HIPCHK(h, launch_session_fit_begin(S.arr.pool, d_ids, n, st));   // IM := GIM (NPE.py:332)
+    *id = items[i].session;
+  });
+  if (rc) return rc;
+  HIPCHK(h, launch_session_fit_begin(S.arr.pool, tab.ids, n, st));   // IM := GIM (NPE.py:332)
   Slot& zs = h->slots[h->desc.z_slot];
   double* d_loss = loss ? (loss_dev ? loss : S.d_fit_loss) : nullptr;
-  const bool shown_dev = shown && is_device_ptr(shown);
-  unsigned char* d_shown = shown ? (shown_dev ? shown : S.d_shown) : nullptr;
+  const ResultTarget sh = shown_target(h, shown, false);
   const int pass = h->opt.brush_pass;
   for (int off = 0; off < n; off += pass) {
     const int nc = std::min(pass, n - off);
     if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
-    HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
+    HIPCHK(h, launch_session_gather_z(S.arr.pool, tab.ids + off, zs.d, zs.cs, nc, st));
     float* m = S.d_fit;
     float* v = S.d_fit + (size_t)nc * zl;
     HIPCHK(h, hipMemsetAsync(S.d_fit, 0, (size_t)2 * nc * zl * sizeof(float), st));   // the moments start at zero on every call
     BrushSeedSrc seed;
-    seed.table = d_items + (size_t)7 * off;
+    seed.table = tab.items + (size_t)7 * off;
     seed.gim = S.arr.pool.gim;
-    seed.ids = d_ids + off;
+    seed.ids = tab.ids + off;
     seed.tanh_tab = S.d_tanh;
     auto read_loss = [&](int t) -> hipError_t {
-      return launch_session_fit_loss(out.d, S.arr.pool, d_ids + off, seed.table, S.d_tanh, d_loss + (size_t)off * lstride + t, lstride, nc, st);
+      return launch_session_fit_loss(out.d, S.arr.pool, seed.ids, seed.table, S.d_tanh, d_loss + (size_t)off * lstride + t, lstride, nc, st);
     };
     for (int t = 1; t <= steps; ++t) {
       if ((rc = batch_forward(h, nullptr, nc, st))) return rc;   // sample_at(Z_{t-1}), every activation kept
@@ -934,33 +960,19 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
     }
     if ((rc = run_segment(h, IAN_SEG_DEC, nc, st))) return rc;   // sample_at(Z_steps) at this batch, as ian_decode_u8 runs it
     if (d_loss) HIPCHK(h, read_loss(steps));
-    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, d_ids + off, 0, 1, d_shown ? d_shown + (size_t)off * SESS_IMG : nullptr, nc, st));
+    HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, seed.ids, 0, 1, sh.dev ? sh.dev + (size_t)off * SESS_IMG : nullptr, nc, st));
   }
   h->slot_stale[h->desc.out_slot] = 0;
-  if (S.arr.pool.umask) HIPCHK(h, launch_session_local_set(S.arr.pool, d_ids, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:337); LOCAL stays
-  for (int i = 0; i < n; ++i) {   // as session_open_finish: a new latent version, the saved states no longer belong to the picture
-    ++S.version[items[i].session];
-    session_history_note(S, items[i].session, true);
-  }
+  if (S.arr.pool.umask) HIPCHK(h, launch_session_local_set(S.arr.pool, tab.ids, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:337); LOCAL stays
+  for (int i = 0; i < n; ++i) session_latent_written(S, items[i].session, true);   // the saved states no longer belong to the picture
   const bool loss_host = loss && !loss_dev;
   if (loss_host) HIPCHK(h, hipMemcpyAsync(loss, S.d_fit_loss, (size_t)n * lstride * sizeof(double), hipMemcpyDeviceToHost, st));
-  return session_finish(h, n, shown, shown_dev, loss_host, st);
+  return session_finish(h, n, sh, loss_host, st);
 }
 
 int session_render(ian_handle* h, int n, const ian_session_view* views, int vw, int vh, uint8_t* out, void* stream) {
-  const char* fn = "ian_session_render";
-  int rc = session_view_check(h, fn, n, views, vw, vh, out, nullptr);
-  if (rc) return rc;
-  auto& S = h->sess;
-  unsigned char* d_out = nullptr;
-  bool out_dev = false;
-  const size_t bytes = (size_t)n * 3 * (size_t)vh * (size_t)vw;
-  if ((rc = session_render_target(h, out, bytes, &d_out, &out_dev))) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if ((rc = session_rows_enter(h, st))) return rc;
-  if ((rc = session_render_enqueue(h, n, views, vw, vh, d_out, st))) return rc;
-  if (!out_dev) HIPCHK(h, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
-  return session_rows_leave(h, st, out_dev);
+  if (int rc = session_view_check(h, "ian_session_render", n, views, vw, vh, out, nullptr)) return rc;
+  return window_call(h, n, vw, vh, out, stream, [&](unsigned char* d, hipStream_t st) { return session_render_enqueue(h, n, views, vw, vh, d, st); });
 }
 
 int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
@@ -970,8 +982,7 @@ int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
   auto& S = h->sess;
   if ((rc = session_need(h, fn, SESS_BASE))) return rc;
   if (!out) return fail(h, -1, "null pointer passed to %s", fn);
-  if (id < 0 || id >= S.capacity) return fail(h, -7, "%s: session %d outside the pool (capacity %d)", fn, id, S.capacity);
-  if (!S.opened[id]) return fail(h, -7, "%s: session %d has not been opened", fn, id);
+  if ((rc = session_check_one(h, fn, -1, id, true))) return rc;
   const SessColumn* col = nullptr;
   for (const SessColumn& c : SESS_COLUMNS)
     if (c.field >= 0 && c.field == what) col = &c;
@@ -1151,13 +1162,13 @@ int ian_session_render(ian_handle* h, int32_t n, const ian_session_view* views, 
 }
 int ian_session_brush_view(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, const ian_session_view* views,
                            int32_t vw, int32_t vh, uint8_t* out, void* stream) {
-  return h ? session_brush(h, n, events, shown, stream, true, views, vw, vh, out) : -1;
+  return h ? session_brush(h, n, events, shown, stream, BrushWindows{BrushWindows::VIEWS, views, nullptr, n, vw, vh, out}) : -1;
 }
 int ian_session_set_latent(ian_handle* h, int32_t n, const int32_t* ids, const float* z, int32_t as_sample, uint8_t* shown, void* stream) {
   return h ? session_set_latent(h, n, ids, z, as_sample, shown, stream) : -1;
 }
 int ian_session_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, void* stream) {
-  return h ? session_brush(h, n, events, shown, stream) : -1;
+  return h ? session_brush(h, n, events, shown, stream, BrushWindows{}) : -1;
 }
 int ian_session_read(ian_handle* h, int32_t id, int32_t what, void* out, void* stream) {
   return h ? session_read(h, id, what, out, stream) : -1;

@@ -110,6 +110,16 @@ int fail(ian_handle* h, int code, const char* fmt, ...) {
   return code;
 }
 
+// the rectangle (c1,r1)-(c2,r2) of a brush, a loss or a fit lies inside the model's image; fn != nullptr: item `item` of a batched
+// call fn.  `what` is the caller's word for it ("patch", "rectangle").
+int check_rect(ian_handle* h, const char* fn, int item, int c1, int r1, int c2, int r2, const char* what) {
+  const Slot& out = h->slots[h->desc.out_slot];
+  if (c1 >= 0 && r1 >= 0 && c2 <= out.w && r2 <= out.h) return 0;
+  char where[96] = "";
+  if (fn) snprintf(where, sizeof where, "%s: item %d: ", fn, item);
+  return fail(h, -7, "%s%s (%d,%d,%d,%d) outside the %dx%d image", where, what, c1, r1, c2, r2, out.w, out.h);
+}
+
 #define HIPCHK(h, expr)                                                                            \
   do {                                                                                             \
     hipError_t _e = (expr);                                                                        \

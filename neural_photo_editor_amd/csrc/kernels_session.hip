@@ -16,6 +16,7 @@
 //   session_pack_kernel / session_unpack_kernel  saved sessions: every row of a session, its ring included, to and from one record
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
 #include <cstring>
+#include <type_traits>
 
 #include "ian_internal.h"
 
@@ -125,61 +126,61 @@ __device__ __forceinline__ char* rec_addr(const RecSel& s, const int4 it, unsign
   return s.base + row * s.unit + w;
 }
 
-__global__ __launch_bounds__(REC_T) void session_pack_kernel(SessionRecordCols T, SessionRecordBases B,
-                                                             const int* __restrict__ items, unsigned char* __restrict__ body) {
+// One walk for both directions.  PACK: the pool's side is loaded (ring slots rotated into canonical order) and the record stored;
+// otherwise the record is loaded and the pool's side stored (the ring restarts at slot 0: no rotation).  Either way all loads of a
+// lane's REC_PIECES pieces are issued before its stores.
+template <bool PACK>
+using RecBody = std::conditional_t<PACK, unsigned char, const unsigned char>;
+template <bool PACK>
+__device__ __forceinline__ void session_record_walk(const SessionRecordCols& T, const SessionRecordBases& B, const int* __restrict__ items,
+                                                    RecBody<PACK>* __restrict__ body) {
   const int i = blockIdx.y;
   const int4 it = reinterpret_cast<const int4*>(items)[i];
-  unsigned char* rec = body + (size_t)i * T.body_bytes;
+  RecBody<PACK>* rec = body + (size_t)i * T.body_bytes;
   uint4 v[REC_PIECES];
+  // the pool's side of piece p (already loaded into / still to be stored from v[p]); the 16-byte path or word by word
+  auto pool_side = [&](int p, unsigned o) {
+    const RecSel s = rec_select(T, B, o);
+    const unsigned w = o - s.off;
+    if ((s.unit & 15u) == 0) {
+      if (char* a = rec_addr(s, it, w, PACK)) {
+        if constexpr (PACK) v[p] = *reinterpret_cast<const uint4*>(a);
+        else *reinterpret_cast<uint4*>(a) = v[p];
+      }
+    } else {
+      unsigned t[4] = {v[p].x, v[p].y, v[p].z, v[p].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (char* a = rec_addr(s, it, w + 4u * j, PACK)) {
+          if constexpr (PACK) t[j] = *reinterpret_cast<const unsigned*>(a);
+          else *reinterpret_cast<unsigned*>(a) = t[j];
+        }
+      if constexpr (PACK) v[p] = make_uint4(t[0], t[1], t[2], t[3]);
+    }
+  };
 #pragma unroll
   for (int p = 0; p < REC_PIECES; ++p) {
     const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
     v[p] = make_uint4(0u, 0u, 0u, 0u);
     if (o >= T.body_bytes) continue;
-    const RecSel s = rec_select(T, B, o);
-    const unsigned w = o - s.off;
-    if ((s.unit & 15u) == 0) {
-      if (const char* a = rec_addr(s, it, w, true)) v[p] = *reinterpret_cast<const uint4*>(a);
-    } else {
-      unsigned t[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (const char* a = rec_addr(s, it, w + 4u * j, true)) t[j] = *reinterpret_cast<const unsigned*>(a);
-      v[p] = make_uint4(t[0], t[1], t[2], t[3]);
-    }
-  }
-#pragma unroll
-  for (int p = 0; p < REC_PIECES; ++p) {
-    const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
-    if (o < T.body_bytes) *reinterpret_cast<uint4*>(rec + o) = v[p];
-  }
-}
-__global__ __launch_bounds__(REC_T) void session_unpack_kernel(SessionRecordCols T, SessionRecordBases B,
-                                                               const int* __restrict__ items, const unsigned char* __restrict__ body) {
-  const int i = blockIdx.y;
-  const int4 it = reinterpret_cast<const int4*>(items)[i];
-  const unsigned char* rec = body + (size_t)i * T.body_bytes;
-  uint4 v[REC_PIECES];
-#pragma unroll
-  for (int p = 0; p < REC_PIECES; ++p) {
-    const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
-    v[p] = o < T.body_bytes ? *reinterpret_cast<const uint4*>(rec + o) : make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (PACK) pool_side(p, o);
+    else v[p] = *reinterpret_cast<const uint4*>(rec + o);
   }
 #pragma unroll
   for (int p = 0; p < REC_PIECES; ++p) {
     const unsigned o = blockIdx.x * (unsigned)REC_CHUNK + (unsigned)(p * REC_T + threadIdx.x) * 16u;
     if (o >= T.body_bytes) continue;
-    const RecSel s = rec_select(T, B, o);
-    const unsigned w = o - s.off;
-    if ((s.unit & 15u) == 0) {
-      if (char* a = rec_addr(s, it, w, false)) *reinterpret_cast<uint4*>(a) = v[p];
-    } else {
-      const unsigned t[4] = {v[p].x, v[p].y, v[p].z, v[p].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (char* a = rec_addr(s, it, w + 4u * j, false)) *reinterpret_cast<unsigned*>(a) = t[j];
-    }
+    if constexpr (PACK) *reinterpret_cast<uint4*>(rec + o) = v[p];
+    else pool_side(p, o);
   }
+}
+__global__ __launch_bounds__(REC_T) void session_pack_kernel(SessionRecordCols T, SessionRecordBases B, const int* __restrict__ items,
+                                                             unsigned char* __restrict__ body) {
+  session_record_walk<true>(T, B, items, body);
+}
+__global__ __launch_bounds__(REC_T) void session_unpack_kernel(SessionRecordCols T, SessionRecordBases B, const int* __restrict__ items,
+                                                               const unsigned char* __restrict__ body) {
+  session_record_walk<false>(T, B, items, body);
 }
 // What both launchers refuse: a table that does not describe these arrays (every offset and size is checked here, so that no lane
 // can be sent outside a row), a body that is not 16-byte aligned.  -> B: the arrays' pointers, taken out of P and R here: a kernel
@@ -203,19 +204,21 @@ static bool session_record_args_ok(const SessionPool& P, const SessionRings& R, 
   }
   return end == T.body_bytes;
 }
-hipError_t launch_session_pack(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
-                               unsigned char* body, int n, hipStream_t s) {
+template <typename Body>
+static hipError_t launch_session_record(void (*kernel)(SessionRecordCols, SessionRecordBases, const int*, Body*), const SessionPool& P,
+                                        const SessionRings& R, const SessionRecordCols& T, const int* items, Body* body, int n, hipStream_t s) {
   SessionRecordBases B;
   if (!session_record_args_ok(P, R, T, items, body, n, B)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_pack_kernel, dim3((T.body_bytes + REC_CHUNK - 1) / REC_CHUNK, n), dim3(REC_T), 0, s, T, B, items, body);
+  hipLaunchKernelGGL(kernel, dim3((T.body_bytes + REC_CHUNK - 1) / REC_CHUNK, n), dim3(REC_T), 0, s, T, B, items, body);
   return hipGetLastError();
+}
+hipError_t launch_session_pack(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
+                               unsigned char* body, int n, hipStream_t s) {
+  return launch_session_record(session_pack_kernel, P, R, T, items, body, n, s);
 }
 hipError_t launch_session_unpack(const SessionPool& P, const SessionRings& R, const SessionRecordCols& T, const int* items,
                                  const unsigned char* body, int n, hipStream_t s) {
-  SessionRecordBases B;
-  if (!session_record_args_ok(P, R, T, items, body, n, B)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_unpack_kernel, dim3((T.body_bytes + REC_CHUNK - 1) / REC_CHUNK, n), dim3(REC_T), 0, s, T, B, items, body);
-  return hipGetLastError();
+  return launch_session_record(session_unpack_kernel, P, R, T, items, body, n, s);
 }
 
 }  // namespace ian
@@ -227,6 +230,23 @@ namespace ian {
 
 constexpr int S_IMG = 3 * 64 * 64;
 
+// the host's to_tanh table of the 256 uint8 levels (ian_session_tanh_table) -> LDS.  The barrier also publishes whatever the caller
+// wrote to LDS before the call.  T: the workgroup's size where the kernel fixes it (256: one load and one store per lane, no loop
+// left), 0: whatever the launch chose.
+template <int T = 0>
+__device__ __forceinline__ void stage_tanh_table(float* tab, const float* __restrict__ table) {
+  for (int j = threadIdx.x; j < 256; j += T ? T : blockDim.x) tab[j] = table[j];
+  __syncthreads();
+}
+// what every open writes per uchar4 at offset o of a 3x64x64 row: GIM and IM of session id, and the encoder's input row i,
+// x = np.asarray([to_tanh(IM)], dtype=np.float32) through the table
+__device__ __forceinline__ void store_opened_px(const SessionPool& P, int id, int i, size_t o, const uchar4 v, const float* tab,
+                                                float* __restrict__ x) {
+  *reinterpret_cast<uchar4*>(P.gim + (size_t)id * S_IMG + o) = v;
+  *reinterpret_cast<uchar4*>(P.im + (size_t)id * S_IMG + o) = v;
+  *reinterpret_cast<float4*>(x + (size_t)i * S_IMG + o) = make_float4(tab[v.x], tab[v.y], tab[v.z], tab[v.w]);
+}
+
 // ---- open, input side (NPE.py:244-257 infer, :332-333 Reset, :344 UpdateGIM) --------------------------------------------------
 // grid (S_IMG / 1024, n), a lane owns 4 consecutive bytes.  The source row is photos[i] (a new photo), the session's GIM (Reset) or
 // its IM (UpdateGIM); it becomes GIM and IM, and x[i] = np.asarray([to_tanh(IM)], dtype=np.float32): the host builds `table` with
@@ -235,16 +255,13 @@ __global__ __launch_bounds__(256) void session_open_in_kernel(const unsigned cha
                                                               const int* __restrict__ ids, int source, const float* __restrict__ table,
                                                               float* __restrict__ x) {
   __shared__ float tab[256];
-  tab[threadIdx.x] = table[threadIdx.x];
-  __syncthreads();
+  stage_tanh_table<256>(tab, table);
   const int i = blockIdx.y;
-  const size_t row = (size_t)ids[i] * S_IMG;
+  const int id = ids[i];
+  const size_t row = (size_t)id * S_IMG;
   const int e = (blockIdx.x * 256 + threadIdx.x) * 4;
   const unsigned char* src = photos ? photos + (size_t)i * S_IMG : (source == 1 ? P.im + row : P.gim + row);
-  const uchar4 v = *reinterpret_cast<const uchar4*>(src + e);
-  *reinterpret_cast<uchar4*>(P.gim + row + e) = v;
-  *reinterpret_cast<uchar4*>(P.im + row + e) = v;
-  *reinterpret_cast<float4*>(x + (size_t)i * S_IMG + e) = make_float4(tab[v.x], tab[v.y], tab[v.z], tab[v.w]);
+  store_opened_px(P, id, i, e, *reinterpret_cast<const uchar4*>(src + e), tab, x);
 }
 hipError_t launch_session_open_in(const unsigned char* photos, const SessionPool& P, const int* ids, int source, const float* table,
                                   float* x, int n, hipStream_t s) {
@@ -462,8 +479,7 @@ __global__ __launch_bounds__(256) void session_fit_loss_kernel(const float* __re
                                                                double* __restrict__ loss, int loss_stride) {
   __shared__ float tab[256];
   __shared__ double part[256];
-  tab[threadIdx.x] = table[threadIdx.x];
-  __syncthreads();
+  stage_tanh_table<256>(tab, table);
   const int i = blockIdx.x;
   const int c1 = items[i * 7], r1 = items[i * 7 + 1];
   const int w = max(0, items[i * 7 + 2] - c1), hgt = max(0, items[i * 7 + 3] - r1);
@@ -497,173 +513,31 @@ hipError_t launch_session_fit_loss(const float* xhat, const SessionPool& P, cons
 // kept as FIELD / FIELD_KIND, and a window of the picture at full size is SRC + 127.5 * bilinear(FIELD) (kind 0: the unedited part of
 // the photo stays pixel-exact) or 127.5 * (bilinear(FIELD) + 1) (kind 1: FIELD holds x, a sample has no photo under it).
 
-// open, input side.  grid (64, 3, n): one workgroup per row of one channel of the 64x64 picture, i.e. scale rows of S bytes of the
-// photo; lane q < 16 * scale owns the uchar4 at byte 4q of each of those rows (consecutive lanes, consecutive bytes), copies it to SRC
-// (photos == nullptr: the row is there already) and adds its bytes to the integer sum of the 64x64 pixel they fall in.  Integer
-// sums are exact in any order; (sum + s*s/2) / (s*s) is hires_downsample.  Lanes 0..15 then write GIM, IM and x as
-// session_open_in_kernel does.  photos may be the SRC rows themselves, so neither pointer is __restrict__.
-__global__ __launch_bounds__(256) void session_hires_open_kernel(const unsigned char* photos, SessionPool P, const int* __restrict__ ids,
-                                                                 const float* __restrict__ table, float* __restrict__ x) {
-  __shared__ float tab[256];
-  __shared__ int sum[64];
-  for (int j = threadIdx.x; j < 256; j += blockDim.x) tab[j] = table[j];
+// The box mean of one row of one channel of a session's 64x64 picture: the work of one workgroup in both kernels below.  The row is
+// s rows of 64 * s bytes that start `lead` (0..3) bytes into the aligned uchar4 at `in`, `stride` bytes apart.  Lane q owns the
+// aligned uchar4 at byte 4q of each of them -- (lead + 64s + 3) / 4 lanes, consecutive lanes, consecutive bytes; the lanes loop when
+// that is more than the workgroup -- sums its bytes over the s rows in registers, leaves out the bytes before and behind the square,
+// merges the bytes that fall into the same 64x64 pixel and does one LDS add per pixel touched.  Integer sums are exact in any order;
+// (sum + s*s/2) / (s*s) is hires_downsample / canvas_crop_mean.  Lanes 0..15 then write GIM, IM and x through store_opened_px.
+// COPY: every loaded uchar4 also goes to the same place of `copy` (nullptr: it is there already).
+template <bool COPY>
+__device__ __forceinline__ void box_mean_row(const unsigned char* in, unsigned char* copy, size_t stride, int lead, int s, const SessionPool& P,
+                                             int id, int i, size_t o_row, const float* __restrict__ table, float* __restrict__ x, float* tab,
+                                             int* sum) {
   if (threadIdx.x < 64) sum[threadIdx.x] = 0;
-  __syncthreads();
-  const int s = P.scale, S = 64 * s;
-  const int gy = blockIdx.x, c = blockIdx.y, i = blockIdx.z;
-  const int id = ids[i];
-  const size_t plane = (size_t)S * S, first = (size_t)gy * s * S;
-  unsigned char* dst = P.src + ((size_t)id * 3 + c) * plane + first;
-  const unsigned char* in = photos ? photos + ((size_t)i * 3 + c) * plane + first : dst;
-  const int q = threadIdx.x;
-  if (q < 16 * s) {
-    int acc[4] = {0, 0, 0, 0};
-    for (int r = 0; r < s; ++r) {
-      const uchar4 v = *reinterpret_cast<const uchar4*>(in + (size_t)r * S + 4 * q);
-      if (photos) *reinterpret_cast<uchar4*>(dst + (size_t)r * S + 4 * q) = v;
-      acc[0] += v.x;
-      acc[1] += v.y;
-      acc[2] += v.z;
-      acc[3] += v.w;
-    }
-    int bin = (4 * q) / s, t = acc[0];   // bytes of one 64x64 pixel are summed in the lane first: one LDS add per pixel touched
-#pragma unroll
-    for (int e = 1; e < 4; ++e) {
-      const int b = (4 * q + e) / s;
-      if (b != bin) {
-        atomicAdd(&sum[bin], t);
-        bin = b;
-        t = 0;
-      }
-      t += acc[e];
-    }
-    atomicAdd(&sum[bin], t);
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    const int e = threadIdx.x * 4, d = s * s, half = d / 2;
-    uchar4 v;
-    v.x = (unsigned char)((sum[e] + half) / d);
-    v.y = (unsigned char)((sum[e + 1] + half) / d);
-    v.z = (unsigned char)((sum[e + 2] + half) / d);
-    v.w = (unsigned char)((sum[e + 3] + half) / d);
-    const size_t o = (size_t)c * 64 * 64 + gy * 64 + e;
-    *reinterpret_cast<uchar4*>(P.gim + (size_t)id * S_IMG + o) = v;
-    *reinterpret_cast<uchar4*>(P.im + (size_t)id * S_IMG + o) = v;
-    *reinterpret_cast<float4*>(x + (size_t)i * S_IMG + o) = make_float4(tab[v.x], tab[v.y], tab[v.z], tab[v.w]);
-  }
-}
-hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,
-                                     hipStream_t s) {
-  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_hires_open_kernel, dim3(64, 3, n), dim3((16 * P.scale + 63) / 64 * 64), 0, s, photos, P, ids, table, x);
-  return hipGetLastError();
-}
-
-// hires_axis_taps for one output coordinate: half-pixel centres in integers, a = 2Y + 1 - s in (-2s, 128s), i0 = floor(a / 2s) >= -1,
-// t = float32(a - 2s * i0) / float32(2s) (one division), both taps clamped to 0..63
-__device__ __forceinline__ void hires_taps(int Y, int s, int& lo, int& hi, float& t) {
-  const int s2 = 2 * s, a = 2 * Y + 1 - s;
-  const int i0 = (a + s2) / s2 - 1;   // a + 2s > 0: truncation is the floor
-  t = (float)(a - s2 * i0) / (float)s2;
-  lo = min(max(i0, 0), 63);
-  hi = min(max(i0 + 1, 0), 63);
-}
-
-// render.  grid (bands of RENDER_BAND output rows, 3, n); a lane owns 4 consecutive output bytes: one uchar4 load of SRC, one uchar4
-// store.  The band's field rows -- at most ceil((RENDER_BAND - 1) / s) + 2 <= RENDER_BAND + 2 consecutive rows of 64 floats -- go to LDS
-// once; every tap reads from there.  All arithmetic is float32 with contraction off, in hires_render's order.
-// Band height: the traffic is 2 bytes per output byte plus the staged rows, so the band only has to keep the staging small against
-// 8 * vw bytes of output and the grid large; 8 rows give 384 workgroups (1.5 per CU) for ONE whole 1024 x 1024 picture and
-// 2 uchar4 per lane at a 256-wide window.
-// out == nullptr: the whole picture over the session's own SRC row (commit): every lane stores exactly the bytes it loaded, so
-// this is safe in place; SRC and out are therefore not __restrict__.
-constexpr int RENDER_BAND = 8;
-__global__ __launch_bounds__(256) void session_render_kernel(SessionPool P, const int* __restrict__ views, int vw, int vh, unsigned char* out) {
-  __shared__ float f[(RENDER_BAND + 2) * 64];
-  const int s = P.scale, S = 64 * s;
-  const int c = blockIdx.y, i = blockIdx.z;
-  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
-  const int y0 = blockIdx.x * RENDER_BAND, rows = min(RENDER_BAND, vh - y0);
-  int fr0, fr1, unused;
-  float tunused;
-  hires_taps(vy + y0, s, fr0, unused, tunused);
-  hires_taps(vy + y0 + rows - 1, s, unused, fr1, tunused);
-  const int nfr = min(fr1 - fr0 + 1, RENDER_BAND + 2);
-  const float* frow = P.field + ((size_t)id * 3 + c) * (64 * 64) + fr0 * 64;
-  for (int j = threadIdx.x; j < nfr * 64; j += 256) f[j] = frow[j];
-  __syncthreads();
-  const int kind = P.kind[id];
-  const unsigned char* src = P.src + ((size_t)id * 3 + c) * S * S;
-  unsigned char* dst = out ? out + ((size_t)i * 3 + c) * vh * vw : P.src + ((size_t)id * 3 + c) * S * S;
-  const int dstride = out ? vw : S;
-  const int L = vw >> 2;
-  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
-    const int ry = idx / L, cx = (idx - ry * L) * 4;
-    const int Y = vy + y0 + ry;
-    int r0, r1;
-    float ty;
-    hires_taps(Y, s, r0, r1, ty);
-    const float* top = f + (r0 - fr0) * 64;
-    const float* bot = f + (r1 - fr0) * 64;
-    uchar4 pv = make_uchar4(0, 0, 0, 0);
-    if (kind == 0) pv = *reinterpret_cast<const uchar4*>(src + (size_t)Y * S + vx + cx);
-    const unsigned char pb[4] = {pv.x, pv.y, pv.z, pv.w};
-    unsigned char ob[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      int c0, c1;
-      float tx;
-      hires_taps(vx + cx + e, s, c0, c1, tx);
-      const float a0 = top[c0], a1 = bot[c0];
-      const float t = a0 + tx * (top[c1] - a0);
-      const float b = a1 + tx * (bot[c1] - a1);
-      const float v = t + ty * (b - t);
-      const float qv = kind == 0 ? (float)pb[e] + 127.5f * v : 127.5f * (v + 1.0f);
-      ob[e] = (unsigned char)fminf(fmaxf(rintf(qv), 0.0f), 255.0f);
-    }
-    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : vx + cx)) = make_uchar4(ob[0], ob[1], ob[2], ob[3]);
-  }
-}
-hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s) {
-  const int S = 64 * P.scale;
-  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || vw < 4 || (vw & 3) || vh < 1 || vw > S || vh > S)
-    return hipErrorInvalidValue;
-  if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_render_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, P, views, vw, vh, out);
-  return hipGetLastError();
-}
-
-// ---- canvases (DESIGN.md 4.7; the arithmetic is npe_ops.canvas_crop_mean / canvas_ramp / canvas_compose) ------------------------------
-// A canvas is a whole photo of w x hgt pixels in rows of C.max_w bytes; a session is placed on it as a square of 64 * s pixels at
-// (ox, oy), s per placement.
-
-// place, input side: session_hires_open_kernel's job on a square of a canvas.  grid (64, 3, n): one workgroup per row of one channel
-// of the 64x64 picture, i.e. s canvas rows of 64 * s bytes starting at byte ox of ANY alignment.  The loads stay aligned uchar4: lane q
-// owns the uchar4 at byte (ox & ~3) + 4q of each row, 16s lanes when ox % 4 == 0 and 16s + 1 otherwise (257 at s = 16: the lanes
-// loop), and the bytes that fall outside the square are masked out of the sums.  The aligned span ends at most at the next
-// multiple of 4 after ox + 64s <= w, and w % 4 == 0: inside the picture's row.  No SRC copy; GIM, IM and x as the open kernels write them.
-__global__ __launch_bounds__(256) void canvas_place_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ items,
-                                                           const float* __restrict__ table, float* __restrict__ x) {
-  __shared__ float tab[256];
-  __shared__ int sum[64];
-  for (int j = threadIdx.x; j < 256; j += blockDim.x) tab[j] = table[j];
-  if (threadIdx.x < 64) sum[threadIdx.x] = 0;
-  __syncthreads();
-  const int gy = blockIdx.x, c = blockIdx.y, i = blockIdx.z;
-  const int id = items[5 * i], cv = items[5 * i + 1], ox = items[5 * i + 2], oy = items[5 * i + 3], s = items[5 * i + 4];
-  const int S = 64 * s, lead = ox & 3, nq = (lead + S + 3) >> 2;
-  const unsigned char* in = C.pix + (((size_t)cv * 3 + c) * C.max_h + (size_t)oy + (size_t)gy * s) * C.max_w + (ox - lead);
+  stage_tanh_table(tab, table);
+  const int S = 64 * s, nq = (lead + S + 3) >> 2;
   for (int q = threadIdx.x; q < nq; q += blockDim.x) {
     int acc[4] = {0, 0, 0, 0};
     for (int r = 0; r < s; ++r) {
-      const uchar4 v = *reinterpret_cast<const uchar4*>(in + (size_t)r * C.max_w + 4 * q);
+      const uchar4 v = *reinterpret_cast<const uchar4*>(in + (size_t)r * stride + 4 * q);
+      if (COPY && copy) *reinterpret_cast<uchar4*>(copy + (size_t)r * stride + 4 * q) = v;
       acc[0] += v.x;
       acc[1] += v.y;
       acc[2] += v.z;
       acc[3] += v.w;
     }
-    int bin = -1, t = 0;   // bytes of one 64x64 pixel are summed in the lane first: one LDS add per pixel touched
+    int bin = -1, t = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int u = 4 * q + e - lead;   // the byte's column in the square
@@ -686,11 +560,144 @@ __global__ __launch_bounds__(256) void canvas_place_kernel(SessionCanvases C, Se
     v.y = (unsigned char)((sum[e + 1] + half) / d);
     v.z = (unsigned char)((sum[e + 2] + half) / d);
     v.w = (unsigned char)((sum[e + 3] + half) / d);
-    const size_t o = (size_t)c * 64 * 64 + gy * 64 + e;
-    *reinterpret_cast<uchar4*>(P.gim + (size_t)id * S_IMG + o) = v;
-    *reinterpret_cast<uchar4*>(P.im + (size_t)id * S_IMG + o) = v;
-    *reinterpret_cast<float4*>(x + (size_t)i * S_IMG + o) = make_float4(tab[v.x], tab[v.y], tab[v.z], tab[v.w]);
+    store_opened_px(P, id, i, o_row + e, v, tab, x);
   }
+}
+
+// open, input side.  grid (64, 3, n): one workgroup per row of one channel of the 64x64 picture, i.e. scale rows of S bytes of the
+// photo, aligned (lead 0: 16 * scale lanes, one pass), each uchar4 copied to SRC on the way (photos == nullptr: the row is there
+// already).  photos may be the SRC rows themselves, so neither pointer is __restrict__.
+__global__ __launch_bounds__(256) void session_hires_open_kernel(const unsigned char* photos, SessionPool P, const int* __restrict__ ids,
+                                                                 const float* __restrict__ table, float* __restrict__ x) {
+  __shared__ float tab[256];
+  __shared__ int sum[64];
+  const int s = P.scale, S = 64 * s;
+  const int gy = blockIdx.x, c = blockIdx.y, i = blockIdx.z;
+  const int id = ids[i];
+  const size_t plane = (size_t)S * S, first = (size_t)gy * s * S;
+  unsigned char* dst = P.src + ((size_t)id * 3 + c) * plane + first;
+  const unsigned char* in = photos ? photos + ((size_t)i * 3 + c) * plane + first : dst;
+  box_mean_row<true>(in, photos ? dst : nullptr, (size_t)S, 0, s, P, id, i, (size_t)c * 64 * 64 + gy * 64, table, x, tab, sum);
+}
+hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,
+                                     hipStream_t s) {
+  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_hires_open_kernel, dim3(64, 3, n), dim3((16 * P.scale + 63) / 64 * 64), 0, s, photos, P, ids, table, x);
+  return hipGetLastError();
+}
+
+// hires_axis_taps for one output coordinate: half-pixel centres in integers, a = 2Y + 1 - s in (-2s, 128s), i0 = floor(a / 2s) >= -1,
+// t = float32(a - 2s * i0) / float32(2s) (one division), both taps clamped to 0..63
+__device__ __forceinline__ void hires_taps(int Y, int s, int& lo, int& hi, float& t) {
+  const int s2 = 2 * s, a = 2 * Y + 1 - s;
+  const int i0 = (a + s2) / s2 - 1;   // a + 2s > 0: truncation is the floor
+  t = (float)(a - s2 * i0) / (float)s2;
+  lo = min(max(i0, 0), 63);
+  hi = min(max(i0 + 1, 0), 63);
+}
+
+// the field at square coordinate u of the output row whose two tapped field rows are top and bot (weight ty): hires_render's bilinear
+// tap, float32, in exactly this order of operations (contraction is off here)
+__device__ __forceinline__ float field_bilinear(const float* top, const float* bot, int s, int u, float ty) {
+  int c0, c1;
+  float tx;
+  hires_taps(u, s, c0, c1, tx);
+  const float a0 = top[c0], a1 = bot[c0];
+  const float t = a0 + tx * (top[c1] - a0);
+  const float b = a1 + tx * (bot[c1] - a1);
+  return t + ty * (b - t);
+}
+// np.clip(np.rint(q), 0, 255).astype(uint8)
+__device__ __forceinline__ unsigned char round_u8(float q) { return (unsigned char)fminf(fmaxf(rintf(q), 0.0f), 255.0f); }
+
+// The field rows that output rows u0..u1 (square coordinates, both inclusive) of a picture at scale s tap: n <= ceil((RENDER_BAND - 1) / s)
+// + 2 <= RENDER_BAND + 2 consecutive rows of 64 floats, from row fr0.  field_rows says which (render: every lane; compose: lane 0, per
+// kept placement, into LDS); stage_field_rows copies them from the field's plane to f, all 256 lanes of either window kernel; the
+// caller's barrier publishes f.
+constexpr int RENDER_BAND = 8;
+struct FieldRows {
+  int fr0, n;
+};
+__device__ __forceinline__ FieldRows field_rows(int u0, int u1, int s) {
+  int fr0, fr1, unused;
+  float tunused;
+  hires_taps(u0, s, fr0, unused, tunused);
+  hires_taps(u1, s, unused, fr1, tunused);
+  return FieldRows{fr0, min(fr1 - fr0 + 1, RENDER_BAND + 2)};
+}
+__device__ __forceinline__ void stage_field_rows(float* f, const float* plane, const FieldRows r) {
+  const float* frow = plane + r.fr0 * 64;
+  for (int j = threadIdx.x; j < r.n * 64; j += 256) f[j] = frow[j];
+}
+
+// render.  grid (bands of RENDER_BAND output rows, 3, n); a lane owns 4 consecutive output bytes: one uchar4 load of SRC, one uchar4
+// store.  The band's field rows go to LDS once; every tap reads from there.  All arithmetic is float32 with contraction off, in
+// hires_render's order.
+// Band height: the traffic is 2 bytes per output byte plus the staged rows, so the band only has to keep the staging small against
+// 8 * vw bytes of output and the grid large; 8 rows give 384 workgroups (1.5 per CU) for ONE whole 1024 x 1024 picture and
+// 2 uchar4 per lane at a 256-wide window.
+// out == nullptr: the whole picture over the session's own SRC row (commit): every lane stores exactly the bytes it loaded, so
+// this is safe in place; SRC and out are therefore not __restrict__.
+__global__ __launch_bounds__(256) void session_render_kernel(SessionPool P, const int* __restrict__ views, int vw, int vh, unsigned char* out) {
+  __shared__ float f[(RENDER_BAND + 2) * 64];
+  const int s = P.scale, S = 64 * s;
+  const int c = blockIdx.y, i = blockIdx.z;
+  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
+  const int y0 = blockIdx.x * RENDER_BAND, rows = min(RENDER_BAND, vh - y0);
+  const FieldRows fr = field_rows(vy + y0, vy + y0 + rows - 1, s);
+  stage_field_rows(f, P.field + ((size_t)id * 3 + c) * (64 * 64), fr);
+  __syncthreads();
+  const int kind = P.kind[id];
+  const unsigned char* src = P.src + ((size_t)id * 3 + c) * S * S;
+  unsigned char* dst = out ? out + ((size_t)i * 3 + c) * vh * vw : P.src + ((size_t)id * 3 + c) * S * S;
+  const int dstride = out ? vw : S;
+  const int L = vw >> 2;
+  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
+    const int ry = idx / L, cx = (idx - ry * L) * 4;
+    const int Y = vy + y0 + ry;
+    int r0, r1;
+    float ty;
+    hires_taps(Y, s, r0, r1, ty);
+    const float* top = f + (r0 - fr.fr0) * 64;
+    const float* bot = f + (r1 - fr.fr0) * 64;
+    uchar4 pv = make_uchar4(0, 0, 0, 0);
+    if (kind == 0) pv = *reinterpret_cast<const uchar4*>(src + (size_t)Y * S + vx + cx);
+    const unsigned char pb[4] = {pv.x, pv.y, pv.z, pv.w};
+    unsigned char ob[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float v = field_bilinear(top, bot, s, vx + cx + e, ty);
+      ob[e] = round_u8(kind == 0 ? (float)pb[e] + 127.5f * v : 127.5f * (v + 1.0f));
+    }
+    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : vx + cx)) = make_uchar4(ob[0], ob[1], ob[2], ob[3]);
+  }
+}
+hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s) {
+  const int S = 64 * P.scale;
+  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || vw < 4 || (vw & 3) || vh < 1 || vw > S || vh > S)
+    return hipErrorInvalidValue;
+  if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_render_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, P, views, vw, vh, out);
+  return hipGetLastError();
+}
+
+// ---- canvases (DESIGN.md 4.7; the arithmetic is npe_ops.canvas_crop_mean / canvas_ramp / canvas_compose) ------------------------------
+// A canvas is a whole photo of w x hgt pixels in rows of C.max_w bytes; a session is placed on it as a square of 64 * s pixels at
+// (ox, oy), s per placement.
+
+// place, input side: box_mean_row on a square of a canvas.  grid (64, 3, n): one workgroup per row of one channel of the 64x64
+// picture, i.e. s canvas rows of 64 * s bytes starting at byte ox of ANY alignment: lead = ox % 4, 16s lanes when it is 0 and 16s + 1
+// otherwise (257 at s = 16: the lanes loop).  The aligned span ends at most at the next multiple of 4 after ox + 64s <= w, and
+// w % 4 == 0: inside the picture's row.  No SRC copy.
+__global__ __launch_bounds__(256) void canvas_place_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ items,
+                                                           const float* __restrict__ table, float* __restrict__ x) {
+  __shared__ float tab[256];
+  __shared__ int sum[64];
+  const int gy = blockIdx.x, c = blockIdx.y, i = blockIdx.z;
+  const int id = items[5 * i], cv = items[5 * i + 1], ox = items[5 * i + 2], oy = items[5 * i + 3], s = items[5 * i + 4];
+  const int lead = ox & 3;
+  const unsigned char* in = C.pix + (((size_t)cv * 3 + c) * C.max_h + (size_t)oy + (size_t)gy * s) * C.max_w + (ox - lead);
+  box_mean_row<false>(in, nullptr, (size_t)C.max_w, lead, s, P, id, i, (size_t)c * 64 * 64 + gy * 64, table, x, tab, sum);
 }
 static bool canvases_ok(const SessionCanvases& C) {
   return C.pix && C.table && C.count >= 1 && C.max_w >= 64 && C.max_h >= 64 && (C.max_w & 3) == 0 && C.feather >= 0 && C.feather <= 16 &&
@@ -712,19 +719,19 @@ __device__ __forceinline__ float canvas_ramp1(int u, int S, int f2s) {
 
 // compose.  session_render_kernel's shape: grid (bands of RENDER_BAND output rows, 3, n), a lane owns 4 consecutive output bytes: one
 // uchar4 load of the canvas, one uchar4 store.  Lane 0 reads the canvas's placement table and keeps the placements whose squares meet
-// the band (a test that is uniform over the workgroup); each kept placement's tapped field rows -- at most RENDER_BAND + 2 rows of
-// 64 floats -- go to LDS once, 20 KB for 8; the lanes then walk their pixels with the placements in the inner loop, so acc lives in
-// registers.  A band that meets no square is a plain copy.  All arithmetic is float32 with contraction off, in canvas_compose's order.
+// the band (a test that is uniform over the workgroup) and which field rows each taps (field_rows); each kept placement's rows go to
+// LDS once (stage_field_rows), 20 KB for 8; the lanes then walk their pixels with the placements in the inner loop, so acc lives in registers.  A band that meets no
+// square is a plain copy.  All arithmetic is float32 with contraction off, in canvas_compose's order.
 // out == nullptr: the window is the whole picture, written over the canvas itself (commit): every lane stores exactly the bytes it
 // loaded and the fields live elsewhere, so overlapping squares are safe in place; neither pointer is __restrict__.
 struct CanvasKept {
-  int ox, oy, s, kind, fr0;
+  int id, ox, oy, s, kind;
 };
 __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ windows, int vw, int vh,
                                                              unsigned char* out) {
   __shared__ float f[CANVAS_MAX_PLACED][(RENDER_BAND + 2) * 64];
   __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
-  __shared__ int frow_id[CANVAS_MAX_PLACED], frow_n[CANVAS_MAX_PLACED];
+  __shared__ FieldRows frows[CANVAS_MAX_PLACED];   // the staged field rows of each kept placement
   __shared__ int nkept;
   const int c = blockIdx.y, i = blockIdx.z;
   const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
@@ -738,24 +745,14 @@ __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, 
       if (id < 0) break;
       const int S = 64 * s;
       if (s < 1 || s > 16 || Y1 < oy || Y0 > oy + S - 1 || vx + vw - 1 < ox || vx > ox + S - 1) continue;
-      int fr0, fr1, unused;
-      float tunused;
-      hires_taps(max(Y0, oy) - oy, s, fr0, unused, tunused);
-      hires_taps(min(Y1, oy + S - 1) - oy, s, unused, fr1, tunused);
-      kept[nk] = CanvasKept{ox, oy, s, P.kind[id], fr0};
-      frow_id[nk] = id;
-      frow_n[nk] = min(fr1 - fr0 + 1, RENDER_BAND + 2);
-      ++nk;
+      frows[nk] = field_rows(max(Y0, oy) - oy, min(Y1, oy + S - 1) - oy, s);   // the band's rows inside the square, in its coordinates
+      kept[nk++] = CanvasKept{id, ox, oy, s, P.kind[id]};
     }
     nkept = nk;
   }
   __syncthreads();
   const int nk = nkept;
-  for (int k = 0; k < nk; ++k) {
-    const float* frow = P.field + ((size_t)frow_id[k] * 3 + c) * (64 * 64) + kept[k].fr0 * 64;
-    const int cnt = frow_n[k] * 64;
-    for (int j = threadIdx.x; j < cnt; j += 256) f[k][j] = frow[j];
-  }
+  for (int k = 0; k < nk; ++k) stage_field_rows(f[k], P.field + ((size_t)kept[k].id * 3 + c) * (64 * 64), frows[k]);
   __syncthreads();
   const size_t plane = ((size_t)cv * 3 + c) * C.max_h * C.max_w;
   const unsigned char* src = C.pix + plane;
@@ -771,24 +768,18 @@ __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, 
       const CanvasKept q = kept[k];
       const int S = 64 * q.s, uy = Y - q.oy;
       if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
-      const int f2s = 2 * C.feather * q.s;
+      const int f2s = 2 * C.feather * q.s, fr0 = frows[k].fr0;
       int r0, r1;
       float ty;
       hires_taps(uy, q.s, r0, r1, ty);
-      const float* top = f[k] + (r0 - q.fr0) * 64;
-      const float* bot = f[k] + (r1 - q.fr0) * 64;
+      const float* top = f[k] + (r0 - fr0) * 64;
+      const float* bot = f[k] + (r1 - fr0) * 64;
       const float wy = canvas_ramp1(uy, S, f2s);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int ux = X + e - q.ox;
         if (ux < 0 || ux >= S) continue;
-        int c0, c1;
-        float tx;
-        hires_taps(ux, q.s, c0, c1, tx);
-        const float a0 = top[c0], a1 = bot[c0];
-        const float t = a0 + tx * (top[c1] - a0);
-        const float b = a1 + tx * (bot[c1] - a1);
-        const float v = t + ty * (b - t);
+        const float v = field_bilinear(top, bot, q.s, ux, ty);
         const float w = wy * canvas_ramp1(ux, S, f2s);
         if (q.kind == 0) {
           acc[e] = acc[e] + (127.5f * v) * w;
@@ -798,12 +789,8 @@ __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, 
         }
       }
     }
-    uchar4 o;
-    o.x = (unsigned char)fminf(fmaxf(rintf(acc[0]), 0.0f), 255.0f);
-    o.y = (unsigned char)fminf(fmaxf(rintf(acc[1]), 0.0f), 255.0f);
-    o.z = (unsigned char)fminf(fmaxf(rintf(acc[2]), 0.0f), 255.0f);
-    o.w = (unsigned char)fminf(fmaxf(rintf(acc[3]), 0.0f), 255.0f);
-    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) = o;
+    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) =
+        make_uchar4(round_u8(acc[0]), round_u8(acc[1]), round_u8(acc[2]), round_u8(acc[3]));
   }
 }
 hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, unsigned char* out,

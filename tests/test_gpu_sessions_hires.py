@@ -47,9 +47,8 @@ def assert_same64(a, b, tag):
 
 
 # ---- 1. open --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("s", [1, 2, 3])
-@pytest.mark.parametrize("n", [1, 3])
-def test_open_hires_is_open_of_the_box_mean(s, n):
+def check_open_hires(s, n):
+    """open_hires of n photos at scale s against the specification -> (the pool, ids, photos, what read() gave per session)."""
     from neural_photo_editor_amd import npe_ops as N
     _, sh, _, sp = pools()
     sh.reserve_hires(s)
@@ -60,14 +59,45 @@ def test_open_hires_is_open_of_the_box_mean(s, n):
     shown_p = sp.open(ids, down)
     assert np.array_equal(shown, shown_p) and np.array_equal(shown, down)
     S = 64 * s
+    state = []
     for k, i in enumerate(ids):
         got = sh.read(i)
         assert_same64(got, sp.read(i), (s, n, i))
         assert np.array_equal(got["GIM"], down[k])
         assert got["SOURCE"].shape == (3, S, S) and np.array_equal(got["SOURCE"], src[k])
         assert got["FIELD"].dtype == np.float32 and not got["FIELD"].any() and got["FIELD_KIND"] == 0
+        state.append(got)
     whole = sh.render(ids, (0, 0), S)
     assert np.array_equal(whole, src)
+    return sh, ids, src, state
+
+
+@pytest.mark.parametrize("s", [1, 2, 3])
+@pytest.mark.parametrize("n", [1, 3])
+def test_open_hires_is_open_of_the_box_mean(s, n):
+    check_open_hires(s, n)
+
+
+def test_open_hires_at_scale_5_and_the_same_photo_placed_on_a_canvas():
+    """s = 5: 80 lanes in a 128-lane workgroup, and a lane's four bytes straddle two 64x64 pixels at every phase (neither holds at
+    1, 2, 3, 16).  Then the same photos as canvases, placed at (0, 0) and scale 5: the box mean's other entry leaves the same state."""
+    from neural_photo_editor_amd import npe_ops as N
+    s, n = 5, 2
+    sh, ids, src, opened = check_open_hires(s, n)
+    for p in src:                                                              # what the second half rests on, on the CPU
+        assert np.array_equal(N.hires_downsample(p, s), N.canvas_crop_mean(p, 0, 0, s))
+    sh.reserve_canvases(n, 64 * s, 64 * s, 0)
+    try:
+        for c, p in enumerate(src):
+            sh.canvas_put(c, p)
+        shown = sh.place(ids, list(range(n)), [(0, 0)] * n, s)
+        for k, i in enumerate(ids):
+            got = sh.read(i)
+            assert np.array_equal(shown[k], opened[k]["IM"])
+            for key in ("GIM", "IM", "Z"):
+                assert np.array_equal(got[key], opened[k][key]), (key, i)
+    finally:
+        sh.reserve_canvases(0)
 
 
 # ---- 2. the brush script ---------------------------------------------------------------------------------------------------------
