@@ -439,6 +439,46 @@ typedef struct ian_session_fit_item {
 int ian_session_fit(ian_handle* h, int32_t n, const ian_session_fit_item* items, int32_t steps, float lr, double* loss, uint8_t* shown,
                     void* stream);
 
+/* ---- strokes: a session's whole brush path in ONE submission ----
+   ian_session_brush takes one event per session per call, as NPE.paint takes one <B1-Motion>.  An editor behind a server receives the
+   path of a drag -- K rectangles along the mouse track -- and wants the picture at its end.  A stroke is that path: per session
+   `count` rectangles boxes[first .. first + count), applied in that order, with one mode, coef and colour for all of them.
+   Meaning: let Kmax = strokes[0].count.  For k = 0 .. Kmax-1 take the strokes with count > k, in the order given, and call
+   ian_session_brush on them with the events
+       rectangle = boxes[first + k], gscale = boxes[first + k].gscale, mode / coef / rgb = the stroke's.
+   The result is what that sequence of calls gives: afterwards every session equals the session after it, byte for byte -- Z, IM, RECON,
+   ERROR, GIM, the mode and, where the pool has them, FIELD, FIELD_KIND, UMASK and LOCAL -- and shown[i] (u8[n,3,64,64], host or device,
+   or NULL) is what session i's last event displayed.  What is saved is everything between the steps that nobody looks at: one table
+   upload instead of Kmax, no blend, no copy of shown and no synchronisation before the last point of a stroke, and no decoder forward
+   at the start of a step whose sessions are those of the step before (brush_step's forward at z_new is the next step's forward at Z).
+   In a pool with the local reservation the footprints of ALL of a stroke's rectangles go into UMASK before its first step (max is
+   exact, so the order does not matter); the blend of the last point then sees the UMASK the K calls would have built.
+   Order: the strokes must come with non-increasing count, so that the strokes of every step are a prefix of the array and the ones
+   that end at a step the tail of that prefix.
+   flags: bit 0 = mark first: what ian_session_mark does on the n sessions, in the same submission, so that one stroke is one undo step
+   (-6 without the history reservation).  ian_session_history afterwards reports what the separate calls would.
+   More than `brush_pass` strokes (ian_set_option) run as passes, each pass through all its steps before the next starts.  The
+   residency of ian_session_brush is used at the start (same ids, same order, same latent versions) and re-armed at the end when the
+   call was one pass and every stroke was active at the last step.  One synchronisation at the end, and only when shown is host memory.
+   -6: no pool, ian_sessions_set_blend not called, a session with LOCAL flags but no falloff table, bit 0 without a history.  -7, naming
+   the item (and the point, where one is concerned), before anything is enqueued or any host state moves: everything ian_session_brush
+   refuses, count outside 1..IAN_STROKE_MAX_POINTS, first < 0 or first + count > nboxes, a rectangle outside the image (an empty one is
+   allowed and gives a zero gradient), counts that increase, a flag bit other than bit 0, strokes or boxes in device memory. */
+#define IAN_STROKE_MAX_POINTS 64
+typedef struct ian_stroke_box {
+  int32_t c1, r1, c2, r2;   /* API.py:66-76 rectangle, columns first */
+  float gscale;             /* as ian_session_event.gscale: NPE.py:206 has 1 + (c2 - c1) */
+} ian_stroke_box;
+typedef struct ian_session_stroke_item {
+  int32_t session;          /* id in the pool */
+  int32_t first, count;     /* its rectangles: boxes[first .. first + count), applied in that order */
+  int32_t mode;             /* as ian_session_event.mode, for every point of the stroke */
+  float coef;               /* as ian_session_event.coef, for every point */
+  float rgb[3];             /* as ian_session_event.rgb */
+} ian_session_stroke_item;
+int ian_session_stroke(ian_handle* h, int32_t n, const ian_session_stroke_item* strokes, int32_t nboxes, const ian_stroke_box* boxes,
+                       int32_t flags, uint8_t* shown, void* stream);
+
 /* ---- saving and loading whole sessions: the editor state as bytes that can leave the pool ----
    Everything a session is -- the 64x64 state, the full-resolution source and edit field, the user mask and flags, the ring of undo
    states with its cursor -- lives in one handle's pool.  A record is that state as plain bytes: keep a project beyond the process,

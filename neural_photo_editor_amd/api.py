@@ -22,7 +22,7 @@ import warnings
 import numpy as np
 
 from . import checkpoints, config_loader, lowering, made
-from .lib import BrushItem, Handle, SessionEvent, SessionFitItem, SessionView
+from .lib import STROKE_MAX_POINTS, BrushItem, Handle, SessionEvent, SessionFitItem, SessionStroke, SessionView, StrokeBox
 
 BATCH_MAX = 256     # ian_grad_batch / ian_brush_step_batch: 1 <= n <= 256
 
@@ -113,19 +113,9 @@ def check_session_ids(ids, capacity=None, opened=None, repeats=False, what="sess
     return np.ascontiguousarray(a, np.int32)
 
 
-def pack_session_events(ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, capacity=None, opened=None):
-    """Python arguments of ian_session_brush -> a ctypes array of ian_session_event (include/ian.h), validated before the library
-    sees anything.  ids (n,) session ids; boxes (n,4) or (4,) as (c1, r1, c2, r2), floats truncated as imgrad's int() does;
-    colours (n,3) or (3,) uint8-range levels, or None (then every mode is 0); modes default to 1 with colours and 0 without;
-    weight and sign are scalars or length-n arrays: coef = float32(sign*weight), gscale = float32(1 + (c2 - c1)).
-    capacity / opened (a container of opened ids), when given, bound and vet the ids."""
-    idl = [int(v) for v in check_session_ids(ids, capacity, opened)]
-    n = len(idl)
-    b = np.asarray(boxes)
-    if b.ndim == 1 and b.shape == (4,):
-        b = np.tile(b, (n, 1))
-    if b.ndim != 2 or b.shape != (n, 4):
-        raise ValueError("boxes must have shape (%d,4) or (4,) as (c1,r1,c2,r2), got %s" % (n, b.shape))
+def _colours_and_modes(colours, modes, n):
+    """colours (n,3) or (3,) or None and modes (n,), a scalar or None of n session events or strokes -> (col (n,3) or None, modes as a
+    list): every mode is 0 without colours and defaults to 1 with them; mode 1 needs a colour."""
     col = None
     if colours is not None:
         col = np.asarray(colours)
@@ -145,6 +135,23 @@ def pack_session_events(ids, boxes, colours=None, modes=None, weight=0.05, sign=
                 raise ValueError("item %d has mode %d (0 = imgrad, 1 = imgradRGB)" % (i, v))
         if col is None and any(m):
             raise ValueError("item %d has mode 1 (imgradRGB) but no colour was given" % m.index(1))
+    return col, m
+
+
+def pack_session_events(ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, capacity=None, opened=None):
+    """Python arguments of ian_session_brush -> a ctypes array of ian_session_event (include/ian.h), validated before the library
+    sees anything.  ids (n,) session ids; boxes (n,4) or (4,) as (c1, r1, c2, r2), floats truncated as imgrad's int() does;
+    colours (n,3) or (3,) uint8-range levels, or None (then every mode is 0); modes default to 1 with colours and 0 without;
+    weight and sign are scalars or length-n arrays: coef = float32(sign*weight), gscale = float32(1 + (c2 - c1)).
+    capacity / opened (a container of opened ids), when given, bound and vet the ids."""
+    idl = [int(v) for v in check_session_ids(ids, capacity, opened)]
+    n = len(idl)
+    b = np.asarray(boxes)
+    if b.ndim == 1 and b.shape == (4,):
+        b = np.tile(b, (n, 1))
+    if b.ndim != 2 or b.shape != (n, 4):
+        raise ValueError("boxes must have shape (%d,4) or (4,) as (c1,r1,c2,r2), got %s" % (n, b.shape))
+    col, m = _colours_and_modes(colours, modes, n)
     w, sg = per_item(weight, "weight", n), per_item(sign, "sign", n)
     ev = (SessionEvent * n)()
     for i in range(n):
@@ -158,6 +165,52 @@ def pack_session_events(ids, boxes, colours=None, modes=None, weight=0.05, sign=
         if col is not None:
             e.rgb[0], e.rgb[1], e.rgb[2] = [float(v) for v in brush_colour(col[i])]
     return ev
+
+
+def pack_session_strokes(ids, paths, colours=None, modes=None, weight=0.05, sign=-1.0, capacity=None, opened=None):
+    """Python arguments of ian_session_stroke -> (a ctypes array of ian_session_stroke_item, one of ian_stroke_box, perm), validated
+    before the library sees anything.  ids (n,) session ids; paths a sequence of n arrays of shape (K_i, 4), 1 <= K_i <= 64: the
+    rectangles (c1, r1, c2, r2) of session i's stroke in the order they are applied, floats truncated as imgrad's int() does;
+    colours, modes, weight and sign as in pack_session_events, one value per STROKE: coef = float32(sign*weight) for every point,
+    gscale = float32(1 + (c2 - c1)) per rectangle.  The library wants the strokes with non-increasing K: they are sorted stably by
+    descending K, the boxes laid out in that order, and perm[j] is the caller's index of sorted stroke j (what the library returns
+    for stroke j belongs to ids[perm[j]])."""
+    idl = [int(v) for v in check_session_ids(ids, capacity, opened)]
+    n = len(idl)
+    if isinstance(paths, np.ndarray) and paths.ndim == 3:
+        paths = list(paths)
+    if len(paths) != n:
+        raise ValueError("paths must hold one (K,4) array per session: %d for %d sessions" % (len(paths), n))
+    pl = []
+    for i, p in enumerate(paths):
+        b = np.asarray(p)
+        if b.ndim != 2 or b.shape[1] != 4:
+            raise ValueError("item %d: a path has shape (K,4) as (c1,r1,c2,r2) per point, got %s" % (i, b.shape))
+        if not 1 <= b.shape[0] <= STROKE_MAX_POINTS:
+            raise ValueError("item %d: a stroke has 1..%d points, got %d" % (i, STROKE_MAX_POINTS, b.shape[0]))
+        rows = [[int(v) for v in r] for r in b]
+        for k, (c1, r1, c2, r2) in enumerate(rows):
+            if c1 < 0 or r1 < 0 or c2 > 64 or r2 > 64:
+                raise ValueError("item %d: point %d: patch (%d,%d,%d,%d) outside the 64x64 image" % (i, k, c1, r1, c2, r2))
+        pl.append(rows)
+    col, m = _colours_and_modes(colours, modes, n)
+    w, sg = per_item(weight, "weight", n), per_item(sign, "sign", n)
+    perm = sorted(range(n), key=lambda i: -len(pl[i]))      # stable: equal lengths keep the caller's order
+    strokes = (SessionStroke * n)()
+    boxes = (StrokeBox * sum(len(p) for p in pl))()
+    first = 0
+    for j, i in enumerate(perm):
+        s = strokes[j]
+        s.session, s.first, s.count, s.mode = idl[i], first, len(pl[i]), m[i]
+        s.coef = sg[i] * w[i]                  # rounded to float32 by ctypes, as numpy rounds the scalar
+        if col is not None:
+            s.rgb[0], s.rgb[1], s.rgb[2] = [float(v) for v in brush_colour(col[i])]
+        for k, (c1, r1, c2, r2) in enumerate(pl[i]):
+            b = boxes[first + k]
+            b.c1, b.r1, b.c2, b.r2 = c1, r1, c2, r2
+            b.gscale = float(1 + (c2 - c1))
+        first += len(pl[i])
+    return strokes, boxes, perm
 
 
 def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, sourced=None, events=None):
@@ -469,6 +522,7 @@ class EditSessions:
         open    infer (NPE.py:239-274)          reset   Reset (:330-340)           commit  UpdateGIM (:342-345)
         sample  sample (:317-327), z from the caller                                set_latent  paint_latents (:286-302)
         paint   NPE.paint (:192-235)            scroll  NPE.scroll (:305-316)      brush   the general form of both
+        stroke / paint_stroke  a whole drag per session (K rectangles along the mouse track) in one submission -> the picture at its end
     Photos larger than 64x64 (no counterpart in NPE.py): reserve_hires(scale) keeps every session's photo at 64*scale pixels a side;
         open_hires  infer from the full-size photo     render  windows of the edited picture at full size
         brush_view / paint(view=) / scroll(view=)      the event and its window in one submission
@@ -875,6 +929,34 @@ class EditSessions:
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
         self._h.session_brush(ev, shown)
         return shown
+
+    def stroke(self, ids, paths, colours=None, modes=None, weight=0.05, sign=-1.0, mark=False):
+        """Whole brush paths in one submission (ian_session_stroke): paths = one (K_i,4) array of rectangles per session, 1..64 points,
+        applied in order with the stroke's one colour / mode / weight / sign (pack_session_strokes).  The sessions end byte for byte
+        where the loop `for k: brush(the sessions with more than k points)` leaves them -> shown uint8 (n,3,64,64), in the caller's
+        order: what each session's LAST point displays.  mark=True saves the states first, as mark(ids) would, in the same
+        submission: one stroke is one undo step.  For windows call render or compose afterwards."""
+        if mark:
+            self._need_history()
+        strokes, boxes, perm = pack_session_strokes(ids, paths, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
+        got = np.empty((len(strokes), 3, 64, 64), np.uint8)
+        self._h.session_stroke(strokes, boxes, 1 if mark else 0, got)
+        shown = np.empty_like(got)
+        shown[perm] = got                      # sorted stroke j is the caller's item perm[j]
+        return shown
+
+    def paint_stroke(self, ids, points, colours_uint8, d=12, weight=0.05, mark=True):
+        """A drag of NPE.paint per session: points = one (K_i,2) array of (x, y) mouse positions in 64-pixel space per session (NPE.py:148
+        has event.x//4), d = the brush-size slider (npe_ops.brush_rect gives each point move_mouse's rectangle), painted toward
+        colours_uint8 (levels 0..255) -> shown, as stroke."""
+        from . import npe_ops
+        paths = []
+        for i, p in enumerate(points):
+            q = np.asarray(p)
+            if q.ndim != 2 or q.shape[1] != 2:
+                raise ValueError("item %d: the points of a stroke have shape (K,2) as (x,y), got %s" % (i, q.shape))
+            paths.append(np.array([npe_ops.brush_rect(x, y, d) for x, y in q], np.int64).reshape(-1, 4))
+        return self.stroke(ids, paths, colours_uint8, None, weight, -1.0, mark)
 
     def paint(self, ids, boxes, colours_uint8, weight=0.05, view=None):
         """NPE.paint: Z -= weight * grad toward the brush colour (levels 0..255 per channel).  view = (origins, size): also the

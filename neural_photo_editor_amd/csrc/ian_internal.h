@@ -412,6 +412,13 @@ struct SessionBlendArgs {
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s);
 // UMASK row of session ids[i] := 0 and, with flags (device int[n]), LOCAL[ids[i]] := flags[i]
 hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const int* flags, int n, hipStream_t s);
+// ian_session_stroke: UMASK row of session ids[g] := max(UMASK, the footprint of every rectangle of stroke g) for g = first .. first +
+// n - 1, under the blend's conditions (LOCAL bit 0, a paint stroke, photo mode).  items = the call's ian_brush_item rows (7 words
+// each), step after step; rows = device int[steps + 1]: step k's rows start at rows[k], one per stroke with more than k points in
+// stroke order, so stroke g's row of step k is rows[k] + g while g < rows[k + 1] - rows[k]; falloff = device f64[64].
+constexpr int STROKE_MAX_POINTS = 64;
+hipError_t launch_session_stroke_umask(const SessionPool& P, const int* ids, const int* items, const int* rows, int steps, int first,
+                                       const double* falloff, int n, hipStream_t s);
 // ian_session_fit.  begin: IM := GIM of sessions ids[0..n).  adam: rows 0..n-1 of the latent slot z (stride zs) move by one Adam step
 // (ian_fit_step.h) on the gradient rows g (same stride); m, v = the moments, [n][zl]; c1, c2 = the step's bias corrections.
 // loss: loss[i * loss_stride] = the float64 mean of (xhat[i] - table[GIM of ids[i]])^2 over the rectangle of row i of the

@@ -430,6 +430,12 @@ int ian_brush_step_batch(ian_handle* h, int32_t n, const ian_brush_item* items, 
   return batch_common(h, n, items, rgb, z, z_new, dz, x, photo, stream, true);
 }
 
+// the sessions' strokes (ian_rt_session.inc): every step of the batched brush above in one submission
+int ian_session_stroke(ian_handle* h, int32_t n, const ian_session_stroke_item* strokes, int32_t nboxes, const ian_stroke_box* boxes,
+                       int32_t flags, uint8_t* shown, void* stream) {
+  return h ? session_stroke(h, n, strokes, nboxes, boxes, flags, shown, stream) : -1;
+}
+
 int ian_autotune(ian_handle* h, int32_t n, int32_t what, void* stream) {
   int rc = check_ready(h, n);
   if (rc) return rc;

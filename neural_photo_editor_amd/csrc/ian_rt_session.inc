@@ -69,6 +69,7 @@ const SessScratchBuf SESS_SCRATCH[] = {
     {offsetof(SessionScratch, d_stage), 0, SESS_BASE},
     {offsetof(SessionScratch, d_fit), 0, SESS_BASE},
     {offsetof(SessionScratch, d_fit_loss), 0, SESS_BASE},
+    {offsetof(SessionScratch, d_stab), 0, SESS_BASE},
     {offsetof(SessionScratch, d_tanh), 256 * sizeof(float), SESS_BASE},   // last of its group: a failed build never leaves it without its upload
     {offsetof(SessionScratch, d_views), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HIRES},
     {offsetof(SessionScratch, d_out), 0, SESS_HIRES},
@@ -201,6 +202,7 @@ void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
     S.arr.pool.zl = 0;
     S.capacity = 0;
     S.stage_cap = 0;
+    S.stab_cap = 0;
     S.opened.clear(); S.version.clear(); S.has_src.clear(); S.local_flags.clear(); S.hist.clear();
     S.res_valid = false;
   }
@@ -824,6 +826,26 @@ int brush_table_upload(ian_handle* h, int n, bool colours, hipStream_t st, Brush
   *T = BrushTable{S.d_tab, S.d_tab + (size_t)7 * n, colours ? reinterpret_cast<const float*>(S.d_tab + (size_t)8 * n) : nullptr};
   return 0;
 }
+// The residency of ian_session_brush / ian_session_stroke: the decoder's activations belong to sessions ids[i * stride], in that order, at
+// their current latent versions.  hit: a call on exactly these may skip its gather and forward (IAN_NO_DEC_CACHE switches that off);
+// arm: what a call that left them so records at its end (session_enter ended the residency at its start).
+bool session_residency_hit(const decltype(ian_handle::sess)& S, int n, const int32_t* ids, int stride) {
+  bool hit = S.res_valid && (int)S.res_ids.size() == n && getenv("IAN_NO_DEC_CACHE") == nullptr;
+  for (int i = 0; hit && i < n; ++i) {
+    const int id = ids[(size_t)i * stride];
+    hit = S.res_ids[i] == id && S.res_ver[i] == S.version[id];
+  }
+  return hit;
+}
+void session_residency_arm(decltype(ian_handle::sess)& S, int n, const int32_t* ids, int stride) {
+  S.res_ids.resize(n);
+  S.res_ver.resize(n);
+  for (int i = 0; i < n; ++i) {
+    S.res_ids[i] = ids[(size_t)i * stride];
+    S.res_ver[i] = S.version[S.res_ids[i]];
+  }
+  S.res_valid = true;
+}
 // What a brush renders after the events, in the same submission, one synchronisation for both results: nothing (ian_session_brush),
 // window i of session views[i].session == ev[i].session (ian_session_brush_view: count == n) or canvas windows (ian_canvas_brush) -> out
 struct BrushWindows {
@@ -851,8 +873,7 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
   const size_t win_bytes = (size_t)W.count * 3 * (size_t)W.vh * (size_t)W.vw;
   if (W.kind != W.NONE && (rc = session_render_target(h, W.out, win_bytes, &win))) return rc;
   const int pass = h->opt.brush_pass;
-  bool hit = n <= pass && S.res_valid && (int)S.res_ids.size() == n && getenv("IAN_NO_DEC_CACHE") == nullptr;
-  for (int i = 0; hit && i < n; ++i) hit = S.res_ids[i] == ev[i].session && S.res_ver[i] == S.version[ev[i].session];
+  const bool hit = n <= pass && session_residency_hit(S, n, &ev->session, 11);
   hipStream_t st = (hipStream_t)stream;
   session_enter(h, st);   // also ends the residency: re-armed below
   TotalTimer tt(h, st);
@@ -883,15 +904,133 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
   if (W.kind == W.VIEWS && (rc = session_render_enqueue(h, W.count, W.views, W.vw, W.vh, win.dev, st))) return rc;
   if (W.kind == W.CANVAS && (rc = canvas_compose_enqueue(h, W.count, W.windows, W.vw, W.vh, win.dev, st))) return rc;
   if ((rc = session_finish(h, n, sh, false, st, win, win_bytes))) return rc;
-  if (n <= pass) {   // one pass: the resident activations belong to these sessions' new latents
-    S.res_ids.resize(n);
-    S.res_ver.resize(n);
-    for (int i = 0; i < n; ++i) {
-      S.res_ids[i] = ev[i].session;
-      S.res_ver[i] = S.version[ev[i].session];
+  if (n <= pass) session_residency_arm(S, n, &ev->session, 11);   // one pass: the resident activations belong to these sessions' new latents
+  return 0;
+}
+
+// ian_session_stroke (DESIGN.md 4.9): per session a path of rectangles, every step of it in one submission.  The meaning is the loop
+// of ian_session_brush calls in include/ian.h; what is left out is what nobody would look at between the steps.
+// The table (d_stab, one upload): [n ids | n history slots (bit 0 of flags) | 3n colours | steps + 1 row offsets | the rows], the rows
+// step after step, step k holding one ian_brush_item row per stroke with more than k points in stroke order.  The counts do not
+// increase along the array, so the strokes of a step are a prefix of it, the ones that end at a step the tail of that prefix, and a
+// pass (at most opt.brush_pass strokes) is a slice of every step's rows.
+// Per pass: gather Z and one forward (neither when the residency of ian_session_brush hits); the footprints of every point into UMASK
+// (pools with the local reservation); per step the shared middle -- seed, backward, update, forward at z_new -- on the strokes that
+// still run, then the stored blend of those that end here (their Z rows, IM / FIELD, shown), then, when some are left, the forward
+// again at the smaller batch: the per-event calls would miss their residency at the same point, and the decoder's kernels may differ
+// with the batch.  While the set of strokes stays the same, the forward at z_new IS the next step's forward.
+int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int nboxes, const ian_stroke_box* boxes, int flags,
+                   uint8_t* shown, void* stream) {
+  const char* fn = "ian_session_stroke";
+  static_assert(sizeof(ian_session_stroke_item) == 8 * sizeof(int32_t), "ian_session_stroke_item is 8 words");
+  static_assert(sizeof(ian_stroke_box) == 5 * sizeof(int32_t), "ian_stroke_box is 5 words");
+  static_assert(IAN_STROKE_MAX_POINTS == STROKE_MAX_POINTS, "the kernel's LDS holds one rectangle per point");
+  int rc = session_check(h, fn, n, sk ? &sk->session : nullptr, 8, true, true);
+  if (rc) return rc;
+  if (flags & ~1) return fail(h, -7, "%s: flags %d: only bit 0 (mark first) is defined", fn, flags);
+  const bool mark = (flags & 1) != 0;
+  if (mark && (rc = session_need(h, fn, SESS_HISTORY))) return rc;
+  if (!boxes) return fail(h, -1, "null pointer passed to %s", fn);
+  if (is_device_ptr(boxes)) return fail(h, -7, "%s: the boxes must be a host array", fn);
+  if (nboxes < 1) return fail(h, -7, "%s: nboxes = %d: a stroke has at least one rectangle", fn, nboxes);
+  for (int i = 0; i < n; ++i) {
+    const ian_session_stroke_item& s = sk[i];
+    if (s.mode != 0 && s.mode != 1) return fail(h, -7, "%s: item %d has mode %d (0 = imgrad, 1 = imgradRGB toward rgb)", fn, i, s.mode);
+    if (s.count < 1 || s.count > IAN_STROKE_MAX_POINTS)
+      return fail(h, -7, "%s: item %d: count %d outside 1..%d", fn, i, s.count, IAN_STROKE_MAX_POINTS);
+    if (s.first < 0 || (long long)s.first + s.count > nboxes)
+      return fail(h, -7, "%s: item %d: rectangles %d..%lld outside the %d boxes", fn, i, s.first, (long long)s.first + s.count - 1, nboxes);
+    if (i > 0 && s.count > sk[i - 1].count)
+      return fail(h, -7, "%s: item %d: count %d after item %d's %d (the strokes must come with non-increasing count)", fn, i, s.count, i - 1,
+                  sk[i - 1].count);
+    for (int k = 0; k < s.count; ++k) {
+      const ian_stroke_box& b = boxes[s.first + k];
+      if (b.c1 < 0 || b.r1 < 0 || b.c2 > 64 || b.r2 > 64)
+        return fail(h, -7, "%s: item %d: point %d: patch (%d,%d,%d,%d) outside the 64x64 image", fn, i, k, b.c1, b.r1, b.c2, b.r2);
     }
-    S.res_valid = true;
   }
+  if ((rc = session_local_check(h, fn, n, &sk->session, 8))) return rc;
+  auto& S = h->sess;
+  const int pass = h->opt.brush_pass;
+  const bool hit = n <= pass && session_residency_hit(S, n, &sk->session, 8);
+  // the table
+  const int steps = sk[0].count;
+  int rows[IAN_STROKE_MAX_POINTS + 1] = {0};
+  for (int k = 0, act = n; k < steps; ++k) {
+    while (act > 0 && sk[act - 1].count <= k) --act;
+    rows[k + 1] = rows[k] + act;
+  }
+  const size_t o_save = (size_t)n, o_col = (size_t)2 * n, o_rows = (size_t)5 * n, o_items = o_rows + (size_t)steps + 1;
+  const size_t words = o_items + (size_t)7 * rows[steps];
+  if ((rc = grow_dev(h, &S.d_stab, &S.stab_cap, words))) return rc;
+  S.stab_shadow.assign(words, 0);
+  int32_t* t = S.stab_shadow.data();
+  std::vector<SessionHistory> next;   // bit 0: the histories after the mark; they move only after every enqueue succeeded
+  if (mark) next.resize((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    t[i] = sk[i].session;
+    if (mark) {
+      next[i] = S.hist[sk[i].session];
+      t[o_save + i] = session_history_mark(next[i], S.arr.rings.depth);
+    }
+    memcpy(t + o_col + (size_t)3 * i, sk[i].rgb, 3 * sizeof(float));
+  }
+  memcpy(t + o_rows, rows, ((size_t)steps + 1) * sizeof(int32_t));
+  for (int k = 0; k < steps; ++k)
+    for (int i = 0; i < rows[k + 1] - rows[k]; ++i) {
+      int32_t* row = t + o_items + (size_t)7 * (rows[k] + i);   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
+      const ian_stroke_box& b = boxes[sk[i].first + k];
+      row[0] = b.c1; row[1] = b.r1; row[2] = b.c2; row[3] = b.r2; row[4] = sk[i].mode;
+      memcpy(row + 5, &sk[i].coef, sizeof(float));
+      memcpy(row + 6, &b.gscale, sizeof(float));
+    }
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);   // also ends the residency: re-armed below
+  TotalTimer tt(h, st);
+  HIPCHK(h, hipMemcpyAsync(S.d_stab, t, words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int* d_ids = S.d_stab;
+  const int* d_items = S.d_stab + o_items;
+  const float* d_col = reinterpret_cast<const float*>(S.d_stab + o_col);
+  if (mark) HIPCHK(h, launch_session_history_save(S.arr.pool, S.arr.rings, d_ids, S.d_stab + o_save, n, st));   // before UMASK moves
+  Slot& zs = h->slots[h->desc.z_slot];
+  const ResultTarget sh = shown_target(h, shown, true);
+  for (int off = 0; off < n; off += pass) {
+    const int nc = std::min(pass, n - off);
+    const int K = sk[off].count;   // the longest stroke of the pass
+    if (!hit) {
+      if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
+      HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
+      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
+    }
+    bool footprints = false;   // what the kernel would find on the device, as far as the host knows it: the mode flag it does not
+    for (int i = off; S.arr.pool.umask && !footprints && i < off + nc; ++i) footprints = sk[i].mode == 1 && (S.local_flags[sk[i].session] & 1);
+    if (footprints) HIPCHK(h, launch_session_stroke_umask(S.arr.pool, d_ids, d_items, S.d_stab + o_rows, K, off, S.d_falloff, nc, st));
+    for (int k = 0, act = nc; k < K; ++k) {   // act: the strokes of this pass with more than k points
+      BrushSeedSrc seed;
+      seed.table = d_items + (size_t)7 * (rows[k] + off);
+      seed.colour = d_col + (size_t)3 * off;
+      if ((rc = brush_pass_middle(h, act, seed, true, st))) return rc;
+      int keep = act;
+      while (keep > 0 && sk[off + keep - 1].count == k + 1) --keep;
+      if (keep == act) continue;   // the same strokes go on: the activations at z_new are the next step's
+      SessionBlendArgs a = session_blend_args(h, d_ids + off + keep, seed.table + (size_t)7 * keep, sh.dev + (size_t)(off + keep) * SESS_IMG, 1);
+      a.xhat += (size_t)keep * SESS_IMG;
+      a.zslot += (size_t)keep * zs.cs;
+      HIPCHK(h, launch_session_blend(a, act - keep, st));
+      if (keep > 0 && (rc = batch_forward(h, nullptr, keep, st))) return rc;
+      act = keep;
+    }
+  }
+  h->slot_stale[h->desc.out_slot] = 0;
+  // One note per session where the per-event calls make `count` of them.  The version is only ever compared for equality, and
+  // session_history_edited is idempotent: its first call leaves cur == len, where every further one returns at once.  So
+  // ian_session_history reports what the calls would.
+  for (int i = 0; i < n; ++i) {
+    if (mark) S.hist[sk[i].session] = next[i];
+    session_latent_written(S, sk[i].session, false);
+  }
+  if ((rc = session_finish(h, n, sh, false, st))) return rc;
+  if (n <= pass && sk[n - 1].count == steps) session_residency_arm(S, n, &sk->session, 8);   // the brush's rule: one pass, and every stroke ran in the last forward
   return 0;
 }
 

@@ -303,6 +303,7 @@ struct ian_handle {
     unsigned char* d_stage = nullptr;  // saved sessions: staging of records for a host `body`, grown on demand (stage_cap) up to opt.session_stage_bytes
     float* d_fit = nullptr;            // ian_session_fit: Adam's moments of one pass, m [256][zl] then v [256][zl]; by the first such call
     double* d_fit_loss = nullptr;      // ian_session_fit: staging of the loss trace for a host `loss`, [256][513]; by the first call that asks for one
+    int* d_stab = nullptr;             // ian_session_stroke: per call [n ids | n history slots | 3n colours | steps + 1 row offsets | the steps' ian_brush_item rows], grown on demand (stab_cap words)
   };
   struct SessionState : SessionScratch {
     int capacity = 0;
@@ -336,6 +337,9 @@ struct ian_handle {
     // saved sessions (ian_session_save / ian_session_load)
     std::vector<int32_t> rtab_shadow;    // upload source of d_rtab
     size_t stage_cap = 0;
+    // strokes (ian_session_stroke)
+    std::vector<int32_t> stab_shadow;    // upload source of d_stab
+    size_t stab_cap = 0;
     // canvases (ian_sessions_reserve_canvas, ian_rt_canvas.inc): the device arrays, per canvas the size of its picture (0 x 0: never
     // put), per session where it is placed (canvas -1: nowhere; sized with the pool while canvases exist, empty otherwise), and the
     // host's copy of the device table (canv.table), from which a canvas's 8 entries are uploaded whenever they change

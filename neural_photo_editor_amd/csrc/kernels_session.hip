@@ -7,6 +7,7 @@
 //   session_blend_kernel       brush / paint_latents: photo blend (photo mode) or uint8 image (sample mode) per session, z_new -> pool
 //   session_blend_local_kernel the same in a pool with the local reservation: per-session user mask, brush footprint, dampen
 //   session_local_set_kernel   local edits: a session's UMASK := 0 (every open) and its LOCAL flags (ian_session_local)
+//   session_stroke_umask_kernel  strokes: the footprints of all of a stroke's rectangles max-ed into the session's UMASK
 //   session_fit_begin_kernel / _adam_kernel / _loss_kernel  ian_session_fit: IM := GIM, one Adam step on the latent rows, the loss read-out
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
@@ -432,6 +433,70 @@ __global__ __launch_bounds__(256) void session_local_set_kernel(SessionPool P, c
 hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const int* flags, int n, hipStream_t s) {
   if (n < 1 || n > 65535 || !P.umask || !P.local) return hipErrorInvalidValue;
   hipLaunchKernelGGL(session_local_set_kernel, dim3(n), dim3(256), 0, s, P, ids, flags);
+  return hipGetLastError();
+}
+
+// ---- strokes: the footprints of ALL of a stroke's rectangles into the session's UMASK, before its first step --------
+// ian_session_stroke blends only the last point of a stroke, and that blend max-es only its own rectangle's footprint into UMASK; the
+// per-event calls would have max-ed every point's.  This kernel adds them under exactly the blend's conditions (uniform over the
+// workgroup): LOCAL bit 0 of the session, a paint stroke (word 4 of its rows), photo mode.  max is exact and idempotent: the order of
+// the points does not matter, and the last footprint added again by the final blend changes nothing.
+// One workgroup per stroke.  Lane k < steps fetches the stroke's rectangle of step k into LDS (an empty one, or one that is not inside
+// the image -- the host refuses those -- as all zeros: it adds nothing), lanes 0..63 the falloff table.  A lane owns whole pixels: 8
+// pairs of neighbours in a row, one 16-byte load and one 16-byte store each (consecutive lanes, consecutive addresses), and in
+// between the float64 product falloff[dy] * falloff[dx] of photo_blend_image per point and pixel, on gk's distances
+// (PhotoLocalArgs / npe_ops.local_footprint), contraction off.  A stroke without any footprint stores nothing.
+__global__ __launch_bounds__(256) void session_stroke_umask_kernel(SessionPool P, const int* __restrict__ ids, const int* __restrict__ items,
+                                                                   const int* __restrict__ rows, int steps, int first,
+                                                                   const double* __restrict__ falloff) {
+  __shared__ double fall[64];
+  __shared__ int4 rect[STROKE_MAX_POINTS];
+  const int g = first + blockIdx.x;
+  const int id = ids[g];
+  if (!(P.local[id] & 1) || P.mode[id] != 0 || items[(size_t)(rows[0] + g) * 7 + 4] != 1) return;
+  int valid = 0;
+  if (threadIdx.x < 64) fall[threadIdx.x] = falloff[threadIdx.x];
+  if (threadIdx.x < STROKE_MAX_POINTS) {
+    const int k = threadIdx.x;
+    int4 r = make_int4(0, 0, 0, 0);
+    if (k < steps) {
+      const int r0 = rows[k];
+      if (g < rows[k + 1] - r0) {
+        const int* it = items + (size_t)(r0 + g) * 7;
+        const int c1 = it[0], r1 = it[1], c2 = it[2], r2 = it[3];
+        if (c1 >= 0 && r1 >= 0 && c2 <= 64 && r2 <= 64 && c1 < c2 && r1 < r2) {
+          r = make_int4(c1, r1, c2, r2);
+          valid = 1;
+        }
+      }
+    }
+    rect[k] = r;
+  }
+  if (!__syncthreads_or(valid)) return;
+  double2* row = reinterpret_cast<double2*>(P.umask + (size_t)id * (64 * 64));
+  for (int j = threadIdx.x; j < 64 * 64 / 2; j += 256) {
+    const int y = j >> 5, x = (j & 31) * 2;
+    double2 u = row[j];
+    for (int k = 0; k < steps; ++k) {
+      const int4 r = rect[k];   // (c1, r1, c2, r2): the same address for every lane
+      if (r.z <= r.x) continue;
+      const int dy = y < r.y ? r.y - y : (y >= r.w ? y - r.w + 1 : 0);   // 0..63 for 0 <= r1 < r2 <= 64
+      const int dx0 = x < r.x ? r.x - x : (x >= r.z ? x - r.z + 1 : 0);
+      const int dx1 = x + 1 < r.x ? r.x - x - 1 : (x + 1 >= r.z ? x - r.z + 2 : 0);
+      const double fy = fall[dy];
+      const double f0 = fy * fall[dx0], f1 = fy * fall[dx1];
+      u.x = u.x < f0 ? f0 : u.x;
+      u.y = u.y < f1 ? f1 : u.y;
+    }
+    row[j] = u;
+  }
+}
+hipError_t launch_session_stroke_umask(const SessionPool& P, const int* ids, const int* items, const int* rows, int steps, int first,
+                                       const double* falloff, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || first < 0 || steps < 1 || steps > STROKE_MAX_POINTS || !P.umask || !P.local || !P.mode || !ids || !items || !rows ||
+      !falloff)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_stroke_umask_kernel, dim3(n), dim3(256), 0, s, P, ids, items, rows, steps, first, falloff);
   return hipGetLastError();
 }
 

@@ -48,7 +48,7 @@ EXPORTS = (
     "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
-    "ian_session_fit",
+    "ian_session_fit", "ian_session_stroke",
     "ian_session_record_info", "ian_session_save", "ian_session_load",
     "ian_sessions_reserve_canvas", "ian_canvas_put", "ian_canvas_place", "ian_canvas_compose", "ian_canvas_brush", "ian_canvas_commit",
     "ian_canvas_read", "ian_canvas_placements",
@@ -129,6 +129,7 @@ def load_library():
     lib.ian_session_undo.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_history.argtypes = [vp, i32, fp]
     lib.ian_session_fit.argtypes = [vp, i32, C.POINTER(SessionFitItem), i32, C.c_float, fp, fp, vp]
+    lib.ian_session_stroke.argtypes = [vp, i32, C.POINTER(SessionStroke), i32, C.POINTER(StrokeBox), i32, fp, vp]
     lib.ian_session_record_info.argtypes = [vp, C.POINTER(SessionMeta), fp, fp]
     lib.ian_session_save.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_load.argtypes = [vp, i32, fp, fp, fp, vp]
@@ -194,6 +195,21 @@ class SessionView(C.Structure):
 class SessionFitItem(C.Structure):
     """ian_session_fit_item (include/ian.h): one session of ian_session_fit and the rectangle its loss is taken over."""
     _fields_ = [("session", C.c_int32), ("c1", C.c_int32), ("r1", C.c_int32), ("c2", C.c_int32), ("r2", C.c_int32)]
+
+
+STROKE_MAX_POINTS = 64       # IAN_STROKE_MAX_POINTS (include/ian.h)
+
+
+class StrokeBox(C.Structure):
+    """ian_stroke_box (include/ian.h): one rectangle of a stroke and the gradient scale that goes with it."""
+    _fields_ = [("c1", C.c_int32), ("r1", C.c_int32), ("c2", C.c_int32), ("r2", C.c_int32), ("gscale", C.c_float)]
+
+
+class SessionStroke(C.Structure):
+    """ian_session_stroke_item (include/ian.h): one session's stroke in ian_session_stroke: its rectangles boxes[first .. first + count),
+    and the mode, coefficient and colour of every point."""
+    _fields_ = [("session", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("mode", C.c_int32), ("coef", C.c_float),
+                ("rgb", C.c_float * 3)]
 
 
 class CanvasPlacement(C.Structure):
@@ -446,6 +462,12 @@ class Handle:
         null = C.c_void_p(0)
         self._check(self.lib.ian_session_fit(self._h, len(items), items, int(steps), float(lr), _ptr(loss) if loss is not None else null,
                                              _ptr(shown) if shown is not None else null, C.c_void_p(stream or 0)))
+
+    def session_stroke(self, strokes, boxes, flags=0, shown=None, stream=None):
+        """ian_session_stroke; strokes / boxes = ctypes arrays of SessionStroke (n = its length, counts non-increasing) and StrokeBox,
+        flags bit 0 = mark first, shown u8[n,3,64,64] or None."""
+        self._check(self.lib.ian_session_stroke(self._h, len(strokes), strokes, len(boxes), boxes, int(flags),
+                                                _ptr(shown) if shown is not None else C.c_void_p(0), C.c_void_p(stream or 0)))
 
     def session_record_info(self):
         """ian_session_record_info -> (the pool's layout as a SessionMeta, the byte offsets of its arrays in a body); host only."""

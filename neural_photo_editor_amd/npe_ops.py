@@ -329,6 +329,27 @@ def umask_paint(U, box, t):
     return np.maximum(U, local_footprint(c1, r1, c2, r2, t))
 
 
+def brush_rect(x, y, d):
+    """move_mouse's brush rectangle (NPE.py:148-156) for a point (x, y) that is already in 64-pixel space and the brush-size slider's
+    value d -> (c1, r1, c2, r2): brush_width = d//4 + 1 pixels a side, centred on the point and pushed back inside the image.  The //4
+    of NPE.py:148 (canvas to image) and of :202 (the rectangle read back from the canvas, exact: its corners are multiples of 4) stay
+    with the caller."""
+    x, y, d = int(x), int(y), int(d)
+    brush_width = (d // 4) + 1
+    xmin = max(min(x - brush_width // 2, 64 - brush_width), 0)
+    ymin = max(min(y - brush_width // 2, 64 - brush_width), 0)
+    return xmin, ymin, xmin + brush_width, ymin + brush_width
+
+
+def stroke_footprint(U, boxes, t):
+    """USER_MASK after a whole stroke (ian_session_stroke): umask_paint for every rectangle of boxes (K,4), in sequence.  np.maximum is
+    exact, so the order of the rectangles does not matter and a rectangle given twice adds nothing."""
+    U = np.array(U, np.float64)
+    for box in np.asarray(boxes).reshape(-1, 4):
+        U = umask_paint(U, box, t)
+    return U
+
+
 def photo_blend_local(xhat, recon_uint8, error, U=None, half=None, dampen=False, thresh=DAMPEN_THRESH):
     """photo_blend_host with the user mask and / or dampen -> (IM uint8, MASK_L float64, FIELD float32).
       MASK    exactly photo_blend_host's (half = gaussian_half_kernel(...): the same filter through separable_reflect_filter, which
