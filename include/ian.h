@@ -479,6 +479,45 @@ typedef struct ian_session_stroke_item {
 int ian_session_stroke(ian_handle* h, int32_t n, const ian_session_stroke_item* strokes, int32_t nboxes, const ian_stroke_box* boxes,
                        int32_t flags, uint8_t* shown, void* stream);
 
+/* ---- the clone brush: paint from another picture of the pool ----
+   ian_session_brush pulls a rectangle towards one flat colour.  A photo editor's second brush pulls it towards a picture: "give A the
+   mouth of B" (another session as the source), the clone stamp (the session itself, at an offset), the restore brush (the session's own
+   GIM at offset 0).  Every byte of such a target already lies in the pool, so nothing but the event table is uploaded.
+   Meaning, steps == 1: item i is a mode-1 event of ian_session_brush on events[i].session whose target image T_i replaces the constant
+   colour,
+       T_i[co, r, c] = tanh_table[F[source][co, r + dr, c + dc]]   for (r, c) inside the rectangle,
+   F the source's GIM, IM or RECON row and tanh_table the table of ian_session_open / ian_session_fit
+   (np.asarray([to_tanh(level)], dtype=np.float32), ian_session_tanh_table); elements outside the rectangle are not read.  Z, IM (photo-mode
+   destination: the NPE.py:218-231 blend), shown and, where the pool has them, FIELD / FIELD_KIND and UMASK (the rectangle's footprint
+   under LOCAL bit 0, exactly as a paint event) are bit for bit what ian_brush_step_batch gives for the same latents, rectangles, coef,
+   gscale and rgb = T at the same batch size with photo = (RECON, ERROR) of the destinations.  A sample-mode destination shows
+   np.uint8(from_tanh(x)) and keeps its IM, as in ian_session_brush.
+   steps == K (1..IAN_CLONE_MAX_STEPS; a target picture needs several gradient steps where a flat colour gets them from the drag): every
+   session ends byte for byte where K calls with steps == 1 and the same events leave it, and shown is what the last of them displays.
+   Only the last step blends: IM and FIELD are rewritten from RECON by every event and the UMASK footprint of a repeated rectangle is
+   idempotent; the forward at z_new of step k is the forward at Z of step k + 1.  The sources do not change during the call: GIM and
+   RECON are not written by a brush, and an IM source that is also a destination is refused.  The same source may serve several items.
+   Residency, latent versions and the history behave as in ian_session_brush: a hit on the same ids, order and versions skips the
+   gather and the forward, the residency is re-armed at the end when the call was one pass, every destination gets one new latent version
+   and one `edited` note.  For one undo step per call, call ian_session_mark first.  More than `brush_pass` items (ian_set_option) run
+   as passes, each pass through all its steps before the next starts.  Host -> device: the event table (11 words per event); device ->
+   host: shown (u8[n,3,64,64], host or device, or NULL).  One synchronisation at the end, and only when shown is host memory.  A pool
+   that never calls this launches, moves and computes nothing it did not before.
+   -6 where ian_session_brush returns it.  -7, naming the item, before anything is enqueued or any host state moves: everything
+   ian_session_brush refuses for the destination, a source outside the pool or not opened, a field other than the three, a non-empty
+   rectangle whose shifted copy leaves the image (c1 + dc < 0, c2 + dc > 64, likewise rows), a source with field == IAN_SESSION_IM that
+   is also a destination of this call, steps outside 1..IAN_CLONE_MAX_STEPS, events in device memory. */
+#define IAN_CLONE_MAX_STEPS 64
+typedef struct ian_session_clone_event {
+  int32_t session;          /* destination: id in the pool */
+  int32_t c1, r1, c2, r2;   /* rectangle on the destination, columns first; an empty one gives a zero gradient */
+  int32_t source;           /* id of the session the target is read from; may equal `session` */
+  int32_t field;            /* IAN_SESSION_GIM, IAN_SESSION_IM or IAN_SESSION_RECON of the source */
+  int32_t dc, dr;           /* the target of destination pixel (r, c) is source pixel (r + dr, c + dc) */
+  float coef, gscale;       /* Z := Z + coef * (dZ * gscale), as ian_session_event */
+} ian_session_clone_event;
+int ian_session_clone(ian_handle* h, int32_t n, const ian_session_clone_event* events, int32_t steps, uint8_t* shown, void* stream);
+
 /* ---- saving and loading whole sessions: the editor state as bytes that can leave the pool ----
    Everything a session is -- the 64x64 state, the full-resolution source and edit field, the user mask and flags, the ring of undo
    states with its cursor -- lives in one handle's pool.  A record is that state as plain bytes: keep a project beyond the process,

@@ -22,7 +22,8 @@ import warnings
 import numpy as np
 
 from . import checkpoints, config_loader, lowering, made
-from .lib import STROKE_MAX_POINTS, BrushItem, Handle, SessionEvent, SessionFitItem, SessionStroke, SessionView, StrokeBox
+from .lib import CLONE_MAX_STEPS, SESSION_FIELDS, STROKE_MAX_POINTS, BrushItem, Handle, SessionCloneEvent, SessionEvent, SessionFitItem
+from .lib import SessionStroke, SessionView, StrokeBox
 
 BATCH_MAX = 256     # ian_grad_batch / ian_brush_step_batch: 1 <= n <= 256
 
@@ -211,6 +212,66 @@ def pack_session_strokes(ids, paths, colours=None, modes=None, weight=0.05, sign
             b.gscale = float(1 + (c2 - c1))
         first += len(pl[i])
     return strokes, boxes, perm
+
+
+CLONE_FIELDS = ("GIM", "IM", "RECON")       # what a clone event may read of its source
+
+
+def check_clone_steps(steps):
+    """steps of ian_session_clone -> int, refused with the library's wording."""
+    if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= CLONE_MAX_STEPS:
+        raise ValueError("steps = %r outside 1..%d" % (steps, CLONE_MAX_STEPS))
+    return int(steps)
+
+
+def pack_session_clones(ids, boxes, sources, offsets=(0, 0), field="GIM", weight=0.05, sign=-1.0, capacity=None, opened=None):
+    """Python arguments of ian_session_clone -> a ctypes array of ian_session_clone_event (include/ian.h), validated with the library's
+    own rules and wording before the library sees anything.  ids (n,) destination session ids, each once; boxes (n,4) or (4,) as
+    (c1, r1, c2, r2) on the destination, floats truncated as imgrad's int() does; sources (n,) or one id: the sessions the targets are
+    read from (a source may equal its destination, and serve several items); offsets (n,2) or (2,) as (dc, dr): the target of
+    destination pixel (r, c) is source pixel (r + dr, c + dc); field "GIM", "IM" or "RECON", one for all or one per item; weight and
+    sign scalars or length-n arrays: coef = float32(sign*weight), gscale = float32(1 + (c2 - c1)) (NPE.py:206).
+    capacity / opened (a container of opened ids), when given, bound and vet destinations and sources alike."""
+    idl = [int(v) for v in check_session_ids(ids, capacity, opened)]
+    n = len(idl)
+    b = np.asarray(boxes)
+    if b.ndim == 1 and b.shape == (4,):
+        b = np.tile(b, (n, 1))
+    if b.ndim != 2 or b.shape != (n, 4):
+        raise ValueError("boxes must have shape (%d,4) or (4,) as (c1,r1,c2,r2), got %s" % (n, b.shape))
+    src = np.asarray(sources)
+    if src.ndim == 0:
+        src = np.tile(src, n)
+    if src.shape != (n,) or not np.issubdtype(src.dtype, np.integer):
+        raise ValueError("sources must be one session id or %d of them, got %s %s" % (n, src.dtype, src.shape))
+    off = _int_pairs(offsets, n, "offsets")
+    fl = [field] * n if isinstance(field, str) else list(field)
+    if len(fl) != n:
+        raise ValueError("field must be one name or %d of them, got %d" % (n, len(fl)))
+    w, sg = per_item(weight, "weight", n), per_item(sign, "sign", n)
+    dest = {v: i for i, v in enumerate(idl)}
+    ev = (SessionCloneEvent * n)()
+    for i in range(n):
+        c1, r1, c2, r2 = [int(v) for v in b[i]]
+        s, dc, dr = int(src[i]), int(off[i, 0]), int(off[i, 1])
+        if c1 < 0 or r1 < 0 or c2 > 64 or r2 > 64:
+            raise ValueError("item %d: patch (%d,%d,%d,%d) outside the 64x64 image" % (i, c1, r1, c2, r2))
+        if s < 0 or (capacity is not None and s >= capacity):
+            raise ValueError("item %d: source session %d outside the pool%s" % (i, s, "" if capacity is None else " (capacity %d)" % capacity))
+        if opened is not None and s not in opened:
+            raise ValueError("item %d: source session %d has not been opened" % (i, s))
+        if fl[i] not in CLONE_FIELDS:
+            raise ValueError("item %d: field %r (GIM, IM or RECON of the source)" % (i, fl[i]))
+        if c1 < c2 and r1 < r2 and (c1 + dc < 0 or c2 + dc > 64 or r1 + dr < 0 or r2 + dr > 64):
+            raise ValueError("item %d: patch (%d,%d,%d,%d) shifted by (%d,%d) leaves the 64x64 image" % (i, c1, r1, c2, r2, dc, dr))
+        if fl[i] == "IM" and s in dest:
+            raise ValueError("item %d: source session %d is read from IM, which item %d of this call writes" % (i, s, dest[s]))
+        e = ev[i]
+        e.session, e.c1, e.r1, e.c2, e.r2 = idl[i], c1, r1, c2, r2
+        e.source, e.field, e.dc, e.dr = s, SESSION_FIELDS[fl[i]][0], dc, dr
+        e.coef = sg[i] * w[i]                  # rounded to float32 by ctypes, as numpy rounds the scalar
+        e.gscale = float(1 + (c2 - c1))
+    return ev
 
 
 def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, sourced=None, events=None):
@@ -523,6 +584,7 @@ class EditSessions:
         sample  sample (:317-327), z from the caller                                set_latent  paint_latents (:286-302)
         paint   NPE.paint (:192-235)            scroll  NPE.scroll (:305-316)      brush   the general form of both
         stroke / paint_stroke  a whole drag per session (K rectangles along the mouse track) in one submission -> the picture at its end
+        clone / restore  paint towards a rectangle of another session's picture, or back towards the session's own photo, several steps
     Photos larger than 64x64 (no counterpart in NPE.py): reserve_hires(scale) keeps every session's photo at 64*scale pixels a side;
         open_hires  infer from the full-size photo     render  windows of the edited picture at full size
         brush_view / paint(view=) / scroll(view=)      the event and its window in one submission
@@ -929,6 +991,23 @@ class EditSessions:
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
         self._h.session_brush(ev, shown)
         return shown
+
+    def clone(self, ids, boxes, sources, offsets=(0, 0), field="GIM", steps=1, weight=0.05, sign=-1.0):
+        """The clone brush (ian_session_clone): the rectangle boxes[i] of session ids[i] is pulled towards the rectangle shifted by
+        offsets[i] = (dc, dr) of session sources[i]'s GIM, IM or RECON (pack_session_clones), `steps` gradient steps (1..64) in one
+        submission -> shown uint8 (n,3,64,64).  Each step is a paint event whose target is that picture instead of a flat colour; the
+        sessions end byte for byte where `steps` calls with steps=1 leave them.  For one undo step call mark(ids) first."""
+        steps = check_clone_steps(steps)
+        ev = pack_session_clones(ids, boxes, sources, offsets, field, weight, sign, capacity=self.capacity, opened=self._opened)
+        shown = np.empty((len(ev), 3, 64, 64), np.uint8)
+        self._h.session_clone(ev, steps, shown)
+        return shown
+
+    def restore(self, ids, boxes, steps=1, weight=0.05):
+        """The restore brush: the rectangles are pulled back towards the sessions' own photos -- clone from each session's own GIM at
+        offset 0.  The user mask, the edit field and the undo history go on as for a paint event (reset and fit would clear them)."""
+        idv = self._ids(ids, True)
+        return self.clone(idv, boxes, idv, (0, 0), "GIM", steps, weight, -1.0)
 
     def stroke(self, ids, paths, colours=None, modes=None, weight=0.05, sign=-1.0, mark=False):
         """Whole brush paths in one submission (ian_session_stroke): paths = one (K_i,4) array of rectangles per session, 1..64 points,

@@ -234,6 +234,11 @@ struct BrushSeedSrc {
   const unsigned char* gim = nullptr;   // the session pool's GIM base, u8 [capacity][3*64*64]
   const int* ids = nullptr;             // device int[n]: the items' session ids
   const float* tanh_tab = nullptr;      // device float[256]: to_tanh of the uint8 levels (ian_session_tanh_table)
+  // ... or, with a table, another picture of the pool, shifted (ian_session_clone; needs gim and tanh_tab too): the target of element
+  // o of item i is tanh_tab[F[clone[3i] * 12288 + o + clone[3i + 2]]], F = gim, im or recon for clone[3i + 1] = 0, 1, 2
+  const unsigned char* im = nullptr;    // the pool's IM and RECON bases, as gim
+  const unsigned char* recon = nullptr;
+  const int* clone = nullptr;           // device int[n][3]: source session, field selector, shift dr * 64 + dc
 };
 // d loss / d x_hat of n items: g NCHW [n,3,H,W], zero outside each item's rectangle
 hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, float* g, int H, int W, hipStream_t s);

@@ -908,6 +908,78 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
   return 0;
 }
 
+// ian_session_clone (DESIGN.md 4.10): a paint event whose target is a rectangle of another picture of the pool, `steps` gradient steps in
+// one submission.  The table is the brush's (brush_table_upload, 11 words per event); the colour slot carries the three words of
+// SEED_CLONE: source id, field selector (0 GIM, 1 IM, 2 RECON), shift dr * 64 + dc.  The item rows carry loss kind 1, so the blend sees
+// a paint event.  Per pass: gather Z and one forward (neither when the residency of ian_session_brush hits), `steps` times the shared
+// middle -- seed, backward, update, forward at z_new, which IS the next step's forward -- then the stored blend once: the blends of
+// the steps before it would be overwritten (IM and FIELD are a function of the latent, RECON, ERROR and UMASK; the footprint of the
+// one rectangle into UMASK is a max, the same after one time as after `steps`).
+int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int steps, uint8_t* shown, void* stream) {
+  const char* fn = "ian_session_clone";
+  static_assert(sizeof(ian_session_clone_event) == 11 * sizeof(int32_t), "ian_session_clone_event is 11 words");
+  int rc = session_check(h, fn, n, ev ? &ev->session : nullptr, 11, true, true);
+  if (rc) return rc;
+  if (steps < 1 || steps > IAN_CLONE_MAX_STEPS) return fail(h, -7, "%s: steps = %d outside 1..%d", fn, steps, IAN_CLONE_MAX_STEPS);
+  auto& S = h->sess;
+  std::map<int, int> dest;
+  for (int i = 0; i < n; ++i) dest.emplace(ev[i].session, i);
+  auto selector = [](int field) { return field == IAN_SESSION_GIM ? 0 : (field == IAN_SESSION_IM ? 1 : (field == IAN_SESSION_RECON ? 2 : -1)); };
+  auto inside = [](const ian_session_clone_event& e) { return e.c1 < e.c2 && e.r1 < e.r2; };   // the rectangle has elements: only then is the source read
+  for (int i = 0; i < n; ++i) {
+    const ian_session_clone_event& e = ev[i];
+    if ((rc = check_rect(h, fn, i, e.c1, e.r1, e.c2, e.r2, "patch"))) return rc;
+    if (e.source < 0 || e.source >= S.capacity) return fail(h, -7, "%s: item %d: source session %d outside the pool (capacity %d)", fn, i, e.source, S.capacity);
+    if (!S.opened[e.source]) return fail(h, -7, "%s: item %d: source session %d has not been opened", fn, i, e.source);
+    if (selector(e.field) < 0)
+      return fail(h, -7, "%s: item %d: field %d (IAN_SESSION_GIM, IAN_SESSION_IM or IAN_SESSION_RECON of the source)", fn, i, e.field);
+    if (inside(e) && ((long long)e.c1 + e.dc < 0 || (long long)e.c2 + e.dc > 64 || (long long)e.r1 + e.dr < 0 || (long long)e.r2 + e.dr > 64))
+      return fail(h, -7, "%s: item %d: patch (%d,%d,%d,%d) shifted by (%d,%d) leaves the 64x64 image", fn, i, e.c1, e.r1, e.c2, e.r2, e.dc, e.dr);
+    if (e.field == IAN_SESSION_IM && dest.count(e.source))
+      return fail(h, -7, "%s: item %d: source session %d is read from IM, which item %d of this call writes", fn, i, e.source, dest[e.source]);
+  }
+  if ((rc = session_local_check(h, fn, n, &ev->session, 11))) return rc;
+  const int pass = h->opt.brush_pass;
+  const bool hit = n <= pass && session_residency_hit(S, n, &ev->session, 11);
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);   // also ends the residency: re-armed below
+  TotalTimer tt(h, st);
+  BrushTable tab;
+  rc = brush_table_upload(h, n, true, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* src) {
+    const ian_session_clone_event& e = ev[i];
+    row[0] = e.c1; row[1] = e.r1; row[2] = e.c2; row[3] = e.r2; row[4] = 1;   // ian_brush_item's layout, loss kind 1
+    memcpy(row + 5, &e.coef, sizeof(float));
+    memcpy(row + 6, &e.gscale, sizeof(float));
+    *id = e.session;
+    src[0] = e.source; src[1] = selector(e.field); src[2] = inside(e) ? e.dr * 64 + e.dc : 0;
+  });
+  if (rc) return rc;
+  Slot& zs = h->slots[h->desc.z_slot];
+  const ResultTarget sh = shown_target(h, shown, true);
+  for (int off = 0; off < n; off += pass) {
+    const int nc = std::min(pass, n - off);
+    if (!hit) {
+      if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
+      HIPCHK(h, launch_session_gather_z(S.arr.pool, tab.ids + off, zs.d, zs.cs, nc, st));
+      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
+    }
+    BrushSeedSrc seed;
+    seed.table = tab.items + (size_t)7 * off;
+    seed.clone = reinterpret_cast<const int*>(tab.colour) + (size_t)3 * off;
+    seed.gim = S.arr.pool.gim; seed.im = S.arr.pool.im; seed.recon = S.arr.pool.recon;
+    seed.tanh_tab = S.d_tanh;
+    for (int k = 0; k < steps; ++k)
+      if ((rc = brush_pass_middle(h, nc, seed, true, st))) return rc;
+    HIPCHK(h, launch_session_blend(session_blend_args(h, tab.ids + off, seed.table, sh.dev + (size_t)off * SESS_IMG, 1), nc, st));
+  }
+  h->slot_stale[h->desc.out_slot] = 0;
+  // one note per destination where `steps` calls make `steps`: see ian_session_stroke
+  for (int i = 0; i < n; ++i) session_latent_written(S, ev[i].session, false);
+  if ((rc = session_finish(h, n, sh, false, st))) return rc;
+  if (n <= pass) session_residency_arm(S, n, &ev->session, 11);
+  return 0;
+}
+
 // ian_session_stroke (DESIGN.md 4.9): per session a path of rectangles, every step of it in one submission.  The meaning is the loop
 // of ian_session_brush calls in include/ian.h; what is left out is what nobody would look at between the steps.
 // The table (d_stab, one upload): [n ids | n history slots (bit 0 of flags) | 3n colours | steps + 1 row offsets | the rows], the rows
@@ -1336,6 +1408,9 @@ int ian_session_history(ian_handle* h, int32_t id, int32_t out[3]) {
 int ian_session_fit(ian_handle* h, int32_t n, const ian_session_fit_item* items, int32_t steps, float lr, double* loss, uint8_t* shown,
                     void* stream) {
   return h ? session_fit(h, n, items, steps, lr, loss, shown, stream) : -1;
+}
+int ian_session_clone(ian_handle* h, int32_t n, const ian_session_clone_event* events, int32_t steps, uint8_t* shown, void* stream) {
+  return h ? session_clone(h, n, events, steps, shown, stream) : -1;
 }
 int ian_session_record_info(ian_handle* h, ian_session_meta* layout, int64_t* offsets, int32_t* ncols) {
   return h ? session_record_info(h, layout, offsets, ncols) : -1;

@@ -19,11 +19,14 @@ namespace ian {
 enum { SEED_IMM = 0,      // the rectangle and loss kind are launch arguments, the target an image (the eager single call)
        SEED_RGB = 1,      // row blockIdx.y of the ian_brush_item table, the target an image rgb [n,3,H,W]
        SEED_COLOUR = 2,   // the same table, the target a constant colour [n][3] (ian_session_brush, NPE.py:205 myRGB)
-       SEED_PHOTO = 3 };  // the same table, the target the item's own photo: tab[GIM byte] of session ids[item] (ian_session_fit)
-struct SeedRect { int c1, r1, c2, r2, mode, id; };   // id: SEED_PHOTO only, the item's session
-constexpr int SEED_PHOTO_IMG = 3 * 64 * 64;          // a GIM row of the session pool
+       SEED_PHOTO = 3,    // the same table, the target the item's own photo: tab[GIM byte] of session ids[item] (ian_session_fit)
+       SEED_CLONE = 4 };  // the same table, the target another picture of the pool, shifted: tab[F byte at o + shift] of session
+                          // clone[3 item], F = its GIM, IM or RECON row (ian_session_clone)
+struct SeedRect { int c1, r1, c2, r2, mode, id, field, shift; };   // id: SEED_PHOTO the item's session, SEED_CLONE its source;
+                                                                   // field, shift: SEED_CLONE only
+constexpr int SEED_PHOTO_IMG = 3 * 64 * 64;          // a GIM / IM / RECON row of the session pool
 template <int KIND> struct SeedLds {                 // ints / floats of LDS a kernel hands to seed_fetch
-  static constexpr int SP = KIND == SEED_PHOTO ? 6 : 5, SC = KIND == SEED_PHOTO ? 256 : 4;
+  static constexpr int SP = KIND == SEED_CLONE ? 8 : (KIND == SEED_PHOTO ? 6 : 5), SC = (KIND == SEED_PHOTO || KIND == SEED_CLONE) ? 256 : 4;
 };
 
 // The table may live in mapped host memory (zero-copy graphs): ONE lane per word fetches it and hands it on through LDS -- a scalar
@@ -36,6 +39,8 @@ template <int KIND> struct SeedLds {                 // ints / floats of LDS a k
 // no bank conflict).  Staging costs one load per thread under the barrier the rectangle needs anyway (the workgroups are 256
 // threads, one per entry), as session_open_in_kernel stages it.  The unfused kernel looks up once per thread: there staging neither
 // wins nor loses, and it keeps the one seed_value body.
+// SEED_CLONE is SEED_PHOTO with the row chosen per item: its three words (source id, field selector, shift) travel like SEED_PHOTO's
+// id, one lane per word, and the table is staged for the same reason (ian_session_clone takes the whole picture as a rectangle too).
 template <int KIND>
 __device__ __forceinline__ SeedRect seed_fetch(const BrushSeedSrc& src, int item, int* sp, float* sc) {
   if (KIND == SEED_IMM) return {src.c1, src.r1, src.c2, src.r2, src.mode, 0};
@@ -45,11 +50,24 @@ __device__ __forceinline__ SeedRect seed_fetch(const BrushSeedSrc& src, int item
     if (threadIdx.x == 5) sp[5] = src.ids[item];
     sc[threadIdx.x] = src.tanh_tab[threadIdx.x];
   }
+  if (KIND == SEED_CLONE) {
+    if (threadIdx.x >= 5 && threadIdx.x < 8) sp[threadIdx.x] = src.clone[item * 3 + (threadIdx.x - 5)];
+    sc[threadIdx.x] = src.tanh_tab[threadIdx.x];
+  }
   __syncthreads();
   // the same five words in every lane: kept in scalar registers, as the launch arguments of SEED_IMM are
   return {__builtin_amdgcn_readfirstlane(sp[0]), __builtin_amdgcn_readfirstlane(sp[1]), __builtin_amdgcn_readfirstlane(sp[2]),
           __builtin_amdgcn_readfirstlane(sp[3]), __builtin_amdgcn_readfirstlane(sp[4]),
-          KIND == SEED_PHOTO ? __builtin_amdgcn_readfirstlane(sp[5]) : 0};
+          (KIND == SEED_PHOTO || KIND == SEED_CLONE) ? __builtin_amdgcn_readfirstlane(sp[5]) : 0,
+          KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[6]) : 0, KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[7]) : 0};
+}
+// the u8 row a seed's targets are looked up in: SEED_PHOTO the GIM row of the item's session, SEED_CLONE the row of its source that
+// the field selector names (0 GIM, 1 IM, 2 RECON: the same for every lane of the workgroup); the other kinds have none
+template <int KIND>
+__device__ __forceinline__ const unsigned char* seed_row(const BrushSeedSrc& src, const SeedRect& R) {
+  if (KIND == SEED_PHOTO) return src.gim + (size_t)R.id * SEED_PHOTO_IMG;
+  if (KIND == SEED_CLONE) return (R.field == 0 ? src.gim : (R.field == 1 ? src.im : src.recon)) + (size_t)R.id * SEED_PHOTO_IMG;
+  return nullptr;
 }
 // 1/N, or 0 for an empty rectangle
 __device__ __forceinline__ float seed_inv(const SeedRect& R) {
@@ -57,11 +75,16 @@ __device__ __forceinline__ float seed_inv(const SeedRect& R) {
   return cnt > 0 ? 1.f / (float)cnt : 0.f;
 }
 // the seed of element o (channel co, value xh) of the item's image, for an element INSIDE a non-empty rectangle; rgb_i = the item's
-// target image, sc = its colour in LDS (SEED_PHOTO: the tanh table, gim_i = the session's GIM row): whichever KIND names is read,
-// and only in mode 1
+// target image, sc = its colour in LDS (SEED_PHOTO / SEED_CLONE: the tanh table, gim_i = the row of seed_row): whichever KIND names
+// is read, and only in mode 1
 template <int KIND>
 __device__ __forceinline__ float seed_value(int mode, float inv, float xh, const float* rgb_i, const float* sc,
-                                            const unsigned char* gim_i, int o, int co) {
+                                            const unsigned char* gim_i, int o, int co, int shift) {
+  if (KIND == SEED_CLONE) {
+    // o lies inside the item's rectangle, and ian_session_clone refused every rectangle whose copy shifted by (dr, dc) leaves the
+    // 64x64 image: o + shift = (co * 64 + r + dr) * 64 + c + dc stays inside channel plane co of the source row
+    return (mode == 0) ? inv : 2.f * (xh - sc[gim_i[o + shift]]) * inv;
+  }
   return (mode == 0) ? inv : 2.f * (xh - (KIND == SEED_COLOUR ? sc[co] : (KIND == SEED_PHOTO ? sc[gim_i[o]] : rgb_i[o]))) * inv;
 }
 
@@ -77,13 +100,13 @@ __global__ __launch_bounds__(256) void brush_seed_kernel(BrushSeedSrc src, const
   if (i >= 3 * H * W) return;
   const size_t img = (size_t)item * 3 * H * W;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && R.mode) ? src.rgb + img : nullptr;
-  const unsigned char* gim_i = KIND == SEED_PHOTO ? src.gim + (size_t)R.id * SEED_PHOTO_IMG : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
+  const unsigned char* gim_i = seed_row<KIND>(src, R);
   const int xx = i % W, yy = (i / W) % H;
   float v = 0.f;
   if (yy >= R.r1 && yy < R.r2 && xx >= R.c1 && xx < R.c2) {
     const float inv = seed_inv(R);
-    if (inv > 0.f) v = seed_value<KIND>(R.mode, inv, xh_i[i], rgb_i, sc, gim_i, i, i / (H * W));
+    if (inv > 0.f) v = seed_value<KIND>(R.mode, inv, xh_i[i], rgb_i, sc, gim_i, i, i / (H * W), R.shift);
   }
   (g + img)[i] = v;
 }
@@ -113,8 +136,8 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
   const int OH = 2 * H, OW = 2 * W;
   const size_t img = (size_t)item * Cout * OH * OW;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && R.mode) ? src.rgb + img : nullptr;
-  const unsigned char* gim_i = KIND == SEED_PHOTO ? src.gim + (size_t)R.id * SEED_PHOTO_IMG : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
+  const unsigned char* gim_i = seed_row<KIND>(src, R);
   const float inv = seed_inv(R);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   if (inv > 0.f) {
@@ -129,7 +152,7 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
         for (int co = 0; co < Cout; ++co) {
           const int o = (co * OH + oy) * OW + ox;
           const float xh = xh_i[o];
-          float gv = seed_value<KIND>(R.mode, inv, xh, rgb_i, sc, gim_i, o, co);
+          float gv = seed_value<KIND>(R.mode, inv, xh, rgb_i, sc, gim_i, o, co, R.shift);
           gv = gv * m_dact(xh, out_act) * (oscale ? oscale[co] : 1.f);
           const float4 wv = *reinterpret_cast<const float4*>(w + ((size_t)(ky * 5 + kx) * 4 + co) * Cin + ci);
           acc[0] = fmaf(gv, wv.x, acc[0]);
@@ -152,18 +175,24 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
 }
 
 static int seed_kind(const BrushSeedSrc& src) {
-  return !src.table ? SEED_IMM : (src.gim ? SEED_PHOTO : (src.colour ? SEED_COLOUR : SEED_RGB));
+  return !src.table ? SEED_IMM : (src.clone ? SEED_CLONE : (src.gim ? SEED_PHOTO : (src.colour ? SEED_COLOUR : SEED_RGB)));
 }
 // a photo target is a GIM row of the pool: 3 x 64 x 64 bytes, with the id list and the table to go with it
 static bool seed_photo_ok(const BrushSeedSrc& src, int C, int H, int W) { return src.ids && src.tanh_tab && C * H * W == SEED_PHOTO_IMG; }
+// a cloned target is a GIM, IM or RECON row of the pool: all three bases, the table, and the 3 x 64 x 64 image the shift is made for
+static bool seed_clone_ok(const BrushSeedSrc& src, int C, int H, int W) {
+  return src.gim && src.im && src.recon && src.tanh_tab && C == 3 && H == 64 && W == 64;
+}
 
 hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, float* g, int H, int W, hipStream_t s) {
   const int kind = seed_kind(src);
   if (n < 1 || n > 65535 || (kind == SEED_IMM && n != 1) || (kind == SEED_PHOTO && !seed_photo_ok(src, 3, H, W))) return hipErrorInvalidValue;
+  if (kind == SEED_CLONE && !seed_clone_ok(src, 3, H, W)) return hipErrorInvalidValue;
   const dim3 grid((3 * H * W + 255) / 256, n);
   if (kind == SEED_IMM) hipLaunchKernelGGL(brush_seed_kernel<SEED_IMM>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_RGB) hipLaunchKernelGGL(brush_seed_kernel<SEED_RGB>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_PHOTO) hipLaunchKernelGGL(brush_seed_kernel<SEED_PHOTO>, grid, dim3(256), 0, s, src, xhat, g, H, W);
+  else if (kind == SEED_CLONE) hipLaunchKernelGGL(brush_seed_kernel<SEED_CLONE>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else hipLaunchKernelGGL(brush_seed_kernel<SEED_COLOUR>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   return hipGetLastError();
 }
@@ -173,8 +202,12 @@ hipError_t launch_brush_seed_dec_out(const BrushSeedSrc& src, int n, const float
   const int kind = seed_kind(src);   // a colour has three channels; the fused form always reads a table
   if ((Cin & 3) || n < 1 || n > 65535 || kind == SEED_IMM || (kind == SEED_COLOUR && Cout > 3)) return hipErrorInvalidValue;
   if (kind == SEED_PHOTO && !seed_photo_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
+  if (kind == SEED_CLONE && !seed_clone_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
   const dim3 grid((H * W * (Cin >> 2) + 255) / 256, n);
-  if (kind == SEED_PHOTO)
+  if (kind == SEED_CLONE)
+    hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_CLONE>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H, W,
+                       Cin, Cout, act);
+  else if (kind == SEED_PHOTO)
     hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_PHOTO>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H, W,
                        Cin, Cout, act);
   else if (kind == SEED_RGB)

@@ -48,7 +48,7 @@ EXPORTS = (
     "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
-    "ian_session_fit", "ian_session_stroke",
+    "ian_session_fit", "ian_session_stroke", "ian_session_clone",
     "ian_session_record_info", "ian_session_save", "ian_session_load",
     "ian_sessions_reserve_canvas", "ian_canvas_put", "ian_canvas_place", "ian_canvas_compose", "ian_canvas_brush", "ian_canvas_commit",
     "ian_canvas_read", "ian_canvas_placements",
@@ -130,6 +130,7 @@ def load_library():
     lib.ian_session_history.argtypes = [vp, i32, fp]
     lib.ian_session_fit.argtypes = [vp, i32, C.POINTER(SessionFitItem), i32, C.c_float, fp, fp, vp]
     lib.ian_session_stroke.argtypes = [vp, i32, C.POINTER(SessionStroke), i32, C.POINTER(StrokeBox), i32, fp, vp]
+    lib.ian_session_clone.argtypes = [vp, i32, C.POINTER(SessionCloneEvent), i32, fp, vp]
     lib.ian_session_record_info.argtypes = [vp, C.POINTER(SessionMeta), fp, fp]
     lib.ian_session_save.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_load.argtypes = [vp, i32, fp, fp, fp, vp]
@@ -210,6 +211,16 @@ class SessionStroke(C.Structure):
     and the mode, coefficient and colour of every point."""
     _fields_ = [("session", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("mode", C.c_int32), ("coef", C.c_float),
                 ("rgb", C.c_float * 3)]
+
+
+CLONE_MAX_STEPS = 64         # IAN_CLONE_MAX_STEPS (include/ian.h)
+
+
+class SessionCloneEvent(C.Structure):
+    """ian_session_clone_event (include/ian.h): one clone event of ian_session_clone: the destination's rectangle is pulled towards the
+    rectangle shifted by (dc, dr) of the source session's GIM, IM or RECON (field = SESSION_FIELDS[...])."""
+    _fields_ = [("session", C.c_int32), ("c1", C.c_int32), ("r1", C.c_int32), ("c2", C.c_int32), ("r2", C.c_int32), ("source", C.c_int32),
+                ("field", C.c_int32), ("dc", C.c_int32), ("dr", C.c_int32), ("coef", C.c_float), ("gscale", C.c_float)]
 
 
 class CanvasPlacement(C.Structure):
@@ -468,6 +479,12 @@ class Handle:
         flags bit 0 = mark first, shown u8[n,3,64,64] or None."""
         self._check(self.lib.ian_session_stroke(self._h, len(strokes), strokes, len(boxes), boxes, int(flags),
                                                 _ptr(shown) if shown is not None else C.c_void_p(0), C.c_void_p(stream or 0)))
+
+    def session_clone(self, events, steps=1, shown=None, stream=None):
+        """ian_session_clone; events = a ctypes array of SessionCloneEvent (n = its length), steps 1..CLONE_MAX_STEPS, shown
+        u8[n,3,64,64] or None."""
+        self._check(self.lib.ian_session_clone(self._h, len(events), events, int(steps), _ptr(shown) if shown is not None else C.c_void_p(0),
+                                               C.c_void_p(stream or 0)))
 
     def session_record_info(self):
         """ian_session_record_info -> (the pool's layout as a SessionMeta, the byte offsets of its arrays in a body); host only."""

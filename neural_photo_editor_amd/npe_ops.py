@@ -350,6 +350,27 @@ def stroke_footprint(U, boxes, t):
     return U
 
 
+def clone_target(picture_u8, box, offset=(0, 0)):
+    """The target image of one clone event (ian_session_clone) as a stateless call would be given it -> float32 (3,64,64):
+    T[:, r, c] = np.asarray(to_tanh(picture[:, r + dr, c + dc]), dtype=np.float32) for (r, c) inside box = (c1, r1, c2, r2), zero
+    elsewhere (the loss never reads there); offset = (dc, dr).  picture_u8 is the source session's GIM, IM or RECON, uint8 (3,64,64).
+    An empty rectangle gives all zeros; a non-empty one must lie inside the image, and so must its shifted copy."""
+    p = np.asarray(picture_u8)
+    if p.dtype != np.uint8 or p.shape != (3, 64, 64):
+        raise ValueError("a source picture is uint8 (3,64,64), got %s %s" % (p.dtype, p.shape))
+    c1, r1, c2, r2 = [int(v) for v in box]
+    dc, dr = [int(v) for v in offset]
+    T = np.zeros((3, 64, 64), np.float32)
+    if c2 <= c1 or r2 <= r1:
+        return T
+    if c1 < 0 or r1 < 0 or c2 > 64 or r2 > 64:
+        raise ValueError("patch (%d,%d,%d,%d) outside the 64x64 image" % (c1, r1, c2, r2))
+    if c1 + dc < 0 or c2 + dc > 64 or r1 + dr < 0 or r2 + dr > 64:
+        raise ValueError("patch (%d,%d,%d,%d) shifted by (%d,%d) leaves the 64x64 image" % (c1, r1, c2, r2, dc, dr))
+    T[:, r1:r2, c1:c2] = np.asarray(to_tanh(p[:, r1 + dr:r2 + dr, c1 + dc:c2 + dc]), dtype=np.float32)   # float64, one rounding: NPE.py:257
+    return T
+
+
 def photo_blend_local(xhat, recon_uint8, error, U=None, half=None, dampen=False, thresh=DAMPEN_THRESH):
     """photo_blend_host with the user mask and / or dampen -> (IM uint8, MASK_L float64, FIELD float32).
       MASK    exactly photo_blend_host's (half = gaussian_half_kernel(...): the same filter through separable_reflect_filter, which
