@@ -290,10 +290,8 @@ int run_head_fused(ian_handle* h, int n, hipStream_t st) {
   a.H = H; a.W = W; a.xs = src.cs; a.ntaps = (int)R.fwd.taps.size(); a.halo = P.halo;
   a.w_tap_stride = (long long)R.fwd.CoutPad * R.fwd.Cin;
   // bands: whole images per workgroup when the batch alone fills the chip (no halo rows recomputed); smaller batches
-  // are cut into row bands so that at least ~256 workgroups exist (each band re-reads 2*halo rows)
-  int bands = 1;
-  while (n * bands < 256 && bands < 8 && (H % (bands * 2)) == 0 && H / (bands * 2) >= 2 * P.halo) bands *= 2;
-  a.bands = bands;
+  // are cut into row bands so that at least head_wgs (256) workgroups exist (each band re-reads 2*halo rows)
+  a.bands = row_bands(n, h->opt.head_wgs, H, 1, 2 * P.halo);
   HIPCHK(h, launch_head6(a, n, st));
   HeadTailArgs t;
   memset(&t, 0, sizeof t);
@@ -372,9 +370,7 @@ int run_op_fwd(ian_handle* h, OpPlan& op, int n, hipStream_t st) {
         DeconvSmallArgs a;
         a.x = src.d; a.w = op.d_edge_w; a.scale = op.d_scale; a.shift = op.d_shift; a.y = dst.d;
         a.H = op.d.in_h; a.W = op.d.in_w; a.xs = src.cs; a.act = op.d.act;
-        int bands = 1;
-        while (n * bands < h->opt.dec_out_wgs && bands < 8 && (op.d.in_h % (4 * bands)) == 0) bands *= 2;   // one halo row per side of a band
-        a.bands = bands;
+        a.bands = row_bands(n, h->opt.dec_out_wgs, op.d.in_h, 2, 0);   // whole row pairs; one halo row per side of a band
         a.balanced = h->opt.dec_out_bal;
         HIPCHK(h, launch_deconv_small(a, n, op.d.cout, st));
         h->pin_img_valid = false;

@@ -568,9 +568,7 @@ int ian_layer_head6_forward(ian_layer* l0, ian_layer* l1, ian_layer* l2, const f
   a.x = x; a.w0 = l0->op.fwd.d_w; a.w1 = l1->op.fwd.d_w; a.w2 = l2->op.fwd.d_w; a.out = P.d_comp; a.itab = P.d_itab; a.ftab = P.d_ftab;
   a.H = H; a.W = W; a.xs = L.Cin; a.ntaps = (int)L.taps.size(); a.halo = P.halo;
   a.w_tap_stride = (long long)L.CoutPad * L.Cin;
-  int bands = 1;
-  while (n * bands < 256 && bands < 8 && (H % (bands * 2)) == 0 && H / (bands * 2) >= 2 * P.halo) bands *= 2;
-  a.bands = bands;
+  a.bands = row_bands(n, h->opt.head_wgs, H, 1, 2 * P.halo);   // as run_head_fused (ian_rt_exec.inc)
   LHIP(l0, launch_head6(a, n, st));
   LHIP(l0, launch_head6_scatter(P.d_comp, y0, y1, y2, y_stride, (long long)n * H * W, st));
   return 0;

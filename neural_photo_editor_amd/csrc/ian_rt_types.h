@@ -162,7 +162,8 @@ struct Options {
   int b1_conv = 0;                   // batch-1 transposed convs and their backward-data as whole-contraction streaming launches
                                      // (kernels_b1.hip).  OFF: measured slower than tapgemm + reduce (brush event 0.178 vs 0.160 ms):
                                      // 16-pixel tiles re-read weights and input rows from L2 at 4 FLOP/B
-  int dec_out_wgs = 256;             // image-producing deconv: split images into row bands until this many workgroups exist
+  int dec_out_wgs = 256;             // image-producing deconv: split images into row bands until this many workgroups exist (ian_row_bands.h)
+  int head_wgs = 256;                // RGB-Beta head (head6_kernel, inference and ian_layer_head6_forward): the same, 1 / 2 / 4 / 8 bands per image
   int alias_io = 1;                  // ian_reconstruct: device-pointer images are read / written in place (no boundary copies)
   int dense_gemv = 1;                // batch-1 backward of the dense layer fed by the latent as one GEMV launch
   int dec_out_px = 1;                // ... and, below that batch, 8 lanes per output pixel instead of 16 tile workgroups

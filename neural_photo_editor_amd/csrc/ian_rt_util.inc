@@ -66,6 +66,7 @@ bool apply_option(Options& o, const std::string& k, int value) {
   }
   else if (k == "alias_io") o.alias_io = value;
   else if (k == "dec_out_wgs") o.dec_out_wgs = std::max(1, value);
+  else if (k == "head_wgs") o.head_wgs = std::max(1, value);
   else if (k == "dec_out_bal") o.dec_out_bal = value;
   else if (k == "mdc_thin_tile") o.mdc_thin_tile = value;
   else if (k == "wg_target_items") o.wg_target_items = value;

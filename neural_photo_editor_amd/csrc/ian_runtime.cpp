@@ -19,6 +19,7 @@
 #include "ian_internal.h"
 #include "ian_guard.h"   // IAN_SANITIZE builds: guard bands around every device allocation (no-op otherwise)
 #include "ian_tg_plan.h"           // the tap-GEMM planner (tiles, per-tile tap lists, K ranges, launch model): plain C++, also compiled on its own by a test
+#include "ian_row_bands.h"         // row bands per image of the image-producing kernels (kernels_head.hip): plain C++, also compiled on its own by a test
 #include "ian_session_history.h"   // the undo history's bookkeeping per edit session: plain C++, also compiled on its own by a test
 #include "ian_session_record.h"    // a saved session's padding rule, meta validation and ring map: plain C++, also compiled on its own by a test
 

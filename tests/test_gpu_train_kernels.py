@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import row_band_cases as RB
+
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5
@@ -574,11 +576,14 @@ def test_layer_autotune_keeps_the_arithmetic(env):
     layer.close()
 
 
-@pytest.mark.parametrize("n", [2, 8])
-def test_head6_forward_equals_three_layer_forwards(env, n):
+@pytest.mark.parametrize("n,head_wgs", [pytest.param(2, 256, id="2"), pytest.param(8, 256, id="8")] +
+                         [pytest.param(RB.TRAIN_HEAD_BATCH, RB.TRAIN_HEAD_WGS[b], id="2-%dband%s" % (b, "s" if b > 1 else "")) for b in (1, 2, 4)])
+def test_head6_forward_equals_three_layer_forwards(env, n, head_wgs, monkeypatch):
     """ian_layer_head6_forward (R, G_a, B_a of IAN.py:183-199 in one pass over the 128-channel map) vs the three separate
-    ian_layer_forward calls and vs float64 torch."""
+    ian_layer_forward calls and vs float64 torch.  head_wgs = 256 (the default) cuts the 64 rows of 2 and of 8 images into 8 bands;
+    1, 4 and 8 give 2 images 1, 2 and 4 bands (pinned on the CPU by tests/test_row_bands_host.py)."""
     lib, T, k = env
+    monkeypatch.setenv("IAN_OPTS", "head_wgs=%d" % head_wgs)   # read when a layer is created
     rs = np.random.RandomState(11 + n)
     sc = [2, 3, 4]
     x = rs.randn(n, 128, 64, 64).astype(np.float32)
