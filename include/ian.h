@@ -321,6 +321,33 @@ int ian_session_render(ian_handle* h, int32_t n, const ian_session_view* views, 
 int ian_session_brush_view(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, const ian_session_view* views,
                            int32_t vw, int32_t vh, uint8_t* out, void* stream);
 
+/* ---- edge-aware render: the edit field guided by the photo (joint bilateral upsampling) ----
+   The plain bilinear tap above lets an edit bleed over every edge of the photo by up to `scale` pixels.  With a guide reserved, each
+   of the four taps is also weighted by how close the photo's pixel is to the tap's pixel of GIM (the photo's own 64x64 box mean),
+   through a table of 766 range weights indexed by the summed absolute byte difference of the three channels.  The table is made
+   on the host (npe_ops.guide_table(sigma): max(float32(exp(-d*d / (2 * (3*sigma)^2))), 2^-24), exponent in float64, sigma in levels
+   per channel); no exp runs on the device.  Kind 1 (FIELD is a sample, there is no photo to guide by) renders as without a guide.
+   Kind 0, per output pixel (Y, X), float32, every operation rounded on its own:
+     (r0, r1, ty), (c0, c1, tx) = the taps of ian_session_render;  tap k = 0..3 is (r0,c0), (r0,c1), (r1,c0), (r1,c1);
+     s_k = wy * wx, wy in {1.0f - ty, ty}, wx in {1.0f - tx, tx};
+     d_k = sum over c of |int(SRC[c,Y,X]) - int(GIM[c,r_k,c_k])|;   w_k = s_k * table[d_k]   (the same four weights for all channels);
+     den = ((w0 + w1) + w2) + w3;   num_c = ((w0*f0 + w1*f1) + w2*f2) + w3*f3, f_k = FIELD[c,r_k,c_k];   v = num_c / den (one division);
+     out = uint8(clip(rint(float32(SRC[c,Y,X]) + 127.5f * v), 0, 255)).
+   A zero field gives num = 0: the source bytes.  The arithmetic is npe_ops.hires_render_guided; the device matches it bit for bit.
+
+   count == 766: table (host, f32[766], every entry finite and > 0) goes to a device buffer the pool owns and the guide is on; again:
+   the table is replaced.  count == 0 (table ignored): the buffer is freed and the guide is off.  While it is on, ian_session_render,
+   ian_session_brush_view and the whole-picture render of ian_session_open(source = 1) launch the guided kernel in place of the
+   bilinear one, with the same checks, copies and synchronisation; without it every call enqueues what it always did.  The table is a
+   setting of the pool, not session state: ian_session_save / _load, records and history do not know it.  Synchronises the device.
+   ian_sessions_reserve_hires(0) frees the guide with its group; a new scale keeps it.
+   -6: no full-resolution reservation, or canvases are reserved (ian_canvas_compose shares the bilinear tap and promises
+   ian_session_render's bytes; ian_sessions_reserve_canvas returns -6 while a guide is reserved).  -7: any other count, a null
+   table, an entry that is not finite or is <= 0. */
+int ian_sessions_reserve_guide(ian_handle* h, const float* table, int32_t count);
+/* 1 with a guide (its table -> table_out, host f32[766], or NULL), 0 without one; -6 without a full-resolution reservation. */
+int ian_sessions_guide(ian_handle* h, float* table_out);
+
 /* ---- local edits: the edit stays where the user painted ----
    NPE.paint's MASK comes from |DELTA| anywhere in the picture, so a stroke on the hair can change the mouth.  The reference left three
    tools for that: USER_MASK ("currently not implemented", NPE.py:58-59, :221), the brush falloff gk (NPE.py:167-175) and dampen

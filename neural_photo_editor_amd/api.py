@@ -588,6 +588,7 @@ class EditSessions:
     Photos larger than 64x64 (no counterpart in NPE.py): reserve_hires(scale) keeps every session's photo at 64*scale pixels a side;
         open_hires  infer from the full-size photo     render  windows of the edited picture at full size
         brush_view / paint(view=) / scroll(view=)      the event and its window in one submission
+        reserve_guide(sigma) / guide()                 edge-aware render: the edit stops at the photo's edges (joint bilateral upsampling)
     Local edits (NPE.py's unimplemented USER_MASK, gk and dampen): reserve_local() keeps a user mask per session;
         set_local(ids, local, dampen)  from then on a paint on those sessions changes the photo only around the strokes made since
     Undo (no counterpart in NPE.py): reserve_history(depth) keeps a ring of saved latents (and user masks) per session on the device;
@@ -612,6 +613,7 @@ class EditSessions:
         self._zdim = zdim
         self.capacity = 0
         self.scale = 0                  # full-resolution reservation: photos are (3, 64*scale, 64*scale); 0 = none
+        self.guided = False             # guide reservation: the full-resolution render weights the field's taps by the photo
         self.local = False              # local reservation: UMASK and the LOCAL flags per session
         self.history_depth = 0          # history reservation: how many marks a session can undo; 0 = none
         self._opened = set()
@@ -647,6 +649,43 @@ class EditSessions:
         if scale != self.scale:
             self._sourced = set()
         self.scale = scale
+        if not scale:
+            self.guided = False
+
+    def reserve_guide(self, sigma=None, table=None):
+        """Edge-aware render: from now on render, brush_view / paint(view=) and commit weight the edit field's four bilinear taps by
+        how close the photo's pixel is to each tap's pixel of the 64x64 picture (joint bilateral upsampling), so an edit no longer
+        bleeds over the photo's edges.  Exactly one of sigma (levels per channel; the table is npe_ops.guide_table(sigma)) and table
+        (766 positive float32 weights by summed absolute byte difference); neither switches the guide off again.  Needs reserve_hires
+        first, and no canvases: compose renders with the plain bilinear tap."""
+        from . import npe_ops
+        if sigma is not None and table is not None:
+            raise ValueError("give sigma or table, not both")
+        if sigma is None and table is None:
+            if self.scale:
+                self._h.sessions_reserve_guide(None)
+            self.guided = False
+            return
+        if not self.scale:
+            raise ValueError("the pool has no full-resolution reservation (reserve_hires)")
+        if self.canvases:
+            raise ValueError("canvases are reserved: free them first (reserve_canvases(0))")
+        if sigma is not None:
+            table = npe_ops.guide_table(sigma)
+        else:
+            table = np.ascontiguousarray(np.asarray(table), np.float32)
+            if table.shape != (npe_ops.GUIDE_TABLE_LEN,):
+                raise ValueError("a guide table has %d entries, got shape %s" % (npe_ops.GUIDE_TABLE_LEN, table.shape))
+            if not (np.isfinite(table).all() and (table > 0).all()):
+                raise ValueError("every entry of a guide table is a finite positive weight")
+        self._h.sessions_reserve_guide(table)
+        self.guided = True
+
+    def guide(self):
+        """-> the float32 (766,) table of the reserved guide, from the library, or None without one."""
+        if not self.scale:
+            return None
+        return self._h.sessions_guide()
 
     def reserve_local(self, on=True, sigma=0.3, dampen_thresh=0.75):
         """Keep a user mask (UMASK float64 (64,64)) and the LOCAL flags per session, 32 772 bytes each, and set the brush footprint's
@@ -856,6 +895,8 @@ class EditSessions:
         if count:
             if not self.scale:
                 raise ValueError("the pool has no full-resolution reservation (reserve_hires)")
+            if self.guided:
+                raise ValueError("a guide is reserved: free it first (reserve_guide())")
             if not (64 <= max_w <= 8192 and 64 <= max_h <= 8192):
                 raise ValueError("max_w and max_h must be in 64..8192, got %d x %d" % (max_w, max_h))
             if max_w % 4:

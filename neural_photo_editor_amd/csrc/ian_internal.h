@@ -475,6 +475,11 @@ hipError_t launch_session_hires_open(const unsigned char* photos, const SessionP
 // npe_ops.hires_render of n windows: views = device int[n][3] (session, x, y), every window vw x vh with x and vw multiples of 4.
 // out u8 [n][3][vh][vw]; out == nullptr: the whole picture (vw = vh = S, x = y = 0) written over the session's own SRC row
 hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s);
+// npe_ops.hires_render_guided of the same windows (ian_sessions_reserve_guide): table = device float[766], the range
+// weights by summed absolute byte difference; the guide of a session is its own GIM.  views, out and out == nullptr as above.
+constexpr int SESSION_GUIDE_TABLE_LEN = 3 * 255 + 1;
+hipError_t launch_session_render_guided(const SessionPool& P, const float* table, const int* views, int vw, int vh, unsigned char* out, int n,
+                                        hipStream_t s);
 // canvases (ian_sessions_reserve_canvas): whole photos in device memory and, per canvas, the table of the sessions
 // placed on it.  Beside the pool for SessionRings' reason; only the two canvas kernels take it.  All nullptr / 0 without the reservation.
 constexpr int CANVAS_MAX_PLACED = 8;

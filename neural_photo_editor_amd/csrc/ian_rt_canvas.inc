@@ -106,6 +106,8 @@ int sessions_reserve_canvas(ian_handle* h, int count, int max_w, int max_h, int 
   auto& S = h->sess;
   if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
   if (count < 0 || count > CANVAS_MAX_COUNT) return fail(h, -7, "%s: count %d outside 0..%d", fn, count, CANVAS_MAX_COUNT);
+  if (count > 0 && S.d_guide)   // the compose shares the plain bilinear tap and promises ian_session_render's bytes
+    return fail(h, -6, "%s: a guide is reserved: free it first (ian_sessions_reserve_guide(NULL, 0))", fn);
   if (count > 0) {
     if (max_w < CANVAS_MIN_SIDE || max_w > CANVAS_MAX_SIDE || max_h < CANVAS_MIN_SIDE || max_h > CANVAS_MAX_SIDE)
       return fail(h, -7, "%s: %d x %d: both sizes must be in %d..%d", fn, max_w, max_h, CANVAS_MIN_SIDE, CANVAS_MAX_SIDE);

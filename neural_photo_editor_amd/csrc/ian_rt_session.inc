@@ -73,6 +73,7 @@ const SessScratchBuf SESS_SCRATCH[] = {
     {offsetof(SessionScratch, d_tanh), 256 * sizeof(float), SESS_BASE},   // last of its group: a failed build never leaves it without its upload
     {offsetof(SessionScratch, d_views), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HIRES},
     {offsetof(SessionScratch, d_out), 0, SESS_HIRES},
+    {offsetof(SessionScratch, d_guide), 0, SESS_HIRES},   // by ian_sessions_reserve_guide; goes with its group
     {offsetof(SessionScratch, d_falloff), 64 * sizeof(double), SESS_LOCAL},
     {offsetof(SessionScratch, d_ltab), (size_t)BATCH_MAX * 2 * sizeof(int32_t), SESS_LOCAL},
     {offsetof(SessionScratch, d_htab), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HISTORY},
@@ -325,6 +326,60 @@ int sessions_reserve_hires(ian_handle* h, int scale) {
   return 0;
 }
 
+// The guide is a setting of the pool, not session state: one device table beside the pool (S.d_guide, freed with the hires group), and
+// while it exists session_render_enqueue launches the guided kernel.  Records, history and ian_session_read know nothing of it.
+int sessions_reserve_guide(ian_handle* h, const float* table, int count) {
+  const char* fn = "ian_sessions_reserve_guide";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
+  if (S.canv.pix)   // canvas_compose_kernel promises ian_session_render's bytes with the plain bilinear tap
+    return fail(h, -6, "%s: canvases are reserved: free them first (ian_sessions_reserve_canvas(0))", fn);
+  if (count != 0 && count != SESSION_GUIDE_TABLE_LEN) return fail(h, -7, "%s: count %d (0 frees, %d sets the table)", fn, count, SESSION_GUIDE_TABLE_LEN);
+  if (count) {
+    if (!table) return fail(h, -7, "%s: null table", fn);
+    if (is_device_ptr(table)) return fail(h, -7, "%s: the table must be a host array", fn);
+    for (int d = 0; d < count; ++d)
+      if (!std::isfinite(table[d]) || !(table[d] > 0.0f)) return fail(h, -7, "%s: table[%d] = %g is not a finite positive weight", fn, d, (double)table[d]);
+  }
+  HIPCHK(h, hipDeviceSynchronize());   // pending work may still read the table that is replaced or freed
+  h->last_pending = false;
+  if (!count) {
+    if (S.d_guide) (void)hipFree(S.d_guide);
+    S.d_guide = nullptr;
+    return 0;
+  }
+  float* d = S.d_guide;
+  if (!d) {
+    hipError_t e = hipMalloc((void**)&d, SESSION_GUIDE_TABLE_LEN * sizeof(float));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(h, -2, "%s: %s for the table of %zu bytes", fn, hipGetErrorString(e), SESSION_GUIDE_TABLE_LEN * sizeof(float));
+    }
+  }
+  hipError_t e = hipMemcpy(d, table, SESSION_GUIDE_TABLE_LEN * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {   // a new buffer goes; an old one keeps the guide it had or has half of the new one: the error is fatal either way
+    if (!S.d_guide) (void)hipFree(d);
+    HIPCHK(h, e);
+  }
+  S.d_guide = d;
+  return 0;
+}
+int sessions_guide(ian_handle* h, float* table_out) {
+  const char* fn = "ian_sessions_guide";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
+  if (!S.d_guide) return 0;
+  if (table_out) {
+    if (is_device_ptr(table_out)) return fail(h, -7, "%s: table_out must be a host array", fn);
+    HIPCHK(h, hipMemcpy(table_out, S.d_guide, SESSION_GUIDE_TABLE_LEN * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return 1;
+}
+
 int sessions_set_blend(ian_handle* h, const double* gauss_half, int radius) {
   if (!h) return -1;
   if (!gauss_half) return fail(h, -1, "null pointer passed to ian_sessions_set_blend");
@@ -554,7 +609,10 @@ int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, 
   S.views_shadow.resize((size_t)3 * n);
   memcpy(S.views_shadow.data(), views, (size_t)n * sizeof(ian_session_view));
   HIPCHK(h, hipMemcpyAsync(S.d_views, S.views_shadow.data(), (size_t)n * sizeof(ian_session_view), hipMemcpyHostToDevice, st));
-  HIPCHK(h, launch_session_render(S.arr.pool, S.d_views, vw, vh, d_out, n, st));
+  if (S.d_guide)   // ian_sessions_reserve_guide: the same windows, the field's taps weighted by the photo
+    HIPCHK(h, launch_session_render_guided(S.arr.pool, S.d_guide, S.d_views, vw, vh, d_out, n, st));
+  else
+    HIPCHK(h, launch_session_render(S.arr.pool, S.d_views, vw, vh, d_out, n, st));
   return 0;
 }
 
@@ -1364,6 +1422,12 @@ int ian_session_open(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t
 }
 int ian_sessions_reserve_hires(ian_handle* h, int32_t scale) {
   return h ? sessions_reserve_hires(h, scale) : -1;
+}
+int ian_sessions_reserve_guide(ian_handle* h, const float* table, int32_t count) {
+  return h ? sessions_reserve_guide(h, table, count) : -1;
+}
+int ian_sessions_guide(ian_handle* h, float* table_out) {
+  return h ? sessions_guide(h, table_out) : -1;
 }
 int ian_session_open_hires(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t* photos, uint8_t* shown, void* stream) {
   return h ? session_open(h, n, ids, photos, 0, shown, stream, true) : -1;

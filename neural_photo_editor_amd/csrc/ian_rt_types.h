@@ -297,6 +297,7 @@ struct ian_handle {
     unsigned char* d_shown = nullptr;  // staging of the canvas images [256][3*64*64]
     int* d_views = nullptr;            // full-resolution: per call n ian_session_view records
     unsigned char* d_out = nullptr;    // full-resolution: staging of rendered windows for a host `out`, grown on demand (out_cap)
+    float* d_guide = nullptr;          // full-resolution: f32[766], the range weights of ian_sessions_reserve_guide; nullptr = no guide, the plain bilinear render
     double* d_falloff = nullptr;       // local edits: f64[64], the table of ian_sessions_set_local
     int* d_ltab = nullptr;             // local edits: per ian_session_local call [n ids | n flags]
     int* d_htab = nullptr;             // undo history: per ian_session_mark / _undo call [n ids | n save slots | n load slots]

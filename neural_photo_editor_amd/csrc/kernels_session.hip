@@ -11,6 +11,7 @@
 //   session_fit_begin_kernel / _adam_kernel / _loss_kernel  ian_session_fit: IM := GIM, one Adam step on the latent rows, the loss read-out
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
+//   session_render_guided_kernel  the same window with the field's four taps weighted by the photo (ian_sessions_reserve_guide)
 //   canvas_place_kernel        canvases: the exact box mean of a square of a whole photo -> GIM, IM, encoder input (any byte alignment)
 //   canvas_compose_kernel      a window of a whole photo: the canvas plus every placed session's feathered edit field
 //   session_history_save_kernel / _move_kernel  undo history: a session's Z and UMASK rows to and from its ring of saved states
@@ -743,6 +744,111 @@ hipError_t launch_session_render(const SessionPool& P, const int* views, int vw,
     return hipErrorInvalidValue;
   if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(session_render_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, P, views, vw, vh, out);
+  return hipGetLastError();
+}
+
+// guided render (npe_ops.hires_render_guided): the four bilinear taps of the field weighted by how close the photo's
+// pixel is to each tap's pixel of GIM.  grid (bands of GUIDE_BAND output rows, 1, n): the range weights need all three channels of a
+// pixel and are computed once per pixel, so a lane owns 4 consecutive output pixels in ALL THREE channels: three uchar4 loads of SRC,
+// three uchar4 stores.  The band's field rows of the three channels (field_rows / stage_field_rows), the same rows of GIM as bytes
+// and the 766 range weights go to LDS once, 8.8 KB; every tap and every weight reads from there.  The weights were computed on the
+// host (no exp here); all arithmetic is float32 with contraction off, in hires_render_guided's order, and the division is IEEE.
+// A kind-1 session (its field is a sample, there is no photo to guide by) takes session_render_kernel's arithmetic; the kind is
+// uniform over the workgroup, and a call may mix kinds.
+// Band height: with the channel planes gone from the grid, ONE whole 1024 x 1024 picture is 128 workgroups at 8 rows and 256 at 4,
+// against 256 CUs.  Both were measured in one run on an MI355X: that picture takes 16.1 us at 4 rows and 24.7 us
+// at 8 (the bilinear kernel: 15.7), sixteen of them 86.6 against 89.5 us, a 256 x 256 window 9.3 against 12.4 us.  So GUIDE_BAND = 4:
+// it fills every CU for one picture, and the staging per workgroup (at most 6 field rows of 3 channels, 5.8 KB, and the 3 KB table)
+// for half as many output rows does not show.
+// out == nullptr: the whole picture over the session's own SRC rows (commit).  A lane loads all three channels of its 4 pixels
+// before it stores any of them, no lane reads another lane's pixels of SRC, and FIELD, GIM and the table live elsewhere: safe in
+// place, as in session_render_kernel; SRC and out are therefore not __restrict__.
+constexpr int GUIDE_BAND = 4;
+static_assert(GUIDE_BAND >= 1 && GUIDE_BAND <= RENDER_BAND, "field_rows stages at most RENDER_BAND + 2 rows");
+__global__ __launch_bounds__(256) void session_render_guided_kernel(SessionPool P, const float* __restrict__ table,
+                                                                    const int* __restrict__ views, int vw, int vh, unsigned char* out) {
+  __shared__ float f[3][(GUIDE_BAND + 2) * 64];
+  __shared__ __align__(4) unsigned char g[3][(GUIDE_BAND + 2) * 64];
+  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
+  const int s = P.scale, S = 64 * s;
+  const int i = blockIdx.z;
+  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
+  const int y0 = blockIdx.x * GUIDE_BAND, rows = min(GUIDE_BAND, vh - y0);
+  const FieldRows fr = field_rows(vy + y0, vy + y0 + rows - 1, s);   // at most ceil((GUIDE_BAND - 1) / s) + 2 <= GUIDE_BAND + 2 rows
+  for (int c = 0; c < 3; ++c) {
+    stage_field_rows(f[c], P.field + ((size_t)id * 3 + c) * (64 * 64), fr);
+    const unsigned* grow = reinterpret_cast<const unsigned*>(P.gim + ((size_t)id * 3 + c) * (64 * 64) + fr.fr0 * 64);
+    unsigned* gl = reinterpret_cast<unsigned*>(g[c]);
+    for (int j = threadIdx.x; j < fr.n * 16; j += 256) gl[j] = grow[j];
+  }
+  for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
+  __syncthreads();
+  const int kind = P.kind[id];
+  const size_t plane = (size_t)S * S, dplane = out ? (size_t)vh * vw : plane;
+  const unsigned char* src = P.src + (size_t)id * 3 * plane;
+  unsigned char* dst = out ? out + (size_t)i * 3 * dplane : P.src + (size_t)id * 3 * plane;
+  const int dstride = out ? vw : S;
+  const int L = vw >> 2;
+  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
+    const int ry = idx / L, cx = (idx - ry * L) * 4;
+    const int Y = vy + y0 + ry, X = vx + cx;
+    int r0, r1;
+    float ty;
+    hires_taps(Y, s, r0, r1, ty);
+    const int o0 = (r0 - fr.fr0) * 64, o1 = (r1 - fr.fr0) * 64;
+    unsigned char pb[3][4] = {}, ob[3][4];
+    if (kind == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * plane + (size_t)Y * S + X);
+        pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (kind == 0) {
+        int c0, c1;
+        float tx;
+        hires_taps(X + e, s, c0, c1, tx);
+        const float wy0 = 1.0f - ty, wx0 = 1.0f - tx;
+        const int at[4] = {o0 + c0, o0 + c1, o1 + c0, o1 + c1};
+        const float sw[4] = {wy0 * wx0, wy0 * tx, ty * wx0, ty * tx};
+        float w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int d = abs((int)pb[0][e] - (int)g[0][at[k]]) + abs((int)pb[1][e] - (int)g[1][at[k]]) + abs((int)pb[2][e] - (int)g[2][at[k]]);
+          w[k] = sw[k] * tab[d];
+        }
+        const float den = ((w[0] + w[1]) + w[2]) + w[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float num = ((w[0] * f[c][at[0]] + w[1] * f[c][at[1]]) + w[2] * f[c][at[2]]) + w[3] * f[c][at[3]];
+          const float v = num / den;
+          ob[c][e] = round_u8((float)pb[c][e] + 127.5f * v);
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float v = field_bilinear(f[c] + o0, f[c] + o1, s, X + e, ty);
+          ob[c][e] = round_u8(127.5f * (v + 1.0f));
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<uchar4*>(dst + c * dplane + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) =
+          make_uchar4(ob[c][0], ob[c][1], ob[c][2], ob[c][3]);
+  }
+}
+hipError_t launch_session_render_guided(const SessionPool& P, const float* table, const int* views, int vw, int vh, unsigned char* out, int n,
+                                        hipStream_t s) {
+  const int S = 64 * P.scale;
+  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src || !P.gim || !P.field || !P.kind || !table || !views || vw < 4 || (vw & 3) ||
+      vh < 1 || vw > S || vh > S)
+    return hipErrorInvalidValue;
+  if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_render_guided_kernel, dim3((vh + GUIDE_BAND - 1) / GUIDE_BAND, 1, n), dim3(256), 0, s, P, table, views, vw, vh,
+                     out);
   return hipGetLastError();
 }
 

@@ -46,6 +46,7 @@ EXPORTS = (
     "ian_brush_step", "ian_grad_batch", "ian_brush_step_batch",
     "ian_sessions_reserve", "ian_sessions_set_blend", "ian_session_open", "ian_session_set_latent", "ian_session_brush", "ian_session_read",
     "ian_sessions_reserve_hires", "ian_session_open_hires", "ian_session_render", "ian_session_brush_view",
+    "ian_sessions_reserve_guide", "ian_sessions_guide",
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
     "ian_session_fit", "ian_session_stroke", "ian_session_clone",
@@ -121,6 +122,8 @@ def load_library():
     lib.ian_session_open_hires.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_render.argtypes = [vp, i32, C.POINTER(SessionView), i32, i32, fp, vp]
     lib.ian_session_brush_view.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, C.POINTER(SessionView), i32, i32, fp, vp]
+    lib.ian_sessions_reserve_guide.argtypes = [vp, fp, i32]
+    lib.ian_sessions_guide.argtypes = [vp, fp]
     lib.ian_sessions_reserve_local.argtypes = [vp, i32]
     lib.ian_sessions_set_local.argtypes = [vp, fp, C.c_double]
     lib.ian_session_local.argtypes = [vp, i32, fp, fp, vp]
@@ -422,6 +425,24 @@ class Handle:
         """ian_session_brush_view; events / views = ctypes arrays of SessionEvent / SessionView of the same length."""
         self._check(self.lib.ian_session_brush_view(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
                                                     views, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def sessions_reserve_guide(self, table=None):
+        """ian_sessions_reserve_guide; table = 766 float32 range weights (npe_ops.guide_table), or None to switch the guide off."""
+        if table is None:
+            self._check(self.lib.ian_sessions_reserve_guide(self._h, C.c_void_p(0), 0))
+            return
+        t = np.ascontiguousarray(table, np.float32)
+        if t.ndim != 1:
+            raise ValueError("the guide table is one-dimensional, got shape %s" % (t.shape,))
+        self._check(self.lib.ian_sessions_reserve_guide(self._h, _ptr(t), t.shape[0]))
+
+    def sessions_guide(self):
+        """ian_sessions_guide -> the float32[766] table of the reserved guide, or None without one."""
+        t = np.empty(766, np.float32)
+        rc = self.lib.ian_sessions_guide(self._h, _ptr(t))
+        if rc < 0:
+            self._check(rc)
+        return t if rc == 1 else None
 
     def sessions_reserve_local(self, on=True):
         self._check(self.lib.ian_sessions_reserve_local(self._h, int(bool(on))))

@@ -195,6 +195,74 @@ def hires_render(src, field, kind, s, vx, vy, vw, vh):
     return np.uint8(np.clip(np.rint(q), 0, 255))
 
 
+# ---- edge-aware render (ian_sessions_reserve_guide, include/ian.h) -----------------------------------------------------
+# Joint bilateral upsampling of the edit field: each of the four bilinear taps is weighted by how close the photo's pixel is to the
+# tap's pixel of GIM, the photo's own 64x64 box mean.  These two functions ARE the specification, as hires_* are.
+GUIDE_TABLE_LEN = 3 * 255 + 1
+GUIDE_FLOOR = np.float32(2.0 ** -24)
+
+
+def guide_table(sigma):
+    """The range weights of the guided render -> float32 (766,): entry d, the sum over the three channels of the absolute byte
+    differences, is max(float32(exp(-d^2 / (2 * (3*sigma)^2))), 2^-24) with the exponent in float64; sigma in levels per channel.
+    The floor keeps every denominator of hires_render_guided positive and normal."""
+    sigma = float(sigma)
+    if not np.isfinite(sigma) or sigma <= 0:
+        raise ValueError("sigma must be a positive number of levels, got %r" % (sigma,))
+    d = np.arange(GUIDE_TABLE_LEN, dtype=np.float64)
+    return np.maximum(np.float32(np.exp(-(d ** 2) / (2.0 * (3.0 * sigma) ** 2))), GUIDE_FLOOR)
+
+
+def hires_guide_field(src, gim, field, s, vx, vy, vw, vh, table):
+    """The guided sample v of the field over window (vx, vy, vw, vh) -> float32 (3, vh, vw): hires_render_guided's kind 0 up to and
+    including the division."""
+    s = _hires_scale(s)
+    S = 64 * s
+    vx, vy, vw, vh = int(vx), int(vy), int(vw), int(vh)
+    if vw < 1 or vh < 1 or vx < 0 or vy < 0 or vx + vw > S or vy + vh > S:
+        raise ValueError("window (%d,%d) + %d x %d outside the %d x %d picture" % (vx, vy, vw, vh, S, S))
+    table = np.asarray(table)
+    if table.dtype != np.float32 or table.shape != (GUIDE_TABLE_LEN,):
+        raise ValueError("a guide table is float32 (%d,), got %s %s" % (GUIDE_TABLE_LEN, table.dtype, table.shape))
+    F = np.asarray(field, np.float32)
+    P = np.int32(np.asarray(src)[:, vy:vy + vh, vx:vx + vw])
+    G = np.int32(np.asarray(gim))
+    c0, c1, tx = hires_axis_taps(s, vx, vw)
+    r0, r1, ty = hires_axis_taps(s, vy, vh)
+    one = np.float32(1.0)
+    den = num = None
+    for rr, wy in ((r0, one - ty), (r1, ty)):
+        for cc, wx in ((c0, one - tx), (c1, tx)):
+            d = np.abs(P - G[:, rr][:, :, cc]).sum(axis=0)                 # (vh, vw), 0..765
+            w = (wy[:, None] * wx[None, :]) * table[d]
+            t = w[None] * F[:, rr][:, :, cc]
+            den, num = (w, t) if den is None else (den + w, num + t)
+    v = num / den[None]
+    assert v.dtype == np.float32
+    return v
+
+
+def hires_render_guided(src, gim, field, kind, s, vx, vy, vw, vh, table):
+    """hires_render with the field's four bilinear taps weighted by the photo (joint bilateral upsampling) -> uint8 (3, vh, vw).
+    gim uint8 (3,64,64) is the session's GIM, table = guide_table(sigma).  kind 1 (the field is a sample, there is no photo to guide
+    by): exactly hires_render.  kind 0, per output pixel (Y, X), float32 throughout, every operation rounded on its own (no fma):
+      (r0, r1, ty), (c0, c1, tx) = hires_axis_taps;  the taps k = 0..3 are (r0,c0), (r0,c1), (r1,c0), (r1,c1);
+      s_k = wy*wx, wy in {1.0f - ty, ty}, wx in {1.0f - tx, tx};   d_k = sum_c |int(src[c,Y,X]) - int(gim[c,r_k,c_k])|;
+      w_k = s_k * table[d_k]  (the same four weights for the three channels);   den = ((w0 + w1) + w2) + w3;
+      num_c = ((w0*f0 + w1*f1) + w2*f2) + w3*f3, f_k = field[c,r_k,c_k];   v = num_c / den  (one division);
+      q = float32(src[c,Y,X]) + 127.5f*v;   out = uint8(clip(rint(q), 0, 255)).
+    A zero field gives num = 0, v = 0: the source bytes."""
+    if kind not in (0, 1):
+        raise ValueError("kind must be 0 (photo plus field) or 1 (plain sample), got %r" % (kind,))
+    if kind == 1:
+        return hires_render(src, field, kind, s, vx, vy, vw, vh)
+    v = hires_guide_field(src, gim, field, s, vx, vy, vw, vh, table)
+    vx, vy, vw, vh = int(vx), int(vy), int(vw), int(vh)
+    q = np.float32(np.asarray(src)[:, vy:vy + vh, vx:vx + vw]) + np.float32(127.5) * v
+    assert q.dtype == np.float32
+    return np.uint8(np.clip(np.rint(q), 0, 255))
+
+
 # ---- canvases (ian_sessions_reserve_canvas / ian_canvas_*, include/ian.h; DESIGN.md 4.7) ----------------------------------------------
 # A canvas is a whole photo, uint8 (3, H, W); a session is placed on it as a square of 64*s pixels a side at pixel offset (ox, oy), each
 # placement with its own scale s.  The reference has no counterpart, so these three functions ARE the specification, as hires_* are:
