@@ -545,6 +545,44 @@ typedef struct ian_session_clone_event {
 } ian_session_clone_event;
 int ian_session_clone(ian_handle* h, int32_t n, const ian_session_clone_event* events, int32_t steps, uint8_t* shown, void* stream);
 
+/* ---- brush tips: a weighted brush loss, for round brushes with a soft edge ----
+   Every brush above weights the pixels of its rectangle alike (1/N).  A tip is a small weight image wn, f32[th][tw] with
+   1 <= tw, th <= 64, and a paint or light event that names a tip takes the tip's weights in the place of the flat 1/N:
+       mode 1:  loss = sum_{co,r,c} wn[r - r1][c - c1] * (x_hat[co,r,c] - rgb[co])^2      seed g = 2.f * (x_hat - rgb[co]) * wn[r - r1][c - c1]
+       mode 0:  loss = sum wn * x_hat                                                       seed g = wn[r - r1][c - c1]
+   and zero outside the rectangle; the three channels share the one weight.  The library takes wn as given (a general weighted loss);
+   how a brush shape becomes weights is the host's policy: npe_ops.tip_weights(w) = float32(w) * (float32(1) / float32(3 * sum w)), for
+   which an all-ones tip IS the rectangle brush, bit for bit, in both modes (wn == 1.f / (float)(3 * th * tw), the rectangle's own 1/N).
+   The event's rectangle lies inside the image as always, and its size is exactly the tip's: c2 - c1 == tw and r2 - r1 == th.
+   Tips belong to the handle, not to a session: they are no part of a saved session, of the undo history, of the guide or of a canvas.
+   Tips weight colour brushes only: ian_session_clone, ian_session_fit, the stateless ian_grad_batch / ian_brush_step_batch and
+   ian_canvas_brush keep the unweighted loss.  Under the local reservation the footprint that goes into UMASK stays that of the
+   rectangle; a footprint shaped by the tip is out of scope.  A pool that never reserves tips launches, moves and computes nothing it
+   did not before. */
+
+/* Room for `count` tips (0..64; 0 frees them; another count frees them and every tip starts unset; the same count changes nothing).
+   Needs the pool (-6 otherwise), synchronises the device.  ian_sessions_reserve(0) and ian_destroy free the tips too. */
+int ian_sessions_reserve_tips(ian_handle* h, int32_t count);
+/* Tip `tip` := wn, host f32[th][tw].  Synchronises the device first, so that no event in flight sees the tip change.  -6 without the
+   tip reservation.  -7, with nothing changed: tip outside the reservation, tw or th outside 1..64, a weight that is negative,
+   infinite or NaN (all zero is allowed and gives a zero gradient), wn in device memory. */
+int ian_sessions_set_tip(ian_handle* h, int32_t tip, int32_t tw, int32_t th, const float* wn);
+/* wh := (tw, th) of tip `tip` and, where wn_out (host f32[th][tw]) is given, its weights.  -7 for a tip never set. */
+int ian_sessions_tip(ian_handle* h, int32_t tip, int32_t wh[2], float* wn_out);
+/* ian_session_brush (views == NULL; vw, vh, out unused) or ian_session_brush_view (views given) with one tip index per event: tips
+   int32[n], host; -1 = no tip, and such an item is today's rectangle event, byte for byte.  Everything else is the plain call's:
+   residency, latent versions, history notes, passes of brush_pass, the blend, shown and the windows.  Host -> device: the event table,
+   12 words per event.  -6 where the plain call returns it, and without the tip reservation.  -7, naming the item, before anything
+   is enqueued: everything the plain call refuses, a tip outside -1..count-1, a tip never set, a rectangle whose size is not the
+   tip's, tips NULL or in device memory. */
+int ian_session_brush_tip(ian_handle* h, int32_t n, const ian_session_event* events, const int32_t* tips, uint8_t* shown,
+                          const ian_session_view* views, int32_t vw, int32_t vh, uint8_t* out, void* stream);
+/* ian_session_stroke with one tip per stroke (tips int32[n], host; -1 = none): every rectangle of stroke i must have the size of tip
+   tips[i].  Its meaning is the loop given for ian_session_stroke with ian_session_brush_tip in the place of ian_session_brush, byte
+   for byte.  Refusals: those of ian_session_stroke and of ian_session_brush_tip, naming the item and the point. */
+int ian_session_path_tip(ian_handle* h, int32_t n, const ian_session_stroke_item* strokes, const int32_t* tips, int32_t nboxes,
+                         const ian_stroke_box* boxes, int32_t flags, uint8_t* shown, void* stream);
+
 /* ---- saving and loading whole sessions: the editor state as bytes that can leave the pool ----
    Everything a session is -- the 64x64 state, the full-resolution source and edit field, the user mask and flags, the ring of undo
    states with its cursor -- lives in one handle's pool.  A record is that state as plain bytes: keep a project beyond the process,

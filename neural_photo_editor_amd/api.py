@@ -214,6 +214,31 @@ def pack_session_strokes(ids, paths, colours=None, modes=None, weight=0.05, sign
     return strokes, boxes, perm
 
 
+def pack_session_tips(tips, boxes, tip_sizes, count=None):
+    """The tips argument of ian_session_brush_tip / ian_session_path_tip -> int32 (n,), refusing on the host what the library would
+    refuse, naming the item.  tips: one integer for all n items or one per item, -1 = no tip; boxes: per item an array (K,4) (or (4,))
+    of the rectangles (c1, r1, c2, r2) it is applied to, n = len(boxes); tip_sizes: {tip: (tw, th)} of the tips that were set; count:
+    the reservation (None: not checked)."""
+    n = len(boxes)
+    a = np.asarray(tips)
+    if a.ndim == 0:
+        a = np.tile(a, n)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("tips must be one integer or %d integers, got %s %s" % (n, a.dtype, a.shape))
+    for i, t in enumerate(int(t) for t in a):
+        if t == -1:
+            continue
+        if t < -1 or (count is not None and t >= count):
+            raise ValueError("item %d: tip %d outside -1..%s" % (i, t, "count-1" if count is None else count - 1))
+        if t not in tip_sizes:
+            raise ValueError("item %d: tip %d has never been set (set_tip)" % (i, t))
+        tw, th = tip_sizes[t]
+        for k, (c1, r1, c2, r2) in enumerate([int(v) for v in r] for r in np.asarray(boxes[i]).reshape(-1, 4)):
+            if c2 - c1 != tw or r2 - r1 != th:
+                raise ValueError("item %d: point %d: patch (%d,%d,%d,%d) is not the %d x %d of tip %d" % (i, k, c1, r1, c2, r2, tw, th, t))
+    return np.ascontiguousarray(a, np.int32)
+
+
 CLONE_FIELDS = ("GIM", "IM", "RECON")       # what a clone event may read of its source
 
 
@@ -605,7 +630,10 @@ class EditSessions:
         brush_compose(..., windows=)       the event and the windows in one submission -> (shown, out)
         canvas_commit(cid)                 the composed photo becomes the canvas, its sessions start again from it -> shown
         canvas_read(cid) / placements(cid) the stored photo / [(session, x, y, scale)]
-    open, open_hires and load un-place a session; commit on a placed session is refused (canvas_commit is its form)."""
+    open, open_hires and load un-place a session; commit on a placed session is refused (canvas_commit is its form).
+    Brush tips (no counterpart in NPE.py, whose brush is a square): reserve_tips(count) keeps weight images of up to 64x64 per handle;
+        set_tip(tip, weights) / tip(tip)   e.g. npe_ops.round_tip(diameter, hardness): a round brush with a soft edge
+        brush / brush_view / paint / scroll / stroke (tips=) and paint_stroke(tip=)   the event's loss weighted by the tip"""
 
     def __init__(self, handle, capacity, zdim, sigma=0.7):
         from . import npe_ops
@@ -623,6 +651,8 @@ class EditSessions:
         self.feather = 0
         self._canvas_wh = []            # per canvas (w, h) of its picture, None before canvas_put
         self._placed = {}               # session id -> (canvas id, x, y, scale)
+        self.tips = 0                   # tip reservation: how many brush tips the handle keeps; 0 = none
+        self._tips = {}                 # tip -> (tw, th) of the tips that were set
         self.reserve(capacity)
         self._h.sessions_set_blend(npe_ops.gaussian_half_kernel(sigma, int(4.0 * float(sigma) + 0.5)))
 
@@ -805,6 +835,51 @@ class EditSessions:
             self._placed.pop(v, None)
             (self._sourced.add if int(m["has_source"]) else self._sourced.discard)(v)
 
+    # ---- brush tips ----
+    def reserve_tips(self, count):
+        """Room for `count` brush tips (0..64; 0 frees them).  Another count drops the tips that were set."""
+        count = int(count)
+        if not 0 <= count <= 64:
+            raise ValueError("count must be in 0..64, got %d" % count)
+        self._h.sessions_reserve_tips(count)
+        if count != self.tips:
+            self._tips = {}
+        self.tips = count
+
+    def _need_tip(self, tip):
+        tip = int(tip)
+        if not self.tips:
+            raise ValueError("the pool has no tip reservation (reserve_tips)")
+        if not 0 <= tip < self.tips:
+            raise ValueError("tip %d outside the reservation (0..%d)" % (tip, self.tips - 1))
+        return tip
+
+    def set_tip(self, tip, weights, normalise=True):
+        """Tip `tip` := weights (th, tw), both sides 1..64, every weight finite and >= 0.  normalise=True: a brush shape, e.g.
+        npe_ops.round_tip(d, hardness), made a weighted mean by npe_ops.tip_weights (an all-ones shape is then the rectangle brush, bit
+        for bit); False: the float32 weights as given (ian_sessions_set_tip's general weighted loss; all zero gives a zero gradient)."""
+        from . import npe_ops
+        tip = self._need_tip(tip)
+        wn = npe_ops.tip_weights(weights) if normalise else np.ascontiguousarray(weights, np.float32)
+        if wn.ndim != 2 or not 1 <= wn.shape[0] <= 64 or not 1 <= wn.shape[1] <= 64:
+            raise ValueError("a tip has shape (th, tw) with both sides 1..64, got %s" % (wn.shape,))
+        if not np.all(np.isfinite(wn)) or np.any(wn < 0):
+            raise ValueError("the weights of a tip are finite and >= 0")
+        self._h.sessions_set_tip(tip, wn)
+        self._tips[tip] = (wn.shape[1], wn.shape[0])
+
+    def tip(self, tip):
+        """-> the float32 (th, tw) weights tip `tip` holds on the device."""
+        tip = self._need_tip(tip)
+        if tip not in self._tips:
+            raise ValueError("tip %d has never been set (set_tip)" % tip)
+        return self._h.sessions_tip(tip)
+
+    def _tipsel(self, tips, boxes):
+        if not self.tips:
+            raise ValueError("the pool has no tip reservation (reserve_tips)")
+        return pack_session_tips(tips, boxes, self._tips, self.tips)
+
     def _ids(self, ids, need_opened):
         return check_session_ids(ids, self.capacity, self._opened if need_opened else None)
 
@@ -858,14 +933,22 @@ class EditSessions:
         self._h.session_render(views, vw, vh, out)
         return out
 
-    def brush_view(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, origins=(0, 0), size=64):
-        """brush, and window i of session ids[i] at full resolution after its event, in ONE submission -> (shown, out)."""
+    def brush_view(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, origins=(0, 0), size=64, tips=None):
+        """brush, and window i of session ids[i] at full resolution after its event, in ONE submission -> (shown, out).  tips: as in
+        brush."""
         ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
         views, vw, vh = self._views(ids, origins, size, ev)
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
         out = np.empty((len(ev), 3, vh, vw), np.uint8)
-        self._h.session_brush_view(ev, views, vw, vh, out, shown)
+        if tips is None:
+            self._h.session_brush_view(ev, views, vw, vh, out, shown)
+        else:
+            self._h.session_brush_tip(ev, self._tipsel(tips, self._event_boxes(ev)), shown, views, vw, vh, out)
         return shown, out
+
+    @staticmethod
+    def _event_boxes(ev):
+        return [[(e.c1, e.r1, e.c2, e.r2)] for e in ev]
 
     # ---- canvases ----
     def _unplace(self, ids):
@@ -1026,11 +1109,15 @@ class EditSessions:
         self._h.session_fit(items, steps, lr, loss, recon)
         return recon, loss
 
-    def brush(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0):
-        """n brush events (pack_session_events) in one submission -> shown."""
+    def brush(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, tips=None):
+        """n brush events (pack_session_events) in one submission -> shown.  tips: one tip index for all events or one per event
+        (-1 = none, the plain rectangle event): the event's loss is weighted by that tip (set_tip), whose size the box must have."""
         ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
-        self._h.session_brush(ev, shown)
+        if tips is None:
+            self._h.session_brush(ev, shown)
+        else:
+            self._h.session_brush_tip(ev, self._tipsel(tips, self._event_boxes(ev)), shown)
         return shown
 
     def clone(self, ids, boxes, sources, offsets=(0, 0), field="GIM", steps=1, weight=0.05, sign=-1.0):
@@ -1050,46 +1137,61 @@ class EditSessions:
         idv = self._ids(ids, True)
         return self.clone(idv, boxes, idv, (0, 0), "GIM", steps, weight, -1.0)
 
-    def stroke(self, ids, paths, colours=None, modes=None, weight=0.05, sign=-1.0, mark=False):
+    def stroke(self, ids, paths, colours=None, modes=None, weight=0.05, sign=-1.0, mark=False, tips=None):
         """Whole brush paths in one submission (ian_session_stroke): paths = one (K_i,4) array of rectangles per session, 1..64 points,
         applied in order with the stroke's one colour / mode / weight / sign (pack_session_strokes).  The sessions end byte for byte
         where the loop `for k: brush(the sessions with more than k points)` leaves them -> shown uint8 (n,3,64,64), in the caller's
         order: what each session's LAST point displays.  mark=True saves the states first, as mark(ids) would, in the same
-        submission: one stroke is one undo step.  For windows call render or compose afterwards."""
+        submission: one stroke is one undo step.  For windows call render or compose afterwards.  tips: one tip index for all strokes
+        or one per stroke, in the caller's order (-1 = none); every rectangle of a stroke must have its tip's size."""
         if mark:
             self._need_history()
         strokes, boxes, perm = pack_session_strokes(ids, paths, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
         got = np.empty((len(strokes), 3, 64, 64), np.uint8)
-        self._h.session_stroke(strokes, boxes, 1 if mark else 0, got)
+        if tips is None:
+            self._h.session_stroke(strokes, boxes, 1 if mark else 0, got)
+        else:
+            sel = self._tipsel(tips, [np.asarray(p).reshape(-1, 4) for p in (list(paths) if not isinstance(paths, list) else paths)])
+            self._h.session_path_tip(strokes, np.ascontiguousarray(sel[perm]), boxes, 1 if mark else 0, got)    # sorted stroke j carries the tip of the caller's item perm[j]
         shown = np.empty_like(got)
         shown[perm] = got                      # sorted stroke j is the caller's item perm[j]
         return shown
 
-    def paint_stroke(self, ids, points, colours_uint8, d=12, weight=0.05, mark=True):
+    def paint_stroke(self, ids, points, colours_uint8, d=12, weight=0.05, mark=True, tip=None):
         """A drag of NPE.paint per session: points = one (K_i,2) array of (x, y) mouse positions in 64-pixel space per session (NPE.py:148
         has event.x//4), d = the brush-size slider (npe_ops.brush_rect gives each point move_mouse's rectangle), painted toward
-        colours_uint8 (levels 0..255) -> shown, as stroke."""
+        colours_uint8 (levels 0..255) -> shown, as stroke.  tip: paint with that brush tip instead: every point becomes the
+        npe_ops.tip_rect rectangle of the tip's size, and d is ignored."""
         from . import npe_ops
         paths = []
+        if tip is not None:
+            tip = self._need_tip(tip)
+            if tip not in self._tips:
+                raise ValueError("tip %d has never been set (set_tip)" % tip)
+            tw, th = self._tips[tip]
         for i, p in enumerate(points):
             q = np.asarray(p)
             if q.ndim != 2 or q.shape[1] != 2:
                 raise ValueError("item %d: the points of a stroke have shape (K,2) as (x,y), got %s" % (i, q.shape))
-            paths.append(np.array([npe_ops.brush_rect(x, y, d) for x, y in q], np.int64).reshape(-1, 4))
-        return self.stroke(ids, paths, colours_uint8, None, weight, -1.0, mark)
+            rect = (lambda x, y: npe_ops.brush_rect(x, y, d)) if tip is None else (lambda x, y: npe_ops.tip_rect(x, y, tw, th))
+            paths.append(np.array([rect(x, y) for x, y in q], np.int64).reshape(-1, 4))
+        return self.stroke(ids, paths, colours_uint8, None, weight, -1.0, mark, tip)
 
-    def paint(self, ids, boxes, colours_uint8, weight=0.05, view=None):
+    def paint(self, ids, boxes, colours_uint8, weight=0.05, view=None, tips=None):
         """NPE.paint: Z -= weight * grad toward the brush colour (levels 0..255 per channel).  view = (origins, size): also the
-        full-resolution windows, as brush_view -> (shown, out)."""
+        full-resolution windows, as brush_view -> (shown, out).  tips: as in brush."""
         if view is not None:
-            return self.brush_view(ids, boxes, colours_uint8, None, weight, -1.0, *view)
-        return self.brush(ids, boxes, colours_uint8, None, weight, -1.0)
+            origins, size = view
+            return self.brush_view(ids, boxes, colours_uint8, None, weight, -1.0, origins, size, tips)
+        return self.brush(ids, boxes, colours_uint8, None, weight, -1.0, tips)
 
-    def scroll(self, ids, boxes, signs, weight=0.1, view=None):
-        """NPE.scroll: Z += sign(event.delta) * weight * grad of the patch mean.  view = (origins, size): as in paint."""
+    def scroll(self, ids, boxes, signs, weight=0.1, view=None, tips=None):
+        """NPE.scroll: Z += sign(event.delta) * weight * grad of the patch mean.  view = (origins, size): as in paint.  tips: as in
+        brush."""
         if view is not None:
-            return self.brush_view(ids, boxes, None, None, weight, signs, *view)
-        return self.brush(ids, boxes, None, None, weight, signs)
+            origins, size = view
+            return self.brush_view(ids, boxes, None, None, weight, signs, origins, size, tips)
+        return self.brush(ids, boxes, None, None, weight, signs, tips)
 
     def read(self, sid):
         """-> {"Z" (zdim,), "RECON", "ERROR", "IM", "GIM" (3,64,64), "MODE" int}; in a full-resolution pool also "FIELD" (3,64,64),
@@ -1124,6 +1226,7 @@ class EditSessions:
             self._opened = set()
             self._sourced = set()
             self.canvases, self.canvas_max, self.feather, self._canvas_wh, self._placed = 0, (0, 0), 0, [], {}
+            self.tips, self._tips = 0, {}
 
 
 class IAN:

@@ -239,6 +239,11 @@ struct BrushSeedSrc {
   const unsigned char* im = nullptr;    // the pool's IM and RECON bases, as gim
   const unsigned char* recon = nullptr;
   const int* clone = nullptr;           // device int[n][3]: source session, field selector, shift dr * 64 + dc
+  // ... or, with a table and colours, a brush tip per item (ian_session_brush_tip): inside its rectangle item i's loss is weighted by
+  // tips[tipsel[i] * 4096 + (r - r1) * 64 + (c - c1)] in the place of the flat 1/N; tipsel[i] = -1 keeps 1/N.  Colour brushes only:
+  // the photo and clone targets, the colour images of the stateless batched calls and the eager single call have no weighted form.
+  const float* tips = nullptr;          // device float[count][64 * 64], row stride 64 (ian_sessions_set_tip)
+  const int* tipsel = nullptr;          // device int[n]: the items' tip indices
 };
 // d loss / d x_hat of n items: g NCHW [n,3,H,W], zero outside each item's rectangle
 hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, float* g, int H, int W, hipStream_t s);

@@ -435,6 +435,10 @@ int ian_session_stroke(ian_handle* h, int32_t n, const ian_session_stroke_item* 
                        int32_t flags, uint8_t* shown, void* stream) {
   return h ? session_stroke(h, n, strokes, nboxes, boxes, flags, shown, stream) : -1;
 }
+int ian_session_path_tip(ian_handle* h, int32_t n, const ian_session_stroke_item* strokes, const int32_t* tips, int32_t nboxes,
+                         const ian_stroke_box* boxes, int32_t flags, uint8_t* shown, void* stream) {
+  return h ? session_stroke(h, n, strokes, nboxes, boxes, flags, shown, stream, true, tips) : -1;
+}
 
 int ian_autotune(ian_handle* h, int32_t n, int32_t what, void* stream) {
   int rc = check_ready(h, n);

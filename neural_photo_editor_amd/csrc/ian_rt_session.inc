@@ -11,14 +11,15 @@
 // the surviving rows, rollback, freeing, the byte count of the -2 messages, ian_session_read and the body of a saved session
 // (ian_session_save / ian_session_load: whole sessions as bytes, ian_session_record.h) are loops over that table;
 // SESS_SCRATCH does the same for the per-handle device buffers.
-// Four reservations own them (sess_free_group frees exactly one):
-//   base   ian_sessions_reserve        GIM IM RECON ERROR Z MODE; reserve(0) frees all four groups
+// Five reservations own them (sess_free_group frees exactly one):
+//   base   ian_sessions_reserve        GIM IM RECON ERROR Z MODE; reserve(0) frees all five groups
 //   hires  ian_sessions_reserve_hires  SRC (the photo at S x S, S = 64 * scale), FIELD and FIELD_KIND (what the last call displayed,
 //          as something ian_session_render can apply to SRC; DESIGN.md 4.3), and a per-session host flag "SRC holds a photo"
 //   local  ian_sessions_reserve_local  UMASK (where the user has brushed) and the LOCAL flags, and per handle the falloff table of
 //          the brush footprint (DESIGN.md 4.4)
 //   history ian_sessions_reserve_history  per session a ring of depth + 1 saved states: its Z rows and, when the local reservation
 //          exists at that moment, its UMASK rows; per session on the host the list and cursor of ian_session_history.h (DESIGN.md 4.5)
+//   tips   ian_sessions_reserve_tips   no column: per handle the brush tips' weights (d_tips) and, on the host, their sizes (DESIGN.md 4.12)
 // Without a reservation its pointers are null, no kernel touches them, and launch_session_blend runs session_blend_kernel.
 namespace {
 
@@ -26,7 +27,7 @@ constexpr size_t SESS_IMG = 3 * 64 * 64;
 constexpr int SESS_MAX_CAPACITY = 1 << 20;
 size_t sess_src_bytes(int scale) { return 3 * (size_t)(64 * scale) * (size_t)(64 * scale); }
 
-enum SessGroup { SESS_BASE, SESS_HIRES, SESS_LOCAL, SESS_HISTORY };
+enum SessGroup { SESS_BASE, SESS_HIRES, SESS_LOCAL, SESS_HISTORY, SESS_TIPS };
 using SessionArrays = ian_handle::SessionState::SessionArrays;
 struct SessColumn {
   size_t at;                                  // offsetof(SessionArrays, pool.member / rings.member): both structs go to kernels by value
@@ -62,7 +63,7 @@ struct SessScratchBuf {
   SessGroup group;
 };
 const SessScratchBuf SESS_SCRATCH[] = {
-    {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 11 * sizeof(int32_t), SESS_BASE},
+    {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 12 * sizeof(int32_t), SESS_BASE},
     {offsetof(SessionScratch, d_photo), 0, SESS_BASE},
     {offsetof(SessionScratch, d_shown), (size_t)BATCH_MAX * SESS_IMG, SESS_BASE},
     {offsetof(SessionScratch, d_rtab), 0, SESS_BASE},
@@ -77,6 +78,7 @@ const SessScratchBuf SESS_SCRATCH[] = {
     {offsetof(SessionScratch, d_falloff), 64 * sizeof(double), SESS_LOCAL},
     {offsetof(SessionScratch, d_ltab), (size_t)BATCH_MAX * 2 * sizeof(int32_t), SESS_LOCAL},
     {offsetof(SessionScratch, d_htab), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HISTORY},
+    {offsetof(SessionScratch, d_tips), 0, SESS_TIPS},   // by ian_sessions_reserve_tips, at its count
 };
 
 // the pointer member at byte `at` of a SessionArrays / SessionScratch (members of several pointer types: copied, not aliased)
@@ -199,6 +201,9 @@ void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
   } else if (g == SESS_HISTORY) {
     S.arr.rings.depth = 0;
     std::fill(S.hist.begin(), S.hist.end(), SessionHistory{});
+  } else if (g == SESS_TIPS) {
+    S.tip_count = 0;
+    S.tip_wh.clear();
   } else {
     S.arr.pool.zl = 0;
     S.capacity = 0;
@@ -211,12 +216,13 @@ void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
 // ian_sessions_reserve(0) and ian_destroy: w, radius (ian_sessions_set_blend) and dampen_thresh stay
 void sessions_free(ian_handle* h) {
   canvases_free(h);
-  for (SessGroup g : {SESS_HISTORY, SESS_LOCAL, SESS_HIRES, SESS_BASE}) sess_free_group(h->sess, g);
+  for (SessGroup g : {SESS_TIPS, SESS_HISTORY, SESS_LOCAL, SESS_HIRES, SESS_BASE}) sess_free_group(h->sess, g);
 }
 // the refusal of a call that needs the pool (SESS_BASE) or one of the other reservations
 int session_need(ian_handle* h, const char* fn, SessGroup g) {
   const auto& S = h->sess;
   if (g == SESS_BASE) return S.capacity > 0 ? 0 : fail(h, -6, "%s: no session pool (call ian_sessions_reserve first)", fn);
+  if (g == SESS_TIPS) return S.tip_count > 0 ? 0 : fail(h, -6, "%s: no tip reservation (call ian_sessions_reserve_tips first)", fn);
   if (sess_has(S.arr, g)) return 0;
   if (g == SESS_HIRES) return fail(h, -6, "%s: no full-resolution reservation (call ian_sessions_reserve_hires first)", fn);
   if (g == SESS_HISTORY) return fail(h, -6, "%s: no history reservation (call ian_sessions_reserve_history first)", fn);
@@ -869,19 +875,117 @@ int session_history(ian_handle* h, int id, int32_t* out) {
   return 0;
 }
 
-// The table of a brush or a fit in d_tab: n ian_brush_item rows of 7 words (what the shared middle reads), then the n session ids,
-// then, for a brush, the n colours of 3 floats.  fill(i, row, id, colour) writes item i into the zeroed shadow (colour: nullptr
-// without colours); one copy up; -> the three parts on the device.
-struct BrushTable { const int* items; const int* ids; const float* colour; };
-template <typename Fill>
-int brush_table_upload(ian_handle* h, int n, bool colours, hipStream_t st, BrushTable* T, Fill fill) {
+// ---- brush tips (DESIGN.md 4.12) ---------------------------------------------------------------------------------------------------
+// A setting of the handle like the guide: one device array beside the pool, [count] slots of 64 x 64 floats.  A new count is a new
+// array and every tip starts unset; the same count changes nothing.
+int sessions_reserve_tips(ian_handle* h, int count) {
+  const char* fn = "ian_sessions_reserve_tips";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
   auto& S = h->sess;
-  const size_t words = (size_t)(colours ? 11 : 8) * n;
+  if ((rc = session_need(h, fn, SESS_BASE))) return rc;
+  if (count < 0 || count > TIP_MAX_COUNT) return fail(h, -7, "%s: count %d outside 0..%d", fn, count, TIP_MAX_COUNT);
+  HIPCHK(h, hipDeviceSynchronize());   // pending work may still read the tips that are freed
+  h->last_pending = false;
+  if (count == S.tip_count) return 0;
+  sess_free_group(S, SESS_TIPS);
+  if (count == 0) return 0;
+  const size_t bytes = (size_t)count * TIP_SLOT * sizeof(float);
+  float* d = nullptr;
+  hipError_t e = hipMalloc((void**)&d, bytes);
+  if (e == hipSuccess && (e = hipMemset(d, 0, bytes)) == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (d) (void)hipFree(d);
+    (void)hipGetLastError();
+    return fail(h, -2, "%s: %s for %d tips of %zu bytes", fn, hipGetErrorString(e), count, TIP_SLOT * sizeof(float));
+  }
+  S.d_tips = d;
+  S.tip_count = count;
+  S.tip_wh.assign((size_t)2 * count, 0);
+  return 0;
+}
+// the tip index of ian_sessions_set_tip / ian_sessions_tip
+int session_tip_index(ian_handle* h, const char* fn, int tip) {
+  const int count = h->sess.tip_count;
+  return tip >= 0 && tip < count ? 0 : fail(h, -7, "%s: tip %d outside the reservation (0..%d)", fn, tip, count - 1);
+}
+int sessions_set_tip(ian_handle* h, int tip, int tw, int th, const float* wn) {
+  const char* fn = "ian_sessions_set_tip";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  if (!wn) return fail(h, -1, "null pointer passed to %s", fn);
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_TIPS))) return rc;
+  if ((rc = session_tip_index(h, fn, tip))) return rc;
+  if (tip_check_size(tw, th) != TIP_OK) return fail(h, -7, "%s: tip %d: size %d x %d, both sides must be 1..%d", fn, tip, tw, th, TIP_MAX_SIDE);
+  if (is_device_ptr(wn)) return fail(h, -7, "%s: wn must be a host array", fn);
+  int at = 0;
+  if (tip_check_weights(wn, tw, th, &at) != TIP_OK)
+    return fail(h, -7, "%s: tip %d: weight [%d][%d] = %g is not a finite number >= 0", fn, tip, at / tw, at % tw, (double)wn[at]);
+  HIPCHK(h, hipDeviceSynchronize());   // no event in flight sees the tip change
+  h->last_pending = false;
+  std::vector<float> slot((size_t)TIP_SLOT);
+  tip_to_slot(wn, tw, th, slot.data());
+  S.tip_wh[2 * tip] = S.tip_wh[2 * tip + 1] = 0;   // a failed copy leaves the tip unset, not half written
+  HIPCHK(h, hipMemcpy(S.d_tips + (size_t)tip * TIP_SLOT, slot.data(), TIP_SLOT * sizeof(float), hipMemcpyHostToDevice));
+  S.tip_wh[2 * tip] = tw;
+  S.tip_wh[2 * tip + 1] = th;
+  return 0;
+}
+int sessions_tip(ian_handle* h, int tip, int32_t* wh, float* wn_out) {
+  const char* fn = "ian_sessions_tip";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  if (!wh) return fail(h, -1, "null pointer passed to %s", fn);
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_TIPS))) return rc;
+  if ((rc = session_tip_index(h, fn, tip))) return rc;
+  const int tw = S.tip_wh[2 * tip], th = S.tip_wh[2 * tip + 1];
+  if (tw < 1) return fail(h, -7, "%s: tip %d has never been set (ian_sessions_set_tip)", fn, tip);
+  if (wn_out) {
+    if (is_device_ptr(wn_out)) return fail(h, -7, "%s: wn_out must be a host array", fn);
+    std::vector<float> slot((size_t)TIP_SLOT);
+    HIPCHK(h, hipMemcpy(slot.data(), S.d_tips + (size_t)tip * TIP_SLOT, TIP_SLOT * sizeof(float), hipMemcpyDeviceToHost));
+    tip_from_slot(slot.data(), tw, th, wn_out);
+  }
+  wh[0] = tw;
+  wh[1] = th;
+  return 0;
+}
+// What ian_session_brush_tip / ian_session_path_tip check about the tips array itself, after the checks of the plain call
+int session_tips_arg(ian_handle* h, const char* fn, const int32_t* tips) {
+  if (!tips) return fail(h, -7, "%s: null tips array (one tip index per item, -1 for none)", fn);
+  if (is_device_ptr(tips)) return fail(h, -7, "%s: the tips must be a host array", fn);
+  return session_need(h, fn, SESS_TIPS);
+}
+// ... and about one rectangle against its item's tip; point < 0: the item has one rectangle only
+int session_tip_rect(ian_handle* h, const char* fn, int item, int point, int tip, int c1, int r1, int c2, int r2) {
+  const auto& S = h->sess;
+  const TipRefusal r = tip_check_event(tip, S.tip_count, S.tip_wh.data(), c1, r1, c2, r2);
+  if (r == TIP_OK) return 0;
+  char where[48];
+  if (point >= 0) snprintf(where, sizeof where, "item %d: point %d", item, point);
+  else snprintf(where, sizeof where, "item %d", item);
+  if (r == TIP_OUTSIDE) return fail(h, -7, "%s: %s: tip %d outside -1..%d", fn, where, tip, S.tip_count - 1);
+  if (r == TIP_NEVER_SET) return fail(h, -7, "%s: %s: tip %d has never been set (ian_sessions_set_tip)", fn, where, tip);
+  return fail(h, -7, "%s: %s: patch (%d,%d,%d,%d) is not the %d x %d of tip %d", fn, where, c1, r1, c2, r2, S.tip_wh[2 * tip], S.tip_wh[2 * tip + 1], tip);
+}
+
+// The table of a brush or a fit in d_tab: n ian_brush_item rows of 7 words (what the shared middle reads), then the n session ids,
+// then, for a brush, the n colours of 3 floats, then, for a brush with tips, the n tip indices.  fill(i, row, id, colour) writes item
+// i into the zeroed shadow (colour: nullptr without colours); one copy up; -> the parts on the device.
+struct BrushTable { const int* items; const int* ids; const float* colour; const int* tipsel; };
+template <typename Fill>
+int brush_table_upload(ian_handle* h, int n, bool colours, const int32_t* tips, hipStream_t st, BrushTable* T, Fill fill) {
+  auto& S = h->sess;
+  const size_t words = (size_t)(colours ? (tips ? 12 : 11) : 8) * n;
   S.tab_shadow.assign(words, 0);
   int32_t* t = S.tab_shadow.data();
   for (int i = 0; i < n; ++i) fill(i, t + (size_t)7 * i, t + (size_t)7 * n + i, colours ? t + (size_t)8 * n + (size_t)3 * i : nullptr);
+  if (tips) memcpy(t + (size_t)11 * n, tips, (size_t)n * sizeof(int32_t));
   HIPCHK(h, hipMemcpyAsync(S.d_tab, t, words * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  *T = BrushTable{S.d_tab, S.d_tab + (size_t)7 * n, colours ? reinterpret_cast<const float*>(S.d_tab + (size_t)8 * n) : nullptr};
+  *T = BrushTable{S.d_tab, S.d_tab + (size_t)7 * n, colours ? reinterpret_cast<const float*>(S.d_tab + (size_t)8 * n) : nullptr,
+                  tips ? S.d_tab + (size_t)11 * n : nullptr};
   return 0;
 }
 // The residency of ian_session_brush / ian_session_stroke: the decoder's activations belong to sessions ids[i * stride], in that order, at
@@ -913,8 +1017,11 @@ struct BrushWindows {
   int count, vw, vh;
   uint8_t* out;
 };
-int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream, const BrushWindows& W) {
-  const char* fn = W.kind == W.CANVAS ? "ian_canvas_brush" : (W.kind == W.VIEWS ? "ian_session_brush_view" : "ian_session_brush");
+// tipped: ian_session_brush_tip, the same call with one tip index per event (tips); item i with tips[i] >= 0 weights its loss by that tip
+int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream, const BrushWindows& W,
+                  bool tipped = false, const int32_t* tips = nullptr) {
+  const char* fn = tipped ? "ian_session_brush_tip"
+                          : (W.kind == W.CANVAS ? "ian_canvas_brush" : (W.kind == W.VIEWS ? "ian_session_brush_view" : "ian_session_brush"));
   static_assert(sizeof(ian_session_event) == 11 * sizeof(int32_t), "ian_session_event is 11 words");
   int rc = session_check(h, fn, n, ev ? &ev->session : nullptr, 11, true, true);
   if (rc) return rc;
@@ -925,6 +1032,13 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
   }
   if ((rc = session_local_check(h, fn, n, &ev->session, 11))) return rc;
   auto& S = h->sess;
+  if (tipped) {
+    if ((rc = session_tips_arg(h, fn, tips))) return rc;
+    for (int i = 0; i < n; ++i)
+      if ((rc = session_tip_rect(h, fn, i, -1, tips[i], ev[i].c1, ev[i].r1, ev[i].c2, ev[i].r2))) return rc;
+  } else {
+    tips = nullptr;
+  }
   if (W.kind == W.VIEWS && (rc = session_view_check(h, fn, W.count, W.views, W.vw, W.vh, W.out, ev))) return rc;
   if (W.kind == W.CANVAS && (rc = canvas_window_check(h, fn, W.count, W.windows, W.vw, W.vh, W.out))) return rc;
   ResultTarget win = {};
@@ -936,7 +1050,7 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
   session_enter(h, st);   // also ends the residency: re-armed below
   TotalTimer tt(h, st);
   BrushTable tab;   // the event table, rearranged for the kernels
-  rc = brush_table_upload(h, n, true, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* colour) {
+  rc = brush_table_upload(h, n, true, tips, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* colour) {
     memcpy(row, &ev[i].c1, 7 * sizeof(int32_t));   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
     *id = ev[i].session;
     memcpy(colour, ev[i].rgb, 3 * sizeof(float));
@@ -954,6 +1068,10 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
     BrushSeedSrc seed;
     seed.table = tab.items + (size_t)7 * off;
     seed.colour = tab.colour + (size_t)3 * off;
+    if (tips) {
+      seed.tips = S.d_tips;
+      seed.tipsel = tab.tipsel + off;
+    }
     if ((rc = brush_pass_middle(h, nc, seed, true, st))) return rc;
     HIPCHK(h, launch_session_blend(session_blend_args(h, tab.ids + off, seed.table, sh.dev + (size_t)off * SESS_IMG, 1), nc, st));
   }
@@ -1003,7 +1121,7 @@ int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int s
   session_enter(h, st);   // also ends the residency: re-armed below
   TotalTimer tt(h, st);
   BrushTable tab;
-  rc = brush_table_upload(h, n, true, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* src) {
+  rc = brush_table_upload(h, n, true, nullptr, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* src) {
     const ian_session_clone_event& e = ev[i];
     row[0] = e.c1; row[1] = e.r1; row[2] = e.c2; row[3] = e.r2; row[4] = 1;   // ian_brush_item's layout, loss kind 1
     memcpy(row + 5, &e.coef, sizeof(float));
@@ -1049,9 +1167,10 @@ int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int s
 // still run, then the stored blend of those that end here (their Z rows, IM / FIELD, shown), then, when some are left, the forward
 // again at the smaller batch: the per-event calls would miss their residency at the same point, and the decoder's kernels may differ
 // with the batch.  While the set of strokes stays the same, the forward at z_new IS the next step's forward.
+// tipped: ian_session_path_tip, the same call with one tip index per stroke (tips), n more words at the end of the table
 int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int nboxes, const ian_stroke_box* boxes, int flags,
-                   uint8_t* shown, void* stream) {
-  const char* fn = "ian_session_stroke";
+                   uint8_t* shown, void* stream, bool tipped = false, const int32_t* tips = nullptr) {
+  const char* fn = tipped ? "ian_session_path_tip" : "ian_session_stroke";
   static_assert(sizeof(ian_session_stroke_item) == 8 * sizeof(int32_t), "ian_session_stroke_item is 8 words");
   static_assert(sizeof(ian_stroke_box) == 5 * sizeof(int32_t), "ian_stroke_box is 5 words");
   static_assert(IAN_STROKE_MAX_POINTS == STROKE_MAX_POINTS, "the kernel's LDS holds one rectangle per point");
@@ -1081,6 +1200,16 @@ int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int 
   }
   if ((rc = session_local_check(h, fn, n, &sk->session, 8))) return rc;
   auto& S = h->sess;
+  if (tipped) {
+    if ((rc = session_tips_arg(h, fn, tips))) return rc;
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < sk[i].count; ++k) {
+        const ian_stroke_box& b = boxes[sk[i].first + k];
+        if ((rc = session_tip_rect(h, fn, i, k, tips[i], b.c1, b.r1, b.c2, b.r2))) return rc;
+      }
+  } else {
+    tips = nullptr;
+  }
   const int pass = h->opt.brush_pass;
   const bool hit = n <= pass && session_residency_hit(S, n, &sk->session, 8);
   // the table
@@ -1091,7 +1220,8 @@ int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int 
     rows[k + 1] = rows[k] + act;
   }
   const size_t o_save = (size_t)n, o_col = (size_t)2 * n, o_rows = (size_t)5 * n, o_items = o_rows + (size_t)steps + 1;
-  const size_t words = o_items + (size_t)7 * rows[steps];
+  const size_t o_tips = o_items + (size_t)7 * rows[steps];
+  const size_t words = o_tips + (tips ? (size_t)n : 0);
   if ((rc = grow_dev(h, &S.d_stab, &S.stab_cap, words))) return rc;
   S.stab_shadow.assign(words, 0);
   int32_t* t = S.stab_shadow.data();
@@ -1106,6 +1236,7 @@ int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int 
     memcpy(t + o_col + (size_t)3 * i, sk[i].rgb, 3 * sizeof(float));
   }
   memcpy(t + o_rows, rows, ((size_t)steps + 1) * sizeof(int32_t));
+  if (tips) memcpy(t + o_tips, tips, (size_t)n * sizeof(int32_t));
   for (int k = 0; k < steps; ++k)
     for (int i = 0; i < rows[k + 1] - rows[k]; ++i) {
       int32_t* row = t + o_items + (size_t)7 * (rows[k] + i);   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
@@ -1139,6 +1270,10 @@ int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int 
       BrushSeedSrc seed;
       seed.table = d_items + (size_t)7 * (rows[k] + off);
       seed.colour = d_col + (size_t)3 * off;
+      if (tips) {   // the strokes of a step are a prefix of the pass: so are their tips
+        seed.tips = S.d_tips;
+        seed.tipsel = S.d_stab + o_tips + off;
+      }
       if ((rc = brush_pass_middle(h, act, seed, true, st))) return rc;
       int keep = act;
       while (keep > 0 && sk[off + keep - 1].count == k + 1) --keep;
@@ -1196,7 +1331,7 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
   session_enter(h, st);   // also ends the residency of ian_session_brush: not re-armed, the last forward keeps no activations
   TotalTimer tt(h, st);
   BrushTable tab;   // the rows: the rectangle, loss kind 1; coef and gscale unused
-  rc = brush_table_upload(h, n, false, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t*) {
+  rc = brush_table_upload(h, n, false, nullptr, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t*) {
     row[0] = items[i].c1; row[1] = items[i].r1; row[2] = items[i].c2; row[3] = items[i].r2; row[4] = 1;
     *id = items[i].session;
   });
@@ -1444,6 +1579,21 @@ int ian_session_set_latent(ian_handle* h, int32_t n, const int32_t* ids, const f
 }
 int ian_session_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, void* stream) {
   return h ? session_brush(h, n, events, shown, stream, BrushWindows{}) : -1;
+}
+int ian_sessions_reserve_tips(ian_handle* h, int32_t count) {
+  return h ? sessions_reserve_tips(h, count) : -1;
+}
+int ian_sessions_set_tip(ian_handle* h, int32_t tip, int32_t tw, int32_t th, const float* wn) {
+  return h ? sessions_set_tip(h, tip, tw, th, wn) : -1;
+}
+int ian_sessions_tip(ian_handle* h, int32_t tip, int32_t wh[2], float* wn_out) {
+  return h ? sessions_tip(h, tip, wh, wn_out) : -1;
+}
+int ian_session_brush_tip(ian_handle* h, int32_t n, const ian_session_event* events, const int32_t* tips, uint8_t* shown,
+                          const ian_session_view* views, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
+  if (!h) return -1;
+  const BrushWindows W = views ? BrushWindows{BrushWindows::VIEWS, views, nullptr, n, vw, vh, out} : BrushWindows{};
+  return session_brush(h, n, events, shown, stream, W, true, tips);
 }
 int ian_session_read(ian_handle* h, int32_t id, int32_t what, void* out, void* stream) {
   return h ? session_read(h, id, what, out, stream) : -1;

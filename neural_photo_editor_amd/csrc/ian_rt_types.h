@@ -291,7 +291,7 @@ struct ian_handle {
   // The device buffers beside the pool, as plain data: SESS_SCRATCH (ian_rt_session.inc) names each once, with the reservation that
   // owns it and its size; nothing else allocates or frees them.
   struct SessionScratch {
-    int* d_tab = nullptr;              // per call: brush = [7n ian_brush_item words | n ids | 3n colours], open / set_latent = n ids
+    int* d_tab = nullptr;              // per call: brush = [7n ian_brush_item words | n ids | 3n colours | with tips: n tip indices], open / set_latent = n ids
     float* d_tanh = nullptr;           // to_tanh of the 256 uint8 levels, float32
     unsigned char* d_photo = nullptr;  // staging of host photos [256][3*64*64], allocated by the first open that needs it
     unsigned char* d_shown = nullptr;  // staging of the canvas images [256][3*64*64]
@@ -306,6 +306,7 @@ struct ian_handle {
     float* d_fit = nullptr;            // ian_session_fit: Adam's moments of one pass, m [256][zl] then v [256][zl]; by the first such call
     double* d_fit_loss = nullptr;      // ian_session_fit: staging of the loss trace for a host `loss`, [256][513]; by the first call that asks for one
     int* d_stab = nullptr;             // ian_session_stroke: per call [n ids | n history slots | 3n colours | steps + 1 row offsets | the steps' ian_brush_item rows], grown on demand (stab_cap words)
+    float* d_tips = nullptr;           // brush tips: f32[tip_count][64 * 64], row stride 64 (ian_sessions_reserve_tips / _set_tip); nullptr = no tips
   };
   struct SessionState : SessionScratch {
     int capacity = 0;
@@ -342,6 +343,10 @@ struct ian_handle {
     // strokes (ian_session_stroke)
     std::vector<int32_t> stab_shadow;    // upload source of d_stab
     size_t stab_cap = 0;
+    // brush tips (ian_sessions_reserve_tips): how many d_tips holds and per tip its (tw, th), (0, 0) until ian_sessions_set_tip gave it
+    // weights.  Per handle, not per session: no record, history or canvas knows of them.
+    int tip_count = 0;
+    std::vector<int32_t> tip_wh;
     // canvases (ian_sessions_reserve_canvas, ian_rt_canvas.inc): the device arrays, per canvas the size of its picture (0 x 0: never
     // put), per session where it is placed (canvas -1: nowhere; sized with the pool while canvases exist, empty otherwise), and the
     // host's copy of the device table (canv.table), from which a canvas's 8 entries are uploaded whenever they change

@@ -22,6 +22,7 @@
 #include "ian_row_bands.h"         // row bands per image of the image-producing kernels (kernels_head.hip): plain C++, also compiled on its own by a test
 #include "ian_session_history.h"   // the undo history's bookkeeping per edit session: plain C++, also compiled on its own by a test
 #include "ian_session_record.h"    // a saved session's padding rule, meta validation and ring map: plain C++, also compiled on its own by a test
+#include "ian_tip_check.h"         // a brush tip's size and weights, an event's rectangle against its tip: plain C++, also compiled on its own by a test
 
 using namespace ian;
 

@@ -20,13 +20,16 @@ enum { SEED_IMM = 0,      // the rectangle and loss kind are launch arguments, t
        SEED_RGB = 1,      // row blockIdx.y of the ian_brush_item table, the target an image rgb [n,3,H,W]
        SEED_COLOUR = 2,   // the same table, the target a constant colour [n][3] (ian_session_brush, NPE.py:205 myRGB)
        SEED_PHOTO = 3,    // the same table, the target the item's own photo: tab[GIM byte] of session ids[item] (ian_session_fit)
-       SEED_CLONE = 4 };  // the same table, the target another picture of the pool, shifted: tab[F byte at o + shift] of session
+       SEED_CLONE = 4,    // the same table, the target another picture of the pool, shifted: tab[F byte at o + shift] of session
                           // clone[3 item], F = its GIM, IM or RECON row (ian_session_clone)
-struct SeedRect { int c1, r1, c2, r2, mode, id, field, shift; };   // id: SEED_PHOTO the item's session, SEED_CLONE its source;
-                                                                   // field, shift: SEED_CLONE only
+       SEED_TIP = 5 };    // SEED_COLOUR with a weight per pixel in the place of the flat 1/N: tips[tipsel[item]][r - r1][c - c1], a
+                          // brush tip of ian_sessions_set_tip (ian_session_brush_tip); an item with tipsel -1 keeps 1/N
+struct SeedRect { int c1, r1, c2, r2, mode, id, field, shift, tip; };   // id: SEED_PHOTO the item's session, SEED_CLONE its source;
+                                                                        // field, shift: SEED_CLONE only; tip: SEED_TIP only
 constexpr int SEED_PHOTO_IMG = 3 * 64 * 64;          // a GIM / IM / RECON row of the session pool
+constexpr int SEED_TIP_ROW = 64, SEED_TIP_IMG = 64 * 64;   // a tip's row stride and its slot in BrushSeedSrc::tips
 template <int KIND> struct SeedLds {                 // ints / floats of LDS a kernel hands to seed_fetch
-  static constexpr int SP = KIND == SEED_CLONE ? 8 : (KIND == SEED_PHOTO ? 6 : 5), SC = (KIND == SEED_PHOTO || KIND == SEED_CLONE) ? 256 : 4;
+  static constexpr int SP = KIND == SEED_CLONE ? 8 : ((KIND == SEED_PHOTO || KIND == SEED_TIP) ? 6 : 5), SC = (KIND == SEED_PHOTO || KIND == SEED_CLONE) ? 256 : 4;
 };
 
 // The table may live in mapped host memory (zero-copy graphs): ONE lane per word fetches it and hands it on through LDS -- a scalar
@@ -41,11 +44,14 @@ template <int KIND> struct SeedLds {                 // ints / floats of LDS a k
 // wins nor loses, and it keeps the one seed_value body.
 // SEED_CLONE is SEED_PHOTO with the row chosen per item: its three words (source id, field selector, shift) travel like SEED_PHOTO's
 // id, one lane per word, and the table is staged for the same reason (ian_session_clone takes the whole picture as a rectangle too).
+// SEED_TIP is SEED_COLOUR with one more word, the item's tip index, which travels like SEED_PHOTO's id.  The tip's weights are NOT
+// staged: a tip is up to 16 KB, a workgroup of the fused kernel covers 8 pixels and reads at most 8 x 25 of its weights, so staging
+// would load far more than is used; they are read through the cache where they are needed (seed_weight).
 template <int KIND>
 __device__ __forceinline__ SeedRect seed_fetch(const BrushSeedSrc& src, int item, int* sp, float* sc) {
-  if (KIND == SEED_IMM) return {src.c1, src.r1, src.c2, src.r2, src.mode, 0};
+  if (KIND == SEED_IMM) return {src.c1, src.r1, src.c2, src.r2, src.mode, 0, 0, 0, -1};
   if (threadIdx.x < 5) sp[threadIdx.x] = src.table[item * 7 + threadIdx.x];
-  if (KIND == SEED_COLOUR && threadIdx.x >= 8 && threadIdx.x < 11) sc[threadIdx.x - 8] = src.colour[item * 3 + (threadIdx.x - 8)];
+  if ((KIND == SEED_COLOUR || KIND == SEED_TIP) && threadIdx.x >= 8 && threadIdx.x < 11) sc[threadIdx.x - 8] = src.colour[item * 3 + (threadIdx.x - 8)];
   if (KIND == SEED_PHOTO) {
     if (threadIdx.x == 5) sp[5] = src.ids[item];
     sc[threadIdx.x] = src.tanh_tab[threadIdx.x];
@@ -54,12 +60,14 @@ __device__ __forceinline__ SeedRect seed_fetch(const BrushSeedSrc& src, int item
     if (threadIdx.x >= 5 && threadIdx.x < 8) sp[threadIdx.x] = src.clone[item * 3 + (threadIdx.x - 5)];
     sc[threadIdx.x] = src.tanh_tab[threadIdx.x];
   }
+  if (KIND == SEED_TIP && threadIdx.x == 5) sp[5] = src.tipsel[item];
   __syncthreads();
   // the same five words in every lane: kept in scalar registers, as the launch arguments of SEED_IMM are
   return {__builtin_amdgcn_readfirstlane(sp[0]), __builtin_amdgcn_readfirstlane(sp[1]), __builtin_amdgcn_readfirstlane(sp[2]),
           __builtin_amdgcn_readfirstlane(sp[3]), __builtin_amdgcn_readfirstlane(sp[4]),
           (KIND == SEED_PHOTO || KIND == SEED_CLONE) ? __builtin_amdgcn_readfirstlane(sp[5]) : 0,
-          KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[6]) : 0, KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[7]) : 0};
+          KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[6]) : 0, KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[7]) : 0,
+          KIND == SEED_TIP ? __builtin_amdgcn_readfirstlane(sp[5]) : -1};
 }
 // the u8 row a seed's targets are looked up in: SEED_PHOTO the GIM row of the item's session, SEED_CLONE the row of its source that
 // the field selector names (0 GIM, 1 IM, 2 RECON: the same for every lane of the workgroup); the other kinds have none
@@ -74,9 +82,20 @@ __device__ __forceinline__ float seed_inv(const SeedRect& R) {
   const int cnt = 3 * (R.r2 - R.r1) * (R.c2 - R.c1);
   return cnt > 0 ? 1.f / (float)cnt : 0.f;
 }
+// The factor of the loss at pixel (r, c) INSIDE the rectangle: the flat inv, or for SEED_TIP the tip's weight there (all three channels
+// share it).  The tip index is the same in every lane (a scalar register), so an item without a tip takes the inv path on a
+// workgroup-uniform branch.  ian_session_brush_tip refused every item whose rectangle is not exactly its tip's tw x th <= 64 x 64 and
+// every tip outside the reservation: (r - r1) * 64 + (c - c1) stays inside the tip's 64 x 64 slot.  A weight of 0 is not skipped: the
+// seed 2 * (xh - t) * 0 is +-0 and adds nothing to an accumulator, so skipping would change no bit, and the branch would serve only
+// the corners of a round tip.
+template <int KIND>
+__device__ __forceinline__ float seed_weight(const BrushSeedSrc& src, const SeedRect& R, float inv, int r, int c) {
+  if (KIND == SEED_TIP && R.tip >= 0) return src.tips[(size_t)R.tip * SEED_TIP_IMG + (r - R.r1) * SEED_TIP_ROW + (c - R.c1)];
+  return inv;
+}
 // the seed of element o (channel co, value xh) of the item's image, for an element INSIDE a non-empty rectangle; rgb_i = the item's
 // target image, sc = its colour in LDS (SEED_PHOTO / SEED_CLONE: the tanh table, gim_i = the row of seed_row): whichever KIND names
-// is read, and only in mode 1
+// is read, and only in mode 1.  inv: the pixel's seed_weight; SEED_TIP is SEED_COLOUR from here on
 template <int KIND>
 __device__ __forceinline__ float seed_value(int mode, float inv, float xh, const float* rgb_i, const float* sc,
                                             const unsigned char* gim_i, int o, int co, int shift) {
@@ -85,7 +104,7 @@ __device__ __forceinline__ float seed_value(int mode, float inv, float xh, const
     // 64x64 image: o + shift = (co * 64 + r + dr) * 64 + c + dc stays inside channel plane co of the source row
     return (mode == 0) ? inv : 2.f * (xh - sc[gim_i[o + shift]]) * inv;
   }
-  return (mode == 0) ? inv : 2.f * (xh - (KIND == SEED_COLOUR ? sc[co] : (KIND == SEED_PHOTO ? sc[gim_i[o]] : rgb_i[o]))) * inv;
+  return (mode == 0) ? inv : 2.f * (xh - ((KIND == SEED_COLOUR || KIND == SEED_TIP) ? sc[co] : (KIND == SEED_PHOTO ? sc[gim_i[o]] : rgb_i[o]))) * inv;
 }
 
 // seed only: g NCHW [n,3,H,W]; element i of an image belongs to channel i / (H*W).  Grid (3*H*W / 256, n).
@@ -100,13 +119,13 @@ __global__ __launch_bounds__(256) void brush_seed_kernel(BrushSeedSrc src, const
   if (i >= 3 * H * W) return;
   const size_t img = (size_t)item * 3 * H * W;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_TIP && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
   const unsigned char* gim_i = seed_row<KIND>(src, R);
   const int xx = i % W, yy = (i / W) % H;
   float v = 0.f;
   if (yy >= R.r1 && yy < R.r2 && xx >= R.c1 && xx < R.c2) {
     const float inv = seed_inv(R);
-    if (inv > 0.f) v = seed_value<KIND>(R.mode, inv, xh_i[i], rgb_i, sc, gim_i, i, i / (H * W), R.shift);
+    if (inv > 0.f) v = seed_value<KIND>(R.mode, seed_weight<KIND>(src, R, inv, yy, xx), xh_i[i], rgb_i, sc, gim_i, i, i / (H * W), R.shift);
   }
   (g + img)[i] = v;
 }
@@ -136,7 +155,7 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
   const int OH = 2 * H, OW = 2 * W;
   const size_t img = (size_t)item * Cout * OH * OW;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_TIP && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
   const unsigned char* gim_i = seed_row<KIND>(src, R);
   const float inv = seed_inv(R);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -149,10 +168,11 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
       for (int kx = kx0; kx < kx1; ++kx) {
         const int ox = 2 * ix - 2 + kx;
         if ((unsigned)ox >= (unsigned)OW) continue;
+        const float wt = seed_weight<KIND>(src, R, inv, oy, ox);   // once per tap: the three channels share it
         for (int co = 0; co < Cout; ++co) {
           const int o = (co * OH + oy) * OW + ox;
           const float xh = xh_i[o];
-          float gv = seed_value<KIND>(R.mode, inv, xh, rgb_i, sc, gim_i, o, co, R.shift);
+          float gv = seed_value<KIND>(R.mode, wt, xh, rgb_i, sc, gim_i, o, co, R.shift);
           gv = gv * m_dact(xh, out_act) * (oscale ? oscale[co] : 1.f);
           const float4 wv = *reinterpret_cast<const float4*>(w + ((size_t)(ky * 5 + kx) * 4 + co) * Cin + ci);
           acc[0] = fmaf(gv, wv.x, acc[0]);
@@ -175,8 +195,10 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
 }
 
 static int seed_kind(const BrushSeedSrc& src) {
-  return !src.table ? SEED_IMM : (src.clone ? SEED_CLONE : (src.gim ? SEED_PHOTO : (src.colour ? SEED_COLOUR : SEED_RGB)));
+  return !src.table ? SEED_IMM : (src.clone ? SEED_CLONE : (src.gim ? SEED_PHOTO : (src.tipsel ? SEED_TIP : (src.colour ? SEED_COLOUR : SEED_RGB))));
 }
+// a tip weights a colour brush: the colours, the tips' array, and the 64x64 image a tip's slot is made for
+static bool seed_tip_ok(const BrushSeedSrc& src, int C, int H, int W) { return src.colour && src.tips && C == 3 && H <= 64 && W <= 64; }
 // a photo target is a GIM row of the pool: 3 x 64 x 64 bytes, with the id list and the table to go with it
 static bool seed_photo_ok(const BrushSeedSrc& src, int C, int H, int W) { return src.ids && src.tanh_tab && C * H * W == SEED_PHOTO_IMG; }
 // a cloned target is a GIM, IM or RECON row of the pool: all three bases, the table, and the 3 x 64 x 64 image the shift is made for
@@ -188,11 +210,13 @@ hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, 
   const int kind = seed_kind(src);
   if (n < 1 || n > 65535 || (kind == SEED_IMM && n != 1) || (kind == SEED_PHOTO && !seed_photo_ok(src, 3, H, W))) return hipErrorInvalidValue;
   if (kind == SEED_CLONE && !seed_clone_ok(src, 3, H, W)) return hipErrorInvalidValue;
+  if (kind == SEED_TIP && !seed_tip_ok(src, 3, H, W)) return hipErrorInvalidValue;
   const dim3 grid((3 * H * W + 255) / 256, n);
   if (kind == SEED_IMM) hipLaunchKernelGGL(brush_seed_kernel<SEED_IMM>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_RGB) hipLaunchKernelGGL(brush_seed_kernel<SEED_RGB>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_PHOTO) hipLaunchKernelGGL(brush_seed_kernel<SEED_PHOTO>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_CLONE) hipLaunchKernelGGL(brush_seed_kernel<SEED_CLONE>, grid, dim3(256), 0, s, src, xhat, g, H, W);
+  else if (kind == SEED_TIP) hipLaunchKernelGGL(brush_seed_kernel<SEED_TIP>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else hipLaunchKernelGGL(brush_seed_kernel<SEED_COLOUR>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   return hipGetLastError();
 }
@@ -203,8 +227,12 @@ hipError_t launch_brush_seed_dec_out(const BrushSeedSrc& src, int n, const float
   if ((Cin & 3) || n < 1 || n > 65535 || kind == SEED_IMM || (kind == SEED_COLOUR && Cout > 3)) return hipErrorInvalidValue;
   if (kind == SEED_PHOTO && !seed_photo_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
   if (kind == SEED_CLONE && !seed_clone_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
+  if (kind == SEED_TIP && !seed_tip_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
   const dim3 grid((H * W * (Cin >> 2) + 255) / 256, n);
-  if (kind == SEED_CLONE)
+  if (kind == SEED_TIP)
+    hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_TIP>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H, W,
+                       Cin, Cout, act);
+  else if (kind == SEED_CLONE)
     hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_CLONE>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H, W,
                        Cin, Cout, act);
   else if (kind == SEED_PHOTO)

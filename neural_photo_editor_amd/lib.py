@@ -50,6 +50,7 @@ EXPORTS = (
     "ian_sessions_reserve_local", "ian_sessions_set_local", "ian_session_local",
     "ian_sessions_reserve_history", "ian_session_mark", "ian_session_undo", "ian_session_history",
     "ian_session_fit", "ian_session_stroke", "ian_session_clone",
+    "ian_sessions_reserve_tips", "ian_sessions_set_tip", "ian_sessions_tip", "ian_session_brush_tip", "ian_session_path_tip",
     "ian_session_record_info", "ian_session_save", "ian_session_load",
     "ian_sessions_reserve_canvas", "ian_canvas_put", "ian_canvas_place", "ian_canvas_compose", "ian_canvas_brush", "ian_canvas_commit",
     "ian_canvas_read", "ian_canvas_placements",
@@ -134,6 +135,11 @@ def load_library():
     lib.ian_session_fit.argtypes = [vp, i32, C.POINTER(SessionFitItem), i32, C.c_float, fp, fp, vp]
     lib.ian_session_stroke.argtypes = [vp, i32, C.POINTER(SessionStroke), i32, C.POINTER(StrokeBox), i32, fp, vp]
     lib.ian_session_clone.argtypes = [vp, i32, C.POINTER(SessionCloneEvent), i32, fp, vp]
+    lib.ian_sessions_reserve_tips.argtypes = [vp, i32]
+    lib.ian_sessions_set_tip.argtypes = [vp, i32, i32, i32, fp]
+    lib.ian_sessions_tip.argtypes = [vp, i32, fp, fp]
+    lib.ian_session_brush_tip.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, fp, C.POINTER(SessionView), i32, i32, fp, vp]
+    lib.ian_session_path_tip.argtypes = [vp, i32, C.POINTER(SessionStroke), fp, i32, C.POINTER(StrokeBox), i32, fp, vp]
     lib.ian_session_record_info.argtypes = [vp, C.POINTER(SessionMeta), fp, fp]
     lib.ian_session_save.argtypes = [vp, i32, fp, fp, fp, vp]
     lib.ian_session_load.argtypes = [vp, i32, fp, fp, fp, vp]
@@ -506,6 +512,43 @@ class Handle:
         u8[n,3,64,64] or None."""
         self._check(self.lib.ian_session_clone(self._h, len(events), events, int(steps), _ptr(shown) if shown is not None else C.c_void_p(0),
                                                C.c_void_p(stream or 0)))
+
+    # ---- brush tips (ian_sessions_reserve_tips, ian_session_brush_tip, ian_session_path_tip) ----
+    def sessions_reserve_tips(self, count):
+        self._check(self.lib.ian_sessions_reserve_tips(self._h, int(count)))
+
+    def sessions_set_tip(self, tip, wn):
+        """ian_sessions_set_tip; wn = float32 [th][tw] weights, taken as given (npe_ops.tip_weights normalises a shape)."""
+        wn = np.ascontiguousarray(wn, np.float32)
+        if wn.ndim != 2:
+            raise ValueError("a tip is a 2-D weight image [th][tw], got shape %s" % (wn.shape,))
+        self._check(self.lib.ian_sessions_set_tip(self._h, int(tip), wn.shape[1], wn.shape[0], _ptr(wn)))
+
+    def sessions_tip(self, tip):
+        """ian_sessions_tip -> the float32 [th][tw] weights of one tip."""
+        wh = np.zeros(2, np.int32)
+        self._check(self.lib.ian_sessions_tip(self._h, int(tip), _ptr(wh), C.c_void_p(0)))
+        wn = np.empty((int(wh[1]), int(wh[0])), np.float32)
+        self._check(self.lib.ian_sessions_tip(self._h, int(tip), _ptr(wh), _ptr(wn)))
+        return wn
+
+    def session_brush_tip(self, events, tips, shown=None, views=None, vw=0, vh=0, out=None, stream=None):
+        """ian_session_brush_tip; events = a ctypes array of SessionEvent (n = its length), tips = int32[n] (-1: no tip); views (a
+        ctypes array of SessionView of the same length) with vw, vh, out as in session_brush_view, or None."""
+        tips = np.ascontiguousarray(tips, np.int32)
+        if tips.shape != (len(events),):
+            raise ValueError("tips must hold one index per event (%d), got shape %s" % (len(events), tips.shape))
+        null = C.c_void_p(0)
+        self._check(self.lib.ian_session_brush_tip(self._h, len(events), events, _ptr(tips), _ptr(shown) if shown is not None else null,
+                                                   views, int(vw), int(vh), _ptr(out) if out is not None else null, C.c_void_p(stream or 0)))
+
+    def session_path_tip(self, strokes, tips, boxes, flags=0, shown=None, stream=None):
+        """ian_session_path_tip; the arguments of session_stroke and tips = int32[n], one per stroke (-1: no tip)."""
+        tips = np.ascontiguousarray(tips, np.int32)
+        if tips.shape != (len(strokes),):
+            raise ValueError("tips must hold one index per stroke (%d), got shape %s" % (len(strokes), tips.shape))
+        self._check(self.lib.ian_session_path_tip(self._h, len(strokes), strokes, _ptr(tips), len(boxes), boxes, int(flags),
+                                                  _ptr(shown) if shown is not None else C.c_void_p(0), C.c_void_p(stream or 0)))
 
     def session_record_info(self):
         """ian_session_record_info -> (the pool's layout as a SessionMeta, the byte offsets of its arrays in a body); host only."""

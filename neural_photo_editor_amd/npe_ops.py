@@ -409,6 +409,77 @@ def brush_rect(x, y, d):
     return xmin, ymin, xmin + brush_width, ymin + brush_width
 
 
+# ---- brush tips (ian_sessions_set_tip, ian_session_brush_tip) -------------------------------------------------------
+# A tip is a weight image [th][tw]; the library takes the weights as given, and what a brush shape means as a loss is decided here.
+def tip_weights(w):
+    """A brush shape w [th][tw] (weights >= 0, not all zero) -> the float32 weights of ian_sessions_set_tip, normalised so that they
+    sum to 1/3 (times three channels: a weighted MEAN, as the rectangle's 1/N is): float32(w) * (float32(1) / float32(3 * S)), S the
+    float64 sum of w.  For w == 1 that is 1.f / (float)(3 * th * tw), the rectangle brush's own factor, bit for bit."""
+    w = np.asarray(w)
+    if w.ndim != 2 or not 1 <= w.shape[0] <= 64 or not 1 <= w.shape[1] <= 64:
+        raise ValueError("a tip has shape (th, tw) with both sides 1..64, got %s" % (w.shape,))
+    w64 = w.astype(np.float64)
+    if not np.all(np.isfinite(w64)) or np.any(w64 < 0):
+        raise ValueError("the weights of a tip are finite and >= 0")
+    S = float(w64.sum())
+    if not S > 0:
+        raise ValueError("a tip that is all zero has no normalisation (pass it with normalise=False for a zero gradient)")
+    return (w.astype(np.float32) * (np.float32(1) / np.float32(3 * S))).astype(np.float32)
+
+
+def tip_rect(x, y, tw, th):
+    """The rectangle of a tw x th tip at the mouse position (x, y) in 64-pixel space -> (c1, r1, c2, r2): placed as move_mouse places
+    its square (NPE.py:148-156, brush_rect), centred on the point and pushed back inside the image."""
+    x, y, tw, th = int(x), int(y), int(tw), int(th)
+    if not (1 <= tw <= 64 and 1 <= th <= 64):
+        raise ValueError("a tip has both sides 1..64, got %d x %d" % (tw, th))
+    xmin = max(min(x - tw // 2, 64 - tw), 0)
+    ymin = max(min(y - th // 2, 64 - th), 0)
+    return xmin, ymin, xmin + tw, ymin + th
+
+
+def round_tip(diameter, hardness=0.5):
+    """A round brush of `diameter` pixels (1..64) with a soft edge -> float32 (diameter, diameter), un-normalised: weight 1 out to
+    hardness * R from the centre, falling smoothly (smoothstep: zero slope at both ends) to 0 at R = diameter / 2; a pixel is taken at
+    its centre.  Built in float64.  hardness in [0, 1]; 1 is a hard disc."""
+    D, hd = int(diameter), float(hardness)
+    if not 1 <= D <= 64:
+        raise ValueError("diameter %r outside 1..64" % (diameter,))
+    if not 0.0 <= hd <= 1.0:
+        raise ValueError("hardness %r outside [0, 1]" % (hardness,))
+    R = D / 2.0
+    o = np.arange(D, dtype=np.float64) + 0.5 - R         # pixel centres, symmetric about 0
+    d2 = o[:, None] ** 2 + o[None, :] ** 2               # the same sum in every one of the square's eight symmetries
+    r = np.sqrt(d2)
+    r0 = hd * R
+    if r0 < R:
+        t = np.clip((R - r) / (R - r0), 0.0, 1.0)
+        w = t * t * (3.0 - 2.0 * t)
+    else:
+        w = (r < R).astype(np.float64)
+    w[r <= r0] = 1.0
+    return w.astype(np.float32)
+
+
+def tip_seed(xhat, box, wn, rgb=None, mode=1):
+    """The loss seed of one tip event, operation by operation what the seed kernels compute (kernels_brush.hip, SEED_TIP) -> float32
+    (3,H,W): inside box = (c1, r1, c2, r2), whose size is wn's, mode 1 gives 2.f * (xhat - rgb[co]) * wn[r - r1][c - c1] (float32:
+    the difference rounded, then each product) and mode 0 gives wn[r - r1][c - c1]; zero outside.  The three channels share wn."""
+    xhat = np.asarray(xhat, np.float32)
+    wn = np.asarray(wn, np.float32)
+    c1, r1, c2, r2 = [int(v) for v in box]
+    if xhat.ndim != 3 or wn.shape != (r2 - r1, c2 - c1):
+        raise ValueError("the box (%d,%d,%d,%d) is not the tip's %s" % (c1, r1, c2, r2, wn.shape))
+    g = np.zeros_like(xhat)
+    if int(mode) == 0:
+        g[:, r1:r2, c1:c2] = wn[None]
+        return g
+    t = np.asarray(rgb, np.float32).reshape(-1, 1, 1)
+    d = (xhat[:, r1:r2, c1:c2] - t).astype(np.float32)
+    g[:, r1:r2, c1:c2] = ((np.float32(2) * d).astype(np.float32) * wn[None]).astype(np.float32)
+    return g
+
+
 def stroke_footprint(U, boxes, t):
     """USER_MASK after a whole stroke (ian_session_stroke): umask_paint for every rectangle of boxes (K,4), in sequence.  np.maximum is
     exact, so the order of the rectangles does not matter and a rectangle given twice adds nothing."""

@@ -2,7 +2,7 @@
 ids: state in HBM, 11 words up per event, 12 KB down) and of IAN.brush_step_batch with host pointers and photo= (per item a 48 KB
 colour image, RECON, ERROR and the latent compared against their shadows, z_new and IM down), in one process, on both configs.
 usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 16 64] [--calls 200] [--repeats 3] [--out FILE] [--local]
-                                                    [--history]
+                                                    [--history] [--tip D]
   --local: the same event stream on a pool with the local reservation and flags 3 (user mask + dampen) on every session: per item
            the blend also reads, max-es and writes the session's 32 KB UMASK.  Compare against a run without --local in the same
            process order on the same build.
@@ -11,6 +11,11 @@ usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 
            undo             one ian_session_undo per call, undo and redo alternating on a marked stroke
            set_latent       the same sessions' latents through set_latent (host z): what an undo should cost, less one small launch
            paint_unused_history  paint in the pool with the history reserved but never marked, to hold against paint without --history
+  --tip D: brush tips instead of the comparison with the stateless call, sessions only: what a tip costs.
+           rectangle  D x D paint events through ian_session_brush
+           tip        the same events with npe_ops.round_tip(D, 0.5) through ian_session_brush_tip
+           alternating within a repeat; n defaults to 1 16 64, --out to profiles/session_tip_latency.json.  With --trace: both, one after
+           the other, for a kernel trace (the two seed kernels are different instantiations and show as two rows).
   --trace: only the first --n on the first config, sessions only: warm-up, an idle second, then --calls timed calls (for a
            rocprofv3 --kernel-trace --stats run).
 Per (config, n, path): the median over --calls calls after warm-up, repeated --repeats times (the two paths alternate within a
@@ -146,6 +151,64 @@ def run_history(arch, ns, calls, repeats, depth=16):
     return rows
 
 
+def tip_boxes(n, D, seed=0):
+    rs = np.random.RandomState(seed)
+    c1, r1 = rs.randint(0, 64 - D + 1, n), rs.randint(0, 64 - D + 1, n)
+    return np.stack([c1, r1, c1 + D, r1 + D], 1)
+
+
+def tip_pool(arch, cap, D):
+    from neural_photo_editor_amd import npe_ops as N
+    m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
+    s = m.sessions(cap)
+    s.reserve_tips(1)
+    s.set_tip(0, N.round_tip(D, 0.5))
+    return m, s
+
+
+def run_tip(arch, ns, calls, repeats, D):
+    m, s = tip_pool(arch, max(ns), D)
+    rows = []
+    for n in ns:
+        ids, boxes, levels = np.arange(n), tip_boxes(n, D), (255, 0, 0)
+        s.open(ids, np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8))
+
+        def rectangle():
+            s.paint(ids, boxes, levels)
+
+        def tip():
+            s.paint(ids, boxes, levels, tips=0)
+        res = {"rectangle": [], "tip": []}
+        for _ in range(repeats):
+            res["rectangle"].append(median_ms(rectangle, calls))
+            res["tip"].append(median_ms(tip, calls))
+        row = {"n": n, "D": D}
+        for k, v in res.items():
+            med = float(np.median(v))
+            row[k] = {"p50_ms": round(med, 4), "events_per_s": round(n * 1e3 / med, 1), "spread": round((max(v) - min(v)) / med, 4),
+                      "repeats_ms": [round(t, 4) for t in v]}
+        row["tip_over_rectangle"] = round(row["tip"]["p50_ms"] / row["rectangle"]["p50_ms"], 4)
+        row["tip_inside_rectangle_repeats"] = bool(min(res["rectangle"]) <= row["tip"]["p50_ms"] <= max(res["rectangle"]))
+        rows.append(row)
+    m.close()
+    return rows
+
+
+def trace_tip(arch, n, calls, D):
+    m, s = tip_pool(arch, n, D)
+    ids, boxes, levels = np.arange(n), tip_boxes(n, D), (255, 0, 0)
+    s.open(ids, np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8))
+    out = {"arch": arch, "n": n, "calls": calls, "D": D}
+    for name, kw in (("rectangle", {}), ("tip", {"tips": 0})):
+        for _ in range(5):
+            s.paint(ids, boxes, levels, **kw)
+        t = time.perf_counter()
+        for _ in range(calls):
+            s.paint(ids, boxes, levels, **kw)
+        out[name + "_ms_per_call"] = round((time.perf_counter() - t) * 1e3 / calls, 4)
+    return out
+
+
 def trace_run(arch, n, calls, local=False):
     m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
     s = m.sessions(n)
@@ -166,15 +229,32 @@ def trace_run(arch, n, calls, local=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None, help="one config (IAN_simple or IAN)")
-    ap.add_argument("--n", type=int, nargs="*", default=[1, 4, 16, 64])
+    ap.add_argument("--n", type=int, nargs="*", default=None, help="default 1 4 16 64; with --tip 1 16 64")
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--local", action="store_true", help="local reservation, flags 3 (user mask + dampen) on every session")
     ap.add_argument("--history", action="store_true", help="undo history: mark + paint + undo, undo alone, set_latent, paint with an unused history")
+    ap.add_argument("--tip", type=int, default=0, metavar="D", help="brush tips: D x D rectangle events against the same events with round_tip(D, 0.5)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     archs = [a.only] if a.only else ["IAN_simple", "IAN"]
+    if a.tip and not 1 <= a.tip <= 64:
+        ap.error("--tip D: a tip has 1..64 pixels a side")
+    if a.n is None:
+        a.n = [1, 16, 64] if a.tip else [1, 4, 16, 64]
+    if a.tip and a.trace:
+        print(json.dumps(trace_tip(archs[0], a.n[0], a.calls, a.tip)))
+        return
+    if a.tip:
+        res = {"metric": "session_tip_latency", "calls": a.calls, "repeats": a.repeats, "D": a.tip}
+        for arch in archs:
+            res[arch] = run_tip(arch, a.n, a.calls, a.repeats, a.tip)
+        print(json.dumps(res))
+        with open(a.out or os.path.join(ROOT, "profiles", "session_tip_latency.json"), "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+        return
     if a.trace:
         print(json.dumps(trace_run(archs[0], a.n[0], a.calls, a.local)))
         return
