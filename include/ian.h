@@ -711,6 +711,28 @@ int ian_canvas_read(ian_handle* h, int32_t canvas, uint8_t* out, int32_t wh[2], 
    only: no device state is touched. */
 int ian_canvas_placements(ian_handle* h, int32_t canvas, ian_canvas_placement* out8, int32_t* count);
 
+/* ---- edge-aware compose: the placed sessions' edit fields guided by the canvas ----
+   The compose above samples a field with the plain bilinear tap, so at scale 16 an edit bleeds over up to 16 pixels of the photo
+   along every edge.  With the table below set, the sample v of every KIND 0 placement is ian_sessions_reserve_guide's: the four
+   taps weighted by table[d_k], d_k the summed absolute byte difference between the canvas's pixel and the tap's pixel of the
+   session's GIM (the box mean of its square), one IEEE division.  The photo's pixel is the STORED canvas byte, not the running
+   acc: overlapping placements do not see each other's edits in their weights.  acc = acc + (127.5f * v) * w follows as above;
+   kind 1 placements, the feather, the order of the placements and the rounding are unchanged.  In the core of a lone placement the
+   result is byte for byte what ian_session_render gives for the crop under a guide with the same table.  The arithmetic is
+   npe_ops.canvas_compose_guided; the device matches it bit for bit.
+
+   count == 766: table (host, f32[766], every entry finite and > 0; npe_ops.guide_table(sigma)) goes to a device buffer that belongs
+   to the canvas reservation and ian_canvas_compose, ian_canvas_brush and ian_canvas_commit launch the guided kernel in place of the
+   plain one; again: the table is replaced.  count == 0 (table ignored): the buffer is freed and the compose is the plain one.
+   Synchronises the device.  The table is no session state: records, the history and ian_session_read do not know it.  Any
+   ian_sessions_reserve_canvas that succeeds frees it (a new reservation starts with the plain compose), as do
+   ian_sessions_reserve(0) and ian_destroy.  -6: no canvas reservation.  -7: any other count, a null table, a device pointer, an
+   entry that is not finite and positive (the message names it); a refused call leaves the previous table in force.  A pool that
+   never calls this launches, uploads and computes exactly what it did before. */
+int ian_sessions_reserve_edges(ian_handle* h, const float* table, int32_t count);
+/* 1 with the edge-aware compose on (its table -> table_out, host f32[766], or NULL), 0 with the plain one; -6 without canvases. */
+int ian_sessions_edges(ian_handle* h, float* table_out);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -630,6 +630,7 @@ class EditSessions:
         brush_compose(..., windows=)       the event and the windows in one submission -> (shown, out)
         canvas_commit(cid)                 the composed photo becomes the canvas, its sessions start again from it -> shown
         canvas_read(cid) / placements(cid) the stored photo / [(session, x, y, scale)]
+        reserve_canvas_guide(sigma) / canvas_guide()   edge-aware compose: every placed session's edit stops at the photo's edges
     open, open_hires and load un-place a session; commit on a placed session is refused (canvas_commit is its form).
     Brush tips (no counterpart in NPE.py, whose brush is a square): reserve_tips(count) keeps weight images of up to 64x64 per handle;
         set_tip(tip, weights) / tip(tip)   e.g. npe_ops.round_tip(diameter, hardness): a round brush with a soft edge
@@ -649,6 +650,7 @@ class EditSessions:
         self.canvases = 0               # canvas reservation: how many photos of up to canvas_max = (max_w, max_h); 0 = none
         self.canvas_max = (0, 0)
         self.feather = 0
+        self.canvas_guided = False      # edge-aware compose: the placed sessions' fields are weighted by the canvas (reserve_canvas_guide)
         self._canvas_wh = []            # per canvas (w, h) of its picture, None before canvas_put
         self._placed = {}               # session id -> (canvas id, x, y, scale)
         self.tips = 0                   # tip reservation: how many brush tips the handle keeps; 0 = none
@@ -971,7 +973,7 @@ class EditSessions:
         """Keep `count` (1..64) photos of up to max_w x max_h pixels (64..8192 each, max_w a multiple of 4) in device memory,
         3 * max_w * max_h bytes each; feather (0..16) is the width, in 64x64 field pixels, over which a placed session's edit fades
         towards the edge of its square.  0 frees them and every placement.  Needs reserve_hires first.  A second reservation starts
-        from nothing: no canvas holds a picture, no session is placed."""
+        from nothing: no canvas holds a picture, no session is placed, the compose is the plain one (reserve_canvas_guide)."""
         count, max_w, max_h, feather = int(count), int(max_w), int(max_h), int(feather)
         if not 0 <= count <= 64:
             raise ValueError("count must be in 0..64, got %d" % count)
@@ -990,6 +992,40 @@ class EditSessions:
         self.canvases, self.canvas_max, self.feather = count, ((max_w, max_h) if count else (0, 0)), (feather if count else 0)
         self._canvas_wh = [None] * count
         self._placed = {}
+        self.canvas_guided = False
+
+    def reserve_canvas_guide(self, sigma=None, table=None):
+        """Edge-aware compose: from now on compose, brush_compose and canvas_commit weight the four bilinear taps of every photo-mode
+        placement's edit field by how close the canvas's pixel is to each tap's pixel of the session's 64x64 picture
+        (npe_ops.canvas_compose_guided), so an edit no longer bleeds over the photo's edges, by up to `scale` pixels.  Exactly one of
+        sigma (levels per channel; the table is npe_ops.guide_table(sigma)) and table (766 positive float32 weights by summed absolute
+        byte difference); neither switches back to the plain compose.  Needs reserve_canvases first; a new canvas reservation
+        switches it off."""
+        from . import npe_ops
+        if sigma is not None and table is not None:
+            raise ValueError("give sigma or table, not both")
+        if sigma is None and table is None:
+            if self.canvases:
+                self._h.sessions_reserve_edges(None)
+            self.canvas_guided = False
+            return
+        self._need_canvases()
+        if sigma is not None:
+            table = npe_ops.guide_table(sigma)
+        else:
+            table = np.ascontiguousarray(np.asarray(table), np.float32)
+            if table.shape != (npe_ops.GUIDE_TABLE_LEN,):
+                raise ValueError("a guide table has %d entries, got shape %s" % (npe_ops.GUIDE_TABLE_LEN, table.shape))
+            if not (np.isfinite(table).all() and (table > 0).all()):
+                raise ValueError("every entry of a guide table is a finite positive weight")
+        self._h.sessions_reserve_edges(table)
+        self.canvas_guided = True
+
+    def canvas_guide(self):
+        """-> the float32 (766,) table of the edge-aware compose, from the library, or None while the compose is the plain one."""
+        if not self.canvases:
+            return None
+        return self._h.sessions_edges()
 
     def canvas_put(self, cid, photo):
         """The picture of canvas cid := photo, uint8 (3,h,w) (a numpy array, or a torch device tensor), 64 <= w <= max_w with w a
@@ -1029,8 +1065,9 @@ class EditSessions:
         return pack_canvas_windows(cids, origins, size, self._canvas_wh)
 
     def compose(self, cids, origins, size):
-        """Windows of the canvases with every placed session's edit on top (npe_ops.canvas_compose) -> uint8 (n,3,vh,vw).  origins
-        (n,2) or (2,) as (x, y), size (vw, vh) or one integer; x and vw multiples of 4.  The same canvas may appear several times."""
+        """Windows of the canvases with every placed session's edit on top (npe_ops.canvas_compose; after reserve_canvas_guide
+        npe_ops.canvas_compose_guided) -> uint8 (n,3,vh,vw).  origins (n,2) or (2,) as (x, y), size (vw, vh) or one integer; x and vw
+        multiples of 4.  The same canvas may appear several times."""
         win, vw, vh = self._windows(cids, origins, size)
         out = np.empty((len(win), 3, vh, vw), np.uint8)
         self._h.canvas_compose(win, vw, vh, out)
@@ -1038,7 +1075,8 @@ class EditSessions:
 
     def brush_compose(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, windows=None):
         """brush on sessions ids, and the windows = (cids, origins, size) of compose() after it, in ONE submission -> (shown, out).
-        The sessions need not be placed, the windows need not show them."""
+        The sessions need not be placed, the windows need not show them.  After reserve_canvas_guide the windows are
+        npe_ops.canvas_compose_guided's."""
         if windows is None or len(windows) != 3:
             raise ValueError("windows must be (cids, origins, size)")
         ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
@@ -1050,7 +1088,8 @@ class EditSessions:
 
     def canvas_commit(self, cid):
         """The canvas becomes its own compose, in place; the sessions placed on it open again on the box means of the new picture, where
-        they are -> IM of those sessions in ascending id, uint8 (k,3,64,64)."""
+        they are -> IM of those sessions in ascending id, uint8 (k,3,64,64).  After reserve_canvas_guide the new picture is
+        npe_ops.canvas_compose_guided of the whole canvas."""
         cid = self._canvas(cid)
         k = sum(1 for q in self._placed.values() if q[0] == cid)
         shown = np.empty((k, 3, 64, 64), np.uint8)

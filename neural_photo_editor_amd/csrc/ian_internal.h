@@ -503,6 +503,11 @@ hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, c
 // out u8 [n][3][vh][vw]; out == nullptr: n == 1 and the window is a whole picture (x = y = 0), written over the canvas itself
 hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, unsigned char* out,
                                  int n, hipStream_t s);
+// npe_ops.canvas_compose_guided of the same windows (ian_sessions_reserve_edges): table = device float[766] as for
+// launch_session_render_guided; the guide of a placed session is its own GIM, the photo is the canvas.  windows, out and out == nullptr
+// as above.
+hipError_t launch_canvas_compose_guided(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh,
+                                        unsigned char* out, int n, hipStream_t s);
 
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,

@@ -3,7 +3,8 @@
 // which declares, at its top, what the session calls need from here).  DESIGN.md 4.7; include/ian.h has the contract.
 //
 // One reservation (ian_sessions_reserve_canvas) owns everything here: `count` pictures u8[3,max_h,max_w] in one allocation, the device
-// table of CANVAS_MAX_PLACED placements per canvas, and the window table of a compose call.  The arrays are per canvas, not per
+// table of CANVAS_MAX_PLACED placements per canvas, the window table of a compose call, and the range weights of
+// ian_sessions_reserve_edges while they are set.  The arrays are per canvas, not per
 // session, so they are not columns of SESS_COLUMNS; a placement is not part of a saved session.  The host owns the placements
 // (S.placed, one entry per session id; S.ctab_shadow, the device table's copy in ascending session id per canvas); a canvas whose
 // list changed is marked dirty and its 8 entries are uploaded on the stream of the call that changed it.  A pool without the
@@ -23,8 +24,10 @@ void canvases_free(ian_handle* h) {
   if (S.canv.pix) (void)hipFree(S.canv.pix);
   if (S.canv.table) (void)hipFree(S.canv.table);
   if (S.d_cwin) (void)hipFree(S.d_cwin);
+  if (S.d_edges) (void)hipFree(S.d_edges);
   S.canv = SessionCanvases{};
   S.d_cwin = nullptr;
+  S.d_edges = nullptr;
   S.canvas_wh.clear();
   S.placed.clear();
   S.ctab_shadow.clear();
@@ -146,6 +149,20 @@ int sessions_reserve_canvas(ian_handle* h, int count, int max_w, int max_h, int 
   for (int c = 0; c < count; ++c)
     for (int k = 0; k < CANVAS_MAX_PLACED; ++k) S.ctab_shadow[((size_t)c * CANVAS_MAX_PLACED + k) * 4] = -1;
   return 0;
+}
+
+// The edge-aware compose is a setting of the canvas reservation, as the guide is one of the pool: one device table that goes with the
+// canvases (canvases_free), and while it exists canvas_compose_enqueue launches the guided kernel.  Records, history and
+// ian_session_read know nothing of it.
+int sessions_reserve_edges(ian_handle* h, const float* table, int count) {
+  const char* fn = "ian_sessions_reserve_edges";
+  if (int rc = canvas_need(h, fn)) return rc;
+  return guide_table_set(h, fn, h->sess.d_edges, table, count);
+}
+int sessions_edges(ian_handle* h, float* table_out) {
+  const char* fn = "ian_sessions_edges";
+  if (int rc = canvas_need(h, fn)) return rc;
+  return guide_table_get(h, fn, h->sess.d_edges, table_out);
 }
 
 // the three planes of a picture of w x hgt between a packed array [3][hgt][w] and a canvas's rows of max_w bytes
@@ -296,7 +313,10 @@ int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int
   S.cwin_shadow.resize((size_t)3 * n);
   memcpy(S.cwin_shadow.data(), w, (size_t)n * sizeof(ian_canvas_window));
   HIPCHK(h, hipMemcpyAsync(S.d_cwin, S.cwin_shadow.data(), (size_t)n * sizeof(ian_canvas_window), hipMemcpyHostToDevice, st));
-  HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_cwin, vw, vh, d_out, n, st));
+  if (S.d_edges)   // ian_sessions_reserve_edges: the same windows, each photo-mode field's taps weighted by the canvas
+    HIPCHK(h, launch_canvas_compose_guided(S.canv, S.arr.pool, S.d_edges, S.d_cwin, vw, vh, d_out, n, st));
+  else
+    HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_cwin, vw, vh, d_out, n, st));
   return 0;
 }
 
@@ -333,6 +353,8 @@ extern "C" {
 int ian_sessions_reserve_canvas(ian_handle* h, int32_t count, int32_t max_w, int32_t max_h, int32_t feather) {
   return h ? sessions_reserve_canvas(h, count, max_w, max_h, feather) : -1;
 }
+int ian_sessions_reserve_edges(ian_handle* h, const float* table, int32_t count) { return h ? sessions_reserve_edges(h, table, count) : -1; }
+int ian_sessions_edges(ian_handle* h, float* table_out) { return h ? sessions_edges(h, table_out) : -1; }
 int ian_canvas_put(ian_handle* h, int32_t canvas, int32_t w, int32_t hgt, const uint8_t* pixels, void* stream) {
   return h ? canvas_put(h, canvas, w, hgt, pixels, stream) : -1;
 }

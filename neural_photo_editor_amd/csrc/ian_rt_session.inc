@@ -332,16 +332,10 @@ int sessions_reserve_hires(ian_handle* h, int scale) {
   return 0;
 }
 
-// The guide is a setting of the pool, not session state: one device table beside the pool (S.d_guide, freed with the hires group), and
-// while it exists session_render_enqueue launches the guided kernel.  Records, history and ian_session_read know nothing of it.
-int sessions_reserve_guide(ian_handle* h, const float* table, int count) {
-  const char* fn = "ian_sessions_reserve_guide";
-  int rc = session_ready(h, fn);
-  if (rc) return rc;
-  auto& S = h->sess;
-  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
-  if (S.canv.pix)   // canvas_compose_kernel promises ian_session_render's bytes with the plain bilinear tap
-    return fail(h, -6, "%s: canvases are reserved: free them first (ian_sessions_reserve_canvas(0))", fn);
+// A table of range weights (ian_sessions_reserve_guide; ian_sessions_reserve_edges in ian_rt_canvas.inc): count 766 checks the host
+// table, synchronises the device and uploads it to slot, allocating the buffer the first time; (any, 0) frees it.  A refusal leaves
+// slot and its table as they were.
+int guide_table_set(ian_handle* h, const char* fn, float*& slot, const float* table, int count) {
   if (count != 0 && count != SESSION_GUIDE_TABLE_LEN) return fail(h, -7, "%s: count %d (0 frees, %d sets the table)", fn, count, SESSION_GUIDE_TABLE_LEN);
   if (count) {
     if (!table) return fail(h, -7, "%s: null table", fn);
@@ -352,11 +346,11 @@ int sessions_reserve_guide(ian_handle* h, const float* table, int count) {
   HIPCHK(h, hipDeviceSynchronize());   // pending work may still read the table that is replaced or freed
   h->last_pending = false;
   if (!count) {
-    if (S.d_guide) (void)hipFree(S.d_guide);
-    S.d_guide = nullptr;
+    if (slot) (void)hipFree(slot);
+    slot = nullptr;
     return 0;
   }
-  float* d = S.d_guide;
+  float* d = slot;
   if (!d) {
     hipError_t e = hipMalloc((void**)&d, SESSION_GUIDE_TABLE_LEN * sizeof(float));
     if (e != hipSuccess) {
@@ -365,12 +359,34 @@ int sessions_reserve_guide(ian_handle* h, const float* table, int count) {
     }
   }
   hipError_t e = hipMemcpy(d, table, SESSION_GUIDE_TABLE_LEN * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {   // a new buffer goes; an old one keeps the guide it had or has half of the new one: the error is fatal either way
-    if (!S.d_guide) (void)hipFree(d);
+  if (e != hipSuccess) {   // a new buffer goes; an old one keeps the table it had or has half of the new one: the error is fatal either way
+    if (!slot) (void)hipFree(d);
     HIPCHK(h, e);
   }
-  S.d_guide = d;
+  slot = d;
   return 0;
+}
+// 1 and the table of slot in table_out (host; may be null), or 0 without one
+int guide_table_get(ian_handle* h, const char* fn, const float* slot, float* table_out) {
+  if (!slot) return 0;
+  if (table_out) {
+    if (is_device_ptr(table_out)) return fail(h, -7, "%s: table_out must be a host array", fn);
+    HIPCHK(h, hipMemcpy(table_out, slot, SESSION_GUIDE_TABLE_LEN * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return 1;
+}
+
+// The guide is a setting of the pool, not session state: one device table beside the pool (S.d_guide, freed with the hires group), and
+// while it exists session_render_enqueue launches the guided kernel.  Records, history and ian_session_read know nothing of it.
+int sessions_reserve_guide(ian_handle* h, const float* table, int count) {
+  const char* fn = "ian_sessions_reserve_guide";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  auto& S = h->sess;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
+  if (S.canv.pix)   // canvas_compose_kernel promises ian_session_render's bytes with the plain bilinear tap
+    return fail(h, -6, "%s: canvases are reserved: free them first (ian_sessions_reserve_canvas(0))", fn);
+  return guide_table_set(h, fn, S.d_guide, table, count);
 }
 int sessions_guide(ian_handle* h, float* table_out) {
   const char* fn = "ian_sessions_guide";
@@ -378,12 +394,7 @@ int sessions_guide(ian_handle* h, float* table_out) {
   if (rc) return rc;
   auto& S = h->sess;
   if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
-  if (!S.d_guide) return 0;
-  if (table_out) {
-    if (is_device_ptr(table_out)) return fail(h, -7, "%s: table_out must be a host array", fn);
-    HIPCHK(h, hipMemcpy(table_out, S.d_guide, SESSION_GUIDE_TABLE_LEN * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  return 1;
+  return guide_table_get(h, fn, S.d_guide, table_out);
 }
 
 int sessions_set_blend(ian_handle* h, const double* gauss_half, int radius) {

@@ -357,6 +357,7 @@ struct ian_handle {
     std::vector<char> cdirty;            // per canvas: the device table lags behind ctab_shadow
     int* d_cwin = nullptr;               // per ian_canvas_compose / _brush / _commit call n ian_canvas_window records
     std::vector<int32_t> cwin_shadow;    // upload source of d_cwin
+    float* d_edges = nullptr;            // f32[766], the range weights of ian_sessions_reserve_edges; nullptr = the plain compose.  Goes with the canvases
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

@@ -14,6 +14,7 @@
 //   session_render_guided_kernel  the same window with the field's four taps weighted by the photo (ian_sessions_reserve_guide)
 //   canvas_place_kernel        canvases: the exact box mean of a square of a whole photo -> GIM, IM, encoder input (any byte alignment)
 //   canvas_compose_kernel      a window of a whole photo: the canvas plus every placed session's feathered edit field
+//   canvas_compose_guided_kernel  the same window with each photo-mode field's four taps weighted by the canvas (ian_sessions_reserve_edges)
 //   session_history_save_kernel / _move_kernel  undo history: a session's Z and UMASK rows to and from its ring of saved states
 //   session_pack_kernel / session_unpack_kernel  saved sessions: every row of a session, its ring included, to and from one record
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
@@ -898,6 +899,22 @@ __device__ __forceinline__ float canvas_ramp1(int u, int S, int f2s) {
 struct CanvasKept {
   int id, ox, oy, s, kind;
 };
+// one lane's walk of canvas cv's placement table: the placements whose squares meet rows Y0..Y1 (both inclusive) of a window at columns
+// vx .. vx + vw - 1 go to kept, in the table's order, each with the field rows the band taps inside its square -> how many
+__device__ __forceinline__ int canvas_keep_band(const SessionCanvases& C, const SessionPool& P, int cv, int vx, int vw, int Y0, int Y1,
+                                                CanvasKept* kept, FieldRows* frows) {
+  int nk = 0;
+  const int* tb = C.table + (size_t)cv * (CANVAS_MAX_PLACED * 4);
+  for (int k = 0; k < CANVAS_MAX_PLACED; ++k) {
+    const int id = tb[4 * k], ox = tb[4 * k + 1], oy = tb[4 * k + 2], s = tb[4 * k + 3];
+    if (id < 0) break;
+    const int S = 64 * s;
+    if (s < 1 || s > 16 || Y1 < oy || Y0 > oy + S - 1 || vx + vw - 1 < ox || vx > ox + S - 1) continue;
+    frows[nk] = field_rows(max(Y0, oy) - oy, min(Y1, oy + S - 1) - oy, s);   // the band's rows inside the square, in its coordinates
+    kept[nk++] = CanvasKept{id, ox, oy, s, P.kind[id]};
+  }
+  return nk;
+}
 __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ windows, int vw, int vh,
                                                              unsigned char* out) {
   __shared__ float f[CANVAS_MAX_PLACED][(RENDER_BAND + 2) * 64];
@@ -908,19 +925,7 @@ __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, 
   const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
   const int y0 = blockIdx.x * RENDER_BAND, rows = min(RENDER_BAND, vh - y0);
   const int Y0 = vy + y0, Y1 = Y0 + rows - 1;   // the band's rows on the canvas, both inclusive
-  if (threadIdx.x == 0) {
-    int nk = 0;
-    const int* tb = C.table + (size_t)cv * (CANVAS_MAX_PLACED * 4);
-    for (int k = 0; k < CANVAS_MAX_PLACED; ++k) {
-      const int id = tb[4 * k], ox = tb[4 * k + 1], oy = tb[4 * k + 2], s = tb[4 * k + 3];
-      if (id < 0) break;
-      const int S = 64 * s;
-      if (s < 1 || s > 16 || Y1 < oy || Y0 > oy + S - 1 || vx + vw - 1 < ox || vx > ox + S - 1) continue;
-      frows[nk] = field_rows(max(Y0, oy) - oy, min(Y1, oy + S - 1) - oy, s);   // the band's rows inside the square, in its coordinates
-      kept[nk++] = CanvasKept{id, ox, oy, s, P.kind[id]};
-    }
-    nkept = nk;
-  }
+  if (threadIdx.x == 0) nkept = canvas_keep_band(C, P, cv, vx, vw, Y0, Y1, kept, frows);
   __syncthreads();
   const int nk = nkept;
   for (int k = 0; k < nk; ++k) stage_field_rows(f[k], P.field + ((size_t)kept[k].id * 3 + c) * (64 * 64), frows[k]);
@@ -970,6 +975,145 @@ hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P,
     return hipErrorInvalidValue;
   if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(canvas_compose_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, C, P, windows, vw, vh, out);
+  return hipGetLastError();
+}
+
+// guided compose (npe_ops.canvas_compose_guided): canvas_compose_kernel's result with the sample of every kind 0
+// placement taken by guide_sample, the photo's pixel being the STORED canvas byte.  session_render_guided_kernel's shape, for its
+// reason (the range weights need all three channels of a pixel, once per pixel): grid (bands of CANVAS_GUIDE_BAND output rows, 1, n),
+// a lane owns 4 consecutive output pixels in all three channels: three uchar4 loads of the canvas, three uchar4 stores.  Lane 0 keeps
+// the band's placements (canvas_keep_band); per kept placement the band's field rows of the three channels and the same rows of its
+// GIM go to LDS, and the 766 range weights once if anything is kept.  A square starts at any ox while a lane's 4 pixels are aligned to
+// the window, so the inside-the-square test is per pixel, as in canvas_compose_kernel.  Kind 1 placements, canvas_ramp1 and round_u8
+// are that kernel's.  All arithmetic is float32 with contraction off, in canvas_compose_guided's order; the division is IEEE.
+// Band height: 8 placements x 3 channels x (band + 2) rows of 256 B field and 64 B GIM are 45 KB at 4 rows and 75 KB at 8, plus the
+// 3 KB table: only the 4-row band fits the 64 KB of static LDS (48.2 KB in all, three workgroups a CU), and it is the height
+// session_render_guided_kernel measured as the faster one.  So CANVAS_GUIDE_BAND = GUIDE_BAND = 4, and the rows of one placement are
+// guide_sample's arrays.
+// out == nullptr: the window is the whole picture, written over the canvas itself (commit).  A lane loads all three channels of its
+// 4 pixels before it stores any of them, it reads no other lane's canvas bytes, and FIELD, GIM and the table live elsewhere: safe in
+// place with overlapping squares; neither pointer is __restrict__.
+constexpr int CANVAS_GUIDE_BAND = GUIDE_BAND;
+// hires_guide_field's v of the three channels at square coordinate u of the output row whose two tapped rows start at o0 and o1 of the
+// staged rows (weight ty): f the field rows, g the same rows of GIM, tab the range weights, all in LDS; p0..p2 the photo's pixel.
+// session_render_guided_kernel's expression, statement for statement; that kernel keeps its own text, because calling this function
+// from it changes the code it compiles to.
+using GuideFieldRows = float[3][(GUIDE_BAND + 2) * 64];
+using GuideGimRows = unsigned char[3][(GUIDE_BAND + 2) * 64];
+__device__ __forceinline__ void guide_sample(const GuideFieldRows& f, const GuideGimRows& g, const float* tab, int o0, int o1, int s, int u,
+                                             float ty, int p0, int p1, int p2, float v[3]) {
+  int c0, c1;
+  float tx;
+  hires_taps(u, s, c0, c1, tx);
+  const float wy0 = 1.0f - ty, wx0 = 1.0f - tx;
+  const int at[4] = {o0 + c0, o0 + c1, o1 + c0, o1 + c1};
+  const float sw[4] = {wy0 * wx0, wy0 * tx, ty * wx0, ty * tx};
+  float w[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int d = abs(p0 - (int)g[0][at[k]]) + abs(p1 - (int)g[1][at[k]]) + abs(p2 - (int)g[2][at[k]]);
+    w[k] = sw[k] * tab[d];
+  }
+  const float den = ((w[0] + w[1]) + w[2]) + w[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float num = ((w[0] * f[c][at[0]] + w[1] * f[c][at[1]]) + w[2] * f[c][at[2]]) + w[3] * f[c][at[3]];
+    v[c] = num / den;
+  }
+}
+// the rows fr of a session's GIM, as bytes, beside its staged field rows: all 256 lanes, 16 words a row
+__device__ __forceinline__ void stage_gim_rows(unsigned char* g, const unsigned char* plane, const FieldRows r) {
+  const unsigned* grow = reinterpret_cast<const unsigned*>(plane + r.fr0 * 64);
+  unsigned* gl = reinterpret_cast<unsigned*>(g);
+  for (int j = threadIdx.x; j < r.n * 16; j += 256) gl[j] = grow[j];
+}
+__global__ __launch_bounds__(256) void canvas_compose_guided_kernel(SessionCanvases C, SessionPool P, const float* __restrict__ table,
+                                                                    const int* __restrict__ windows, int vw, int vh, unsigned char* out) {
+  __shared__ GuideFieldRows f[CANVAS_MAX_PLACED];
+  __shared__ __align__(4) GuideGimRows g[CANVAS_MAX_PLACED];
+  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
+  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
+  __shared__ FieldRows frows[CANVAS_MAX_PLACED];
+  __shared__ int nkept;
+  const int i = blockIdx.z;
+  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
+  const int y0 = blockIdx.x * CANVAS_GUIDE_BAND, rows = min(CANVAS_GUIDE_BAND, vh - y0);
+  const int Y0 = vy + y0, Y1 = Y0 + rows - 1;
+  if (threadIdx.x == 0) {
+    const int nk = canvas_keep_band(C, P, cv, vx, vw, Y0, Y1, kept, frows);
+    for (int k = 0; k < nk; ++k) frows[k].n = min(frows[k].n, CANVAS_GUIDE_BAND + 2);   // 4 output rows tap at most 5 field rows
+    nkept = nk;
+  }
+  __syncthreads();
+  const int nk = nkept;
+  for (int k = 0; k < nk; ++k)
+    for (int c = 0; c < 3; ++c) {
+      stage_field_rows(f[k][c], P.field + ((size_t)kept[k].id * 3 + c) * (64 * 64), frows[k]);
+      stage_gim_rows(g[k][c], P.gim + ((size_t)kept[k].id * 3 + c) * (64 * 64), frows[k]);
+    }
+  if (nk)
+    for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
+  __syncthreads();
+  const size_t cplane = (size_t)C.max_h * C.max_w, dplane = out ? (size_t)vh * vw : cplane;
+  const unsigned char* src = C.pix + (size_t)cv * 3 * cplane;
+  unsigned char* dst = out ? out + (size_t)i * 3 * dplane : C.pix + (size_t)cv * 3 * cplane;
+  const int dstride = out ? vw : C.max_w;
+  const int L = vw >> 2;
+  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
+    const int ry = idx / L, cx = (idx - ry * L) * 4;
+    const int Y = Y0 + ry, X = vx + cx;
+    int pb[3][4];
+    float acc[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * cplane + (size_t)Y * C.max_w + X);
+      pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[c][e] = (float)pb[c][e];
+    }
+    for (int k = 0; k < nk; ++k) {
+      const CanvasKept q = kept[k];
+      const int S = 64 * q.s, uy = Y - q.oy;
+      if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
+      const int f2s = 2 * C.feather * q.s, fr0 = frows[k].fr0;
+      int r0, r1;
+      float ty;
+      hires_taps(uy, q.s, r0, r1, ty);
+      const int o0 = (r0 - fr0) * 64, o1 = (r1 - fr0) * 64;
+      const float wy = canvas_ramp1(uy, S, f2s);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ux = X + e - q.ox;
+        if (ux < 0 || ux >= S) continue;
+        const float w = wy * canvas_ramp1(ux, S, f2s);
+        if (q.kind == 0) {
+          float v[3];
+          guide_sample(f[k], g[k], tab, o0, o1, q.s, ux, ty, pb[0][e], pb[1][e], pb[2][e], v);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c][e] = acc[c][e] + (127.5f * v[c]) * w;
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float tv = 127.5f * (field_bilinear(f[k][c] + o0, f[k][c] + o1, q.s, ux, ty) + 1.0f);
+            acc[c][e] = w == 1.0f ? tv : acc[c][e] + (tv - acc[c][e]) * w;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<uchar4*>(dst + c * dplane + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) =
+          make_uchar4(round_u8(acc[c][0]), round_u8(acc[c][1]), round_u8(acc[c][2]), round_u8(acc[c][3]));
+  }
+}
+hipError_t launch_canvas_compose_guided(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh,
+                                        unsigned char* out, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || !canvases_ok(C) || !P.field || !P.kind || !P.gim || !table || !windows || vw < 4 || (vw & 3) || vh < 1 ||
+      vw > C.max_w || vh > C.max_h)
+    return hipErrorInvalidValue;
+  if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(canvas_compose_guided_kernel, dim3((vh + CANVAS_GUIDE_BAND - 1) / CANVAS_GUIDE_BAND, 1, n), dim3(256), 0, s, C, P, table,
+                     windows, vw, vh, out);
   return hipGetLastError();
 }
 

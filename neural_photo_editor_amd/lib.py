@@ -54,6 +54,7 @@ EXPORTS = (
     "ian_session_record_info", "ian_session_save", "ian_session_load",
     "ian_sessions_reserve_canvas", "ian_canvas_put", "ian_canvas_place", "ian_canvas_compose", "ian_canvas_brush", "ian_canvas_commit",
     "ian_canvas_read", "ian_canvas_placements",
+    "ian_sessions_reserve_edges", "ian_sessions_edges",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -151,6 +152,8 @@ def load_library():
     lib.ian_canvas_commit.argtypes = [vp, i32, fp, vp]
     lib.ian_canvas_read.argtypes = [vp, i32, fp, fp, vp]
     lib.ian_canvas_placements.argtypes = [vp, i32, C.POINTER(CanvasPlacement), fp]
+    lib.ian_sessions_reserve_edges.argtypes = [vp, fp, i32]
+    lib.ian_sessions_edges.argtypes = [vp, fp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -570,6 +573,24 @@ class Handle:
     # ---- canvases (ian_sessions_reserve_canvas, ian_canvas_*) ----
     def sessions_reserve_canvas(self, count, max_w=0, max_h=0, feather=0):
         self._check(self.lib.ian_sessions_reserve_canvas(self._h, int(count), int(max_w), int(max_h), int(feather)))
+
+    def sessions_reserve_edges(self, table=None):
+        """ian_sessions_reserve_edges; table = 766 float32 range weights (npe_ops.guide_table), or None for the plain compose."""
+        if table is None:
+            self._check(self.lib.ian_sessions_reserve_edges(self._h, C.c_void_p(0), 0))
+            return
+        t = np.ascontiguousarray(table, np.float32)
+        if t.ndim != 1:
+            raise ValueError("the guide table is one-dimensional, got shape %s" % (t.shape,))
+        self._check(self.lib.ian_sessions_reserve_edges(self._h, _ptr(t), t.shape[0]))
+
+    def sessions_edges(self):
+        """ian_sessions_edges -> the float32[766] table of the edge-aware compose, or None without one."""
+        t = np.empty(766, np.float32)
+        rc = self.lib.ian_sessions_edges(self._h, _ptr(t))
+        if rc < 0:
+            self._check(rc)
+        return t if rc == 1 else None
 
     def canvas_put(self, canvas, pixels, stream=None):
         """ian_canvas_put; pixels u8[3,hgt,w], a contiguous numpy array or a device tensor."""

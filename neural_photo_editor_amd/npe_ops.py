@@ -307,15 +307,8 @@ def canvas_ramp(s, f, lo, cnt):
     return np.minimum(np.float32(1.0), np.float32(2 * d + 1) / np.float32(2 * f * s))
 
 
-def canvas_compose(canvas, placed, f, vx, vy, vw, vh):
-    """Window (vx, vy, vw, vh) of a canvas with its placed sessions' edits on top -> uint8 (3, vh, vw).  placed = [(ox, oy, s, FIELD,
-    kind), ...] in ascending session id; FIELD float32 (3,64,64) and kind as ian_session_read gives them.  Per pixel and channel
-    acc = float32(canvas byte); then, for every placement whose square covers the pixel, in list order: v = the bilinear sample of
-    FIELD at square coordinates (X-ox, Y-oy) with hires_render's expressions in hires_render's order, w = ry * rx (canvas_ramp), and
-      kind 0:  acc = acc + (127.5f*v)*w
-      kind 1:  t = 127.5f*(v + 1.0f);  acc = t where w == 1.0f, elsewhere acc = acc + (t - acc)*w
-    out = uint8(clip(rint(acc), 0, 255)), ties to even.  Zero fields return the canvas bytes; in the core of a lone placement
-    (w == 1) the result is hires_render(crop, FIELD, kind, s, ...) byte for byte."""
+def _canvas_compose(canvas, placed, f, vx, vy, vw, vh, table):
+    """The body of canvas_compose (table None; placements of 5 entries) and canvas_compose_guided (placements of 6, GIM last)."""
     canvas = np.asarray(canvas)
     if canvas.dtype != np.uint8 or canvas.ndim != 3 or canvas.shape[0] != 3:
         raise ValueError("a canvas is uint8 (3,H,W), got %s %s" % (canvas.dtype, canvas.shape))
@@ -326,7 +319,9 @@ def canvas_compose(canvas, placed, f, vx, vy, vw, vh):
     if len(placed) > CANVAS_MAX_PLACED:
         raise ValueError("a canvas holds at most %d placements, got %d" % (CANVAS_MAX_PLACED, len(placed)))
     acc = np.float32(canvas[:, vy:vy + vh, vx:vx + vw])
-    for (ox, oy, s, field, kind) in placed:
+    for (ox, oy, s, field, kind, *gim) in placed:
+        if len(gim) != (table is not None):
+            raise ValueError("a placement is (ox, oy, s, FIELD, kind%s)" % ("" if table is None else ", GIM"))
         _, ox, oy, s = _canvas_square(canvas, ox, oy, s)
         if kind not in (0, 1):
             raise ValueError("kind must be 0 (photo plus field) or 1 (plain sample), got %r" % (kind,))
@@ -335,12 +330,15 @@ def canvas_compose(canvas, placed, f, vx, vy, vw, vh):
         if x0 >= x1 or y0 >= y1:
             continue
         F = np.asarray(field, np.float32)
-        c0, c1, tx = hires_axis_taps(s, x0 - ox, x1 - x0)
-        r0, r1, ty = hires_axis_taps(s, y0 - oy, y1 - y0)
-        A = F[:, :, c0]
-        rows = A + tx * (F[:, :, c1] - A)
-        top = rows[:, r0]
-        v = top + ty[None, :, None] * (rows[:, r1] - top)
+        if table is not None and kind == 0:      # the photo is the stored canvas, never the running acc
+            v = hires_guide_field(canvas[:, oy:oy + S, ox:ox + S], gim[0], F, s, x0 - ox, y0 - oy, x1 - x0, y1 - y0, table)
+        else:
+            c0, c1, tx = hires_axis_taps(s, x0 - ox, x1 - x0)
+            r0, r1, ty = hires_axis_taps(s, y0 - oy, y1 - y0)
+            A = F[:, :, c0]
+            rows = A + tx * (F[:, :, c1] - A)
+            top = rows[:, r0]
+            v = top + ty[None, :, None] * (rows[:, r1] - top)
         w = canvas_ramp(s, f, y0 - oy, y1 - y0)[:, None] * canvas_ramp(s, f, x0 - ox, x1 - x0)[None, :]
         part = acc[:, y0 - vy:y1 - vy, x0 - vx:x1 - vx]
         if kind == 0:
@@ -351,6 +349,33 @@ def canvas_compose(canvas, placed, f, vx, vy, vw, vh):
         assert new.dtype == np.float32 and w.dtype == np.float32
         acc[:, y0 - vy:y1 - vy, x0 - vx:x1 - vx] = new
     return np.uint8(np.clip(np.rint(acc), 0, 255))
+
+
+def canvas_compose(canvas, placed, f, vx, vy, vw, vh):
+    """Window (vx, vy, vw, vh) of a canvas with its placed sessions' edits on top -> uint8 (3, vh, vw).  placed = [(ox, oy, s, FIELD,
+    kind), ...] in ascending session id; FIELD float32 (3,64,64) and kind as ian_session_read gives them.  Per pixel and channel
+    acc = float32(canvas byte); then, for every placement whose square covers the pixel, in list order: v = the bilinear sample of
+    FIELD at square coordinates (X-ox, Y-oy) with hires_render's expressions in hires_render's order, w = ry * rx (canvas_ramp), and
+      kind 0:  acc = acc + (127.5f*v)*w
+      kind 1:  t = 127.5f*(v + 1.0f);  acc = t where w == 1.0f, elsewhere acc = acc + (t - acc)*w
+    out = uint8(clip(rint(acc), 0, 255)), ties to even.  Zero fields return the canvas bytes; in the core of a lone placement
+    (w == 1) the result is hires_render(crop, FIELD, kind, s, ...) byte for byte."""
+    return _canvas_compose(canvas, placed, f, vx, vy, vw, vh, None)
+
+
+def canvas_compose_guided(canvas, placed, f, vx, vy, vw, vh, table):
+    """canvas_compose with the edit field guided by the photo (ian_sessions_reserve_edges) -> uint8 (3, vh, vw).
+    placed = [(ox, oy, s, FIELD, kind, GIM), ...] in ascending session id, GIM uint8 (3,64,64) as ian_session_read gives it (the box
+    mean of the square, canvas_crop_mean); table = guide_table(sigma).  The one change: for a kind 0 placement the sample v at square
+    coordinates (X-ox, Y-oy) is hires_guide_field's v, with the STORED canvas byte as the photo's pixel (not the running acc, so
+    overlapping placements do not see each other's edits in their range weights); then acc = acc + (127.5f*v)*w as in canvas_compose.
+    Kind 1 placements, the feather, the order of the placements and the rounding are canvas_compose's.  Zero fields return the canvas
+    bytes; in the core of a lone kind 0 placement (w == 1) the result is hires_render_guided(crop, GIM, FIELD, 0, s, ...) byte for
+    byte."""
+    table = np.asarray(table)
+    if table.dtype != np.float32 or table.shape != (GUIDE_TABLE_LEN,):
+        raise ValueError("a guide table is float32 (%d,), got %s %s" % (GUIDE_TABLE_LEN, table.dtype, table.shape))
+    return _canvas_compose(canvas, placed, f, vx, vy, vw, vh, table)
 
 
 # ---- local edits (ian_sessions_reserve_local / ian_session_local, include/ian.h; DESIGN.md 4.4) -------------------------------------

@@ -9,7 +9,11 @@ one painted: kind 0 with a non-zero field), for a 256 x 256 window inside the sq
 The one comparison with something older (`against_render`): one placement at scale 16 and feather 0 composed over a 1024 x 1024 window,
 against ian_session_render of a 1024 x 1024 picture (scale 16) in the same run, both into device buffers, alternating: the two move
 the same bytes.
-usage (GPU box): python scripts/canvas_latency.py [--calls 200] [--repeats 3] [--out FILE]
+--guided measures the edge-aware compose (ian_sessions_reserve_edges) instead: the same four rows, device buffers only,
+plain and guided compose alternating per repeat in one run (the table is switched between the bursts, outside the timing), the
+ratio guided / plain per row; and the comparison above with the guide on both sides: the guided compose of the scale-16 placement
+against ian_session_render under ian_sessions_reserve_guide with the same table on a second pool (a pool has a guide or canvases).
+usage (GPU box): python scripts/canvas_latency.py [--guided] [--calls 200] [--repeats 3] [--out FILE]
 Medians over --calls calls after warm-up, repeated --repeats times; reported are the median of the repeats and their spread
 (max - min) / median.  Prints one JSON line and, with --out, writes it there."""
 import argparse
@@ -118,16 +122,80 @@ def run(arch, calls, repeats):
     return rows, against
 
 
+def run_guided(arch, calls, repeats, sigma=8.0):
+    import torch
+    from neural_photo_editor_amd import npe_ops
+    cfg = os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py")
+    m = IAN(cfg, True, params=O.make_params(arch, 1))
+    s = m.sessions(16)
+    s.reserve_hires(16)
+    table = npe_ops.guide_table(sigma)
+    rs = np.random.RandomState(0)
+    photo = rs.randint(0, 256, (3, CH, CW)).astype(np.uint8)
+    s.reserve_canvases(1, CW, CH, 4)
+
+    def alternate(win, vw, vh, d_out, also=None):
+        plain, guided, other = [], [], []
+        for _ in range(repeats):                                            # alternating: all see the same machine
+            s.reserve_canvas_guide()
+            plain += device_us(lambda: m.handle.canvas_compose(win, vw, vh, d_out), calls, 1)
+            s.reserve_canvas_guide(table=table)
+            guided += device_us(lambda: m.handle.canvas_compose(win, vw, vh, d_out), calls, 1)
+            if also:
+                other += device_us(also, calls, 1)
+        return plain, guided, other
+
+    rows = []
+    for placed in (1, 8):
+        s.canvas_put(0, photo)
+        ids = np.arange(placed)
+        s.place(ids, 0, [(301 + 200 * k, 403 + 40 * k) for k in range(placed)], 4)
+        s.paint(ids, (20, 20, 44, 44), (255, 0, 0))
+        for (vw, vh, origin) in ((256, 256, (400, 450)), (CW, CH, (0, 0))):
+            win, _, _ = api.pack_canvas_windows([0], origin, (vw, vh), [(CW, CH)])
+            d_out = torch.empty((1, 3, vh, vw), dtype=torch.uint8, device="cuda")
+            plain, guided, _ = alternate(win, vw, vh, d_out)
+            row = {"placed": placed, "window": [vw, vh], "device_bytes": compose_bytes(1, vw, vh), "plain_device": stat(plain),
+                   "guided_device": stat(guided)}
+            row["guided_over_plain"] = round(row["guided_device"]["p50_us"] / row["plain_device"]["p50_us"], 3)
+            rows.append(row)
+    # one placement at scale 16, feather 0, a 1024 x 1024 window: plain and guided compose, and the guided render of a second pool
+    s.reserve_canvases(1, CW, CH, 0)
+    s.canvas_put(0, photo)
+    s.place([0], 0, (512, 256), 16)
+    s.paint([0], (20, 20, 44, 44), (255, 0, 0))
+    m2 = IAN(cfg, True, params=O.make_params(arch, 1))
+    r = m2.sessions(16)
+    r.reserve_hires(16)
+    r.reserve_guide(table=table)
+    r.open_hires([1], np.ascontiguousarray(photo[None, :, 256:1280, 512:1536]))
+    r.paint([1], (20, 20, 44, 44), (255, 0, 0))
+    win, _, _ = api.pack_canvas_windows([0], (512, 256), 1024, [(CW, CH)])
+    views, _, _ = api.pack_session_views([1], (0, 0), 1024, 16)
+    d_out = torch.empty((1, 3, 1024, 1024), dtype=torch.uint8, device="cuda")
+    d_ref = torch.empty((1, 3, 1024, 1024), dtype=torch.uint8, device="cuda")
+    plain, guided, rend = alternate(win, 1024, 1024, d_out, lambda: m2.handle.session_render(views, 1024, 1024, d_ref))
+    # the last bursts left the guided compose in d_out and the guided render in d_ref: the same bytes, so the same work
+    against = {"window": [1024, 1024], "device_bytes": compose_bytes(1, 1024, 1024), "plain_device": stat(plain),
+               "guided_device": stat(guided), "render_guided_device": stat(rend), "same_bytes": bool(torch.equal(d_out, d_ref))}
+    against["guided_over_plain"] = round(against["guided_device"]["p50_us"] / against["plain_device"]["p50_us"], 3)
+    against["guided_compose_over_guided_render"] = round(against["guided_device"]["p50_us"] / against["render_guided_device"]["p50_us"], 3)
+    m.close()
+    m2.close()
+    return rows, against
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="IAN_simple")
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--guided", action="store_true", help="the edge-aware compose against the plain one (DESIGN.md 4.13)")
     a = ap.parse_args()
-    rows, against = run(a.arch, a.calls, a.repeats)
-    res = {"metric": "canvas_latency", "arch": a.arch, "canvas": [CW, CH], "calls": a.calls, "repeats": a.repeats, "rows": rows,
-           "against_render": against}
+    rows, against = (run_guided if a.guided else run)(a.arch, a.calls, a.repeats)
+    res = {"metric": "canvas_guided_latency" if a.guided else "canvas_latency", "arch": a.arch, "canvas": [CW, CH], "calls": a.calls,
+           "repeats": a.repeats, "rows": rows, "against_render": against}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as fh:
