@@ -24,6 +24,7 @@
 namespace {
 
 constexpr size_t SESS_IMG = 3 * 64 * 64;
+constexpr size_t EDIT_TABLE_FLOOR = (size_t)BATCH_MAX * 12;   // words: the table of BATCH_MAX one-step events with tips (ian_edit_plan.h); d_stab never has less
 constexpr int SESS_MAX_CAPACITY = 1 << 20;
 size_t sess_src_bytes(int scale) { return 3 * (size_t)(64 * scale) * (size_t)(64 * scale); }
 
@@ -63,14 +64,14 @@ struct SessScratchBuf {
   SessGroup group;
 };
 const SessScratchBuf SESS_SCRATCH[] = {
-    {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 12 * sizeof(int32_t), SESS_BASE},
+    {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 6 * sizeof(int32_t), SESS_BASE},
     {offsetof(SessionScratch, d_photo), 0, SESS_BASE},
     {offsetof(SessionScratch, d_shown), (size_t)BATCH_MAX * SESS_IMG, SESS_BASE},
     {offsetof(SessionScratch, d_rtab), 0, SESS_BASE},
     {offsetof(SessionScratch, d_stage), 0, SESS_BASE},
     {offsetof(SessionScratch, d_fit), 0, SESS_BASE},
     {offsetof(SessionScratch, d_fit_loss), 0, SESS_BASE},
-    {offsetof(SessionScratch, d_stab), 0, SESS_BASE},
+    {offsetof(SessionScratch, d_stab), EDIT_TABLE_FLOOR * sizeof(int32_t), SESS_BASE},   // grown on demand beyond that (stab_cap)
     {offsetof(SessionScratch, d_tanh), 256 * sizeof(float), SESS_BASE},   // last of its group: a failed build never leaves it without its upload
     {offsetof(SessionScratch, d_views), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HIRES},
     {offsetof(SessionScratch, d_out), 0, SESS_HIRES},
@@ -284,6 +285,7 @@ int sessions_reserve(ian_handle* h, int capacity) {
   }
   const bool had_table = S.d_tanh != nullptr;   // the table is uploaded once, when its buffer is new
   HIPCHK(h, scratch_build(S, SESS_BASE));
+  S.stab_cap = std::max(S.stab_cap, EDIT_TABLE_FLOOR);   // a d_stab this call built has the floor, one a stroke grew keeps its size
   if (!had_table) {
     float tab[256];
     session_tanh_table(tab);
@@ -982,22 +984,23 @@ int session_tip_rect(ian_handle* h, const char* fn, int item, int point, int tip
   return fail(h, -7, "%s: %s: patch (%d,%d,%d,%d) is not the %d x %d of tip %d", fn, where, c1, r1, c2, r2, S.tip_wh[2 * tip], S.tip_wh[2 * tip + 1], tip);
 }
 
-// The table of a brush or a fit in d_tab: n ian_brush_item rows of 7 words (what the shared middle reads), then the n session ids,
-// then, for a brush, the n colours of 3 floats, then, for a brush with tips, the n tip indices.  fill(i, row, id, colour) writes item
-// i into the zeroed shadow (colour: nullptr without colours); one copy up; -> the parts on the device.
-struct BrushTable { const int* items; const int* ids; const float* colour; const int* tipsel; };
-template <typename Fill>
-int brush_table_upload(ian_handle* h, int n, bool colours, const int32_t* tips, hipStream_t st, BrushTable* T, Fill fill) {
+// The table of a brush, clone, stroke or fit call (EditTable, ian_edit_plan.h) starts here: d_stab holds L.words (it only grows, from
+// the EDIT_TABLE_FLOOR it is reserved with: only a stroke of many points ever allocates), *t is its zeroed shadow with the tip indices in
+// place.  The caller fills ids, seed words and item rows and, after session_enter, copies L.words up from the shadow.
+int edit_table_begin(ian_handle* h, const EditTable& L, int n, const int32_t* tips, int32_t** t) {
   auto& S = h->sess;
-  const size_t words = (size_t)(colours ? (tips ? 12 : 11) : 8) * n;
-  S.tab_shadow.assign(words, 0);
-  int32_t* t = S.tab_shadow.data();
-  for (int i = 0; i < n; ++i) fill(i, t + (size_t)7 * i, t + (size_t)7 * n + i, colours ? t + (size_t)8 * n + (size_t)3 * i : nullptr);
-  if (tips) memcpy(t + (size_t)11 * n, tips, (size_t)n * sizeof(int32_t));
-  HIPCHK(h, hipMemcpyAsync(S.d_tab, t, words * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  *T = BrushTable{S.d_tab, S.d_tab + (size_t)7 * n, colours ? reinterpret_cast<const float*>(S.d_tab + (size_t)8 * n) : nullptr,
-                  tips ? S.d_tab + (size_t)11 * n : nullptr};
+  int rc = grow_dev(h, &S.d_stab, &S.stab_cap, L.words);
+  if (rc) return rc;
+  S.stab_shadow.assign(L.words, 0);
+  *t = S.stab_shadow.data();
+  if (L.has_tips) memcpy(*t + L.tips, tips, (size_t)n * sizeof(int32_t));
   return 0;
+}
+// one item row: ian_brush_item's layout
+void edit_row(int32_t* row, int c1, int r1, int c2, int r2, int kind, float coef, float gscale) {
+  row[0] = c1; row[1] = r1; row[2] = c2; row[3] = r2; row[4] = kind;
+  memcpy(row + 5, &coef, sizeof(float));
+  memcpy(row + 6, &gscale, sizeof(float));
 }
 // The residency of ian_session_brush / ian_session_stroke: the decoder's activations belong to sessions ids[i * stride], in that order, at
 // their current latent versions.  hit: a call on exactly these may skip its gather and forward (IAN_NO_DEC_CACHE switches that off);
@@ -1028,7 +1031,88 @@ struct BrushWindows {
   int count, vw, vh;
   uint8_t* out;
 };
-// tipped: ian_session_brush_tip, the same call with one tip index per event (tips); item i with tips[i] >= 0 weights its loss by that tip
+// A brush, clone or stroke call after its checks, its table filled in the shadow (edit_table_begin): everything it enqueues.
+struct EditCall {
+  const int32_t* ids; int stride;   // the sessions, ids[i * stride]
+  EditPlan plan;
+  EditTable tab;
+  bool clone;                   // the seed words are SEED_CLONE's (source id, field selector, shift), not colours
+  const int32_t* modes;         // strokes: modes[i * stride], the footprints of all their points go into UMASK first; nullptr: the blend's one will do
+  const SessionHistory* next;   // strokes with bit 0 of flags: the histories after the mark; nullptr: no mark
+  BrushWindows W;               // brushes only
+};
+EditCall edit_call(const int32_t* ids, int stride, const EditPlan& plan, bool tips, bool clone = false, const int32_t* modes = nullptr,
+                   const SessionHistory* next = nullptr, const BrushWindows& W = BrushWindows{}) {
+  return EditCall{ids, stride, plan, edit_table(plan, next != nullptr, tips), clone, modes, next, W};
+}
+// The pass loop of DESIGN.md 4.2.  Per pass of at most opt.brush_pass items: gather Z and one forward (neither when the residency hits),
+// [the footprints,] and per step the shared middle -- seed, backward, update, forward at z_new, which IS the next step's forward while
+// the same items go on -- then the stored blend of the items that end here (an earlier blend would be overwritten) and, when some are
+// left, the forward again at their batch: per-event calls would miss their residency there, and the decoder's kernels may differ with it.
+int edit_passes(ian_handle* h, const EditCall& C, uint8_t* shown, void* stream) {
+  auto& S = h->sess;
+  const EditPlan& P = C.plan; const EditTable& L = C.tab; const BrushWindows& W = C.W;
+  const int n = P.n, pass = h->opt.brush_pass;
+  int rc;
+  ResultTarget win = {};
+  const size_t win_bytes = (size_t)W.count * 3 * (size_t)W.vh * (size_t)W.vw;
+  if (W.kind != W.NONE && (rc = session_render_target(h, W.out, win_bytes, &win))) return rc;
+  const bool hit = n <= pass && session_residency_hit(S, n, C.ids, C.stride);
+  hipStream_t st = (hipStream_t)stream;
+  session_enter(h, st);   // also ends the residency: re-armed below
+  TotalTimer tt(h, st);
+  HIPCHK(h, hipMemcpyAsync(S.d_stab, S.stab_shadow.data(), L.words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int* d = S.d_stab;
+  if (C.next) HIPCHK(h, launch_session_history_save(S.arr.pool, S.arr.rings, d + L.ids, d + L.save, n, st));
+  BrushSeedSrc seed0;   // what every step's seed has in common
+  if (C.clone) { seed0.gim = S.arr.pool.gim; seed0.im = S.arr.pool.im; seed0.recon = S.arr.pool.recon; seed0.tanh_tab = S.d_tanh; }
+  if (L.has_tips) seed0.tips = S.d_tips;
+  Slot& zs = h->slots[h->desc.z_slot];
+  const ResultTarget sh = shown_target(h, shown, true);
+  for (int off = 0; off < n; off += pass) {
+    const int nc = std::min(pass, n - off);
+    if (!hit) {
+      if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
+      HIPCHK(h, launch_session_gather_z(S.arr.pool, d + L.ids + off, zs.d, zs.cs, nc, st));
+      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
+    }
+    bool footprints = false;   // what the kernel would find on the device, as far as the host knows it: the mode flag it does not
+    for (int i = off; C.modes && S.arr.pool.umask && !footprints && i < off + nc; ++i)
+      footprints = C.modes[(size_t)i * C.stride] == 1 && (S.local_flags[C.ids[(size_t)i * C.stride]] & 1);
+    if (footprints) HIPCHK(h, launch_session_stroke_umask(S.arr.pool, d + L.ids, d + L.items, d + L.rows, P.count(off), off, S.d_falloff, nc, st));
+    rc = edit_pass_steps(P, off, nc, [&](const EditStep& s) -> int {
+      BrushSeedSrc seed = seed0;
+      seed.table = d + L.items + (size_t)EDIT_ROW_WORDS * s.row;
+      const int* words = d + L.seed + (size_t)3 * off;
+      if (C.clone) seed.clone = words;
+      else seed.colour = reinterpret_cast<const float*>(words);
+      if (L.has_tips) seed.tipsel = d + L.tips + off;   // the items of a step are a prefix of the pass: so are their tips
+      if (int e = brush_pass_middle(h, s.act, seed, true, st)) return e;
+      if (s.keep == s.act) return 0;   // the same items go on: the activations at z_new are the next step's
+      SessionBlendArgs a = session_blend_args(h, d + L.ids + off + s.keep, seed.table + (size_t)EDIT_ROW_WORDS * s.keep,
+                                              sh.dev + (size_t)(off + s.keep) * SESS_IMG, 1);
+      a.xhat += (size_t)s.keep * SESS_IMG; a.zslot += (size_t)s.keep * zs.cs;
+      HIPCHK(h, launch_session_blend(a, s.act - s.keep, st));
+      return s.keep > 0 ? batch_forward(h, nullptr, s.keep, st) : 0;
+    });
+    if (rc) return rc;
+  }
+  h->slot_stale[h->desc.out_slot] = 0;
+  // One note per session where per-event calls make one per step: the version is only ever compared for equality, and
+  // session_history_edited is idempotent (DESIGN.md 4.9).  The marked histories move only now, after every enqueue succeeded.
+  for (int i = 0; i < n; ++i) {
+    const int id = C.ids[(size_t)i * C.stride];
+    if (C.next) S.hist[id] = C.next[i];
+    session_latent_written(S, id, false);
+  }
+  if (W.kind == W.VIEWS && (rc = session_render_enqueue(h, W.count, W.views, W.vw, W.vh, win.dev, st))) return rc;
+  if (W.kind == W.CANVAS && (rc = canvas_compose_enqueue(h, W.count, W.windows, W.vw, W.vh, win.dev, st))) return rc;
+  if ((rc = session_finish(h, n, sh, false, st, win, win_bytes))) return rc;
+  if (edit_plan_resident(P, pass)) session_residency_arm(S, n, C.ids, C.stride);
+  return 0;
+}
+
+// ian_session_brush and its forms: a stroke whose counts are all 1.  tipped: ian_session_brush_tip, one tip index per event (tips)
 int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream, const BrushWindows& W,
                   bool tipped = false, const int32_t* tips = nullptr) {
   const char* fn = tipped ? "ian_session_brush_tip"
@@ -1042,66 +1126,26 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
     if ((rc = check_rect(h, fn, i, e.c1, e.r1, e.c2, e.r2, "patch"))) return rc;
   }
   if ((rc = session_local_check(h, fn, n, &ev->session, 11))) return rc;
-  auto& S = h->sess;
-  if (tipped) {
-    if ((rc = session_tips_arg(h, fn, tips))) return rc;
-    for (int i = 0; i < n; ++i)
-      if ((rc = session_tip_rect(h, fn, i, -1, tips[i], ev[i].c1, ev[i].r1, ev[i].c2, ev[i].r2))) return rc;
-  } else {
-    tips = nullptr;
-  }
+  if (tipped && (rc = session_tips_arg(h, fn, tips))) return rc;
+  for (int i = 0; tipped && i < n; ++i)
+    if ((rc = session_tip_rect(h, fn, i, -1, tips[i], ev[i].c1, ev[i].r1, ev[i].c2, ev[i].r2))) return rc;
   if (W.kind == W.VIEWS && (rc = session_view_check(h, fn, W.count, W.views, W.vw, W.vh, W.out, ev))) return rc;
   if (W.kind == W.CANVAS && (rc = canvas_window_check(h, fn, W.count, W.windows, W.vw, W.vh, W.out))) return rc;
-  ResultTarget win = {};
-  const size_t win_bytes = (size_t)W.count * 3 * (size_t)W.vh * (size_t)W.vw;
-  if (W.kind != W.NONE && (rc = session_render_target(h, W.out, win_bytes, &win))) return rc;
-  const int pass = h->opt.brush_pass;
-  const bool hit = n <= pass && session_residency_hit(S, n, &ev->session, 11);
-  hipStream_t st = (hipStream_t)stream;
-  session_enter(h, st);   // also ends the residency: re-armed below
-  TotalTimer tt(h, st);
-  BrushTable tab;   // the event table, rearranged for the kernels
-  rc = brush_table_upload(h, n, true, tips, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* colour) {
-    memcpy(row, &ev[i].c1, 7 * sizeof(int32_t));   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
-    *id = ev[i].session;
-    memcpy(colour, ev[i].rgb, 3 * sizeof(float));
-  });
-  if (rc) return rc;
-  Slot& zs = h->slots[h->desc.z_slot];
-  const ResultTarget sh = shown_target(h, shown, true);
-  for (int off = 0; off < n; off += pass) {
-    const int nc = std::min(pass, n - off);
-    if (!hit) {
-      if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
-      HIPCHK(h, launch_session_gather_z(S.arr.pool, tab.ids + off, zs.d, zs.cs, nc, st));
-      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
-    }
-    BrushSeedSrc seed;
-    seed.table = tab.items + (size_t)7 * off;
-    seed.colour = tab.colour + (size_t)3 * off;
-    if (tips) {
-      seed.tips = S.d_tips;
-      seed.tipsel = tab.tipsel + off;
-    }
-    if ((rc = brush_pass_middle(h, nc, seed, true, st))) return rc;
-    HIPCHK(h, launch_session_blend(session_blend_args(h, tab.ids + off, seed.table, sh.dev + (size_t)off * SESS_IMG, 1), nc, st));
+  static const int32_t one = 1;
+  const EditCall C = edit_call(&ev->session, 11, edit_plan(n, &one, 0, false), tipped, false, nullptr, nullptr, W);
+  const EditTable& L = C.tab;
+  int32_t* t;
+  if ((rc = edit_table_begin(h, L, n, tips, &t))) return rc;
+  for (int i = 0; i < n; ++i) {
+    t[L.ids + i] = ev[i].session;
+    memcpy(t + L.seed + (size_t)3 * i, ev[i].rgb, 3 * sizeof(float));
+    memcpy(t + L.items + (size_t)EDIT_ROW_WORDS * i, &ev[i].c1, EDIT_ROW_WORDS * sizeof(int32_t));   // c1 .. gscale: ian_brush_item's layout
   }
-  h->slot_stale[h->desc.out_slot] = 0;
-  for (int i = 0; i < n; ++i) session_latent_written(S, ev[i].session, false);
-  if (W.kind == W.VIEWS && (rc = session_render_enqueue(h, W.count, W.views, W.vw, W.vh, win.dev, st))) return rc;
-  if (W.kind == W.CANVAS && (rc = canvas_compose_enqueue(h, W.count, W.windows, W.vw, W.vh, win.dev, st))) return rc;
-  if ((rc = session_finish(h, n, sh, false, st, win, win_bytes))) return rc;
-  if (n <= pass) session_residency_arm(S, n, &ev->session, 11);   // one pass: the resident activations belong to these sessions' new latents
-  return 0;
+  return edit_passes(h, C, shown, stream);
 }
 
-// ian_session_clone (DESIGN.md 4.10): a paint event whose target is a rectangle of another picture of the pool, `steps` gradient steps in
-// one submission.  The table is the brush's (brush_table_upload, 11 words per event); the colour slot carries the three words of
-// SEED_CLONE: source id, field selector (0 GIM, 1 IM, 2 RECON), shift dr * 64 + dc.  The item rows carry loss kind 1, so the blend sees
-// a paint event.  Per pass: gather Z and one forward (neither when the residency of ian_session_brush hits), `steps` times the shared
-// middle -- seed, backward, update, forward at z_new, which IS the next step's forward -- then the stored blend once: the blends of
-// the steps before it would be overwritten (IM and FIELD are a function of the latent, RECON, ERROR and UMASK; the footprint of the
-// one rectangle into UMASK is a max, the same after one time as after `steps`).
+// ian_session_clone (DESIGN.md 4.10): a paint event towards a rectangle of another picture of the pool, `steps` gradient steps: a stroke
+// whose items all have `steps` points on one row.  Seed words: source id, field selector (0 GIM, 1 IM, 2 RECON), shift dr * 64 + dc.
 int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int steps, uint8_t* shown, void* stream) {
   const char* fn = "ian_session_clone";
   static_assert(sizeof(ian_session_clone_event) == 11 * sizeof(int32_t), "ian_session_clone_event is 11 words");
@@ -1126,59 +1170,24 @@ int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int s
       return fail(h, -7, "%s: item %d: source session %d is read from IM, which item %d of this call writes", fn, i, e.source, dest[e.source]);
   }
   if ((rc = session_local_check(h, fn, n, &ev->session, 11))) return rc;
-  const int pass = h->opt.brush_pass;
-  const bool hit = n <= pass && session_residency_hit(S, n, &ev->session, 11);
-  hipStream_t st = (hipStream_t)stream;
-  session_enter(h, st);   // also ends the residency: re-armed below
-  TotalTimer tt(h, st);
-  BrushTable tab;
-  rc = brush_table_upload(h, n, true, nullptr, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t* src) {
+  const int32_t count = steps;
+  const EditCall C = edit_call(&ev->session, 11, edit_plan(n, &count, 0, false), false, true);
+  const EditTable& L = C.tab;
+  int32_t* t;
+  if ((rc = edit_table_begin(h, L, n, nullptr, &t))) return rc;
+  for (int i = 0; i < n; ++i) {
     const ian_session_clone_event& e = ev[i];
-    row[0] = e.c1; row[1] = e.r1; row[2] = e.c2; row[3] = e.r2; row[4] = 1;   // ian_brush_item's layout, loss kind 1
-    memcpy(row + 5, &e.coef, sizeof(float));
-    memcpy(row + 6, &e.gscale, sizeof(float));
-    *id = e.session;
+    t[L.ids + i] = e.session;
+    int32_t* src = t + L.seed + (size_t)3 * i;
     src[0] = e.source; src[1] = selector(e.field); src[2] = inside(e) ? e.dr * 64 + e.dc : 0;
-  });
-  if (rc) return rc;
-  Slot& zs = h->slots[h->desc.z_slot];
-  const ResultTarget sh = shown_target(h, shown, true);
-  for (int off = 0; off < n; off += pass) {
-    const int nc = std::min(pass, n - off);
-    if (!hit) {
-      if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
-      HIPCHK(h, launch_session_gather_z(S.arr.pool, tab.ids + off, zs.d, zs.cs, nc, st));
-      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
-    }
-    BrushSeedSrc seed;
-    seed.table = tab.items + (size_t)7 * off;
-    seed.clone = reinterpret_cast<const int*>(tab.colour) + (size_t)3 * off;
-    seed.gim = S.arr.pool.gim; seed.im = S.arr.pool.im; seed.recon = S.arr.pool.recon;
-    seed.tanh_tab = S.d_tanh;
-    for (int k = 0; k < steps; ++k)
-      if ((rc = brush_pass_middle(h, nc, seed, true, st))) return rc;
-    HIPCHK(h, launch_session_blend(session_blend_args(h, tab.ids + off, seed.table, sh.dev + (size_t)off * SESS_IMG, 1), nc, st));
+    edit_row(t + L.items + (size_t)EDIT_ROW_WORDS * i, e.c1, e.r1, e.c2, e.r2, 1, e.coef, e.gscale);   // loss kind 1: the blend sees a paint event
   }
-  h->slot_stale[h->desc.out_slot] = 0;
-  // one note per destination where `steps` calls make `steps`: see ian_session_stroke
-  for (int i = 0; i < n; ++i) session_latent_written(S, ev[i].session, false);
-  if ((rc = session_finish(h, n, sh, false, st))) return rc;
-  if (n <= pass) session_residency_arm(S, n, &ev->session, 11);
-  return 0;
+  return edit_passes(h, C, shown, stream);
 }
 
 // ian_session_stroke (DESIGN.md 4.9): per session a path of rectangles, every step of it in one submission.  The meaning is the loop
-// of ian_session_brush calls in include/ian.h; what is left out is what nobody would look at between the steps.
-// The table (d_stab, one upload): [n ids | n history slots (bit 0 of flags) | 3n colours | steps + 1 row offsets | the rows], the rows
-// step after step, step k holding one ian_brush_item row per stroke with more than k points in stroke order.  The counts do not
-// increase along the array, so the strokes of a step are a prefix of it, the ones that end at a step the tail of that prefix, and a
-// pass (at most opt.brush_pass strokes) is a slice of every step's rows.
-// Per pass: gather Z and one forward (neither when the residency of ian_session_brush hits); the footprints of every point into UMASK
-// (pools with the local reservation); per step the shared middle -- seed, backward, update, forward at z_new -- on the strokes that
-// still run, then the stored blend of those that end here (their Z rows, IM / FIELD, shown), then, when some are left, the forward
-// again at the smaller batch: the per-event calls would miss their residency at the same point, and the decoder's kernels may differ
-// with the batch.  While the set of strokes stays the same, the forward at z_new IS the next step's forward.
-// tipped: ian_session_path_tip, the same call with one tip index per stroke (tips), n more words at the end of the table
+// of ian_session_brush calls in include/ian.h; what is left out is what nobody would look at between the steps.  Step k has its own
+// item rows (EditPlan, own_rows).  tipped: ian_session_path_tip, the same call with one tip index per stroke (tips)
 int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int nboxes, const ian_stroke_box* boxes, int flags,
                    uint8_t* shown, void* stream, bool tipped = false, const int32_t* tips = nullptr) {
   const char* fn = tipped ? "ian_session_path_tip" : "ian_session_stroke";
@@ -1211,103 +1220,32 @@ int session_stroke(ian_handle* h, int n, const ian_session_stroke_item* sk, int 
   }
   if ((rc = session_local_check(h, fn, n, &sk->session, 8))) return rc;
   auto& S = h->sess;
-  if (tipped) {
-    if ((rc = session_tips_arg(h, fn, tips))) return rc;
-    for (int i = 0; i < n; ++i)
-      for (int k = 0; k < sk[i].count; ++k) {
-        const ian_stroke_box& b = boxes[sk[i].first + k];
-        if ((rc = session_tip_rect(h, fn, i, k, tips[i], b.c1, b.r1, b.c2, b.r2))) return rc;
-      }
-  } else {
-    tips = nullptr;
-  }
-  const int pass = h->opt.brush_pass;
-  const bool hit = n <= pass && session_residency_hit(S, n, &sk->session, 8);
-  // the table
-  const int steps = sk[0].count;
-  int rows[IAN_STROKE_MAX_POINTS + 1] = {0};
-  for (int k = 0, act = n; k < steps; ++k) {
-    while (act > 0 && sk[act - 1].count <= k) --act;
-    rows[k + 1] = rows[k] + act;
-  }
-  const size_t o_save = (size_t)n, o_col = (size_t)2 * n, o_rows = (size_t)5 * n, o_items = o_rows + (size_t)steps + 1;
-  const size_t o_tips = o_items + (size_t)7 * rows[steps];
-  const size_t words = o_tips + (tips ? (size_t)n : 0);
-  if ((rc = grow_dev(h, &S.d_stab, &S.stab_cap, words))) return rc;
-  S.stab_shadow.assign(words, 0);
-  int32_t* t = S.stab_shadow.data();
-  std::vector<SessionHistory> next;   // bit 0: the histories after the mark; they move only after every enqueue succeeded
-  if (mark) next.resize((size_t)n);
+  if (tipped && (rc = session_tips_arg(h, fn, tips))) return rc;
+  for (int i = 0; tipped && i < n; ++i)
+    for (int k = 0; k < sk[i].count; ++k) {
+      const ian_stroke_box& b = boxes[sk[i].first + k];
+      if ((rc = session_tip_rect(h, fn, i, k, tips[i], b.c1, b.r1, b.c2, b.r2))) return rc;
+    }
+  std::vector<SessionHistory> next((size_t)(mark ? n : 0));   // bit 0: the histories after the mark
+  const EditCall C = edit_call(&sk->session, 8, edit_plan(n, &sk->count, 8, true), tipped, false, &sk->mode, mark ? next.data() : nullptr);
+  const EditPlan& P = C.plan; const EditTable& L = C.tab;
+  int32_t* t;
+  if ((rc = edit_table_begin(h, L, n, tips, &t))) return rc;
   for (int i = 0; i < n; ++i) {
-    t[i] = sk[i].session;
+    t[L.ids + i] = sk[i].session;
     if (mark) {
       next[i] = S.hist[sk[i].session];
-      t[o_save + i] = session_history_mark(next[i], S.arr.rings.depth);
+      t[L.save + i] = session_history_mark(next[i], S.arr.rings.depth);
     }
-    memcpy(t + o_col + (size_t)3 * i, sk[i].rgb, 3 * sizeof(float));
+    memcpy(t + L.seed + (size_t)3 * i, sk[i].rgb, 3 * sizeof(float));
   }
-  memcpy(t + o_rows, rows, ((size_t)steps + 1) * sizeof(int32_t));
-  if (tips) memcpy(t + o_tips, tips, (size_t)n * sizeof(int32_t));
-  for (int k = 0; k < steps; ++k)
-    for (int i = 0; i < rows[k + 1] - rows[k]; ++i) {
-      int32_t* row = t + o_items + (size_t)7 * (rows[k] + i);   // c1 r1 c2 r2 mode coef gscale: ian_brush_item's layout
+  memcpy(t + L.rows, P.rows, ((size_t)P.steps + 1) * sizeof(int32_t));
+  for (int k = 0; k < P.steps; ++k)
+    for (int i = 0; i < P.rows[k + 1] - P.rows[k]; ++i) {
       const ian_stroke_box& b = boxes[sk[i].first + k];
-      row[0] = b.c1; row[1] = b.r1; row[2] = b.c2; row[3] = b.r2; row[4] = sk[i].mode;
-      memcpy(row + 5, &sk[i].coef, sizeof(float));
-      memcpy(row + 6, &b.gscale, sizeof(float));
+      edit_row(t + L.items + (size_t)EDIT_ROW_WORDS * (P.rows[k] + i), b.c1, b.r1, b.c2, b.r2, sk[i].mode, sk[i].coef, b.gscale);
     }
-  hipStream_t st = (hipStream_t)stream;
-  session_enter(h, st);   // also ends the residency: re-armed below
-  TotalTimer tt(h, st);
-  HIPCHK(h, hipMemcpyAsync(S.d_stab, t, words * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  const int* d_ids = S.d_stab;
-  const int* d_items = S.d_stab + o_items;
-  const float* d_col = reinterpret_cast<const float*>(S.d_stab + o_col);
-  if (mark) HIPCHK(h, launch_session_history_save(S.arr.pool, S.arr.rings, d_ids, S.d_stab + o_save, n, st));   // before UMASK moves
-  Slot& zs = h->slots[h->desc.z_slot];
-  const ResultTarget sh = shown_target(h, shown, true);
-  for (int off = 0; off < n; off += pass) {
-    const int nc = std::min(pass, n - off);
-    const int K = sk[off].count;   // the longest stroke of the pass
-    if (!hit) {
-      if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
-      HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
-      if ((rc = batch_forward(h, nullptr, nc, st))) return rc;
-    }
-    bool footprints = false;   // what the kernel would find on the device, as far as the host knows it: the mode flag it does not
-    for (int i = off; S.arr.pool.umask && !footprints && i < off + nc; ++i) footprints = sk[i].mode == 1 && (S.local_flags[sk[i].session] & 1);
-    if (footprints) HIPCHK(h, launch_session_stroke_umask(S.arr.pool, d_ids, d_items, S.d_stab + o_rows, K, off, S.d_falloff, nc, st));
-    for (int k = 0, act = nc; k < K; ++k) {   // act: the strokes of this pass with more than k points
-      BrushSeedSrc seed;
-      seed.table = d_items + (size_t)7 * (rows[k] + off);
-      seed.colour = d_col + (size_t)3 * off;
-      if (tips) {   // the strokes of a step are a prefix of the pass: so are their tips
-        seed.tips = S.d_tips;
-        seed.tipsel = S.d_stab + o_tips + off;
-      }
-      if ((rc = brush_pass_middle(h, act, seed, true, st))) return rc;
-      int keep = act;
-      while (keep > 0 && sk[off + keep - 1].count == k + 1) --keep;
-      if (keep == act) continue;   // the same strokes go on: the activations at z_new are the next step's
-      SessionBlendArgs a = session_blend_args(h, d_ids + off + keep, seed.table + (size_t)7 * keep, sh.dev + (size_t)(off + keep) * SESS_IMG, 1);
-      a.xhat += (size_t)keep * SESS_IMG;
-      a.zslot += (size_t)keep * zs.cs;
-      HIPCHK(h, launch_session_blend(a, act - keep, st));
-      if (keep > 0 && (rc = batch_forward(h, nullptr, keep, st))) return rc;
-      act = keep;
-    }
-  }
-  h->slot_stale[h->desc.out_slot] = 0;
-  // One note per session where the per-event calls make `count` of them.  The version is only ever compared for equality, and
-  // session_history_edited is idempotent: its first call leaves cur == len, where every further one returns at once.  So
-  // ian_session_history reports what the calls would.
-  for (int i = 0; i < n; ++i) {
-    if (mark) S.hist[sk[i].session] = next[i];
-    session_latent_written(S, sk[i].session, false);
-  }
-  if ((rc = session_finish(h, n, sh, false, st))) return rc;
-  if (n <= pass && sk[n - 1].count == steps) session_residency_arm(S, n, &sk->session, 8);   // the brush's rule: one pass, and every stroke ran in the last forward
-  return 0;
+  return edit_passes(h, C, shown, stream);
 }
 
 // ian_session_fit (DESIGN.md 4.8): the sessions' latents fitted to their own photos, `steps` Adam steps in one submission.  Per pass
@@ -1338,16 +1276,21 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
     c1[t] = (float)(1.0 / (1.0 - std::pow(0.9, (double)t)));
     c2[t] = (float)(1.0 / (1.0 - std::pow(0.999, (double)t)));
   }
+  // the brush calls' table: one row per item (the rectangle, loss kind 1; coef and gscale unused), the seed words left zero
+  static const int32_t one = 1;
+  const EditTable L = edit_table(edit_plan(n, &one, 0, false), false, false);
+  int32_t* t;
+  if ((rc = edit_table_begin(h, L, n, nullptr, &t))) return rc;
+  for (int i = 0; i < n; ++i) {
+    t[L.ids + i] = items[i].session;
+    edit_row(t + L.items + (size_t)EDIT_ROW_WORDS * i, items[i].c1, items[i].r1, items[i].c2, items[i].r2, 1, 0.f, 0.f);
+  }
   hipStream_t st = (hipStream_t)stream;
   session_enter(h, st);   // also ends the residency of ian_session_brush: not re-armed, the last forward keeps no activations
   TotalTimer tt(h, st);
-  BrushTable tab;   // the rows: the rectangle, loss kind 1; coef and gscale unused
-  rc = brush_table_upload(h, n, false, nullptr, st, &tab, [&](int i, int32_t* row, int32_t* id, int32_t*) {
-    row[0] = items[i].c1; row[1] = items[i].r1; row[2] = items[i].c2; row[3] = items[i].r2; row[4] = 1;
-    *id = items[i].session;
-  });
-  if (rc) return rc;
-  HIPCHK(h, launch_session_fit_begin(S.arr.pool, tab.ids, n, st));   // IM := GIM (NPE.py:332)
+  HIPCHK(h, hipMemcpyAsync(S.d_stab, t, L.words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int* d_ids = S.d_stab + L.ids;
+  HIPCHK(h, launch_session_fit_begin(S.arr.pool, d_ids, n, st));   // IM := GIM (NPE.py:332)
   Slot& zs = h->slots[h->desc.z_slot];
   double* d_loss = loss ? (loss_dev ? loss : S.d_fit_loss) : nullptr;
   const ResultTarget sh = shown_target(h, shown, false);
@@ -1355,14 +1298,14 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
   for (int off = 0; off < n; off += pass) {
     const int nc = std::min(pass, n - off);
     if ((rc = ensure_slot(h, h->desc.z_slot, nc))) return rc;
-    HIPCHK(h, launch_session_gather_z(S.arr.pool, tab.ids + off, zs.d, zs.cs, nc, st));
+    HIPCHK(h, launch_session_gather_z(S.arr.pool, d_ids + off, zs.d, zs.cs, nc, st));
     float* m = S.d_fit;
     float* v = S.d_fit + (size_t)nc * zl;
     HIPCHK(h, hipMemsetAsync(S.d_fit, 0, (size_t)2 * nc * zl * sizeof(float), st));   // the moments start at zero on every call
     BrushSeedSrc seed;
-    seed.table = tab.items + (size_t)7 * off;
+    seed.table = S.d_stab + L.items + (size_t)EDIT_ROW_WORDS * off;
     seed.gim = S.arr.pool.gim;
-    seed.ids = tab.ids + off;
+    seed.ids = d_ids + off;
     seed.tanh_tab = S.d_tanh;
     auto read_loss = [&](int t) -> hipError_t {
       return launch_session_fit_loss(out.d, S.arr.pool, seed.ids, seed.table, S.d_tanh, d_loss + (size_t)off * lstride + t, lstride, nc, st);
@@ -1378,7 +1321,7 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
     HIPCHK(h, launch_session_store(out.d, zs.d, zs.cs, S.arr.pool, seed.ids, 0, 1, sh.dev ? sh.dev + (size_t)off * SESS_IMG : nullptr, nc, st));
   }
   h->slot_stale[h->desc.out_slot] = 0;
-  if (S.arr.pool.umask) HIPCHK(h, launch_session_local_set(S.arr.pool, tab.ids, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:337); LOCAL stays
+  if (S.arr.pool.umask) HIPCHK(h, launch_session_local_set(S.arr.pool, d_ids, nullptr, n, st));   // USER_MASK *= 0 (NPE.py:337); LOCAL stays
   for (int i = 0; i < n; ++i) session_latent_written(S, items[i].session, true);   // the saved states no longer belong to the picture
   const bool loss_host = loss && !loss_dev;
   if (loss_host) HIPCHK(h, hipMemcpyAsync(loss, S.d_fit_loss, (size_t)n * lstride * sizeof(double), hipMemcpyDeviceToHost, st));

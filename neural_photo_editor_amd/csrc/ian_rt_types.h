@@ -291,7 +291,7 @@ struct ian_handle {
   // The device buffers beside the pool, as plain data: SESS_SCRATCH (ian_rt_session.inc) names each once, with the reservation that
   // owns it and its size; nothing else allocates or frees them.
   struct SessionScratch {
-    int* d_tab = nullptr;              // per call: brush = [7n ian_brush_item words | n ids | 3n colours | with tips: n tip indices], open / set_latent = n ids
+    int* d_tab = nullptr;              // per call: open / set_latent = n ids, ian_canvas_place = [n ids | 5n placement words]
     float* d_tanh = nullptr;           // to_tanh of the 256 uint8 levels, float32
     unsigned char* d_photo = nullptr;  // staging of host photos [256][3*64*64], allocated by the first open that needs it
     unsigned char* d_shown = nullptr;  // staging of the canvas images [256][3*64*64]
@@ -305,7 +305,7 @@ struct ian_handle {
     unsigned char* d_stage = nullptr;  // saved sessions: staging of records for a host `body`, grown on demand (stage_cap) up to opt.session_stage_bytes
     float* d_fit = nullptr;            // ian_session_fit: Adam's moments of one pass, m [256][zl] then v [256][zl]; by the first such call
     double* d_fit_loss = nullptr;      // ian_session_fit: staging of the loss trace for a host `loss`, [256][513]; by the first call that asks for one
-    int* d_stab = nullptr;             // ian_session_stroke: per call [n ids | n history slots | 3n colours | steps + 1 row offsets | the steps' ian_brush_item rows], grown on demand (stab_cap words)
+    int* d_stab = nullptr;             // brush, clone, stroke and fit calls: the call's table, laid out by EditTable (ian_edit_plan.h), grown on demand (stab_cap words)
     float* d_tips = nullptr;           // brush tips: f32[tip_count][64 * 64], row stride 64 (ian_sessions_reserve_tips / _set_tip); nullptr = no tips
   };
   struct SessionState : SessionScratch {
@@ -340,7 +340,7 @@ struct ian_handle {
     // saved sessions (ian_session_save / ian_session_load)
     std::vector<int32_t> rtab_shadow;    // upload source of d_rtab
     size_t stage_cap = 0;
-    // strokes (ian_session_stroke)
+    // the table of a brush, clone, stroke or fit call
     std::vector<int32_t> stab_shadow;    // upload source of d_stab
     size_t stab_cap = 0;
     // brush tips (ian_sessions_reserve_tips): how many d_tips holds and per tip its (tw, th), (0, 0) until ian_sessions_set_tip gave it
