@@ -733,6 +733,30 @@ int ian_sessions_reserve_edges(ian_handle* h, const float* table, int32_t count)
 /* 1 with the edge-aware compose on (its table -> table_out, host f32[766], or NULL), 0 with the plain one; -6 without canvases. */
 int ian_sessions_edges(ian_handle* h, float* table_out);
 
+/* ---- zoomed views: a picture or a canvas at 1/zoom, produced on the device ----
+   What an editor shows while the user paints is a fit-to-window view, not the photo pixel for pixel.  For zoom in 1..16, output
+   pixel (Y, X) of a window whose source origin is (x, y) is the exact integer box mean of the full-resolution result,
+     (sum of the zoom x zoom block of result bytes at (y + zoom*Y .., x + zoom*X ..) + zoom*zoom/2) / (zoom*zoom),
+   the result bytes being exactly those ian_session_render (ian_canvas_compose) gives for the source window
+   (x, y, zoom*vw, zoom*vh): rounded to uint8 per pixel first, then averaged, the rounding of ian_session_open_hires's box mean.
+   The arithmetic is npe_ops.zoom_box_mean over hires_render / hires_render_guided / canvas_compose / canvas_compose_guided; no
+   full-resolution result is written on the way, the device stores and sends 3*vw*vh bytes a window.  x and y of the views and
+   windows stay in full-resolution pixels; vw, vh are the OUTPUT size; out u8[n,3,vh,vw], host or device, 4-byte aligned.  Only
+   whole blocks count: the source window must lie inside the picture.  A reserved guide (edges table) applies as it does at 1:1.
+   zoom == 1 is the plain call.  The four entries are, in this order, ian_session_render, ian_session_brush_view (tips == NULL) or
+   ian_session_brush_tip with views (tips given), ian_canvas_compose and ian_canvas_brush with a zoom; everything those calls say
+   about submissions, synchronisation, the decoder's activations and the residency holds.  The commit has no zoomed form.
+   -6: the reservation the plain call needs is missing.  -7, naming the item, before anything is enqueued: zoom outside 1..16, the
+   source window outside the picture or canvas, x or vw not a multiple of 4, vw < 4, vh < 1, and whatever the plain call refuses. */
+int ian_session_zoom(ian_handle* h, int32_t n, const ian_session_view* views, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out,
+                     void* stream);
+int ian_session_brush_zoom(ian_handle* h, int32_t n, const ian_session_event* events, const int32_t* tips, uint8_t* shown,
+                           const ian_session_view* views, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out, void* stream);
+int ian_compose_zoom(ian_handle* h, int32_t n, const ian_canvas_window* windows, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out,
+                     void* stream);
+int ian_compose_brush_zoom(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, int32_t m,
+                           const ian_canvas_window* windows, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out, void* stream);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -299,11 +299,27 @@ def pack_session_clones(ids, boxes, sources, offsets=(0, 0), field="GIM", weight
     return ev
 
 
-def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, sourced=None, events=None):
+def check_zoom(zoom):
+    """The zoom of a view -> int in 1..16."""
+    if isinstance(zoom, (bool, np.bool_)) or not isinstance(zoom, (int, np.integer)) or not 1 <= int(zoom) <= 16:
+        raise ValueError("zoom must be an integer in 1..16, got %r" % (zoom,))
+    return int(zoom)
+
+
+def _window_outside(i, x, y, vw, vh, zoom, w, h, what):
+    """The refusal of window i whose source (x, y, zoom*vw, zoom*vh) leaves the w x h picture, or None."""
+    if x < 0 or y < 0 or x + zoom * vw > w or y + zoom * vh > h:
+        at = "" if zoom == 1 else " at zoom %d" % zoom
+        return "item %d: window (%d,%d) + %d x %d%s outside the %d x %d %s" % (i, x, y, vw, vh, at, w, h, what)
+    return None
+
+
+def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, sourced=None, events=None, zoom=1):
     """Python arguments of ian_session_render / ian_session_brush_view -> (a ctypes array of ian_session_view, vw, vh), validated
     before the library sees anything.  ids (n,) session ids -- the same id may appear several times, as tiles of one picture;
     origins (n,2) or (2,) as (x, y), the windows' top-left corners in the S x S picture, S = 64 * scale; size = (vw, vh) or one
-    integer for a square window.  x and vw must be multiples of 4, the window inside the picture.  scale is the pool's (None or
+    integer for a square window.  x and vw must be multiples of 4, the window inside the picture.  zoom (1..16): size is that of the
+    view at 1/zoom, and the source window (x, y, zoom*vw, zoom*vh) is the one that must lie inside.  scale is the pool's (None or
     0: there is no full-resolution reservation).  capacity / opened / sourced (containers of opened ids and of ids that hold a
     full-resolution source), when given, bound and vet the ids; events (a ctypes array of ian_session_event), when given, must name
     the same sessions in the same order."""
@@ -313,6 +329,7 @@ def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, so
     if not 1 <= scale <= 16:
         raise ValueError("scale must be in 1..16, got %d" % scale)
     S = 64 * scale
+    zoom = check_zoom(zoom)
     a = check_session_ids(ids, capacity, opened, repeats=True, what="views")
     n = a.shape[0]
     sz = np.asarray(size)
@@ -341,8 +358,9 @@ def pack_session_views(ids, origins, size, scale, capacity=None, opened=None, so
             raise ValueError("item %d: session %d has no full-resolution source (open_hires)" % (i, sid))
         if x % 4:
             raise ValueError("item %d: window x %d is not a multiple of 4" % (i, x))
-        if x < 0 or y < 0 or x + vw > S or y + vh > S:
-            raise ValueError("item %d: window (%d,%d) + %d x %d outside the %d x %d picture" % (i, x, y, vw, vh, S, S))
+        bad = _window_outside(i, x, y, vw, vh, zoom, S, S, "picture")
+        if bad:
+            raise ValueError(bad)
         v = views[i]
         v.session, v.x, v.y = sid, x, y
     return views, vw, vh
@@ -409,12 +427,13 @@ def pack_canvas_placements(ids, cids, origins, scales, sizes, placed=None, capac
     return items
 
 
-def pack_canvas_windows(cids, origins, size, sizes):
+def pack_canvas_windows(cids, origins, size, sizes, zoom=1):
     """Python arguments of ian_canvas_compose / ian_canvas_brush -> (a ctypes array of ian_canvas_window, vw, vh), validated before
     the library sees anything.  cids (n,) canvas ids -- the same canvas may appear several times, as tiles; origins (n,2) or (2,)
-    as (x, y); size = (vw, vh) or one integer.  x and vw must be multiples of 4, the window inside the canvas's picture.  sizes as in
-    pack_canvas_placements."""
+    as (x, y); size = (vw, vh) or one integer.  x and vw must be multiples of 4, the window inside the canvas's picture.  zoom as in
+    pack_session_views.  sizes as in pack_canvas_placements."""
     from .lib import CanvasWindow
+    zoom = check_zoom(zoom)
     a = np.asarray(cids)
     if a.ndim == 0:
         a = a.reshape(1)
@@ -439,8 +458,9 @@ def pack_canvas_windows(cids, origins, size, sizes):
         w, h = sizes[cv[i]]
         if x % 4:
             raise ValueError("item %d: window x %d is not a multiple of 4" % (i, x))
-        if x < 0 or y < 0 or x + vw > w or y + vh > h:
-            raise ValueError("item %d: window (%d,%d) + %d x %d outside the %d x %d canvas" % (i, x, y, vw, vh, w, h))
+        bad = _window_outside(i, x, y, vw, vh, zoom, w, h, "canvas")
+        if bad:
+            raise ValueError(bad)
         win[i].canvas, win[i].x, win[i].y = cv[i], x, y
     return win, vw, vh
 
@@ -924,28 +944,36 @@ class EditSessions:
         self._unplace(ids)
         return shown
 
-    def _views(self, ids, origins, size, events=None):
-        return pack_session_views(ids, origins, size, self.scale, self.capacity, self._opened, self._sourced, events)
+    def _views(self, ids, origins, size, events=None, zoom=1):
+        return pack_session_views(ids, origins, size, self.scale, self.capacity, self._opened, self._sourced, events, zoom)
 
-    def render(self, ids, origins, size):
+    def render(self, ids, origins, size, zoom=1):
         """Windows of the pictures at full resolution, as last displayed -> uint8 (n,3,vh,vw).  origins (n,2) or (2,) as (x, y),
-        size (vw, vh) or one integer; x and vw multiples of 4.  The same id may appear several times (tiles)."""
-        views, vw, vh = self._views(ids, origins, size)
+        size (vw, vh) or one integer; x and vw multiples of 4.  The same id may appear several times (tiles).  zoom = k > 1: the
+        views at 1/k (npe_ops.hires_render_zoom): origins stay in full-resolution pixels, size is the output's, and the source
+        window (x, y, k*vw, k*vh) must lie inside the picture (npe_ops.zoom_window gives the size that shows all of it)."""
+        views, vw, vh = self._views(ids, origins, size, None, zoom)
         out = np.empty((len(views), 3, vh, vw), np.uint8)
-        self._h.session_render(views, vw, vh, out)
+        if zoom == 1:
+            self._h.session_render(views, vw, vh, out)
+        else:
+            self._h.session_zoom(views, vw, vh, zoom, out)
         return out
 
-    def brush_view(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, origins=(0, 0), size=64, tips=None):
+    def brush_view(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, origins=(0, 0), size=64, tips=None, zoom=1):
         """brush, and window i of session ids[i] at full resolution after its event, in ONE submission -> (shown, out).  tips: as in
-        brush."""
+        brush.  zoom: as in render."""
         ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
-        views, vw, vh = self._views(ids, origins, size, ev)
+        views, vw, vh = self._views(ids, origins, size, ev, zoom)
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
         out = np.empty((len(ev), 3, vh, vw), np.uint8)
-        if tips is None:
+        sel = None if tips is None else self._tipsel(tips, self._event_boxes(ev))
+        if zoom != 1:
+            self._h.session_brush_zoom(ev, sel, shown, views, vw, vh, zoom, out)
+        elif tips is None:
             self._h.session_brush_view(ev, views, vw, vh, out, shown)
         else:
-            self._h.session_brush_tip(ev, self._tipsel(tips, self._event_boxes(ev)), shown, views, vw, vh, out)
+            self._h.session_brush_tip(ev, sel, shown, views, vw, vh, out)
         return shown, out
 
     @staticmethod
@@ -1060,30 +1088,38 @@ class EditSessions:
             self._placed[p.session] = (p.canvas, p.x, p.y, p.scale)
         return shown
 
-    def _windows(self, cids, origins, size):
+    def _windows(self, cids, origins, size, zoom=1):
         self._need_canvases()
-        return pack_canvas_windows(cids, origins, size, self._canvas_wh)
+        return pack_canvas_windows(cids, origins, size, self._canvas_wh, zoom)
 
-    def compose(self, cids, origins, size):
+    def compose(self, cids, origins, size, zoom=1):
         """Windows of the canvases with every placed session's edit on top (npe_ops.canvas_compose; after reserve_canvas_guide
         npe_ops.canvas_compose_guided) -> uint8 (n,3,vh,vw).  origins (n,2) or (2,) as (x, y), size (vw, vh) or one integer; x and vw
-        multiples of 4.  The same canvas may appear several times."""
-        win, vw, vh = self._windows(cids, origins, size)
+        multiples of 4.  The same canvas may appear several times.  zoom = k > 1: the windows at 1/k (npe_ops.canvas_compose_zoom),
+        as in render."""
+        win, vw, vh = self._windows(cids, origins, size, zoom)
         out = np.empty((len(win), 3, vh, vw), np.uint8)
-        self._h.canvas_compose(win, vw, vh, out)
+        if zoom == 1:
+            self._h.canvas_compose(win, vw, vh, out)
+        else:
+            self._h.compose_zoom(win, vw, vh, zoom, out)
         return out
 
     def brush_compose(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, windows=None):
-        """brush on sessions ids, and the windows = (cids, origins, size) of compose() after it, in ONE submission -> (shown, out).
-        The sessions need not be placed, the windows need not show them.  After reserve_canvas_guide the windows are
-        npe_ops.canvas_compose_guided's."""
-        if windows is None or len(windows) != 3:
-            raise ValueError("windows must be (cids, origins, size)")
+        """brush on sessions ids, and the windows = (cids, origins, size) or (cids, origins, size, zoom) of compose() after it, in ONE
+        submission -> (shown, out).  The sessions need not be placed, the windows need not show them.  After reserve_canvas_guide
+        the windows are npe_ops.canvas_compose_guided's."""
+        if windows is None or len(windows) not in (3, 4):
+            raise ValueError("windows must be (cids, origins, size) or (cids, origins, size, zoom)")
         ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
         win, vw, vh = self._windows(*windows)
+        zoom = windows[3] if len(windows) == 4 else 1
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
         out = np.empty((len(win), 3, vh, vw), np.uint8)
-        self._h.canvas_brush(ev, win, vw, vh, out, shown)
+        if zoom == 1:
+            self._h.canvas_brush(ev, win, vw, vh, out, shown)
+        else:
+            self._h.compose_brush_zoom(ev, win, vw, vh, zoom, out, shown)
         return shown, out
 
     def canvas_commit(self, cid):
@@ -1217,19 +1253,25 @@ class EditSessions:
         return self.stroke(ids, paths, colours_uint8, None, weight, -1.0, mark, tip)
 
     def paint(self, ids, boxes, colours_uint8, weight=0.05, view=None, tips=None):
-        """NPE.paint: Z -= weight * grad toward the brush colour (levels 0..255 per channel).  view = (origins, size): also the
-        full-resolution windows, as brush_view -> (shown, out).  tips: as in brush."""
+        """NPE.paint: Z -= weight * grad toward the brush colour (levels 0..255 per channel).  view = (origins, size) or (origins,
+        size, zoom): also the full-resolution windows, as brush_view -> (shown, out).  tips: as in brush."""
         if view is not None:
-            origins, size = view
-            return self.brush_view(ids, boxes, colours_uint8, None, weight, -1.0, origins, size, tips)
+            origins, size, zoom = self._view3(view)
+            return self.brush_view(ids, boxes, colours_uint8, None, weight, -1.0, origins, size, tips, zoom)
         return self.brush(ids, boxes, colours_uint8, None, weight, -1.0, tips)
+
+    @staticmethod
+    def _view3(view):
+        if len(view) not in (2, 3):
+            raise ValueError("view must be (origins, size) or (origins, size, zoom)")
+        return tuple(view) if len(view) == 3 else (view[0], view[1], 1)
 
     def scroll(self, ids, boxes, signs, weight=0.1, view=None, tips=None):
         """NPE.scroll: Z += sign(event.delta) * weight * grad of the patch mean.  view = (origins, size): as in paint.  tips: as in
         brush."""
         if view is not None:
-            origins, size = view
-            return self.brush_view(ids, boxes, None, None, weight, signs, origins, size, tips)
+            origins, size, zoom = self._view3(view)
+            return self.brush_view(ids, boxes, None, None, weight, signs, origins, size, tips, zoom)
         return self.brush(ids, boxes, None, None, weight, signs, tips)
 
     def read(self, sid):

@@ -508,6 +508,18 @@ hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P,
 // as above.
 hipError_t launch_canvas_compose_guided(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh,
                                         unsigned char* out, int n, hipStream_t s);
+// zoomed views: the four window launches above at 1/zoom, zoom in 2..16 (1 is the launch above).  Output pixel
+// (Y, X) of window i is npe_ops.zoom_box_mean of the 1:1 result of the source window (x, y, zoom * vw, zoom * vh), which must lie
+// inside the picture: x and y of views / windows stay in full-resolution pixels, vw x vh is the OUTPUT size, out u8 [n][3][vh][vw],
+// never nullptr.  No full-resolution result is written anywhere.
+hipError_t launch_session_render_zoom(const SessionPool& P, const int* views, int vw, int vh, int zoom, unsigned char* out, int n,
+                                      hipStream_t s);
+hipError_t launch_session_render_guided_zoom(const SessionPool& P, const float* table, const int* views, int vw, int vh, int zoom,
+                                             unsigned char* out, int n, hipStream_t s);
+hipError_t launch_canvas_compose_zoom(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, int zoom,
+                                      unsigned char* out, int n, hipStream_t s);
+hipError_t launch_canvas_compose_guided_zoom(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw,
+                                             int vh, int zoom, unsigned char* out, int n, hipStream_t s);
 
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,

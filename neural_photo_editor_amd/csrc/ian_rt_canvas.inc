@@ -288,9 +288,10 @@ int canvas_place(ian_handle* h, int n, const ian_canvas_placement* items, uint8_
 }
 
 // what ian_canvas_compose and ian_canvas_brush check about the windows, before anything is enqueued
-int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_window* w, int vw, int vh, const uint8_t* out) {
+// zoom: as in session_view_check
+int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_window* w, int vw, int vh, const uint8_t* out, int zoom) {
   int rc = canvas_need(h, fn);
-  if (rc) return rc;
+  if (rc || (rc = zoom_check(h, fn, zoom))) return rc;
   auto& S = h->sess;
   if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: %d windows outside 1..%d", fn, n, BATCH_MAX);
   if (!w || !out) return fail(h, -1, "null pointer passed to %s", fn);
@@ -301,28 +302,36 @@ int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_w
     if ((rc = canvas_check_id(h, fn, i, w[i].canvas, true))) return rc;
     const int cw = S.canvas_wh[2 * w[i].canvas], ch = S.canvas_wh[2 * w[i].canvas + 1];
     if (w[i].x & 3) return fail(h, -7, "%s: item %d: window x %d is not a multiple of 4", fn, i, w[i].x);
-    if (w[i].x < 0 || w[i].y < 0 || w[i].x > cw - vw || w[i].y > ch - vh)
+    if (zoom == 1 && (w[i].x < 0 || w[i].y < 0 || w[i].x > cw - vw || w[i].y > ch - vh))
       return fail(h, -7, "%s: item %d: window (%d,%d) + %d x %d outside the %d x %d canvas", fn, i, w[i].x, w[i].y, vw, vh, cw, ch);
+    if (zoom_outside(w[i].x, vw, zoom, cw) || zoom_outside(w[i].y, vh, zoom, ch))
+      return fail(h, -7, "%s: item %d: window (%d,%d) + %d x %d at zoom %d outside the %d x %d canvas", fn, i, w[i].x, w[i].y, vw, vh, zoom,
+                  cw, ch);
   }
   return 0;
 }
 
-// the windows of n canvases into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, one whole picture over its own canvas
-int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st) {
+// the windows of n canvases into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, one whole picture over its own canvas.
+// zoom > 1: the windows at 1/zoom, the zoomed kernels; 1 takes the launches it always took
+int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st, int zoom) {
   auto& S = h->sess;
   S.cwin_shadow.resize((size_t)3 * n);
   memcpy(S.cwin_shadow.data(), w, (size_t)n * sizeof(ian_canvas_window));
   HIPCHK(h, hipMemcpyAsync(S.d_cwin, S.cwin_shadow.data(), (size_t)n * sizeof(ian_canvas_window), hipMemcpyHostToDevice, st));
-  if (S.d_edges)   // ian_sessions_reserve_edges: the same windows, each photo-mode field's taps weighted by the canvas
+  if (zoom > 1) {
+    if (S.d_edges) HIPCHK(h, launch_canvas_compose_guided_zoom(S.canv, S.arr.pool, S.d_edges, S.d_cwin, vw, vh, zoom, d_out, n, st));
+    else HIPCHK(h, launch_canvas_compose_zoom(S.canv, S.arr.pool, S.d_cwin, vw, vh, zoom, d_out, n, st));
+  } else if (S.d_edges)   // ian_sessions_reserve_edges: the same windows, each photo-mode field's taps weighted by the canvas
     HIPCHK(h, launch_canvas_compose_guided(S.canv, S.arr.pool, S.d_edges, S.d_cwin, vw, vh, d_out, n, st));
   else
     HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_cwin, vw, vh, d_out, n, st));
   return 0;
 }
 
-int canvas_compose(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, uint8_t* out, void* stream) {
-  if (int rc = canvas_window_check(h, "ian_canvas_compose", n, w, vw, vh, out)) return rc;
-  return window_call(h, n, vw, vh, out, stream, [&](unsigned char* d, hipStream_t st) { return canvas_compose_enqueue(h, n, w, vw, vh, d, st); });
+int canvas_compose(ian_handle* h, const char* fn, int n, const ian_canvas_window* w, int vw, int vh, int zoom, uint8_t* out, void* stream) {
+  if (int rc = canvas_window_check(h, fn, n, w, vw, vh, out, zoom)) return rc;
+  return window_call(h, n, vw, vh, out, stream,
+                     [&](unsigned char* d, hipStream_t st) { return canvas_compose_enqueue(h, n, w, vw, vh, d, st, zoom); });
 }
 
 int canvas_commit(ian_handle* h, int canvas, uint8_t* shown, void* stream) {
@@ -362,7 +371,18 @@ int ian_canvas_place(ian_handle* h, int32_t n, const ian_canvas_placement* items
   return h ? canvas_place(h, n, items, shown, stream) : -1;
 }
 int ian_canvas_compose(ian_handle* h, int32_t n, const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
-  return h ? canvas_compose(h, n, windows, vw, vh, out, stream) : -1;
+  return h ? canvas_compose(h, "ian_canvas_compose", n, windows, vw, vh, 1, out, stream) : -1;
+}
+int ian_compose_zoom(ian_handle* h, int32_t n, const ian_canvas_window* windows, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out,
+                            void* stream) {
+  return h ? canvas_compose(h, "ian_compose_zoom", n, windows, vw, vh, zoom, out, stream) : -1;
+}
+int ian_compose_brush_zoom(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, int32_t m,
+                          const ian_canvas_window* windows, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out, void* stream) {
+  if (!h) return -1;
+  if (!windows) return fail(h, -1, "null pointer passed to ian_compose_brush_zoom");
+  return session_brush(h, n, events, shown, stream,
+                       BrushWindows{BrushWindows::CANVAS, nullptr, windows, m, vw, vh, out, zoom, "ian_compose_brush_zoom"});
 }
 int ian_canvas_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, int32_t m,
                      const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream) {

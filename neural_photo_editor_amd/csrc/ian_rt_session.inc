@@ -97,8 +97,9 @@ int canvases_pool_resized(ian_handle* h);                           // ian_sessi
 bool canvas_is_placed(const ian_handle* h, int id);
 void canvas_unplace(ian_handle* h, int id);                         // host side; the table's upload follows with canvas_table_flush
 int canvas_table_flush(ian_handle* h, hipStream_t st);
-int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_window* w, int vw, int vh, const uint8_t* out);
-int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st);
+int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_window* w, int vw, int vh, const uint8_t* out, int zoom = 1);
+int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st,
+                           int zoom = 1);
 
 bool sess_has(const SessionArrays& P, SessGroup g) {
   for (const SessColumn& c : SESS_COLUMNS)
@@ -593,14 +594,21 @@ int session_finish(ian_handle* h, int n, const ResultTarget& shown, bool host_in
 
 // what ian_session_render and ian_session_brush_view check about the windows, before anything is enqueued: the reservation, n, and
 // per item the session (in the pool, opened, holding a photo; ev given: the session of event i) and the window.  The same session may
-// appear several times (tiles of one picture).
+// appear several times (tiles of one picture).  zoom: vw x vh is the size of a view at 1/zoom (DESIGN.md 4.14), whose source window
+// (x, y, zoom * vw, zoom * vh) is the one that must lie inside the picture; 1: the window itself.
+constexpr int ZOOM_LIMIT = 16;
+int zoom_check(ian_handle* h, const char* fn, int zoom) {
+  return zoom < 1 || zoom > ZOOM_LIMIT ? fail(h, -7, "%s: zoom %d outside 1..%d", fn, zoom, ZOOM_LIMIT) : 0;
+}
+// "x > limit - zoom * size" of one axis without overflow
+bool zoom_outside(int at, int size, int zoom, int limit) { return at < 0 || (long long)at + (long long)zoom * size > limit; }
 int session_view_check(ian_handle* h, const char* fn, int n, const ian_session_view* views, int vw, int vh, const uint8_t* out,
-                       const ian_session_event* ev) {
+                       const ian_session_event* ev, int zoom = 1) {
   static_assert(sizeof(ian_session_view) == 3 * sizeof(int32_t), "ian_session_view is 3 words");
   int rc = check_ready(h, 1);
   if (rc) return rc;
   auto& S = h->sess;
-  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES)) || (rc = zoom_check(h, fn, zoom))) return rc;
   if (n < 1 || n > BATCH_MAX) return fail(h, -7, "%s: n = %d outside 1..%d", fn, n, BATCH_MAX);
   if (!views || !out) return fail(h, -1, "null pointer passed to %s", fn);
   if (is_device_ptr(views)) return fail(h, -7, "%s: the views must be a host array", fn);
@@ -616,19 +624,26 @@ int session_view_check(ian_handle* h, const char* fn, int n, const ian_session_v
     if (!S.has_src[v.session])
       return fail(h, -7, "%s: item %d: session %d has no full-resolution source (open it with ian_session_open_hires)", fn, i, v.session);
     if (v.x & 3) return fail(h, -7, "%s: item %d: window x %d is not a multiple of 4", fn, i, v.x);
-    if (v.x < 0 || v.y < 0 || v.x > Sz - vw || v.y > Sz - vh)
+    if (zoom == 1 && (v.x < 0 || v.y < 0 || v.x > Sz - vw || v.y > Sz - vh))
       return fail(h, -7, "%s: item %d: window (%d,%d) + %d x %d outside the %d x %d picture", fn, i, v.x, v.y, vw, vh, Sz, Sz);
+    if (zoom_outside(v.x, vw, zoom, Sz) || zoom_outside(v.y, vh, zoom, Sz))
+      return fail(h, -7, "%s: item %d: window (%d,%d) + %d x %d at zoom %d outside the %d x %d picture", fn, i, v.x, v.y, vw, vh, zoom, Sz, Sz);
   }
   return 0;
 }
 
-// the windows of n views into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, the whole picture over each session's own SRC
-int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, int vw, int vh, unsigned char* d_out, hipStream_t st) {
+// the windows of n views into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, the whole picture over each session's own SRC.
+// zoom > 1: the views at 1/zoom, the zoomed kernels; 1 takes the launches it always took
+int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, int vw, int vh, unsigned char* d_out, hipStream_t st,
+                           int zoom = 1) {
   auto& S = h->sess;
   S.views_shadow.resize((size_t)3 * n);
   memcpy(S.views_shadow.data(), views, (size_t)n * sizeof(ian_session_view));
   HIPCHK(h, hipMemcpyAsync(S.d_views, S.views_shadow.data(), (size_t)n * sizeof(ian_session_view), hipMemcpyHostToDevice, st));
-  if (S.d_guide)   // ian_sessions_reserve_guide: the same windows, the field's taps weighted by the photo
+  if (zoom > 1) {
+    if (S.d_guide) HIPCHK(h, launch_session_render_guided_zoom(S.arr.pool, S.d_guide, S.d_views, vw, vh, zoom, d_out, n, st));
+    else HIPCHK(h, launch_session_render_zoom(S.arr.pool, S.d_views, vw, vh, zoom, d_out, n, st));
+  } else if (S.d_guide)   // ian_sessions_reserve_guide: the same windows, the field's taps weighted by the photo
     HIPCHK(h, launch_session_render_guided(S.arr.pool, S.d_guide, S.d_views, vw, vh, d_out, n, st));
   else
     HIPCHK(h, launch_session_render(S.arr.pool, S.d_views, vw, vh, d_out, n, st));
@@ -1030,6 +1045,8 @@ struct BrushWindows {
   const ian_canvas_window* windows;    // CANVAS: [count]
   int count, vw, vh;
   uint8_t* out;
+  int zoom = 1;               // vw x vh is the size at 1/zoom (DESIGN.md 4.14)
+  const char* fn = nullptr;   // the entry's name in messages; nullptr: the one session_brush derives from kind
 };
 // A brush, clone or stroke call after its checks, its table filled in the shadow (edit_table_begin): everything it enqueues.
 struct EditCall {
@@ -1105,8 +1122,8 @@ int edit_passes(ian_handle* h, const EditCall& C, uint8_t* shown, void* stream) 
     if (C.next) S.hist[id] = C.next[i];
     session_latent_written(S, id, false);
   }
-  if (W.kind == W.VIEWS && (rc = session_render_enqueue(h, W.count, W.views, W.vw, W.vh, win.dev, st))) return rc;
-  if (W.kind == W.CANVAS && (rc = canvas_compose_enqueue(h, W.count, W.windows, W.vw, W.vh, win.dev, st))) return rc;
+  if (W.kind == W.VIEWS && (rc = session_render_enqueue(h, W.count, W.views, W.vw, W.vh, win.dev, st, W.zoom))) return rc;
+  if (W.kind == W.CANVAS && (rc = canvas_compose_enqueue(h, W.count, W.windows, W.vw, W.vh, win.dev, st, W.zoom))) return rc;
   if ((rc = session_finish(h, n, sh, false, st, win, win_bytes))) return rc;
   if (edit_plan_resident(P, pass)) session_residency_arm(S, n, C.ids, C.stride);
   return 0;
@@ -1115,7 +1132,7 @@ int edit_passes(ian_handle* h, const EditCall& C, uint8_t* shown, void* stream) 
 // ian_session_brush and its forms: a stroke whose counts are all 1.  tipped: ian_session_brush_tip, one tip index per event (tips)
 int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* shown, void* stream, const BrushWindows& W,
                   bool tipped = false, const int32_t* tips = nullptr) {
-  const char* fn = tipped ? "ian_session_brush_tip"
+  const char* fn = W.fn ? W.fn : tipped ? "ian_session_brush_tip"
                           : (W.kind == W.CANVAS ? "ian_canvas_brush" : (W.kind == W.VIEWS ? "ian_session_brush_view" : "ian_session_brush"));
   static_assert(sizeof(ian_session_event) == 11 * sizeof(int32_t), "ian_session_event is 11 words");
   int rc = session_check(h, fn, n, ev ? &ev->session : nullptr, 11, true, true);
@@ -1129,8 +1146,8 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
   if (tipped && (rc = session_tips_arg(h, fn, tips))) return rc;
   for (int i = 0; tipped && i < n; ++i)
     if ((rc = session_tip_rect(h, fn, i, -1, tips[i], ev[i].c1, ev[i].r1, ev[i].c2, ev[i].r2))) return rc;
-  if (W.kind == W.VIEWS && (rc = session_view_check(h, fn, W.count, W.views, W.vw, W.vh, W.out, ev))) return rc;
-  if (W.kind == W.CANVAS && (rc = canvas_window_check(h, fn, W.count, W.windows, W.vw, W.vh, W.out))) return rc;
+  if (W.kind == W.VIEWS && (rc = session_view_check(h, fn, W.count, W.views, W.vw, W.vh, W.out, ev, W.zoom))) return rc;
+  if (W.kind == W.CANVAS && (rc = canvas_window_check(h, fn, W.count, W.windows, W.vw, W.vh, W.out, W.zoom))) return rc;
   static const int32_t one = 1;
   const EditCall C = edit_call(&ev->session, 11, edit_plan(n, &one, 0, false), tipped, false, nullptr, nullptr, W);
   const EditTable& L = C.tab;
@@ -1328,9 +1345,10 @@ int session_fit(ian_handle* h, int n, const ian_session_fit_item* items, int ste
   return session_finish(h, n, sh, loss_host, st);
 }
 
-int session_render(ian_handle* h, int n, const ian_session_view* views, int vw, int vh, uint8_t* out, void* stream) {
-  if (int rc = session_view_check(h, "ian_session_render", n, views, vw, vh, out, nullptr)) return rc;
-  return window_call(h, n, vw, vh, out, stream, [&](unsigned char* d, hipStream_t st) { return session_render_enqueue(h, n, views, vw, vh, d, st); });
+int session_render(ian_handle* h, const char* fn, int n, const ian_session_view* views, int vw, int vh, int zoom, uint8_t* out, void* stream) {
+  if (int rc = session_view_check(h, fn, n, views, vw, vh, out, nullptr, zoom)) return rc;
+  return window_call(h, n, vw, vh, out, stream,
+                     [&](unsigned char* d, hipStream_t st) { return session_render_enqueue(h, n, views, vw, vh, d, st, zoom); });
 }
 
 int session_read(ian_handle* h, int id, int what, void* out, void* stream) {
@@ -1522,7 +1540,18 @@ int ian_session_open_hires(ian_handle* h, int32_t n, const int32_t* ids, const u
   return h ? session_open(h, n, ids, photos, 0, shown, stream, true) : -1;
 }
 int ian_session_render(ian_handle* h, int32_t n, const ian_session_view* views, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
-  return h ? session_render(h, n, views, vw, vh, out, stream) : -1;
+  return h ? session_render(h, "ian_session_render", n, views, vw, vh, 1, out, stream) : -1;
+}
+int ian_session_zoom(ian_handle* h, int32_t n, const ian_session_view* views, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out,
+                            void* stream) {
+  return h ? session_render(h, "ian_session_zoom", n, views, vw, vh, zoom, out, stream) : -1;
+}
+int ian_session_brush_zoom(ian_handle* h, int32_t n, const ian_session_event* events, const int32_t* tips, uint8_t* shown,
+                                const ian_session_view* views, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out, void* stream) {
+  if (!h) return -1;
+  if (!views) return fail(h, -1, "null pointer passed to ian_session_brush_zoom");
+  const BrushWindows W = {BrushWindows::VIEWS, views, nullptr, n, vw, vh, out, zoom, "ian_session_brush_zoom"};
+  return session_brush(h, n, events, shown, stream, W, tips != nullptr, tips);
 }
 int ian_session_brush_view(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, const ian_session_view* views,
                            int32_t vw, int32_t vh, uint8_t* out, void* stream) {

@@ -1117,4 +1117,407 @@ hipError_t launch_canvas_compose_guided(const SessionCanvases& C, const SessionP
   return hipGetLastError();
 }
 
+// ---- zoomed views (npe_ops.zoom_box_mean over hires_render[_guided] / canvas_compose[_guided]) ----------------------------
+// Output pixel (Y, X) of a window at 1/k is (sum of the k x k block of 1:1 result bytes + k*k/2) / (k*k), the block at source
+// (vy + k*Y, vx + k*X).  The four kernels below are the four window kernels above with the uchar4 store replaced by integer adds: the
+// byte that enters a sum comes from the same device functions in the same float32 expressions (contraction off), so it IS the byte
+// the 1:1 kernel stores, and integer sums are exact in any order.  No 1:1 byte reaches memory; 3 * vw * vh bytes a window are written.
+//   Work split.  A workgroup owns a tile of the SOURCE: `orows` = max(1, band / k) output rows, i.e. k * orows source rows, by at
+// most `tile` source columns, i.e. ow <= (tile / k) & ~3 output columns (a multiple of 4, so a tile starts on an aligned uchar4 of
+// the source and of the output).  blockIdx.x = row group * column tiles + column tile; y, z as in the 1:1 kernel.
+//   Staging.  The source rows of the tile are walked in chunks of at most `band` rows, band = the 1:1 kernel's band height, and each
+// chunk stages exactly what that kernel stages for a band (field_rows / stage_field_rows / stage_gim_rows, canvas_keep_band for the
+// chunk's rows and the tile's columns): 16 source rows at scale 1 tap 18 field rows, which field_rows would silently cap at 10.  The
+// sums stay in LDS across the chunks.
+//   Lanes.  Consecutive lanes load consecutive aligned uchar4 of a source row (box_mean_row's ownership), compute the four result
+// bytes, merge those that fall into the same output pixel and do one LDS add per pixel touched (zoom_add4).  The plain kernels sum
+// a column of source rows in registers first, as box_mean_row does (zoom_chunk): measured on an MI355X, one 1024 x 1024 picture at
+// k = 16 takes 16.1 us so and 24.1 us with one LDS add per source row.  After the last chunk orows * ow / 4 lanes
+// divide and store one uchar4 each (zoom_store).
+//   Sizes.  Plain: band 8, tile 1024 columns (one lane pass per source row at the widest), sums orows * ow <= 8 * 1024 / 4 ints,
+// 8 KB.  Guided (no channel planes in the grid, three channels per lane): band 4, tile 256 columns, so a chunk is one pass of the 256
+// lanes and ONE 1024 x 1024 picture at k = 16 is 64 x 4 = 256 workgroups; sums 3 * 4 * 256 / 4 ints, 3 KB.
+constexpr int ZOOM_MAX = 16;
+constexpr int ZOOM_TILE = 1024, ZOOM_TILE_GUIDED = 256;
+constexpr int ZOOM_SUMS = RENDER_BAND * ZOOM_TILE / 4, ZOOM_SUMS_GUIDED = GUIDE_BAND * ZOOM_TILE_GUIDED / 4;   // per channel; k >= 2
+struct ZoomSplit {
+  int orows, ow_tile, ntiles;
+};
+__host__ __device__ inline ZoomSplit zoom_split(int band, int tile, int k, int vw) {
+  const int ow_tile = (tile / k) & ~3;
+  return ZoomSplit{band / k > 1 ? band / k : 1, ow_tile, (vw + ow_tile - 1) / ow_tile};
+}
+// this workgroup's tile: output rows oy0 .. oy0 + orows - 1, output columns ox0 .. ox0 + ow - 1 of the window
+struct ZoomTileAt {
+  int oy0, orows, ox0, ow;
+};
+__device__ __forceinline__ ZoomTileAt zoom_tile_at(int band, int tile, int k, int vw, int vh) {
+  const ZoomSplit z = zoom_split(band, tile, k, vw);
+  const int grp = blockIdx.x / z.ntiles, t = blockIdx.x - grp * z.ntiles;
+  const int oy0 = grp * z.orows, ox0 = t * z.ow_tile;
+  return ZoomTileAt{oy0, min(z.orows, vh - oy0), ox0, min(z.ow_tile, vw - ox0)};
+}
+// the four result bytes of the aligned uchar4 at source column cx of the tile -> the sums of its output row
+template <typename T>
+__device__ __forceinline__ void zoom_add4(int* row, int cx, int k, const T ob[4]) {
+  int bin = cx / k, r = cx - bin * k, t = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    t += ob[e];
+    if (++r == k) {
+      atomicAdd(&row[bin], t);
+      ++bin;
+      r = 0;
+      t = 0;
+    }
+  }
+  if (r) atomicAdd(&row[bin], t);   // r bytes (at most 4 of them this lane's) of a pixel that goes on in the next uchar4
+}
+// The output rows a chunk of `rows` source rows meets, for the kernels whose lanes sum a column of source rows in registers first
+// (box_mean_row's order): k <= band: the tile is ONE chunk of orows whole output rows, k source rows each; k > band: the tile is one
+// output row and every chunk a part of it.  A lane's work item is (output row of the chunk, aligned uchar4 column): `each` source rows.
+struct ZoomChunk {
+  int nor, each;
+};
+__device__ __forceinline__ ZoomChunk zoom_chunk(int band, int k, int orows, int rows) {
+  const int nor = k <= band ? orows : 1;
+  return ZoomChunk{nor, rows / nor};
+}
+// sum[orows][ow] -> the tile's bytes of one output plane (u8[vh][vw]): (sum + k*k/2) / (k*k), one uchar4 per lane
+__device__ __forceinline__ void zoom_store(const int* sum, const ZoomTileAt& z, int k, unsigned char* plane, int vw) {
+  const int L = z.ow >> 2, d = k * k, half = d / 2;
+  for (int j = threadIdx.x; j < z.orows * L; j += 256) {
+    const int ry = j / L, q = (j - ry * L) * 4;
+    const int* p = sum + ry * z.ow + q;
+    *reinterpret_cast<uchar4*>(plane + (size_t)(z.oy0 + ry) * vw + z.ox0 + q) =
+        make_uchar4((unsigned char)((p[0] + half) / d), (unsigned char)((p[1] + half) / d), (unsigned char)((p[2] + half) / d),
+                    (unsigned char)((p[3] + half) / d));
+  }
+}
+
+// session_render_kernel at 1/k.  grid (row groups * column tiles, 3, n)
+__global__ __launch_bounds__(256) void session_render_zoom_kernel(SessionPool P, const int* __restrict__ views, int vw, int vh, int k,
+                                                                  unsigned char* __restrict__ out) {
+  __shared__ float f[(RENDER_BAND + 2) * 64];
+  __shared__ int sum[ZOOM_SUMS];
+  const int s = P.scale, S = 64 * s;
+  const int c = blockIdx.y, i = blockIdx.z;
+  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
+  const ZoomTileAt z = zoom_tile_at(RENDER_BAND, ZOOM_TILE, k, vw, vh);
+  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile in the picture
+  for (int j = threadIdx.x; j < z.orows * z.ow; j += 256) sum[j] = 0;
+  const int kind = P.kind[id];
+  const unsigned char* src = P.src + ((size_t)id * 3 + c) * S * S;
+  const float* field = P.field + ((size_t)id * 3 + c) * (64 * 64);
+  for (int y0 = 0; y0 < R; y0 += RENDER_BAND) {
+    const int rows = min(RENDER_BAND, R - y0);
+    const FieldRows fr = field_rows(Y0 + y0, Y0 + y0 + rows - 1, s);
+    stage_field_rows(f, field, fr);
+    __syncthreads();   // the first one also publishes the zeroed sums
+    const ZoomChunk ch = zoom_chunk(RENDER_BAND, k, z.orows, rows);
+    for (int idx = threadIdx.x; idx < ch.nor * L; idx += 256) {
+      const int oy = idx / L, cx = (idx - oy * L) * 4;
+      int col[4] = {0, 0, 0, 0};
+      const int Yb = Y0 + y0 + oy * ch.each;
+      uchar4 pvs[RENDER_BAND];   // the item's source bytes first, every load in flight at once: the rows are at most RENDER_BAND
+#pragma unroll
+      for (int r = 0; r < RENDER_BAND; ++r)
+        pvs[r] = kind == 0 && r < ch.each ? *reinterpret_cast<const uchar4*>(src + (size_t)(Yb + r) * S + X0 + cx) : make_uchar4(0, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < RENDER_BAND; ++r) {
+        if (r >= ch.each) break;
+        const int Y = Yb + r;
+        int r0, r1;
+        float ty;
+        hires_taps(Y, s, r0, r1, ty);
+        const float* top = f + (r0 - fr.fr0) * 64;
+        const float* bot = f + (r1 - fr.fr0) * 64;
+        const uchar4 pv = pvs[r];
+        const unsigned char pb[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = field_bilinear(top, bot, s, X0 + cx + e, ty);
+          col[e] += round_u8(kind == 0 ? (float)pb[e] + 127.5f * v : 127.5f * (v + 1.0f));
+        }
+      }
+      zoom_add4(sum + ((y0 + oy * ch.each) / k) * z.ow, cx, k, col);
+    }
+    __syncthreads();   // f is restaged; after the last chunk: the sums are complete
+  }
+  zoom_store(sum, z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
+}
+// what the four zoomed launchers check alike: k, the output window, the result
+static bool zoom_args_ok(int n, int k, int vw, int vh, int src_w, int src_h, const void* win, const unsigned char* out) {
+  return n >= 1 && n <= 65535 && k >= 2 && k <= ZOOM_MAX && win && out && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && vw >= 4 &&
+         (vw & 3) == 0 && vh >= 1 && vw <= src_w / k && vh <= src_h / k;
+}
+static dim3 zoom_grid(int band, int tile, int k, int vw, int vh, int planes, int n) {
+  const ZoomSplit z = zoom_split(band, tile, k, vw);
+  return dim3((unsigned)((vh + z.orows - 1) / z.orows) * z.ntiles, planes, n);
+}
+hipError_t launch_session_render_zoom(const SessionPool& P, const int* views, int vw, int vh, int zoom, unsigned char* out, int n,
+                                      hipStream_t s) {
+  const int S = 64 * P.scale;
+  if (P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || !zoom_args_ok(n, zoom, vw, vh, S, S, views, out))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_render_zoom_kernel, zoom_grid(RENDER_BAND, ZOOM_TILE, zoom, vw, vh, 3, n), dim3(256), 0, s, P, views, vw, vh,
+                     zoom, out);
+  return hipGetLastError();
+}
+
+// session_render_guided_kernel at 1/k.  grid (row groups * column tiles, 1, n); sum[c] is channel c's orows x ow
+__global__ __launch_bounds__(256) void session_render_guided_zoom_kernel(SessionPool P, const float* __restrict__ table,
+                                                                         const int* __restrict__ views, int vw, int vh, int k,
+                                                                         unsigned char* __restrict__ out) {
+  __shared__ GuideFieldRows f;
+  __shared__ __align__(4) GuideGimRows g;
+  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
+  __shared__ int sum[3][ZOOM_SUMS_GUIDED];
+  const int s = P.scale, S = 64 * s;
+  const int i = blockIdx.z;
+  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
+  const ZoomTileAt z = zoom_tile_at(GUIDE_BAND, ZOOM_TILE_GUIDED, k, vw, vh);
+  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;
+  for (int j = threadIdx.x; j < 3 * ZOOM_SUMS_GUIDED; j += 256) (&sum[0][0])[j] = 0;
+  for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
+  const int kind = P.kind[id];
+  const size_t plane = (size_t)S * S;
+  const unsigned char* src = P.src + (size_t)id * 3 * plane;
+  for (int y0 = 0; y0 < R; y0 += GUIDE_BAND) {
+    const int rows = min(GUIDE_BAND, R - y0);
+    const FieldRows fr = field_rows(Y0 + y0, Y0 + y0 + rows - 1, s);   // at most ceil((GUIDE_BAND - 1) / s) + 2 <= GUIDE_BAND + 2 rows
+    for (int c = 0; c < 3; ++c) {
+      stage_field_rows(f[c], P.field + ((size_t)id * 3 + c) * (64 * 64), fr);
+      stage_gim_rows(g[c], P.gim + ((size_t)id * 3 + c) * (64 * 64), fr);
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
+      const int ry = idx / L, cx = (idx - ry * L) * 4;
+      const int Y = Y0 + y0 + ry, X = X0 + cx;
+      int r0, r1;
+      float ty;
+      hires_taps(Y, s, r0, r1, ty);
+      const int o0 = (r0 - fr.fr0) * 64, o1 = (r1 - fr.fr0) * 64;
+      int pb[3][4] = {};
+      unsigned char ob[3][4];
+      if (kind == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * plane + (size_t)Y * S + X);
+          pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (kind == 0) {
+          float v[3];
+          guide_sample(f, g, tab, o0, o1, s, X + e, ty, pb[0][e], pb[1][e], pb[2][e], v);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) ob[c][e] = round_u8((float)pb[c][e] + 127.5f * v[c]);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) ob[c][e] = round_u8(127.5f * (field_bilinear(f[c] + o0, f[c] + o1, s, X + e, ty) + 1.0f));
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) zoom_add4(sum[c] + ((y0 + ry) / k) * z.ow, cx, k, ob[c]);
+    }
+    __syncthreads();
+  }
+  for (int c = 0; c < 3; ++c) zoom_store(sum[c], z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
+}
+hipError_t launch_session_render_guided_zoom(const SessionPool& P, const float* table, const int* views, int vw, int vh, int zoom,
+                                             unsigned char* out, int n, hipStream_t s) {
+  const int S = 64 * P.scale;
+  if (P.scale < 1 || P.scale > 16 || !P.src || !P.gim || !P.field || !P.kind || !table || !zoom_args_ok(n, zoom, vw, vh, S, S, views, out))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_render_guided_zoom_kernel, zoom_grid(GUIDE_BAND, ZOOM_TILE_GUIDED, zoom, vw, vh, 1, n), dim3(256), 0, s, P,
+                     table, views, vw, vh, zoom, out);
+  return hipGetLastError();
+}
+
+// canvas_keep_band's field rows of one kept placement for rows Y0..Y1 of the canvas (a chunk of the band it was kept for)
+__device__ __forceinline__ FieldRows canvas_chunk_rows(const CanvasKept& q, int Y0, int Y1) {
+  const int a = max(Y0, q.oy), b = min(Y1, q.oy + 64 * q.s - 1);
+  return a <= b ? field_rows(a - q.oy, b - q.oy, q.s) : FieldRows{0, 0};
+}
+// canvas_compose_kernel at 1/k.  grid (row groups * column tiles, 3, n); lane 0 keeps the placements once, for the tile's rows and
+// columns (a walk of the table in global memory by one lane: not once per chunk), and per chunk lane p says which rows of kept
+// placement p the chunk taps
+__global__ __launch_bounds__(256) void canvas_compose_zoom_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ windows, int vw,
+                                                                  int vh, int k, unsigned char* __restrict__ out) {
+  __shared__ float f[CANVAS_MAX_PLACED][(RENDER_BAND + 2) * 64];
+  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
+  __shared__ FieldRows frows[CANVAS_MAX_PLACED];
+  __shared__ int nkept;
+  __shared__ int sum[ZOOM_SUMS];
+  const int c = blockIdx.y, i = blockIdx.z;
+  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
+  const ZoomTileAt z = zoom_tile_at(RENDER_BAND, ZOOM_TILE, k, vw, vh);
+  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile on the canvas
+  for (int j = threadIdx.x; j < z.orows * z.ow; j += 256) sum[j] = 0;
+  const unsigned char* src = C.pix + ((size_t)cv * 3 + c) * C.max_h * C.max_w;
+  if (threadIdx.x == 0) nkept = canvas_keep_band(C, P, cv, X0, k * z.ow, Y0, Y0 + R - 1, kept, frows);   // once: the tile's rows
+  __syncthreads();
+  const int nk = nkept;
+  for (int y0 = 0; y0 < R; y0 += RENDER_BAND) {
+    const int rows = min(RENDER_BAND, R - y0);
+    if (R > RENDER_BAND) {   // several chunks: lane p says which field rows THIS chunk taps inside kept placement p (none: n = 0)
+      if (threadIdx.x < nk) frows[threadIdx.x] = canvas_chunk_rows(kept[threadIdx.x], Y0 + y0, Y0 + y0 + rows - 1);
+      __syncthreads();
+    }
+    for (int p = 0; p < nk; ++p) stage_field_rows(f[p], P.field + ((size_t)kept[p].id * 3 + c) * (64 * 64), frows[p]);
+    __syncthreads();
+    const ZoomChunk ch = zoom_chunk(RENDER_BAND, k, z.orows, rows);
+    for (int idx = threadIdx.x; idx < ch.nor * L; idx += 256) {
+      const int oy = idx / L, cx = (idx - oy * L) * 4;
+      const int X = X0 + cx;
+      int col[4] = {0, 0, 0, 0};
+      const int Yb = Y0 + y0 + oy * ch.each;
+      uchar4 pvs[RENDER_BAND];   // the item's canvas bytes first, every load in flight at once: the rows are at most RENDER_BAND
+#pragma unroll
+      for (int r = 0; r < RENDER_BAND; ++r)
+        pvs[r] = r < ch.each ? *reinterpret_cast<const uchar4*>(src + (size_t)(Yb + r) * C.max_w + X) : make_uchar4(0, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < RENDER_BAND; ++r) {
+        if (r >= ch.each) break;
+        const int Y = Yb + r;
+        const uchar4 pv = pvs[r];
+        float acc[4] = {(float)pv.x, (float)pv.y, (float)pv.z, (float)pv.w};
+        for (int p = 0; p < nk; ++p) {
+          const CanvasKept q = kept[p];
+          const int S = 64 * q.s, uy = Y - q.oy;
+          if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
+          const int f2s = 2 * C.feather * q.s, fr0 = frows[p].fr0;
+          int r0, r1;
+          float ty;
+          hires_taps(uy, q.s, r0, r1, ty);
+          const float* top = f[p] + (r0 - fr0) * 64;
+          const float* bot = f[p] + (r1 - fr0) * 64;
+          const float wy = canvas_ramp1(uy, S, f2s);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int ux = X + e - q.ox;
+            if (ux < 0 || ux >= S) continue;
+            const float v = field_bilinear(top, bot, q.s, ux, ty);
+            const float w = wy * canvas_ramp1(ux, S, f2s);
+            if (q.kind == 0) {
+              acc[e] = acc[e] + (127.5f * v) * w;
+            } else {
+              const float tv = 127.5f * (v + 1.0f);
+              acc[e] = w == 1.0f ? tv : acc[e] + (tv - acc[e]) * w;
+            }
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) col[e] += round_u8(acc[e]);
+      }
+      zoom_add4(sum + ((y0 + oy * ch.each) / k) * z.ow, cx, k, col);
+    }
+    __syncthreads();   // kept, frows and f are rewritten; after the last chunk: the sums are complete
+  }
+  zoom_store(sum, z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
+}
+hipError_t launch_canvas_compose_zoom(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, int zoom,
+                                      unsigned char* out, int n, hipStream_t s) {
+  if (!canvases_ok(C) || !P.field || !P.kind || !zoom_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(canvas_compose_zoom_kernel, zoom_grid(RENDER_BAND, ZOOM_TILE, zoom, vw, vh, 3, n), dim3(256), 0, s, C, P, windows, vw,
+                     vh, zoom, out);
+  return hipGetLastError();
+}
+
+// canvas_compose_guided_kernel at 1/k.  grid (row groups * column tiles, 1, n)
+__global__ __launch_bounds__(256) void canvas_compose_guided_zoom_kernel(SessionCanvases C, SessionPool P, const float* __restrict__ table,
+                                                                         const int* __restrict__ windows, int vw, int vh, int k,
+                                                                         unsigned char* __restrict__ out) {
+  __shared__ GuideFieldRows f[CANVAS_MAX_PLACED];
+  __shared__ __align__(4) GuideGimRows g[CANVAS_MAX_PLACED];
+  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
+  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
+  __shared__ FieldRows frows[CANVAS_MAX_PLACED];
+  __shared__ int nkept;
+  __shared__ int sum[3][ZOOM_SUMS_GUIDED];
+  const int i = blockIdx.z;
+  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
+  const ZoomTileAt z = zoom_tile_at(CANVAS_GUIDE_BAND, ZOOM_TILE_GUIDED, k, vw, vh);
+  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;
+  for (int j = threadIdx.x; j < 3 * ZOOM_SUMS_GUIDED; j += 256) (&sum[0][0])[j] = 0;
+  for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
+  const size_t cplane = (size_t)C.max_h * C.max_w;
+  const unsigned char* src = C.pix + (size_t)cv * 3 * cplane;
+  for (int y0 = 0; y0 < R; y0 += CANVAS_GUIDE_BAND) {
+    const int rows = min(CANVAS_GUIDE_BAND, R - y0);
+    if (threadIdx.x == 0) {
+      const int nk = canvas_keep_band(C, P, cv, X0, k * z.ow, Y0 + y0, Y0 + y0 + rows - 1, kept, frows);
+      for (int p = 0; p < nk; ++p) frows[p].n = min(frows[p].n, CANVAS_GUIDE_BAND + 2);   // 4 source rows tap at most 5 field rows
+      nkept = nk;
+    }
+    __syncthreads();
+    const int nk = nkept;
+    for (int p = 0; p < nk; ++p)
+      for (int c = 0; c < 3; ++c) {
+        stage_field_rows(f[p][c], P.field + ((size_t)kept[p].id * 3 + c) * (64 * 64), frows[p]);
+        stage_gim_rows(g[p][c], P.gim + ((size_t)kept[p].id * 3 + c) * (64 * 64), frows[p]);
+      }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
+      const int ry = idx / L, cx = (idx - ry * L) * 4;
+      const int Y = Y0 + y0 + ry, X = X0 + cx;
+      int pb[3][4];
+      float acc[3][4];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * cplane + (size_t)Y * C.max_w + X);
+        pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[c][e] = (float)pb[c][e];
+      }
+      for (int p = 0; p < nk; ++p) {
+        const CanvasKept q = kept[p];
+        const int S = 64 * q.s, uy = Y - q.oy;
+        if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
+        const int f2s = 2 * C.feather * q.s, fr0 = frows[p].fr0;
+        int r0, r1;
+        float ty;
+        hires_taps(uy, q.s, r0, r1, ty);
+        const int o0 = (r0 - fr0) * 64, o1 = (r1 - fr0) * 64;
+        const float wy = canvas_ramp1(uy, S, f2s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int ux = X + e - q.ox;
+          if (ux < 0 || ux >= S) continue;
+          const float w = wy * canvas_ramp1(ux, S, f2s);
+          if (q.kind == 0) {
+            float v[3];
+            guide_sample(f[p], g[p], tab, o0, o1, q.s, ux, ty, pb[0][e], pb[1][e], pb[2][e], v);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c][e] = acc[c][e] + (127.5f * v[c]) * w;
+          } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const float tv = 127.5f * (field_bilinear(f[p][c] + o0, f[p][c] + o1, q.s, ux, ty) + 1.0f);
+              acc[c][e] = w == 1.0f ? tv : acc[c][e] + (tv - acc[c][e]) * w;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const unsigned char ob[4] = {round_u8(acc[c][0]), round_u8(acc[c][1]), round_u8(acc[c][2]), round_u8(acc[c][3])};
+        zoom_add4(sum[c] + ((y0 + ry) / k) * z.ow, cx, k, ob);
+      }
+    }
+    __syncthreads();
+  }
+  for (int c = 0; c < 3; ++c) zoom_store(sum[c], z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
+}
+hipError_t launch_canvas_compose_guided_zoom(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw,
+                                             int vh, int zoom, unsigned char* out, int n, hipStream_t s) {
+  if (!canvases_ok(C) || !P.field || !P.kind || !P.gim || !table || !zoom_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(canvas_compose_guided_zoom_kernel, zoom_grid(CANVAS_GUIDE_BAND, ZOOM_TILE_GUIDED, zoom, vw, vh, 1, n), dim3(256), 0, s,
+                     C, P, table, windows, vw, vh, zoom, out);
+  return hipGetLastError();
+}
+
 }  // namespace ian

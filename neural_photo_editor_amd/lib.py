@@ -55,6 +55,7 @@ EXPORTS = (
     "ian_sessions_reserve_canvas", "ian_canvas_put", "ian_canvas_place", "ian_canvas_compose", "ian_canvas_brush", "ian_canvas_commit",
     "ian_canvas_read", "ian_canvas_placements",
     "ian_sessions_reserve_edges", "ian_sessions_edges",
+    "ian_session_zoom", "ian_session_brush_zoom", "ian_compose_zoom", "ian_compose_brush_zoom",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -154,6 +155,10 @@ def load_library():
     lib.ian_canvas_placements.argtypes = [vp, i32, C.POINTER(CanvasPlacement), fp]
     lib.ian_sessions_reserve_edges.argtypes = [vp, fp, i32]
     lib.ian_sessions_edges.argtypes = [vp, fp]
+    lib.ian_session_zoom.argtypes = [vp, i32, C.POINTER(SessionView), i32, i32, i32, fp, vp]
+    lib.ian_session_brush_zoom.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, fp, C.POINTER(SessionView), i32, i32, i32, fp, vp]
+    lib.ian_compose_zoom.argtypes = [vp, i32, C.POINTER(CanvasWindow), i32, i32, i32, fp, vp]
+    lib.ian_compose_brush_zoom.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, i32, C.POINTER(CanvasWindow), i32, i32, i32, fp, vp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -435,6 +440,16 @@ class Handle:
         self._check(self.lib.ian_session_brush_view(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
                                                     views, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
 
+    def session_zoom(self, views, vw, vh, zoom, out, stream=None):
+        """ian_session_zoom: session_render at 1/zoom; vw, vh = the output size, out u8[n,3,vh,vw]."""
+        self._check(self.lib.ian_session_zoom(self._h, len(views), views, int(vw), int(vh), int(zoom), _ptr(out), C.c_void_p(stream or 0)))
+
+    def session_brush_zoom(self, events, tips, shown, views, vw, vh, zoom, out, stream=None):
+        """ian_session_brush_zoom: session_brush_view (tips None) or session_brush_tip with views (tips int32[n]) at 1/zoom."""
+        self._check(self.lib.ian_session_brush_zoom(self._h, len(events), events, _ptr(tips) if tips is not None else C.c_void_p(0),
+                                                    _ptr(shown) if shown is not None else C.c_void_p(0), views, int(vw), int(vh),
+                                                    int(zoom), _ptr(out), C.c_void_p(stream or 0)))
+
     def sessions_reserve_guide(self, table=None):
         """ian_sessions_reserve_guide; table = 766 float32 range weights (npe_ops.guide_table), or None to switch the guide off."""
         if table is None:
@@ -610,6 +625,15 @@ class Handle:
         """ian_canvas_brush; events = a ctypes array of SessionEvent, windows = one of CanvasWindow (m = its length), out u8[m,3,vh,vw]."""
         self._check(self.lib.ian_canvas_brush(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
                                               len(windows), windows, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def compose_zoom(self, windows, vw, vh, zoom, out, stream=None):
+        """ian_compose_zoom: canvas_compose at 1/zoom; vw, vh = the output size, out u8[n,3,vh,vw]."""
+        self._check(self.lib.ian_compose_zoom(self._h, len(windows), windows, int(vw), int(vh), int(zoom), _ptr(out), C.c_void_p(stream or 0)))
+
+    def compose_brush_zoom(self, events, windows, vw, vh, zoom, out, shown=None, stream=None):
+        """ian_compose_brush_zoom: canvas_brush with the windows at 1/zoom."""
+        self._check(self.lib.ian_compose_brush_zoom(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
+                                                    len(windows), windows, int(vw), int(vh), int(zoom), _ptr(out), C.c_void_p(stream or 0)))
 
     def canvas_commit(self, canvas, shown=None, stream=None):
         """ian_canvas_commit; shown u8[k,3,64,64] for the k sessions placed on the canvas, or None."""

@@ -378,6 +378,61 @@ def canvas_compose_guided(canvas, placed, f, vx, vy, vw, vh, table):
     return _canvas_compose(canvas, placed, f, vx, vy, vw, vh, table)
 
 
+# ---- zoomed views (ian_session_zoom / ian_compose_zoom, include/ian.h) ------------------------------------------------
+# A view at 1/k is the exact integer box mean of the full-resolution result: the four functions above give the bytes of the source
+# window (vx, vy, k*vw, k*vh), rounded to uint8 per pixel, and zoom_box_mean averages whole k x k blocks of them with
+# hires_downsample's rounding.  These functions ARE the specification; the device matches them bit for bit without ever writing the
+# full-resolution bytes.
+ZOOM_MAX = 16
+
+
+def _zoom(k):
+    if int(k) != k or not 1 <= int(k) <= ZOOM_MAX:
+        raise ValueError("zoom must be an integer in 1..%d, got %r" % (ZOOM_MAX, k))
+    return int(k)
+
+
+def zoom_box_mean(img_u8, k):
+    """uint8 (3, k*vh, k*vw) -> uint8 (3, vh, vw): (sum of the k x k block + (k*k)//2) // (k*k), half rounds up."""
+    k = _zoom(k)
+    a = np.asarray(img_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[0] != 3 or a.shape[1] % k or a.shape[2] % k or not a.shape[1] or not a.shape[2]:
+        raise ValueError("a picture to view at 1/%d is uint8 (3, %d*vh, %d*vw), got %s %s" % (k, k, k, a.dtype, a.shape))
+    vh, vw = a.shape[1] // k, a.shape[2] // k
+    total = a.reshape(3, vh, k, vw, k).sum(axis=(2, 4), dtype=np.int64)
+    return np.uint8((total + (k * k) // 2) // (k * k))
+
+
+def zoom_window(w, h, k):
+    """The largest (vw, vh) a w x h picture shows whole at 1/k: vw % 4 == 0, k*vw <= w, k*vh <= h."""
+    k = _zoom(k)
+    return (int(w) // k) & ~3, int(h) // k
+
+
+def hires_render_zoom(src, field, kind, s, vx, vy, vw, vh, k):
+    """hires_render of the source window (vx, vy, k*vw, k*vh) at 1/k -> uint8 (3, vh, vw)."""
+    k = _zoom(k)
+    return zoom_box_mean(hires_render(src, field, kind, s, vx, vy, k * int(vw), k * int(vh)), k)
+
+
+def hires_render_guided_zoom(src, gim, field, kind, s, vx, vy, vw, vh, k, table):
+    """hires_render_guided of the source window (vx, vy, k*vw, k*vh) at 1/k -> uint8 (3, vh, vw)."""
+    k = _zoom(k)
+    return zoom_box_mean(hires_render_guided(src, gim, field, kind, s, vx, vy, k * int(vw), k * int(vh), table), k)
+
+
+def canvas_compose_zoom(canvas, placed, f, vx, vy, vw, vh, k):
+    """canvas_compose of the source window (vx, vy, k*vw, k*vh) at 1/k -> uint8 (3, vh, vw)."""
+    k = _zoom(k)
+    return zoom_box_mean(canvas_compose(canvas, placed, f, vx, vy, k * int(vw), k * int(vh)), k)
+
+
+def canvas_compose_guided_zoom(canvas, placed, f, vx, vy, vw, vh, k, table):
+    """canvas_compose_guided of the source window (vx, vy, k*vw, k*vh) at 1/k -> uint8 (3, vh, vw)."""
+    k = _zoom(k)
+    return zoom_box_mean(canvas_compose_guided(canvas, placed, f, vx, vy, k * int(vw), k * int(vh), table), k)
+
+
 # ---- local edits (ian_sessions_reserve_local / ian_session_local, include/ian.h; DESIGN.md 4.4) -------------------------------------
 # NPE.py declares USER_MASK "currently not implemented" (NPE.py:58-59, :221), offers gk (NPE.py:167-175) for "changes to MASK ... more
 # localized to the brush location" and dampen (NPE.py:184-189) as a commented-out alternative for D (NPE.py:227, :298).  These four

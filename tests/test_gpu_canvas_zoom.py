@@ -1,0 +1,230 @@
+"""Zoomed views of canvases (ian_compose_zoom, ian_compose_brush_zoom; EditSessions.compose / brush_compose with a zoom; DESIGN.md
+4.14).  Every comparison is np.array_equal against npe_ops.zoom_box_mean of npe_ops.canvas_compose / canvas_compose_guided of the
+whole canvas, computed once per case (a window is its crop: the host test), whose inputs (the canvas, and FIELD, FIELD_KIND and GIM of
+every placed session) are read back from the pool after paint events that leave non-zero fields.  Every case runs plain and under
+reserve_canvas_guide(sigma).  The main canvas is 200 x 136 in a 256 x 160 reservation, so a row's stride is not its width."""
+import numpy as np
+import pytest
+
+from neural_photo_editor_amd import lib as L
+from neural_photo_editor_amd import npe_ops as N
+from oracle import ian_oracle as O
+from session_helpers import KEYS64, assert_fields, model_pool, refused, session_events as events
+
+pytestmark = pytest.mark.gpu
+
+CAP = 16
+W, H = 200, 136
+MAXW, MAXH = 256, 160
+SIGMAS = [None, 8.0]
+KEYS = KEYS64 + ("FIELD", "FIELD_KIND")
+
+_cache = {}
+
+
+def picture(w, h, seed):
+    """A smooth picture plus noise, as session_helpers.sources makes them, at any size."""
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = 127.5 + 100.0 * np.sin(xx / 9.0 + rs.uniform(0, 6, (3, 1, 1))) * np.cos(yy / 11.0 + rs.uniform(0, 6, (3, 1, 1)))
+    return np.uint8(np.clip(base + rs.randint(-40, 41, (3, h, w)), 0, 255))
+
+
+def pools(sigma, f=4, max_w=MAXW, max_h=MAXH):
+    """(model, the pool with one fresh canvas reservation, plain or edge-aware, model, a plain pool, the table or None)."""
+    if "p" not in _cache:
+        _cache["p"] = model_pool("IAN_simple", capacity=CAP) + model_pool("IAN_simple", capacity=CAP)
+    mh, sh, mp, sp = _cache["p"]
+    if sh.canvases:
+        sh.reserve_canvases(0)
+    if not sh.scale:
+        sh.reserve_hires(1)
+    sh.reserve_canvases(1, max_w, max_h, f)
+    table = None
+    if sigma is not None:
+        table = N.guide_table(sigma)
+        sh.reserve_canvas_guide(table=table)
+    return mh, sh, mp, sp, table
+
+
+def Wn(items):
+    w = (L.CanvasWindow * len(items))()
+    for d, (c, x, y) in zip(w, items):
+        d.canvas, d.x, d.y = c, x, y
+    return w
+
+
+def paint_all(sh, ids, seed=0):
+    """One paint event per session that leaves a non-zero field."""
+    n = len(ids)
+    boxes = np.array([(6 + 5 * (k % 4), 8 + 3 * (k % 5), 34 + 3 * (k % 6), 40 + 2 * (k % 7)) for k in range(n)])
+    sh.paint(ids, boxes, np.random.RandomState(seed).randint(0, 256, (n, 3)), weight=0.5)
+    for i in ids:
+        assert sh.read(i)["FIELD"].any(), i
+
+
+def whole_compose(sh, c, table):
+    """npe_ops' compose of the whole canvas 0 from what the pool holds -> uint8 (3,h,w)."""
+    placed = []
+    for (i, x, y, s) in sh.placements(0):
+        got = sh.read(i)
+        placed.append((x, y, s, got["FIELD"], int(got["FIELD_KIND"])) + (() if table is None else (got["GIM"],)))
+    if table is None:
+        return N.canvas_compose(c, placed, sh.feather, 0, 0, c.shape[2], c.shape[1])
+    return N.canvas_compose_guided(c, placed, sh.feather, 0, 0, c.shape[2], c.shape[1], table)
+
+
+def assert_zooms(sh, whole, wins, tag):
+    """Every window (x, y, vw, vh, k) against the box mean of its source window of `whole`."""
+    for (x, y, vw, vh, k) in wins:
+        out = sh.compose([0], (x, y), (vw, vh), zoom=k)
+        assert out.shape == (1, 3, vh, vw) and out.dtype == np.uint8
+        want = N.zoom_box_mean(np.ascontiguousarray(whole[:, y:y + k * vh, x:x + k * vw]), k)
+        assert np.array_equal(out[0], want), (tag, (x, y, vw, vh, k))
+
+
+# ---- 1. parity --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma", SIGMAS)
+@pytest.mark.parametrize("f", [4, 0])
+def test_overlapping_placements_of_both_kinds_at_every_zoom(f, sigma):
+    _, sh, _, _, table = pools(sigma, f=f)
+    c = picture(W, H, 100 + f)
+    sh.canvas_put(0, c)
+    squares = {3: (37, 3, 2), 11: (100, 60, 1), 6: (5, 70, 1)}                 # 11 overlaps 3; 6 goes to sample mode
+    ids = list(squares)
+    sh.place(ids, 0, [squares[i][:2] for i in ids], [squares[i][2] for i in ids])
+    sh.sample([6], O.make_latents(1, seed=5))
+    paint_all(sh, [3, 11], f)
+    whole = whole_compose(sh, c, table)
+    assert (whole != c).any() and N.zoom_window(W, H, 2) == (100, 68) and N.zoom_window(W, H, 3) == (64, 45) and N.zoom_window(W, H, 16) == (12, 8)
+    wins = [(0, 0, 100, 68, 2),                                               # the whole canvas
+            (0, 0, 64, 45, 3), (8, 1, 64, 45, 3),                             # ... ends at the last column and the last row
+            (0, 0, 12, 8, 16), (8, 8, 12, 8, 16),
+            (168, 0, 16, 30, 2)]                                              # meets no square
+    assert_zooms(sh, whole, wins, (f, sigma))
+    assert np.array_equal(whole[:, :60, 168:], c[:, :60, 168:])               # ... so that one is the box mean of the canvas
+    assert np.array_equal(sh.canvas_read(0), c)                               # a compose stores nothing
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_eight_placements_under_one_output_row(sigma):
+    """Eight overlapping scale-1 squares on a 96 x 80 canvas at zoom 16: every chunk of an output row's 16 source rows keeps all 8,
+    the kernels' whole LDS budget."""
+    _, sh, _, _, table = pools(sigma)
+    c = picture(96, 80, 31)
+    sh.canvas_put(0, c)
+    ids = [1, 3, 4, 7, 8, 10, 12, 15]
+    sh.place(ids, 0, [(4 * k, 2 * k) for k in range(8)], 1)
+    paint_all(sh, ids, 2)
+    assert len(sh.placements(0)) == 8
+    whole = whole_compose(sh, c, table)
+    assert_zooms(sh, whole, [(0, 0, 4, 5, 16), (32, 0, 4, 5, 16)], "eight")
+    assert (N.zoom_box_mean(whole, 16) != N.zoom_box_mean(c, 16)).any()
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_a_scale_16_placement_on_a_large_canvas(sigma):
+    mh, sh, _, _, table = pools(sigma, max_w=1028, max_h=1024)
+    try:
+        c = picture(1028, 1024, 16)
+        sh.canvas_put(0, c)
+        sh.place([5], 0, (3, 0), 16)
+        sh.paint([5], (20, 20, 44, 44), (240, 30, 30), weight=0.5)
+        whole = whole_compose(sh, c, table)
+        assert N.zoom_window(1028, 1024, 16) == (64, 64) and N.zoom_window(1028, 1024, 7) == (144, 146)
+        assert_zooms(sh, whole, [(0, 0, 64, 64, 16), (0, 0, 144, 146, 7), (20, 2, 144, 146, 7)], "large")
+        assert (N.zoom_box_mean(whole[:, :, :1024], 16) != N.zoom_box_mean(c[:, :, :1024], 16)).any()
+    finally:
+        sh.reserve_canvases(0)
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_the_zoom_entry_at_zoom_1_is_the_compose(sigma):
+    mh, sh, _, _, _ = pools(sigma)
+    sh.canvas_put(0, picture(W, H, 3))
+    sh.place([2], 0, (37, 3), 2)
+    paint_all(sh, [2], 4)
+    w = Wn([(0, 8, 1), (0, 100, 60)])
+    a, b = np.zeros((2, 3, 45, 64), np.uint8), np.ones((2, 3, 45, 64), np.uint8)
+    mh.handle.canvas_compose(w, 64, 45, a)
+    mh.handle.compose_zoom(w, 64, 45, 1, b)
+    assert np.array_equal(a, b)
+
+
+# ---- 2. one submission --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_brush_compose_at_a_zoom_is_brush_then_compose_at_that_zoom(sigma):
+    _, sh, _, _, _ = pools(sigma)
+    c = picture(W, H, 9)
+    ids, where, scales = [1, 7], [(37, 3), (100, 60)], [2, 1]
+    boxes, colours = np.array([(10, 12, 30, 28), (33, 5, 50, 20)]), np.array([(250, 20, 20), (10, 240, 90)])
+    win = ([0, 0], [(0, 0), (8, 1)], (64, 45))
+
+    def start():
+        sh.canvas_put(0, c)                                                   # un-places everything
+        sh.place(ids, 0, where, scales)                                       # ... and the sessions open again on the same box means
+
+    start()
+    got = [sh.brush_compose(ids, boxes, colours, None, 0.5, -1.0, windows=win + (3,)) for _ in range(2)]   # the second hits residency
+    state = [sh.read(i) for i in ids]
+    start()
+    want = [(sh.paint(ids, boxes, colours, weight=0.5), sh.compose(*win, zoom=3)) for _ in range(2)]
+    for step, ((shown, out), (shown_w, out_w)) in enumerate(zip(got, want)):
+        assert np.array_equal(shown, shown_w), step
+        assert out.shape == (2, 3, 45, 64) and np.array_equal(out, out_w), step
+    for a, i in zip(state, ids):
+        assert_fields(a, sh.read(i), KEYS)
+    assert (got[0][1][0] != N.zoom_box_mean(np.ascontiguousarray(c[:, :135, :192]), 3)).any()      # the window shows an edit
+    assert (got[0][1] != got[1][1]).any()
+
+
+# ---- 3. refusals ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_refusals_return_their_code_and_change_nothing(sigma):
+    mh, sh, mp, sp, _ = pools(sigma)
+    h = mh.handle
+    c = picture(W, H, 55)
+    sh.canvas_put(0, c)
+    ids = [0, 1]
+    sh.place(ids, 0, [(37, 3), (100, 60)], [2, 1])
+    paint_all(sh, ids, 5)
+    before = [sh.read(i) for i in ids]
+    out = np.full((2, 3, 16, 16), 7, np.uint8)
+    whole = np.full((2, 3, H, W), 7, np.uint8)
+    shown = np.full((2, 3, 64, 64), 7, np.uint8)
+    ok = Wn([(0, 0, 0), (0, 0, 0)])
+    ev = events([0, 1])
+    h.canvas_compose(ok, W, H, np.empty_like(whole))                             # the window fits at zoom 1
+    bad = [
+        ("zoom 0 outside 1..16", lambda: h.compose_zoom(ok, 16, 16, 0, out)),
+        ("zoom 17 outside 1..16", lambda: h.compose_zoom(ok, 16, 16, 17, out)),
+        ("item 0: .* at zoom 2 outside the 200 x 136 canvas", lambda: h.compose_zoom(ok, W, H, 2, whole)),
+        ("item 1: .* at zoom 4 outside", lambda: h.compose_zoom(Wn([(0, 0, 0), (0, 136, 76)]), 16, 16, 4, out)),
+        ("item 1: .* at zoom 4 outside", lambda: h.compose_zoom(Wn([(0, 0, 0), (0, 140, 0)]), 16, 16, 4, out)),
+        ("item 1: window x 2 is not a multiple of 4", lambda: h.compose_zoom(Wn([(0, 0, 0), (0, 2, 0)]), 16, 16, 2, out)),
+        ("multiple of 4", lambda: h.compose_zoom(ok, 18, 16, 2, out)),
+        ("at least 1", lambda: h.compose_zoom(ok, 16, 0, 2, out)),
+        ("ian_compose_brush_zoom: zoom 0 outside", lambda: h.compose_brush_zoom(ev, ok, 16, 16, 0, out, shown)),
+        ("ian_compose_brush_zoom: zoom 17 outside", lambda: h.compose_brush_zoom(ev, ok, 16, 16, 17, out, shown)),
+        ("item 0: .* at zoom 2 outside", lambda: h.compose_brush_zoom(ev, ok, W, H, 2, whole, shown)),
+        ("item 0: window x 2", lambda: h.compose_brush_zoom(ev, Wn([(0, 2, 0), (0, 0, 0)]), 16, 16, 2, out, shown)),
+    ]
+    for needle, call in bad:
+        refused(call, needle, -7)
+        assert np.all(out == 7) and np.all(shown == 7) and np.all(whole == 7), needle
+        for i, b in zip(ids, before):
+            assert_fields(sh.read(i), b, KEYS, (needle, i))
+        assert np.array_equal(sh.canvas_read(0), c), needle
+    # -6: a pool without the reservation
+    hp = mp.handle
+    sp.open([0, 1], c[None, :, :64, :64].repeat(2, 0))
+    z0 = sp.read(0)["Z"]
+    for call in (lambda: hp.compose_zoom(ok, 16, 16, 2, out), lambda: hp.compose_brush_zoom(ev, ok, 16, 16, 2, out, shown)):
+        refused(call, "no canvas reservation", -6)
+    assert np.all(out == 7) and np.all(shown == 7) and np.array_equal(sp.read(0)["Z"], z0)
+    # the Python surface refuses the same before the library is called, and the handle still works
+    for call in (lambda: sh.compose([0], (0, 0), (W, H), zoom=2), lambda: sh.compose([0], (0, 0), 16, zoom=0), lambda: sh.compose([0], (2, 0), 16, zoom=2)):
+        with pytest.raises(ValueError):
+            call()
+    got = sh.compose([0], (0, 0), (100, 68), zoom=2)
+    assert got.shape == (1, 3, 68, 100) and np.array_equal(got[0], N.zoom_box_mean(sh.compose([0], (0, 0), (W, H))[0], 2))

@@ -1,0 +1,247 @@
+"""Zoomed views of full-resolution sessions (ian_session_zoom, ian_session_brush_zoom; EditSessions.render / brush_view / paint /
+scroll with a zoom).  Every comparison is np.array_equal against npe_ops.hires_render_zoom / hires_render_guided_zoom,
+whose inputs (SOURCE, GIM, FIELD, FIELD_KIND) are read back from the pool after paint events that leave non-zero fields: the numpy
+functions specify the arithmetic and the device matches them bit for bit.  Every case runs with the guide off and under
+reserve_guide(sigma)."""
+import numpy as np
+import pytest
+
+from neural_photo_editor_amd import npe_ops as N
+from oracle import ian_oracle as O
+from session_helpers import KEYS64, assert_fields, model_pool, refused, session_events as events, session_views as views, sources
+
+pytestmark = pytest.mark.gpu
+
+CAP = 16
+SIGMAS = [None, 8.0]
+ALL = KEYS64 + ("FIELD", "FIELD_KIND", "SOURCE")
+
+_cache = {}
+
+
+def pools(s, sigma):
+    """(model, the full-resolution pool at scale s with the guide off (sigma None) or on, model, a plain pool, the guide's table)."""
+    if "p" not in _cache:
+        _cache["p"] = model_pool("IAN_simple", capacity=CAP) + model_pool("IAN_simple", capacity=CAP)
+    mh, sh, mp, sp = _cache["p"]
+    sh.reserve_guide()
+    sh.reserve_hires(s)
+    table = None
+    if sigma is not None:
+        table = N.guide_table(sigma)
+        sh.reserve_guide(table=table)
+    return mh, sh, mp, sp, table
+
+
+def painted(sh, s, photo_ids, sample_ids, seed):
+    """Sessions opened on their own photos; sample_ids go to sample mode; every session gets a paint event that leaves a non-zero
+    field -> {id: (SOURCE, GIM, FIELD, KIND)} as read back."""
+    ids = list(photo_ids) + list(sample_ids)
+    sh.open_hires(ids, sources(len(ids), s, seed))
+    if sample_ids:
+        sh.sample(list(sample_ids), O.make_latents(len(sample_ids), seed=seed))
+    boxes = np.array([(6 + 5 * (k % 4), 8 + 3 * (k % 5), 34 + 3 * (k % 6), 40 + 2 * (k % 7)) for k in range(len(ids))])
+    sh.paint(ids, boxes, np.random.RandomState(seed).randint(0, 256, (len(ids), 3)), weight=0.5)
+    return {i: state(sh, i, kind=int(i in sample_ids)) for i in ids}
+
+
+def state(sh, i, kind=None):
+    got = sh.read(i)
+    assert got["FIELD"].any() and (kind is None or got["FIELD_KIND"] == kind), i
+    return got["SOURCE"], got["GIM"], got["FIELD"], int(got["FIELD_KIND"])
+
+
+def spec(st, s, x, y, vw, vh, k, table):
+    src, gim, field, kind = st
+    if table is None:
+        return N.hires_render_zoom(src, field, kind, s, x, y, vw, vh, k)
+    return N.hires_render_guided_zoom(src, gim, field, kind, s, x, y, vw, vh, k, table)
+
+
+def assert_views(sh, st, s, table, wins, k, tag):
+    """Every window (x, y, vw, vh) of every session of st, all sessions in one call, against the specification."""
+    ids = list(st)
+    for (x, y, vw, vh) in wins:
+        out = sh.render(ids, (x, y), (vw, vh), zoom=k)
+        assert out.shape == (len(ids), 3, vh, vw) and out.dtype == np.uint8
+        for j, i in enumerate(ids):
+            assert np.array_equal(out[j], spec(st[i], s, x, y, vw, vh, k, table)), (tag, i, (x, y, vw, vh), k)
+    return out
+
+
+# ---- 1. parity --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_scale_1_at_zoom_16_walks_more_field_rows_than_one_band_stages(sigma):
+    """One output row spans 16 source rows, which tap 17 field rows at scale 1: past the 10 rows a band stages."""
+    _, sh, _, _, table = pools(1, sigma)
+    st = painted(sh, 1, [3], [6], 11)
+    out = assert_views(sh, st, 1, table, [(0, 0, 4, 4)], 16, "s1k16")
+    assert (out[0] != N.zoom_box_mean(st[3][0], 16)).any()                     # the field shows at 1/16
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+@pytest.mark.parametrize("s", [2, 3, 16])
+def test_the_whole_picture_at_zoom_scale_is_gim_untouched_and_the_specification_painted(s, sigma):
+    _, sh, _, _, table = pools(s, sigma)
+    try:
+        ids = [9, 2]
+        sh.open_hires(ids, sources(2, s, 20 + s))
+        out = sh.render(ids, (0, 0), 64, zoom=s)
+        for j, i in enumerate(ids):
+            assert np.array_equal(out[j], sh.read(i)["GIM"]), (s, i)
+        st = painted(sh, s, [9], [2], 20 + s)
+        out = assert_views(sh, st, s, table, [(0, 0, 64, 64)], s, "whole")
+        assert (out[0] != st[9][1]).any()
+    finally:
+        if s == 16:
+            sh.reserve_guide()
+            sh.reserve_hires(0)
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_scale_3_at_zoom_5_neither_divides_the_other(sigma):
+    """The far window ends at the picture's last row and column, where the taps are clamped."""
+    _, sh, _, _, table = pools(3, sigma)
+    st = painted(sh, 3, [3, 11], [6], 31)
+    assert 12 + 5 * 36 == 192 and 2 + 5 * 38 == 192
+    assert_views(sh, st, 3, table, [(4, 1, 36, 38), (12, 2, 36, 38)], 5, "s3k5")
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_scale_4_at_zoom_2_narrowest_window_and_one_that_ends_at_the_last_column(sigma):
+    _, sh, _, _, table = pools(4, sigma)
+    st = painted(sh, 4, [1], [7], 41)
+    assert 8 + 2 * 124 == 256
+    assert_views(sh, st, 4, table, [(0, 5, 4, 13), (8, 0, 124, 13), (8, 238, 124, 9)], 2, "s4k2")
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_tiles_of_one_session_and_another_kind_in_one_call(sigma):
+    _, sh, _, _, table = pools(4, sigma)
+    st = painted(sh, 4, [5], [12], 51)
+    tiles = sh.render([5, 5, 12], [(0, 4), (64, 4), (0, 4)], (32, 20), zoom=2)
+    wide = sh.render([5], (0, 4), (64, 20), zoom=2)
+    assert np.array_equal(np.concatenate([tiles[0], tiles[1]], axis=2), wide[0])
+    assert np.array_equal(wide[0], spec(st[5], 4, 0, 4, 64, 20, 2, table))
+    assert np.array_equal(tiles[2], spec(st[12], 4, 0, 4, 32, 20, 2, table))
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_the_zoom_entry_at_zoom_1_is_the_render(sigma):
+    mh, sh, _, _, _ = pools(3, sigma)
+    painted(sh, 3, [3], [6], 61)
+    v = views([(3, 40, 37), (6, 40, 37)])
+    a, b = np.zeros((2, 3, 50, 64), np.uint8), np.ones((2, 3, 50, 64), np.uint8)
+    mh.handle.session_render(v, 64, 50, a)
+    mh.handle.session_zoom(v, 64, 50, 1, b)
+    assert np.array_equal(a, b)
+
+
+# ---- 2. one submission, and what a view leaves alone --------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma", SIGMAS)
+@pytest.mark.parametrize("tip", [False, True])
+def test_brush_view_at_a_zoom_is_brush_then_render_at_that_zoom(tip, sigma):
+    s, k = 3, 3
+    _, sh, _, _, _ = pools(s, sigma)
+    A, B = [1, 7], [8, 2]
+    src = sources(2, s, 13)
+    sh.open_hires(A, src)
+    sh.open_hires(B, src)
+    boxes, colours = np.array([(10, 12, 30, 28), (33, 5, 53, 21)]), np.array([(250, 20, 20), (10, 240, 90)])
+    origins, size = np.array([(0, 0), (24, 3)]), (56, 63)
+    tips = None
+    try:
+        if tip:
+            sh.reserve_tips(1)
+            sh.set_tip(0, 0.1 + np.random.RandomState(3).uniform(0, 1, (16, 20)))
+            tips = 0
+        got = [sh.brush_view(A, boxes, colours, None, 0.5, -1.0, origins, size, tips, zoom=k) for _ in range(2)]   # the second hits residency
+        got.append(sh.scroll(A, boxes, [1.0, -1.0], weight=0.3, view=(origins, size, k), tips=tips))
+        want = []
+        for call in (lambda: sh.paint(B, boxes, colours, weight=0.5, tips=tips), lambda: sh.paint(B, boxes, colours, weight=0.5, tips=tips),
+                     lambda: sh.scroll(B, boxes, [1.0, -1.0], weight=0.3, tips=tips)):
+            shown = call()
+            want.append((shown, sh.render(B, origins, size, zoom=k)))
+    finally:
+        if tip:
+            sh.reserve_tips(0)
+    for step, ((shown, out), (shown_w, out_w)) in enumerate(zip(got, want)):
+        assert np.array_equal(shown, shown_w), step
+        assert out.shape == (2, 3, 63, 56) and np.array_equal(out, out_w), step
+    assert (got[0][1][0] != N.zoom_box_mean(np.ascontiguousarray(src[0][:, :189, :168]), k)).any()      # the window shows an edit
+    for a, b in zip(A, B):
+        assert_fields(sh.read(a), sh.read(b), ALL)
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_a_zoomed_view_between_two_brushes_leaves_them_what_they_are(sigma):
+    s = 2
+    _, sh, _, _, _ = pools(s, sigma)
+    A, B = [4, 10], [0, 13]
+    src = sources(2, s, 17)
+    sh.open_hires(A, src)
+    sh.open_hires(B, src)
+    box, col = (12, 10, 40, 36), (240, 30, 60)
+    a1 = sh.paint(A, box, col, weight=0.5)
+    sh.render(A, (0, 0), (32, 32), zoom=4)                                      # between two brushes on the same sessions
+    a2 = sh.paint(A, box, col, weight=0.5)
+    b1 = sh.paint(B, box, col, weight=0.5)
+    b2 = sh.paint(B, box, col, weight=0.5)
+    assert np.array_equal(a1, b1) and np.array_equal(a2, b2)
+    for a, b in zip(A, B):
+        assert_fields(sh.read(a), sh.read(b), ALL)
+
+
+# ---- 3. refusals ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma", SIGMAS)
+def test_refusals_return_their_code_and_change_nothing(sigma):
+    s = 2
+    S = 64 * s
+    mh, sh, mp, sp, _ = pools(s, sigma)
+    h = mh.handle
+    ids = [0, 1]
+    sh.open_hires(ids, sources(2, s, 55))
+    sh.paint(ids, (10, 10, 30, 30), (200, 100, 50), weight=0.5)
+    before = [sh.read(i) for i in ids]
+    out = np.full((2, 3, 16, 16), 7, np.uint8)
+    whole = np.full((2, 3, S, S), 7, np.uint8)
+    shown = np.full((2, 3, 64, 64), 7, np.uint8)
+    ok = views([(0, 0, 0), (1, 0, 0)])
+    ev = events([0, 1])
+    h.session_render(ok, S, S, np.empty_like(whole))                             # the window fits at zoom 1
+    bad = [
+        ("zoom 0 outside 1..16", lambda: h.session_zoom(ok, 16, 16, 0, out)),
+        ("zoom 17 outside 1..16", lambda: h.session_zoom(ok, 16, 16, 17, out)),
+        ("zoom -1 outside", lambda: h.session_zoom(ok, 16, 16, -1, out)),
+        ("item 0: .* at zoom 2 outside", lambda: h.session_zoom(ok, S, S, 2, whole)),
+        ("item 1: .* at zoom 4 outside", lambda: h.session_zoom(views([(0, 0, 0), (1, 64, 68)]), 16, 16, 4, out)),
+        ("item 1: window x 2 is not a multiple of 4", lambda: h.session_zoom(views([(0, 0, 0), (1, 2, 0)]), 16, 16, 2, out)),
+        ("multiple of 4", lambda: h.session_zoom(ok, 18, 16, 2, out)),
+        ("at least 1", lambda: h.session_zoom(ok, 16, 0, 2, out)),
+        ("at least 1", lambda: h.session_zoom(ok, 0, 16, 2, out)),
+        ("ian_session_brush_zoom: zoom 0 outside", lambda: h.session_brush_zoom(ev, None, shown, ok, 16, 16, 0, out)),
+        ("ian_session_brush_zoom: zoom 17 outside", lambda: h.session_brush_zoom(ev, None, shown, ok, 16, 16, 17, out)),
+        ("item 0: .* at zoom 2 outside", lambda: h.session_brush_zoom(ev, None, shown, ok, S, S, 2, whole)),
+        ("item 0: window x 2", lambda: h.session_brush_zoom(ev, None, shown, views([(0, 2, 0), (1, 0, 0)]), 16, 16, 2, out)),
+        ("item 1", lambda: h.session_brush_zoom(ev, None, shown, views([(0, 0, 0), (0, 0, 0)]), 16, 16, 2, out)),      # view != event
+    ]
+    for needle, call in bad:
+        refused(call, needle, -7)
+        assert np.all(out == 7) and np.all(shown == 7) and np.all(whole == 7)
+        for i, b in zip(ids, before):
+            assert_fields(sh.read(i), b, ALL, (needle, i))
+    # -6: a pool without the reservation
+    hp = mp.handle
+    if sp.scale:
+        sp.reserve_hires(0)
+    sp.open([0, 1], sources(2, 1, 57))
+    z0 = sp.read(0)["Z"]
+    for call in (lambda: hp.session_zoom(ok, 16, 16, 2, out), lambda: hp.session_brush_zoom(ev, None, shown, ok, 16, 16, 2, out)):
+        refused(call, "no full-resolution reservation", -6)
+    assert np.all(out == 7) and np.all(shown == 7) and np.array_equal(sp.read(0)["Z"], z0)
+    # the Python surface refuses the same before the library is called, and the handle still works
+    for call in (lambda: sh.render(ids, (0, 0), S, zoom=2), lambda: sh.render(ids, (0, 0), 16, zoom=0), lambda: sh.render(ids, (2, 0), 16, zoom=2)):
+        with pytest.raises(ValueError):
+            call()
+    got = sh.render(ids, (0, 0), (32, 64), zoom=2)
+    assert got.shape == (2, 3, 64, 32) and np.array_equal(got[0], N.zoom_box_mean(sh.render(ids, (0, 0), (64, 128))[0], 2))
