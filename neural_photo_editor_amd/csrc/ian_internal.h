@@ -477,16 +477,21 @@ hipError_t launch_session_unpack(const SessionPool& P, const SessionRings& R, co
 // box mean -> GIM, IM and x[i] = table[byte], the outputs of launch_session_open_in
 hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,
                                      hipStream_t s);
-// npe_ops.hires_render of n windows: views = device int[n][3] (session, x, y), every window vw x vh with x and vw multiples of 4.
-// out u8 [n][3][vh][vw]; out == nullptr: the whole picture (vw = vh = S, x = y = 0) written over the session's own SRC row
-hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s);
-// npe_ops.hires_render_guided of the same windows (ian_sessions_reserve_guide): table = device float[766], the range
-// weights by summed absolute byte difference; the guide of a session is its own GIM.  views, out and out == nullptr as above.
+// The window launches (kernels_window.hip).  Both take table and zoom:
+//   table   nullptr: the plain arithmetic.  Otherwise device float[766], the range weights by summed absolute byte difference
+//           (ian_sessions_reserve_guide; ian_sessions_reserve_edges, 4.13): the guided arithmetic, the guide of a
+//           session being its own GIM and the photo the session's SRC or the canvas.
+//   zoom    1: the windows as they are.  2..16: the same windows at 1/zoom.  Output pixel (Y, X) of window i is
+//           npe_ops.zoom_box_mean of the 1:1 result of the source window (x, y, zoom * vw, zoom * vh), which must lie inside the
+//           picture: x and y of views / windows stay in full-resolution pixels, vw x vh is the OUTPUT size, out is never nullptr
+//           and 4-byte aligned.  No full-resolution result is written anywhere.
+// npe_ops.hires_render[_guided] of n windows: views = device int[n][3] (session, x, y), every window vw x vh with x and vw multiples
+// of 4.  out u8 [n][3][vh][vw]; out == nullptr: the whole picture (vw = vh = S, x = y = 0) written over the session's own SRC row
 constexpr int SESSION_GUIDE_TABLE_LEN = 3 * 255 + 1;
-hipError_t launch_session_render_guided(const SessionPool& P, const float* table, const int* views, int vw, int vh, unsigned char* out, int n,
-                                        hipStream_t s);
+hipError_t launch_session_render(const SessionPool& P, const float* table, const int* views, int vw, int vh, int zoom, unsigned char* out, int n,
+                                 hipStream_t s);
 // canvases (ian_sessions_reserve_canvas): whole photos in device memory and, per canvas, the table of the sessions
-// placed on it.  Beside the pool for SessionRings' reason; only the two canvas kernels take it.  All nullptr / 0 without the reservation.
+// placed on it.  Beside the pool for SessionRings' reason; only the canvas kernels take it.  All nullptr / 0 without the reservation.
 constexpr int CANVAS_MAX_PLACED = 8;
 struct SessionCanvases {
   unsigned char* pix;     // u8 [count][3][max_h][max_w]: row stride max_w whatever a picture's own width (size_t offsets throughout)
@@ -494,32 +499,21 @@ struct SessionCanvases {
   int count, max_w, max_h;
   int feather;            // 0..16, in field pixels
 };
+// what every canvas launcher checks of it
+inline bool canvases_ok(const SessionCanvases& C) {
+  return C.pix && C.table && C.count >= 1 && C.max_w >= 64 && C.max_h >= 64 && (C.max_w & 3) == 0 && C.feather >= 0 && C.feather <= 16 &&
+         (reinterpret_cast<uintptr_t>(C.pix) & 3) == 0;
+}
 // place: items = device int[n][5] (ian_canvas_placement: session, canvas, x, y, scale).  The exact box mean of the canvas's square ->
 // GIM, IM of the session and x[i] = table[byte]: the outputs of launch_session_hires_open, without an SRC copy, the square at any
 // byte alignment, the scale per item.
 hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, const int* items, const float* table, float* x, int n,
                                hipStream_t s);
-// npe_ops.canvas_compose of n windows: windows = device int[n][3] (canvas, x, y), every window vw x vh with x and vw multiples of 4.
-// out u8 [n][3][vh][vw]; out == nullptr: n == 1 and the window is a whole picture (x = y = 0), written over the canvas itself
-hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, unsigned char* out,
-                                 int n, hipStream_t s);
-// npe_ops.canvas_compose_guided of the same windows (ian_sessions_reserve_edges): table = device float[766] as for
-// launch_session_render_guided; the guide of a placed session is its own GIM, the photo is the canvas.  windows, out and out == nullptr
-// as above.
-hipError_t launch_canvas_compose_guided(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh,
-                                        unsigned char* out, int n, hipStream_t s);
-// zoomed views: the four window launches above at 1/zoom, zoom in 2..16 (1 is the launch above).  Output pixel
-// (Y, X) of window i is npe_ops.zoom_box_mean of the 1:1 result of the source window (x, y, zoom * vw, zoom * vh), which must lie
-// inside the picture: x and y of views / windows stay in full-resolution pixels, vw x vh is the OUTPUT size, out u8 [n][3][vh][vw],
-// never nullptr.  No full-resolution result is written anywhere.
-hipError_t launch_session_render_zoom(const SessionPool& P, const int* views, int vw, int vh, int zoom, unsigned char* out, int n,
-                                      hipStream_t s);
-hipError_t launch_session_render_guided_zoom(const SessionPool& P, const float* table, const int* views, int vw, int vh, int zoom,
-                                             unsigned char* out, int n, hipStream_t s);
-hipError_t launch_canvas_compose_zoom(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, int zoom,
-                                      unsigned char* out, int n, hipStream_t s);
-hipError_t launch_canvas_compose_guided_zoom(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw,
-                                             int vh, int zoom, unsigned char* out, int n, hipStream_t s);
+// npe_ops.canvas_compose[_guided] of n windows: windows = device int[n][3] (canvas, x, y), every window vw x vh with x and vw multiples
+// of 4; table and zoom as for launch_session_render.  out u8 [n][3][vh][vw], 4-byte aligned; out == nullptr: n == 1 and the window is
+// a whole picture (x = y = 0), written over the canvas itself
+hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh, int zoom,
+                                 unsigned char* out, int n, hipStream_t s);
 
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,

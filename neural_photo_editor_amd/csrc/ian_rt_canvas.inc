@@ -312,19 +312,13 @@ int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_w
 }
 
 // the windows of n canvases into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, one whole picture over its own canvas.
-// zoom > 1: the windows at 1/zoom, the zoomed kernels; 1 takes the launches it always took
+// zoom > 1: the windows at 1/zoom.  S.d_edges (ian_sessions_reserve_edges): each photo-mode field's taps weighted by the canvas
 int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st, int zoom) {
   auto& S = h->sess;
   S.cwin_shadow.resize((size_t)3 * n);
   memcpy(S.cwin_shadow.data(), w, (size_t)n * sizeof(ian_canvas_window));
   HIPCHK(h, hipMemcpyAsync(S.d_cwin, S.cwin_shadow.data(), (size_t)n * sizeof(ian_canvas_window), hipMemcpyHostToDevice, st));
-  if (zoom > 1) {
-    if (S.d_edges) HIPCHK(h, launch_canvas_compose_guided_zoom(S.canv, S.arr.pool, S.d_edges, S.d_cwin, vw, vh, zoom, d_out, n, st));
-    else HIPCHK(h, launch_canvas_compose_zoom(S.canv, S.arr.pool, S.d_cwin, vw, vh, zoom, d_out, n, st));
-  } else if (S.d_edges)   // ian_sessions_reserve_edges: the same windows, each photo-mode field's taps weighted by the canvas
-    HIPCHK(h, launch_canvas_compose_guided(S.canv, S.arr.pool, S.d_edges, S.d_cwin, vw, vh, d_out, n, st));
-  else
-    HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_cwin, vw, vh, d_out, n, st));
+  HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_edges, S.d_cwin, vw, vh, zoom, d_out, n, st));
   return 0;
 }
 

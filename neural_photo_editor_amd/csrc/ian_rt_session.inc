@@ -633,20 +633,14 @@ int session_view_check(ian_handle* h, const char* fn, int n, const ian_session_v
 }
 
 // the windows of n views into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, the whole picture over each session's own SRC.
-// zoom > 1: the views at 1/zoom, the zoomed kernels; 1 takes the launches it always took
+// zoom > 1: the views at 1/zoom.  S.d_guide (ian_sessions_reserve_guide): the field's taps weighted by the photo; nullptr: plain
 int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, int vw, int vh, unsigned char* d_out, hipStream_t st,
                            int zoom = 1) {
   auto& S = h->sess;
   S.views_shadow.resize((size_t)3 * n);
   memcpy(S.views_shadow.data(), views, (size_t)n * sizeof(ian_session_view));
   HIPCHK(h, hipMemcpyAsync(S.d_views, S.views_shadow.data(), (size_t)n * sizeof(ian_session_view), hipMemcpyHostToDevice, st));
-  if (zoom > 1) {
-    if (S.d_guide) HIPCHK(h, launch_session_render_guided_zoom(S.arr.pool, S.d_guide, S.d_views, vw, vh, zoom, d_out, n, st));
-    else HIPCHK(h, launch_session_render_zoom(S.arr.pool, S.d_views, vw, vh, zoom, d_out, n, st));
-  } else if (S.d_guide)   // ian_sessions_reserve_guide: the same windows, the field's taps weighted by the photo
-    HIPCHK(h, launch_session_render_guided(S.arr.pool, S.d_guide, S.d_views, vw, vh, d_out, n, st));
-  else
-    HIPCHK(h, launch_session_render(S.arr.pool, S.d_views, vw, vh, d_out, n, st));
+  HIPCHK(h, launch_session_render(S.arr.pool, S.d_guide, S.d_views, vw, vh, zoom, d_out, n, st));
   return 0;
 }
 

@@ -10,13 +10,11 @@
 //   session_stroke_umask_kernel  strokes: the footprints of all of a stroke's rectangles max-ed into the session's UMASK
 //   session_fit_begin_kernel / _adam_kernel / _loss_kernel  ian_session_fit: IM := GIM, one Adam step on the latent rows, the loss read-out
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
-//   session_render_kernel      a window of the full-resolution picture: SRC + 127.5 * bilinear(FIELD), or the upsampled sample
-//   session_render_guided_kernel  the same window with the field's four taps weighted by the photo (ian_sessions_reserve_guide)
 //   canvas_place_kernel        canvases: the exact box mean of a square of a whole photo -> GIM, IM, encoder input (any byte alignment)
-//   canvas_compose_kernel      a window of a whole photo: the canvas plus every placed session's feathered edit field
-//   canvas_compose_guided_kernel  the same window with each photo-mode field's four taps weighted by the canvas (ian_sessions_reserve_edges)
 //   session_history_save_kernel / _move_kernel  undo history: a session's Z and UMASK rows to and from its ring of saved states
 //   session_pack_kernel / session_unpack_kernel  saved sessions: every row of a session, its ring included, to and from one record
+// The kernels that show a window of a full-resolution picture or of a canvas (render, compose, their zoomed views) are in
+// kernels_window.hip.
 // Every image row is addressed as pool + id * 12288: consecutive lanes touch consecutive bytes (uchar4 / float4 per lane).
 #include <cstring>
 #include <type_traits>
@@ -575,10 +573,9 @@ hipError_t launch_session_fit_loss(const float* xhat, const SessionPool& P, cons
   return hipGetLastError();
 }
 
-// ---- full-resolution sessions (the arithmetic is npe_ops.hires_downsample / hires_axis_taps / hires_render) ------------
+// ---- full-resolution sessions (the arithmetic is npe_ops.hires_downsample) ---------------------------------------------
 // The photo lives in the pool at S x S, S = 64 * scale; the 64x64 state above is that of its exact box mean.  What a call displays is
-// kept as FIELD / FIELD_KIND, and a window of the picture at full size is SRC + 127.5 * bilinear(FIELD) (kind 0: the unedited part of
-// the photo stays pixel-exact) or 127.5 * (bilinear(FIELD) + 1) (kind 1: FIELD holds x, a sample has no photo under it).
+// kept as FIELD / FIELD_KIND; the kernels that render a window of the picture from them are in kernels_window.hip.
 
 // The box mean of one row of one channel of a session's 64x64 picture: the work of one workgroup in both kernels below.  The row is
 // s rows of 64 * s bytes that start `lead` (0..3) bytes into the aligned uchar4 at `in`, `stride` bytes apart.  Lane q owns the
@@ -653,206 +650,6 @@ hipError_t launch_session_hires_open(const unsigned char* photos, const SessionP
   return hipGetLastError();
 }
 
-// hires_axis_taps for one output coordinate: half-pixel centres in integers, a = 2Y + 1 - s in (-2s, 128s), i0 = floor(a / 2s) >= -1,
-// t = float32(a - 2s * i0) / float32(2s) (one division), both taps clamped to 0..63
-__device__ __forceinline__ void hires_taps(int Y, int s, int& lo, int& hi, float& t) {
-  const int s2 = 2 * s, a = 2 * Y + 1 - s;
-  const int i0 = (a + s2) / s2 - 1;   // a + 2s > 0: truncation is the floor
-  t = (float)(a - s2 * i0) / (float)s2;
-  lo = min(max(i0, 0), 63);
-  hi = min(max(i0 + 1, 0), 63);
-}
-
-// the field at square coordinate u of the output row whose two tapped field rows are top and bot (weight ty): hires_render's bilinear
-// tap, float32, in exactly this order of operations (contraction is off here)
-__device__ __forceinline__ float field_bilinear(const float* top, const float* bot, int s, int u, float ty) {
-  int c0, c1;
-  float tx;
-  hires_taps(u, s, c0, c1, tx);
-  const float a0 = top[c0], a1 = bot[c0];
-  const float t = a0 + tx * (top[c1] - a0);
-  const float b = a1 + tx * (bot[c1] - a1);
-  return t + ty * (b - t);
-}
-// np.clip(np.rint(q), 0, 255).astype(uint8)
-__device__ __forceinline__ unsigned char round_u8(float q) { return (unsigned char)fminf(fmaxf(rintf(q), 0.0f), 255.0f); }
-
-// The field rows that output rows u0..u1 (square coordinates, both inclusive) of a picture at scale s tap: n <= ceil((RENDER_BAND - 1) / s)
-// + 2 <= RENDER_BAND + 2 consecutive rows of 64 floats, from row fr0.  field_rows says which (render: every lane; compose: lane 0, per
-// kept placement, into LDS); stage_field_rows copies them from the field's plane to f, all 256 lanes of either window kernel; the
-// caller's barrier publishes f.
-constexpr int RENDER_BAND = 8;
-struct FieldRows {
-  int fr0, n;
-};
-__device__ __forceinline__ FieldRows field_rows(int u0, int u1, int s) {
-  int fr0, fr1, unused;
-  float tunused;
-  hires_taps(u0, s, fr0, unused, tunused);
-  hires_taps(u1, s, unused, fr1, tunused);
-  return FieldRows{fr0, min(fr1 - fr0 + 1, RENDER_BAND + 2)};
-}
-__device__ __forceinline__ void stage_field_rows(float* f, const float* plane, const FieldRows r) {
-  const float* frow = plane + r.fr0 * 64;
-  for (int j = threadIdx.x; j < r.n * 64; j += 256) f[j] = frow[j];
-}
-
-// render.  grid (bands of RENDER_BAND output rows, 3, n); a lane owns 4 consecutive output bytes: one uchar4 load of SRC, one uchar4
-// store.  The band's field rows go to LDS once; every tap reads from there.  All arithmetic is float32 with contraction off, in
-// hires_render's order.
-// Band height: the traffic is 2 bytes per output byte plus the staged rows, so the band only has to keep the staging small against
-// 8 * vw bytes of output and the grid large; 8 rows give 384 workgroups (1.5 per CU) for ONE whole 1024 x 1024 picture and
-// 2 uchar4 per lane at a 256-wide window.
-// out == nullptr: the whole picture over the session's own SRC row (commit): every lane stores exactly the bytes it loaded, so
-// this is safe in place; SRC and out are therefore not __restrict__.
-__global__ __launch_bounds__(256) void session_render_kernel(SessionPool P, const int* __restrict__ views, int vw, int vh, unsigned char* out) {
-  __shared__ float f[(RENDER_BAND + 2) * 64];
-  const int s = P.scale, S = 64 * s;
-  const int c = blockIdx.y, i = blockIdx.z;
-  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
-  const int y0 = blockIdx.x * RENDER_BAND, rows = min(RENDER_BAND, vh - y0);
-  const FieldRows fr = field_rows(vy + y0, vy + y0 + rows - 1, s);
-  stage_field_rows(f, P.field + ((size_t)id * 3 + c) * (64 * 64), fr);
-  __syncthreads();
-  const int kind = P.kind[id];
-  const unsigned char* src = P.src + ((size_t)id * 3 + c) * S * S;
-  unsigned char* dst = out ? out + ((size_t)i * 3 + c) * vh * vw : P.src + ((size_t)id * 3 + c) * S * S;
-  const int dstride = out ? vw : S;
-  const int L = vw >> 2;
-  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
-    const int ry = idx / L, cx = (idx - ry * L) * 4;
-    const int Y = vy + y0 + ry;
-    int r0, r1;
-    float ty;
-    hires_taps(Y, s, r0, r1, ty);
-    const float* top = f + (r0 - fr.fr0) * 64;
-    const float* bot = f + (r1 - fr.fr0) * 64;
-    uchar4 pv = make_uchar4(0, 0, 0, 0);
-    if (kind == 0) pv = *reinterpret_cast<const uchar4*>(src + (size_t)Y * S + vx + cx);
-    const unsigned char pb[4] = {pv.x, pv.y, pv.z, pv.w};
-    unsigned char ob[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float v = field_bilinear(top, bot, s, vx + cx + e, ty);
-      ob[e] = round_u8(kind == 0 ? (float)pb[e] + 127.5f * v : 127.5f * (v + 1.0f));
-    }
-    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : vx + cx)) = make_uchar4(ob[0], ob[1], ob[2], ob[3]);
-  }
-}
-hipError_t launch_session_render(const SessionPool& P, const int* views, int vw, int vh, unsigned char* out, int n, hipStream_t s) {
-  const int S = 64 * P.scale;
-  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || vw < 4 || (vw & 3) || vh < 1 || vw > S || vh > S)
-    return hipErrorInvalidValue;
-  if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_render_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, P, views, vw, vh, out);
-  return hipGetLastError();
-}
-
-// guided render (npe_ops.hires_render_guided): the four bilinear taps of the field weighted by how close the photo's
-// pixel is to each tap's pixel of GIM.  grid (bands of GUIDE_BAND output rows, 1, n): the range weights need all three channels of a
-// pixel and are computed once per pixel, so a lane owns 4 consecutive output pixels in ALL THREE channels: three uchar4 loads of SRC,
-// three uchar4 stores.  The band's field rows of the three channels (field_rows / stage_field_rows), the same rows of GIM as bytes
-// and the 766 range weights go to LDS once, 8.8 KB; every tap and every weight reads from there.  The weights were computed on the
-// host (no exp here); all arithmetic is float32 with contraction off, in hires_render_guided's order, and the division is IEEE.
-// A kind-1 session (its field is a sample, there is no photo to guide by) takes session_render_kernel's arithmetic; the kind is
-// uniform over the workgroup, and a call may mix kinds.
-// Band height: with the channel planes gone from the grid, ONE whole 1024 x 1024 picture is 128 workgroups at 8 rows and 256 at 4,
-// against 256 CUs.  Both were measured in one run on an MI355X: that picture takes 16.1 us at 4 rows and 24.7 us
-// at 8 (the bilinear kernel: 15.7), sixteen of them 86.6 against 89.5 us, a 256 x 256 window 9.3 against 12.4 us.  So GUIDE_BAND = 4:
-// it fills every CU for one picture, and the staging per workgroup (at most 6 field rows of 3 channels, 5.8 KB, and the 3 KB table)
-// for half as many output rows does not show.
-// out == nullptr: the whole picture over the session's own SRC rows (commit).  A lane loads all three channels of its 4 pixels
-// before it stores any of them, no lane reads another lane's pixels of SRC, and FIELD, GIM and the table live elsewhere: safe in
-// place, as in session_render_kernel; SRC and out are therefore not __restrict__.
-constexpr int GUIDE_BAND = 4;
-static_assert(GUIDE_BAND >= 1 && GUIDE_BAND <= RENDER_BAND, "field_rows stages at most RENDER_BAND + 2 rows");
-__global__ __launch_bounds__(256) void session_render_guided_kernel(SessionPool P, const float* __restrict__ table,
-                                                                    const int* __restrict__ views, int vw, int vh, unsigned char* out) {
-  __shared__ float f[3][(GUIDE_BAND + 2) * 64];
-  __shared__ __align__(4) unsigned char g[3][(GUIDE_BAND + 2) * 64];
-  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
-  const int s = P.scale, S = 64 * s;
-  const int i = blockIdx.z;
-  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
-  const int y0 = blockIdx.x * GUIDE_BAND, rows = min(GUIDE_BAND, vh - y0);
-  const FieldRows fr = field_rows(vy + y0, vy + y0 + rows - 1, s);   // at most ceil((GUIDE_BAND - 1) / s) + 2 <= GUIDE_BAND + 2 rows
-  for (int c = 0; c < 3; ++c) {
-    stage_field_rows(f[c], P.field + ((size_t)id * 3 + c) * (64 * 64), fr);
-    const unsigned* grow = reinterpret_cast<const unsigned*>(P.gim + ((size_t)id * 3 + c) * (64 * 64) + fr.fr0 * 64);
-    unsigned* gl = reinterpret_cast<unsigned*>(g[c]);
-    for (int j = threadIdx.x; j < fr.n * 16; j += 256) gl[j] = grow[j];
-  }
-  for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
-  __syncthreads();
-  const int kind = P.kind[id];
-  const size_t plane = (size_t)S * S, dplane = out ? (size_t)vh * vw : plane;
-  const unsigned char* src = P.src + (size_t)id * 3 * plane;
-  unsigned char* dst = out ? out + (size_t)i * 3 * dplane : P.src + (size_t)id * 3 * plane;
-  const int dstride = out ? vw : S;
-  const int L = vw >> 2;
-  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
-    const int ry = idx / L, cx = (idx - ry * L) * 4;
-    const int Y = vy + y0 + ry, X = vx + cx;
-    int r0, r1;
-    float ty;
-    hires_taps(Y, s, r0, r1, ty);
-    const int o0 = (r0 - fr.fr0) * 64, o1 = (r1 - fr.fr0) * 64;
-    unsigned char pb[3][4] = {}, ob[3][4];
-    if (kind == 0) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * plane + (size_t)Y * S + X);
-        pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (kind == 0) {
-        int c0, c1;
-        float tx;
-        hires_taps(X + e, s, c0, c1, tx);
-        const float wy0 = 1.0f - ty, wx0 = 1.0f - tx;
-        const int at[4] = {o0 + c0, o0 + c1, o1 + c0, o1 + c1};
-        const float sw[4] = {wy0 * wx0, wy0 * tx, ty * wx0, ty * tx};
-        float w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int d = abs((int)pb[0][e] - (int)g[0][at[k]]) + abs((int)pb[1][e] - (int)g[1][at[k]]) + abs((int)pb[2][e] - (int)g[2][at[k]]);
-          w[k] = sw[k] * tab[d];
-        }
-        const float den = ((w[0] + w[1]) + w[2]) + w[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float num = ((w[0] * f[c][at[0]] + w[1] * f[c][at[1]]) + w[2] * f[c][at[2]]) + w[3] * f[c][at[3]];
-          const float v = num / den;
-          ob[c][e] = round_u8((float)pb[c][e] + 127.5f * v);
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float v = field_bilinear(f[c] + o0, f[c] + o1, s, X + e, ty);
-          ob[c][e] = round_u8(127.5f * (v + 1.0f));
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      *reinterpret_cast<uchar4*>(dst + c * dplane + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) =
-          make_uchar4(ob[c][0], ob[c][1], ob[c][2], ob[c][3]);
-  }
-}
-hipError_t launch_session_render_guided(const SessionPool& P, const float* table, const int* views, int vw, int vh, unsigned char* out, int n,
-                                        hipStream_t s) {
-  const int S = 64 * P.scale;
-  if (n < 1 || n > 65535 || P.scale < 1 || P.scale > 16 || !P.src || !P.gim || !P.field || !P.kind || !table || !views || vw < 4 || (vw & 3) ||
-      vh < 1 || vw > S || vh > S)
-    return hipErrorInvalidValue;
-  if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_render_guided_kernel, dim3((vh + GUIDE_BAND - 1) / GUIDE_BAND, 1, n), dim3(256), 0, s, P, table, views, vw, vh,
-                     out);
-  return hipGetLastError();
-}
-
 // ---- canvases (the arithmetic is npe_ops.canvas_crop_mean / canvas_ramp / canvas_compose) ------------------------------
 // A canvas is a whole photo of w x hgt pixels in rows of C.max_w bytes; a session is placed on it as a square of 64 * s pixels at
 // (ox, oy), s per placement.
@@ -871,652 +668,10 @@ __global__ __launch_bounds__(256) void canvas_place_kernel(SessionCanvases C, Se
   const unsigned char* in = C.pix + (((size_t)cv * 3 + c) * C.max_h + (size_t)oy + (size_t)gy * s) * C.max_w + (ox - lead);
   box_mean_row<false>(in, nullptr, (size_t)C.max_w, lead, s, P, id, i, (size_t)c * 64 * 64 + gy * 64, table, x, tab, sum);
 }
-static bool canvases_ok(const SessionCanvases& C) {
-  return C.pix && C.table && C.count >= 1 && C.max_w >= 64 && C.max_h >= 64 && (C.max_w & 3) == 0 && C.feather >= 0 && C.feather <= 16 &&
-         (reinterpret_cast<uintptr_t>(C.pix) & 3) == 0;
-}
 hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, const int* items, const float* table, float* x, int n,
                                hipStream_t s) {
   if (n < 1 || n > 65535 || !canvases_ok(C) || !P.gim || !P.im || !items || !table || !x) return hipErrorInvalidValue;
   hipLaunchKernelGGL(canvas_place_kernel, dim3(64, 3, n), dim3(256), 0, s, C, P, items, table, x);
-  return hipGetLastError();
-}
-
-// canvas_ramp for one square coordinate u: f2s = 2 * feather * s (0: no feather)
-__device__ __forceinline__ float canvas_ramp1(int u, int S, int f2s) {
-  if (f2s == 0) return 1.0f;
-  const int d = min(u, S - 1 - u);
-  return fminf(1.0f, (float)(2 * d + 1) / (float)f2s);
-}
-
-// compose.  session_render_kernel's shape: grid (bands of RENDER_BAND output rows, 3, n), a lane owns 4 consecutive output bytes: one
-// uchar4 load of the canvas, one uchar4 store.  Lane 0 reads the canvas's placement table and keeps the placements whose squares meet
-// the band (a test that is uniform over the workgroup) and which field rows each taps (field_rows); each kept placement's rows go to
-// LDS once (stage_field_rows), 20 KB for 8; the lanes then walk their pixels with the placements in the inner loop, so acc lives in registers.  A band that meets no
-// square is a plain copy.  All arithmetic is float32 with contraction off, in canvas_compose's order.
-// out == nullptr: the window is the whole picture, written over the canvas itself (commit): every lane stores exactly the bytes it
-// loaded and the fields live elsewhere, so overlapping squares are safe in place; neither pointer is __restrict__.
-struct CanvasKept {
-  int id, ox, oy, s, kind;
-};
-// one lane's walk of canvas cv's placement table: the placements whose squares meet rows Y0..Y1 (both inclusive) of a window at columns
-// vx .. vx + vw - 1 go to kept, in the table's order, each with the field rows the band taps inside its square -> how many
-__device__ __forceinline__ int canvas_keep_band(const SessionCanvases& C, const SessionPool& P, int cv, int vx, int vw, int Y0, int Y1,
-                                                CanvasKept* kept, FieldRows* frows) {
-  int nk = 0;
-  const int* tb = C.table + (size_t)cv * (CANVAS_MAX_PLACED * 4);
-  for (int k = 0; k < CANVAS_MAX_PLACED; ++k) {
-    const int id = tb[4 * k], ox = tb[4 * k + 1], oy = tb[4 * k + 2], s = tb[4 * k + 3];
-    if (id < 0) break;
-    const int S = 64 * s;
-    if (s < 1 || s > 16 || Y1 < oy || Y0 > oy + S - 1 || vx + vw - 1 < ox || vx > ox + S - 1) continue;
-    frows[nk] = field_rows(max(Y0, oy) - oy, min(Y1, oy + S - 1) - oy, s);   // the band's rows inside the square, in its coordinates
-    kept[nk++] = CanvasKept{id, ox, oy, s, P.kind[id]};
-  }
-  return nk;
-}
-__global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ windows, int vw, int vh,
-                                                             unsigned char* out) {
-  __shared__ float f[CANVAS_MAX_PLACED][(RENDER_BAND + 2) * 64];
-  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
-  __shared__ FieldRows frows[CANVAS_MAX_PLACED];   // the staged field rows of each kept placement
-  __shared__ int nkept;
-  const int c = blockIdx.y, i = blockIdx.z;
-  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
-  const int y0 = blockIdx.x * RENDER_BAND, rows = min(RENDER_BAND, vh - y0);
-  const int Y0 = vy + y0, Y1 = Y0 + rows - 1;   // the band's rows on the canvas, both inclusive
-  if (threadIdx.x == 0) nkept = canvas_keep_band(C, P, cv, vx, vw, Y0, Y1, kept, frows);
-  __syncthreads();
-  const int nk = nkept;
-  for (int k = 0; k < nk; ++k) stage_field_rows(f[k], P.field + ((size_t)kept[k].id * 3 + c) * (64 * 64), frows[k]);
-  __syncthreads();
-  const size_t plane = ((size_t)cv * 3 + c) * C.max_h * C.max_w;
-  const unsigned char* src = C.pix + plane;
-  unsigned char* dst = out ? out + ((size_t)i * 3 + c) * vh * vw : C.pix + plane;
-  const int dstride = out ? vw : C.max_w;
-  const int L = vw >> 2;
-  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
-    const int ry = idx / L, cx = (idx - ry * L) * 4;
-    const int Y = Y0 + ry, X = vx + cx;
-    const uchar4 pv = *reinterpret_cast<const uchar4*>(src + (size_t)Y * C.max_w + X);
-    float acc[4] = {(float)pv.x, (float)pv.y, (float)pv.z, (float)pv.w};
-    for (int k = 0; k < nk; ++k) {
-      const CanvasKept q = kept[k];
-      const int S = 64 * q.s, uy = Y - q.oy;
-      if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
-      const int f2s = 2 * C.feather * q.s, fr0 = frows[k].fr0;
-      int r0, r1;
-      float ty;
-      hires_taps(uy, q.s, r0, r1, ty);
-      const float* top = f[k] + (r0 - fr0) * 64;
-      const float* bot = f[k] + (r1 - fr0) * 64;
-      const float wy = canvas_ramp1(uy, S, f2s);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int ux = X + e - q.ox;
-        if (ux < 0 || ux >= S) continue;
-        const float v = field_bilinear(top, bot, q.s, ux, ty);
-        const float w = wy * canvas_ramp1(ux, S, f2s);
-        if (q.kind == 0) {
-          acc[e] = acc[e] + (127.5f * v) * w;
-        } else {
-          const float tv = 127.5f * (v + 1.0f);
-          acc[e] = w == 1.0f ? tv : acc[e] + (tv - acc[e]) * w;
-        }
-      }
-    }
-    *reinterpret_cast<uchar4*>(dst + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) =
-        make_uchar4(round_u8(acc[0]), round_u8(acc[1]), round_u8(acc[2]), round_u8(acc[3]));
-  }
-}
-hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, unsigned char* out,
-                                 int n, hipStream_t s) {
-  if (n < 1 || n > 65535 || !canvases_ok(C) || !P.field || !P.kind || !windows || vw < 4 || (vw & 3) || vh < 1 || vw > C.max_w || vh > C.max_h)
-    return hipErrorInvalidValue;
-  if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(canvas_compose_kernel, dim3((vh + RENDER_BAND - 1) / RENDER_BAND, 3, n), dim3(256), 0, s, C, P, windows, vw, vh, out);
-  return hipGetLastError();
-}
-
-// guided compose (npe_ops.canvas_compose_guided): canvas_compose_kernel's result with the sample of every kind 0
-// placement taken by guide_sample, the photo's pixel being the STORED canvas byte.  session_render_guided_kernel's shape, for its
-// reason (the range weights need all three channels of a pixel, once per pixel): grid (bands of CANVAS_GUIDE_BAND output rows, 1, n),
-// a lane owns 4 consecutive output pixels in all three channels: three uchar4 loads of the canvas, three uchar4 stores.  Lane 0 keeps
-// the band's placements (canvas_keep_band); per kept placement the band's field rows of the three channels and the same rows of its
-// GIM go to LDS, and the 766 range weights once if anything is kept.  A square starts at any ox while a lane's 4 pixels are aligned to
-// the window, so the inside-the-square test is per pixel, as in canvas_compose_kernel.  Kind 1 placements, canvas_ramp1 and round_u8
-// are that kernel's.  All arithmetic is float32 with contraction off, in canvas_compose_guided's order; the division is IEEE.
-// Band height: 8 placements x 3 channels x (band + 2) rows of 256 B field and 64 B GIM are 45 KB at 4 rows and 75 KB at 8, plus the
-// 3 KB table: only the 4-row band fits the 64 KB of static LDS (48.2 KB in all, three workgroups a CU), and it is the height
-// session_render_guided_kernel measured as the faster one.  So CANVAS_GUIDE_BAND = GUIDE_BAND = 4, and the rows of one placement are
-// guide_sample's arrays.
-// out == nullptr: the window is the whole picture, written over the canvas itself (commit).  A lane loads all three channels of its
-// 4 pixels before it stores any of them, it reads no other lane's canvas bytes, and FIELD, GIM and the table live elsewhere: safe in
-// place with overlapping squares; neither pointer is __restrict__.
-constexpr int CANVAS_GUIDE_BAND = GUIDE_BAND;
-// hires_guide_field's v of the three channels at square coordinate u of the output row whose two tapped rows start at o0 and o1 of the
-// staged rows (weight ty): f the field rows, g the same rows of GIM, tab the range weights, all in LDS; p0..p2 the photo's pixel.
-// session_render_guided_kernel's expression, statement for statement; that kernel keeps its own text, because calling this function
-// from it changes the code it compiles to.
-using GuideFieldRows = float[3][(GUIDE_BAND + 2) * 64];
-using GuideGimRows = unsigned char[3][(GUIDE_BAND + 2) * 64];
-__device__ __forceinline__ void guide_sample(const GuideFieldRows& f, const GuideGimRows& g, const float* tab, int o0, int o1, int s, int u,
-                                             float ty, int p0, int p1, int p2, float v[3]) {
-  int c0, c1;
-  float tx;
-  hires_taps(u, s, c0, c1, tx);
-  const float wy0 = 1.0f - ty, wx0 = 1.0f - tx;
-  const int at[4] = {o0 + c0, o0 + c1, o1 + c0, o1 + c1};
-  const float sw[4] = {wy0 * wx0, wy0 * tx, ty * wx0, ty * tx};
-  float w[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int d = abs(p0 - (int)g[0][at[k]]) + abs(p1 - (int)g[1][at[k]]) + abs(p2 - (int)g[2][at[k]]);
-    w[k] = sw[k] * tab[d];
-  }
-  const float den = ((w[0] + w[1]) + w[2]) + w[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float num = ((w[0] * f[c][at[0]] + w[1] * f[c][at[1]]) + w[2] * f[c][at[2]]) + w[3] * f[c][at[3]];
-    v[c] = num / den;
-  }
-}
-// the rows fr of a session's GIM, as bytes, beside its staged field rows: all 256 lanes, 16 words a row
-__device__ __forceinline__ void stage_gim_rows(unsigned char* g, const unsigned char* plane, const FieldRows r) {
-  const unsigned* grow = reinterpret_cast<const unsigned*>(plane + r.fr0 * 64);
-  unsigned* gl = reinterpret_cast<unsigned*>(g);
-  for (int j = threadIdx.x; j < r.n * 16; j += 256) gl[j] = grow[j];
-}
-__global__ __launch_bounds__(256) void canvas_compose_guided_kernel(SessionCanvases C, SessionPool P, const float* __restrict__ table,
-                                                                    const int* __restrict__ windows, int vw, int vh, unsigned char* out) {
-  __shared__ GuideFieldRows f[CANVAS_MAX_PLACED];
-  __shared__ __align__(4) GuideGimRows g[CANVAS_MAX_PLACED];
-  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
-  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
-  __shared__ FieldRows frows[CANVAS_MAX_PLACED];
-  __shared__ int nkept;
-  const int i = blockIdx.z;
-  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
-  const int y0 = blockIdx.x * CANVAS_GUIDE_BAND, rows = min(CANVAS_GUIDE_BAND, vh - y0);
-  const int Y0 = vy + y0, Y1 = Y0 + rows - 1;
-  if (threadIdx.x == 0) {
-    const int nk = canvas_keep_band(C, P, cv, vx, vw, Y0, Y1, kept, frows);
-    for (int k = 0; k < nk; ++k) frows[k].n = min(frows[k].n, CANVAS_GUIDE_BAND + 2);   // 4 output rows tap at most 5 field rows
-    nkept = nk;
-  }
-  __syncthreads();
-  const int nk = nkept;
-  for (int k = 0; k < nk; ++k)
-    for (int c = 0; c < 3; ++c) {
-      stage_field_rows(f[k][c], P.field + ((size_t)kept[k].id * 3 + c) * (64 * 64), frows[k]);
-      stage_gim_rows(g[k][c], P.gim + ((size_t)kept[k].id * 3 + c) * (64 * 64), frows[k]);
-    }
-  if (nk)
-    for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
-  __syncthreads();
-  const size_t cplane = (size_t)C.max_h * C.max_w, dplane = out ? (size_t)vh * vw : cplane;
-  const unsigned char* src = C.pix + (size_t)cv * 3 * cplane;
-  unsigned char* dst = out ? out + (size_t)i * 3 * dplane : C.pix + (size_t)cv * 3 * cplane;
-  const int dstride = out ? vw : C.max_w;
-  const int L = vw >> 2;
-  for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
-    const int ry = idx / L, cx = (idx - ry * L) * 4;
-    const int Y = Y0 + ry, X = vx + cx;
-    int pb[3][4];
-    float acc[3][4];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * cplane + (size_t)Y * C.max_w + X);
-      pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[c][e] = (float)pb[c][e];
-    }
-    for (int k = 0; k < nk; ++k) {
-      const CanvasKept q = kept[k];
-      const int S = 64 * q.s, uy = Y - q.oy;
-      if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
-      const int f2s = 2 * C.feather * q.s, fr0 = frows[k].fr0;
-      int r0, r1;
-      float ty;
-      hires_taps(uy, q.s, r0, r1, ty);
-      const int o0 = (r0 - fr0) * 64, o1 = (r1 - fr0) * 64;
-      const float wy = canvas_ramp1(uy, S, f2s);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int ux = X + e - q.ox;
-        if (ux < 0 || ux >= S) continue;
-        const float w = wy * canvas_ramp1(ux, S, f2s);
-        if (q.kind == 0) {
-          float v[3];
-          guide_sample(f[k], g[k], tab, o0, o1, q.s, ux, ty, pb[0][e], pb[1][e], pb[2][e], v);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) acc[c][e] = acc[c][e] + (127.5f * v[c]) * w;
-        } else {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float tv = 127.5f * (field_bilinear(f[k][c] + o0, f[k][c] + o1, q.s, ux, ty) + 1.0f);
-            acc[c][e] = w == 1.0f ? tv : acc[c][e] + (tv - acc[c][e]) * w;
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      *reinterpret_cast<uchar4*>(dst + c * dplane + (size_t)(out ? y0 + ry : Y) * dstride + (out ? cx : X)) =
-          make_uchar4(round_u8(acc[c][0]), round_u8(acc[c][1]), round_u8(acc[c][2]), round_u8(acc[c][3]));
-  }
-}
-hipError_t launch_canvas_compose_guided(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh,
-                                        unsigned char* out, int n, hipStream_t s) {
-  if (n < 1 || n > 65535 || !canvases_ok(C) || !P.field || !P.kind || !P.gim || !table || !windows || vw < 4 || (vw & 3) || vh < 1 ||
-      vw > C.max_w || vh > C.max_h)
-    return hipErrorInvalidValue;
-  if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(canvas_compose_guided_kernel, dim3((vh + CANVAS_GUIDE_BAND - 1) / CANVAS_GUIDE_BAND, 1, n), dim3(256), 0, s, C, P, table,
-                     windows, vw, vh, out);
-  return hipGetLastError();
-}
-
-// ---- zoomed views (npe_ops.zoom_box_mean over hires_render[_guided] / canvas_compose[_guided]) ----------------------------
-// Output pixel (Y, X) of a window at 1/k is (sum of the k x k block of 1:1 result bytes + k*k/2) / (k*k), the block at source
-// (vy + k*Y, vx + k*X).  The four kernels below are the four window kernels above with the uchar4 store replaced by integer adds: the
-// byte that enters a sum comes from the same device functions in the same float32 expressions (contraction off), so it IS the byte
-// the 1:1 kernel stores, and integer sums are exact in any order.  No 1:1 byte reaches memory; 3 * vw * vh bytes a window are written.
-//   Work split.  A workgroup owns a tile of the SOURCE: `orows` = max(1, band / k) output rows, i.e. k * orows source rows, by at
-// most `tile` source columns, i.e. ow <= (tile / k) & ~3 output columns (a multiple of 4, so a tile starts on an aligned uchar4 of
-// the source and of the output).  blockIdx.x = row group * column tiles + column tile; y, z as in the 1:1 kernel.
-//   Staging.  The source rows of the tile are walked in chunks of at most `band` rows, band = the 1:1 kernel's band height, and each
-// chunk stages exactly what that kernel stages for a band (field_rows / stage_field_rows / stage_gim_rows, canvas_keep_band for the
-// chunk's rows and the tile's columns): 16 source rows at scale 1 tap 18 field rows, which field_rows would silently cap at 10.  The
-// sums stay in LDS across the chunks.
-//   Lanes.  Consecutive lanes load consecutive aligned uchar4 of a source row (box_mean_row's ownership), compute the four result
-// bytes, merge those that fall into the same output pixel and do one LDS add per pixel touched (zoom_add4).  The plain kernels sum
-// a column of source rows in registers first, as box_mean_row does (zoom_chunk): measured on an MI355X, one 1024 x 1024 picture at
-// k = 16 takes 16.1 us so and 24.1 us with one LDS add per source row.  After the last chunk orows * ow / 4 lanes
-// divide and store one uchar4 each (zoom_store).
-//   Sizes.  Plain: band 8, tile 1024 columns (one lane pass per source row at the widest), sums orows * ow <= 8 * 1024 / 4 ints,
-// 8 KB.  Guided (no channel planes in the grid, three channels per lane): band 4, tile 256 columns, so a chunk is one pass of the 256
-// lanes and ONE 1024 x 1024 picture at k = 16 is 64 x 4 = 256 workgroups; sums 3 * 4 * 256 / 4 ints, 3 KB.
-constexpr int ZOOM_MAX = 16;
-constexpr int ZOOM_TILE = 1024, ZOOM_TILE_GUIDED = 256;
-constexpr int ZOOM_SUMS = RENDER_BAND * ZOOM_TILE / 4, ZOOM_SUMS_GUIDED = GUIDE_BAND * ZOOM_TILE_GUIDED / 4;   // per channel; k >= 2
-struct ZoomSplit {
-  int orows, ow_tile, ntiles;
-};
-__host__ __device__ inline ZoomSplit zoom_split(int band, int tile, int k, int vw) {
-  const int ow_tile = (tile / k) & ~3;
-  return ZoomSplit{band / k > 1 ? band / k : 1, ow_tile, (vw + ow_tile - 1) / ow_tile};
-}
-// this workgroup's tile: output rows oy0 .. oy0 + orows - 1, output columns ox0 .. ox0 + ow - 1 of the window
-struct ZoomTileAt {
-  int oy0, orows, ox0, ow;
-};
-__device__ __forceinline__ ZoomTileAt zoom_tile_at(int band, int tile, int k, int vw, int vh) {
-  const ZoomSplit z = zoom_split(band, tile, k, vw);
-  const int grp = blockIdx.x / z.ntiles, t = blockIdx.x - grp * z.ntiles;
-  const int oy0 = grp * z.orows, ox0 = t * z.ow_tile;
-  return ZoomTileAt{oy0, min(z.orows, vh - oy0), ox0, min(z.ow_tile, vw - ox0)};
-}
-// the four result bytes of the aligned uchar4 at source column cx of the tile -> the sums of its output row
-template <typename T>
-__device__ __forceinline__ void zoom_add4(int* row, int cx, int k, const T ob[4]) {
-  int bin = cx / k, r = cx - bin * k, t = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    t += ob[e];
-    if (++r == k) {
-      atomicAdd(&row[bin], t);
-      ++bin;
-      r = 0;
-      t = 0;
-    }
-  }
-  if (r) atomicAdd(&row[bin], t);   // r bytes (at most 4 of them this lane's) of a pixel that goes on in the next uchar4
-}
-// The output rows a chunk of `rows` source rows meets, for the kernels whose lanes sum a column of source rows in registers first
-// (box_mean_row's order): k <= band: the tile is ONE chunk of orows whole output rows, k source rows each; k > band: the tile is one
-// output row and every chunk a part of it.  A lane's work item is (output row of the chunk, aligned uchar4 column): `each` source rows.
-struct ZoomChunk {
-  int nor, each;
-};
-__device__ __forceinline__ ZoomChunk zoom_chunk(int band, int k, int orows, int rows) {
-  const int nor = k <= band ? orows : 1;
-  return ZoomChunk{nor, rows / nor};
-}
-// sum[orows][ow] -> the tile's bytes of one output plane (u8[vh][vw]): (sum + k*k/2) / (k*k), one uchar4 per lane
-__device__ __forceinline__ void zoom_store(const int* sum, const ZoomTileAt& z, int k, unsigned char* plane, int vw) {
-  const int L = z.ow >> 2, d = k * k, half = d / 2;
-  for (int j = threadIdx.x; j < z.orows * L; j += 256) {
-    const int ry = j / L, q = (j - ry * L) * 4;
-    const int* p = sum + ry * z.ow + q;
-    *reinterpret_cast<uchar4*>(plane + (size_t)(z.oy0 + ry) * vw + z.ox0 + q) =
-        make_uchar4((unsigned char)((p[0] + half) / d), (unsigned char)((p[1] + half) / d), (unsigned char)((p[2] + half) / d),
-                    (unsigned char)((p[3] + half) / d));
-  }
-}
-
-// session_render_kernel at 1/k.  grid (row groups * column tiles, 3, n)
-__global__ __launch_bounds__(256) void session_render_zoom_kernel(SessionPool P, const int* __restrict__ views, int vw, int vh, int k,
-                                                                  unsigned char* __restrict__ out) {
-  __shared__ float f[(RENDER_BAND + 2) * 64];
-  __shared__ int sum[ZOOM_SUMS];
-  const int s = P.scale, S = 64 * s;
-  const int c = blockIdx.y, i = blockIdx.z;
-  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
-  const ZoomTileAt z = zoom_tile_at(RENDER_BAND, ZOOM_TILE, k, vw, vh);
-  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile in the picture
-  for (int j = threadIdx.x; j < z.orows * z.ow; j += 256) sum[j] = 0;
-  const int kind = P.kind[id];
-  const unsigned char* src = P.src + ((size_t)id * 3 + c) * S * S;
-  const float* field = P.field + ((size_t)id * 3 + c) * (64 * 64);
-  for (int y0 = 0; y0 < R; y0 += RENDER_BAND) {
-    const int rows = min(RENDER_BAND, R - y0);
-    const FieldRows fr = field_rows(Y0 + y0, Y0 + y0 + rows - 1, s);
-    stage_field_rows(f, field, fr);
-    __syncthreads();   // the first one also publishes the zeroed sums
-    const ZoomChunk ch = zoom_chunk(RENDER_BAND, k, z.orows, rows);
-    for (int idx = threadIdx.x; idx < ch.nor * L; idx += 256) {
-      const int oy = idx / L, cx = (idx - oy * L) * 4;
-      int col[4] = {0, 0, 0, 0};
-      const int Yb = Y0 + y0 + oy * ch.each;
-      uchar4 pvs[RENDER_BAND];   // the item's source bytes first, every load in flight at once: the rows are at most RENDER_BAND
-#pragma unroll
-      for (int r = 0; r < RENDER_BAND; ++r)
-        pvs[r] = kind == 0 && r < ch.each ? *reinterpret_cast<const uchar4*>(src + (size_t)(Yb + r) * S + X0 + cx) : make_uchar4(0, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < RENDER_BAND; ++r) {
-        if (r >= ch.each) break;
-        const int Y = Yb + r;
-        int r0, r1;
-        float ty;
-        hires_taps(Y, s, r0, r1, ty);
-        const float* top = f + (r0 - fr.fr0) * 64;
-        const float* bot = f + (r1 - fr.fr0) * 64;
-        const uchar4 pv = pvs[r];
-        const unsigned char pb[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = field_bilinear(top, bot, s, X0 + cx + e, ty);
-          col[e] += round_u8(kind == 0 ? (float)pb[e] + 127.5f * v : 127.5f * (v + 1.0f));
-        }
-      }
-      zoom_add4(sum + ((y0 + oy * ch.each) / k) * z.ow, cx, k, col);
-    }
-    __syncthreads();   // f is restaged; after the last chunk: the sums are complete
-  }
-  zoom_store(sum, z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
-}
-// what the four zoomed launchers check alike: k, the output window, the result
-static bool zoom_args_ok(int n, int k, int vw, int vh, int src_w, int src_h, const void* win, const unsigned char* out) {
-  return n >= 1 && n <= 65535 && k >= 2 && k <= ZOOM_MAX && win && out && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && vw >= 4 &&
-         (vw & 3) == 0 && vh >= 1 && vw <= src_w / k && vh <= src_h / k;
-}
-static dim3 zoom_grid(int band, int tile, int k, int vw, int vh, int planes, int n) {
-  const ZoomSplit z = zoom_split(band, tile, k, vw);
-  return dim3((unsigned)((vh + z.orows - 1) / z.orows) * z.ntiles, planes, n);
-}
-hipError_t launch_session_render_zoom(const SessionPool& P, const int* views, int vw, int vh, int zoom, unsigned char* out, int n,
-                                      hipStream_t s) {
-  const int S = 64 * P.scale;
-  if (P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || !zoom_args_ok(n, zoom, vw, vh, S, S, views, out))
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_render_zoom_kernel, zoom_grid(RENDER_BAND, ZOOM_TILE, zoom, vw, vh, 3, n), dim3(256), 0, s, P, views, vw, vh,
-                     zoom, out);
-  return hipGetLastError();
-}
-
-// session_render_guided_kernel at 1/k.  grid (row groups * column tiles, 1, n); sum[c] is channel c's orows x ow
-__global__ __launch_bounds__(256) void session_render_guided_zoom_kernel(SessionPool P, const float* __restrict__ table,
-                                                                         const int* __restrict__ views, int vw, int vh, int k,
-                                                                         unsigned char* __restrict__ out) {
-  __shared__ GuideFieldRows f;
-  __shared__ __align__(4) GuideGimRows g;
-  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
-  __shared__ int sum[3][ZOOM_SUMS_GUIDED];
-  const int s = P.scale, S = 64 * s;
-  const int i = blockIdx.z;
-  const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
-  const ZoomTileAt z = zoom_tile_at(GUIDE_BAND, ZOOM_TILE_GUIDED, k, vw, vh);
-  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;
-  for (int j = threadIdx.x; j < 3 * ZOOM_SUMS_GUIDED; j += 256) (&sum[0][0])[j] = 0;
-  for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
-  const int kind = P.kind[id];
-  const size_t plane = (size_t)S * S;
-  const unsigned char* src = P.src + (size_t)id * 3 * plane;
-  for (int y0 = 0; y0 < R; y0 += GUIDE_BAND) {
-    const int rows = min(GUIDE_BAND, R - y0);
-    const FieldRows fr = field_rows(Y0 + y0, Y0 + y0 + rows - 1, s);   // at most ceil((GUIDE_BAND - 1) / s) + 2 <= GUIDE_BAND + 2 rows
-    for (int c = 0; c < 3; ++c) {
-      stage_field_rows(f[c], P.field + ((size_t)id * 3 + c) * (64 * 64), fr);
-      stage_gim_rows(g[c], P.gim + ((size_t)id * 3 + c) * (64 * 64), fr);
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
-      const int ry = idx / L, cx = (idx - ry * L) * 4;
-      const int Y = Y0 + y0 + ry, X = X0 + cx;
-      int r0, r1;
-      float ty;
-      hires_taps(Y, s, r0, r1, ty);
-      const int o0 = (r0 - fr.fr0) * 64, o1 = (r1 - fr.fr0) * 64;
-      int pb[3][4] = {};
-      unsigned char ob[3][4];
-      if (kind == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * plane + (size_t)Y * S + X);
-          pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (kind == 0) {
-          float v[3];
-          guide_sample(f, g, tab, o0, o1, s, X + e, ty, pb[0][e], pb[1][e], pb[2][e], v);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) ob[c][e] = round_u8((float)pb[c][e] + 127.5f * v[c]);
-        } else {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) ob[c][e] = round_u8(127.5f * (field_bilinear(f[c] + o0, f[c] + o1, s, X + e, ty) + 1.0f));
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) zoom_add4(sum[c] + ((y0 + ry) / k) * z.ow, cx, k, ob[c]);
-    }
-    __syncthreads();
-  }
-  for (int c = 0; c < 3; ++c) zoom_store(sum[c], z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
-}
-hipError_t launch_session_render_guided_zoom(const SessionPool& P, const float* table, const int* views, int vw, int vh, int zoom,
-                                             unsigned char* out, int n, hipStream_t s) {
-  const int S = 64 * P.scale;
-  if (P.scale < 1 || P.scale > 16 || !P.src || !P.gim || !P.field || !P.kind || !table || !zoom_args_ok(n, zoom, vw, vh, S, S, views, out))
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_render_guided_zoom_kernel, zoom_grid(GUIDE_BAND, ZOOM_TILE_GUIDED, zoom, vw, vh, 1, n), dim3(256), 0, s, P,
-                     table, views, vw, vh, zoom, out);
-  return hipGetLastError();
-}
-
-// canvas_keep_band's field rows of one kept placement for rows Y0..Y1 of the canvas (a chunk of the band it was kept for)
-__device__ __forceinline__ FieldRows canvas_chunk_rows(const CanvasKept& q, int Y0, int Y1) {
-  const int a = max(Y0, q.oy), b = min(Y1, q.oy + 64 * q.s - 1);
-  return a <= b ? field_rows(a - q.oy, b - q.oy, q.s) : FieldRows{0, 0};
-}
-// canvas_compose_kernel at 1/k.  grid (row groups * column tiles, 3, n); lane 0 keeps the placements once, for the tile's rows and
-// columns (a walk of the table in global memory by one lane: not once per chunk), and per chunk lane p says which rows of kept
-// placement p the chunk taps
-__global__ __launch_bounds__(256) void canvas_compose_zoom_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ windows, int vw,
-                                                                  int vh, int k, unsigned char* __restrict__ out) {
-  __shared__ float f[CANVAS_MAX_PLACED][(RENDER_BAND + 2) * 64];
-  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
-  __shared__ FieldRows frows[CANVAS_MAX_PLACED];
-  __shared__ int nkept;
-  __shared__ int sum[ZOOM_SUMS];
-  const int c = blockIdx.y, i = blockIdx.z;
-  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
-  const ZoomTileAt z = zoom_tile_at(RENDER_BAND, ZOOM_TILE, k, vw, vh);
-  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile on the canvas
-  for (int j = threadIdx.x; j < z.orows * z.ow; j += 256) sum[j] = 0;
-  const unsigned char* src = C.pix + ((size_t)cv * 3 + c) * C.max_h * C.max_w;
-  if (threadIdx.x == 0) nkept = canvas_keep_band(C, P, cv, X0, k * z.ow, Y0, Y0 + R - 1, kept, frows);   // once: the tile's rows
-  __syncthreads();
-  const int nk = nkept;
-  for (int y0 = 0; y0 < R; y0 += RENDER_BAND) {
-    const int rows = min(RENDER_BAND, R - y0);
-    if (R > RENDER_BAND) {   // several chunks: lane p says which field rows THIS chunk taps inside kept placement p (none: n = 0)
-      if (threadIdx.x < nk) frows[threadIdx.x] = canvas_chunk_rows(kept[threadIdx.x], Y0 + y0, Y0 + y0 + rows - 1);
-      __syncthreads();
-    }
-    for (int p = 0; p < nk; ++p) stage_field_rows(f[p], P.field + ((size_t)kept[p].id * 3 + c) * (64 * 64), frows[p]);
-    __syncthreads();
-    const ZoomChunk ch = zoom_chunk(RENDER_BAND, k, z.orows, rows);
-    for (int idx = threadIdx.x; idx < ch.nor * L; idx += 256) {
-      const int oy = idx / L, cx = (idx - oy * L) * 4;
-      const int X = X0 + cx;
-      int col[4] = {0, 0, 0, 0};
-      const int Yb = Y0 + y0 + oy * ch.each;
-      uchar4 pvs[RENDER_BAND];   // the item's canvas bytes first, every load in flight at once: the rows are at most RENDER_BAND
-#pragma unroll
-      for (int r = 0; r < RENDER_BAND; ++r)
-        pvs[r] = r < ch.each ? *reinterpret_cast<const uchar4*>(src + (size_t)(Yb + r) * C.max_w + X) : make_uchar4(0, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < RENDER_BAND; ++r) {
-        if (r >= ch.each) break;
-        const int Y = Yb + r;
-        const uchar4 pv = pvs[r];
-        float acc[4] = {(float)pv.x, (float)pv.y, (float)pv.z, (float)pv.w};
-        for (int p = 0; p < nk; ++p) {
-          const CanvasKept q = kept[p];
-          const int S = 64 * q.s, uy = Y - q.oy;
-          if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
-          const int f2s = 2 * C.feather * q.s, fr0 = frows[p].fr0;
-          int r0, r1;
-          float ty;
-          hires_taps(uy, q.s, r0, r1, ty);
-          const float* top = f[p] + (r0 - fr0) * 64;
-          const float* bot = f[p] + (r1 - fr0) * 64;
-          const float wy = canvas_ramp1(uy, S, f2s);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int ux = X + e - q.ox;
-            if (ux < 0 || ux >= S) continue;
-            const float v = field_bilinear(top, bot, q.s, ux, ty);
-            const float w = wy * canvas_ramp1(ux, S, f2s);
-            if (q.kind == 0) {
-              acc[e] = acc[e] + (127.5f * v) * w;
-            } else {
-              const float tv = 127.5f * (v + 1.0f);
-              acc[e] = w == 1.0f ? tv : acc[e] + (tv - acc[e]) * w;
-            }
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) col[e] += round_u8(acc[e]);
-      }
-      zoom_add4(sum + ((y0 + oy * ch.each) / k) * z.ow, cx, k, col);
-    }
-    __syncthreads();   // kept, frows and f are rewritten; after the last chunk: the sums are complete
-  }
-  zoom_store(sum, z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
-}
-hipError_t launch_canvas_compose_zoom(const SessionCanvases& C, const SessionPool& P, const int* windows, int vw, int vh, int zoom,
-                                      unsigned char* out, int n, hipStream_t s) {
-  if (!canvases_ok(C) || !P.field || !P.kind || !zoom_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(canvas_compose_zoom_kernel, zoom_grid(RENDER_BAND, ZOOM_TILE, zoom, vw, vh, 3, n), dim3(256), 0, s, C, P, windows, vw,
-                     vh, zoom, out);
-  return hipGetLastError();
-}
-
-// canvas_compose_guided_kernel at 1/k.  grid (row groups * column tiles, 1, n)
-__global__ __launch_bounds__(256) void canvas_compose_guided_zoom_kernel(SessionCanvases C, SessionPool P, const float* __restrict__ table,
-                                                                         const int* __restrict__ windows, int vw, int vh, int k,
-                                                                         unsigned char* __restrict__ out) {
-  __shared__ GuideFieldRows f[CANVAS_MAX_PLACED];
-  __shared__ __align__(4) GuideGimRows g[CANVAS_MAX_PLACED];
-  __shared__ float tab[SESSION_GUIDE_TABLE_LEN];
-  __shared__ CanvasKept kept[CANVAS_MAX_PLACED];
-  __shared__ FieldRows frows[CANVAS_MAX_PLACED];
-  __shared__ int nkept;
-  __shared__ int sum[3][ZOOM_SUMS_GUIDED];
-  const int i = blockIdx.z;
-  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
-  const ZoomTileAt z = zoom_tile_at(CANVAS_GUIDE_BAND, ZOOM_TILE_GUIDED, k, vw, vh);
-  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;
-  for (int j = threadIdx.x; j < 3 * ZOOM_SUMS_GUIDED; j += 256) (&sum[0][0])[j] = 0;
-  for (int j = threadIdx.x; j < SESSION_GUIDE_TABLE_LEN; j += 256) tab[j] = table[j];
-  const size_t cplane = (size_t)C.max_h * C.max_w;
-  const unsigned char* src = C.pix + (size_t)cv * 3 * cplane;
-  for (int y0 = 0; y0 < R; y0 += CANVAS_GUIDE_BAND) {
-    const int rows = min(CANVAS_GUIDE_BAND, R - y0);
-    if (threadIdx.x == 0) {
-      const int nk = canvas_keep_band(C, P, cv, X0, k * z.ow, Y0 + y0, Y0 + y0 + rows - 1, kept, frows);
-      for (int p = 0; p < nk; ++p) frows[p].n = min(frows[p].n, CANVAS_GUIDE_BAND + 2);   // 4 source rows tap at most 5 field rows
-      nkept = nk;
-    }
-    __syncthreads();
-    const int nk = nkept;
-    for (int p = 0; p < nk; ++p)
-      for (int c = 0; c < 3; ++c) {
-        stage_field_rows(f[p][c], P.field + ((size_t)kept[p].id * 3 + c) * (64 * 64), frows[p]);
-        stage_gim_rows(g[p][c], P.gim + ((size_t)kept[p].id * 3 + c) * (64 * 64), frows[p]);
-      }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
-      const int ry = idx / L, cx = (idx - ry * L) * 4;
-      const int Y = Y0 + y0 + ry, X = X0 + cx;
-      int pb[3][4];
-      float acc[3][4];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const uchar4 pv = *reinterpret_cast<const uchar4*>(src + c * cplane + (size_t)Y * C.max_w + X);
-        pb[c][0] = pv.x; pb[c][1] = pv.y; pb[c][2] = pv.z; pb[c][3] = pv.w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[c][e] = (float)pb[c][e];
-      }
-      for (int p = 0; p < nk; ++p) {
-        const CanvasKept q = kept[p];
-        const int S = 64 * q.s, uy = Y - q.oy;
-        if (uy < 0 || uy >= S || X + 3 < q.ox || X > q.ox + S - 1) continue;
-        const int f2s = 2 * C.feather * q.s, fr0 = frows[p].fr0;
-        int r0, r1;
-        float ty;
-        hires_taps(uy, q.s, r0, r1, ty);
-        const int o0 = (r0 - fr0) * 64, o1 = (r1 - fr0) * 64;
-        const float wy = canvas_ramp1(uy, S, f2s);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int ux = X + e - q.ox;
-          if (ux < 0 || ux >= S) continue;
-          const float w = wy * canvas_ramp1(ux, S, f2s);
-          if (q.kind == 0) {
-            float v[3];
-            guide_sample(f[p], g[p], tab, o0, o1, q.s, ux, ty, pb[0][e], pb[1][e], pb[2][e], v);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c][e] = acc[c][e] + (127.5f * v[c]) * w;
-          } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-              const float tv = 127.5f * (field_bilinear(f[p][c] + o0, f[p][c] + o1, q.s, ux, ty) + 1.0f);
-              acc[c][e] = w == 1.0f ? tv : acc[c][e] + (tv - acc[c][e]) * w;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const unsigned char ob[4] = {round_u8(acc[c][0]), round_u8(acc[c][1]), round_u8(acc[c][2]), round_u8(acc[c][3])};
-        zoom_add4(sum[c] + ((y0 + ry) / k) * z.ow, cx, k, ob);
-      }
-    }
-    __syncthreads();
-  }
-  for (int c = 0; c < 3; ++c) zoom_store(sum[c], z, k, out + ((size_t)i * 3 + c) * vh * vw, vw);
-}
-hipError_t launch_canvas_compose_guided_zoom(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw,
-                                             int vh, int zoom, unsigned char* out, int n, hipStream_t s) {
-  if (!canvases_ok(C) || !P.field || !P.kind || !P.gim || !table || !zoom_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out))
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(canvas_compose_guided_zoom_kernel, zoom_grid(CANVAS_GUIDE_BAND, ZOOM_TILE_GUIDED, zoom, vw, vh, 1, n), dim3(256), 0, s,
-                     C, P, table, windows, vw, vh, zoom, out);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // npe_blend.h -- device code of NPE.paint's photo blend shared by kernels_npe.hip (ian_photo_blend, ian_brush_step_batch) and
-// kernels_session.hip (ian_session_brush / ian_session_set_latent): the byte casts and photo_blend_image.
+// kernels_session.hip (ian_session_brush / ian_session_set_latent): the byte casts and photo_blend_image.  kernels_window.hip
+// includes it for the pragma alone.
 // Everything BELOW the include of this header is compiled with floating-point contraction off (see the pragma).
 #pragma once
 #include "ian_internal.h"

@@ -126,7 +126,7 @@ def photo_blend(model, Z, recon_uint8, error):
 
 # ---- full-resolution sessions (ian_sessions_reserve_hires, include/ian.h) ------------------------------------------------
 # The reference has no counterpart (NPE.py:152: "This 64 may need to change if the canvas size changes"), so these four functions ARE
-# the specification: the device (kernels_session.hip) matches them bit for bit.  s is the pool's integer scale, 1 <= s <= 16; a source
+# the specification: the device (kernels_session.hip the box mean, kernels_window.hip the render) matches them bit for bit.  s is the pool's integer scale, 1 <= s <= 16; a source
 # photo is uint8 (3, 64*s, 64*s).
 HIRES_MAX_SCALE = 16
 
@@ -266,7 +266,8 @@ def hires_render_guided(src, gim, field, kind, s, vx, vy, vw, vh, table):
 # ---- canvases (ian_sessions_reserve_canvas / ian_canvas_*, include/ian.h) ----------------------------------------------
 # A canvas is a whole photo, uint8 (3, H, W); a session is placed on it as a square of 64*s pixels a side at pixel offset (ox, oy), each
 # placement with its own scale s.  The reference has no counterpart, so these three functions ARE the specification, as hires_* are:
-# float32, every operation rounded on its own, and the device (kernels_session.hip) matches them bit for bit.
+# float32, every operation rounded on its own, and the device (kernels_session.hip the crop mean, kernels_window.hip the compose)
+# matches them bit for bit.
 CANVAS_MAX_PLACED = 8
 CANVAS_MAX_FEATHER = 16
 

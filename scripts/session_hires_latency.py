@@ -95,7 +95,7 @@ def run(arch, scales, ns, calls, repeats):
 
 def run_guided(arch, scales, ns, calls, repeats, sigma):
     """Per case: ian_session_render into a device buffer, --calls calls back to back and one device synchronisation, with the guide
-    off (session_render_kernel) and on (session_render_guided_kernel), off / on / off / on ... so that drift hits both alike."""
+    off (session_render_kernel<false>) and on (session_render_kernel<true>), off / on / off / on ... so that drift hits both alike."""
     import torch
     m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
     s = m.sessions(max(ns))

@@ -8,8 +8,10 @@ source -- the 2048 x 1536 canvas of scripts/canvas_latency.py with 1 and with 8 
                npe_ops.zoom_box_mean in numpy, medians.
   (c) event    the paint event with the zoomed window in its submission (brush_compose / brush_view) against the plain brush, medians:
                window_adds_us is what the view costs inside the event.
-usage (GPU box): python scripts/zoom_latency.py [--calls 200] [--repeats 3] [--device-only] [--out FILE]
+usage (GPU box): python scripts/zoom_latency.py [--calls 200] [--repeats 3] [--device-only] [--guided] [--out FILE]
 --device-only measures (a) alone, for comparing two builds of the kernels.
+--guided: every call under the guide (reserve_canvas_guide / reserve_guide, --sigma, default 8, as in canvas_latency.py --guided and
+session_hires_latency.py --guided): the guided zoomed kernels against the guided 1:1 kernels.
 Medians over --calls calls after warm-up, repeated --repeats times; reported are the median of the repeats and their spread
 (max - min) / median.  Prints one JSON line and, with --out, writes it there."""
 import argparse
@@ -55,7 +57,7 @@ def measure(name, k, size, plain_dev, zoom_dev, plain_host, zoom_host, brush, br
     return row
 
 
-def run(arch, calls, repeats, device_only=False):
+def run(arch, calls, repeats, device_only=False, sigma=None):
     import torch
     m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
     h = m.handle
@@ -64,6 +66,8 @@ def run(arch, calls, repeats, device_only=False):
     rs = np.random.RandomState(0)
     rows = []
     s.reserve_canvases(1, CW, CH, 4)
+    if sigma is not None:
+        s.reserve_canvas_guide(sigma)
     photo = rs.randint(0, 256, (3, CH, CW)).astype(np.uint8)
     for placed in (1, 8):
         s.canvas_put(0, photo)                                              # drops the placements of the round before
@@ -82,6 +86,8 @@ def run(arch, calls, repeats, device_only=False):
                 lambda: s.paint([0], BOX, RED), lambda: s.brush_compose([0], BOX, RED, windows=([0], (0, 0), (vw, vh), k)),
                 calls, repeats, device_only))
     s.reserve_canvases(0)
+    if sigma is not None:
+        s.reserve_guide(sigma)
     s.open_hires([1], rs.randint(0, 256, (1, 3, 1024, 1024)).astype(np.uint8))
     s.paint([1], BOX, RED)
     for k in ZOOMS:
@@ -105,10 +111,14 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--device-only", action="store_true")
+    ap.add_argument("--guided", action="store_true", help="the guided zoomed kernels against the guided 1:1 kernels")
+    ap.add_argument("--sigma", type=float, default=8.0, help="--guided: the range sigma, in levels per channel")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = {"metric": "zoom_latency", "arch": a.arch, "canvas": [CW, CH], "calls": a.calls, "repeats": a.repeats,
-           "rows": run(a.arch, a.calls, a.repeats, a.device_only)}
+    res = {"metric": "zoom_guided_latency" if a.guided else "zoom_latency", "arch": a.arch, "canvas": [CW, CH], "calls": a.calls,
+           "repeats": a.repeats, "rows": run(a.arch, a.calls, a.repeats, a.device_only, a.sigma if a.guided else None)}
+    if a.guided:
+        res["sigma"] = a.sigma
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as fh:

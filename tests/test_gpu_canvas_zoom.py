@@ -123,6 +123,24 @@ def test_eight_placements_under_one_output_row(sigma):
 
 
 @pytest.mark.parametrize("sigma", SIGMAS)
+def test_zoom_11_ends_a_tile_in_an_uneven_chunk(sigma):
+    """Two overlapping scale-1 squares, one a sample, on a 96 x 80 canvas at zoom 11: an output row's 11 source rows are a chunk of
+    8 and one of 3 plain, 4 + 4 + 3 edge-aware, and the placements kept for the tile are restaged for each."""
+    _, sh, _, _, table = pools(sigma)
+    c = picture(96, 80, 41)
+    sh.canvas_put(0, c)
+    sh.place([2, 9], 0, [(10, 6), (28, 13)], 1)
+    sh.sample([9], O.make_latents(1, seed=7))
+    paint_all(sh, [2, 9], 3)
+    assert [int(sh.read(i)["FIELD_KIND"]) for i in (2, 9)] == [0, 1]
+    whole = whole_compose(sh, c, table)
+    vw, vh = N.zoom_window(96, 80, 11)
+    assert (vw, vh) == (8, 7)
+    assert_zooms(sh, whole, [(0, 0, vw, vh, 11), (8, 0, vw, vh, 11)], "k11")
+    assert (N.zoom_box_mean(np.ascontiguousarray(whole[:, :77, :88]), 11) != N.zoom_box_mean(np.ascontiguousarray(c[:, :77, :88]), 11)).any()
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
 def test_a_scale_16_placement_on_a_large_canvas(sigma):
     mh, sh, _, _, table = pools(sigma, max_w=1028, max_h=1024)
     try:

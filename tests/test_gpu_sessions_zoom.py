@@ -80,6 +80,21 @@ def test_scale_1_at_zoom_16_walks_more_field_rows_than_one_band_stages(sigma):
 
 
 @pytest.mark.parametrize("sigma", SIGMAS)
+def test_scale_1_at_zoom_11_ends_a_tile_in_an_uneven_chunk(sigma):
+    """One output row spans 11 source rows: a chunk of 8 and one of 3 with the guide off, 4 + 4 + 3 with it on.  The far window ends
+    at the picture's last row, where the taps are clamped."""
+    _, sh, _, _, table = pools(1, sigma)
+    painted(sh, 1, [3], [6], 71)
+    # A strong second edit: painted()'s field moves a byte by under half a level, which the mean of 121 bytes does not show.  With
+    # this one the oracle's model and npe_ops alone (on the host) change 44 to 48 of a window's 60 bytes.
+    sh.paint([3, 6], (6, 8, 34, 40), (250, 30, 60), weight=32.0)
+    st = {3: state(sh, 3, kind=0), 6: state(sh, 6, kind=1)}
+    assert 9 + 11 * 5 == 64 and 8 + 11 * 4 <= 64
+    out = assert_views(sh, st, 1, table, [(8, 9, 4, 5), (0, 0, 4, 5)], 11, "s1k11")
+    assert (out[0] != N.zoom_box_mean(np.ascontiguousarray(st[3][0][:, :55, :44]), 11)).any()      # the field shows at 1/11
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
 @pytest.mark.parametrize("s", [2, 3, 16])
 def test_the_whole_picture_at_zoom_scale_is_gim_untouched_and_the_specification_painted(s, sigma):
     _, sh, _, _, table = pools(s, sigma)
@@ -124,6 +139,8 @@ def test_tiles_of_one_session_and_another_kind_in_one_call(sigma):
     assert np.array_equal(np.concatenate([tiles[0], tiles[1]], axis=2), wide[0])
     assert np.array_equal(wide[0], spec(st[5], 4, 0, 4, 64, 20, 2, table))
     assert np.array_equal(tiles[2], spec(st[12], 4, 0, 4, 32, 20, 2, table))
+    src, gim, field, kind = st[12]
+    assert kind == 1 and (tiles[2] != spec((src, gim, field, 0), 4, 0, 4, 32, 20, 2, table)).any()     # a sample is not the photo's arithmetic
 
 
 @pytest.mark.parametrize("sigma", SIGMAS)
