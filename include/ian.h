@@ -757,6 +757,44 @@ int ian_compose_zoom(ian_handle* h, int32_t n, const ian_canvas_window* windows,
 int ian_compose_brush_zoom(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, int32_t m,
                            const ian_canvas_window* windows, int32_t vw, int32_t vh, int32_t zoom, uint8_t* out, void* stream);
 
+/* ---- oriented placements: a session on a canvas at any size and tilt ----
+   A face in a group photo is 150 or 230 pixels across and leans; ian_canvas_place only knows upright squares of 64 * scale pixels.
+   An oriented placement is a similarity transform in integers: the centre (cx2, cy2) of the square in HALF pixels of the canvas
+   (pixel X covers [X, X+1), its centre is 2X+1) and A = (ax, ay), the canvas displacement per field pixel along the field's x axis
+   in Q16; the field's y axis is B = (-ay, ax).  L2 = ax*ax + ay*ay must lie in [2^32, 2^40]: a step of 1..16 canvas pixels, a side
+   of 64..1024 at any angle.  The library derives m (the smallest of 0..4 with 2^(32+2m) >= L2) and (bx, by) = round(A * 2^36 / L2),
+   field pixels per canvas pixel in Q20.
+     gather   n = 2^m nearest-pixel samples per field pixel per axis: sub-sample k of 64n has U = 2k + 1 - 64n (rows: V),
+              X = ((cx2 << (16+m)) + U*ax - V*ay) >> (17+m), Y = ((cy2 << (16+m)) + U*ay + V*ax) >> (17+m);
+              GIM = (sum of the n*n bytes + n*n/2) / (n*n).
+     compose  per pixel dx = 2X+1-cx2, dy = 2Y+1-cy2, Uq = dx*bx + dy*by (u - 32 in Q21), Vq = dy*bx - dx*by; inside the square when
+              -2^26 <= Uq, Vq < 2^26; bilinear taps at a = Q + 2^26 - 2^20, i0 = a >> 21, t = (a & (2^21-1)) / 2^21, clamped to 0..63;
+              the feather min(1, (min(Q + 2^26, 2^26 - Q) >> 5) / (feather << 16)) per axis; kinds, order and rounding as above.
+   At angle 0 with an integer origin and an integer step both are ian_canvas_place's and ian_canvas_compose's bytes.  The arithmetic
+   is npe_ops.canvas_crop_mean_oriented / canvas_compose_oriented (numpy); the device matches them bit for bit.
+   A canvas holds placements of ONE form: placing the other form while any placement of the first remains returns -7 and names the
+   canvas (a caller with mixed faces places the upright ones at angle 0).  Eight per canvas and every un-place rule hold unchanged:
+   ian_canvas_put, ian_session_open with photos, ian_session_open_hires, ian_session_load and a smaller pool un-place an oriented
+   session, ian_session_open(source = 1) on it returns -7.  ian_canvas_compose, ian_canvas_brush, ian_compose_zoom,
+   ian_compose_brush_zoom and ian_canvas_commit work on such a canvas as they are, and one call may name canvases of both forms.
+   The edge-aware compose is not extended: ian_place_oriented returns -6 while ian_sessions_reserve_edges holds a table, and
+   ian_sessions_reserve_edges returns -6 while any oriented placement exists. */
+typedef struct ian_canvas_oriented {
+  int32_t session; /* id of the session, 0..capacity-1 */
+  int32_t canvas;  /* id of the canvas, 0..count-1 */
+  int32_t cx2, cy2; /* centre of the square on the canvas, in half pixels */
+  int32_t ax, ay;  /* canvas displacement per field pixel along the field's x axis, Q16 */
+} ian_canvas_oriented;
+/* ian_canvas_place with the oriented gather in place of the box mean: GIM, then exactly ian_session_open(photos = GIM), and the
+   session is placed.  A session already placed (in either form) moves.  shown as for ian_canvas_place.
+   -6: no canvas reservation, or an edges table is reserved.  -7, naming the item, before anything is enqueued: n outside 1..256, an
+   id or a canvas outside its range, a canvas never put, L2 outside 2^32..2^40, a gather sample off the canvas, an id given twice, a
+   ninth session on one canvas, a canvas that holds placements of the other form. */
+int ian_place_oriented(ian_handle* h, int32_t n, const ian_canvas_oriented* items, uint8_t* shown, void* stream);
+/* The oriented sessions placed on one canvas, in ascending session id -> out8 (host; room for IAN_CANVAS_MAX_PLACED) and their
+   count.  Host only. */
+int ian_placements_oriented(ian_handle* h, int32_t canvas, ian_canvas_oriented* out8, int32_t* count);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -427,6 +427,43 @@ def pack_canvas_placements(ids, cids, origins, scales, sizes, placed=None, capac
     return items
 
 
+def pack_canvas_oriented(ids, cids, items, sizes, placed=None, capacity=None):
+    """Python arguments of ian_place_oriented -> a ctypes array of ian_canvas_oriented (include/ian.h), validated before the library
+    sees anything.  ids (n,) session ids, each once; cids one canvas id or (n,); items (n,4) or (4,) integers (cx2, cy2, ax, ay):
+    the square's centre in half pixels and the canvas displacement per field pixel in Q16 (npe_ops.oriented_placement), with
+    ax*ax + ay*ay in 2^32..2^40 and every gather sample on the canvas.  sizes, placed and capacity as in pack_canvas_placements."""
+    from . import npe_ops
+    from .lib import CANVAS_MAX_PLACED, CanvasOriented
+    idv = check_session_ids(ids, capacity)
+    n = len(idv)
+    cv = _canvas_ids(cids, n, sizes)
+    a = np.asarray(items)
+    if a.shape == (4,):
+        a = np.tile(a, (n, 1))
+    if a.shape != (n, 4) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("items must be integers of shape (%d,4) or (4,) as (cx2, cy2, ax, ay), got %s %s" % (n, a.dtype, a.shape))
+    after = dict(placed or {})
+    out = (CanvasOriented * n)()
+    for i in range(n):
+        sid, c = int(idv[i]), cv[i]
+        cx2, cy2, ax, ay = (int(v) for v in a[i])
+        if max(abs(cx2), abs(cy2), abs(ax), abs(ay)) >= 2 ** 31:
+            raise ValueError("item %d: (%d,%d,%d,%d) are not int32" % (i, cx2, cy2, ax, ay))
+        if not npe_ops.ORIENTED_L2_MIN <= ax * ax + ay * ay <= npe_ops.ORIENTED_L2_MAX:
+            raise ValueError("item %d: ax*ax + ay*ay of (%d,%d) outside 2^32..2^40 (a side of 64..1024 pixels)" % (i, ax, ay))
+        w, h = sizes[c]
+        if not npe_ops.oriented_inside(w, h, cx2, cy2, ax, ay):
+            raise ValueError("item %d: square (%d,%d,%d,%d) samples outside the %d x %d canvas" % (i, cx2, cy2, ax, ay, w, h))
+        after.pop(sid, None)                   # a session that moves leaves its square first
+        p = out[i]
+        p.session, p.canvas, p.cx2, p.cy2, p.ax, p.ay = sid, c, cx2, cy2, ax, ay
+    for i in range(n):
+        after[int(idv[i])] = cv[i]
+        if sum(1 for c in after.values() if c == cv[i]) > CANVAS_MAX_PLACED:
+            raise ValueError("item %d: canvas %d already holds %d sessions" % (i, cv[i], CANVAS_MAX_PLACED))
+    return out
+
+
 def pack_canvas_windows(cids, origins, size, sizes, zoom=1):
     """Python arguments of ian_canvas_compose / ian_canvas_brush -> (a ctypes array of ian_canvas_window, vw, vh), validated before
     the library sees anything.  cids (n,) canvas ids -- the same canvas may appear several times, as tiles; origins (n,2) or (2,)
@@ -650,6 +687,8 @@ class EditSessions:
         brush_compose(..., windows=)       the event and the windows in one submission -> (shown, out)
         canvas_commit(cid)                 the composed photo becomes the canvas, its sessions start again from it -> shown
         canvas_read(cid) / placements(cid) the stored photo / [(session, x, y, scale)]
+        place_oriented(ids, cids, centres, sides, angles)   the same for squares of any side (64..1024) and tilt; place_oriented_raw
+                                           takes the integers (cx2, cy2, ax, ay); placements_oriented(cid) lists them.  A canvas holds one form
         reserve_canvas_guide(sigma) / canvas_guide()   edge-aware compose: every placed session's edit stops at the photo's edges
     open, open_hires and load un-place a session; commit on a placed session is refused (canvas_commit is its form).
     Brush tips (no counterpart in NPE.py, whose brush is a square): reserve_tips(count) keeps weight images of up to 64x64 per handle;
@@ -672,7 +711,7 @@ class EditSessions:
         self.feather = 0
         self.canvas_guided = False      # edge-aware compose: the placed sessions' fields are weighted by the canvas (reserve_canvas_guide)
         self._canvas_wh = []            # per canvas (w, h) of its picture, None before canvas_put
-        self._placed = {}               # session id -> (canvas id, x, y, scale)
+        self._placed = {}               # session id -> (canvas id, x, y, scale), or oriented (canvas id, cx2, cy2, ax, ay)
         self.tips = 0                   # tip reservation: how many brush tips the handle keeps; 0 = none
         self._tips = {}                 # tip -> (tw, th) of the tips that were set
         self.reserve(capacity)
@@ -1038,6 +1077,8 @@ class EditSessions:
             self.canvas_guided = False
             return
         self._need_canvases()
+        if any(len(q) == 5 for q in self._placed.values()):
+            raise ValueError("oriented placements exist: the edge-aware compose is for upright squares")
         if sigma is not None:
             table = npe_ops.guide_table(sigma)
         else:
@@ -1080,6 +1121,7 @@ class EditSessions:
         self._need_canvases()
         items = pack_canvas_placements(ids, cids, origins, scales, self._canvas_wh, {v: q[0] for v, q in self._placed.items()},
                                        self.capacity)
+        self._one_form(items, 4)
         shown = np.empty((len(items), 3, 64, 64), np.uint8)
         self._h.canvas_place(items, shown)
         for p in items:
@@ -1087,6 +1129,56 @@ class EditSessions:
             self._sourced.discard(p.session)
             self._placed[p.session] = (p.canvas, p.x, p.y, p.scale)
         return shown
+
+    def _one_form(self, items, words):
+        """A canvas holds placements of one form (words = 4: upright, 5: oriented): refused while any of the other form remains."""
+        moving = {p.session for p in items}
+        for i, p in enumerate(items):
+            k = sum(1 for v, q in self._placed.items() if q[0] == p.canvas and len(q) != words and v not in moving)
+            if k:
+                raise ValueError("item %d: canvas %d holds %d %s placements: a canvas holds one form (place upright squares at angle 0)"
+                                 % (i, p.canvas, k, "oriented" if words == 4 else "upright"))
+
+    def place_oriented_raw(self, ids, cids, items):
+        """Sessions ids[i] open on the oriented gather (npe_ops.canvas_crop_mean_oriented) of the square items[i] = (cx2, cy2, ax, ay)
+        of canvas cids[i] (pack_canvas_oriented) and are placed there -> IM, uint8 (n,3,64,64).  Exactly open() of that picture, in
+        one submission; a session already placed, in either form, moves.  A canvas holds placements of one form, and the edge-aware
+        compose (reserve_canvas_guide) has no oriented form."""
+        self._need_canvases()
+        if self.canvas_guided:
+            raise ValueError("the edge-aware compose is on: free it first (reserve_canvas_guide())")
+        items = pack_canvas_oriented(ids, cids, items, self._canvas_wh, {v: q[0] for v, q in self._placed.items()}, self.capacity)
+        self._one_form(items, 5)
+        shown = np.empty((len(items), 3, 64, 64), np.uint8)
+        self._h.place_oriented(items, shown)
+        for p in items:
+            self._opened.add(p.session)
+            self._sourced.discard(p.session)
+            self._placed[p.session] = (p.canvas, p.cx2, p.cy2, p.ax, p.ay)
+        return shown
+
+    def place_oriented(self, ids, cids, centres, sides, angles):
+        """place_oriented_raw with the squares given as centres (n,2) or (2,) in canvas pixels (pixel X covers [X, X+1): 0.5 steps are
+        exact), sides in pixels (64..1024; one value or (n,)) and angles in degrees (one value or (n,)), through
+        npe_ops.oriented_placement.  A side of exactly 64 or 1024 is safe at multiples of 90 degrees only: elsewhere the rounding of
+        (ax, ay) may leave ax*ax + ay*ay just outside its range."""
+        from . import npe_ops
+        n = len(np.asarray(ids).reshape(-1))
+        c = np.asarray(centres, np.float64)
+        if c.shape == (2,):
+            c = np.tile(c, (n, 1))
+        sd, an = np.asarray(sides, np.float64), np.asarray(angles, np.float64)
+        sd = np.tile(sd, n) if sd.ndim == 0 else sd
+        an = np.tile(an, n) if an.ndim == 0 else an
+        if c.shape != (n, 2) or sd.shape != (n,) or an.shape != (n,) or not (np.isfinite(c).all() and np.isfinite(sd).all() and np.isfinite(an).all()):
+            raise ValueError("centres must be finite of shape (%d,2) or (2,), sides and angles one finite value or %d" % (n, n))
+        items = [npe_ops.oriented_placement(c[i, 0], c[i, 1], sd[i], an[i]) for i in range(n)]
+        return self.place_oriented_raw(ids, cids, np.asarray(items, np.int64).reshape(n, 4))
+
+    def placements_oriented(self, cid):
+        """-> [(session, cx2, cy2, ax, ay)] of the oriented sessions placed on canvas cid, in ascending session id."""
+        cid = self._canvas(cid, need_put=False)
+        return sorted((v,) + tuple(q[1:]) for v, q in self._placed.items() if q[0] == cid and len(q) == 5)
 
     def _windows(self, cids, origins, size, zoom=1):
         self._need_canvases()
@@ -1139,7 +1231,7 @@ class EditSessions:
     def placements(self, cid):
         """-> [(session, x, y, scale)] of the sessions placed on canvas cid, in ascending session id."""
         cid = self._canvas(cid, need_put=False)
-        return sorted((v, q[1], q[2], q[3]) for v, q in self._placed.items() if q[0] == cid)
+        return sorted((v, q[1], q[2], q[3]) for v, q in self._placed.items() if q[0] == cid and len(q) == 4)
 
     def reset(self, ids):
         """Reset: re-open from the stored GIM."""

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["kernels_tapgemm.hip", "kernels_misc.hip", "kernels_brush.hip", "kernels_head.hip", "kernels_npe.hip", "kernels_session.hip", "kernels_window.hip", "kernels_wgrad.hip", "kernels_train.hip", "ian_runtime.cpp", "ian_train_abi.cpp", "ian_trainer.cpp", "ian_comm_rccl.cpp"]
 HEADERS = ["ian_internal.h", "ian_tg_types.h", "ian_tg_plan.h", "ian_row_bands.h", "ian_guard.h", "npe_blend.h", "ian_dact.h", "ian_rt_types.h", "ian_rt_util.inc", "ian_rt_pack.inc", "ian_rt_schedule.inc", "ian_rt_exec.inc",
-           "ian_rt_autotune.inc", "ian_rt_io.inc", "ian_rt_backward.inc", "ian_rt_edit.inc", "ian_rt_session.inc", "ian_rt_canvas.inc", "ian_session_history.h", "ian_session_record.h", "ian_tip_check.h", "ian_edit_plan.h", "ian_fit_step.h", "ian_rt_api.inc", "ian_rt_layer.inc", os.path.join("..", "..", "include", "ian.h"), os.path.join("..", "..", "include", "ian_train.h")]
+           "ian_rt_autotune.inc", "ian_rt_io.inc", "ian_rt_backward.inc", "ian_rt_edit.inc", "ian_rt_session.inc", "ian_rt_canvas.inc", "ian_session_history.h", "ian_session_record.h", "ian_tip_check.h", "ian_edit_plan.h", "ian_oriented.h", "ian_fit_step.h", "ian_rt_api.inc", "ian_rt_layer.inc", os.path.join("..", "..", "include", "ian.h"), os.path.join("..", "..", "include", "ian_train.h")]
 # IAN_ABLATION_BUILD=1 (tests/test_gpu_ablation.py, scripts/ablate_tapgemm.sh): a SEPARATE library, libian_ablation.so, with
 # -DIAN_ABLATION: the measured NEGATIVE results kept runnable (tapgemm K-loop schedules 0 and 3, the in-launch split-K
 # combine, the batch-1 streaming deconv of kernels_b1.hip, the 4-wave tapwgrad tile -- all bitwise / parity tested there)

@@ -514,6 +514,17 @@ hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, c
 // a whole picture (x = y = 0), written over the canvas itself
 hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh, int zoom,
                                  unsigned char* out, int n, hipStream_t s);
+// oriented placements (ian_place_oriented).  The canvases' second table, device int[count][CANVAS_MAX_PLACED][8]:
+// (session, cx2, cy2, ax, ay, bx, by, m) in ascending session id, session -1 ends the list.  It is not a member of SessionCanvases,
+// so the kernels above keep their arguments.
+// place: items = device int[n][6] (ian_canvas_oriented: session, canvas, cx2, cy2, ax, ay), every sample on the picture (the host
+// has checked).  npe_ops.canvas_crop_mean_oriented -> what launch_canvas_place writes.
+hipError_t launch_canvas_place_oriented(const SessionCanvases& C, const SessionPool& P, const int* items, const float* table, float* x, int n,
+                                        hipStream_t s);
+// npe_ops.canvas_compose_oriented[_zoom] of n windows of canvases that hold oriented placements; windows, zoom and out as for
+// launch_canvas_compose, no guided form
+hipError_t launch_canvas_compose_oriented(const SessionCanvases& C, const int* otable, const SessionPool& P, const int* windows, int vw, int vh,
+                                          int zoom, unsigned char* out, int n, hipStream_t s);
 
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,

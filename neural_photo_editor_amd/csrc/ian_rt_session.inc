@@ -64,7 +64,7 @@ struct SessScratchBuf {
   SessGroup group;
 };
 const SessScratchBuf SESS_SCRATCH[] = {
-    {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 6 * sizeof(int32_t), SESS_BASE},
+    {offsetof(SessionScratch, d_tab), (size_t)BATCH_MAX * 7 * sizeof(int32_t), SESS_BASE},
     {offsetof(SessionScratch, d_photo), 0, SESS_BASE},
     {offsetof(SessionScratch, d_shown), (size_t)BATCH_MAX * SESS_IMG, SESS_BASE},
     {offsetof(SessionScratch, d_rtab), 0, SESS_BASE},

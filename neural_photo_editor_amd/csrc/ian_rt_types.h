@@ -291,7 +291,7 @@ struct ian_handle {
   // The device buffers beside the pool, as plain data: SESS_SCRATCH (ian_rt_session.inc) names each once, with the reservation that
   // owns it and its size; nothing else allocates or frees them.
   struct SessionScratch {
-    int* d_tab = nullptr;              // per call: open / set_latent = n ids, ian_canvas_place = [n ids | 5n placement words]
+    int* d_tab = nullptr;              // per call: open / set_latent = n ids, ian_canvas_place = [n ids | 5n placement words], ian_place_oriented = [n ids | 6n]
     float* d_tanh = nullptr;           // to_tanh of the 256 uint8 levels, float32
     unsigned char* d_photo = nullptr;  // staging of host photos [256][3*64*64], allocated by the first open that needs it
     unsigned char* d_shown = nullptr;  // staging of the canvas images [256][3*64*64]
@@ -358,6 +358,13 @@ struct ian_handle {
     int* d_cwin = nullptr;               // per ian_canvas_compose / _brush / _commit call n ian_canvas_window records
     std::vector<int32_t> cwin_shadow;    // upload source of d_cwin
     float* d_edges = nullptr;            // f32[766], the range weights of ian_sessions_reserve_edges; nullptr = the plain compose.  Goes with the canvases
+    // oriented placements (ian_place_oriented): per session where it is placed in that form (canvas -1: nowhere;
+    // sized with `placed`, a session is in at most one of the two), the canvases' second device table int[count][8][8], allocated
+    // by the first oriented place of a reservation and freed with the canvases, its host copy and per canvas whether it lags
+    std::vector<ian_canvas_oriented> oplaced;
+    int* d_otab = nullptr;
+    std::vector<int32_t> otab_shadow;
+    std::vector<char> odirty;
   } sess;
   bool warm_armed = false;       // a keep_warm_kernel is (or may still be) spinning on edit_stream: enter_stream releases it
   bool pin_img_valid = false;    // pin[PIN_IMG..] holds the image that is resident in the output slot

@@ -24,6 +24,7 @@
 #include "ian_session_record.h"    // a saved session's padding rule, meta validation and ring map: plain C++, also compiled on its own by a test
 #include "ian_tip_check.h"         // a brush tip's size and weights, an event's rectangle against its tip: plain C++, also compiled on its own by a test
 #include "ian_edit_plan.h"         // the passes and steps of a brush, clone or stroke call and the layout of its table: plain C++, also compiled on its own by a test
+#include "ian_oriented.h"          // the integer geometry of an oriented placement: derive, inside, bounding box: plain C++, also compiled on its own by a test
 
 using namespace ian;
 

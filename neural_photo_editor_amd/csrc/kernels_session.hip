@@ -11,6 +11,7 @@
 //   session_fit_begin_kernel / _adam_kernel / _loss_kernel  ian_session_fit: IM := GIM, one Adam step on the latent rows, the loss read-out
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   canvas_place_kernel        canvases: the exact box mean of a square of a whole photo -> GIM, IM, encoder input (any byte alignment)
+//   canvas_place_oriented_kernel   the same for a square of any size and tilt: n x n nearest-pixel samples per field pixel, in integers
 //   session_history_save_kernel / _move_kernel  undo history: a session's Z and UMASK rows to and from its ring of saved states
 //   session_pack_kernel / session_unpack_kernel  saved sessions: every row of a session, its ring included, to and from one record
 // The kernels that show a window of a full-resolution picture or of a canvas (render, compose, their zoomed views) are in
@@ -672,6 +673,57 @@ hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, c
                                hipStream_t s) {
   if (n < 1 || n > 65535 || !canvases_ok(C) || !P.gim || !P.im || !items || !table || !x) return hipErrorInvalidValue;
   hipLaunchKernelGGL(canvas_place_kernel, dim3(64, 3, n), dim3(256), 0, s, C, P, items, table, x);
+  return hipGetLastError();
+}
+
+// place, input side, for an oriented placement (npe_ops.canvas_crop_mean_oriented): grid (64, 3, n) as above, one
+// workgroup per row gy of one channel of the 64x64 picture.  The row is n sub-rows of 64n nearest-pixel samples, n = 2^m; a lane owns
+// sub-sample column k (and k + 256, ... at n > 4), sums its n samples in a register and does one LDS add into field pixel k >> m.
+// The coordinates are the specification's, in 64 bits (U*ax reaches 2^30 and cx2 << (16+m) 2^34).  The host has checked that all
+// four corner samples lie on the picture, and X, Y are monotone in (U, V); the clamp only keeps a corrupted table inside the array.
+// Along a tilted row consecutive lanes read bytes 1/n of a step apart on a slanted line: the reads are not coalesced.  A place is
+// rare and reads at most 3 * (64n)^2 bytes (3 MB at side 1024), so that is left as it is.
+__global__ __launch_bounds__(256) void canvas_place_oriented_kernel(SessionCanvases C, SessionPool P, const int* __restrict__ items,
+                                                                    const float* __restrict__ table, float* __restrict__ x) {
+  __shared__ float tab[256];
+  __shared__ int sum[64];
+  const int gy = blockIdx.x, c = blockIdx.y, i = blockIdx.z;
+  const int* it = items + 6 * i;
+  const int id = it[0], cv = it[1], cx2 = it[2], cy2 = it[3], ax = it[4], ay = it[5];
+  if (threadIdx.x < 64) sum[threadIdx.x] = 0;
+  stage_tanh_table<256>(tab, table);
+  const long long L2 = (long long)ax * ax + (long long)ay * ay;
+  int m = 0;
+  while (m < 4 && (1LL << (32 + 2 * m)) < L2) ++m;   // npe_ops.oriented_derive's m
+  const int n = 1 << m, N = 64 * n, sh = 17 + m;
+  const long long X00 = (long long)cx2 * (1LL << (16 + m)), Y00 = (long long)cy2 * (1LL << (16 + m));
+  const unsigned char* plane = C.pix + ((size_t)cv * 3 + c) * C.max_h * C.max_w;
+  for (int k = threadIdx.x; k < N; k += 256) {
+    const long long U = 2 * k + 1 - N;
+    int acc = 0;
+    for (int r = 0; r < n; ++r) {
+      const long long V = 2 * (gy * n + r) + 1 - N;
+      const long long X = (X00 + U * ax - V * ay) >> sh, Y = (Y00 + U * ay + V * ax) >> sh;
+      const int Xc = (int)min(max(X, 0LL), (long long)C.max_w - 1), Yc = (int)min(max(Y, 0LL), (long long)C.max_h - 1);
+      acc += plane[(size_t)Yc * C.max_w + Xc];
+    }
+    atomicAdd(&sum[k >> m], acc);
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    const int e = threadIdx.x * 4, d = n * n, half = d / 2;
+    uchar4 v;
+    v.x = (unsigned char)((sum[e] + half) / d);
+    v.y = (unsigned char)((sum[e + 1] + half) / d);
+    v.z = (unsigned char)((sum[e + 2] + half) / d);
+    v.w = (unsigned char)((sum[e + 3] + half) / d);
+    store_opened_px(P, id, i, (size_t)c * 64 * 64 + gy * 64 + e, v, tab, x);
+  }
+}
+hipError_t launch_canvas_place_oriented(const SessionCanvases& C, const SessionPool& P, const int* items, const float* table, float* x, int n,
+                                        hipStream_t s) {
+  if (n < 1 || n > 65535 || !canvases_ok(C) || !P.gim || !P.im || !items || !table || !x) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(canvas_place_oriented_kernel, dim3(64, 3, n), dim3(256), 0, s, C, P, items, table, x);
   return hipGetLastError();
 }
 

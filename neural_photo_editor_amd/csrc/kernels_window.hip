@@ -2,6 +2,8 @@
 //   session_render_kernel<GUIDED>       a window of a session's picture: SRC + 127.5 * FIELD sampled at full size (4.3; guided 4.11)
 //   canvas_compose_kernel<GUIDED>       a window of a whole photo: the canvas plus every placed session's feathered field (4.7; 4.13)
 //   session_render_zoom_kernel<GUIDED>, canvas_compose_zoom_kernel<GUIDED>   the same windows at 1/k, never written at 1:1 (4.14)
+//   canvas_compose_oriented_kernel, canvas_compose_oriented_zoom_kernel      a canvas whose placements have any size and tilt (4.16):
+//                                       ComposeOrientedPx4 in the same loops and sinks, the taps read from global memory, no staging
 // GUIDED: the field's four taps weighted by the photo (ian_sessions_reserve_guide / _edges).  Every result byte is specified by
 // npe_ops.py (hires_render[_guided], canvas_compose[_guided], zoom_box_mean) and matched bit for bit.  Three layers, each written once:
 //   staging  the field rows a band of output rows taps (and, guided, the same rows of GIM and the range weights) -> LDS
@@ -11,7 +13,8 @@
 #include <cstdint>
 
 #include "ian_internal.h"
-#include "npe_blend.h"   // floating-point contraction off from here on: every expression below depends on it
+#include "ian_oriented.h"   // oriented_bbox, shared with the host
+#include "npe_blend.h"  // floating-point contraction off from here on: every expression below depends on it
 
 namespace ian {
 
@@ -337,6 +340,106 @@ __device__ __forceinline__ void canvas_stage(CanvasStage<GUIDED>& st, const Sess
   for (int p = 0; p < nk; ++p) stage_rows(st.rows[p], P, st.kept[p].id, c0, st.frows[p]);
 }
 
+// ---- px4: a canvas of oriented placements (npe_ops.canvas_compose_oriented) -----------------------------------------
+// A placement is a similarity transform in integers: centre (cx2, cy2) in half pixels, (bx, by) field pixels per canvas pixel in Q20.
+// A pixel's field coordinates are Uq = dx*bx + dy*by (u - 32 in Q21) and Vq = dy*bx - dx*by with dx = 2X+1-cx2, dy = 2Y+1-cy2: up to
+// 2^36, so 64 bits until the inside test (-2^26 <= Q < 2^26) has passed, 32 from there.  A band that crosses a tilted square can tap
+// any of the 64 field rows, so nothing is staged: the four taps are read from the session's FIELD plane in global memory (16 KB a
+// channel, read-only during a compose, shared by every workgroup of the launch: L2 and the vector cache serve them).
+struct OrientedKept {
+  int id, cx2, cy2, bx, by, kind;
+  OrientedBox box;
+};
+struct OrientedStage {
+  OrientedKept kept[CANVAS_MAX_PLACED];
+  int nkept;
+};
+constexpr int ORIENTED_LIM = 1 << 26;
+// the taps of one axis at field coordinate Q: a = Q + 2^26 - 2^20 in [-2^20, 2^27), t exact in float32 (21 bits over a power of two)
+__device__ __forceinline__ void oriented_taps(int Q, int& lo, int& hi, float& t) {
+  const int a = Q + ORIENTED_LIM - (1 << 20), i0 = a >> 21;
+  t = (float)(a & ((1 << 21) - 1)) / 2097152.0f;
+  lo = min(max(i0, 0), 63);
+  hi = min(max(i0 + 1, 0), 63);
+}
+// the feather along one axis: f16 = feather << 16 (0: none); d <= 2^21 is exact in float32
+__device__ __forceinline__ float oriented_ramp1(int Q, int f16) {
+  if (f16 == 0) return 1.0f;
+  const int d = min(Q + ORIENTED_LIM, ORIENTED_LIM - Q) >> 5;
+  return fminf(1.0f, (float)d / (float)f16);
+}
+// The result bytes of the aligned uchar4 at (X, Y) of a canvas in channel c0: ComposePx4's walk of the kept placements with the
+// oriented geometry.  A lane's four pixels advance (Uq, Vq) by (2bx, -2by) from one 64-bit base per row and placement.
+struct ComposeOrientedPx4 {
+  static constexpr int NC = 1;
+  const OrientedStage& st;
+  const float* field;   // channel c0's plane of session 0: a session's is 3 * 4096 floats on
+  const unsigned char* src;
+  int stride, feather, nk;
+  __device__ __forceinline__ void load(int X, int Y, uchar4 pv[NC]) const {
+    pv[0] = *reinterpret_cast<const uchar4*>(src + (size_t)Y * stride + X);
+  }
+  __device__ __forceinline__ void operator()(int X, int Y, const uchar4 pv[NC], unsigned char ob[NC][4]) const {
+    int pb[4];
+    float acc[4];
+    unpack4(pv[0], pb);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = (float)pb[e];
+    const int f16 = feather << 16;
+    for (int k = 0; k < nk; ++k) {
+      const OrientedKept q = st.kept[k];
+      if (Y < q.box.y0 || Y > q.box.y1 || X + 3 < q.box.x0 || X > q.box.x1) continue;
+      const long long dx = 2 * X + 1 - q.cx2, dy = 2 * Y + 1 - q.cy2;
+      long long Uq = dx * q.bx + dy * q.by, Vq = dy * q.bx - dx * q.by;
+      const float* F = field + (size_t)q.id * (3 * 64 * 64);
+#pragma unroll
+      for (int e = 0; e < 4; ++e, Uq += 2 * q.bx, Vq -= 2 * q.by) {
+        if (Uq < -ORIENTED_LIM || Uq >= ORIENTED_LIM || Vq < -ORIENTED_LIM || Vq >= ORIENTED_LIM) continue;
+        const int U = (int)Uq, V = (int)Vq;
+        int c0, c1, r0, r1;
+        float tx, ty;
+        oriented_taps(U, c0, c1, tx);
+        oriented_taps(V, r0, r1, ty);
+        const float* top = F + r0 * 64;
+        const float* bot = F + r1 * 64;
+        const float a0 = top[c0], a1 = bot[c0];
+        const float t = a0 + tx * (top[c1] - a0);
+        const float b = a1 + tx * (bot[c1] - a1);
+        const float v = t + ty * (b - t);
+        const float w = oriented_ramp1(V, f16) * oriented_ramp1(U, f16);
+        if (q.kind == 0) {   // uniform over the workgroup
+          acc[e] = acc[e] + (127.5f * v) * w;
+        } else {
+          const float tv = 127.5f * (v + 1.0f);
+          acc[e] = w == 1.0f ? tv : acc[e] + (tv - acc[e]) * w;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ob[0][e] = round_u8(acc[e]);
+  }
+};
+// Lane 0 walks canvas cv's oriented table (int[8][8]: session, cx2, cy2, ax, ay, bx, by, m; session -1 ends the list) once per
+// workgroup and keeps the placements whose bounding boxes meet rows Y0..Y1, columns X0 .. X0 + W - 1, in the table's order -> how many
+__device__ __forceinline__ int oriented_keep(OrientedStage& st, const int* __restrict__ otable, const SessionPool& P, int cv, int X0, int W, int Y0,
+                                             int Y1) {
+  if (threadIdx.x == 0) {
+    int nk = 0;
+    const int* tb = otable + (size_t)cv * (CANVAS_MAX_PLACED * 8);
+    for (int k = 0; k < CANVAS_MAX_PLACED; ++k) {
+      const int* t = tb + 8 * k;
+      const int id = t[0];
+      if (id < 0) break;
+      const OrientedBox box = oriented_bbox(t[1], t[2], t[3], t[4]);
+      if (Y1 < box.y0 || Y0 > box.y1 || X0 + W - 1 < box.x0 || X0 > box.x1) continue;
+      st.kept[nk++] = OrientedKept{id, t[1], t[2], t[5], t[6], P.kind[id], box};
+    }
+    st.nkept = nk;
+  }
+  __syncthreads();
+  return st.nkept;
+}
+
 // ---- sinks and loops -------------------------------------------------------------------------------------------------------------
 // 1:1: the bytes of item (ry, cx) of a band go to row row0 + ry, column col0 + cx of plane c.  A window of `out` (u8 [n][3][vh][vw]),
 // or, out == nullptr, the whole picture over the source itself (commit): a lane stores exactly the bytes it loaded, after loading
@@ -600,6 +703,41 @@ __global__ __launch_bounds__(256) void canvas_compose_zoom_kernel(SessionCanvase
   zoom_store<NC>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
 }
 
+// compose over oriented placements: the plain kernels' grid and loops, nothing staged but the kept placements
+__global__ __launch_bounds__(256) void canvas_compose_oriented_kernel(SessionCanvases C, const int* __restrict__ otable, SessionPool P,
+                                                                      const int* __restrict__ windows, int vw, int vh, unsigned char* out) {
+  __shared__ OrientedStage st;
+  const int c0 = blockIdx.y, i = blockIdx.z;
+  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
+  const int y0 = blockIdx.x * RENDER_BAND, nrows = min(RENDER_BAND, vh - y0);
+  const int Y0 = vy + y0;
+  const int nk = oriented_keep(st, otable, P, cv, vx, vw, Y0, Y0 + nrows - 1);
+  const size_t plane = (size_t)C.max_h * C.max_w;
+  unsigned char* src = C.pix + ((size_t)cv * 3 + c0) * plane;
+  const ComposeOrientedPx4 px{st, P.field + c0 * (64 * 64), src, C.max_w, C.feather, nk};
+  const StoreRows to = out ? StoreRows{out + ((size_t)i * 3 + c0) * vh * vw, (size_t)vh * vw, vw, y0, 0} : StoreRows{src, plane, C.max_w, Y0, vx};
+  px_rows(px, vx, Y0, nrows, vw >> 2, to);
+}
+// the same at 1/k: canvas_compose_zoom_kernel<false>'s tiles and chunks; the sums are LDS adds, so the chunks need no barrier between them
+__global__ __launch_bounds__(256) void canvas_compose_oriented_zoom_kernel(SessionCanvases C, const int* __restrict__ otable, SessionPool P,
+                                                                           const int* __restrict__ windows, int vw, int vh, int k,
+                                                                           unsigned char* __restrict__ out) {
+  using Z = ZoomShape<false>;
+  __shared__ OrientedStage st;
+  __shared__ int sum[1][Z::SUMS];
+  const int c0 = blockIdx.y, i = blockIdx.z;
+  const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
+  const ZoomTileAt z = zoom_tile_at(Z::BAND, Z::TILE, k, vw, vh);
+  const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile on the canvas
+  zoom_clear<1>(sum, z);
+  const int nk = oriented_keep(st, otable, P, cv, X0, k * z.ow, Y0, Y0 + R - 1);   // its barrier also publishes the zeroed sums
+  const size_t plane = (size_t)C.max_h * C.max_w;
+  const ComposeOrientedPx4 px{st, P.field + c0 * (64 * 64), C.pix + ((size_t)cv * 3 + c0) * plane, C.max_w, C.feather, nk};
+  for (int y0 = 0; y0 < R; y0 += Z::BAND) zoom_chunk_sum<false>(px, sum, z, k, X0, Y0 + y0, y0, min(Z::BAND, R - y0), L);
+  __syncthreads();   // the sums are complete
+  zoom_store<1>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
+}
+
 // ---- the launchers ---------------------------------------------------------------------------------------------------------------
 // what both check alike: the count, the zoom, the window against its source, the table of windows, and at 1/k the result
 static bool window_args_ok(int n, int zoom, int vw, int vh, int src_w, int src_h, const void* win, const unsigned char* out) {
@@ -641,6 +779,18 @@ hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P,
     auto kernel = table ? canvas_compose_zoom_kernel<true> : canvas_compose_zoom_kernel<false>;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, C, P, table, windows, vw, vh, zoom, out);
   }
+  return hipGetLastError();
+}
+hipError_t launch_canvas_compose_oriented(const SessionCanvases& C, const int* otable, const SessionPool& P, const int* windows, int vw, int vh,
+                                          int zoom, unsigned char* out, int n, hipStream_t s) {
+  if (!canvases_ok(C) || !otable || !P.field || !P.kind || !window_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out))
+    return hipErrorInvalidValue;
+  if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
+  const dim3 grid = window_grid(false, zoom, vw, vh, n);
+  if (zoom == 1)
+    hipLaunchKernelGGL(canvas_compose_oriented_kernel, grid, dim3(256), 0, s, C, otable, P, windows, vw, vh, out);
+  else
+    hipLaunchKernelGGL(canvas_compose_oriented_zoom_kernel, grid, dim3(256), 0, s, C, otable, P, windows, vw, vh, zoom, out);
   return hipGetLastError();
 }
 

@@ -56,6 +56,7 @@ EXPORTS = (
     "ian_canvas_read", "ian_canvas_placements",
     "ian_sessions_reserve_edges", "ian_sessions_edges",
     "ian_session_zoom", "ian_session_brush_zoom", "ian_compose_zoom", "ian_compose_brush_zoom",
+    "ian_place_oriented", "ian_placements_oriented",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -159,6 +160,8 @@ def load_library():
     lib.ian_session_brush_zoom.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, fp, C.POINTER(SessionView), i32, i32, i32, fp, vp]
     lib.ian_compose_zoom.argtypes = [vp, i32, C.POINTER(CanvasWindow), i32, i32, i32, fp, vp]
     lib.ian_compose_brush_zoom.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, i32, C.POINTER(CanvasWindow), i32, i32, i32, fp, vp]
+    lib.ian_place_oriented.argtypes = [vp, i32, C.POINTER(CanvasOriented), fp, vp]
+    lib.ian_placements_oriented.argtypes = [vp, i32, C.POINTER(CanvasOriented), fp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -243,6 +246,12 @@ class SessionCloneEvent(C.Structure):
 class CanvasPlacement(C.Structure):
     """ian_canvas_placement (include/ian.h): one session placed on a canvas as a square of 64 * scale pixels at (x, y)."""
     _fields_ = [("session", C.c_int32), ("canvas", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("scale", C.c_int32)]
+
+
+class CanvasOriented(C.Structure):
+    """ian_canvas_oriented (include/ian.h): one session placed on a canvas as a square of any size and tilt: the centre in half pixels
+    and the canvas displacement per field pixel in Q16 (npe_ops.oriented_placement)."""
+    _fields_ = [("session", C.c_int32), ("canvas", C.c_int32), ("cx2", C.c_int32), ("cy2", C.c_int32), ("ax", C.c_int32), ("ay", C.c_int32)]
 
 
 class CanvasWindow(C.Structure):
@@ -654,6 +663,18 @@ class Handle:
         count = np.zeros(1, np.int32)
         self._check(self.lib.ian_canvas_placements(self._h, int(canvas), out, _ptr(count)))
         return [(p.session, p.x, p.y, p.scale) for p in out[:int(count[0])]]
+
+    def place_oriented(self, items, shown=None, stream=None):
+        """ian_place_oriented; items = a ctypes array of CanvasOriented (n = its length), shown u8[n,3,64,64] or None."""
+        self._check(self.lib.ian_place_oriented(self._h, len(items), items, _ptr(shown) if shown is not None else C.c_void_p(0),
+                                                C.c_void_p(stream or 0)))
+
+    def placements_oriented(self, canvas):
+        """ian_placements_oriented -> [(session, cx2, cy2, ax, ay)] of one canvas in ascending session id; host only."""
+        out = (CanvasOriented * CANVAS_MAX_PLACED)()
+        count = np.zeros(1, np.int32)
+        self._check(self.lib.ian_placements_oriented(self._h, int(canvas), out, _ptr(count)))
+        return [(p.session, p.cx2, p.cy2, p.ax, p.ay) for p in out[:int(count[0])]]
 
     def session_read(self, sid, what, stream=None, scale=0):
         code, dtype, shape = SESSION_FIELDS[what]

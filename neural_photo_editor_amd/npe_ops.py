@@ -434,6 +434,161 @@ def canvas_compose_guided_zoom(canvas, placed, f, vx, vy, vw, vh, k, table):
     return zoom_box_mean(canvas_compose_guided(canvas, placed, f, vx, vy, k * int(vw), k * int(vh), table), k)
 
 
+# ---- oriented placements (ian_place_oriented, include/ian.h) -----------------------------------------------------------
+# A placement as a similarity transform: the square's centre (cx2, cy2) in half pixels of the canvas (pixel X covers [X, X+1), its
+# centre is 2X+1), and A = (ax, ay), the canvas displacement per field pixel along the field's x axis in Q16; the field's y axis is
+# B = (-ay, ax).  L2 = ax*ax + ay*ay in [2^32, 2^40] is a step of 1..16 canvas pixels, a side of 64..1024.  The geometry is all
+# integers (Python ints / int64 here), so these functions ARE the specification and the device matches them bit for bit;
+# oriented_placement is the only place a float touches it.
+ORIENTED_L2_MIN, ORIENTED_L2_MAX = 1 << 32, 1 << 40
+
+
+def oriented_placement(cx, cy, side, angle_deg):
+    """A centre in canvas pixels, a side in pixels and an angle in degrees -> (cx2, cy2, ax, ay)."""
+    a = np.deg2rad(float(angle_deg))
+    step = float(side) / 64.0
+    return (int(round(2.0 * float(cx))), int(round(2.0 * float(cy))), int(round(step * np.cos(a) * 65536.0)),
+            int(round(step * np.sin(a) * 65536.0)))
+
+
+def _oriented_ints(*v):
+    out = []
+    for x in v:
+        if int(x) != x or not -2 ** 31 <= int(x) < 2 ** 31:
+            raise ValueError("an oriented placement is (cx2, cy2, ax, ay), all int32, got %r" % (v,))
+        out.append(int(x))
+    return out
+
+
+def oriented_derive(ax, ay):
+    """-> (m, bx, by).  m in 0..4 is the smallest with 2^(32+2m) >= L2: the gather takes n = 2^m samples per field pixel per axis.
+    (bx, by) = round(A * 2^36 / L2), field pixels per canvas pixel in Q20, by floor division: floor((2*a*2^36 + L2) / (2*L2))."""
+    ax, ay = _oriented_ints(ax, ay)
+    L2 = ax * ax + ay * ay
+    if not ORIENTED_L2_MIN <= L2 <= ORIENTED_L2_MAX:
+        raise ValueError("ax*ax + ay*ay = %d outside 2^32..2^40 (a side of 64..1024 pixels)" % L2)
+    m = next(k for k in range(5) if (1 << (32 + 2 * k)) >= L2)
+    return m, ((ax << 37) + L2) // (2 * L2), ((ay << 37) + L2) // (2 * L2)
+
+
+def _oriented_sample(c2, m, d):
+    return ((c2 << (16 + m)) + d) >> (17 + m)
+
+
+def oriented_inside(w, h, cx2, cy2, ax, ay):
+    """Whether every sample of canvas_crop_mean_oriented lies on a w x h canvas.  The sample coordinates are monotone in (U, V), so
+    the four corner samples decide."""
+    cx2, cy2, ax, ay = _oriented_ints(cx2, cy2, ax, ay)
+    m = oriented_derive(ax, ay)[0]
+    e = (64 << m) - 1
+    for U in (-e, e):
+        for V in (-e, e):
+            X, Y = _oriented_sample(cx2, m, U * ax - V * ay), _oriented_sample(cy2, m, U * ay + V * ax)
+            if not (0 <= X < int(w) and 0 <= Y < int(h)):
+                return False
+    return True
+
+
+def oriented_bbox(cx2, cy2, ax, ay):
+    """-> (x0, y0, x1, y1), inclusive pixel bounds that contain every pixel canvas_compose_oriented can change: the square's half
+    extent along either axis is 32 * (|ax| + |ay|) / 65536 pixels, rounded up to half pixels, plus one pixel for the rounding of
+    (bx, by)."""
+    cx2, cy2, ax, ay = _oriented_ints(cx2, cy2, ax, ay)
+    h2 = (abs(ax) + abs(ay) + 1023) >> 10
+    return ((cx2 - h2) >> 1) - 1, ((cy2 - h2) >> 1) - 1, ((cx2 + h2) >> 1) + 1, ((cy2 + h2) >> 1) + 1
+
+
+def canvas_crop_mean_oriented(canvas, cx2, cy2, ax, ay):
+    """The 64x64 picture a session placed at (cx2, cy2, ax, ay) starts from -> uint8 (3,64,64).  Sub-sample k = 0 .. 64n-1 of an axis
+    has U = 2k + 1 - 64n (rows: V); DX = U*ax - V*ay, DY = U*ay + V*ax; the sample is canvas pixel
+    X = ((cx2 << (16+m)) + DX) >> (17+m), Y likewise (arithmetic shifts), and GIM = (sum of the n*n bytes + n*n/2) // (n*n)."""
+    canvas = np.asarray(canvas)
+    if canvas.dtype != np.uint8 or canvas.ndim != 3 or canvas.shape[0] != 3:
+        raise ValueError("a canvas is uint8 (3,H,W), got %s %s" % (canvas.dtype, canvas.shape))
+    cx2, cy2, ax, ay = _oriented_ints(cx2, cy2, ax, ay)
+    m = oriented_derive(ax, ay)[0]
+    if not oriented_inside(canvas.shape[2], canvas.shape[1], cx2, cy2, ax, ay):
+        raise ValueError("square (%d,%d,%d,%d) samples outside the %d x %d canvas" % (cx2, cy2, ax, ay, canvas.shape[2], canvas.shape[1]))
+    n = 1 << m
+    U = (2 * np.arange(64 * n, dtype=np.int64) + 1 - 64 * n)[None, :]
+    V = U.T
+    X = ((cx2 << (16 + m)) + U * ax - V * ay) >> (17 + m)
+    Y = ((cy2 << (16 + m)) + U * ay + V * ax) >> (17 + m)
+    total = canvas[:, Y, X].reshape(3, 64, n, 64, n).sum(axis=(2, 4), dtype=np.int64)
+    return np.uint8((total + (n * n) // 2) // (n * n))
+
+
+def _oriented_taps(Q):
+    a = Q + (1 << 26) - (1 << 20)
+    i0 = a >> 21
+    t = np.float32(a & ((1 << 21) - 1)) / np.float32(1 << 21)
+    return np.clip(i0, 0, 63), np.clip(i0 + 1, 0, 63), t
+
+
+def _oriented_ramp(Q, f):
+    if f == 0:
+        return np.ones(Q.shape, np.float32)
+    d = np.minimum(Q + (1 << 26), (1 << 26) - Q) >> 5
+    return np.minimum(np.float32(1.0), np.float32(d) / np.float32(f << 16))
+
+
+def canvas_compose_oriented(canvas, placed, f, vx, vy, vw, vh):
+    """canvas_compose for oriented placements -> uint8 (3, vh, vw).  placed = [(cx2, cy2, ax, ay, FIELD, kind), ...] in ascending
+    session id.  Per pixel (X, Y) and placement: dx = 2X+1-cx2, dy = 2Y+1-cy2, Uq = dx*bx + dy*by (u - 32 in Q21),
+    Vq = dy*bx - dx*by; the pixel is inside when -2^26 <= Uq, Vq < 2^26.  Taps along an axis: a = Q + 2^26 - 2^20, i0 = a >> 21,
+    t = float32(a & (2^21-1)) / float32(2^21), both taps clamped to 0..63; the sample is hires_render's bilinear expression.  The
+    ramp is 1.0f at f == 0, otherwise d = min(Q + 2^26, 2^26 - Q) >> 5 and r = min(1.0f, float32(d) / float32(f << 16));
+    w = r(Vq) * r(Uq).  Kinds, order and rounding are canvas_compose's."""
+    canvas = np.asarray(canvas)
+    if canvas.dtype != np.uint8 or canvas.ndim != 3 or canvas.shape[0] != 3:
+        raise ValueError("a canvas is uint8 (3,H,W), got %s %s" % (canvas.dtype, canvas.shape))
+    H, W = canvas.shape[1:]
+    vx, vy, vw, vh = int(vx), int(vy), int(vw), int(vh)
+    if vw < 1 or vh < 1 or vx < 0 or vy < 0 or vx + vw > W or vy + vh > H:
+        raise ValueError("window (%d,%d) + %d x %d outside the %d x %d canvas" % (vx, vy, vw, vh, W, H))
+    if len(placed) > CANVAS_MAX_PLACED:
+        raise ValueError("a canvas holds at most %d placements, got %d" % (CANVAS_MAX_PLACED, len(placed)))
+    if int(f) != f or not 0 <= int(f) <= CANVAS_MAX_FEATHER:
+        raise ValueError("feather must be an integer in 0..%d, got %r" % (CANVAS_MAX_FEATHER, f))
+    f = int(f)
+    acc = np.float32(canvas[:, vy:vy + vh, vx:vx + vw])
+    Xc = (2 * np.arange(vx, vx + vw, dtype=np.int64) + 1)[None, :]
+    Yc = (2 * np.arange(vy, vy + vh, dtype=np.int64) + 1)[:, None]
+    for (cx2, cy2, ax, ay, field, kind) in placed:
+        cx2, cy2, ax, ay = _oriented_ints(cx2, cy2, ax, ay)
+        _, bx, by = oriented_derive(ax, ay)
+        if kind not in (0, 1):
+            raise ValueError("kind must be 0 (photo plus field) or 1 (plain sample), got %r" % (kind,))
+        dx, dy = Xc - cx2, Yc - cy2
+        Uq, Vq = dx * bx + dy * by, dy * bx - dx * by
+        lim = 1 << 26
+        inside = (Uq >= -lim) & (Uq < lim) & (Vq >= -lim) & (Vq < lim)
+        if not inside.any():
+            continue
+        Uq, Vq = np.where(inside, Uq, 0), np.where(inside, Vq, 0)
+        F = np.asarray(field, np.float32)
+        c0, c1, tx = _oriented_taps(Uq)
+        r0, r1, ty = _oriented_taps(Vq)
+        top = F[:, r0, c0] + tx * (F[:, r0, c1] - F[:, r0, c0])
+        bot = F[:, r1, c0] + tx * (F[:, r1, c1] - F[:, r1, c0])
+        v = top + ty * (bot - top)
+        w = _oriented_ramp(Vq, f) * _oriented_ramp(Uq, f)
+        if kind == 0:
+            new = acc + (np.float32(127.5) * v) * w
+        else:
+            t = np.float32(127.5) * (v + np.float32(1.0))
+            new = np.where(w == np.float32(1.0), t, acc + (t - acc) * w)
+        assert new.dtype == np.float32 and w.dtype == np.float32
+        acc = np.where(inside[None], new, acc)
+    return np.uint8(np.clip(np.rint(acc), 0, 255))
+
+
+def canvas_compose_oriented_zoom(canvas, placed, f, vx, vy, vw, vh, k):
+    """canvas_compose_oriented of the source window (vx, vy, k*vw, k*vh) at 1/k -> uint8 (3, vh, vw)."""
+    k = _zoom(k)
+    return zoom_box_mean(canvas_compose_oriented(canvas, placed, f, vx, vy, k * int(vw), k * int(vh)), k)
+
+
 # ---- local edits (ian_sessions_reserve_local / ian_session_local, include/ian.h; DESIGN.md 4.4) -------------------------------------
 # NPE.py declares USER_MASK "currently not implemented" (NPE.py:58-59, :221), offers gk (NPE.py:167-175) for "changes to MASK ... more
 # localized to the brush location" and dampen (NPE.py:184-189) as a commented-out alternative for D (NPE.py:227, :298).  These four

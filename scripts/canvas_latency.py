@@ -13,7 +13,11 @@ the same bytes.
 plain and guided compose alternating per repeat in one run (the table is switched between the bursts, outside the timing), the
 ratio guided / plain per row; and the comparison above with the guide on both sides: the guided compose of the scale-16 placement
 against ian_session_render under ian_sessions_reserve_guide with the same table on a second pool (a pool has a guide or canvases).
-usage (GPU box): python scripts/canvas_latency.py [--guided] [--calls 200] [--repeats 3] [--out FILE]
+--oriented measures the compose over oriented placements (ian_place_oriented): two canvases with the same photo, one
+with 1 / 8 upright squares of 256 pixels (scale 4), one with 1 / 8 squares of side 256 at 23 degrees around the same centres, every
+session painted; the same two windows, device buffers only, the aligned and the oriented compose alternating per repeat in one run,
+and the ratio oriented / aligned per row.
+usage (GPU box): python scripts/canvas_latency.py [--guided | --oriented] [--calls 200] [--repeats 3] [--out FILE]
 Medians over --calls calls after warm-up, repeated --repeats times; reported are the median of the repeats and their spread
 (max - min) / median.  Prints one JSON line and, with --out, writes it there."""
 import argparse
@@ -185,6 +189,39 @@ def run_guided(arch, calls, repeats, sigma=8.0):
     return rows, against
 
 
+def run_oriented(arch, calls, repeats, side=256.0, angle=23.0):
+    import torch
+    m = IAN(os.path.join(ROOT, "neural_photo_editor_amd", "configs", arch + ".py"), True, params=O.make_params(arch, 1))
+    s = m.sessions(16)
+    s.reserve_hires(16)
+    rs = np.random.RandomState(0)
+    photo = rs.randint(0, 256, (3, CH, CW)).astype(np.uint8)
+    s.reserve_canvases(2, CW, CH, 4)
+    rows = []
+    for placed in (1, 8):
+        for cid in (0, 1):
+            s.canvas_put(cid, photo)                                        # drops the placements of the round before
+        origins = [(301 + 200 * k, 403 + 40 * k) for k in range(placed)]
+        s.place(np.arange(placed), 0, origins, 4)
+        s.place_oriented(8 + np.arange(placed), 1, [(x + 128, y + 128) for (x, y) in origins], side, angle)
+        s.paint(np.arange(placed), (20, 20, 44, 44), (255, 0, 0))
+        s.paint(8 + np.arange(placed), (20, 20, 44, 44), (255, 0, 0))
+        for (vw, vh, origin) in ((256, 256, (400, 450)), (CW, CH, (0, 0))):
+            wa, _, _ = api.pack_canvas_windows([0], origin, (vw, vh), [(CW, CH)] * 2)
+            wo, _, _ = api.pack_canvas_windows([1], origin, (vw, vh), [(CW, CH)] * 2)
+            d_out = torch.empty((1, 3, vh, vw), dtype=torch.uint8, device="cuda")
+            al, orr = [], []
+            for _ in range(repeats):                                        # alternating: the two see the same machine
+                al += device_us(lambda: m.handle.canvas_compose(wa, vw, vh, d_out), calls, 1)
+                orr += device_us(lambda: m.handle.canvas_compose(wo, vw, vh, d_out), calls, 1)
+            row = {"placed": placed, "window": [vw, vh], "side": side, "angle": angle, "device_bytes": compose_bytes(1, vw, vh),
+                   "aligned_device": stat(al), "oriented_device": stat(orr)}
+            row["oriented_over_aligned"] = round(row["oriented_device"]["p50_us"] / row["aligned_device"]["p50_us"], 3)
+            rows.append(row)
+    m.close()
+    return rows, None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="IAN_simple")
@@ -192,10 +229,15 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--guided", action="store_true", help="the edge-aware compose against the plain one (DESIGN.md 4.13)")
+    ap.add_argument("--oriented", action="store_true", help="the compose over oriented placements against the aligned one (DESIGN.md 4.16)")
     a = ap.parse_args()
-    rows, against = (run_guided if a.guided else run)(a.arch, a.calls, a.repeats)
-    res = {"metric": "canvas_guided_latency" if a.guided else "canvas_latency", "arch": a.arch, "canvas": [CW, CH], "calls": a.calls,
-           "repeats": a.repeats, "rows": rows, "against_render": against}
+    if a.guided and a.oriented:
+        ap.error("--guided and --oriented are two runs")
+    rows, against = (run_oriented if a.oriented else run_guided if a.guided else run)(a.arch, a.calls, a.repeats)
+    metric = "canvas_oriented_latency" if a.oriented else "canvas_guided_latency" if a.guided else "canvas_latency"
+    res = {"metric": metric, "arch": a.arch, "canvas": [CW, CH], "calls": a.calls, "repeats": a.repeats, "rows": rows}
+    if against is not None:
+        res["against_render"] = against
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as fh:
