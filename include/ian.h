@@ -795,6 +795,28 @@ int ian_place_oriented(ian_handle* h, int32_t n, const ian_canvas_oriented* item
    count.  Host only. */
 int ian_placements_oriented(ian_handle* h, int32_t canvas, ian_canvas_oriented* out8, int32_t* count);
 
+/* ---- display-ready pixels: interleaved RGB, RGBA and BGRA out ----
+   Whatever shows or saves a picture (a toolkit's image, a browser's ImageData, a texture upload, PIL) takes interleaved pixels; the
+   calls above write planes.  The pool has one pixel format for `out` of ian_session_render, ian_canvas_compose, ian_session_zoom,
+   ian_session_brush_zoom, ian_compose_zoom, ian_compose_brush_zoom, ian_session_brush_view, ian_session_brush_tip with views and
+   ian_canvas_brush, at every zoom, with or without a guide or an edges table, for upright and oriented canvases:
+     0  planar (the default)  u8[n,3,vh,vw], exactly as documented with each call
+     1  rgb                   u8[n,vh,vw,3]
+     2  rgba                  u8[n,vh,vw,4], A = 255
+     3  bgra                  u8[n,vh,vw,4], A = 255
+   Window i starts at out + i * vh * vw * bytes-per-pixel.  Every byte is the byte format 0 gives for that pixel and channel
+   (npe_ops.pack_window of the planar result); the device stores a lane's four pixels at once, 12 or 16 consecutive bytes, and no
+   planar copy is written on the way.  What the calls check stays: x and vw multiples of 4, out 4-byte aligned.
+   Not governed: shown (64x64, planar), ian_session_read, ian_canvas_read, and what is written in place (ian_canvas_commit,
+   ian_session_open(source = 1)): the stored pictures stay planar, and ian_canvas_put / ian_session_open_hires keep taking planes.
+   The format is a setting of the pool, not session state: records, history and ian_session_read know nothing of it.  Host only: no
+   device state is touched, nothing is synchronised, and the next call is the first under the new format.  ian_sessions_reserve(0)
+   puts it back to 0, a resize keeps it.
+   -6 without ian_sessions_reserve.  -7: a format outside 0..3; the previous format stays in force. */
+int ian_sessions_set_pixels(ian_handle* h, int32_t format);
+/* The format in force, 0..3; -6 without ian_sessions_reserve. */
+int ian_sessions_pixels(ian_handle* h);
+
 /* The 256 float32 values the open kernel maps uint8 levels to: np.float32(2.0 * (level / 255.0) - 1.0), i.e. NPE.py:257's
    np.asarray([to_tanh(IM)], dtype=np.float32) per level.  Needs no handle and no device. */
 void ian_session_tanh_table(float* out256);

@@ -714,6 +714,7 @@ class EditSessions:
         self._placed = {}               # session id -> (canvas id, x, y, scale), or oriented (canvas id, cx2, cy2, ax, ay)
         self.tips = 0                   # tip reservation: how many brush tips the handle keeps; 0 = none
         self._tips = {}                 # tip -> (tw, th) of the tips that were set
+        self.pixels = 0                 # the pixel format of every window result (pixel_format): 0 planar, 1 rgb, 2 rgba, 3 bgra
         self.reserve(capacity)
         self._h.sessions_set_blend(npe_ops.gaussian_half_kernel(sigma, int(4.0 * float(sigma) + 0.5)))
 
@@ -727,6 +728,23 @@ class EditSessions:
         self._opened = {v for v in self._opened if v < capacity}
         self._sourced = {v for v in self._sourced if v < capacity}
         self._placed = {v: p for v, p in self._placed.items() if v < capacity}
+
+    def pixel_format(self, fmt=None):
+        """What render, brush_view, paint(view=), scroll(view=), compose and brush_compose return from now on: "planar" (0, the
+        default) uint8 (n,3,vh,vw); "rgb" (1) uint8 (n,vh,vw,3); "rgba" (2) and "bgra" (3) uint8 (n,vh,vw,4) with A = 255 --
+        npe_ops.pack_window of the planar result, stored that way by the device.  A name or an id sets the format; None changes
+        nothing.  -> the name of the format in force.  shown, read(), canvas_read() and what the pool stores stay planar."""
+        from . import npe_ops
+        if fmt is not None:
+            fid = npe_ops.pixel_format_id(fmt)
+            self._h.sessions_set_pixels(fid)
+            self.pixels = fid
+        return npe_ops.PIXEL_FORMATS[self.pixels]
+
+    def _window_out(self, n, vw, vh):
+        """The array a window call writes: n windows of vw x vh in the pool's pixel format."""
+        from . import npe_ops
+        return np.empty(npe_ops.window_shape(n, vw, vh, self.pixels), np.uint8)
 
     def reserve_hires(self, scale):
         """Keep every session's photo at (3, 64*scale, 64*scale), scale in 1..16; 0 frees that again.  Changing the scale drops the
@@ -987,12 +1005,12 @@ class EditSessions:
         return pack_session_views(ids, origins, size, self.scale, self.capacity, self._opened, self._sourced, events, zoom)
 
     def render(self, ids, origins, size, zoom=1):
-        """Windows of the pictures at full resolution, as last displayed -> uint8 (n,3,vh,vw).  origins (n,2) or (2,) as (x, y),
+        """Windows of the pictures at full resolution, as last displayed -> uint8 (n,3,vh,vw) (pixel_format: (n,vh,vw,3|4)).  origins (n,2) or (2,) as (x, y),
         size (vw, vh) or one integer; x and vw multiples of 4.  The same id may appear several times (tiles).  zoom = k > 1: the
         views at 1/k (npe_ops.hires_render_zoom): origins stay in full-resolution pixels, size is the output's, and the source
         window (x, y, k*vw, k*vh) must lie inside the picture (npe_ops.zoom_window gives the size that shows all of it)."""
         views, vw, vh = self._views(ids, origins, size, None, zoom)
-        out = np.empty((len(views), 3, vh, vw), np.uint8)
+        out = self._window_out(len(views), vw, vh)
         if zoom == 1:
             self._h.session_render(views, vw, vh, out)
         else:
@@ -1005,7 +1023,7 @@ class EditSessions:
         ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
         views, vw, vh = self._views(ids, origins, size, ev, zoom)
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
-        out = np.empty((len(ev), 3, vh, vw), np.uint8)
+        out = self._window_out(len(ev), vw, vh)
         sel = None if tips is None else self._tipsel(tips, self._event_boxes(ev))
         if zoom != 1:
             self._h.session_brush_zoom(ev, sel, shown, views, vw, vh, zoom, out)
@@ -1186,11 +1204,11 @@ class EditSessions:
 
     def compose(self, cids, origins, size, zoom=1):
         """Windows of the canvases with every placed session's edit on top (npe_ops.canvas_compose; after reserve_canvas_guide
-        npe_ops.canvas_compose_guided) -> uint8 (n,3,vh,vw).  origins (n,2) or (2,) as (x, y), size (vw, vh) or one integer; x and vw
+        npe_ops.canvas_compose_guided) -> uint8 (n,3,vh,vw) (pixel_format: (n,vh,vw,3|4)).  origins (n,2) or (2,) as (x, y), size (vw, vh) or one integer; x and vw
         multiples of 4.  The same canvas may appear several times.  zoom = k > 1: the windows at 1/k (npe_ops.canvas_compose_zoom),
         as in render."""
         win, vw, vh = self._windows(cids, origins, size, zoom)
-        out = np.empty((len(win), 3, vh, vw), np.uint8)
+        out = self._window_out(len(win), vw, vh)
         if zoom == 1:
             self._h.canvas_compose(win, vw, vh, out)
         else:
@@ -1207,7 +1225,7 @@ class EditSessions:
         win, vw, vh = self._windows(*windows)
         zoom = windows[3] if len(windows) == 4 else 1
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
-        out = np.empty((len(win), 3, vh, vw), np.uint8)
+        out = self._window_out(len(win), vw, vh)
         if zoom == 1:
             self._h.canvas_brush(ev, win, vw, vh, out, shown)
         else:
@@ -1400,6 +1418,7 @@ class EditSessions:
             self._sourced = set()
             self.canvases, self.canvas_max, self.feather, self._canvas_wh, self._placed = 0, (0, 0), 0, [], {}
             self.tips, self._tips = 0, {}
+            self.pixels = 0
 
 
 class IAN:

@@ -477,7 +477,7 @@ hipError_t launch_session_unpack(const SessionPool& P, const SessionRings& R, co
 // box mean -> GIM, IM and x[i] = table[byte], the outputs of launch_session_open_in
 hipError_t launch_session_hires_open(const unsigned char* photos, const SessionPool& P, const int* ids, const float* table, float* x, int n,
                                      hipStream_t s);
-// The window launches (kernels_window.hip).  Both take table and zoom:
+// The window launches (kernels_window.hip).  They take table (the oriented one has no guided form), zoom and format:
 //   table   nullptr: the plain arithmetic.  Otherwise device float[766], the range weights by summed absolute byte difference
 //           (ian_sessions_reserve_guide; ian_sessions_reserve_edges, 4.13): the guided arithmetic, the guide of a
 //           session being its own GIM and the photo the session's SRC or the canvas.
@@ -485,11 +485,17 @@ hipError_t launch_session_hires_open(const unsigned char* photos, const SessionP
 //           npe_ops.zoom_box_mean of the 1:1 result of the source window (x, y, zoom * vw, zoom * vh), which must lie inside the
 //           picture: x and y of views / windows stay in full-resolution pixels, vw x vh is the OUTPUT size, out is never nullptr
 //           and 4-byte aligned.  No full-resolution result is written anywhere.
+//   format  the pixels of out (ian_sessions_set_pixels; npe_ops.pack_window).  PIXELS_PLANAR: u8 [n][3][vh][vw], the
+//           kernels as they were before the formats.  PIXELS_RGB / _RGBA / _BGRA: interleaved, u8 [n][vh][vw][window_bpp], A = 255;
+//           a lane then owns its four pixels in all three channels and stores them at once, guided or not.  out is never nullptr
+//           under a packed format: what is written in place is planar.
 // npe_ops.hires_render[_guided] of n windows: views = device int[n][3] (session, x, y), every window vw x vh with x and vw multiples
 // of 4.  out u8 [n][3][vh][vw]; out == nullptr: the whole picture (vw = vh = S, x = y = 0) written over the session's own SRC row
 constexpr int SESSION_GUIDE_TABLE_LEN = 3 * 255 + 1;
+constexpr int PIXELS_PLANAR = 0, PIXELS_RGB = 1, PIXELS_RGBA = 2, PIXELS_BGRA = 3;
+constexpr int pixels_bpp(int format) { return format == PIXELS_RGBA || format == PIXELS_BGRA ? 4 : 3; }   // bytes a pixel of out, planar: over its planes
 hipError_t launch_session_render(const SessionPool& P, const float* table, const int* views, int vw, int vh, int zoom, unsigned char* out, int n,
-                                 hipStream_t s);
+                                 int format, hipStream_t s);
 // canvases (ian_sessions_reserve_canvas): whole photos in device memory and, per canvas, the table of the sessions
 // placed on it.  Beside the pool for SessionRings' reason; only the canvas kernels take it.  All nullptr / 0 without the reservation.
 constexpr int CANVAS_MAX_PLACED = 8;
@@ -510,10 +516,10 @@ inline bool canvases_ok(const SessionCanvases& C) {
 hipError_t launch_canvas_place(const SessionCanvases& C, const SessionPool& P, const int* items, const float* table, float* x, int n,
                                hipStream_t s);
 // npe_ops.canvas_compose[_guided] of n windows: windows = device int[n][3] (canvas, x, y), every window vw x vh with x and vw multiples
-// of 4; table and zoom as for launch_session_render.  out u8 [n][3][vh][vw], 4-byte aligned; out == nullptr: n == 1 and the window is
+// of 4; table, zoom and format as for launch_session_render.  out u8 [n][3][vh][vw], 4-byte aligned; out == nullptr: n == 1 and the window is
 // a whole picture (x = y = 0), written over the canvas itself
 hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh, int zoom,
-                                 unsigned char* out, int n, hipStream_t s);
+                                 unsigned char* out, int n, int format, hipStream_t s);
 // oriented placements (ian_place_oriented).  The canvases' second table, device int[count][CANVAS_MAX_PLACED][8]:
 // (session, cx2, cy2, ax, ay, bx, by, m) in ascending session id, session -1 ends the list.  It is not a member of SessionCanvases,
 // so the kernels above keep their arguments.
@@ -524,7 +530,7 @@ hipError_t launch_canvas_place_oriented(const SessionCanvases& C, const SessionP
 // npe_ops.canvas_compose_oriented[_zoom] of n windows of canvases that hold oriented placements; windows, zoom and out as for
 // launch_canvas_compose, no guided form
 hipError_t launch_canvas_compose_oriented(const SessionCanvases& C, const int* otable, const SessionPool& P, const int* windows, int vw, int vh,
-                                          int zoom, unsigned char* out, int n, hipStream_t s);
+                                          int zoom, unsigned char* out, int n, int format, hipStream_t s);
 
 // identity-edge gradient hand-over: gd[p,c] (+)= gs[p,coff+c] * act'(y[p,c]) * scale[c]   (NHWC, strides ss / ds)
 hipError_t launch_grad_pass(const float* gs, int ss, int coff, float* gd, const float* y, int ds, const float* scale,

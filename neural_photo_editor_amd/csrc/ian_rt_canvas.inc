@@ -454,7 +454,8 @@ int canvas_window_check(ian_handle* h, const char* fn, int n, const ian_canvas_w
   return 0;
 }
 
-// the windows of n canvases into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, one whole picture over its own canvas.
+// the windows of n canvases into d_out (device, u8[n,3,vh,vw]; packed under S.pixels), or, d_out == nullptr, one whole picture over
+// its own canvas, planar whatever the pool's format.
 // zoom > 1: the windows at 1/zoom.  S.d_edges (ian_sessions_reserve_edges): each photo-mode field's taps weighted by the canvas
 int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int vw, int vh, unsigned char* d_out, hipStream_t st, int zoom) {
   auto& S = h->sess;
@@ -466,14 +467,15 @@ int canvas_compose_enqueue(ian_handle* h, int n, const ian_canvas_window* w, int
   std::vector<char> oriented((size_t)S.canv.count, 0);
   for (const ian_canvas_oriented& p : S.oplaced)
     if (p.canvas >= 0) oriented[p.canvas] = 1;
-  const size_t each = (size_t)3 * vh * vw;
+  const int format = d_out ? S.pixels : PIXELS_PLANAR;
+  const size_t each = (size_t)pixels_bpp(format) * vh * vw;
   for (int a = 0; a < n;) {
     const bool form = oriented[w[a].canvas] != 0;
     int b = a + 1;
     while (b < n && (oriented[w[b].canvas] != 0) == form) ++b;
     unsigned char* out = d_out ? d_out + (size_t)a * each : nullptr;
-    if (form) HIPCHK(h, launch_canvas_compose_oriented(S.canv, S.d_otab, S.arr.pool, S.d_cwin + 3 * a, vw, vh, zoom, out, b - a, st));
-    else HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_edges, S.d_cwin + 3 * a, vw, vh, zoom, out, b - a, st));
+    if (form) HIPCHK(h, launch_canvas_compose_oriented(S.canv, S.d_otab, S.arr.pool, S.d_cwin + 3 * a, vw, vh, zoom, out, b - a, format, st));
+    else HIPCHK(h, launch_canvas_compose(S.canv, S.arr.pool, S.d_edges, S.d_cwin + 3 * a, vw, vh, zoom, out, b - a, format, st));
     a = b;
   }
   return 0;

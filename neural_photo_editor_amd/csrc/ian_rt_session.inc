@@ -215,8 +215,9 @@ void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
     S.res_valid = false;
   }
 }
-// ian_sessions_reserve(0) and ian_destroy: w, radius (ian_sessions_set_blend) and dampen_thresh stay
+// ian_sessions_reserve(0) and ian_destroy: w, radius (ian_sessions_set_blend) and dampen_thresh stay, the pixel format does not
 void sessions_free(ian_handle* h) {
+  h->sess.pixels = PIXELS_PLANAR;
   canvases_free(h);
   for (SessGroup g : {SESS_TIPS, SESS_HISTORY, SESS_LOCAL, SESS_HIRES, SESS_BASE}) sess_free_group(h->sess, g);
 }
@@ -398,6 +399,21 @@ int sessions_guide(ian_handle* h, float* table_out) {
   auto& S = h->sess;
   if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_HIRES))) return rc;
   return guide_table_get(h, fn, S.d_guide, table_out);
+}
+
+// The pixel format of `out` in every window call (DESIGN.md 4.17) is a setting of the pool like the guide, and host state only: the
+// enqueue of the next call reads it.  Records, history and ian_session_read know nothing of it.
+int sessions_set_pixels(ian_handle* h, int format) {
+  const char* fn = "ian_sessions_set_pixels";
+  if (int rc = session_need(h, fn, SESS_BASE)) return rc;
+  if (format < PIXELS_PLANAR || format > PIXELS_BGRA)
+    return fail(h, -7, "%s: format %d outside 0..3 (0 planar, 1 rgb, 2 rgba, 3 bgra)", fn, format);
+  h->sess.pixels = format;
+  return 0;
+}
+int sessions_pixels(ian_handle* h) {
+  if (int rc = session_need(h, "ian_sessions_pixels", SESS_BASE)) return rc;
+  return h->sess.pixels;
 }
 
 int sessions_set_blend(ian_handle* h, const double* gauss_half, int radius) {
@@ -632,7 +648,8 @@ int session_view_check(ian_handle* h, const char* fn, int n, const ian_session_v
   return 0;
 }
 
-// the windows of n views into d_out (device, u8[n,3,vh,vw]), or, d_out == nullptr, the whole picture over each session's own SRC.
+// the windows of n views into d_out (device, u8[n,3,vh,vw]; packed under S.pixels), or, d_out == nullptr, the whole picture over each
+// session's own SRC, planar whatever the pool's format.
 // zoom > 1: the views at 1/zoom.  S.d_guide (ian_sessions_reserve_guide): the field's taps weighted by the photo; nullptr: plain
 int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, int vw, int vh, unsigned char* d_out, hipStream_t st,
                            int zoom = 1) {
@@ -640,7 +657,7 @@ int session_render_enqueue(ian_handle* h, int n, const ian_session_view* views, 
   S.views_shadow.resize((size_t)3 * n);
   memcpy(S.views_shadow.data(), views, (size_t)n * sizeof(ian_session_view));
   HIPCHK(h, hipMemcpyAsync(S.d_views, S.views_shadow.data(), (size_t)n * sizeof(ian_session_view), hipMemcpyHostToDevice, st));
-  HIPCHK(h, launch_session_render(S.arr.pool, S.d_guide, S.d_views, vw, vh, zoom, d_out, n, st));
+  HIPCHK(h, launch_session_render(S.arr.pool, S.d_guide, S.d_views, vw, vh, zoom, d_out, n, d_out ? S.pixels : PIXELS_PLANAR, st));
   return 0;
 }
 
@@ -657,7 +674,7 @@ int session_render_target(ian_handle* h, uint8_t* out, size_t bytes, ResultTarge
 // session_rows_enter, the caller's enqueue(d_out, st), the copy down for a host array, session_rows_leave.
 template <typename Enqueue>
 int window_call(ian_handle* h, int n, int vw, int vh, uint8_t* out, void* stream, Enqueue enqueue) {
-  const size_t bytes = (size_t)n * 3 * (size_t)vh * (size_t)vw;
+  const size_t bytes = (size_t)n * pixels_bpp(h->sess.pixels) * (size_t)vh * (size_t)vw;
   ResultTarget t = {};
   int rc = session_render_target(h, out, bytes, &t);
   if (rc) return rc;
@@ -1066,7 +1083,7 @@ int edit_passes(ian_handle* h, const EditCall& C, uint8_t* shown, void* stream) 
   const int n = P.n, pass = h->opt.brush_pass;
   int rc;
   ResultTarget win = {};
-  const size_t win_bytes = (size_t)W.count * 3 * (size_t)W.vh * (size_t)W.vw;
+  const size_t win_bytes = (size_t)W.count * pixels_bpp(S.pixels) * (size_t)W.vh * (size_t)W.vw;
   if (W.kind != W.NONE && (rc = session_render_target(h, W.out, win_bytes, &win))) return rc;
   const bool hit = n <= pass && session_residency_hit(S, n, C.ids, C.stride);
   hipStream_t st = (hipStream_t)stream;
@@ -1524,6 +1541,8 @@ int ian_session_open(ian_handle* h, int32_t n, const int32_t* ids, const uint8_t
 int ian_sessions_reserve_hires(ian_handle* h, int32_t scale) {
   return h ? sessions_reserve_hires(h, scale) : -1;
 }
+int ian_sessions_set_pixels(ian_handle* h, int32_t format) { return h ? sessions_set_pixels(h, format) : -1; }
+int ian_sessions_pixels(ian_handle* h) { return h ? sessions_pixels(h) : -1; }
 int ian_sessions_reserve_guide(ian_handle* h, const float* table, int32_t count) {
   return h ? sessions_reserve_guide(h, table, count) : -1;
 }

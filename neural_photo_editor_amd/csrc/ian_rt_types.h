@@ -320,6 +320,7 @@ struct ian_handle {
     std::vector<int32_t> tab_shadow;   // upload source of d_tab (outlives the caller's array)
     double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int radius = -1;                   // -1: ian_sessions_set_blend has not been called
+    int pixels = 0;                    // the pixel format of every window call's out (ian_sessions_set_pixels; PIXELS_*); ian_sessions_reserve(0): planar again
     std::vector<int32_t> res_ids;
     std::vector<uint64_t> res_ver;
     bool res_valid = false;

@@ -1,14 +1,16 @@
 // Window kernels of the edit sessions: what a call displays of a full-resolution picture or of a canvas.
-//   session_render_kernel<GUIDED>       a window of a session's picture: SRC + 127.5 * FIELD sampled at full size (4.3; guided 4.11)
-//   canvas_compose_kernel<GUIDED>       a window of a whole photo: the canvas plus every placed session's feathered field (4.7; 4.13)
-//   session_render_zoom_kernel<GUIDED>, canvas_compose_zoom_kernel<GUIDED>   the same windows at 1/k, never written at 1:1 (4.14)
-//   canvas_compose_oriented_kernel, canvas_compose_oriented_zoom_kernel      a canvas whose placements have any size and tilt (4.16):
-//                                       ComposeOrientedPx4 in the same loops and sinks, the taps read from global memory, no staging
+//   session_render_kernel<GUIDED, PACKED>       a window of a session's picture: SRC + 127.5 * FIELD sampled at full size (4.3; guided 4.11)
+//   canvas_compose_kernel<GUIDED, PACKED>       a window of a whole photo: the canvas plus every placed session's feathered field (4.7; 4.13)
+//   session_render_zoom_kernel<GUIDED, PACKED>, canvas_compose_zoom_kernel<GUIDED, PACKED>   the same windows at 1/k, never written at 1:1 (4.14)
+//   canvas_compose_oriented_kernel<PACKED>, canvas_compose_oriented_zoom_kernel<PACKED>      a canvas whose placements have any size and tilt
+//                                       (4.16): ComposeOrientedPx4 in the same loops and sinks, the taps read from global memory, no staging
+// PACKED: the window is written as interleaved rgb, rgba or bgra pixels (ian_sessions_set_pixels, 4.17; npe_ops.pack_window).
 // GUIDED: the field's four taps weighted by the photo (ian_sessions_reserve_guide / _edges).  Every result byte is specified by
 // npe_ops.py (hires_render[_guided], canvas_compose[_guided], zoom_box_mean) and matched bit for bit.  Three layers, each written once:
 //   staging  the field rows a band of output rows taps (and, guided, the same rows of GIM and the range weights) -> LDS
 //   px4      the result bytes of one aligned uchar4 of the source: RenderPx4 (a session), ComposePx4 (a canvas)
-//   sink     where a lane's bytes go: a uchar4 store (StoreRows, 1:1) or integer sums in LDS (ZoomSums, 1/k)
+//   sink     where a lane's bytes go: a uchar4 store (StoreRows, 1:1) or integer sums in LDS (ZoomSums, 1/k); packed pixels (4.17):
+//            one 12- or 16-byte store of a lane's four interleaved pixels (PackedRows, zoom_store_packed)
 // A kernel is stage, loop (px_rows / px_columns), px4, sink.
 #include <cstdint>
 
@@ -84,27 +86,31 @@ __device__ __forceinline__ void stage_gim_rows(unsigned char* g, const unsigned 
   for (int j = threadIdx.x; j < r.n * 16; j += 256) gl[j] = grow[j];
 }
 
-// What one session contributes to a band, in LDS: its field rows in the NC channels a lane owns and, guided, the same rows of GIM.
-// Guided, 6 rows of 3 channels are 4.6 KB field and 1.1 KB GIM.
-template <bool GUIDED>
+// What one session contributes to a band, in LDS: its field rows in the NCH channels a lane owns and, guided, the same rows of GIM.
+// A lane owns one channel (plain, planar out: the channel planes are in the grid) or all three (guided; or packed out, DESIGN.md
+// 4.17: an interleaved pixel needs its three bytes in one lane).  Three channels take the 4-row band whatever asks for them, for the
+// guided kernels' reason: 6 rows of 3 channels are 4.6 KB field (and, guided, 1.1 KB GIM).
+template <bool GUIDED, int NCH>
 struct StagedRows;
-template <>
-struct StagedRows<false> {
-  static constexpr int NC = 1, BAND = RENDER_BAND;
+template <int NCH>
+struct StagedRows<false, NCH> {
+  static constexpr int NC = NCH, BAND = NCH == 3 ? GUIDE_BAND : RENDER_BAND;
   float f[NC][(BAND + 2) * 64];
 };
 template <>
-struct StagedRows<true> {
+struct StagedRows<true, 3> {
   static constexpr int NC = 3, BAND = GUIDE_BAND;
   float f[NC][(BAND + 2) * 64];
   alignas(4) unsigned char g[NC][(BAND + 2) * 64];
 };
+// the channels a lane owns in a kernel: one only where nothing asks for all three
+constexpr int window_nc(bool guided, bool packed) { return guided || packed ? 3 : 1; }
 // rows fr of session id, channels c0 .. c0 + NC - 1 -> r.  A band of BAND output rows taps at most BAND + 2 field rows; the cap keeps
 // whatever a caller computed inside r (a guided compose's 4 output rows tap at most 5 field rows, field_rows itself caps at 10).
-template <bool GUIDED>
-__device__ __forceinline__ void stage_rows(StagedRows<GUIDED>& r, const SessionPool& P, int id, int c0, FieldRows fr) {
-  fr.n = min(fr.n, StagedRows<GUIDED>::BAND + 2);
-  for (int c = 0; c < StagedRows<GUIDED>::NC; ++c) {
+template <bool GUIDED, int NC>
+__device__ __forceinline__ void stage_rows(StagedRows<GUIDED, NC>& r, const SessionPool& P, int id, int c0, FieldRows fr) {
+  fr.n = min(fr.n, StagedRows<GUIDED, NC>::BAND + 2);
+  for (int c = 0; c < NC; ++c) {
     const size_t plane = ((size_t)id * 3 + c0 + c) * (64 * 64);
     stage_field_rows(r.f[c], P.field + plane, fr);
     if constexpr (GUIDED) stage_gim_rows(r.g[c], P.gim + plane, fr);
@@ -119,7 +125,7 @@ __device__ __forceinline__ void stage_guide_table(float* tab, const float* __res
 // hires_guide_field's v of the three channels at square coordinate u of the output row whose two tapped rows start at o0 and o1 of the
 // staged rows (weight ty): the four bilinear taps of the field weighted by how close the photo's pixel p[0..2] is to each tap's pixel
 // of GIM; tab the range weights.  float32 in hires_render_guided's order, and the division is IEEE.
-__device__ __forceinline__ void guide_sample(const StagedRows<true>& r, const float* tab, int o0, int o1, int s, int u, float ty, const int p[3],
+__device__ __forceinline__ void guide_sample(const StagedRows<true, 3>& r, const float* tab, int o0, int o1, int s, int u, float ty, const int p[3],
                                              float v[3]) {
   int c0, c1;
   float tx;
@@ -142,14 +148,14 @@ __device__ __forceinline__ void guide_sample(const StagedRows<true>& r, const fl
 }
 // the field of a lane's NC channels at that place: the guided tap where the guide is on and a photo lies under the field (PHOTO:
 // kind 0), the bilinear tap otherwise (a kind 1 field is a sample: there is no photo to guide by)
-template <bool GUIDED, bool PHOTO>
-__device__ __forceinline__ void field_sample(const StagedRows<GUIDED>& r, const float* tab, int o0, int o1, int s, int u, float ty, const int* p,
+template <bool GUIDED, bool PHOTO, int NC>
+__device__ __forceinline__ void field_sample(const StagedRows<GUIDED, NC>& r, const float* tab, int o0, int o1, int s, int u, float ty, const int* p,
                                              float* v) {
   if constexpr (GUIDED && PHOTO) {
     guide_sample(r, tab, o0, o1, s, u, ty, p, v);
   } else {
 #pragma unroll
-    for (int c = 0; c < StagedRows<GUIDED>::NC; ++c) v[c] = field_bilinear(r.f[c] + o0, r.f[c] + o1, s, u, ty);
+    for (int c = 0; c < NC; ++c) v[c] = field_bilinear(r.f[c] + o0, r.f[c] + o1, s, u, ty);
   }
 }
 __device__ __forceinline__ void unpack4(const uchar4 v, int b[4]) {
@@ -158,10 +164,10 @@ __device__ __forceinline__ void unpack4(const uchar4 v, int b[4]) {
 
 // The result bytes of the aligned uchar4 at (X, Y) of a session's picture, in the lane's NC channels: hires_render[_guided].  rows
 // holds the field rows from fr0 on; src is channel c0's plane of the session's SRC.  All arithmetic is float32 in hires_render's order.
-template <bool GUIDED>
+template <bool GUIDED, int NCH>
 struct RenderPx4 {
-  static constexpr int NC = StagedRows<GUIDED>::NC;
-  const StagedRows<GUIDED>& rows;
+  static constexpr int NC = NCH;
+  const StagedRows<GUIDED, NC>& rows;
   const float* tab;
   const unsigned char* src;
   size_t plane;
@@ -197,7 +203,7 @@ struct RenderPx4 {
     float v[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) p[c] = pb[c][e];
-    field_sample<GUIDED, KIND == 0>(rows, tab, o0, o1, s, X + e, ty, p, v);
+    field_sample<GUIDED, KIND == 0, NC>(rows, tab, o0, o1, s, X + e, ty, p, v);
 #pragma unroll
     for (int c = 0; c < NC; ++c) ob[c][e] = round_u8(kd == 0 ? (float)p[c] + 127.5f * v[c] : 127.5f * (v[c] + 1.0f));
   }
@@ -217,10 +223,10 @@ struct CanvasKept {
   int id, ox, oy, s, kind;
 };
 // What a band of a canvas needs, in LDS: the placements whose squares meet it, which field rows each taps, and those rows
-// (StagedRows per kept placement: 20 KB plain, 45 KB guided).
-template <bool GUIDED>
+// (StagedRows per kept placement: 20 KB plain, 45 KB guided, 36 KB plain with three channels a lane).
+template <bool GUIDED, int NC>
 struct CanvasStage {
-  StagedRows<GUIDED> rows[CANVAS_MAX_PLACED];
+  StagedRows<GUIDED, NC> rows[CANVAS_MAX_PLACED];
   CanvasKept kept[CANVAS_MAX_PLACED];
   FieldRows frows[CANVAS_MAX_PLACED];   // the staged field rows of each kept placement
   int nkept;
@@ -229,10 +235,10 @@ struct CanvasStage {
 // the kept placements in the table's order, so it lives in registers.  A square starts at any ox while a lane's 4 pixels are aligned
 // to the window, so the inside-the-square test is per pixel.  Guided, the sample of a kind 0 placement is guide_sample's, the photo's
 // pixel being the STORED canvas byte.  All arithmetic is float32 in canvas_compose's order.  src is channel c0's plane of the canvas.
-template <bool GUIDED>
+template <bool GUIDED, int NCH>
 struct ComposePx4 {
-  static constexpr int NC = StagedRows<GUIDED>::NC;
-  const CanvasStage<GUIDED>& st;
+  static constexpr int NC = NCH;
+  const CanvasStage<GUIDED, NC>& st;
   const float* tab;
   const unsigned char* src;
   size_t plane;
@@ -276,13 +282,13 @@ struct ComposePx4 {
   }
   // one placement's field at column ux of its square (weight w) onto pixel e of acc: a photo's edit is added, a sample is blended in
   template <bool PHOTO>
-  __device__ __forceinline__ void place1(const StagedRows<GUIDED>& r, int o0, int o1, float ty, int s, int ux, float w, int e,
+  __device__ __forceinline__ void place1(const StagedRows<GUIDED, NC>& r, int o0, int o1, float ty, int s, int ux, float w, int e,
                                          const int pb[NC][4], float acc[NC][4]) const {
     int p[NC];
     float v[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) p[c] = pb[c][e];
-    field_sample<GUIDED, PHOTO>(r, tab, o0, o1, s, ux, ty, p, v);
+    field_sample<GUIDED, PHOTO, NC>(r, tab, o0, o1, s, ux, ty, p, v);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       if (PHOTO) {
@@ -319,8 +325,8 @@ __device__ __forceinline__ FieldRows canvas_chunk_rows(const CanvasKept& q, int 
 // Lane 0 reads the canvas's placement table once per workgroup (a walk in global memory by one lane; the test is uniform over the
 // workgroup) and keeps the placements that meet rows Y0..Y1, columns X0 .. X0 + W - 1; guided, the range weights follow if anything
 // is kept -> how many.  Rows that meet no square are a plain copy.
-template <bool GUIDED>
-__device__ __forceinline__ int canvas_keep(CanvasStage<GUIDED>& st, float* tab, const SessionCanvases& C, const SessionPool& P,
+template <bool GUIDED, int NC>
+__device__ __forceinline__ int canvas_keep(CanvasStage<GUIDED, NC>& st, float* tab, const SessionCanvases& C, const SessionPool& P,
                                            const float* __restrict__ table, int cv, int X0, int W, int Y0, int Y1) {
   if (threadIdx.x == 0) st.nkept = canvas_keep_band(C, P, cv, X0, W, Y0, Y1, st.kept, st.frows);
   __syncthreads();
@@ -331,8 +337,8 @@ __device__ __forceinline__ int canvas_keep(CanvasStage<GUIDED>& st, float* tab, 
 }
 // Each kept placement's rows for rows Y0..Y1 -> LDS; the caller's barrier publishes them.  chunk: Y0..Y1 are a part of the rows the
 // placements were kept for, and lane p first says which field rows THIS part taps inside kept placement p (none: n = 0).
-template <bool GUIDED>
-__device__ __forceinline__ void canvas_stage(CanvasStage<GUIDED>& st, const SessionPool& P, int nk, int c0, bool chunk, int Y0, int Y1) {
+template <bool GUIDED, int NC>
+__device__ __forceinline__ void canvas_stage(CanvasStage<GUIDED, NC>& st, const SessionPool& P, int nk, int c0, bool chunk, int Y0, int Y1) {
   if (chunk) {
     if (threadIdx.x < nk) st.frows[threadIdx.x] = canvas_chunk_rows(st.kept[threadIdx.x], Y0, Y1);
     __syncthreads();
@@ -370,21 +376,28 @@ __device__ __forceinline__ float oriented_ramp1(int Q, int f16) {
 }
 // The result bytes of the aligned uchar4 at (X, Y) of a canvas in channel c0: ComposePx4's walk of the kept placements with the
 // oriented geometry.  A lane's four pixels advance (Uq, Vq) by (2bx, -2by) from one 64-bit base per row and placement.
+template <int NCH>
 struct ComposeOrientedPx4 {
-  static constexpr int NC = 1;
+  static constexpr int NC = NCH;
   const OrientedStage& st;
   const float* field;   // channel c0's plane of session 0: a session's is 3 * 4096 floats on
   const unsigned char* src;
+  size_t plane;
   int stride, feather, nk;
   __device__ __forceinline__ void load(int X, int Y, uchar4 pv[NC]) const {
-    pv[0] = *reinterpret_cast<const uchar4*>(src + (size_t)Y * stride + X);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) pv[c] = *reinterpret_cast<const uchar4*>(src + c * plane + (size_t)Y * stride + X);
   }
+  // the geometry (taps, weights, feather) is the pixel's, computed once; the channels differ in the field plane and the accumulator
   __device__ __forceinline__ void operator()(int X, int Y, const uchar4 pv[NC], unsigned char ob[NC][4]) const {
     int pb[4];
-    float acc[4];
-    unpack4(pv[0], pb);
+    float acc[NC][4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = (float)pb[e];
+    for (int c = 0; c < NC; ++c) {
+      unpack4(pv[c], pb);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[c][e] = (float)pb[e];
+    }
     const int f16 = feather << 16;
     for (int k = 0; k < nk; ++k) {
       const OrientedKept q = st.kept[k];
@@ -400,23 +413,32 @@ struct ComposeOrientedPx4 {
         float tx, ty;
         oriented_taps(U, c0, c1, tx);
         oriented_taps(V, r0, r1, ty);
-        const float* top = F + r0 * 64;
-        const float* bot = F + r1 * 64;
-        const float a0 = top[c0], a1 = bot[c0];
-        const float t = a0 + tx * (top[c1] - a0);
-        const float b = a1 + tx * (bot[c1] - a1);
-        const float v = t + ty * (b - t);
+        float v[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const float* top = F + c * (64 * 64) + r0 * 64;
+          const float* bot = F + c * (64 * 64) + r1 * 64;
+          const float a0 = top[c0], a1 = bot[c0];
+          const float t = a0 + tx * (top[c1] - a0);
+          const float b = a1 + tx * (bot[c1] - a1);
+          v[c] = t + ty * (b - t);
+        }
         const float w = oriented_ramp1(V, f16) * oriented_ramp1(U, f16);
-        if (q.kind == 0) {   // uniform over the workgroup
-          acc[e] = acc[e] + (127.5f * v) * w;
-        } else {
-          const float tv = 127.5f * (v + 1.0f);
-          acc[e] = w == 1.0f ? tv : acc[e] + (tv - acc[e]) * w;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          if (q.kind == 0) {   // uniform over the workgroup
+            acc[c][e] = acc[c][e] + (127.5f * v[c]) * w;
+          } else {
+            const float tv = 127.5f * (v[c] + 1.0f);
+            acc[c][e] = w == 1.0f ? tv : acc[c][e] + (tv - acc[c][e]) * w;
+          }
         }
       }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ob[0][e] = round_u8(acc[e]);
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ob[c][e] = round_u8(acc[c][e]);
   }
 };
 // Lane 0 walks canvas cv's oriented table (int[8][8]: session, cx2, cy2, ax, ay, bx, by, m; session -1 ends the list) once per
@@ -449,12 +471,43 @@ struct StoreRows {
   unsigned char* base;
   size_t plane;
   int stride, row0, col0;
-  __device__ __forceinline__ void put(int c, int ry, int cx, const unsigned char ob[4]) const {
-    *reinterpret_cast<uchar4*>(base + c * plane + (size_t)(row0 + ry) * stride + col0 + cx) = make_uchar4(ob[0], ob[1], ob[2], ob[3]);
+  template <int NC>
+  __device__ __forceinline__ void put(int ry, int cx, const unsigned char (&ob)[NC][4]) const {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      *reinterpret_cast<uchar4*>(base + c * plane + (size_t)(row0 + ry) * stride + col0 + cx) = make_uchar4(ob[c][0], ob[c][1], ob[c][2], ob[c][3]);
   }
 };
-// A lane owns 4 consecutive bytes of a row of the source window rows x 4L at (X0, Y0), in Px::NC channels: NC uchar4 loads, px4, NC
-// puts.  Consecutive lanes, consecutive uchar4.
+// Packed pixels (npe_ops.pack_window): a lane's four pixels in all three channels, interleaved, as ONE store of 12
+// (rgb) or 16 bytes (rgba, bgra; A = 255) at `at`, which is 4-byte aligned: `out` is, and x, vw and the lane's column are multiples
+// of 4 pixels.  Consecutive lanes store consecutive addresses.  The format is uniform over the grid: the byte order is a select.
+typedef unsigned Packed12 __attribute__((ext_vector_type(3), aligned(4)));   // vectors at the alignment `out` promises: dwordx3 / dwordx4
+typedef unsigned Packed16 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ void store_packed4(unsigned char* at, int format, const unsigned char (&ob)[3][4]) {
+  if (format == PIXELS_RGB) {
+    Packed12 v;
+    v[0] = ob[0][0] | ob[1][0] << 8 | ob[2][0] << 16 | (unsigned)ob[0][1] << 24;
+    v[1] = ob[1][1] | ob[2][1] << 8 | ob[0][2] << 16 | (unsigned)ob[1][2] << 24;
+    v[2] = ob[2][2] | ob[0][3] << 8 | ob[1][3] << 16 | (unsigned)ob[2][3] << 24;
+    *reinterpret_cast<Packed12*>(at) = v;
+  } else {
+    const bool bgr = format == PIXELS_BGRA;
+    Packed16 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (bgr ? ob[2][e] : ob[0][e]) | ob[1][e] << 8 | (bgr ? ob[0][e] : ob[2][e]) << 16 | 0xff000000u;
+    *reinterpret_cast<Packed16*>(at) = v;
+  }
+}
+// 1:1, packed: the pixels of item (ry, cx) of a band go to row row0 + ry, pixel cx of a window (u8 [vh][vw][bpp]) of `out`
+struct PackedRows {
+  unsigned char* base;
+  int vw, row0, format;
+  __device__ __forceinline__ void put(int ry, int cx, const unsigned char (&ob)[3][4]) const {
+    store_packed4(base + ((size_t)(row0 + ry) * vw + cx) * pixels_bpp(format), format, ob);
+  }
+};
+// A lane owns 4 consecutive bytes of a row of the source window rows x 4L at (X0, Y0), in Px::NC channels: NC uchar4 loads, px4, one
+// put.  Consecutive lanes, consecutive uchar4.
 template <typename Px, typename Sink>
 __device__ __forceinline__ void px_rows(const Px& px, int X0, int Y0, int rows, int L, const Sink& to) {
   for (int idx = threadIdx.x; idx < rows * L; idx += 256) {
@@ -463,8 +516,7 @@ __device__ __forceinline__ void px_rows(const Px& px, int X0, int Y0, int rows, 
     unsigned char ob[Px::NC][4];
     px.load(X0 + cx, Y0 + ry, pv);
     px(X0 + cx, Y0 + ry, pv, ob);
-#pragma unroll
-    for (int c = 0; c < Px::NC; ++c) to.put(c, ry, cx, ob[c]);
+    to.put(ry, cx, ob);
   }
 }
 
@@ -487,11 +539,12 @@ __device__ __forceinline__ void px_rows(const Px& px, int X0, int Y0, int rows, 
 // divide and store one uchar4 each (zoom_store).
 //   Sizes.  Plain: band 8, tile 1024 columns (one lane pass per source row at the widest), sums orows * ow <= 8 * 1024 / 4 ints,
 // 8 KB.  Guided (no channel planes in the grid, three channels per lane): band 4, tile 256 columns, so a chunk is one pass of the 256
-// lanes (px_rows) and ONE 1024 x 1024 picture at k = 16 is 64 x 4 = 256 workgroups; sums 3 * 4 * 256 / 4 ints, 3 KB.
+// lanes (px_rows) and ONE 1024 x 1024 picture at k = 16 is 64 x 4 = 256 workgroups; sums 3 * 4 * 256 / 4 ints, 3 KB.  The shape
+// goes with the channels a lane owns, not with the guide: the packed plain kernels take the guided one.
 constexpr int ZOOM_MAX = 16;
-template <bool GUIDED>
+template <int NC>
 struct ZoomShape {
-  static constexpr int BAND = StagedRows<GUIDED>::BAND, TILE = GUIDED ? 256 : 1024, SUMS = BAND * TILE / 4;   // sums per channel; k >= 2
+  static constexpr int BAND = NC == 3 ? GUIDE_BAND : RENDER_BAND, TILE = NC == 3 ? 256 : 1024, SUMS = BAND * TILE / 4;   // sums per channel; k >= 2
 };
 struct ZoomSplit {
   int orows, ow_tile, ntiles;
@@ -531,9 +584,10 @@ __device__ __forceinline__ void zoom_add4(int* row, int cx, int k, const T ob[4]
 struct ZoomSums {
   int* sum;
   int per, ow, k, row0;
-  template <typename T>
-  __device__ __forceinline__ void put(int c, int ry, int cx, const T ob[4]) const {
-    zoom_add4(sum + c * per + ((row0 + ry) / k) * ow, cx, k, ob);
+  template <typename T, int NC>
+  __device__ __forceinline__ void put(int ry, int cx, const T (&ob)[NC][4]) const {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) zoom_add4(sum + c * per + ((row0 + ry) / k) * ow, cx, k, ob[c]);
   }
 };
 // The output rows a chunk of `rows` source rows meets, for the kernels whose lanes sum a column of source rows in registers first
@@ -554,7 +608,7 @@ __device__ __forceinline__ void px_columns(const Px& px, int X0, int Y0, const Z
   for (int idx = threadIdx.x; idx < ch.nor * L; idx += 256) {
     const int oy = idx / L, cx = (idx - oy * L) * 4;
     const int X = X0 + cx, Yb = Y0 + oy * ch.each;
-    int col[4] = {0, 0, 0, 0};
+    int col[1][4] = {{0, 0, 0, 0}};
     uchar4 pvs[RENDER_BAND][1];
 #pragma unroll
     for (int r = 0; r < RENDER_BAND; ++r) {
@@ -567,18 +621,18 @@ __device__ __forceinline__ void px_columns(const Px& px, int X0, int Y0, const Z
       unsigned char ob[1][4];
       px(X, Yb + r, pvs[r], ob);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) col[e] += ob[0][e];
+      for (int e = 0; e < 4; ++e) col[0][e] += ob[0][e];
     }
-    to.put(0, oy * ch.each, cx, col);
+    to.put(oy * ch.each, cx, col);
   }
 }
 // one chunk of a tile -> the sums: `rows` source rows of 4L bytes at (X0, Y0), source row row0 of the tile
-template <bool GUIDED, typename Px>
-__device__ __forceinline__ void zoom_chunk_sum(const Px& px, int (*sum)[ZoomShape<GUIDED>::SUMS], const ZoomTileAt& z, int k, int X0, int Y0,
+template <typename Px>
+__device__ __forceinline__ void zoom_chunk_sum(const Px& px, int (*sum)[ZoomShape<Px::NC>::SUMS], const ZoomTileAt& z, int k, int X0, int Y0,
                                                int row0, int rows, int L) {
-  const ZoomSums to{&sum[0][0], ZoomShape<GUIDED>::SUMS, z.ow, k, row0};
-  if constexpr (GUIDED) px_rows(px, X0, Y0, rows, L, to);
-  else px_columns(px, X0, Y0, zoom_chunk(ZoomShape<GUIDED>::BAND, k, z.orows, rows), L, to);
+  const ZoomSums to{&sum[0][0], ZoomShape<Px::NC>::SUMS, z.ow, k, row0};
+  if constexpr (Px::NC == 3) px_rows(px, X0, Y0, rows, L, to);
+  else px_columns(px, X0, Y0, zoom_chunk(ZoomShape<Px::NC>::BAND, k, z.orows, rows), L, to);
 }
 template <int NC, int SUMS>
 __device__ __forceinline__ void zoom_clear(int (*sum)[SUMS], const ZoomTileAt& z) {
@@ -598,19 +652,41 @@ __device__ __forceinline__ void zoom_store(const int (*sum)[SUMS], const ZoomTil
                       (unsigned char)((p[3] + half) / d));
     }
 }
+// the same, packed: the three sums of each of a lane's four pixels divided, then store_packed4 into the window (u8 [vh][vw][bpp])
+template <int SUMS>
+__device__ __forceinline__ void zoom_store_packed(const int (*sum)[SUMS], const ZoomTileAt& z, int k, unsigned char* window, int vw, int format) {
+  const int L = z.ow >> 2, d = k * k, half = d / 2;
+  for (int j = threadIdx.x; j < z.orows * L; j += 256) {
+    const int ry = j / L, q = (j - ry * L) * 4;
+    unsigned char ob[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ob[c][e] = (unsigned char)((sum[c][ry * z.ow + q + e] + half) / d);
+    store_packed4(window + ((size_t)(z.oy0 + ry) * vw + z.ox0 + q) * pixels_bpp(format), format, ob);
+  }
+}
+// where window i of a call starts in `out`, and the sink of its band that starts at row y0: planar, channel c0's plane (StoreRows
+// over `out`, or over the source itself for out == nullptr); packed, the window's pixels
+__device__ __forceinline__ unsigned char* packed_window(unsigned char* out, int i, int vw, int vh, int format) {
+  return out + (size_t)i * vh * vw * pixels_bpp(format);
+}
 
 // ---- the kernels ---------------------------------------------------------------------------------------------------------------------
 // Plain: grid (bands or tiles, 3, n), a lane owns 4 consecutive bytes of channel blockIdx.y.  Guided: grid (bands or tiles, 1, n), a
 // lane owns its 4 pixels in all three channels.  A call may mix kinds; the kind is uniform over the workgroup.
+// PACKED: `out` holds interleaved pixels of `format` (PIXELS_*), u8 [n][vh][vw][bpp].  A lane owns all three channels
+// with or without a guide, so the grid is the guided one (y = 1) and so are band and tile; out is never nullptr.  Not PACKED, `format`
+// is not read: these instantiations are the planar kernels as they always were.
 
 // render.  grid x: bands of BAND output rows.  The band's field rows go to LDS once; every tap reads from there.
-template <bool GUIDED>
+template <bool GUIDED, bool PACKED>
 __global__ __launch_bounds__(256) void session_render_kernel(SessionPool P, const float* __restrict__ table, const int* __restrict__ views,
-                                                             int vw, int vh, unsigned char* out) {
-  constexpr int BAND = StagedRows<GUIDED>::BAND;
-  __shared__ StagedRows<GUIDED> rows;
+                                                             int vw, int vh, unsigned char* out, int format) {
+  constexpr int NC = window_nc(GUIDED, PACKED), BAND = StagedRows<GUIDED, NC>::BAND;
+  __shared__ StagedRows<GUIDED, NC> rows;
   __shared__ float tab[GUIDED ? SESSION_GUIDE_TABLE_LEN : 1];
-  const int s = P.scale, S = 64 * s, c0 = GUIDED ? 0 : blockIdx.y, i = blockIdx.z;
+  const int s = P.scale, S = 64 * s, c0 = NC == 3 ? 0 : blockIdx.y, i = blockIdx.z;
   const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
   const int y0 = blockIdx.x * BAND, nrows = min(BAND, vh - y0);
   const FieldRows fr = field_rows(vy + y0, vy + y0 + nrows - 1, s);
@@ -619,19 +695,23 @@ __global__ __launch_bounds__(256) void session_render_kernel(SessionPool P, cons
   __syncthreads();
   const size_t plane = (size_t)S * S;
   unsigned char* src = P.src + ((size_t)id * 3 + c0) * plane;
-  const RenderPx4<GUIDED> px{rows, tab, src, plane, S, s, P.kind[id], fr.fr0};
-  const StoreRows to = out ? StoreRows{out + ((size_t)i * 3 + c0) * vh * vw, (size_t)vh * vw, vw, y0, 0} : StoreRows{src, plane, S, vy + y0, vx};
-  px_rows(px, vx, vy + y0, nrows, vw >> 2, to);
+  const RenderPx4<GUIDED, NC> px{rows, tab, src, plane, S, s, P.kind[id], fr.fr0};
+  if constexpr (PACKED) {
+    px_rows(px, vx, vy + y0, nrows, vw >> 2, PackedRows{packed_window(out, i, vw, vh, format), vw, y0, format});
+  } else {
+    const StoreRows to = out ? StoreRows{out + ((size_t)i * 3 + c0) * vh * vw, (size_t)vh * vw, vw, y0, 0} : StoreRows{src, plane, S, vy + y0, vx};
+    px_rows(px, vx, vy + y0, nrows, vw >> 2, to);
+  }
 }
 
 // compose.  grid x: bands of BAND output rows
-template <bool GUIDED>
+template <bool GUIDED, bool PACKED>
 __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, SessionPool P, const float* __restrict__ table,
-                                                             const int* __restrict__ windows, int vw, int vh, unsigned char* out) {
-  constexpr int BAND = StagedRows<GUIDED>::BAND;
-  __shared__ CanvasStage<GUIDED> st;
+                                                             const int* __restrict__ windows, int vw, int vh, unsigned char* out, int format) {
+  constexpr int NC = window_nc(GUIDED, PACKED), BAND = StagedRows<GUIDED, NC>::BAND;
+  __shared__ CanvasStage<GUIDED, NC> st;
   __shared__ float tab[GUIDED ? SESSION_GUIDE_TABLE_LEN : 1];
-  const int c0 = GUIDED ? 0 : blockIdx.y, i = blockIdx.z;
+  const int c0 = NC == 3 ? 0 : blockIdx.y, i = blockIdx.z;
   const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
   const int y0 = blockIdx.x * BAND, nrows = min(BAND, vh - y0);
   const int Y0 = vy + y0, Y1 = Y0 + nrows - 1;   // the band's rows on the canvas, both inclusive
@@ -640,22 +720,26 @@ __global__ __launch_bounds__(256) void canvas_compose_kernel(SessionCanvases C, 
   __syncthreads();
   const size_t plane = (size_t)C.max_h * C.max_w;
   unsigned char* src = C.pix + ((size_t)cv * 3 + c0) * plane;
-  const ComposePx4<GUIDED> px{st, tab, src, plane, C.max_w, C.feather, nk};
-  const StoreRows to = out ? StoreRows{out + ((size_t)i * 3 + c0) * vh * vw, (size_t)vh * vw, vw, y0, 0} : StoreRows{src, plane, C.max_w, Y0, vx};
-  px_rows(px, vx, Y0, nrows, vw >> 2, to);
+  const ComposePx4<GUIDED, NC> px{st, tab, src, plane, C.max_w, C.feather, nk};
+  if constexpr (PACKED) {
+    px_rows(px, vx, Y0, nrows, vw >> 2, PackedRows{packed_window(out, i, vw, vh, format), vw, y0, format});
+  } else {
+    const StoreRows to = out ? StoreRows{out + ((size_t)i * 3 + c0) * vh * vw, (size_t)vh * vw, vw, y0, 0} : StoreRows{src, plane, C.max_w, Y0, vx};
+    px_rows(px, vx, Y0, nrows, vw >> 2, to);
+  }
 }
 
 // render at 1/k.  grid x: row groups * column tiles
-template <bool GUIDED>
+template <bool GUIDED, bool PACKED>
 __global__ __launch_bounds__(256) void session_render_zoom_kernel(SessionPool P, const float* __restrict__ table,
                                                                   const int* __restrict__ views, int vw, int vh, int k,
-                                                                  unsigned char* __restrict__ out) {
-  using Z = ZoomShape<GUIDED>;
-  constexpr int NC = StagedRows<GUIDED>::NC;
-  __shared__ StagedRows<GUIDED> rows;
+                                                                  unsigned char* __restrict__ out, int format) {
+  constexpr int NC = window_nc(GUIDED, PACKED);
+  using Z = ZoomShape<NC>;
+  __shared__ StagedRows<GUIDED, NC> rows;
   __shared__ float tab[GUIDED ? SESSION_GUIDE_TABLE_LEN : 1];
   __shared__ int sum[NC][Z::SUMS];
-  const int s = P.scale, S = 64 * s, c0 = GUIDED ? 0 : blockIdx.y, i = blockIdx.z;
+  const int s = P.scale, S = 64 * s, c0 = NC == 3 ? 0 : blockIdx.y, i = blockIdx.z;
   const int id = views[3 * i], vx = views[3 * i + 1], vy = views[3 * i + 2];
   const ZoomTileAt z = zoom_tile_at(Z::BAND, Z::TILE, k, vw, vh);
   const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile in the picture
@@ -668,129 +752,152 @@ __global__ __launch_bounds__(256) void session_render_zoom_kernel(SessionPool P,
     const FieldRows fr = field_rows(Y0 + y0, Y0 + y0 + nrows - 1, s);
     stage_rows(rows, P, id, c0, fr);
     __syncthreads();   // the first one also publishes the zeroed sums
-    const RenderPx4<GUIDED> px{rows, tab, P.src + ((size_t)id * 3 + c0) * plane, plane, S, s, kind, fr.fr0};
-    zoom_chunk_sum<GUIDED>(px, sum, z, k, X0, Y0 + y0, y0, nrows, L);
+    const RenderPx4<GUIDED, NC> px{rows, tab, P.src + ((size_t)id * 3 + c0) * plane, plane, S, s, kind, fr.fr0};
+    zoom_chunk_sum(px, sum, z, k, X0, Y0 + y0, y0, nrows, L);
     __syncthreads();   // rows is restaged; after the last chunk: the sums are complete
   }
-  zoom_store<NC>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
+  if constexpr (PACKED) zoom_store_packed(sum, z, k, packed_window(out, i, vw, vh, format), vw, format);
+  else zoom_store<NC>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
 }
 
 // compose at 1/k.  grid x: row groups * column tiles
-template <bool GUIDED>
+template <bool GUIDED, bool PACKED>
 __global__ __launch_bounds__(256) void canvas_compose_zoom_kernel(SessionCanvases C, SessionPool P, const float* __restrict__ table,
                                                                   const int* __restrict__ windows, int vw, int vh, int k,
-                                                                  unsigned char* __restrict__ out) {
-  using Z = ZoomShape<GUIDED>;
-  constexpr int NC = StagedRows<GUIDED>::NC;
-  __shared__ CanvasStage<GUIDED> st;
+                                                                  unsigned char* __restrict__ out, int format) {
+  constexpr int NC = window_nc(GUIDED, PACKED);
+  using Z = ZoomShape<NC>;
+  __shared__ CanvasStage<GUIDED, NC> st;
   __shared__ float tab[GUIDED ? SESSION_GUIDE_TABLE_LEN : 1];
   __shared__ int sum[NC][Z::SUMS];
-  const int c0 = GUIDED ? 0 : blockIdx.y, i = blockIdx.z;
+  const int c0 = NC == 3 ? 0 : blockIdx.y, i = blockIdx.z;
   const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
   const ZoomTileAt z = zoom_tile_at(Z::BAND, Z::TILE, k, vw, vh);
   const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile on the canvas
   zoom_clear<NC>(sum, z);
   const int nk = canvas_keep(st, tab, C, P, table, cv, X0, k * z.ow, Y0, Y0 + R - 1);   // once: the tile's rows
   const size_t plane = (size_t)C.max_h * C.max_w;
-  const ComposePx4<GUIDED> px{st, tab, C.pix + ((size_t)cv * 3 + c0) * plane, plane, C.max_w, C.feather, nk};
+  const ComposePx4<GUIDED, NC> px{st, tab, C.pix + ((size_t)cv * 3 + c0) * plane, plane, C.max_w, C.feather, nk};
   for (int y0 = 0; y0 < R; y0 += Z::BAND) {
     const int nrows = min(Z::BAND, R - y0);
     canvas_stage(st, P, nk, c0, R > Z::BAND, Y0 + y0, Y0 + y0 + nrows - 1);
     __syncthreads();   // the first one also publishes the zeroed sums
-    zoom_chunk_sum<GUIDED>(px, sum, z, k, X0, Y0 + y0, y0, nrows, L);
+    zoom_chunk_sum(px, sum, z, k, X0, Y0 + y0, y0, nrows, L);
     __syncthreads();   // frows and rows are rewritten; after the last chunk: the sums are complete
   }
-  zoom_store<NC>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
+  if constexpr (PACKED) zoom_store_packed(sum, z, k, packed_window(out, i, vw, vh, format), vw, format);
+  else zoom_store<NC>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
 }
 
 // compose over oriented placements: the plain kernels' grid and loops, nothing staged but the kept placements
+template <bool PACKED>
 __global__ __launch_bounds__(256) void canvas_compose_oriented_kernel(SessionCanvases C, const int* __restrict__ otable, SessionPool P,
-                                                                      const int* __restrict__ windows, int vw, int vh, unsigned char* out) {
+                                                                      const int* __restrict__ windows, int vw, int vh, unsigned char* out,
+                                                                      int format) {
+  constexpr int NC = window_nc(false, PACKED), BAND = ZoomShape<NC>::BAND;
   __shared__ OrientedStage st;
-  const int c0 = blockIdx.y, i = blockIdx.z;
+  const int c0 = NC == 3 ? 0 : blockIdx.y, i = blockIdx.z;
   const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
-  const int y0 = blockIdx.x * RENDER_BAND, nrows = min(RENDER_BAND, vh - y0);
+  const int y0 = blockIdx.x * BAND, nrows = min(BAND, vh - y0);
   const int Y0 = vy + y0;
   const int nk = oriented_keep(st, otable, P, cv, vx, vw, Y0, Y0 + nrows - 1);
   const size_t plane = (size_t)C.max_h * C.max_w;
   unsigned char* src = C.pix + ((size_t)cv * 3 + c0) * plane;
-  const ComposeOrientedPx4 px{st, P.field + c0 * (64 * 64), src, C.max_w, C.feather, nk};
-  const StoreRows to = out ? StoreRows{out + ((size_t)i * 3 + c0) * vh * vw, (size_t)vh * vw, vw, y0, 0} : StoreRows{src, plane, C.max_w, Y0, vx};
-  px_rows(px, vx, Y0, nrows, vw >> 2, to);
+  const ComposeOrientedPx4<NC> px{st, P.field + c0 * (64 * 64), src, plane, C.max_w, C.feather, nk};
+  if constexpr (PACKED) {
+    px_rows(px, vx, Y0, nrows, vw >> 2, PackedRows{packed_window(out, i, vw, vh, format), vw, y0, format});
+  } else {
+    const StoreRows to = out ? StoreRows{out + ((size_t)i * 3 + c0) * vh * vw, (size_t)vh * vw, vw, y0, 0} : StoreRows{src, plane, C.max_w, Y0, vx};
+    px_rows(px, vx, Y0, nrows, vw >> 2, to);
+  }
 }
 // the same at 1/k: canvas_compose_zoom_kernel<false>'s tiles and chunks; the sums are LDS adds, so the chunks need no barrier between them
+template <bool PACKED>
 __global__ __launch_bounds__(256) void canvas_compose_oriented_zoom_kernel(SessionCanvases C, const int* __restrict__ otable, SessionPool P,
                                                                            const int* __restrict__ windows, int vw, int vh, int k,
-                                                                           unsigned char* __restrict__ out) {
-  using Z = ZoomShape<false>;
+                                                                           unsigned char* __restrict__ out, int format) {
+  constexpr int NC = window_nc(false, PACKED);
+  using Z = ZoomShape<NC>;
   __shared__ OrientedStage st;
-  __shared__ int sum[1][Z::SUMS];
-  const int c0 = blockIdx.y, i = blockIdx.z;
+  __shared__ int sum[NC][Z::SUMS];
+  const int c0 = NC == 3 ? 0 : blockIdx.y, i = blockIdx.z;
   const int cv = windows[3 * i], vx = windows[3 * i + 1], vy = windows[3 * i + 2];
   const ZoomTileAt z = zoom_tile_at(Z::BAND, Z::TILE, k, vw, vh);
   const int X0 = vx + k * z.ox0, Y0 = vy + k * z.oy0, R = k * z.orows, L = (k * z.ow) >> 2;   // the tile on the canvas
-  zoom_clear<1>(sum, z);
+  zoom_clear<NC>(sum, z);
   const int nk = oriented_keep(st, otable, P, cv, X0, k * z.ow, Y0, Y0 + R - 1);   // its barrier also publishes the zeroed sums
   const size_t plane = (size_t)C.max_h * C.max_w;
-  const ComposeOrientedPx4 px{st, P.field + c0 * (64 * 64), C.pix + ((size_t)cv * 3 + c0) * plane, C.max_w, C.feather, nk};
-  for (int y0 = 0; y0 < R; y0 += Z::BAND) zoom_chunk_sum<false>(px, sum, z, k, X0, Y0 + y0, y0, min(Z::BAND, R - y0), L);
+  const ComposeOrientedPx4<NC> px{st, P.field + c0 * (64 * 64), C.pix + ((size_t)cv * 3 + c0) * plane, plane, C.max_w, C.feather, nk};
+  for (int y0 = 0; y0 < R; y0 += Z::BAND) zoom_chunk_sum(px, sum, z, k, X0, Y0 + y0, y0, min(Z::BAND, R - y0), L);
   __syncthreads();   // the sums are complete
-  zoom_store<1>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
+  if constexpr (PACKED) zoom_store_packed(sum, z, k, packed_window(out, i, vw, vh, format), vw, format);
+  else zoom_store<NC>(sum, z, k, out + ((size_t)i * 3 + c0) * vh * vw, vw, vh);
 }
 
 // ---- the launchers ---------------------------------------------------------------------------------------------------------------
-// what both check alike: the count, the zoom, the window against its source, the table of windows, and at 1/k the result
-static bool window_args_ok(int n, int zoom, int vw, int vh, int src_w, int src_h, const void* win, const unsigned char* out) {
+// what all check alike: the count, the zoom, the window against its source, the table of windows, at 1/k the result, and the pixel
+// format (0 planar, PIXELS_*), which needs an `out`: in place is planar
+static bool window_args_ok(int n, int zoom, int vw, int vh, int src_w, int src_h, const void* win, const unsigned char* out, int format) {
   return n >= 1 && n <= 65535 && zoom >= 1 && zoom <= ZOOM_MAX && win && vw >= 4 && (vw & 3) == 0 && vh >= 1 && vw <= src_w / zoom &&
-         vh <= src_h / zoom && (zoom == 1 || (out && (reinterpret_cast<uintptr_t>(out) & 3) == 0));
+         vh <= src_h / zoom && (zoom == 1 || (out && (reinterpret_cast<uintptr_t>(out) & 3) == 0)) && format >= 0 && format <= PIXELS_BGRA &&
+         (format == 0 || (out && (reinterpret_cast<uintptr_t>(out) & 3) == 0));
 }
-static dim3 window_grid(bool guided, int zoom, int vw, int vh, int n) {
-  const int band = guided ? GUIDE_BAND : RENDER_BAND, planes = guided ? 1 : 3;
+// wide: a lane owns all three channels (guided, or packed pixels)
+static dim3 window_grid(bool wide, int zoom, int vw, int vh, int n) {
+  const int band = wide ? GUIDE_BAND : RENDER_BAND, planes = wide ? 1 : 3;
   if (zoom == 1) return dim3((vh + band - 1) / band, planes, n);
-  const ZoomSplit z = zoom_split(band, guided ? ZoomShape<true>::TILE : ZoomShape<false>::TILE, zoom, vw);
+  const ZoomSplit z = zoom_split(band, wide ? ZoomShape<3>::TILE : ZoomShape<1>::TILE, zoom, vw);
   return dim3((unsigned)((vh + z.orows - 1) / z.orows) * z.ntiles, planes, n);
 }
 hipError_t launch_session_render(const SessionPool& P, const float* table, const int* views, int vw, int vh, int zoom, unsigned char* out, int n,
-                                 hipStream_t s) {
+                                 int format, hipStream_t s) {
   const int S = 64 * P.scale;
-  if (P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || (table && !P.gim) || !window_args_ok(n, zoom, vw, vh, S, S, views, out))
+  if (P.scale < 1 || P.scale > 16 || !P.src || !P.field || !P.kind || (table && !P.gim) ||
+      !window_args_ok(n, zoom, vw, vh, S, S, views, out, format))
     return hipErrorInvalidValue;
   if (!out && (vw != S || vh != S)) return hipErrorInvalidValue;
-  const dim3 grid = window_grid(table != nullptr, zoom, vw, vh, n);
+  const dim3 grid = window_grid(table || format, zoom, vw, vh, n);
   if (zoom == 1) {
-    auto kernel = table ? session_render_kernel<true> : session_render_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, P, table, views, vw, vh, out);
+    auto kernel = format ? (table ? session_render_kernel<true, true> : session_render_kernel<false, true>)
+                         : (table ? session_render_kernel<true, false> : session_render_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, P, table, views, vw, vh, out, format);
   } else {
-    auto kernel = table ? session_render_zoom_kernel<true> : session_render_zoom_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, P, table, views, vw, vh, zoom, out);
+    auto kernel = format ? (table ? session_render_zoom_kernel<true, true> : session_render_zoom_kernel<false, true>)
+                         : (table ? session_render_zoom_kernel<true, false> : session_render_zoom_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, P, table, views, vw, vh, zoom, out, format);
   }
   return hipGetLastError();
 }
 hipError_t launch_canvas_compose(const SessionCanvases& C, const SessionPool& P, const float* table, const int* windows, int vw, int vh, int zoom,
-                                 unsigned char* out, int n, hipStream_t s) {
-  if (!canvases_ok(C) || !P.field || !P.kind || (table && !P.gim) || !window_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out))
+                                 unsigned char* out, int n, int format, hipStream_t s) {
+  if (!canvases_ok(C) || !P.field || !P.kind || (table && !P.gim) || !window_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out, format))
     return hipErrorInvalidValue;
   if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
-  const dim3 grid = window_grid(table != nullptr, zoom, vw, vh, n);
+  const dim3 grid = window_grid(table || format, zoom, vw, vh, n);
   if (zoom == 1) {
-    auto kernel = table ? canvas_compose_kernel<true> : canvas_compose_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, C, P, table, windows, vw, vh, out);
+    auto kernel = format ? (table ? canvas_compose_kernel<true, true> : canvas_compose_kernel<false, true>)
+                         : (table ? canvas_compose_kernel<true, false> : canvas_compose_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, C, P, table, windows, vw, vh, out, format);
   } else {
-    auto kernel = table ? canvas_compose_zoom_kernel<true> : canvas_compose_zoom_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, C, P, table, windows, vw, vh, zoom, out);
+    auto kernel = format ? (table ? canvas_compose_zoom_kernel<true, true> : canvas_compose_zoom_kernel<false, true>)
+                         : (table ? canvas_compose_zoom_kernel<true, false> : canvas_compose_zoom_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, C, P, table, windows, vw, vh, zoom, out, format);
   }
   return hipGetLastError();
 }
 hipError_t launch_canvas_compose_oriented(const SessionCanvases& C, const int* otable, const SessionPool& P, const int* windows, int vw, int vh,
-                                          int zoom, unsigned char* out, int n, hipStream_t s) {
-  if (!canvases_ok(C) || !otable || !P.field || !P.kind || !window_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out))
+                                          int zoom, unsigned char* out, int n, int format, hipStream_t s) {
+  if (!canvases_ok(C) || !otable || !P.field || !P.kind || !window_args_ok(n, zoom, vw, vh, C.max_w, C.max_h, windows, out, format))
     return hipErrorInvalidValue;
   if (out ? (reinterpret_cast<uintptr_t>(out) & 3) != 0 : n != 1) return hipErrorInvalidValue;
-  const dim3 grid = window_grid(false, zoom, vw, vh, n);
-  if (zoom == 1)
-    hipLaunchKernelGGL(canvas_compose_oriented_kernel, grid, dim3(256), 0, s, C, otable, P, windows, vw, vh, out);
-  else
-    hipLaunchKernelGGL(canvas_compose_oriented_zoom_kernel, grid, dim3(256), 0, s, C, otable, P, windows, vw, vh, zoom, out);
+  const dim3 grid = window_grid(format != 0, zoom, vw, vh, n);
+  if (zoom == 1) {
+    auto kernel = format ? canvas_compose_oriented_kernel<true> : canvas_compose_oriented_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, C, otable, P, windows, vw, vh, out, format);
+  } else {
+    auto kernel = format ? canvas_compose_oriented_zoom_kernel<true> : canvas_compose_oriented_zoom_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, C, otable, P, windows, vw, vh, zoom, out, format);
+  }
   return hipGetLastError();
 }
 

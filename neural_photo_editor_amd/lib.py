@@ -57,6 +57,7 @@ EXPORTS = (
     "ian_sessions_reserve_edges", "ian_sessions_edges",
     "ian_session_zoom", "ian_session_brush_zoom", "ian_compose_zoom", "ian_compose_brush_zoom",
     "ian_place_oriented", "ian_placements_oriented",
+    "ian_sessions_set_pixels", "ian_sessions_pixels",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -162,6 +163,8 @@ def load_library():
     lib.ian_compose_brush_zoom.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, i32, C.POINTER(CanvasWindow), i32, i32, i32, fp, vp]
     lib.ian_place_oriented.argtypes = [vp, i32, C.POINTER(CanvasOriented), fp, vp]
     lib.ian_placements_oriented.argtypes = [vp, i32, C.POINTER(CanvasOriented), fp]
+    lib.ian_sessions_set_pixels.argtypes = [vp, i32]
+    lib.ian_sessions_pixels.argtypes = [vp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
     lib.ian_read_slot.argtypes = [vp, i32, i32, fp, vp]
@@ -476,6 +479,17 @@ class Handle:
         if rc < 0:
             self._check(rc)
         return t if rc == 1 else None
+
+    def sessions_set_pixels(self, fmt):
+        """ian_sessions_set_pixels; fmt = 0 planar, 1 rgb, 2 rgba, 3 bgra (npe_ops.PIXEL_FORMATS): what `out` of every window call holds."""
+        self._check(self.lib.ian_sessions_set_pixels(self._h, int(fmt)))
+
+    def sessions_pixels(self):
+        """ian_sessions_pixels -> the pixel format in force, 0..3."""
+        rc = self.lib.ian_sessions_pixels(self._h)
+        if rc < 0:
+            self._check(rc)
+        return rc
 
     def sessions_reserve_local(self, on=True):
         self._check(self.lib.ian_sessions_reserve_local(self._h, int(bool(on))))

@@ -404,6 +404,45 @@ def zoom_box_mean(img_u8, k):
     return np.uint8((total + (k * k) // 2) // (k * k))
 
 
+# The pixel formats of a window result (ian_sessions_set_pixels): the id is the index.
+PIXEL_FORMATS = ("planar", "rgb", "rgba", "bgra")
+
+
+def pixel_format_id(fmt):
+    """A format's name or id -> its id, 0..3."""
+    if isinstance(fmt, str):
+        if fmt not in PIXEL_FORMATS:
+            raise ValueError("a pixel format is one of %s, got %r" % (", ".join(PIXEL_FORMATS), fmt))
+        return PIXEL_FORMATS.index(fmt)
+    if isinstance(fmt, (bool, float)) or int(fmt) != fmt or not 0 <= int(fmt) < len(PIXEL_FORMATS):
+        raise ValueError("a pixel format is 0..%d or one of %s, got %r" % (len(PIXEL_FORMATS) - 1, ", ".join(PIXEL_FORMATS), fmt))
+    return int(fmt)
+
+
+def window_shape(n, vw, vh, fmt):
+    """The shape of n windows of vw x vh under a pixel format: (n,3,vh,vw) planar, (n,vh,vw,3) rgb, (n,vh,vw,4) rgba / bgra."""
+    f = pixel_format_id(fmt)
+    return (n, 3, vh, vw) if f == 0 else (n, vh, vw, 3 if f == 1 else 4)
+
+
+def pack_window(planar, fmt):
+    """The specification of the packed window formats: planar uint8 (...,3,vh,vw), what every window call writes under format 0 ->
+    what it writes under fmt.  planar: the array itself; rgb: (...,vh,vw,3); rgba: (...,vh,vw,4) as R, G, B, 255; bgra: as B, G, R,
+    255.  Every colour byte is the planar byte of that pixel and channel."""
+    f = pixel_format_id(fmt)
+    a = np.asarray(planar)
+    if a.dtype != np.uint8 or a.ndim < 3 or a.shape[-3] != 3:
+        raise ValueError("planar windows are uint8 (...,3,vh,vw), got %s %s" % (a.dtype, a.shape))
+    if f == 0:
+        return a
+    rgb = np.moveaxis(a, -3, -1)
+    if f == 1:
+        return np.ascontiguousarray(rgb)
+    out = np.full(rgb.shape[:-1] + (4,), 255, np.uint8)
+    out[..., :3] = rgb if f == 2 else rgb[..., ::-1]
+    return out
+
+
 def zoom_window(w, h, k):
     """The largest (vw, vh) a w x h picture shows whole at 1/k: vw % 4 == 0, k*vw <= w, k*vh <= h."""
     k = _zoom(k)
