@@ -555,10 +555,11 @@ int ian_session_clone(ian_handle* h, int32_t n, const ian_session_clone_event* e
    which an all-ones tip IS the rectangle brush, bit for bit, in both modes (wn == 1.f / (float)(3 * th * tw), the rectangle's own 1/N).
    The event's rectangle lies inside the image as always, and its size is exactly the tip's: c2 - c1 == tw and r2 - r1 == th.
    Tips belong to the handle, not to a session: they are no part of a saved session, of the undo history, of the guide or of a canvas.
-   Tips weight colour brushes only: ian_session_clone, ian_session_fit, the stateless ian_grad_batch / ian_brush_step_batch and
-   ian_canvas_brush keep the unweighted loss.  Under the local reservation the footprint that goes into UMASK stays that of the
-   rectangle; a footprint shaped by the tip is out of scope.  A pool that never reserves tips launches, moves and computes nothing it
-   did not before. */
+   Tips weight every call that paints on a session: the colour brushes (ian_session_brush_tip, ian_session_path_tip, and on a whole
+   photo ian_compose_brush_soft) and the clone and restore brushes (ian_session_stamp_soft).  ian_session_fit and the stateless
+   ian_grad_batch / ian_brush_step_batch keep the unweighted loss.  Under the local reservation the footprint that goes into UMASK is
+   that of the rectangle unless ian_sessions_set_soft_mask switched on the footprint shaped by the tip (below).  A pool that
+   never reserves tips launches, moves and computes nothing it did not before. */
 
 /* Room for `count` tips (0..64; 0 frees them; another count frees them and every tip starts unset; the same count changes nothing).
    Needs the pool (-6 otherwise), synchronises the device.  ian_sessions_reserve(0) and ian_destroy free the tips too. */
@@ -582,6 +583,29 @@ int ian_session_brush_tip(ian_handle* h, int32_t n, const ian_session_event* eve
    for byte.  Refusals: those of ian_session_stroke and of ian_session_brush_tip, naming the item and the point. */
 int ian_session_path_tip(ian_handle* h, int32_t n, const ian_session_stroke_item* strokes, const int32_t* tips, int32_t nboxes,
                          const ian_stroke_box* boxes, int32_t flags, uint8_t* shown, void* stream);
+
+/* ian_session_clone with one tip index per event (tips int32[n], host; -1 = no tip, and such an item is today's clone event, byte
+   for byte).  Item i with tip t >= 0 is a clone event whose seed, inside the rectangle, is
+       g = 2.f * (x_hat[co,r,c] - tanh_table[F[source][co, r + dr, c + dc]]) * wn_t[r - r1][c - c1]
+   (float32, in that order) and zero outside: the clone's target with the tip's weight in the place of 1/N.  Everything else is
+   ian_session_clone's: steps 1..IAN_CLONE_MAX_STEPS of which only the last blends, residency, latent versions, history notes, passes
+   of brush_pass, the refusals.  Host -> device: the event table, 12 words per event.  -6 also without the tip reservation; -7, naming
+   the item, before anything is enqueued: what ian_session_brush_tip refuses about tips. */
+int ian_session_stamp_soft(ian_handle* h, int32_t n, const ian_session_clone_event* events, const int32_t* tips, int32_t steps,
+                          uint8_t* shown, void* stream);
+/* A user mask shaped by the tip.  on = 1: an item that names a tip >= 0, is a paint event (mode 1, or a clone), targets a session in
+   photo mode with LOCAL bit 0 set, in a pool with the local reservation -- exactly where the rectangle's footprint goes into UMASK
+   -- max-es the footprint of its tip into UMASK in the place of the rectangle's, every point of a stroke included:
+       s[qy,qx] = (double)wn[qy][qx] / (double)max wn          (all zero for an all-zero tip)
+       R[qy,x]  = max_qx s[qy,qx] * falloff[|x - (c1 + qx)|]
+       F[y,x]   = max_qy falloff[|y - (r1 + qy)|] * R[qy,x]    UMASK := max(UMASK, F)        (npe_ops.tip_footprint)
+   in float64, one product each; for an all-ones tip that is the rectangle's footprint bit for bit.  Items with tip -1, light events,
+   sample-mode sessions and sessions with bit 0 clear behave as ever.  on = 0 (the default): every call is byte for byte what it is
+   without this setting.  A setting of the handle like the pixel format: not a LOCAL flag, no part of a saved session (the UMASK it
+   leaves is).  Needs the tip reservation (-6 otherwise), synchronises the device; ian_sessions_reserve_tips with another count and
+   ian_sessions_reserve(0) clear it; without the local reservation it is kept and changes nothing.  -7 for on outside 0..1. */
+int ian_sessions_set_soft_mask(ian_handle* h, int32_t on);
+int ian_sessions_soft_mask(ian_handle* h, int32_t* on);
 
 /* ---- saving and loading whole sessions: the editor state as bytes that can leave the pool ----
    Everything a session is -- the 64x64 state, the full-resolution source and edit field, the user mask and flags, the ring of undo
@@ -697,6 +721,10 @@ int ian_canvas_compose(ian_handle* h, int32_t n, const ian_canvas_window* window
    them.  Every check of both calls is made before anything is enqueued. */
 int ian_canvas_brush(ian_handle* h, int32_t n, const ian_session_event* events, uint8_t* shown, int32_t m,
                      const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream);
+/* ian_canvas_brush with one tip index per event (tips int32[n], host; -1 = none): a soft brush on a whole photo, ian_session_brush_tip
+   whose windows are a canvas's.  Refusals: those of both; ian_sessions_set_soft_mask applies. */
+int ian_compose_brush_soft(ian_handle* h, int32_t n, const ian_session_event* events, const int32_t* tips, uint8_t* shown, int32_t m,
+                         const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream);
 /* The canvas becomes the compose of its whole picture, in place; then every session placed on it is placed again where it is: the
    box mean of the new canvas and the open above, at batch k = the number of sessions placed there.  shown u8[k,3,64,64] (host or
    device; ascending session id) or NULL.  ian_session_open(source = 1) on a placed session returns -7 and names this call: GIM := IM

@@ -714,6 +714,7 @@ class EditSessions:
         self._placed = {}               # session id -> (canvas id, x, y, scale), or oriented (canvas id, cx2, cy2, ax, ay)
         self.tips = 0                   # tip reservation: how many brush tips the handle keeps; 0 = none
         self._tips = {}                 # tip -> (tw, th) of the tips that were set
+        self._tip_footprint = False     # tip_footprint(): a tipped paint event leaves its tip's shape in the user mask
         self.pixels = 0                 # the pixel format of every window result (pixel_format): 0 planar, 1 rgb, 2 rgba, 3 bgra
         self.reserve(capacity)
         self._h.sessions_set_blend(npe_ops.gaussian_half_kernel(sigma, int(4.0 * float(sigma) + 0.5)))
@@ -923,7 +924,20 @@ class EditSessions:
         self._h.sessions_reserve_tips(count)
         if count != self.tips:
             self._tips = {}
+            self._tip_footprint = False
         self.tips = count
+
+    def tip_footprint(self, on=None):
+        """on = True: from now on a paint event (brush, stroke, clone, restore, brush_compose, paint) that names a tip leaves the tip's
+        own shape in the user mask (npe_ops.umask_paint_tip) where it left its rectangle's (npe_ops.umask_paint): under local edits a
+        round brush no longer bleeds into the corners of its square.  False switches back; None changes nothing.  -> the setting in
+        force.  Needs reserve_tips; another tip count switches it off.  Without reserve_local it changes nothing."""
+        if on is not None:
+            if not self.tips:
+                raise ValueError("the pool has no tip reservation (reserve_tips)")
+            self._h.sessions_set_tip_footprint(bool(on))
+            self._tip_footprint = bool(on)
+        return self._tip_footprint
 
     def _need_tip(self, tip):
         tip = int(tip)
@@ -1215,10 +1229,11 @@ class EditSessions:
             self._h.compose_zoom(win, vw, vh, zoom, out)
         return out
 
-    def brush_compose(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, windows=None):
+    def brush_compose(self, ids, boxes, colours=None, modes=None, weight=0.05, sign=-1.0, windows=None, tips=None):
         """brush on sessions ids, and the windows = (cids, origins, size) or (cids, origins, size, zoom) of compose() after it, in ONE
         submission -> (shown, out).  The sessions need not be placed, the windows need not show them.  After reserve_canvas_guide
-        the windows are npe_ops.canvas_compose_guided's."""
+        the windows are npe_ops.canvas_compose_guided's.  tips: as in brush (ian_compose_brush_soft); windows at a zoom have no
+        tipped form."""
         if windows is None or len(windows) not in (3, 4):
             raise ValueError("windows must be (cids, origins, size) or (cids, origins, size, zoom)")
         ev = pack_session_events(ids, boxes, colours, modes, weight, sign, capacity=self.capacity, opened=self._opened)
@@ -1226,7 +1241,11 @@ class EditSessions:
         zoom = windows[3] if len(windows) == 4 else 1
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
         out = self._window_out(len(win), vw, vh)
-        if zoom == 1:
+        if tips is not None:
+            if zoom != 1:
+                raise ValueError("brush_compose with tips has no zoomed form: compose(zoom=) after brush(tips=)")
+            self._h.canvas_brush_tip(ev, self._tipsel(tips, self._event_boxes(ev)), win, vw, vh, out, shown)
+        elif zoom == 1:
             self._h.canvas_brush(ev, win, vw, vh, out, shown)
         else:
             self._h.compose_brush_zoom(ev, win, vw, vh, zoom, out, shown)
@@ -1305,22 +1324,28 @@ class EditSessions:
             self._h.session_brush_tip(ev, self._tipsel(tips, self._event_boxes(ev)), shown)
         return shown
 
-    def clone(self, ids, boxes, sources, offsets=(0, 0), field="GIM", steps=1, weight=0.05, sign=-1.0):
+    def clone(self, ids, boxes, sources, offsets=(0, 0), field="GIM", steps=1, weight=0.05, sign=-1.0, tips=None):
         """The clone brush (ian_session_clone): the rectangle boxes[i] of session ids[i] is pulled towards the rectangle shifted by
         offsets[i] = (dc, dr) of session sources[i]'s GIM, IM or RECON (pack_session_clones), `steps` gradient steps (1..64) in one
         submission -> shown uint8 (n,3,64,64).  Each step is a paint event whose target is that picture instead of a flat colour; the
-        sessions end byte for byte where `steps` calls with steps=1 leave them.  For one undo step call mark(ids) first."""
+        sessions end byte for byte where `steps` calls with steps=1 leave them.  For one undo step call mark(ids) first.  tips: one
+        tip index for all events or one per event (-1 = none, the plain clone event): the event's loss is weighted by that tip
+        (ian_session_stamp_soft; npe_ops.clone_tip_seed), whose size the box must have: a soft round clone stamp."""
         steps = check_clone_steps(steps)
         ev = pack_session_clones(ids, boxes, sources, offsets, field, weight, sign, capacity=self.capacity, opened=self._opened)
         shown = np.empty((len(ev), 3, 64, 64), np.uint8)
-        self._h.session_clone(ev, steps, shown)
+        if tips is None:
+            self._h.session_clone(ev, steps, shown)
+        else:
+            self._h.session_clone_tip(ev, self._tipsel(tips, self._event_boxes(ev)), steps, shown)
         return shown
 
-    def restore(self, ids, boxes, steps=1, weight=0.05):
+    def restore(self, ids, boxes, steps=1, weight=0.05, tips=None):
         """The restore brush: the rectangles are pulled back towards the sessions' own photos -- clone from each session's own GIM at
-        offset 0.  The user mask, the edit field and the undo history go on as for a paint event (reset and fit would clear them)."""
+        offset 0.  The user mask, the edit field and the undo history go on as for a paint event (reset and fit would clear them).
+        tips: as in clone."""
         idv = self._ids(ids, True)
-        return self.clone(idv, boxes, idv, (0, 0), "GIM", steps, weight, -1.0)
+        return self.clone(idv, boxes, idv, (0, 0), "GIM", steps, weight, -1.0, tips)
 
     def stroke(self, ids, paths, colours=None, modes=None, weight=0.05, sign=-1.0, mark=False, tips=None):
         """Whole brush paths in one submission (ian_session_stroke): paths = one (K_i,4) array of rectangles per session, 1..64 points,

@@ -239,9 +239,10 @@ struct BrushSeedSrc {
   const unsigned char* im = nullptr;    // the pool's IM and RECON bases, as gim
   const unsigned char* recon = nullptr;
   const int* clone = nullptr;           // device int[n][3]: source session, field selector, shift dr * 64 + dc
-  // ... or, with a table and colours, a brush tip per item (ian_session_brush_tip): inside its rectangle item i's loss is weighted by
-  // tips[tipsel[i] * 4096 + (r - r1) * 64 + (c - c1)] in the place of the flat 1/N; tipsel[i] = -1 keeps 1/N.  Colour brushes only:
-  // the photo and clone targets, the colour images of the stateless batched calls and the eager single call have no weighted form.
+  // ... and, with a table and colours or a clone's sources, a brush tip per item (ian_session_brush_tip, ian_session_stamp_soft): inside
+  // its rectangle item i's loss is weighted by tips[tipsel[i] * 4096 + (r - r1) * 64 + (c - c1)] in the place of the flat 1/N;
+  // tipsel[i] = -1 keeps 1/N.  The photo target, the colour images of the stateless batched calls and the eager single call have no
+  // weighted form.
   const float* tips = nullptr;          // device float[count][64 * 64], row stride 64 (ian_sessions_set_tip)
   const int* tipsel = nullptr;          // device int[n]: the items' tip indices
 };
@@ -417,6 +418,8 @@ struct SessionBlendArgs {
   int radius;
   const double* falloff;  // pools with the local reservation: device f64[64] (ian_sessions_set_local) and the dampen threshold
   double thresh;
+  const int* tips;        // pools with the local reservation under ian_sessions_set_soft_mask: device int[n], the items' tip indices.  An
+                          // item with a tip >= 0 adds no rectangle footprint: launch_session_tip_umask added its tip's.  nullptr: none
 };
 // P.umask == nullptr: session_blend_kernel; otherwise session_blend_local_kernel, which reads the sessions' LOCAL flags
 hipError_t launch_session_blend(const SessionBlendArgs& a, int n, hipStream_t s);
@@ -426,9 +429,15 @@ hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const 
 // n - 1, under the blend's conditions (LOCAL bit 0, a paint stroke, photo mode).  items = the call's ian_brush_item rows (7 words
 // each), step after step; rows = device int[steps + 1]: step k's rows start at rows[k], one per stroke with more than k points in
 // stroke order, so stroke g's row of step k is rows[k] + g while g < rows[k + 1] - rows[k]; falloff = device f64[64].
+// tips (device int[], indexed like ids; nullptr: none): a stroke whose tip index is >= 0 is launch_session_tip_umask's and is skipped.
 constexpr int STROKE_MAX_POINTS = 64;
 hipError_t launch_session_stroke_umask(const SessionPool& P, const int* ids, const int* items, const int* rows, int steps, int first,
-                                       const double* falloff, int n, hipStream_t s);
+                                       const double* falloff, const int* tips, int n, hipStream_t s);
+// ian_sessions_set_soft_mask: the same for the items with a tip: UMASK row of session ids[g] := max(UMASK, npe_ops.tip_footprint of
+// every rectangle of item g with the shape of tip tips[g]) under the same conditions; an item with tips[g] < 0 is skipped.  shapes =
+// device f64[count][64 * 64] (tip_shape_slot).  rows == nullptr: item g has the one row g (a brush or clone event), steps = 1.
+hipError_t launch_session_tip_umask(const SessionPool& P, const int* ids, const int* items, const int* rows, int steps, int first,
+                                    const double* falloff, const int* tips, const double* shapes, int n, hipStream_t s);
 // ian_session_fit.  begin: IM := GIM of sessions ids[0..n).  adam: rows 0..n-1 of the latent slot z (stride zs) move by one Adam step
 // (ian_fit_step.h) on the gradient rows g (same stride); m, v = the moments, [n][zl]; c1, c2 = the step's bias corrections.
 // loss: loss[i * loss_stride] = the float64 mean of (xhat[i] - table[GIM of ids[i]])^2 over the rectangle of row i of the

@@ -550,6 +550,13 @@ int ian_canvas_brush(ian_handle* h, int32_t n, const ian_session_event* events, 
   if (!windows) return fail(h, -1, "null pointer passed to ian_canvas_brush");
   return session_brush(h, n, events, shown, stream, BrushWindows{BrushWindows::CANVAS, nullptr, windows, m, vw, vh, out});
 }
+int ian_compose_brush_soft(ian_handle* h, int32_t n, const ian_session_event* events, const int32_t* tips, uint8_t* shown, int32_t m,
+                         const ian_canvas_window* windows, int32_t vw, int32_t vh, uint8_t* out, void* stream) {
+  if (!h) return -1;
+  if (!windows) return fail(h, -1, "null pointer passed to ian_compose_brush_soft");
+  return session_brush(h, n, events, shown, stream,
+                       BrushWindows{BrushWindows::CANVAS, nullptr, windows, m, vw, vh, out, 1, "ian_compose_brush_soft"}, true, tips);
+}
 int ian_canvas_commit(ian_handle* h, int32_t canvas, uint8_t* shown, void* stream) {
   return h ? canvas_commit(h, canvas, shown, stream) : -1;
 }

@@ -19,7 +19,8 @@
 //          the brush footprint (DESIGN.md 4.4)
 //   history ian_sessions_reserve_history  per session a ring of depth + 1 saved states: its Z rows and, when the local reservation
 //          exists at that moment, its UMASK rows; per session on the host the list and cursor of ian_session_history.h (DESIGN.md 4.5)
-//   tips   ian_sessions_reserve_tips   no column: per handle the brush tips' weights (d_tips) and, on the host, their sizes (DESIGN.md 4.12)
+//   tips   ian_sessions_reserve_tips   no column: per handle the brush tips' weights (d_tips) and shapes (d_tip_shape) and, on the host,
+//          their sizes and the tip-footprint setting (DESIGN.md 4.12, 4.18)
 // Without a reservation its pointers are null, no kernel touches them, and launch_session_blend runs session_blend_kernel.
 namespace {
 
@@ -80,6 +81,7 @@ const SessScratchBuf SESS_SCRATCH[] = {
     {offsetof(SessionScratch, d_ltab), (size_t)BATCH_MAX * 2 * sizeof(int32_t), SESS_LOCAL},
     {offsetof(SessionScratch, d_htab), (size_t)BATCH_MAX * 3 * sizeof(int32_t), SESS_HISTORY},
     {offsetof(SessionScratch, d_tips), 0, SESS_TIPS},   // by ian_sessions_reserve_tips, at its count
+    {offsetof(SessionScratch, d_tip_shape), 0, SESS_TIPS},   // with d_tips
 };
 
 // the pointer member at byte `at` of a SessionArrays / SessionScratch (members of several pointer types: copied, not aliased)
@@ -206,6 +208,7 @@ void sess_free_group(decltype(ian_handle::sess)& S, SessGroup g) {
   } else if (g == SESS_TIPS) {
     S.tip_count = 0;
     S.tip_wh.clear();
+    S.tip_footprint = false;
   } else {
     S.arr.pool.zl = 0;
     S.capacity = 0;
@@ -929,16 +932,20 @@ int sessions_reserve_tips(ian_handle* h, int count) {
   if (count == S.tip_count) return 0;
   sess_free_group(S, SESS_TIPS);
   if (count == 0) return 0;
-  const size_t bytes = (size_t)count * TIP_SLOT * sizeof(float);
+  const size_t bytes = (size_t)count * TIP_SLOT * sizeof(float), sbytes = (size_t)count * TIP_SLOT * sizeof(double);
   float* d = nullptr;
+  double* ds = nullptr;   // the shapes beside the weights: a tip never set has neither
   hipError_t e = hipMalloc((void**)&d, bytes);
-  if (e == hipSuccess && (e = hipMemset(d, 0, bytes)) == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMalloc((void**)&ds, sbytes);
+  if (e == hipSuccess && (e = hipMemset(d, 0, bytes)) == hipSuccess && (e = hipMemset(ds, 0, sbytes)) == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     if (d) (void)hipFree(d);
+    if (ds) (void)hipFree(ds);
     (void)hipGetLastError();
-    return fail(h, -2, "%s: %s for %d tips of %zu bytes", fn, hipGetErrorString(e), count, TIP_SLOT * sizeof(float));
+    return fail(h, -2, "%s: %s for %d tips of %zu bytes", fn, hipGetErrorString(e), count, TIP_SLOT * (sizeof(float) + sizeof(double)));
   }
   S.d_tips = d;
+  S.d_tip_shape = ds;
   S.tip_count = count;
   S.tip_wh.assign((size_t)2 * count, 0);
   return 0;
@@ -967,6 +974,9 @@ int sessions_set_tip(ian_handle* h, int tip, int tw, int th, const float* wn) {
   tip_to_slot(wn, tw, th, slot.data());
   S.tip_wh[2 * tip] = S.tip_wh[2 * tip + 1] = 0;   // a failed copy leaves the tip unset, not half written
   HIPCHK(h, hipMemcpy(S.d_tips + (size_t)tip * TIP_SLOT, slot.data(), TIP_SLOT * sizeof(float), hipMemcpyHostToDevice));
+  std::vector<double> shape((size_t)TIP_SLOT);
+  tip_shape_slot(wn, tw, th, shape.data());
+  HIPCHK(h, hipMemcpy(S.d_tip_shape + (size_t)tip * TIP_SLOT, shape.data(), TIP_SLOT * sizeof(double), hipMemcpyHostToDevice));
   S.tip_wh[2 * tip] = tw;
   S.tip_wh[2 * tip + 1] = th;
   return 0;
@@ -991,7 +1001,28 @@ int sessions_tip(ian_handle* h, int tip, int32_t* wh, float* wn_out) {
   wh[1] = th;
   return 0;
 }
-// What ian_session_brush_tip / ian_session_path_tip check about the tips array itself, after the checks of the plain call
+// The tip-shaped footprint (DESIGN.md 4.18) is a setting of the handle like the pixel format, and host state only: the enqueue of the
+// next call reads it.  It goes with the tips (sess_free_group).  Records, history and ian_session_read know nothing of it; in a pool
+// without the local reservation it is kept and changes nothing.
+int sessions_set_tip_footprint(ian_handle* h, int on) {
+  const char* fn = "ian_sessions_set_soft_mask";
+  int rc = session_ready(h, fn);
+  if (rc) return rc;
+  if ((rc = session_need(h, fn, SESS_BASE)) || (rc = session_need(h, fn, SESS_TIPS))) return rc;
+  if (on != 0 && on != 1) return fail(h, -7, "%s: on = %d (0 = the rectangle's footprint, 1 = the tip's)", fn, on);
+  HIPCHK(h, hipDeviceSynchronize());   // no event in flight sees the setting change
+  h->last_pending = false;
+  h->sess.tip_footprint = on != 0;
+  return 0;
+}
+int sessions_tip_footprint(ian_handle* h, int32_t* on) {
+  const char* fn = "ian_sessions_soft_mask";
+  if (int rc = session_need(h, fn, SESS_BASE)) return rc;
+  if (!on) return fail(h, -1, "null pointer passed to %s", fn);
+  *on = h->sess.tip_footprint ? 1 : 0;
+  return 0;
+}
+// What ian_session_brush_tip / ian_session_path_tip / ian_session_stamp_soft check about the tips array itself, after the checks of the plain call
 int session_tips_arg(ian_handle* h, const char* fn, const int32_t* tips) {
   if (!tips) return fail(h, -7, "%s: null tips array (one tip index per item, -1 for none)", fn);
   if (is_device_ptr(tips)) return fail(h, -7, "%s: the tips must be a host array", fn);
@@ -1097,6 +1128,13 @@ int edit_passes(ian_handle* h, const EditCall& C, uint8_t* shown, void* stream) 
   if (L.has_tips) seed0.tips = S.d_tips;
   Slot& zs = h->slots[h->desc.z_slot];
   const ResultTarget sh = shown_target(h, shown, true);
+  // ian_sessions_set_soft_mask: an item with a tip leaves the tip's footprint, launch_session_tip_umask's, not its rectangle's
+  const int* foot_tips = (S.tip_footprint && L.has_tips && S.arr.pool.umask) ? d + L.tips : nullptr;
+  auto tip_of = [&](int i) { return foot_tips ? S.stab_shadow[L.tips + (size_t)i] : -1; };
+  // what either footprint kernel would find on the device for item i, as far as the host knows it: the mode flag it does not
+  auto paints_local = [&](int i) {
+    return S.stab_shadow[L.items + (size_t)EDIT_ROW_WORDS * i + 4] == 1 && (S.local_flags[C.ids[(size_t)i * C.stride]] & 1);
+  };
   for (int off = 0; off < n; off += pass) {
     const int nc = std::min(pass, n - off);
     if (!hit) {
@@ -1106,8 +1144,14 @@ int edit_passes(ian_handle* h, const EditCall& C, uint8_t* shown, void* stream) 
     }
     bool footprints = false;   // what the kernel would find on the device, as far as the host knows it: the mode flag it does not
     for (int i = off; C.modes && S.arr.pool.umask && !footprints && i < off + nc; ++i)
-      footprints = C.modes[(size_t)i * C.stride] == 1 && (S.local_flags[C.ids[(size_t)i * C.stride]] & 1);
-    if (footprints) HIPCHK(h, launch_session_stroke_umask(S.arr.pool, d + L.ids, d + L.items, d + L.rows, P.count(off), off, S.d_falloff, nc, st));
+      footprints = C.modes[(size_t)i * C.stride] == 1 && (S.local_flags[C.ids[(size_t)i * C.stride]] & 1) && tip_of(i) < 0;
+    if (footprints)
+      HIPCHK(h, launch_session_stroke_umask(S.arr.pool, d + L.ids, d + L.items, d + L.rows, P.count(off), off, S.d_falloff, foot_tips, nc, st));
+    bool tip_footprints = false;
+    for (int i = off; foot_tips && !tip_footprints && i < off + nc; ++i) tip_footprints = tip_of(i) >= 0 && paints_local(i);
+    if (tip_footprints)
+      HIPCHK(h, launch_session_tip_umask(S.arr.pool, d + L.ids, d + L.items, P.own_rows ? d + L.rows : nullptr, P.own_rows ? P.count(off) : 1, off,
+                                         S.d_falloff, foot_tips, S.d_tip_shape, nc, st));
     rc = edit_pass_steps(P, off, nc, [&](const EditStep& s) -> int {
       BrushSeedSrc seed = seed0;
       seed.table = d + L.items + (size_t)EDIT_ROW_WORDS * s.row;
@@ -1120,6 +1164,7 @@ int edit_passes(ian_handle* h, const EditCall& C, uint8_t* shown, void* stream) 
       SessionBlendArgs a = session_blend_args(h, d + L.ids + off + s.keep, seed.table + (size_t)EDIT_ROW_WORDS * s.keep,
                                               sh.dev + (size_t)(off + s.keep) * SESS_IMG, 1);
       a.xhat += (size_t)s.keep * SESS_IMG; a.zslot += (size_t)s.keep * zs.cs;
+      if (foot_tips) a.tips = foot_tips + off + s.keep;
       HIPCHK(h, launch_session_blend(a, s.act - s.keep, st));
       return s.keep > 0 ? batch_forward(h, nullptr, s.keep, st) : 0;
     });
@@ -1174,8 +1219,10 @@ int session_brush(ian_handle* h, int n, const ian_session_event* ev, uint8_t* sh
 
 // ian_session_clone (DESIGN.md 4.10): a paint event towards a rectangle of another picture of the pool, `steps` gradient steps: a stroke
 // whose items all have `steps` points on one row.  Seed words: source id, field selector (0 GIM, 1 IM, 2 RECON), shift dr * 64 + dc.
-int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int steps, uint8_t* shown, void* stream) {
-  const char* fn = "ian_session_clone";
+// tipped: ian_session_stamp_soft, one tip index per event (tips): the seed is SEED_CLONE_TIP's (DESIGN.md 4.18)
+int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int steps, uint8_t* shown, void* stream, bool tipped = false,
+                  const int32_t* tips = nullptr) {
+  const char* fn = tipped ? "ian_session_stamp_soft" : "ian_session_clone";
   static_assert(sizeof(ian_session_clone_event) == 11 * sizeof(int32_t), "ian_session_clone_event is 11 words");
   int rc = session_check(h, fn, n, ev ? &ev->session : nullptr, 11, true, true);
   if (rc) return rc;
@@ -1198,11 +1245,14 @@ int session_clone(ian_handle* h, int n, const ian_session_clone_event* ev, int s
       return fail(h, -7, "%s: item %d: source session %d is read from IM, which item %d of this call writes", fn, i, e.source, dest[e.source]);
   }
   if ((rc = session_local_check(h, fn, n, &ev->session, 11))) return rc;
+  if (tipped && (rc = session_tips_arg(h, fn, tips))) return rc;
+  for (int i = 0; tipped && i < n; ++i)
+    if ((rc = session_tip_rect(h, fn, i, -1, tips[i], ev[i].c1, ev[i].r1, ev[i].c2, ev[i].r2))) return rc;
   const int32_t count = steps;
-  const EditCall C = edit_call(&ev->session, 11, edit_plan(n, &count, 0, false), false, true);
+  const EditCall C = edit_call(&ev->session, 11, edit_plan(n, &count, 0, false), tipped, true);
   const EditTable& L = C.tab;
   int32_t* t;
-  if ((rc = edit_table_begin(h, L, n, nullptr, &t))) return rc;
+  if ((rc = edit_table_begin(h, L, n, tips, &t))) return rc;
   for (int i = 0; i < n; ++i) {
     const ian_session_clone_event& e = ev[i];
     t[L.ids + i] = e.session;
@@ -1582,6 +1632,8 @@ int ian_sessions_reserve_tips(ian_handle* h, int32_t count) {
 int ian_sessions_set_tip(ian_handle* h, int32_t tip, int32_t tw, int32_t th, const float* wn) {
   return h ? sessions_set_tip(h, tip, tw, th, wn) : -1;
 }
+int ian_sessions_set_soft_mask(ian_handle* h, int32_t on) { return h ? sessions_set_tip_footprint(h, on) : -1; }
+int ian_sessions_soft_mask(ian_handle* h, int32_t* on) { return h ? sessions_tip_footprint(h, on) : -1; }
 int ian_sessions_tip(ian_handle* h, int32_t tip, int32_t wh[2], float* wn_out) {
   return h ? sessions_tip(h, tip, wh, wn_out) : -1;
 }
@@ -1621,6 +1673,10 @@ int ian_session_fit(ian_handle* h, int32_t n, const ian_session_fit_item* items,
 }
 int ian_session_clone(ian_handle* h, int32_t n, const ian_session_clone_event* events, int32_t steps, uint8_t* shown, void* stream) {
   return h ? session_clone(h, n, events, steps, shown, stream) : -1;
+}
+int ian_session_stamp_soft(ian_handle* h, int32_t n, const ian_session_clone_event* events, const int32_t* tips, int32_t steps,
+                          uint8_t* shown, void* stream) {
+  return h ? session_clone(h, n, events, steps, shown, stream, true, tips) : -1;
 }
 int ian_session_record_info(ian_handle* h, ian_session_meta* layout, int64_t* offsets, int32_t* ncols) {
   return h ? session_record_info(h, layout, offsets, ncols) : -1;

@@ -307,6 +307,7 @@ struct ian_handle {
     double* d_fit_loss = nullptr;      // ian_session_fit: staging of the loss trace for a host `loss`, [256][513]; by the first call that asks for one
     int* d_stab = nullptr;             // brush, clone, stroke and fit calls: the call's table, laid out by EditTable (ian_edit_plan.h), grown on demand (stab_cap words)
     float* d_tips = nullptr;           // brush tips: f32[tip_count][64 * 64], row stride 64 (ian_sessions_reserve_tips / _set_tip); nullptr = no tips
+    double* d_tip_shape = nullptr;     // brush tips: f64[tip_count][64 * 64], the tips' shapes wn / max wn (tip_shape_slot) for the tip-shaped footprint; with d_tips
   };
   struct SessionState : SessionScratch {
     int capacity = 0;
@@ -348,6 +349,7 @@ struct ian_handle {
     // weights.  Per handle, not per session: no record, history or canvas knows of them.
     int tip_count = 0;
     std::vector<int32_t> tip_wh;
+    bool tip_footprint = false;          // ian_sessions_set_soft_mask: a tipped paint event leaves its tip's shape in UMASK, not its rectangle's
     // canvases (ian_sessions_reserve_canvas, ian_rt_canvas.inc): the device arrays, per canvas the size of its picture (0 x 0: never
     // put), per session where it is placed (canvas -1: nowhere; sized with the pool while canvases exist, empty otherwise), and the
     // host's copy of the device table (canv.table), from which a canvas's 8 entries are uploaded whenever they change

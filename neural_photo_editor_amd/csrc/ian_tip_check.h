@@ -54,6 +54,16 @@ inline void tip_to_slot(const float* wn, int tw, int th, float* slot) {
   for (int r = 0; r < th; ++r)
     for (int c = 0; c < tw; ++c) slot[r * TIP_MAX_SIDE + c] = wn[r * tw + c];
 }
+// a tip's shape for the footprint it leaves in the user mask (npe_ops.tip_footprint): s = float64(wn) / float64(max wn), one float64
+// division per pixel, into a slot [64][64] of doubles (the rest of the slot is zero); all zeros when max wn == 0
+inline void tip_shape_slot(const float* wn, int tw, int th, double* slot) {
+  double m = 0.0;
+  for (int i = 0; i < tw * th; ++i) m = (double)wn[i] > m ? (double)wn[i] : m;
+  for (int i = 0; i < TIP_SLOT; ++i) slot[i] = 0.0;
+  if (!(m > 0.0)) return;
+  for (int r = 0; r < th; ++r)
+    for (int c = 0; c < tw; ++c) slot[r * TIP_MAX_SIDE + c] = (double)wn[r * tw + c] / m;
+}
 inline void tip_from_slot(const float* slot, int tw, int th, float* wn) {
   for (int r = 0; r < th; ++r)
     for (int c = 0; c < tw; ++c) wn[r * tw + c] = slot[r * TIP_MAX_SIDE + c];

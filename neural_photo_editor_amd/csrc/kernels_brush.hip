@@ -22,14 +22,18 @@ enum { SEED_IMM = 0,      // the rectangle and loss kind are launch arguments, t
        SEED_PHOTO = 3,    // the same table, the target the item's own photo: tab[GIM byte] of session ids[item] (ian_session_fit)
        SEED_CLONE = 4,    // the same table, the target another picture of the pool, shifted: tab[F byte at o + shift] of session
                           // clone[3 item], F = its GIM, IM or RECON row (ian_session_clone)
-       SEED_TIP = 5 };    // SEED_COLOUR with a weight per pixel in the place of the flat 1/N: tips[tipsel[item]][r - r1][c - c1], a
+       SEED_TIP = 5,      // SEED_COLOUR with a weight per pixel in the place of the flat 1/N: tips[tipsel[item]][r - r1][c - c1], a
                           // brush tip of ian_sessions_set_tip (ian_session_brush_tip); an item with tipsel -1 keeps 1/N
-struct SeedRect { int c1, r1, c2, r2, mode, id, field, shift, tip; };   // id: SEED_PHOTO the item's session, SEED_CLONE its source;
-                                                                        // field, shift: SEED_CLONE only; tip: SEED_TIP only
+       SEED_CLONE_TIP = 6 };   // SEED_CLONE with SEED_TIP's weight (ian_session_stamp_soft): the target from the pool, the factor from the tip
+constexpr bool seed_clones(int kind) { return kind == SEED_CLONE || kind == SEED_CLONE_TIP; }   // the target is SEED_CLONE's
+constexpr bool seed_tipped(int kind) { return kind == SEED_TIP || kind == SEED_CLONE_TIP; }     // the factor is SEED_TIP's
+struct SeedRect { int c1, r1, c2, r2, mode, id, field, shift, tip; };   // id: SEED_PHOTO the item's session, the clones its source;
+                                                                        // field, shift: the clones only; tip: the tipped kinds only
 constexpr int SEED_PHOTO_IMG = 3 * 64 * 64;          // a GIM / IM / RECON row of the session pool
 constexpr int SEED_TIP_ROW = 64, SEED_TIP_IMG = 64 * 64;   // a tip's row stride and its slot in BrushSeedSrc::tips
 template <int KIND> struct SeedLds {                 // ints / floats of LDS a kernel hands to seed_fetch
-  static constexpr int SP = KIND == SEED_CLONE ? 8 : ((KIND == SEED_PHOTO || KIND == SEED_TIP) ? 6 : 5), SC = (KIND == SEED_PHOTO || KIND == SEED_CLONE) ? 256 : 4;
+  static constexpr int SP = KIND == SEED_CLONE_TIP ? 9 : (KIND == SEED_CLONE ? 8 : ((KIND == SEED_PHOTO || KIND == SEED_TIP) ? 6 : 5));
+  static constexpr int SC = (KIND == SEED_PHOTO || seed_clones(KIND)) ? 256 : 4;
 };
 
 // The table may live in mapped host memory (zero-copy graphs): ONE lane per word fetches it and hands it on through LDS -- a scalar
@@ -47,6 +51,7 @@ template <int KIND> struct SeedLds {                 // ints / floats of LDS a k
 // SEED_TIP is SEED_COLOUR with one more word, the item's tip index, which travels like SEED_PHOTO's id.  The tip's weights are NOT
 // staged: a tip is up to 16 KB, a workgroup of the fused kernel covers 8 pixels and reads at most 8 x 25 of its weights, so staging
 // would load far more than is used; they are read through the cache where they are needed (seed_weight).
+// SEED_CLONE_TIP is both: SEED_CLONE's three words and staged table, and the tip index as a ninth word by a ninth lane.
 template <int KIND>
 __device__ __forceinline__ SeedRect seed_fetch(const BrushSeedSrc& src, int item, int* sp, float* sc) {
   if (KIND == SEED_IMM) return {src.c1, src.r1, src.c2, src.r2, src.mode, 0, 0, 0, -1};
@@ -56,25 +61,26 @@ __device__ __forceinline__ SeedRect seed_fetch(const BrushSeedSrc& src, int item
     if (threadIdx.x == 5) sp[5] = src.ids[item];
     sc[threadIdx.x] = src.tanh_tab[threadIdx.x];
   }
-  if (KIND == SEED_CLONE) {
+  if (seed_clones(KIND)) {
     if (threadIdx.x >= 5 && threadIdx.x < 8) sp[threadIdx.x] = src.clone[item * 3 + (threadIdx.x - 5)];
     sc[threadIdx.x] = src.tanh_tab[threadIdx.x];
   }
   if (KIND == SEED_TIP && threadIdx.x == 5) sp[5] = src.tipsel[item];
+  if (KIND == SEED_CLONE_TIP && threadIdx.x == 8) sp[8] = src.tipsel[item];
   __syncthreads();
   // the same five words in every lane: kept in scalar registers, as the launch arguments of SEED_IMM are
   return {__builtin_amdgcn_readfirstlane(sp[0]), __builtin_amdgcn_readfirstlane(sp[1]), __builtin_amdgcn_readfirstlane(sp[2]),
           __builtin_amdgcn_readfirstlane(sp[3]), __builtin_amdgcn_readfirstlane(sp[4]),
-          (KIND == SEED_PHOTO || KIND == SEED_CLONE) ? __builtin_amdgcn_readfirstlane(sp[5]) : 0,
-          KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[6]) : 0, KIND == SEED_CLONE ? __builtin_amdgcn_readfirstlane(sp[7]) : 0,
-          KIND == SEED_TIP ? __builtin_amdgcn_readfirstlane(sp[5]) : -1};
+          (KIND == SEED_PHOTO || seed_clones(KIND)) ? __builtin_amdgcn_readfirstlane(sp[5]) : 0,
+          seed_clones(KIND) ? __builtin_amdgcn_readfirstlane(sp[6]) : 0, seed_clones(KIND) ? __builtin_amdgcn_readfirstlane(sp[7]) : 0,
+          seed_tipped(KIND) ? __builtin_amdgcn_readfirstlane(sp[KIND == SEED_TIP ? 5 : 8]) : -1};
 }
-// the u8 row a seed's targets are looked up in: SEED_PHOTO the GIM row of the item's session, SEED_CLONE the row of its source that
+// the u8 row a seed's targets are looked up in: SEED_PHOTO the GIM row of the item's session, the clones the row of their source that
 // the field selector names (0 GIM, 1 IM, 2 RECON: the same for every lane of the workgroup); the other kinds have none
 template <int KIND>
 __device__ __forceinline__ const unsigned char* seed_row(const BrushSeedSrc& src, const SeedRect& R) {
   if (KIND == SEED_PHOTO) return src.gim + (size_t)R.id * SEED_PHOTO_IMG;
-  if (KIND == SEED_CLONE) return (R.field == 0 ? src.gim : (R.field == 1 ? src.im : src.recon)) + (size_t)R.id * SEED_PHOTO_IMG;
+  if (seed_clones(KIND)) return (R.field == 0 ? src.gim : (R.field == 1 ? src.im : src.recon)) + (size_t)R.id * SEED_PHOTO_IMG;
   return nullptr;
 }
 // 1/N, or 0 for an empty rectangle
@@ -82,24 +88,24 @@ __device__ __forceinline__ float seed_inv(const SeedRect& R) {
   const int cnt = 3 * (R.r2 - R.r1) * (R.c2 - R.c1);
   return cnt > 0 ? 1.f / (float)cnt : 0.f;
 }
-// The factor of the loss at pixel (r, c) INSIDE the rectangle: the flat inv, or for SEED_TIP the tip's weight there (all three channels
-// share it).  The tip index is the same in every lane (a scalar register), so an item without a tip takes the inv path on a
-// workgroup-uniform branch.  ian_session_brush_tip refused every item whose rectangle is not exactly its tip's tw x th <= 64 x 64 and
+// The factor of the loss at pixel (r, c) INSIDE the rectangle: the flat inv, or for the tipped kinds the tip's weight there (all three
+// channels share it).  The tip index is the same in every lane (a scalar register), so an item without a tip takes the inv path on a
+// workgroup-uniform branch.  ian_session_brush_tip / ian_session_stamp_soft refused every item whose rectangle is not exactly its tip's tw x th <= 64 x 64 and
 // every tip outside the reservation: (r - r1) * 64 + (c - c1) stays inside the tip's 64 x 64 slot.  A weight of 0 is not skipped: the
 // seed 2 * (xh - t) * 0 is +-0 and adds nothing to an accumulator, so skipping would change no bit, and the branch would serve only
 // the corners of a round tip.
 template <int KIND>
 __device__ __forceinline__ float seed_weight(const BrushSeedSrc& src, const SeedRect& R, float inv, int r, int c) {
-  if (KIND == SEED_TIP && R.tip >= 0) return src.tips[(size_t)R.tip * SEED_TIP_IMG + (r - R.r1) * SEED_TIP_ROW + (c - R.c1)];
+  if (seed_tipped(KIND) && R.tip >= 0) return src.tips[(size_t)R.tip * SEED_TIP_IMG + (r - R.r1) * SEED_TIP_ROW + (c - R.c1)];
   return inv;
 }
 // the seed of element o (channel co, value xh) of the item's image, for an element INSIDE a non-empty rectangle; rgb_i = the item's
 // target image, sc = its colour in LDS (SEED_PHOTO / SEED_CLONE: the tanh table, gim_i = the row of seed_row): whichever KIND names
-// is read, and only in mode 1.  inv: the pixel's seed_weight; SEED_TIP is SEED_COLOUR from here on
+// is read, and only in mode 1.  inv: the pixel's seed_weight; SEED_TIP is SEED_COLOUR, SEED_CLONE_TIP is SEED_CLONE from here on
 template <int KIND>
 __device__ __forceinline__ float seed_value(int mode, float inv, float xh, const float* rgb_i, const float* sc,
                                             const unsigned char* gim_i, int o, int co, int shift) {
-  if (KIND == SEED_CLONE) {
+  if (seed_clones(KIND)) {
     // o lies inside the item's rectangle, and ian_session_clone refused every rectangle whose copy shifted by (dr, dc) leaves the
     // 64x64 image: o + shift = (co * 64 + r + dr) * 64 + c + dc stays inside channel plane co of the source row
     return (mode == 0) ? inv : 2.f * (xh - sc[gim_i[o + shift]]) * inv;
@@ -119,7 +125,7 @@ __global__ __launch_bounds__(256) void brush_seed_kernel(BrushSeedSrc src, const
   if (i >= 3 * H * W) return;
   const size_t img = (size_t)item * 3 * H * W;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_TIP && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_TIP && KIND != SEED_PHOTO && !seed_clones(KIND) && R.mode) ? src.rgb + img : nullptr;
   const unsigned char* gim_i = seed_row<KIND>(src, R);
   const int xx = i % W, yy = (i / W) % H;
   float v = 0.f;
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
   const int OH = 2 * H, OW = 2 * W;
   const size_t img = (size_t)item * Cout * OH * OW;   // this item's image and target image
   const float* xh_i = xhat + img;
-  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_TIP && KIND != SEED_PHOTO && KIND != SEED_CLONE && R.mode) ? src.rgb + img : nullptr;
+  const float* rgb_i = (KIND != SEED_COLOUR && KIND != SEED_TIP && KIND != SEED_PHOTO && !seed_clones(KIND) && R.mode) ? src.rgb + img : nullptr;
   const unsigned char* gim_i = seed_row<KIND>(src, R);
   const float inv = seed_inv(R);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -195,7 +201,7 @@ __global__ __launch_bounds__(256) void brush_seed_dec_out_kernel(BrushSeedSrc sr
 }
 
 static int seed_kind(const BrushSeedSrc& src) {
-  return !src.table ? SEED_IMM : (src.clone ? SEED_CLONE : (src.gim ? SEED_PHOTO : (src.tipsel ? SEED_TIP : (src.colour ? SEED_COLOUR : SEED_RGB))));
+  return !src.table ? SEED_IMM : (src.clone ? (src.tipsel ? SEED_CLONE_TIP : SEED_CLONE) : (src.gim ? SEED_PHOTO : (src.tipsel ? SEED_TIP : (src.colour ? SEED_COLOUR : SEED_RGB))));
 }
 // a tip weights a colour brush: the colours, the tips' array, and the 64x64 image a tip's slot is made for
 static bool seed_tip_ok(const BrushSeedSrc& src, int C, int H, int W) { return src.colour && src.tips && C == 3 && H <= 64 && W <= 64; }
@@ -206,17 +212,22 @@ static bool seed_clone_ok(const BrushSeedSrc& src, int C, int H, int W) {
   return src.gim && src.im && src.recon && src.tanh_tab && C == 3 && H == 64 && W == 64;
 }
 
+// a weighted clone: a clone's sources and the tips' array
+static bool seed_clone_tip_ok(const BrushSeedSrc& src, int C, int H, int W) { return seed_clone_ok(src, C, H, W) && src.tips; }
+
 hipError_t launch_brush_seed(const BrushSeedSrc& src, int n, const float* xhat, float* g, int H, int W, hipStream_t s) {
   const int kind = seed_kind(src);
   if (n < 1 || n > 65535 || (kind == SEED_IMM && n != 1) || (kind == SEED_PHOTO && !seed_photo_ok(src, 3, H, W))) return hipErrorInvalidValue;
   if (kind == SEED_CLONE && !seed_clone_ok(src, 3, H, W)) return hipErrorInvalidValue;
   if (kind == SEED_TIP && !seed_tip_ok(src, 3, H, W)) return hipErrorInvalidValue;
+  if (kind == SEED_CLONE_TIP && !seed_clone_tip_ok(src, 3, H, W)) return hipErrorInvalidValue;
   const dim3 grid((3 * H * W + 255) / 256, n);
   if (kind == SEED_IMM) hipLaunchKernelGGL(brush_seed_kernel<SEED_IMM>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_RGB) hipLaunchKernelGGL(brush_seed_kernel<SEED_RGB>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_PHOTO) hipLaunchKernelGGL(brush_seed_kernel<SEED_PHOTO>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_CLONE) hipLaunchKernelGGL(brush_seed_kernel<SEED_CLONE>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else if (kind == SEED_TIP) hipLaunchKernelGGL(brush_seed_kernel<SEED_TIP>, grid, dim3(256), 0, s, src, xhat, g, H, W);
+  else if (kind == SEED_CLONE_TIP) hipLaunchKernelGGL(brush_seed_kernel<SEED_CLONE_TIP>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   else hipLaunchKernelGGL(brush_seed_kernel<SEED_COLOUR>, grid, dim3(256), 0, s, src, xhat, g, H, W);
   return hipGetLastError();
 }
@@ -228,8 +239,12 @@ hipError_t launch_brush_seed_dec_out(const BrushSeedSrc& src, int n, const float
   if (kind == SEED_PHOTO && !seed_photo_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
   if (kind == SEED_CLONE && !seed_clone_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
   if (kind == SEED_TIP && !seed_tip_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
+  if (kind == SEED_CLONE_TIP && !seed_clone_tip_ok(src, Cout, 2 * H, 2 * W)) return hipErrorInvalidValue;
   const dim3 grid((H * W * (Cin >> 2) + 255) / 256, n);
-  if (kind == SEED_TIP)
+  if (kind == SEED_CLONE_TIP)
+    hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_CLONE_TIP>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H,
+                       W, Cin, Cout, act);
+  else if (kind == SEED_TIP)
     hipLaunchKernelGGL(brush_seed_dec_out_kernel<SEED_TIP>, grid, dim3(256), 0, s, src, xhat, out_act, oscale, w, dx, yfwd, scale, H, W,
                        Cin, Cout, act);
   else if (kind == SEED_CLONE)

@@ -8,6 +8,7 @@
 //   session_blend_local_kernel the same in a pool with the local reservation: per-session user mask, brush footprint, dampen
 //   session_local_set_kernel   local edits: a session's UMASK := 0 (every open) and its LOCAL flags (ian_session_local)
 //   session_stroke_umask_kernel  strokes: the footprints of all of a stroke's rectangles max-ed into the session's UMASK
+//   session_tip_umask_kernel   the same for the items that name a brush tip: the tip's own shape in the place of the rectangle
 //   session_fit_begin_kernel / _adam_kernel / _loss_kernel  ian_session_fit: IM := GIM, one Adam step on the latent rows, the loss read-out
 //   session_hires_open_kernel  full-resolution open: the photo at its own size -> SRC, its exact box mean -> GIM, IM, encoder input
 //   canvas_place_kernel        canvases: the exact box mean of a square of a whole photo -> GIM, IM, encoder input (any byte alignment)
@@ -367,7 +368,9 @@ __device__ __forceinline__ void session_blend_body(const SessionBlendArgs& a, do
   if constexpr (LOCAL) {
     const int flags = a.P.local[id];
     l.umask = (flags & 1) ? a.P.umask + (size_t)id * (64 * 64) : nullptr;
-    l.falloff = a.items ? a.falloff : nullptr;
+    // an item with a tip under ian_sessions_set_soft_mask has its tip's footprint in UMASK already (session_tip_umask_kernel): the
+    // rectangle's would swallow it
+    l.falloff = (a.items && !(a.tips && a.tips[i] >= 0)) ? a.falloff : nullptr;
     l.c1 = l.r1 = l.c2 = l.r2 = 0;
     if (a.items) {
       // a rectangle that is empty or not inside the image (the host refuses the latter) adds no footprint: the table has 64 entries
@@ -447,22 +450,18 @@ hipError_t launch_session_local_set(const SessionPool& P, const int* ids, const 
 // pairs of neighbours in a row, one 16-byte load and one 16-byte store each (consecutive lanes, consecutive addresses), and in
 // between the float64 product falloff[dy] * falloff[dx] of photo_blend_image per point and pixel, on gk's distances
 // (PhotoLocalArgs / npe_ops.local_footprint), contraction off.  A stroke without any footprint stores nothing.
-__global__ __launch_bounds__(256) void session_stroke_umask_kernel(SessionPool P, const int* __restrict__ ids, const int* __restrict__ items,
-                                                                   const int* __restrict__ rows, int steps, int first,
-                                                                   const double* __restrict__ falloff) {
-  __shared__ double fall[64];
-  __shared__ int4 rect[STROKE_MAX_POINTS];
-  const int g = first + blockIdx.x;
-  const int id = ids[g];
-  if (!(P.local[id] & 1) || P.mode[id] != 0 || items[(size_t)(rows[0] + g) * 7 + 4] != 1) return;
+// stroke_rects: the fetch, shared with session_tip_umask_kernel.  rows == nullptr: the item's one row g (a brush or clone event).
+// -> whether any rectangle adds a footprint; ends in a barrier, every thread of the workgroup calls it.
+__device__ __forceinline__ int stroke_rects(const int* __restrict__ items, const int* __restrict__ rows, int steps, int g,
+                                            const double* __restrict__ falloff, double* fall, int4* rect) {
   int valid = 0;
   if (threadIdx.x < 64) fall[threadIdx.x] = falloff[threadIdx.x];
   if (threadIdx.x < STROKE_MAX_POINTS) {
     const int k = threadIdx.x;
     int4 r = make_int4(0, 0, 0, 0);
     if (k < steps) {
-      const int r0 = rows[k];
-      if (g < rows[k + 1] - r0) {
+      const int r0 = rows ? rows[k] : 0;
+      if (rows ? g < rows[k + 1] - r0 : k == 0) {
         const int* it = items + (size_t)(r0 + g) * 7;
         const int c1 = it[0], r1 = it[1], c2 = it[2], r2 = it[3];
         if (c1 >= 0 && r1 >= 0 && c2 <= 64 && r2 <= 64 && c1 < c2 && r1 < r2) {
@@ -473,7 +472,18 @@ __global__ __launch_bounds__(256) void session_stroke_umask_kernel(SessionPool P
     }
     rect[k] = r;
   }
-  if (!__syncthreads_or(valid)) return;
+  return __syncthreads_or(valid);
+}
+__global__ __launch_bounds__(256) void session_stroke_umask_kernel(SessionPool P, const int* __restrict__ ids, const int* __restrict__ items,
+                                                                   const int* __restrict__ rows, int steps, int first,
+                                                                   const double* __restrict__ falloff, const int* __restrict__ tips) {
+  __shared__ double fall[64];
+  __shared__ int4 rect[STROKE_MAX_POINTS];
+  const int g = first + blockIdx.x;
+  const int id = ids[g];
+  if (tips && tips[g] >= 0) return;   // session_tip_umask_kernel's
+  if (!(P.local[id] & 1) || P.mode[id] != 0 || items[(size_t)(rows[0] + g) * 7 + 4] != 1) return;
+  if (!stroke_rects(items, rows, steps, g, falloff, fall, rect)) return;
   double2* row = reinterpret_cast<double2*>(P.umask + (size_t)id * (64 * 64));
   for (int j = threadIdx.x; j < 64 * 64 / 2; j += 256) {
     const int y = j >> 5, x = (j & 31) * 2;
@@ -493,11 +503,87 @@ __global__ __launch_bounds__(256) void session_stroke_umask_kernel(SessionPool P
   }
 }
 hipError_t launch_session_stroke_umask(const SessionPool& P, const int* ids, const int* items, const int* rows, int steps, int first,
-                                       const double* falloff, int n, hipStream_t s) {
+                                       const double* falloff, const int* tips, int n, hipStream_t s) {
   if (n < 1 || n > 65535 || first < 0 || steps < 1 || steps > STROKE_MAX_POINTS || !P.umask || !P.local || !P.mode || !ids || !items || !rows ||
       !falloff)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(session_stroke_umask_kernel, dim3(n), dim3(256), 0, s, P, ids, items, rows, steps, first, falloff);
+  hipLaunchKernelGGL(session_stroke_umask_kernel, dim3(n), dim3(256), 0, s, P, ids, items, rows, steps, first, falloff, tips);
+  return hipGetLastError();
+}
+
+// ---- tip-shaped footprints (ian_sessions_set_soft_mask) ----------------------------------------------------------
+// The stroke kernel's work for the items that name a tip: npe_ops.tip_footprint of every rectangle of item g, in the place of the
+// rectangle's footprint, max-ed into the session's UMASK before the item's first step, under the same workgroup-uniform conditions.
+//   R[qy][x] = max_qx s[qy][qx] * t[|x - (c1 + qx)|]      pass one, into LDS: th rows of 64 doubles
+//   F[y][x]  = max_qy t[|y - (r1 + qy)|] * R[qy][x]       pass two, max-ed into the lane's pixels
+// float64, one product each, contraction off; s = the tip's shape wn / max wn, which the host divided (tip_shape_slot).  Every factor
+// is >= 0 and has no NaN, so a maximum may start from 0.  One workgroup per item, its rectangles one after the other: max is exact, so
+// any order and any split would give the same bits.  R does not fit beside the blend's two planes, hence the kernel of its own.
+// Pass one: wave w owns the tip rows w, w + 4, ...; a lane owns column x, so s[qy][qx] is one address for the whole wave.  Pass two and
+// the UMASK traffic are the stroke kernel's: a lane owns 8 pairs of neighbours, one 16-byte load before the first rectangle and one
+// 16-byte store after the last.  The host refused every rectangle whose size is not its tip's, and a tip's slot is 64 x 64 whatever its
+// size: qy * 64 + qx stays inside it for every rectangle inside the image.
+__global__ __launch_bounds__(256) void session_tip_umask_kernel(SessionPool P, const int* __restrict__ ids, const int* __restrict__ items,
+                                                                const int* __restrict__ rows, int steps, int first,
+                                                                const double* __restrict__ falloff, const int* __restrict__ tips,
+                                                                const double* __restrict__ shapes) {
+  __shared__ double fall[64];
+  __shared__ int4 rect[STROKE_MAX_POINTS];
+  __shared__ __attribute__((aligned(16))) double R[64 * 64];   // read as double2 in pass two
+  const int g = first + blockIdx.x;
+  const int id = ids[g];
+  const int tip = tips[g];
+  if (tip < 0) return;   // session_stroke_umask_kernel's, or the blend's
+  if (!(P.local[id] & 1) || P.mode[id] != 0 || items[(size_t)((rows ? rows[0] : 0) + g) * 7 + 4] != 1) return;
+  if (!stroke_rects(items, rows, steps, g, falloff, fall, rect)) return;
+  const double* shape = shapes + (size_t)tip * (64 * 64);
+  double2* row = reinterpret_cast<double2*>(P.umask + (size_t)id * (64 * 64));
+  double2 u[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) u[e] = row[threadIdx.x + e * 256];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  for (int k = 0; k < steps; ++k) {
+    const int4 r = rect[k];   // (c1, r1, c2, r2): the same address for every lane
+    if (r.z <= r.x) continue;
+    const int tw = r.z - r.x, th = r.w - r.y;
+    for (int qy = wave; qy < th; qy += 4) {
+      const double* srow = shape + qy * 64;
+      double m = 0.0;
+      for (int qx = 0; qx < tw; ++qx) {
+        const int d = lane - (r.x + qx);
+        const double v = srow[qx] * fall[d < 0 ? -d : d];
+        m = m < v ? v : m;
+      }
+      R[qy * 64 + lane] = m;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int j = threadIdx.x + e * 256;
+      const int y = j >> 5, x = (j & 31) * 2;
+      double2 f = make_double2(0.0, 0.0);
+      for (int qy = 0; qy < th; ++qy) {
+        const int d = y - (r.y + qy);
+        const double fy = fall[d < 0 ? -d : d];
+        const double2 rr = *reinterpret_cast<const double2*>(R + qy * 64 + x);
+        const double f0 = fy * rr.x, f1 = fy * rr.y;
+        f.x = f.x < f0 ? f0 : f.x;
+        f.y = f.y < f1 ? f1 : f.y;
+      }
+      u[e].x = u[e].x < f.x ? f.x : u[e].x;
+      u[e].y = u[e].y < f.y ? f.y : u[e].y;
+    }
+    __syncthreads();   // R is rewritten by the next rectangle
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) row[threadIdx.x + e * 256] = u[e];
+}
+hipError_t launch_session_tip_umask(const SessionPool& P, const int* ids, const int* items, const int* rows, int steps, int first,
+                                    const double* falloff, const int* tips, const double* shapes, int n, hipStream_t s) {
+  if (n < 1 || n > 65535 || first < 0 || steps < 1 || steps > STROKE_MAX_POINTS || (!rows && steps != 1) || !P.umask || !P.local || !P.mode ||
+      !ids || !items || !falloff || !tips || !shapes)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_tip_umask_kernel, dim3(n), dim3(256), 0, s, P, ids, items, rows, steps, first, falloff, tips, shapes);
   return hipGetLastError();
 }
 

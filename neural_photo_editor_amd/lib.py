@@ -58,6 +58,7 @@ EXPORTS = (
     "ian_session_zoom", "ian_session_brush_zoom", "ian_compose_zoom", "ian_compose_brush_zoom",
     "ian_place_oriented", "ian_placements_oriented",
     "ian_sessions_set_pixels", "ian_sessions_pixels",
+    "ian_session_stamp_soft", "ian_compose_brush_soft", "ian_sessions_set_soft_mask", "ian_sessions_soft_mask",
     "ian_session_tanh_table", "ian_profile_enable", "ian_profile_read", "ian_autotune", "ian_set_option", "ian_box_probe", "ian_last_error", "ian_version", "ian_destroy",
 )
 
@@ -164,6 +165,10 @@ def load_library():
     lib.ian_place_oriented.argtypes = [vp, i32, C.POINTER(CanvasOriented), fp, vp]
     lib.ian_placements_oriented.argtypes = [vp, i32, C.POINTER(CanvasOriented), fp]
     lib.ian_sessions_set_pixels.argtypes = [vp, i32]
+    lib.ian_session_stamp_soft.argtypes = [vp, i32, C.POINTER(SessionCloneEvent), fp, i32, fp, vp]
+    lib.ian_compose_brush_soft.argtypes = [vp, i32, C.POINTER(SessionEvent), fp, fp, i32, C.POINTER(CanvasWindow), i32, i32, fp, vp]
+    lib.ian_sessions_set_soft_mask.argtypes = [vp, i32]
+    lib.ian_sessions_soft_mask.argtypes = [vp, fp]
     lib.ian_sessions_pixels.argtypes = [vp]
     lib.ian_session_tanh_table.argtypes = [fp]
     lib.ian_session_tanh_table.restype = None
@@ -591,6 +596,24 @@ class Handle:
         self._check(self.lib.ian_session_path_tip(self._h, len(strokes), strokes, _ptr(tips), len(boxes), boxes, int(flags),
                                                   _ptr(shown) if shown is not None else C.c_void_p(0), C.c_void_p(stream or 0)))
 
+    def session_clone_tip(self, events, tips, steps=1, shown=None, stream=None):
+        """ian_session_stamp_soft; the arguments of session_clone and tips = int32[n], one per event (-1: no tip)."""
+        tips = np.ascontiguousarray(tips, np.int32)
+        if tips.shape != (len(events),):
+            raise ValueError("tips must hold one index per event (%d), got shape %s" % (len(events), tips.shape))
+        self._check(self.lib.ian_session_stamp_soft(self._h, len(events), events, _ptr(tips), int(steps),
+                                                   _ptr(shown) if shown is not None else C.c_void_p(0), C.c_void_p(stream or 0)))
+
+    def sessions_set_tip_footprint(self, on):
+        """ian_sessions_set_soft_mask; on = 1: a tipped paint event leaves its tip's shape in the user mask, 0: its rectangle's."""
+        self._check(self.lib.ian_sessions_set_soft_mask(self._h, 1 if on else 0))
+
+    def sessions_tip_footprint(self):
+        """ian_sessions_soft_mask -> bool, the setting in force."""
+        on = np.zeros(1, np.int32)
+        self._check(self.lib.ian_sessions_soft_mask(self._h, _ptr(on)))
+        return bool(on[0])
+
     def session_record_info(self):
         """ian_session_record_info -> (the pool's layout as a SessionMeta, the byte offsets of its arrays in a body); host only."""
         layout = SessionMeta()
@@ -648,6 +671,14 @@ class Handle:
         """ian_canvas_brush; events = a ctypes array of SessionEvent, windows = one of CanvasWindow (m = its length), out u8[m,3,vh,vw]."""
         self._check(self.lib.ian_canvas_brush(self._h, len(events), events, _ptr(shown) if shown is not None else C.c_void_p(0),
                                               len(windows), windows, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
+
+    def canvas_brush_tip(self, events, tips, windows, vw, vh, out, shown=None, stream=None):
+        """ian_compose_brush_soft; the arguments of canvas_brush and tips = int32[n], one per event (-1: no tip)."""
+        tips = np.ascontiguousarray(tips, np.int32)
+        if tips.shape != (len(events),):
+            raise ValueError("tips must hold one index per event (%d), got shape %s" % (len(events), tips.shape))
+        self._check(self.lib.ian_compose_brush_soft(self._h, len(events), events, _ptr(tips), _ptr(shown) if shown is not None else C.c_void_p(0),
+                                                  len(windows), windows, int(vw), int(vh), _ptr(out), C.c_void_p(stream or 0)))
 
     def compose_zoom(self, windows, vw, vh, zoom, out, stream=None):
         """ian_compose_zoom: canvas_compose at 1/zoom; vw, vh = the output size, out u8[n,3,vh,vw]."""

@@ -755,6 +755,57 @@ def tip_seed(xhat, box, wn, rgb=None, mode=1):
     return g
 
 
+def clone_tip_seed(xhat, box, wn, target):
+    """The loss seed of one weighted clone event, operation by operation what the seed kernels compute (kernels_brush.hip,
+    SEED_CLONE_TIP) -> float32 (3,H,W): tip_seed's mode 1 with a target image (clone_target of the source) in the place of the colour:
+    inside box = (c1, r1, c2, r2), whose size is wn's, 2.f * (xhat - target) * wn[r - r1][c - c1] (float32: the difference rounded,
+    then each product); zero outside."""
+    xhat = np.asarray(xhat, np.float32)
+    wn = np.asarray(wn, np.float32)
+    target = np.asarray(target, np.float32)
+    c1, r1, c2, r2 = [int(v) for v in box]
+    if xhat.ndim != 3 or wn.shape != (r2 - r1, c2 - c1):
+        raise ValueError("the box (%d,%d,%d,%d) is not the tip's %s" % (c1, r1, c2, r2, wn.shape))
+    if target.shape != xhat.shape:
+        raise ValueError("the target %s is not the image's %s" % (target.shape, xhat.shape))
+    g = np.zeros_like(xhat)
+    d = (xhat[:, r1:r2, c1:c2] - target[:, r1:r2, c1:c2]).astype(np.float32)
+    g[:, r1:r2, c1:c2] = ((np.float32(2) * d).astype(np.float32) * wn[None]).astype(np.float32)
+    return g
+
+
+def tip_footprint(wn, c1, r1, t):
+    """f64[64,64]: the footprint a tip wn [th][tw] placed at (c1, r1) leaves in the user mask (ian_sessions_set_soft_mask): the
+    tip's shape s = float64(wn) / float64(max wn) spread by the falloff table t,
+        R[qy, x] = max_qx s[qy, qx] * t[|x - (c1 + qx)|]        F[y, x] = max_qy t[|y - (r1 + qy)|] * R[qy, x]
+    one float64 division per tip pixel and one float64 product per term.  All zeros for an all-zero tip.  For an all-ones tip it is
+    local_footprint of the rectangle, bit for bit; for any other it is <= that everywhere, and 1.0 where wn has its maximum."""
+    wn = np.asarray(wn)
+    c1, r1 = int(c1), int(r1)
+    if wn.ndim != 2 or not (1 <= wn.shape[0] <= 64 and 1 <= wn.shape[1] <= 64):
+        raise ValueError("a tip has shape (th, tw) with both sides 1..64, got %s" % (wn.shape,))
+    th, tw = wn.shape
+    if not (0 <= c1 and c1 + tw <= 64 and 0 <= r1 and r1 + th <= 64):
+        raise ValueError("a %d x %d tip at (%d,%d) leaves the 64x64 image" % (tw, th, c1, r1))
+    t = np.asarray(t, np.float64)
+    w = wn.astype(np.float64)
+    m = float(w.max())
+    if not m > 0:
+        return np.zeros((64, 64), np.float64)
+    s = w / m
+    j = np.arange(64)
+    tx = t[np.abs(j[None, :] - (c1 + np.arange(tw))[:, None])]       # [qx, x]
+    ty = t[np.abs(j[:, None] - (r1 + np.arange(th))[None, :])]       # [y, qy]
+    R = (s[:, :, None] * tx[None, :, :]).max(axis=1)                 # [qy, x]
+    return (ty[:, :, None] * R[None, :, :]).max(axis=1)              # [y, x]
+
+
+def umask_paint_tip(U, wn, c1, r1, t):
+    """USER_MASK after a tipped paint event under ian_sessions_set_soft_mask: np.maximum(U, tip_footprint(wn, c1, r1, t)).  Exact
+    and idempotent like umask_paint, and the result of several points does not depend on their order."""
+    return np.maximum(np.asarray(U, np.float64), tip_footprint(wn, c1, r1, t))
+
+
 def stroke_footprint(U, boxes, t):
     """USER_MASK after a whole stroke (ian_session_stroke): umask_paint for every rectangle of boxes (K,4), in sequence.  np.maximum is
     exact, so the order of the rectangles does not matter and a rectangle given twice adds nothing."""

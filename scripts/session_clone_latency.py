@@ -18,6 +18,10 @@ Launches and copies per call come from a trace, not from a stopwatch:
   python scripts/session_clone_latency.py --summarize DIR
       splits the kernel trace at its three longest gaps and counts, per call, the dispatches of every phase (the small pageable copies
       of these calls are dispatches of the runtime's copy kernel and are counted as copies) and their device time -> one JSON line
+  python scripts/session_clone_latency.py --tip D [--n 1 64] [--steps 1]
+      the weighted clone instead: D x D clone events through ian_session_clone (plain) against the same events under
+      npe_ops.round_tip(D, 0.5) through ian_session_stamp_soft (tip), alternating within a repeat on one id range
+      -> profiles/session_soft_clone_latency_D<D>.json
 usage (GPU box): python scripts/session_clone_latency.py [--archs IAN_simple IAN] [--n 1 16 64] [--steps 1 8] [--calls 200] [--repeats 3]"""
 import argparse
 import csv
@@ -151,6 +155,54 @@ def measure(a):
             *r["host_min_max"], r["loop_over_clone"], r["host_over_clone"]))
 
 
+def measure_tip(a):
+    """plain clone against the weighted clone of the same D x D rectangles, one pool, the same ids: what the tip costs a clone event."""
+    from neural_photo_editor_amd import npe_ops as N
+    D, rows = a.tip, []
+    for arch in a.archs:
+        m = model(arch)
+        for n in a.n:
+            s = m.sessions(n)
+            s.reserve_tips(1)
+            s.set_tip(0, N.round_tip(D, 0.5))
+            ids = list(range(n))
+            src = [ids[(i + 1) % n] for i in range(n)]
+            s.open(ids, photos(n, 100 + n))
+            rs = np.random.RandomState(n)
+            c1, r1 = rs.randint(0, 65 - D, n), rs.randint(0, 65 - D, n)
+            boxes = np.stack([c1, r1, c1 + D, r1 + D], axis=1)
+            offs = np.stack([rs.randint(0, 65 - D, n) - c1, rs.randint(0, 65 - D, n) - r1], axis=1)
+            for K in a.steps:
+                def call(tips):
+                    t0 = time.perf_counter()
+                    s.clone(ids, boxes, src, offs, "GIM", steps=K, weight=WEIGHT, tips=tips)
+                    return (time.perf_counter() - t0) * 1e3
+                for _ in range(5):
+                    call(None), call(0)
+                reps = {"plain": [], "tip": []}
+                for _ in range(a.repeats):
+                    s.open(ids, photos(n, 100 + n))
+                    t = {"plain": [], "tip": []}
+                    for _ in range(a.calls):
+                        t["tip"].append(call(0))
+                        t["plain"].append(call(None))
+                    for p in t:
+                        reps[p].append(float(np.median(t[p])))
+                row = {"arch": arch, "n": n, "steps": K, "D": D}
+                for p in reps:
+                    row[p + "_ms"] = round(float(np.median(reps[p])), 4)
+                    row[p + "_min_max"] = [round(min(reps[p]), 4), round(max(reps[p]), 4)]
+                row["tip_over_plain"] = round(row["tip_ms"] / row["plain_ms"], 4)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            s.close()
+        m.close()
+    res = {"metric": "session_soft_clone_latency", "calls": a.calls, "repeats": a.repeats, "D": D, "rows": rows}
+    with open(os.path.join(ROOT, "profiles", "session_soft_clone_latency_D%d.json" % D), "w") as fh:
+        fh.write(json.dumps(res) + "\n")
+    print(json.dumps(res))
+
+
 def trace(arch, n, K):
     m = model(arch)
     c = Case(m, n)
@@ -196,11 +248,14 @@ def main():
     ap.add_argument("--steps", type=int, nargs="*", default=[1, 8])
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--tip", type=int, default=0, metavar="D", help="the weighted clone: D x D plain clone events against the same under round_tip(D, 0.5)")
     ap.add_argument("--trace", nargs=3, metavar=("ARCH", "N", "K"))
     ap.add_argument("--summarize", metavar="DIR")
     a = ap.parse_args()
     if a.summarize:
         summarize(a.summarize)
+    elif a.tip:
+        measure_tip(a)
     elif a.trace:
         trace(a.trace[0], int(a.trace[1]), int(a.trace[2]))
     else:

@@ -2,7 +2,7 @@
 ids: state in HBM, 11 words up per event, 12 KB down) and of IAN.brush_step_batch with host pointers and photo= (per item a 48 KB
 colour image, RECON, ERROR and the latent compared against their shadows, z_new and IM down), in one process, on both configs.
 usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 16 64] [--calls 200] [--repeats 3] [--out FILE] [--local]
-                                                    [--history] [--tip D]
+                                                    [--history] [--tip D [--local [--footprint]]]
   --local: the same event stream on a pool with the local reservation and flags 3 (user mask + dampen) on every session: per item
            the blend also reads, max-es and writes the session's 32 KB UMASK.  Compare against a run without --local in the same
            process order on the same build.
@@ -16,6 +16,11 @@ usage (GPU box): python scripts/session_latency.py [--only IAN_simple] [--n 1 4 
            tip        the same events with npe_ops.round_tip(D, 0.5) through ian_session_brush_tip
            alternating within a repeat; n defaults to 1 16 64, --out to profiles/session_tip_latency.json.  With --trace: both, one after
            the other, for a kernel trace (the two seed kernels are different instantiations and show as two rows).
+           With --local the pool has the local reservation and LOCAL bit 0 on every session (the blend max-es the event's footprint into
+           UMASK); with --footprint as well two more paths: tip_footprint, the tip events under
+           EditSessions.tip_footprint(True), whose footprint is session_tip_umask_kernel's, and a stroke of 64 points with the tip per
+           session, setting off and on (stroke_tip, stroke_tip_footprint; a tenth of --calls).  --out defaults to
+           profiles/session_soft_mask_latency_D<D>.json then.
   --trace: only the first --n on the first config, sessions only: warm-up, an idle second, then --calls timed calls (for a
            rocprofv3 --kernel-trace --stats run).
 Per (config, n, path): the median over --calls calls after warm-up, repeated --repeats times (the two paths alternate within a
@@ -166,22 +171,38 @@ def tip_pool(arch, cap, D):
     return m, s
 
 
-def run_tip(arch, ns, calls, repeats, D):
+def run_tip(arch, ns, calls, repeats, D, local=False, footprint=False):
     m, s = tip_pool(arch, max(ns), D)
+    if local:
+        s.reserve_local()
     rows = []
     for n in ns:
         ids, boxes, levels = np.arange(n), tip_boxes(n, D), (255, 0, 0)
         s.open(ids, np.random.RandomState(n).randint(0, 256, (n, 3, 64, 64)).astype(np.uint8))
+        if local:
+            s.set_local(ids, flags=1)
+        paths = [tip_boxes(64, D, seed=100 + i) for i in range(n)]          # a drag of 64 points per session
 
         def rectangle():
             s.paint(ids, boxes, levels)
 
         def tip():
             s.paint(ids, boxes, levels, tips=0)
+
+        def stroke_tip():
+            s.stroke(ids, paths, levels, None, 0.01, -1.0, tips=0)
         res = {"rectangle": [], "tip": []}
+        if footprint:
+            res.update({"tip_footprint": [], "stroke_tip": [], "stroke_tip_footprint": []})
         for _ in range(repeats):
             res["rectangle"].append(median_ms(rectangle, calls))
             res["tip"].append(median_ms(tip, calls))
+            if footprint:                                                      # the setting synchronises: switched outside the timed calls
+                res["stroke_tip"].append(median_ms(stroke_tip, max(calls // 10, 3), warmup=2))
+                s.tip_footprint(True)
+                res["tip_footprint"].append(median_ms(tip, calls))
+                res["stroke_tip_footprint"].append(median_ms(stroke_tip, max(calls // 10, 3), warmup=2))
+                s.tip_footprint(False)
         row = {"n": n, "D": D}
         for k, v in res.items():
             med = float(np.median(v))
@@ -189,6 +210,9 @@ def run_tip(arch, ns, calls, repeats, D):
                       "repeats_ms": [round(t, 4) for t in v]}
         row["tip_over_rectangle"] = round(row["tip"]["p50_ms"] / row["rectangle"]["p50_ms"], 4)
         row["tip_inside_rectangle_repeats"] = bool(min(res["rectangle"]) <= row["tip"]["p50_ms"] <= max(res["rectangle"]))
+        if footprint:
+            row["footprint_over_tip"] = round(row["tip_footprint"]["p50_ms"] / row["tip"]["p50_ms"], 4)
+            row["stroke_footprint_over_stroke"] = round(row["stroke_tip_footprint"]["p50_ms"] / row["stroke_tip"]["p50_ms"], 4)
         rows.append(row)
     m.close()
     return rows
@@ -236,22 +260,27 @@ def main():
     ap.add_argument("--local", action="store_true", help="local reservation, flags 3 (user mask + dampen) on every session")
     ap.add_argument("--history", action="store_true", help="undo history: mark + paint + undo, undo alone, set_latent, paint with an unused history")
     ap.add_argument("--tip", type=int, default=0, metavar="D", help="brush tips: D x D rectangle events against the same events with round_tip(D, 0.5)")
+    ap.add_argument("--footprint", action="store_true", help="with --tip D --local: also the tip events and a 64-point stroke under tip_footprint(True)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     archs = [a.only] if a.only else ["IAN_simple", "IAN"]
     if a.tip and not 1 <= a.tip <= 64:
         ap.error("--tip D: a tip has 1..64 pixels a side")
+    if a.footprint and not (a.tip and a.local):
+        ap.error("--footprint goes with --tip D --local")
     if a.n is None:
         a.n = [1, 16, 64] if a.tip else [1, 4, 16, 64]
     if a.tip and a.trace:
         print(json.dumps(trace_tip(archs[0], a.n[0], a.calls, a.tip)))
         return
     if a.tip:
-        res = {"metric": "session_tip_latency", "calls": a.calls, "repeats": a.repeats, "D": a.tip}
+        res = {"metric": "session_soft_mask_latency" if a.footprint else "session_tip_latency", "calls": a.calls, "repeats": a.repeats, "D": a.tip,
+               "local": bool(a.local)}
         for arch in archs:
-            res[arch] = run_tip(arch, a.n, a.calls, a.repeats, a.tip)
+            res[arch] = run_tip(arch, a.n, a.calls, a.repeats, a.tip, a.local, a.footprint)
         print(json.dumps(res))
-        with open(a.out or os.path.join(ROOT, "profiles", "session_tip_latency.json"), "w") as fh:
+        default = ("session_soft_mask_latency_D%d.json" % a.tip) if a.footprint else "session_tip_latency.json"
+        with open(a.out or os.path.join(ROOT, "profiles", default), "w") as fh:
             json.dump(res, fh, indent=1)
             fh.write("\n")
         return
